@@ -19,19 +19,28 @@ sigmoid + the per-scan metric sums (written to a row of a device table).  It run
 Everything that is not steady state (arena, weight upload, one forward per context) happens in ScanEngine.prepare()
 before the timed region, whatever --warmup is; short runs use fewer streams (about three timed steps per stream).
 `value` is measured with every step's [N,6] batch copied from a pinned HOST buffer to the device inside the timed region
-("H2D of the input included"); the same steps with the inputs already resident in HBM are timed first and
-reported next to it (`resident_inputs`).
+("H2D of the input included").  `ms_per_step` = wall time of the timed region / --steps.
 
 Scans are sharded data-parallel (each rank owns its scans; weak scaling); the only exchange is one RCCL all-gather of
 the per-scan metric rows at the end of the sequence, inside the timed region.
 
-Prints ONE JSON line on rank 0, including
+Prints ONE JSON line on rank 0.  A plain run does only what the headline needs: set-up, warm-up (the K + W steps below
+with resident inputs, then --warmup host-fed steps), the --steps timed steps, the outputs (--dump-outputs) and the line.
+`--full` adds:
+  "resident_inputs": the rate of those resident-input steps (run before the headline's region in either mode);
   "roofline":     whole-path algorithmic bytes / GPU time per step (hipEvents on the launch streams
                   over the timed region) against the 8 TB/s HBM peak, the per-layer breakdown (hipEvents around every
                   kernel stage, serial pass) and the dominant kernel with its own roofline fractions;
   "cpu_baseline": the C restatement of the MinkowskiEngine algorithm (oracle/, kind "port") timed on this box's host
                   cores on a bounded sample of the same workload (rank 0, N = 1 only);
-  "parity":       scores / labels / dIoU of the measured path against that oracle on the same input and weights.
+  "parity":       scores / labels / dIoU of the measured path against that oracle on the same input and weights;
+  "mean_metrics" / "mean_confusion": per-scan metrics of the timed steps, averaged.
+Without --full those keys are null.
+
+--dump-outputs DIR writes what the headline's last timed step returned to its caller (rank 0): DIR/scores.npy (float32 [rows],
+one score per input row) and DIR/metric_sums.npy (float64 [scans of the step x ranks, 8]: the per-scan metric sums of that
+step).  Inputs (seeded synthetic scans and weights, the `final` bias calibrated on the device) are the same in every run
+with the same arguments, so two builds can be compared output for output.
 """
 from __future__ import annotations
 
@@ -146,6 +155,25 @@ def csrc_sha():
     return h.hexdigest()[:16]
 
 
+DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(d, arrays):
+    """name -> array as DIR/<name>.npy (float32 / float64).  An array that would take the files past DUMP_BYTES is
+    replaced by a fixed, seeded sample of its rows (sorted indices, DIR/<name>_rows.npy names them)."""
+    os.makedirs(d, exist_ok=True)
+    budget = DUMP_BYTES
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a)
+        if a.nbytes > budget // 2:
+            row = a.nbytes // max(len(a), 1)
+            keep = np.sort(np.random.default_rng(0).choice(len(a), size=(budget // 4) // max(row, 1), replace=False))
+            np.save(os.path.join(d, f"{name}_rows.npy"), keep.astype(np.float64))
+            a = a[keep]
+        np.save(os.path.join(d, f"{name}.npy"), a)
+        budget -= a.nbytes
+
+
 def build_workload(config, rank, azimuth, seq_scans, vs, scenes=4):
     """Returns (list of [N,6] float32 numpy batches that the steps cycle through, n_batches per step, description)."""
     from sps_amd import synthetic
@@ -194,10 +222,13 @@ def main():
                     "exercising the multi-rank control flow on a single GPU)")
     ap.add_argument("--force-dist", action="store_true", help="initialise the process group and run the metric all-gather even at "
                     "world size 1 (under torchrun --nproc-per-node 1): executes the RCCL path on a single-GPU box")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="besides the headline: the resident-input timed region, the roofline "
+                    "(probe forward + per-layer hipEvent pass), the CPU baseline + parity against the oracle, per-scan metric means")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's scores and metric sums to DIR/*.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline and parity")
     ap.add_argument("--no-h2d", action="store_true", help="skip the host-buffer-fed timed region: `value` is then the "
                     "resident-input rate (diagnostic runs; the headline includes the copy, SURVEY 8(d))")
-    ap.add_argument("--no-stages", action="store_true", help="skip the per-layer hipEvent pass")
+    ap.add_argument("--no-stages", action="store_true", help="--full without the per-layer hipEvent pass")
     ap.add_argument("--cpu-seconds", type=float, default=8.0, help="target wall time of the CPU baseline sample")
     ap.add_argument("--order", default="scan", choices=["scan", "morton"],
                     help="DIAGNOSTIC: row order of the synthetic batches -- 'scan' = as a LiDAR delivers them (ring by ring; "
@@ -319,20 +350,22 @@ def main():
         return float(el.item()), gpu_ms, gathered, scores
 
     # Headline ("H2D of the input included"): every step's [N,6] batch is copied from a pinned host buffer to the
-    # device on the step's stream INSIDE the timed region.  The same K steps with the inputs already resident in HBM
-    # are measured next to it (`resident_inputs`).
+    # device on the step's stream INSIDE the timed region.  The same K steps with the inputs already resident in HBM run
+    # first; --full reports them (`resident_inputs`).  A plain run keeps them as warm-up so that the headline region follows
+    # the same GPU work in both modes (measured without them: 20-step headline 3-5 % lower, 400 steps unchanged).
+    resident = None
     res_el, res_gpu, res_gathered, res_scores = timed_region(batches)
-    res_issue_ms = issue_s[0] / K * 1e3
-    resident = {"value": round(K * nb * world / res_el, 2), "unit": "scans/s", "ms_per_step": round(res_el / K * 1e3, 4),
-                "gpu_ms_per_step": round(res_gpu / K, 4), "host_issue_ms_per_step": round(res_issue_ms, 4),
-                "note": "same K steps, inputs already resident in HBM when the timed region starts"}
+    if args.full or args.no_h2d:
+        res_issue_ms = issue_s[0] / K * 1e3
+        resident = {"value": round(K * nb * world / res_el, 2), "unit": "scans/s", "ms_per_step": round(res_el / K * 1e3, 4),
+                    "gpu_ms_per_step": round(res_gpu / K, 4), "host_issue_ms_per_step": round(res_issue_ms, 4),
+                    "note": "same K steps, inputs already resident in HBM when the timed region starts"}
     if args.no_h2d:
         elapsed, gpu_ms, gathered, scores, inputs = res_el, res_gpu, res_gathered, res_scores, "resident in HBM (--no-h2d: diagnostic)"
     else:
         elapsed, gpu_ms, gathered, scores = timed_region(pinned)
         inputs = "pinned host buffer -> device copy of every step's [N,6] batch inside the timed region"
     host_issue_ms = issue_s[0] / K * 1e3
-    rows_resident = (torch.cat(gathered, 0) if gathered is not None else eng.table[: K * nb]).cpu().numpy().copy()
     h2d = {"value": round(K * nb * world / elapsed, 2), "unit": "scans/s", "ms_per_step": round(elapsed / K * 1e3, 4),
            "gpu_ms_per_step": round(gpu_ms / K, 4), "bytes_per_step": int(batches_np[0].nbytes),
            "note": "= the headline `value`"} if not args.no_h2d else None
@@ -348,6 +381,46 @@ def main():
     # ---- whole-job numbers ------------------------------------------------------------------
     total_scans = K * nb * world
     value = total_scans / elapsed
+    tables = gathered if gathered is not None else [eng.table[: K * nb]]      # one metric table per rank, K * nb rows each
+    if args.dump_outputs:
+        # the headline's last timed step as its caller receives it: the scores of its rows (this rank) and the metric sums
+        # of its scans (every rank)
+        dump_outputs(args.dump_outputs, {
+            "scores": scores.float().cpu().numpy(),
+            "metric_sums": torch.cat([t[(K - 1) * nb: K * nb] for t in tables], 0).double().cpu().numpy()})
+        wall["dump_outputs"] = round(time.perf_counter() - t_phase, 2)
+        t_phase = time.perf_counter()
+    line = {
+        "metric": "scans/sec @100k pts, 0.1 m voxel", "value": round(value, 2), "unit": "scans/s",
+        "n_gpus": world, "steps": K, "warmup": W, "ms_per_step": round(elapsed / K * 1e3, 4),
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+        "config": {"workload": workload, "baseline_config": args.config, "scans_per_step": nb,
+                   "scan_points": n_scan, "rows": n_points, "sharding": f"dp{world}",
+                   "streams_per_gpu": S, "final_bias_calibrated": float(bias.item()),
+                   "arena_mb_per_context": round(eng.ctxs[-1].arena_bytes() / 2**20, 1),
+                   "arena_mb_all_contexts": round(sum(cx.arena_bytes() for cx in eng.ctxs) / 2**20, 1),
+                   "compact_arenas": eng.compact},
+        "roofline": None, "cpu_baseline": None, "parity": None, "mean_metrics": None,
+        "mean_confusion": None, "inputs": inputs, "resident_inputs": resident, "h2d_inclusive": h2d,
+        "resident_value": resident["value"] if resident else None,
+        "dist_backend": (dist.get_backend() if dist is not None else None), "dist_world_size": (dist.get_world_size() if dist is not None else 1),
+        "host_cores": os.cpu_count(), "host_placement": placement,
+        "host_issue_ms_per_step": round(host_issue_ms, 4), "wall_s": wall,
+    }
+
+    def emit():
+        wall["main_total"] = round(time.perf_counter() - t_main, 2)
+        wall["imports_before_main"] = round(t_main - T_IMPORT0, 2)
+        print(json.dumps(line))
+        if dist is not None:
+            dist.barrier()
+            dist.destroy_process_group()
+
+    if not args.full:
+        emit()
+        return
+
+    rows_resident = torch.cat(tables, 0).cpu().numpy().copy()
     per_scan = [metrics_from_sums(r) for r in rows_resident]
     mean_metrics = {k: float(np.mean([m[k] for m in per_scan])) for k in ("loss", "r2", "dIoU", "precision", "recall", "f1")}
     confusion = {k: float(np.mean([m[k] for m in per_scan])) for k in ("tp", "fp", "fn", "tn")}
@@ -549,30 +622,9 @@ def main():
                   "confusion_TP_FP_FN_TN_gpu": conf_gpu, "confusion_TP_FP_FN_TN_oracle": conf_ref}
 
     wall["cpu_baseline_and_parity"] = round(time.perf_counter() - t_phase, 2)
-    wall["main_total"] = round(time.perf_counter() - t_main, 2)
-    wall["imports_before_main"] = round(t_main - T_IMPORT0, 2)
-    out = {
-        "metric": "scans/sec @100k pts, 0.1 m voxel", "value": round(value, 2), "unit": "scans/s",
-        "n_gpus": world, "steps": K, "warmup": W, "ms_per_step": round(elapsed / K * 1e3, 4),
-        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-        "config": {"workload": workload, "baseline_config": args.config, "scans_per_step": nb,
-                   "scan_points": n_scan, "rows": n_points, "voxels_per_level": V,
-                   "pairs_3x3x3x3_per_level": pairs3, "pairs_5x5x5x1": pairs5, "sharding": f"dp{world}",
-                   "streams_per_gpu": S, "final_bias_calibrated": float(bias.item()),
-                   "arena_mb_per_context": round(eng.ctxs[-1].arena_bytes() / 2**20, 1),
-                   "arena_mb_all_contexts": round(sum(cx.arena_bytes() for cx in eng.ctxs) / 2**20, 1),
-                   "compact_arenas": eng.compact},
-        "roofline": roof, "cpu_baseline": cpu, "parity": parity, "mean_metrics": mean_metrics,
-        "mean_confusion": confusion, "inputs": inputs, "resident_inputs": resident, "h2d_inclusive": h2d,
-        "resident_value": resident["value"],
-        "dist_backend": (dist.get_backend() if dist is not None else None), "dist_world_size": (dist.get_world_size() if dist is not None else 1),
-        "host_cores": os.cpu_count(), "host_placement": placement,
-        "host_issue_ms_per_step": round(host_issue_ms, 4), "wall_s": wall,
-    }
-    print(json.dumps(out))
-    if dist is not None:
-        dist.barrier()
-        dist.destroy_process_group()
+    line["config"].update(voxels_per_level=V, pairs_3x3x3x3_per_level=pairs3, pairs_5x5x5x1=pairs5)
+    line.update(roofline=roof, cpu_baseline=cpu, parity=parity, mean_metrics=mean_metrics, mean_confusion=confusion)
+    emit()
 
 
 if __name__ == "__main__":

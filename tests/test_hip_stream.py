@@ -205,7 +205,7 @@ def test_bench_two_ranks_on_one_gpu_gloo():
     process never hands its GPU state to them."""
     r = _run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
               "--master-port", "29531", "bench.py", "--gpus", "2", "--backend", "gloo", "--steps", "12", "--warmup", "3",
-              "--azimuth", "500", "--streams", "3", "--no-cpu-baseline", "--no-stages"])
+              "--azimuth", "500", "--streams", "3", "--full", "--no-cpu-baseline", "--no-stages"])
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:]
@@ -222,7 +222,7 @@ def test_bench_driver_protocol_is_steady_state():
     short run stays close to a longer one (pipeline fill/drain is all that separates them)."""
     out = {}
     for k, w in ((20, 5), (200, 20)):
-        r = _run([sys.executable, "bench.py", "--steps", str(k), "--warmup", str(w), "--no-cpu-baseline", "--no-stages",
+        r = _run([sys.executable, "bench.py", "--steps", str(k), "--warmup", str(w), "--full", "--no-cpu-baseline", "--no-stages",
                   "--no-h2d"])
         assert r.returncode == 0, r.stderr[-3000:]
         out[k] = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
@@ -230,6 +230,50 @@ def test_bench_driver_protocol_is_steady_state():
     assert out[200]["config"]["streams_per_gpu"] == 8 and out[200]["config"]["arena_mb_all_contexts"] < 3072
     assert out[20]["value"] > 0.75 * out[200]["value"], (out[20]["value"], out[200]["value"])
     assert out[20]["mean_metrics"]["dIoU"] > 0
+
+
+@pytest.mark.timeout(900)
+def test_bench_plain_run_is_the_headline_and_dumps_its_outputs(tmp_path):
+    """A plain run (no --full) times exactly --steps steps and measures nothing else; --dump-outputs writes the last timed
+    step's scores and metric sums, identical in two runs with the same arguments and equal to the oracle's scores."""
+    dumps = []
+    for i in range(2):
+        d = tmp_path / f"run{i}"
+        r = _run([sys.executable, "bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2", "--azimuth", "500",
+                  "--dump-outputs", str(d)])
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1, r.stdout[-2000:]
+        line = json.loads(lines[0])
+        assert line["steps"] == 7 and line["warmup"] == 2 and line["unit"] == "scans/s" and line["higher_is_better"] is True
+        assert line["dtype"] == "f32" and line["value"] == pytest.approx(7 / (line["ms_per_step"] * 7e-3), rel=1e-3)
+        assert line["h2d_inclusive"]["ms_per_step"] == line["ms_per_step"]
+        for k in ("roofline", "cpu_baseline", "parity", "mean_metrics", "resident_inputs", "resident_value"):
+            assert line[k] is None, k
+        scores, sums = np.load(d / "scores.npy"), np.load(d / "metric_sums.npy")
+        assert scores.dtype == np.float32 and scores.ndim == 1
+        assert sums.dtype == np.float64 and sums.shape == (1, 8)
+        assert sums[0, 1:5].sum() == sums[0, 0] > 0                          # count = TP + FP + FN + TN
+        dumps.append((line, scores, sums))
+    (l0, s0, m0), (l1, s1, m1) = dumps
+    assert l0["config"]["final_bias_calibrated"] == l1["config"]["final_bias_calibrated"]
+    np.testing.assert_array_equal(s0, s1)
+    _same_sums(m0, m1)
+    # the same step through the oracle: the synthetic scan of the last timed step, the benchmark's weights
+    import bench
+    from sps_amd.models.models import SPSNet
+    batches, _, _ = bench.build_workload(2, 0, 500, 32, 0.1)
+    with torch.random.fork_rng(devices=[]):
+        torch.manual_seed(0)                                                 # as bench.py seeds before SPSNet()
+        net = bench.synthetic_weights(SPSNet(bench.CFG), seed=0)
+    sd = net.state_dict()
+    sd[bench.KEY_W].mul_(8.0)
+    sd[bench.KEY_B].fill_(l0["config"]["final_bias_calibrated"])
+    params = {k.replace("model.MinkUNet.", ""): v.detach().cpu().numpy() for k, v in sd.items() if "num_batches_tracked" not in k}
+    last = batches[(7 - 1) % len(batches)]
+    assert s0.shape == (len(last),) and m0[0, 0] == (last[:, 4] == 1).sum()    # one score per row; the step's scan points
+    ref, _ = O.sps_forward(params, last[:, :5], 0.1)
+    assert float(np.max(np.abs(s0 - ref))) < 1e-3
 
 
 @pytest.mark.timeout(900)
@@ -453,7 +497,7 @@ def test_rccl_path_runs_at_world_size_one():
     processes that touch the GPU only after the launcher has started them."""
     base = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1"]
     r = _run(base + ["--master-port", "29541", "bench.py", "--gpus", "1", "--force-dist", "--steps", "12", "--warmup", "3",
-                     "--azimuth", "500", "--streams", "3", "--no-cpu-baseline", "--no-stages"])
+                     "--azimuth", "500", "--streams", "3", "--full", "--no-cpu-baseline", "--no-stages"])
     assert r.returncode == 0, r.stderr[-3000:]
     d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     assert d["n_gpus"] == 1 and d["value"] > 0 and d["mean_metrics"]["dIoU"] > 0

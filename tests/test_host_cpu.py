@@ -384,3 +384,21 @@ def test_predict_cli_help_lists_the_reference_options_and_backend():
     assert r.returncode == 0, r.stderr[-2000:]
     for opt in ("--weights", "-w", "--sequence", "-seq", "--config", "-c", "--backend", "--batch-size"):
         assert opt in r.stdout, opt
+
+
+def test_bench_dump_outputs_keeps_small_arrays_and_samples_large_ones(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: arrays within the size cap are written whole with their dtype; one that would pass it is
+    replaced by the same seeded sample of rows in every run, the row indices written beside it."""
+    import bench
+    monkeypatch.setattr(bench, "DUMP_BYTES", 4096)
+    small = np.arange(8, dtype=np.float64).reshape(1, 8)
+    big = np.linspace(0, 1, 3000, dtype=np.float32)
+    for d in (tmp_path / "a", tmp_path / "b"):
+        bench.dump_outputs(str(d), {"small": small, "big": big})
+    a, b = np.load(tmp_path / "a" / "big.npy"), np.load(tmp_path / "b" / "big.npy")
+    rows = np.load(tmp_path / "a" / "big_rows.npy")
+    assert a.dtype == np.float32 and 0 < a.nbytes <= 4096 and np.array_equal(a, b)
+    assert np.array_equal(a, big[rows.astype(np.int64)]) and np.all(np.diff(rows) > 0)
+    np.testing.assert_array_equal(np.load(tmp_path / "a" / "small.npy"), small)
+    assert not (tmp_path / "a" / "small_rows.npy").exists()
+    assert sum(os.path.getsize(p) for p in (tmp_path / "a").iterdir()) < 4096 + 4 * 128

@@ -1,7 +1,7 @@
 #!/bin/bash
 # A/B on ONE box: bench.py for every tools/ab/lib_<tag>.so given, alternating, <reps> times.
 # usage (GPU box): bash tools/ab_bench.sh <reps> "<bench args>" tagA tagB ...   -> gpurun_out/ab_<tag>_<rep>.json, summary on stdout
-reps=$1; args=$2; shift 2
+reps=$1; args="--full $2"; shift 2
 mkdir -p gpurun_out
 for r in $(seq 1 $reps); do
   for t in "$@"; do

@@ -8,6 +8,6 @@ export SPS_LIB=tools/ab/lib_$tag.so
 for r in 1 2 3; do
 for v in "$@"; do
   pad=${v%%:*}; mask=31; [[ "$v" == *:* ]] && mask=${v#*:}
-  SPS_FE_LDS_PAD=$pad SPS_FE_LDS_MASK=$mask python3 bench.py --steps 300 --warmup 30 --no-cpu-baseline --no-stages 2>/dev/null | python3 -c "
+  SPS_FE_LDS_PAD=$pad SPS_FE_LDS_MASK=$mask python3 bench.py --steps 300 --warmup 30 --full --no-cpu-baseline --no-stages 2>/dev/null | python3 -c "
 import sys, json; d = json.loads([l for l in sys.stdin if l.startswith('{')][-1]); print('pad $pad mask $mask rep $r: value', d['value'], 'resident', d['resident_value'])"
 done; done
