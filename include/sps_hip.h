@@ -354,6 +354,47 @@ int sps_get_logits(sps_ctx *ctx, float *logits_dev);
  * f32 (compact, ld = C) into out_dev; *rows,*cols describe it. */
 int sps_get_feature(sps_ctx *ctx, const char *name, float *out_dev, int64_t *rows, int64_t *cols);
 
+
+/* ---- LTS baseline (SPCTReg offset-attention regressor) ------------------------------------------------------------
+ * The reference's third learned baseline, c_ws/src/inference_model/lts_filter/scripts/:
+ *   sps_lts_project : Loader.lidar_to_image + __getitem__ (loader.py:36-59, :62-72): range-image projection of a cloud
+ *                     and its split into windows of N = beams x window_size cells;
+ *   sps_lts_forward : SPCTReg.forward (transformer.py:97-138) in f32, BatchNorm in eval mode (folded at create),
+ *                     dropout = identity; the N x N attention of each OA block (transformer.py:51-67) is never stored;
+ *   the node's metrics and epsilon filter (stability_filter.py:160-193) reuse sps_metrics_dev / sps_compact_stable on
+ *   the metric rows sps_lts_project writes.
+ * Weight blob: the reference state_dict, every key in its order (sps_lts_tensor_info), num_batches_tracked as one float.
+ * q_conv.weight and k_conv.weight are one Parameter in the reference: the k_conv entry is used (it is loaded second).
+ * No function here synchronises except sps_lts_check.  A handle is not thread-safe; its workspace is reused by every
+ * forward (one forward in flight per handle). */
+typedef struct sps_lts sps_lts;
+#define SPS_LTS_VLP16 0 /* 16 beams, fov +-16.8 deg, window 128 -> 8 windows of N = 2048 */
+#define SPS_LTS_HDL32 1 /* 32 beams, fov +30 / -10 deg, window 64 -> 16 windows of N = 2048 */
+int sps_lts_num_tensors(void);
+/* name, offset / numel in floats, shape[3] (unused dims 0), ndim (0 for a scalar) of blob tensor idx; any out may be NULL */
+int sps_lts_tensor_info(int idx, char *name, int name_cap, int64_t *offset, int64_t *numel, int64_t *shape, int *ndim);
+int64_t sps_lts_numel(void);
+int sps_lts_lidar_info(int lidar, int *beams, int *window, int *num_windows);
+/* blob_host: sps_lts_numel() floats on the host, or NULL for a projection-only handle.  Synchronises (uploads the
+ * folded weights). */
+int sps_lts_create(int device, const float *blob_host, int64_t numel, sps_lts **out);
+int sps_lts_destroy(sps_lts *h);
+/* pts_dev: n rows (x, y, z, s, ...) f32 with row stride ld >= 4; rows with s == -1 are dropped; per cell the
+ * lexicographically largest (x, y, z, s) row is kept (np.unique + last write wins; -0.0 == +0.0).
+ * frame_dev [beams][1024][4] (required); x_dev [num_windows][3][N] (the network input, may be NULL);
+ * rows_dev [num_windows * N][6] = (0, x, y, z, 1, s) per cell, empty cells (0, 0, 0, 0, 1, 0) (sps_metrics_dev /
+ * sps_compact_stable input, may be NULL).  A row whose elevation index is outside [-beams, beams) or with a NaN coordinate
+ * (IndexError in the reference) sets the handle's sticky status, reported by sps_lts_check. */
+int sps_lts_project(sps_lts *h, const float *pts_dev, int64_t ld, int64_t n, int lidar, float *frame_dev, float *x_dev,
+                    float *rows_dev, void *stream);
+/* x_dev [B][3][N] f32 (torch layout of the reference's input), scores_dev [B][N] = sigmoid output; any B >= 1, N >= 1. */
+int sps_lts_forward(sps_lts *h, const float *x_dev, int64_t B, int64_t N, float *scores_dev, void *stream);
+/* Synchronises `stream`; SPS_ERR_RANGE if a projection since the last check met an out-of-image or NaN point (then clears). */
+int sps_lts_check(sps_lts *h, void *stream);
+/* Intermediate of the last forward: which = 0 embedding, 1..4 outputs of sa1..sa4 (f32 [B*N][128], point-major),
+ * 5 / 6 linear1's max / mean over the points of each window (f32 [B][2048]).  out_dev NULL: *rows, *cols only. */
+int sps_lts_tap(sps_lts *h, int which, float *out_dev, int64_t *rows, int64_t *cols, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -23,7 +23,7 @@ class SpsError(RuntimeError):
         self.code = code
 
 
-ABI_VERSION = 201          # sps_version() of the library this binding was written against
+ABI_VERSION = 202          # sps_version() of the library this binding was written against
 
 
 def _load() -> C.CDLL:
@@ -108,6 +108,16 @@ def _load() -> C.CDLL:
         "sps_get_kernel_map": (i32, [vp, i32, i32, vp, C.POINTER(i64)]),
         "sps_get_logits": (i32, [vp, vp]),
         "sps_get_feature": (i32, [vp, C.c_char_p, vp, C.POINTER(i64), C.POINTER(i64)]),
+        "sps_lts_num_tensors": (i32, []),
+        "sps_lts_tensor_info": (i32, [i32, C.c_char_p, i32, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64), C.POINTER(i32)]),
+        "sps_lts_numel": (i64, []),
+        "sps_lts_lidar_info": (i32, [i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]),
+        "sps_lts_create": (i32, [i32, vp, i64, C.POINTER(vp)]),
+        "sps_lts_destroy": (i32, [vp]),
+        "sps_lts_project": (i32, [vp, vp, i64, i64, i32, vp, vp, vp, vp]),
+        "sps_lts_forward": (i32, [vp, vp, i64, i64, vp, vp]),
+        "sps_lts_check": (i32, [vp, vp]),
+        "sps_lts_tap": (i32, [vp, i32, vp, C.POINTER(i64), C.POINTER(i64), vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)          # AttributeError here = header/library mismatch: fail loudly
@@ -130,7 +140,9 @@ EXPORTS = ["sps_last_error", "sps_version", "sps_ctx_create", "sps_ctx_destroy",
            "sps_submap_voxel", "sps_submap_voxel_ijk", "sps_transform_points", "sps_filter_prepare", "sps_forward_n",
            "sps_compact_stable", "sps_train_forward", "sps_train_backward", "sps_train_generation", "sps_train_backward_at", "sps_scan_mse", "sps_scan_mse_backward", "sps_radius_grid_upload", "sps_radius_count",
            "sps_radius_fill", "sps_radius_grid_attach", "sps_radius_item", "sps_forward_metrics_n", "sps_level_counts", "sps_get_voxels",
-           "sps_get_inverse", "sps_get_parent", "sps_get_map_pairs", "sps_get_tile_masks", "sps_get_nbr", "sps_get_kernel_map", "sps_get_logits", "sps_get_feature"]
+           "sps_get_inverse", "sps_get_parent", "sps_get_map_pairs", "sps_get_tile_masks", "sps_get_nbr", "sps_get_kernel_map", "sps_get_logits", "sps_get_feature",
+           "sps_lts_num_tensors", "sps_lts_tensor_info", "sps_lts_numel", "sps_lts_lidar_info", "sps_lts_create",
+           "sps_lts_destroy", "sps_lts_project", "sps_lts_forward", "sps_lts_check", "sps_lts_tap"]
 
 
 def check(rc: int) -> None:
@@ -373,3 +385,77 @@ class Context:
         out = (C.c_int64 * 125)()
         check(lib.sps_get_map_pairs(self.handle, which, out))
         return list(out)[: 125 if which == 5 else 81]
+
+
+# ---- LTS baseline (include/sps_hip.h, "LTS baseline") ----------------------------------------------------------------
+LTS_LIDARS = {"vlp-16": 0, "hdl-32": 1}
+_LTS_LAYOUT = None
+
+
+def lts_layout():
+    """((name, offset, numel, shape), ...) of the LTS weight blob: the reference SPCTReg state_dict, in its order."""
+    global _LTS_LAYOUT
+    if _LTS_LAYOUT is None:
+        out = []
+        buf = C.create_string_buffer(128)
+        off, num, nd = C.c_int64(), C.c_int64(), C.c_int()
+        shape = (C.c_int64 * 3)()
+        for i in range(lib.sps_lts_num_tensors()):
+            check(lib.sps_lts_tensor_info(i, buf, 128, C.byref(off), C.byref(num), shape, C.byref(nd)))
+            out.append((buf.value.decode(), off.value, num.value, tuple(shape[d] for d in range(nd.value))))
+        _LTS_LAYOUT = tuple(out)
+    return _LTS_LAYOUT
+
+
+def lts_lidar_info(lidar: str):
+    """(beams, window_size, num_windows) of a lidar name."""
+    if lidar not in LTS_LIDARS:
+        raise ValueError(f"unknown lidar {lidar!r}")
+    b, w, nw = C.c_int(), C.c_int(), C.c_int()
+    check(lib.sps_lts_lidar_info(LTS_LIDARS[lidar], C.byref(b), C.byref(w), C.byref(nw)))
+    return b.value, w.value, nw.value
+
+
+def lts_check(rc: int) -> None:
+    """check() for the LTS calls: an out-of-image or NaN point is the reference's IndexError."""
+    if rc == ERR_RANGE:
+        raise IndexError(lib.sps_last_error().decode())
+    check(rc)
+
+
+class LtsHandle:
+    """One ``sps_lts``: folded SPCTReg weights + workspace on one device."""
+
+    def __init__(self, device: int, blob_host_ptr: int, numel: int):
+        h = C.c_void_p()
+        check(lib.sps_lts_create(int(device), blob_host_ptr, int(numel), C.byref(h)))
+        self.handle = h
+        self.device = int(device)
+
+    def project(self, pts_ptr, ld, n, lidar: int, frame_ptr, x_ptr, rows_ptr, stream):
+        check(lib.sps_lts_project(self.handle, pts_ptr, ld, n, lidar, frame_ptr, x_ptr, rows_ptr, stream))
+
+    def forward(self, x_ptr, B, N, scores_ptr, stream):
+        check(lib.sps_lts_forward(self.handle, x_ptr, B, N, scores_ptr, stream))
+
+    def check_errors(self, stream):
+        lts_check(lib.sps_lts_check(self.handle, stream))
+
+    def tap_shape(self, which: int):
+        r, c = C.c_int64(), C.c_int64()
+        check(lib.sps_lts_tap(self.handle, which, None, C.byref(r), C.byref(c), None))
+        return r.value, c.value
+
+    def tap(self, which: int, out_ptr, stream):
+        check(lib.sps_lts_tap(self.handle, which, out_ptr, None, None, stream))
+
+    def close(self):
+        if getattr(self, "handle", None):
+            lib.sps_lts_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

@@ -13,7 +13,8 @@
 //   variant-A submap (radius query over a map grid)   blt_dataset.py:258-271
 //
 // One translation unit; its sections live in the *.inc.h files next to this one (all inside the
-// anonymous namespace below): keys_hash, grid_kernels, map_kernels, conv_kernels, aux_kernels, netspec.
+// anonymous namespace below): keys_hash, grid_kernels, map_kernels, conv_kernels, aux_kernels, netspec, lts_kernels
+// (the LTS baseline; its host side is lts_host.inc.h).
 //
 // Data layout in HBM
 //   block key   : u64  [b:5 | t+16:5 | BZ:18 | BY:18 | BX:18], BX = (x + 2^17) >> (level + 2); a block is
@@ -36,6 +37,7 @@
 #include <array>
 #include <cstdlib>
 #include <cstring>
+#include <map>
 #include <memory>
 #include <string>
 #include <vector>
@@ -141,6 +143,7 @@ int fail(int code, const char *fmt, ...) {
 #include "aux_kernels.inc.h"
 #include "netspec.inc.h"
 #include "train_kernels.inc.h"
+#include "lts_kernels.inc.h"
 
 // ------------------------------------------------------------------------------------------
 // context
@@ -992,7 +995,7 @@ int transform_launch(const TIN *in, int64_t ld, int64_t n, const Mat4 &T, int id
 extern "C" {
 
 const char *sps_last_error(void) { return g_err.c_str(); }
-int sps_version(void) { return 201; }
+int sps_version(void) { return 202; }
 
 int sps_ctx_create(int device, sps_ctx **out) {
   if (!out) return fail(SPS_ERR_INVALID, "out is null");
@@ -2149,5 +2152,7 @@ int sps_get_feature(sps_ctx *c, const char *name, float *out_dev, int64_t *rows,
   }
   return fail(SPS_ERR_INVALID, "unknown feature tap '%s'", name);
 }
+
+#include "lts_host.inc.h"
 
 }  // extern "C"
