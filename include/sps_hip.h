@@ -34,7 +34,7 @@ extern "C" {
 #define SPS_ERR_NOMEM (-3)   /* device allocation failed / compact arena overflow */
 #define SPS_ERR_RANGE (-4)   /* a coordinate does not fit the 64-bit voxel key   */
 #define SPS_ERR_NOWEIGHTS (-5)
-#define SPS_ERR_ITEMCAP (-6) /* sps_radius_item: the caller's item buffer is too small   */
+#define SPS_ERR_ITEMCAP (-6) /* sps_radius_item: the caller's item buffer is too small; sps_radius_crop: crop capacity */
 
 #define SPS_NUM_LEVELS 5 /* tensor strides 1,2,4,8,16 (minkunet.py:161-219) */
 
@@ -394,6 +394,47 @@ int sps_lts_check(sps_lts *h, void *stream);
 /* Intermediate of the last forward: which = 0 embedding, 1..4 outputs of sa1..sa4 (f32 [B*N][128], point-major),
  * 5 / 6 linear1's max / mean over the points of each window (f32 [B][2048]).  out_dev NULL: *rows, *cols only. */
 int sps_lts_tap(sps_lts *h, int which, float *out_dev, int64_t *rows, int64_t *cols, void *stream);
+
+/* ---- online baseline filters (4DMOS, MapMOS, mask) ------------------------------------------------------------------
+ * The per-frame bodies of the reference's other scan filters (c_ws/src/mos4d/scripts/mos4d_node.py:80-147,
+ * c_ws/src/mapmos/scripts/mapmos_node.py:70-112, c_ws/src/sps_filter/scripts/mask.py:86-147) as stream-ordered calls that
+ * never synchronise with the host; the row counts they produce stay in caller-owned device int32 arrays.
+ *
+ * sps_forward_head_n: sps_forward_head whose row count is read from DEVICE memory (*n_dev <= n_max; grids are sized for
+ *   n_max): MapMOSNet.predict (mapmos.py:59-83, mapmos_node.py:95) on scan rows + a radius crop whose size only the device
+ *   knows.  Rows at or past *n_dev of out_dev are left untouched; *n_dev == 0 is a valid (empty) forward.
+ * sps_transform_rows: the window / batch rows of the baselines -- util.transform_point_cloud (util.py:187-194, the f64
+ *   fused multiply-add chain of sps_transform_points) stored as float32 rows (0, x', y', z', t) with row stride ldo >= 5:
+ *   t = the scan index (mos4d_node.py:97-104, then .to(float32) at :113) or 0 (the MapMOS scan, mapmos.py:39-47).
+ *   feat_dev (may be NULL): feat_dev[i] = feat_value (the MapMOS per-point feature, mapmos.py:64-71).
+ * sps_transform_points_n: sps_transform_points whose row count is read from device memory (*n_dev <= n_max): the mask
+ *   node's inverse transform of the submap that sps_filter_prepare left behind the scan rows (mask.py:121-125,
+ *   util.inverse_transform_point_cloud: pass T_host = inv(T) computed on the host as np.linalg.inv does).
+ * sps_radius_crop: select_points_within_radius (mapmos_node.py:63-68, :79-80, r = 30): map point i is kept iff
+ *   sqrt((dx*dx + dy*dy) + dz*dz) <= r with d = p_i - T[:3, 3], every operation a rounded float64 one (numpy's order;
+ *   float32 maps are widened first).  The kept points, in ascending map index (np.where), become rows n_scan + k of
+ *   rows_dev: (0, x, y, z, -1) as float32, and feat_dev[n_scan + k] = feat_value (feat_dev may be NULL).
+ *   counts_dev[0] = min(kept, cap), counts_dev[1] = n_scan + counts_dev[0].  More than cap kept points: the rest are
+ *   dropped and the next sps_check returns SPS_ERR_ITEMCAP.  scratch_dev: int32[max(1, ceil(m / SPS_CROP_BLOCK))].
+ *   map_dev rows are float32 (in_f64 = 0) or float64 with row stride ld >= 3; T_host NULL = centre at the origin.
+ * sps_label_filter: to_label + `scan[labels == 0]` (mos4d_node.py:121-127, mapmos_node.py:98-103): labels_dev[i] = 1 if
+ *   logits_dev[i * ld_logits] > 0 else 0 (NaN -> 0); the first three floats of every row i of rows_dev (stride ld) with
+ *   label 0 go, in input order, to out_dev [., 4] as (x, y, z, 0); counts_dev[0] = rows kept.  gt_dev (may be NULL): the
+ *   ground-truth column (stride ld_gt), gt = s < 0.84f ? 0 : 1 (mos4d_node.py:83), counts_dev[1..4] = TP, FP, FN, TN of
+ *   util.calculate_metrics (util.py:285-299, positive = 1; integers, deterministic).  counts_dev holds 5 int32. */
+#define SPS_CROP_BLOCK 1024
+int sps_forward_head_n(sps_ctx *ctx, const float *coords_dev, int64_t ld, int64_t n_max, const int32_t *n_dev,
+                       float voxel_size, const float *feats_dev, float t_base, float *out_dev, int64_t ldo, int activation,
+                       void *stream);
+int sps_transform_rows(sps_ctx *ctx, const void *xyz_dev, int in_f64, int64_t ld, int64_t n, const double *T_host, float t,
+                       float *rows_dev, int64_t ldo, float *feat_dev, float feat_value, void *stream);
+int sps_transform_points_n(sps_ctx *ctx, const void *xyz_dev, int in_f64, int64_t ld, int64_t n_max, const int32_t *n_dev,
+                           const double *T_host, void *out_dev, int out_f64, int64_t ldo, void *stream);
+int sps_radius_crop(sps_ctx *ctx, const void *map_dev, int in_f64, int64_t ld, int64_t m, const double *T_host, double r,
+                    int32_t *scratch_dev, int64_t n_scan, float *rows_dev, int64_t ldo, int64_t cap, float *feat_dev,
+                    float feat_value, int32_t *counts_dev, void *stream);
+int sps_label_filter(sps_ctx *ctx, const float *logits_dev, int64_t ld_logits, int64_t n, const float *rows_dev, int64_t ld,
+                     const float *gt_dev, int64_t ld_gt, float *labels_dev, float *out_dev, int32_t *counts_dev, void *stream);
 
 #ifdef __cplusplus
 }

@@ -118,6 +118,11 @@ def _load() -> C.CDLL:
         "sps_lts_forward": (i32, [vp, vp, i64, i64, vp, vp]),
         "sps_lts_check": (i32, [vp, vp]),
         "sps_lts_tap": (i32, [vp, i32, vp, C.POINTER(i64), C.POINTER(i64), vp]),
+        "sps_forward_head_n": (i32, [vp, vp, i64, i64, vp, f32, vp, f32, vp, i64, i32, vp]),
+        "sps_transform_rows": (i32, [vp, vp, i32, i64, i64, vp, f32, vp, i64, vp, f32, vp]),
+        "sps_transform_points_n": (i32, [vp, vp, i32, i64, i64, vp, vp, vp, i32, i64, vp]),
+        "sps_radius_crop": (i32, [vp, vp, i32, i64, i64, vp, C.c_double, vp, i64, vp, i64, i64, vp, f32, vp, vp]),
+        "sps_label_filter": (i32, [vp, vp, i64, i64, vp, i64, vp, i64, vp, vp, vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)          # AttributeError here = header/library mismatch: fail loudly
@@ -142,7 +147,9 @@ EXPORTS = ["sps_last_error", "sps_version", "sps_ctx_create", "sps_ctx_destroy",
            "sps_radius_fill", "sps_radius_grid_attach", "sps_radius_item", "sps_forward_metrics_n", "sps_level_counts", "sps_get_voxels",
            "sps_get_inverse", "sps_get_parent", "sps_get_map_pairs", "sps_get_tile_masks", "sps_get_nbr", "sps_get_kernel_map", "sps_get_logits", "sps_get_feature",
            "sps_lts_num_tensors", "sps_lts_tensor_info", "sps_lts_numel", "sps_lts_lidar_info", "sps_lts_create",
-           "sps_lts_destroy", "sps_lts_project", "sps_lts_forward", "sps_lts_check", "sps_lts_tap"]
+           "sps_lts_destroy", "sps_lts_project", "sps_lts_forward", "sps_lts_check", "sps_lts_tap",
+           "sps_forward_head_n", "sps_transform_rows", "sps_transform_points_n", "sps_radius_crop", "sps_label_filter"]
+CROP_BLOCK = 1024          # SPS_CROP_BLOCK: map rows per int of sps_radius_crop's scratch
 
 
 def check(rc: int) -> None:
@@ -251,6 +258,11 @@ class Context:
         check(lib.sps_forward_head(self.handle, coords_ptr, ld, n, voxel_size, feats_ptr, t_base, out_ptr, ldo,
                                    activation, stream))
 
+    def forward_head_n(self, coords_ptr: int, ld: int, n_max: int, n_dev_ptr: int, voxel_size: float, feats_ptr,
+                       t_base: float, out_ptr: int, ldo: int, activation: int, stream: int):
+        check(lib.sps_forward_head_n(self.handle, coords_ptr, ld, n_max, n_dev_ptr, voxel_size, feats_ptr, t_base, out_ptr,
+                                     ldo, activation, stream))
+
     def forward_metrics(self, batch_ptr: int, ld: int, n: int, voxel_size: float, eps: float, n_batches: int,
                         scores_ptr: int, out_ptr: int, stream: int):
         check(lib.sps_forward_metrics(self.handle, batch_ptr, ld, n, voxel_size, eps, n_batches, scores_ptr, out_ptr, stream))
@@ -345,6 +357,27 @@ class Context:
     def compact_stable(self, scores_ptr: int, rows_ptr: int, ld: int, cols: int, n: int, eps: float, out_ptr: int,
                        count_ptr: int, stream: int):
         check(lib.sps_compact_stable(self.handle, scores_ptr, rows_ptr, ld, cols, n, eps, out_ptr, count_ptr, stream))
+
+    # ---- online baseline filters (include/sps_hip.h, "online baseline filters") ----
+    def transform_rows(self, xyz_ptr: int, in_f64: bool, ld: int, n: int, T, t: float, rows_ptr: int, ldo: int, feat_ptr,
+                       feat_value: float, stream: int):
+        check(lib.sps_transform_rows(self.handle, xyz_ptr, int(in_f64), ld, n, self._mat(T), float(t), rows_ptr, ldo, feat_ptr,
+                                     float(feat_value), stream))
+
+    def transform_points_n(self, xyz_ptr: int, in_f64: bool, ld: int, n_max: int, n_dev_ptr: int, T, out_ptr: int,
+                           out_f64: bool, ldo: int, stream: int):
+        check(lib.sps_transform_points_n(self.handle, xyz_ptr, int(in_f64), ld, n_max, n_dev_ptr, self._mat(T), out_ptr,
+                                         int(out_f64), ldo, stream))
+
+    def radius_crop(self, map_ptr: int, in_f64: bool, ld: int, m: int, T, r: float, scratch_ptr: int, n_scan: int,
+                    rows_ptr: int, ldo: int, cap: int, feat_ptr, feat_value: float, counts_ptr: int, stream: int):
+        check(lib.sps_radius_crop(self.handle, map_ptr, int(in_f64), ld, m, self._mat(T), float(r), scratch_ptr, n_scan,
+                                  rows_ptr, ldo, cap, feat_ptr, float(feat_value), counts_ptr, stream))
+
+    def label_filter(self, logits_ptr: int, ld_logits: int, n: int, rows_ptr: int, ld: int, gt_ptr, ld_gt: int,
+                     labels_ptr: int, out_ptr: int, counts_ptr: int, stream: int):
+        check(lib.sps_label_filter(self.handle, logits_ptr, ld_logits, n, rows_ptr, ld, gt_ptr, ld_gt, labels_ptr, out_ptr,
+                                   counts_ptr, stream))
 
     def train_forward(self, params_ptr: int, numel: int, coords_ptr: int, ld: int, n: int, voxel_size: float,
                       scores_ptr: int, batch_stats_ptr, stream: int):

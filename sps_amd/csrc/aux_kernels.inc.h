@@ -291,11 +291,15 @@ struct Mat4 {
 // util.transform_point_cloud (util.py:187-194): t = [p;1] @ T^T in float64, then t[:3] / t[3].  numpy evaluates the
 // product with dgemm, whose inner loop is a chain of fused multiply-adds over k = 0..3 starting from a rounded product;
 // the same chain here reproduces tests/golden/transform.npz bit for bit in float64.  The result is stored as float32
-// (sps_node.py:107: torch.tensor(..., dtype=float32)) or float64.  WITH_BT also writes the batch index 0 and the scan
-// time stamp 1 around x, y, z: rows (b, x, y, z, t) of util.infer's tensor (util.py:170-172).
+// (sps_node.py:107: torch.tensor(..., dtype=float32)) or float64.  WITH_BT also writes the batch index 0 and the time
+// stamp t_stamp around x, y, z: rows (b, x, y, z, t) of util.infer's tensor (util.py:170-172, t = 1) or of the baselines'
+// windows (mos4d_node.py:98-104: t = scan index; mapmos.py:39-47: t = 0), and feat_value into feat_out[p] when feat_out
+// is set.  n_dev (optional): the row count lives on the device (<= n, the bound the grid was sized for).
 template <typename TIN, typename TOUT, bool WITH_BT>
 __global__ void k_transform_points(const TIN *__restrict__ in, int64_t ld, int n, Mat4 T, int identity,
-                                   TOUT *__restrict__ out, int64_t ldo) {
+                                   TOUT *__restrict__ out, int64_t ldo, float t_stamp, float *__restrict__ feat_out,
+                                   float feat_value, const int *__restrict__ n_dev) {
+  if (n_dev) n = min(n, *n_dev);
   const int p = blockIdx.x * blockDim.x + threadIdx.x;
   if (p >= n) return;
   const TIN *r = in + (size_t)p * ld;
@@ -317,8 +321,9 @@ __global__ void k_transform_points(const TIN *__restrict__ in, int64_t ld, int n
   TOUT *w = out + (size_t)p * ldo;
   if (WITH_BT) {
     w[0] = (TOUT)0;
-    w[4] = (TOUT)1;  // SCAN_TIMESTAMP (util.py:20)
+    w[4] = (TOUT)t_stamp;  // SCAN_TIMESTAMP (util.py:20) on the SPS path
     ++w;
+    if (feat_out) feat_out[p] = feat_value;
   }
   w[0] = (TOUT)o[0];
   w[1] = (TOUT)o[1];

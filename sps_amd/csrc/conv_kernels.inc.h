@@ -1161,8 +1161,10 @@ __global__ __launch_bounds__(256) void k_conv0_fused(const int *__restrict__ n_o
 // (domain: |feature| < 2^15 and < 2^16 points per voxel; the error of the mean is < 2^-32)
 constexpr double FEAT_FIX = 4294967296.0;
 
+// n_dev (optional, sps_forward_head_n): the row count lives on the device; rows at or past it are never read
 __global__ void k_voxel_feat_accum(const float *__restrict__ feats, const int *__restrict__ inv, int n,
-                                   long long *__restrict__ vacc, int *__restrict__ vcnt) {
+                                   long long *__restrict__ vacc, int *__restrict__ vcnt, const int *__restrict__ n_dev) {
+  if (n_dev) n = min(n, *n_dev);
   const int p = blockIdx.x * blockDim.x + threadIdx.x;
   if (p >= n) return;
   const int v = inv[p];
@@ -1263,9 +1265,12 @@ __global__ __launch_bounds__(256) void k_conv0_feat(const int *__restrict__ n_ou
 
 // `final` 1x1 conv (+ bias) on block8's 8-channel output, slice to the points, optional sigmoid:
 //   out[p, j] = act(sum_c F[inv[p], c] * W[c, j] + b[j]),  j < oc     (minkunet.py:152-158, :217-219)
+// n_dev (optional): device-side row count; rows at or past it are left untouched
 __global__ void k_slice_head(const float *__restrict__ F, int ldf, const int *__restrict__ inv, int n,
                              const float *__restrict__ W, const float *__restrict__ bias, int oc, int act,
-                             float *__restrict__ out, int64_t ldo, const int *__restrict__ abort_flag) {
+                             float *__restrict__ out, int64_t ldo, const int *__restrict__ abort_flag,
+                             const int *__restrict__ n_dev) {
+  if (n_dev) n = min(n, *n_dev);
   const int p = blockIdx.x * blockDim.x + threadIdx.x;
   if (p >= n) return;
   const int v = (abort_flag && *abort_flag) ? -1 : inv[p];  // aborted forward: NaN

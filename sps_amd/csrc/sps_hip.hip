@@ -14,7 +14,8 @@
 //
 // One translation unit; its sections live in the *.inc.h files next to this one (all inside the
 // anonymous namespace below): keys_hash, grid_kernels, map_kernels, conv_kernels, aux_kernels, netspec, lts_kernels
-// (the LTS baseline; its host side is lts_host.inc.h).
+// (the LTS baseline; its host side is lts_host.inc.h), baseline_kernels (the online 4DMOS / MapMOS filters; host side
+// baseline_host.inc.h).
 //
 // Data layout in HBM
 //   block key   : u64  [b:5 | t+16:5 | BZ:18 | BY:18 | BX:18], BX = (x + 2^17) >> (level + 2); a block is
@@ -144,6 +145,7 @@ int fail(int code, const char *fmt, ...) {
 #include "netspec.inc.h"
 #include "train_kernels.inc.h"
 #include "lts_kernels.inc.h"
+#include "baseline_kernels.inc.h"
 
 // ------------------------------------------------------------------------------------------
 // context
@@ -974,16 +976,28 @@ int radius_item_launch(sps_ctx *c, const TIN *scan, int64_t ld, int64_t n, const
   return SPS_OK;
 }
 
+// rows (b = 0, x, y, z, t) of a batch (with_bt) or plain xyz rows; rw: the time stamp, the optional per-row feature and
+// the optional device-side row count
+struct RowWrite {
+  float t = 1.f;
+  float *feat = nullptr;
+  float feat_value = 0.f;
+  const int *n_dev = nullptr;
+};
+
 template <typename TIN>
 int transform_launch(const TIN *in, int64_t ld, int64_t n, const Mat4 &T, int identity, void *out, int out_f64,
-                            bool with_bt, int64_t ldo, hipStream_t st) {
+                            bool with_bt, int64_t ldo, const RowWrite &rw, hipStream_t st) {
   const dim3 g((unsigned)((n + 255) / 256)), b(256);
   if (with_bt)
-    hipLaunchKernelGGL((k_transform_points<TIN, float, true>), g, b, 0, st, in, ld, (int)n, T, identity, (float *)out, ldo);
+    hipLaunchKernelGGL((k_transform_points<TIN, float, true>), g, b, 0, st, in, ld, (int)n, T, identity, (float *)out, ldo,
+                       rw.t, rw.feat, rw.feat_value, rw.n_dev);
   else if (out_f64)
-    hipLaunchKernelGGL((k_transform_points<TIN, double, false>), g, b, 0, st, in, ld, (int)n, T, identity, (double *)out, ldo);
+    hipLaunchKernelGGL((k_transform_points<TIN, double, false>), g, b, 0, st, in, ld, (int)n, T, identity, (double *)out, ldo,
+                       rw.t, nullptr, 0.f, rw.n_dev);
   else
-    hipLaunchKernelGGL((k_transform_points<TIN, float, false>), g, b, 0, st, in, ld, (int)n, T, identity, (float *)out, ldo);
+    hipLaunchKernelGGL((k_transform_points<TIN, float, false>), g, b, 0, st, in, ld, (int)n, T, identity, (float *)out, ldo,
+                       rw.t, nullptr, 0.f, rw.n_dev);
   return SPS_OK;
 }
 
@@ -1309,7 +1323,6 @@ static int forward_impl(sps_ctx *c, const float *coords, int64_t ld, int64_t n, 
   Level &L0 = c->lv[0];
   PyramidArgs pa = pyramid_args(c);
   pa.n_dev = fo.n_dev;
-  if (fo.n_dev && (fo.head || fo.feats)) return fail(SPS_ERR_INVALID, "a device-side row count is only supported by sps_forward_n / sps_forward_metrics_n");
   if (!skip_front) {
   // ---- reset: the block hashes are cleaned by the previous forward; full reset only when dirty
   if (c->tables_dirty) {
@@ -1343,7 +1356,7 @@ static int forward_impl(sps_ctx *c, const float *coords, int64_t ld, int64_t n, 
   if (fo.feats) {  // voxel feature = mean of its points' features (App. A.4)
     HIP_TRY(hipMemsetAsync(c->vacc, 0, (size_t)n * sizeof(long long), st));  // V <= n rows are used
     HIP_TRY(hipMemsetAsync(c->vcnt, 0, (size_t)n * sizeof(int), st));
-    hipLaunchKernelGGL(k_voxel_feat_accum, dim3(gp), dim3(256), 0, st, fo.feats, L0.inv, (int)n, c->vacc, c->vcnt);
+    hipLaunchKernelGGL(k_voxel_feat_accum, dim3(gp), dim3(256), 0, st, fo.feats, L0.inv, (int)n, c->vacc, c->vcnt, fo.n_dev);
     hipLaunchKernelGGL(k_voxel_feat_mean, dim3((unsigned)grid_for(n, 256, 2048)), dim3(256), 0, st, c->counts, c->vacc,
                        c->vcnt, c->vfeat);
   }
@@ -1478,7 +1491,8 @@ static int forward_impl(sps_ctx *c, const float *coords, int64_t ld, int64_t n, 
     const NetSpec &s = *c->net;
     const ConvSpec &fs = s.convs[s.find_conv("final")];
     hipLaunchKernelGGL(k_slice_head, dim3((unsigned)gs), dim3(256), 0, st, c->b8o, 8, L0.inv, (int)n,
-                       c->blob + fs.w_off, c->blob + s.bias_off, s.out_channels, fo.act, scores, fo.ldo, c->counts + 15);
+                       c->blob + fs.w_off, c->blob + s.bias_off, s.out_channels, fo.act, scores, fo.ldo, c->counts + 15,
+                       fo.n_dev);
     c->last_kernel = "k_slice_head";
     prof_mark(c, "slice_head", st);
     if (!skip_front) hipLaunchKernelGGL(k_bhash_cleanup, dim3(gbc * NLV), dim3(256), 0, st, pa, gbc);
@@ -1549,7 +1563,7 @@ __global__ void k_err_clear(int *err, int bits) { atomicAnd(err, ~bits); }
 // two users of one context (a training step and a device item loader) each get to see their own error.
 static int report_device_errors(sps_ctx *c, int e, hipStream_t st) {
   if (!e) return SPS_OK;
-  const int bit = (e & 2) ? 2 : (e & 16) ? 16 : (e & 8) ? 8 : (e & 1) ? 1 : (e & 4) ? 4 : e;
+  const int bit = (e & 2) ? 2 : (e & 16) ? 16 : (e & 8) ? 8 : (e & 1) ? 1 : (e & 4) ? 4 : (e & 32) ? 32 : e;
   hipLaunchKernelGGL(k_err_clear, dim3(1), dim3(1), 0, st, c->err, bit);
   if (bit == 2) {
     // a level outgrew its compact arrays: that forward was aborted (NaN scores).  Dense sizes from now on -- the next
@@ -1570,6 +1584,9 @@ static int report_device_errors(sps_ctx *c, int e, hipStream_t st) {
   if (bit == 4)
     return fail(SPS_ERR_ITEMCAP, "sps_radius_item: the item buffer is too small for the scan rows + the radius submap rows "
                                  "(the rows beyond it were dropped): pass a larger row_cap");
+  if (bit == 32)
+    return fail(SPS_ERR_ITEMCAP, "sps_radius_crop: more map points lie within the radius than the crop capacity holds (the "
+                                 "points beyond it were dropped from that frame): pass a larger capacity");
   return fail(SPS_ERR_HIP, "internal: unknown device error bits 0x%x", e);
 }
 
@@ -1737,7 +1754,7 @@ static int submap_impl(sps_ctx *c, const void *src, bool ijk, int64_t ld, int64_
 }
 
 static int transform_impl(sps_ctx *c, const void *xyz, int in_f64, int64_t ld, int64_t n, const double *T_host, void *out,
-                          int out_f64, bool with_bt, int64_t ldo, void *stream) {
+                          int out_f64, bool with_bt, int64_t ldo, void *stream, const RowWrite &rw = RowWrite{}) {
   if (!c || n < 0 || ld < 3 || ldo < (with_bt ? 5 : 3) || (n > 0 && (!xyz || !out))) return fail(SPS_ERR_INVALID, "bad arguments");
   if (n > SPS_MAX_POINTS) return fail(SPS_ERR_INVALID, "too many points (limit %d)", SPS_MAX_POINTS);
   HIP_TRY(hipSetDevice(c->device));
@@ -1746,9 +1763,9 @@ static int transform_impl(sps_ctx *c, const void *xyz, int in_f64, int64_t ld, i
   for (int i = 0; i < 16; ++i) T.m[i] = T_host ? T_host[i] : (i % 5 == 0 ? 1.0 : 0.0);
   const int identity = T_host ? 0 : 1;
   if (in_f64)
-    transform_launch((const double *)xyz, ld, n, T, identity, out, out_f64, with_bt, ldo, (hipStream_t)stream);
+    transform_launch((const double *)xyz, ld, n, T, identity, out, out_f64, with_bt, ldo, rw, (hipStream_t)stream);
   else
-    transform_launch((const float *)xyz, ld, n, T, identity, out, out_f64, with_bt, ldo, (hipStream_t)stream);
+    transform_launch((const float *)xyz, ld, n, T, identity, out, out_f64, with_bt, ldo, rw, (hipStream_t)stream);
   HIP_TRY(hipGetLastError());
   return SPS_OK;
 }
@@ -2154,5 +2171,6 @@ int sps_get_feature(sps_ctx *c, const char *name, float *out_dev, int64_t *rows,
 }
 
 #include "lts_host.inc.h"
+#include "baseline_host.inc.h"
 
 }  // extern "C"

@@ -563,7 +563,8 @@ int sps_train_forward(sps_ctx *c, const float *params_dev, int64_t numel, const 
   // final 1x1 conv + bias, slice, sigmoid (models.py:28-29)
   const ConvSpec &fs = s.convs[s.find_conv("final")];
   hipLaunchKernelGGL(k_slice_head, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, c->b8o, 8, c->lv[0].inv, (int)n,
-                     t->blob + fs.w_off, t->blob + s.bias_off, 1, 1, scores, (int64_t)1, (const int *)nullptr);
+                     t->blob + fs.w_off, t->blob + s.bias_off, 1, 1, scores, (int64_t)1, (const int *)nullptr,
+                     (const int *)nullptr);
   if (batch_stats_dev)
     HIP_TRY(hipMemcpyAsync(batch_stats_dev, t->batch_stats, (size_t)s.ss_numel / 2 * 3 * sizeof(float), hipMemcpyDeviceToDevice, st));
   // the block hashes go back to "free" (the inference forward does this in its tail kernel)
