@@ -218,6 +218,27 @@ int sps_forward_n(sps_ctx *ctx, const float *coords_dev, int64_t ld, int64_t n_m
                   float *scores_dev, void *stream);
 int sps_compact_stable(sps_ctx *ctx, const float *scores_dev, const float *rows_dev, int64_t ld, int cols, int64_t n,
                        float eps, float *out_dev, int32_t *count_dev, void *stream);
+/* sps_filter_finish: everything else the reference's two SPS nodes publish and log from the scores of a frame
+ * (sps_node.py:123-161, sps_node_cvm.py:145-184), in TWO launches, stream-ordered, no host synchronisation, no atomics
+ * (positions and sums are combined from per-workgroup partials in a fixed order: two calls on the same input give the
+ * same bits).  Takes the place of sps_compact_stable in a frame that wants the node's full output.
+ *   scores_dev [n]; raw_dev: the scan rows AS RECEIVED, float32, row stride ld, cols floats per row; label_col: the
+ *   column of raw_dev that holds the label (sps_node.py:107: 3), or -1 for a scan without labels; batch_dev / counts_dev:
+ *   what sps_filter_prepare wrote for this scan (n rows (0, x', y', z', 1), then counts_dev[0] rows (0, vx, vy, vz, 0)).
+ *   keep_strict = 0 keeps score <= eps (sps_node.py:148); keep_strict = 1 keeps score < eps, the rows with pred == 0
+ *   (sps_node_cvm.py:171): a score exactly eps is kept by the first node and dropped by the second.  Float32 compares.
+ * Outputs, each may be NULL (filtered_dev and count_dev go together):
+ *   filtered_dev [., cols]  the whole kept rows in input order, *count_dev = their number (a NaN score is dropped);
+ *   labels_dev   [n] int32  pred = score < eps ? 0 : 1 (a NaN score gives 1, as np.where does);
+ *   cloud_tr_dev [n, 4]     (x', y', z', (float)pred)   -- debug/raw_cloud_tr;
+ *   submap_dev   [n_sub, 4] (vx, vy, vz, 1), n_sub = counts_dev[0] read on the device -- debug/cloud_submap;
+ *   sums_dev     [8] f64    the accumulator row of sps_metrics_dev over all n rows with gt = label < eps ? 0 : 1;
+ *                           written only when label_col >= 0.
+ * n = 0 writes *count_dev = 0 and a zero sums row. */
+int sps_filter_finish(sps_ctx *ctx, const float *scores_dev, int64_t n, const float *raw_dev, int64_t ld, int cols,
+                      int label_col, const float *batch_dev, const int32_t *counts_dev, float eps, int keep_strict,
+                      float *filtered_dev, int32_t *count_dev, int32_t *labels_dev, float *cloud_tr_dev, float *submap_dev,
+                      double *sums_dev, void *stream);
 
 /* ---- variant-A submap (offline path) ----------------------------------------------------
  * Replaces BacchusDataset.select_closest_points (reference src/sps/datasets/blt_dataset.py:258-271:

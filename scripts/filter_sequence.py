@@ -1,0 +1,167 @@
+#!/usr/bin/env python3
+"""Replay one recorded sequence through one of the online scan filters and print what its ROS node would log -- the
+filter side of the reference's localisation experiment (c_ws/src/sps_filter/scripts/loc_exp_general.bash runs
+sps | mos4d | mapmos | lts | mask | raw over a sequence, fed by scans_pub/scripts/pub_scans.py) without ROS and without
+the localiser.
+
+    --filter sps       sps_amd.sps_filters.SPSFilter       (sps_node.py)
+    --filter sps_cvm   sps_amd.sps_filters.SPSCVMFilter    (sps_node_cvm.py: add_pose gets the replayed pose of the PREVIOUS frame)
+    --filter raw       the SPS filter at epsilon = 2: every point passes (how loc_exp_general.bash defines "raw")
+    --filter mos4d | mapmos | mask | lts                   sps_amd.baseline_filters / sps_amd.lts_filter
+
+Two frames are kept in flight: result() of frame i is called after submit() of frame i + 1, so the host work of a
+frame overlaps the device work of the one before.  Per frame the node's lines are printed behind the frame's stamp,
+then the sequence means.  ``--out DIR`` writes every filtered cloud as DIR/<stamp>.npy.  ``--synthetic N`` replays N
+scans of a temporary tree built from sps_amd.synthetic (no $DATA needed); without ``-w`` the weights are a seeded
+random initialisation.
+"""
+from __future__ import annotations
+
+import os
+import sys
+import tempfile
+
+import click
+import numpy as np
+import torch
+import yaml
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+from sps_amd.replay import ScanReplay, write_synthetic_tree  # noqa: E402
+
+FILTERS = ("sps", "sps_cvm", "mos4d", "mapmos", "mask", "lts", "raw")
+DEFAULT_CONFIG_PATH = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "config", "config.yaml")
+RAW_EPSILON = 2.0
+
+
+def build_filter(name, cfg, weights, pc_map, epsilon):
+    vs = cfg["MODEL"]["VOXEL_SIZE"]
+    if name in ("sps", "sps_cvm", "raw"):
+        from sps_amd.models import models
+        from sps_amd.sps_filters import SPSCVMFilter, SPSFilter
+        cls = SPSCVMFilter if name == "sps_cvm" else SPSFilter
+        eps = RAW_EPSILON if name == "raw" else epsilon
+        if weights:
+            return cls.from_checkpoint(cfg, weights, pc_map, epsilon=eps)
+        torch.manual_seed(0)
+        return cls(models.SPSNet(cfg).cuda().eval().freeze(), pc_map, voxel_size=vs, epsilon=eps)
+    if name == "mask":
+        from sps_amd.baseline_filters import MaskFilter
+        return MaskFilter(pc_map, voxel_size=vs)
+    if name == "mos4d":
+        from sps_amd.baseline_filters import MOS4DFilter
+        from sps_amd.models.baselines import MOS4DNet
+        if weights:
+            return MOS4DFilter.from_checkpoint(weights)
+        torch.manual_seed(0)
+        return MOS4DFilter(MOS4DNet(0.2).cuda().eval().freeze(), buffer_size=10)
+    if name == "mapmos":
+        from sps_amd.baseline_filters import MapMOSFilter
+        from sps_amd.models.baselines import MapMOSNet
+        if weights:
+            return MapMOSFilter.from_checkpoint(weights, pc_map[:, :3])
+        torch.manual_seed(0)
+        return MapMOSFilter(MapMOSNet(0.1).cuda().eval().freeze(), pc_map[:, :3])
+    from sps_amd.lts_filter import LTSFilter
+    from sps_amd.models.lts import SPCTReg
+    torch.manual_seed(0)
+    model = SPCTReg()
+    if weights:
+        model.load_state_dict(torch.load(weights, map_location="cpu", weights_only=False))
+    return LTSFilter(model.cuda().eval(), lidar="hdl-32", epsilon_1=epsilon)
+
+
+def frame_lines(name, res):
+    """(the node's log lines of a frame, the numbers that enter the sequence means)."""
+    if name in ("sps", "sps_cvm", "raw"):
+        vals = {"T": res.t_total, "P": res.t_prune, "I": res.t_infer, "N": len(res.scores), "n": len(res.filtered)}
+        if res.loss is not None:
+            vals.update(loss=res.loss, r2=res.r2, dIoU=res.dIoU, accuracy=res.accuracy, precision=res.precision,
+                        recall=res.recall, f1=res.f1)
+        return list(res.log_lines()), vals
+    if name == "mask":
+        hz = lambda t: 1 / t if t else 0
+        line = (f"T: {res.t_total:.3f} [{hz(res.t_total):.2f} Hz] P: {res.t_prune:.3f} [{hz(res.t_prune):.2f} Hz] "
+                f"n: {len(res.filtered):d} S: {res.n_scan_voxels:d} M: {res.n_submap_voxels:d} ")
+        return ["mask", line], {"T": res.t_total, "P": res.t_prune, "n": len(res.filtered)}
+    vals = {"T": res.t_total, "I": res.t_infer, "n": len(res.filtered)}
+    metrics = "no labels"
+    if getattr(res, "dIoU", None) is not None:
+        f1 = res.F1
+        vals.update(dIoU=res.dIoU, accuracy=res.accuracy, precision=res.precision, recall=res.recall, f1=f1)
+        metrics = (f"dIoU: {res.dIoU:.3f} accuracy: {res.accuracy:.3f} precision: {res.precision:.3f} "
+                   f"recall: {res.recall:.3f} f1: {f1:.3f} ")
+    return [metrics, f"T: {res.t_total:.3f} I: {res.t_infer:.3f} n: {len(res.filtered):d} "], vals
+
+
+def submit(name, f, scan, T, prev_pose):
+    if name == "sps_cvm":
+        if prev_pose is not None:
+            f.add_pose(prev_pose)                       # the corrected pose of the frame before: all the node ever has
+        return f.submit(scan)
+    if name == "lts":
+        return f.submit(torch.from_numpy(np.ascontiguousarray(scan[:, :4], dtype=np.float32)).cuda())
+    return f.submit(scan, T)
+
+
+@click.command()
+@click.option("--filter", "name", type=click.Choice(FILTERS), default="sps")
+@click.option("--weights", "-w", type=str, default=None, help="checkpoint of the chosen filter's model")
+@click.option("--sequence", "-seq", type=str, default=None, help="sequence id under $DATA/sequence")
+@click.option("--config", "-c", type=str, default=DEFAULT_CONFIG_PATH, help="Path to the config file (.yaml)")
+@click.option("--epsilon", type=float, default=None, help="stability threshold (default: FILTER.THRESHOLD of the config)")
+@click.option("--out", "out_dir", type=str, default=None, help="write the filtered clouds as DIR/<stamp>.npy")
+@click.option("--synthetic", "n_synth", type=int, default=0, help="replay N synthetic scans instead of $DATA")
+def main(name, weights, sequence, config, epsilon, out_dir, n_synth):
+    cfg = yaml.safe_load(open(config))
+    if epsilon is None:
+        epsilon = float(cfg.get("FILTER", {}).get("THRESHOLD", 0.84))
+    tmp = None
+    if n_synth:
+        tmp = tempfile.TemporaryDirectory()
+        data_dir, sequence = tmp.name, "synthetic"
+        write_synthetic_tree(data_dir, n_synth, sequence)
+    else:
+        assert sequence, "give -seq SEQ or --synthetic N"
+        data_dir = str(os.environ.get("DATA"))
+    replay = ScanReplay(data_dir, sequence)
+    map_pth = os.path.join(data_dir, "maps", cfg["TRAIN"]["MAP"] if not n_synth else "base_map.asc.npy")
+    pc_map = np.load(map_pth) if map_pth.endswith(".npy") else np.loadtxt(map_pth, dtype=np.float32)
+    f = build_filter(name, cfg, weights, torch.from_numpy(np.ascontiguousarray(pc_map[:, :3], dtype=np.float32)), epsilon)
+    if out_dir:
+        os.makedirs(out_dir, exist_ok=True)
+    print(f"filter: {name}  sequence: {sequence}  scans: {len(replay)}  epsilon: {RAW_EPSILON if name == 'raw' else epsilon}")
+
+    totals, n_done = {}, 0
+
+    def finish(stamp, pend):
+        nonlocal n_done
+        res = pend.result()
+        lines, vals = frame_lines(name, res)
+        for line in lines:
+            print(f"[{stamp}] {line}")
+        for k, v in vals.items():
+            totals.setdefault(k, []).append(float(v))
+        if out_dir:
+            np.save(os.path.join(out_dir, stamp + ".npy"), res.filtered.cpu().numpy())
+        n_done += 1
+
+    in_flight, prev_pose = None, None
+    for stamp, scan, pose, map_tr in replay:
+        T = map_tr @ pose
+        pend = submit(name, f, scan, T, prev_pose)
+        prev_pose = T
+        if in_flight is not None:
+            finish(*in_flight)                          # frame i's result after frame i + 1's submit
+        in_flight = (stamp, pend)
+    if in_flight is not None:
+        finish(*in_flight)
+    means = " ".join(f"{k}: {np.mean(v):.3f}" for k, v in totals.items())
+    print(f"sequence means over {n_done} frames: {means}")
+    if tmp is not None:
+        tmp.cleanup()
+
+
+if __name__ == "__main__":
+    main()

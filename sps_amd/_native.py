@@ -86,6 +86,7 @@ def _load() -> C.CDLL:
         "sps_filter_prepare": (i32, [vp, vp, i32, i64, i64, vp, vp, vp, vp]),
         "sps_forward_n": (i32, [vp, vp, i64, i64, vp, f32, vp, vp]),
         "sps_compact_stable": (i32, [vp, vp, vp, i64, i32, i64, f32, vp, vp, vp]),
+        "sps_filter_finish": (i32, [vp, vp, i64, vp, i64, i32, i32, vp, vp, f32, i32, vp, vp, vp, vp, vp, vp, vp]),
         "sps_train_forward": (i32, [vp, vp, i64, vp, i64, i64, f32, vp, vp, vp]),
         "sps_train_backward": (i32, [vp, vp, vp, vp, i64, vp]),
         "sps_train_generation": (i32, [vp, C.POINTER(i64)]),
@@ -143,7 +144,7 @@ EXPORTS = ["sps_last_error", "sps_version", "sps_ctx_create", "sps_ctx_destroy",
            "sps_forward_head", "sps_check", "sps_metrics", "sps_metrics_dev",
            "sps_profile_enable", "sps_profile_count", "sps_profile_read", "sps_profile_kernel", "sps_map_upload", "sps_map_upload_voxels",
            "sps_submap_voxel", "sps_submap_voxel_ijk", "sps_transform_points", "sps_filter_prepare", "sps_forward_n",
-           "sps_compact_stable", "sps_train_forward", "sps_train_backward", "sps_train_generation", "sps_train_backward_at", "sps_scan_mse", "sps_scan_mse_backward", "sps_radius_grid_upload", "sps_radius_count",
+           "sps_compact_stable", "sps_filter_finish", "sps_train_forward", "sps_train_backward", "sps_train_generation", "sps_train_backward_at", "sps_scan_mse", "sps_scan_mse_backward", "sps_radius_grid_upload", "sps_radius_count",
            "sps_radius_fill", "sps_radius_grid_attach", "sps_radius_item", "sps_forward_metrics_n", "sps_level_counts", "sps_get_voxels",
            "sps_get_inverse", "sps_get_parent", "sps_get_map_pairs", "sps_get_tile_masks", "sps_get_nbr", "sps_get_kernel_map", "sps_get_logits", "sps_get_feature",
            "sps_lts_num_tensors", "sps_lts_tensor_info", "sps_lts_numel", "sps_lts_lidar_info", "sps_lts_create",
@@ -357,6 +358,14 @@ class Context:
     def compact_stable(self, scores_ptr: int, rows_ptr: int, ld: int, cols: int, n: int, eps: float, out_ptr: int,
                        count_ptr: int, stream: int):
         check(lib.sps_compact_stable(self.handle, scores_ptr, rows_ptr, ld, cols, n, eps, out_ptr, count_ptr, stream))
+
+    def filter_finish(self, scores_ptr: int, n: int, raw_ptr, ld: int, cols: int, label_col: int, batch_ptr, counts_ptr,
+                      eps: float, keep_strict: bool, filtered_ptr, count_ptr, labels_ptr, cloud_tr_ptr, submap_ptr, sums_ptr,
+                      stream: int):
+        """sps_filter_finish (include/sps_hip.h): label_col = -1 for a scan without labels; any output pointer may be None."""
+        check(lib.sps_filter_finish(self.handle, scores_ptr, n, raw_ptr, ld, cols, label_col, batch_ptr, counts_ptr, eps,
+                                    1 if keep_strict else 0, filtered_ptr, count_ptr, labels_ptr, cloud_tr_ptr, submap_ptr,
+                                    sums_ptr, stream))
 
     # ---- online baseline filters (include/sps_hip.h, "online baseline filters") ----
     def transform_rows(self, xyz_ptr: int, in_f64: bool, ld: int, n: int, T, t: float, rows_ptr: int, ldo: int, feat_ptr,

@@ -15,7 +15,7 @@
 // One translation unit; its sections live in the *.inc.h files next to this one (all inside the
 // anonymous namespace below): keys_hash, grid_kernels, map_kernels, conv_kernels, aux_kernels, netspec, lts_kernels
 // (the LTS baseline; its host side is lts_host.inc.h), baseline_kernels (the online 4DMOS / MapMOS filters; host side
-// baseline_host.inc.h).
+// baseline_host.inc.h), sps_filter_kernels (what the SPS nodes do with a frame's scores; host side sps_filter_finish below).
 //
 // Data layout in HBM
 //   block key   : u64  [b:5 | t+16:5 | BZ:18 | BY:18 | BX:18], BX = (x + 2^17) >> (level + 2); a block is
@@ -146,6 +146,7 @@ int fail(int code, const char *fmt, ...) {
 #include "train_kernels.inc.h"
 #include "lts_kernels.inc.h"
 #include "baseline_kernels.inc.h"
+#include "sps_filter_kernels.inc.h"
 
 // ------------------------------------------------------------------------------------------
 // context
@@ -261,6 +262,7 @@ struct sps_ctx {
   int *counts = nullptr;     // device: [0..4] voxels per level, [5] submap rows, [6] scan voxels, [8..12] blocks per level
   int *err = nullptr;        // device error flag
   int *block_sums = nullptr;
+  double *filter_part = nullptr;  // sps_filter_finish: one metric partial row per SCAN_BLOCK rows
   unsigned long long *scan_agg = nullptr;  // single-pass ranking: one generation-tagged word per logical workgroup and level
   int *keep = nullptr;
   double *macc = nullptr;    // metrics accumulators [32*8]
@@ -467,6 +469,7 @@ int reserve(sps_ctx *c, int64_t n) {
     }
   }
   ALLOC(c->block_sums, int, 2 * (cap / SCAN_BLOCK + 8) * SPS_NUM_LEVELS);
+  ALLOC(c->filter_part, double, 8 * (cap / SCAN_BLOCK + 8));
   const size_t agg_words = (size_t)(cap / SCAN_BLOCK + 8) * NLV;
   ALLOC(c->scan_agg, unsigned long long, agg_words);
   HIP_TRY(hipMemset(c->scan_agg, 0, sizeof(unsigned long long) * agg_words));
@@ -1804,6 +1807,55 @@ int sps_compact_stable(sps_ctx *c, const float *scores_dev, const float *rows_de
   hipLaunchKernelGGL(k_stable_count, dim3(nb), dim3(SCAN_BLOCK), 0, st, scores_dev, (int)n, eps, c->block_sums);
   hipLaunchKernelGGL(k_stable_write, dim3(nb), dim3(SCAN_BLOCK), 0, st, scores_dev, (int)n, eps, c->block_sums, rows_dev, ld,
                      cols, out_dev, count_dev);
+  HIP_TRY(hipGetLastError());
+  return SPS_OK;
+}
+
+int sps_filter_finish(sps_ctx *c, const float *scores_dev, int64_t n, const float *raw_dev, int64_t ld, int cols, int label_col,
+                      const float *batch_dev, const int32_t *counts_dev, float eps, int keep_strict, float *filtered_dev,
+                      int32_t *count_dev, int32_t *labels_dev, float *cloud_tr_dev, float *submap_dev, double *sums_dev,
+                      void *stream) {
+  if (!c || n < 0 || cols < 1 || ld < cols || label_col < -1 || label_col >= cols || (keep_strict != 0 && keep_strict != 1))
+    return fail(SPS_ERR_INVALID, "bad arguments");
+  if ((filtered_dev != nullptr) != (count_dev != nullptr)) return fail(SPS_ERR_INVALID, "filtered_dev and count_dev go together");
+  if (submap_dev && !counts_dev) return fail(SPS_ERR_INVALID, "submap_dev needs counts_dev");
+  if (n > 0 && (!scores_dev || ((filtered_dev || label_col >= 0) && !raw_dev) || ((cloud_tr_dev || submap_dev) && !batch_dev)))
+    return fail(SPS_ERR_INVALID, "null input");
+  if (n > SPS_MAX_POINTS) return fail(SPS_ERR_INVALID, "too many points (limit %d)", SPS_MAX_POINTS);
+  HIP_TRY(hipSetDevice(c->device));
+  hipStream_t st = (hipStream_t)stream;
+  const bool want_sums = sums_dev && label_col >= 0;
+  if (n == 0) {  // zero counts, a zero sums row, no rows
+    if (count_dev) HIP_TRY(hipMemsetAsync(count_dev, 0, sizeof(int32_t), st));
+    if (want_sums) HIP_TRY(hipMemsetAsync(sums_dev, 0, 8 * sizeof(double), st));
+    return SPS_OK;
+  }
+  if (n > c->cap) {
+    int rc = reserve(c, n);
+    if (rc != SPS_OK) return rc;
+  }
+  FilterFinishArgs a;
+  a.scores = scores_dev;
+  a.n = (int)n;
+  a.eps = eps;
+  a.strict = keep_strict;
+  a.raw = raw_dev;
+  a.ld = ld;
+  a.cols = cols;
+  a.label_col = want_sums ? label_col : -1;
+  a.batch = batch_dev;
+  a.counts = counts_dev;
+  a.filtered = filtered_dev;
+  a.count_out = count_dev;
+  a.labels = labels_dev;
+  a.cloud_tr = cloud_tr_dev;
+  a.submap = submap_dev;
+  a.sums = want_sums ? sums_dev : nullptr;
+  a.block_sums = c->block_sums;
+  a.part = c->filter_part;
+  const int nb = (int)((n + SCAN_BLOCK - 1) / SCAN_BLOCK);
+  hipLaunchKernelGGL(k_filter_count, dim3(nb), dim3(SCAN_BLOCK), 0, st, a);
+  hipLaunchKernelGGL(k_filter_write, dim3(nb), dim3(SCAN_BLOCK), 0, st, a);
   HIP_TRY(hipGetLastError());
   return SPS_OK;
 }
