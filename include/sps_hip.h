@@ -457,6 +457,44 @@ int sps_radius_crop(sps_ctx *ctx, const void *map_dev, int in_f64, int64_t ld, i
 int sps_label_filter(sps_ctx *ctx, const float *logits_dev, int64_t ld_logits, int64_t n, const float *rows_dev, int64_t ld,
                      const float *gt_dev, int64_t ld_gt, float *labels_dev, float *out_dev, int32_t *counts_dev, void *stream);
 
+/* ---- localiser (scan-to-map point-to-point ICP) ---------------------------------------------------------------------
+ * The stage the reference's localisation experiment puts behind a scan filter (exp_pipeline/loc_exp_general.bash runs
+ * hdl_localization there, an external package).  This is NOT a port of it -- no NDT, no UKF, no IMU -- but a
+ * deterministic point-to-point ICP that plays the same role: the filter's kept rows are registered against the map and
+ * the corrected pose goes back into the filter.  Both calls are stream-ordered and never synchronise with the host;
+ * their scratch is the caller's.  No float atomics: float sums go through per-workgroup partial rows combined in block
+ * order, so two calls on the same input give the same bits.  Degenerate input never raises the context's sticky error.
+ *
+ * sps_loc_downsample: voxel-grid thinning of rows_dev (f32 rows (x, y, z, ...), row stride ld >= 3), of which the first
+ *   min(*n_dev, n_max) are read (n_dev: the kept-row count sps_filter_finish / sps_label_filter left on the device).
+ *   A row's voxel is floor(double(v) / leaf) per axis; of the rows of one voxel the one with the lowest index survives.
+ *   The survivors go, in ascending row order, to out_xyz_dev as f64 [cap][3]; survivors beyond cap are dropped and
+ *   *count_dev = min(survivors, cap).  A row with a coordinate outside the key range (|voxel| >= 2^20, NaN) is skipped.
+ *   scratch_dev: sps_loc_downsample_scratch(n_max) bytes.
+ * sps_loc_align: `iters` iterations of point-to-point ICP of pts_dev (f64 [cap][3], the first min(*n_dev, cap) used)
+ *   against the map of the context's radius grid (sps_radius_grid_upload with cell_size = r = the correspondence
+ *   distance), starting from the row-major 4x4 T_init_host.  Two launches per iteration:
+ *     A: q = R p + t as ((r0*x + r1*y) + r2*z) + t; the nearest map point m over the 27 cells around q with
+ *        d2 = (ex*ex + ey*ey) + ez*ez <= r*r, e = q - m, ties to the lowest map index; the terms of H = sum J^T J and
+ *        g = sum J^T e with J = [ -[q]x | I ] (unknown delta = (omega, v)), each entry as (a0*b0 + a1*b1) + a2*b2 over
+ *        the three residual rows; one partial row per workgroup, added in point order.
+ *     B: the partial rows added in block order; n_corr < min_corr -> status 2; Cholesky of H (a pivot <= 0 or a
+ *        non-finite solution -> status 3); H delta = -g; Exp(omega) by Rodrigues (first order below |omega| < 1e-12);
+ *        T <- [Exp(omega), v; 0, 1] T; |v| < tol_t and |omega| < tol_r -> status 0.
+ *   Every operation is a float64 one rounded on its own.  Once the status is final the remaining launches return at
+ *   once.  Outputs (device): T_out_dev double[16]; status_dev int32[4] = (code, iterations run, correspondences of the
+ *   last iteration run, 0) with code 0 converged, 1 iterations exhausted, 2 too few correspondences, 3 singular system
+ *   -- on 2 and 3 T_out is T_init bit for bit; trace_dev double[iters][4] = (n_corr, sum d2, |v|, |omega|) per iteration
+ *   (rows of iterations not run are 0); normal_dev (may be NULL) double[iters][28] = the 21 upper-triangle entries of H
+ *   row-major, the 6 entries of b = -g, sum d2.  scratch_dev: sps_loc_align_scratch(cap) bytes. */
+int64_t sps_loc_downsample_scratch(int64_t n_max);
+int64_t sps_loc_align_scratch(int64_t cap);
+int sps_loc_downsample(sps_ctx *ctx, const float *rows_dev, int64_t ld, int64_t n_max, const int32_t *n_dev, double leaf,
+                       double *out_xyz_dev, int64_t cap, int32_t *count_dev, void *scratch_dev, void *stream);
+int sps_loc_align(sps_ctx *ctx, const double *pts_dev, const int32_t *n_dev, int64_t cap, const double *T_init_host,
+                  int iters, int min_corr, double tol_t, double tol_r, double *T_out_dev, int32_t *status_dev,
+                  double *trace_dev, double *normal_dev, void *scratch_dev, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """Replay one recorded sequence through one of the online scan filters and print what its ROS node would log -- the
 filter side of the reference's localisation experiment (c_ws/src/sps_filter/scripts/loc_exp_general.bash runs
-sps | mos4d | mapmos | lts | mask | raw over a sequence, fed by scans_pub/scripts/pub_scans.py) without ROS and without
-the localiser.
+sps | mos4d | mapmos | lts | mask | raw over a sequence, fed by scans_pub/scripts/pub_scans.py) without ROS and, unless
+``--localise`` is given, without the localiser.
 
     --filter sps       sps_amd.sps_filters.SPSFilter       (sps_node.py)
     --filter sps_cvm   sps_amd.sps_filters.SPSCVMFilter    (sps_node_cvm.py: add_pose gets the replayed pose of the PREVIOUS frame)
@@ -14,6 +14,14 @@ frame overlaps the device work of the one before.  Per frame the node's lines ar
 then the sequence means.  ``--out DIR`` writes every filtered cloud as DIR/<stamp>.npy.  ``--synthetic N`` replays N
 scans of a temporary tree built from sps_amd.synthetic (no $DATA needed); without ``-w`` the weights are a seeded
 random initialisation.
+
+``--localise`` closes the loop of the experiment (sps_amd.localiser.LocalisationLoop, seeded with the first replayed
+pose): the filter's kept rows are registered against the map by a device point-to-point ICP (the stand-in for
+hdl_localization; not a port of it), the corrected pose goes back into the filter, and the replayed poses only score
+the result.  Frames then run one at a time; behind each frame's lines comes
+``loc: status iterations n_corr rmse | err_t err_r`` (metres, degrees, against the replayed pose map_tr @ pose) and at
+the end the absolute pose error evo_ape prints by default.  ``--traj-out FILE`` writes the estimated trajectory
+(stamp + the top three rows of the pose per line).
 """
 from __future__ import annotations
 
@@ -105,6 +113,32 @@ def submit(name, f, scan, T, prev_pose):
     return f.submit(scan, T)
 
 
+def closed_loop(name, f, pc_map, replay, finish, traj_out):
+    """--localise: one LocalisationLoop step per frame, scored against the replayed poses."""
+    from sps_amd.localiser import LocalisationLoop, ScanToMapLocaliser
+    from sps_amd.trajectory import ape_translation, rotation_angle, write_trajectory
+    localiser = ScanToMapLocaliser(pc_map[:, :3])
+    loop, stamps, ref = None, [], []
+    for stamp, scan, pose, map_tr in replay:
+        T = map_tr @ pose
+        if loop is None:
+            loop = LocalisationLoop(f, localiser, T)
+        step = loop.step(scan)
+        finish(stamp, None, step.filter_result)
+        p = step.pose_result
+        err_t = float(np.linalg.norm(step.pose[:3, 3] - T[:3, 3]))
+        err_r = float(np.degrees(rotation_angle(step.pose, T)))
+        print(f"[{stamp}] loc: {p.status:d} {p.iterations:d} {p.n_corr:d} {p.rmse:.4f} | {err_t:.4f} {err_r:.4f}"
+              + (" (flagged: the guess is kept)" if step.flagged else ""))
+        stamps.append(stamp)
+        ref.append(T)
+    if loop is not None and stamps:
+        ape = ape_translation(loop.poses, ref)
+        print(f"APE translation (m) over {len(stamps)} frames: " + " ".join(f"{k}: {v:.4f}" for k, v in ape.items()))
+    if traj_out:
+        write_trajectory(traj_out, stamps, loop.poses if loop is not None else [])
+
+
 @click.command()
 @click.option("--filter", "name", type=click.Choice(FILTERS), default="sps")
 @click.option("--weights", "-w", type=str, default=None, help="checkpoint of the chosen filter's model")
@@ -113,7 +147,9 @@ def submit(name, f, scan, T, prev_pose):
 @click.option("--epsilon", type=float, default=None, help="stability threshold (default: FILTER.THRESHOLD of the config)")
 @click.option("--out", "out_dir", type=str, default=None, help="write the filtered clouds as DIR/<stamp>.npy")
 @click.option("--synthetic", "n_synth", type=int, default=0, help="replay N synthetic scans instead of $DATA")
-def main(name, weights, sequence, config, epsilon, out_dir, n_synth):
+@click.option("--localise", is_flag=True, help="close the loop: localise every filtered cloud and feed the pose back")
+@click.option("--traj-out", "traj_out", type=str, default=None, help="with --localise: write the estimated trajectory")
+def main(name, weights, sequence, config, epsilon, out_dir, n_synth, localise, traj_out):
     cfg = yaml.safe_load(open(config))
     if epsilon is None:
         epsilon = float(cfg.get("FILTER", {}).get("THRESHOLD", 0.84))
@@ -135,9 +171,9 @@ def main(name, weights, sequence, config, epsilon, out_dir, n_synth):
 
     totals, n_done = {}, 0
 
-    def finish(stamp, pend):
+    def finish(stamp, pend, res=None):
         nonlocal n_done
-        res = pend.result()
+        res = pend.result() if res is None else res
         lines, vals = frame_lines(name, res)
         for line in lines:
             print(f"[{stamp}] {line}")
@@ -147,8 +183,12 @@ def main(name, weights, sequence, config, epsilon, out_dir, n_synth):
             np.save(os.path.join(out_dir, stamp + ".npy"), res.filtered.cpu().numpy())
         n_done += 1
 
+    if localise:
+        closed_loop(name, f, pc_map, replay, finish, traj_out)
+    elif traj_out:
+        raise click.UsageError("--traj-out needs --localise")
     in_flight, prev_pose = None, None
-    for stamp, scan, pose, map_tr in replay:
+    for stamp, scan, pose, map_tr in ([] if localise else replay):
         T = map_tr @ pose
         pend = submit(name, f, scan, T, prev_pose)
         prev_pose = T

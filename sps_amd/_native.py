@@ -124,6 +124,10 @@ def _load() -> C.CDLL:
         "sps_transform_points_n": (i32, [vp, vp, i32, i64, i64, vp, vp, vp, i32, i64, vp]),
         "sps_radius_crop": (i32, [vp, vp, i32, i64, i64, vp, C.c_double, vp, i64, vp, i64, i64, vp, f32, vp, vp]),
         "sps_label_filter": (i32, [vp, vp, i64, i64, vp, i64, vp, i64, vp, vp, vp, vp]),
+        "sps_loc_downsample_scratch": (i64, [i64]),
+        "sps_loc_align_scratch": (i64, [i64]),
+        "sps_loc_downsample": (i32, [vp, vp, i64, i64, vp, C.c_double, vp, i64, vp, vp, vp]),
+        "sps_loc_align": (i32, [vp, vp, vp, i64, vp, i32, i32, C.c_double, C.c_double, vp, vp, vp, vp, vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)          # AttributeError here = header/library mismatch: fail loudly
@@ -149,7 +153,8 @@ EXPORTS = ["sps_last_error", "sps_version", "sps_ctx_create", "sps_ctx_destroy",
            "sps_get_inverse", "sps_get_parent", "sps_get_map_pairs", "sps_get_tile_masks", "sps_get_nbr", "sps_get_kernel_map", "sps_get_logits", "sps_get_feature",
            "sps_lts_num_tensors", "sps_lts_tensor_info", "sps_lts_numel", "sps_lts_lidar_info", "sps_lts_create",
            "sps_lts_destroy", "sps_lts_project", "sps_lts_forward", "sps_lts_check", "sps_lts_tap",
-           "sps_forward_head_n", "sps_transform_rows", "sps_transform_points_n", "sps_radius_crop", "sps_label_filter"]
+           "sps_forward_head_n", "sps_transform_rows", "sps_transform_points_n", "sps_radius_crop", "sps_label_filter",
+           "sps_loc_downsample_scratch", "sps_loc_align_scratch", "sps_loc_downsample", "sps_loc_align"]
 CROP_BLOCK = 1024          # SPS_CROP_BLOCK: map rows per int of sps_radius_crop's scratch
 
 
@@ -387,6 +392,22 @@ class Context:
                      labels_ptr: int, out_ptr: int, counts_ptr: int, stream: int):
         check(lib.sps_label_filter(self.handle, logits_ptr, ld_logits, n, rows_ptr, ld, gt_ptr, ld_gt, labels_ptr, out_ptr,
                                    counts_ptr, stream))
+
+    # ---- localiser (include/sps_hip.h, "localiser") ----
+    def radius_grid_upload(self, keys_ptr: int, start_ptr: int, pts_ptr: int, xyz_ptr: int, n_cells: int, m: int,
+                           cell_size: float, r: float, stream: int):
+        check(lib.sps_radius_grid_upload(self.handle, keys_ptr, start_ptr, pts_ptr, xyz_ptr, int(n_cells), int(m),
+                                         float(cell_size), float(r), stream))
+
+    def loc_downsample(self, rows_ptr, ld: int, n_max: int, n_dev_ptr: int, leaf: float, out_ptr, cap: int, count_ptr: int,
+                       scratch_ptr: int, stream: int):
+        check(lib.sps_loc_downsample(self.handle, rows_ptr, int(ld), int(n_max), n_dev_ptr, float(leaf), out_ptr, int(cap),
+                                     count_ptr, scratch_ptr, stream))
+
+    def loc_align(self, pts_ptr, n_dev_ptr: int, cap: int, T_init, iters: int, min_corr: int, tol_t: float, tol_r: float,
+                  T_out_ptr: int, status_ptr: int, trace_ptr, normal_ptr, scratch_ptr: int, stream: int):
+        check(lib.sps_loc_align(self.handle, pts_ptr, n_dev_ptr, int(cap), self._mat(T_init), int(iters), int(min_corr),
+                                float(tol_t), float(tol_r), T_out_ptr, status_ptr, trace_ptr, normal_ptr, scratch_ptr, stream))
 
     def train_forward(self, params_ptr: int, numel: int, coords_ptr: int, ld: int, n: int, voxel_size: float,
                       scores_ptr: int, batch_stats_ptr, stream: int):

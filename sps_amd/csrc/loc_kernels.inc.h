@@ -1,0 +1,332 @@
+// loc_kernels.inc.h -- part of sps_hip.hip (included inside its anonymous namespace): the scan-to-map localiser
+// (host side: loc_host.inc.h; ABI: the "localiser" section of include/sps_hip.h).
+//
+//   k_loc_ds_insert / k_loc_ds_count / k_loc_ds_write   voxel-grid thinning of the kept rows (lowest row index per voxel)
+//   k_loc_init                                          T_out = T_init, status = (1, 0, 0, 0), done = 0
+//   k_loc_assoc   (launch A of an iteration)            nearest map point of every scan point + the normal-equation terms
+//   k_loc_solve   (launch B of an iteration)            ordered sum, 6x6 Cholesky, Rodrigues, pose update, status
+//
+// A deterministic point-to-point ICP: no float atomics; every float sum goes through per-workgroup partial rows that
+// are combined in block order; the only atomic is an integer atomicMin whose result does not depend on arrival order.
+// All geometry is float64 and every operation is rounded on its own, so a host restatement that does the same agrees
+// step by step.  The compiler contracts a * b + c into an FMA by default, also through __dmul_rn / __dadd_rn (plain
+// * and + in the HIP headers), so this file switches contraction off for its own code and spells the products and
+// sums through loc_mul / loc_add.
+
+#pragma clang fp contract(off)
+__device__ inline double loc_mul(double a, double b) { return a * b; }
+__device__ inline double loc_add(double a, double b) { return a + b; }
+
+// ---- voxel-grid thinning ---------------------------------------------------------------------------------------------
+// voxel of a row: floor(double(v) / leaf) per axis; a coordinate whose voxel index leaves the key range (NaN included)
+// skips the row.  There is no sticky error: a localiser must survive a bad point.
+__device__ inline bool loc_voxel_key(const float *__restrict__ r, double leaf, uint64_t &key) {
+  long long c[3];
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    const double f = floor(__ddiv_rn((double)r[a], leaf));
+    if (!(f >= -1048575.0 && f <= 1048575.0)) return false;
+    c[a] = (long long)f;
+  }
+  key = radius_key(c[0], c[1], c[2]);
+  return true;
+}
+
+__global__ __launch_bounds__(SCAN_BLOCK) void k_loc_ds_insert(const float *__restrict__ rows, int64_t ld, int n_max,
+                                                               const int *__restrict__ n_dev, double leaf, HashTable h) {
+  const int n = min(n_max, max(*n_dev, 0));
+  const int p = blockIdx.x * SCAN_BLOCK + threadIdx.x;
+  if (p >= n) return;
+  uint64_t key;
+  if (!loc_voxel_key(rows + (size_t)p * ld, leaf, key)) return;
+  const int s = hash_insert(h, key);  // the table holds >= 2 * n_max slots: an insert always finds one
+  atomicMin(&h.first[s], p);
+}
+
+__device__ inline bool loc_ds_survives(const float *__restrict__ rows, int64_t ld, int p, int n, double leaf, const HashTable &h) {
+  if (p >= n) return false;
+  uint64_t key;
+  if (!loc_voxel_key(rows + (size_t)p * ld, leaf, key)) return false;
+  const int s = hash_find_slot(h, key);
+  return s >= 0 && h.first[s] == p;
+}
+
+__global__ __launch_bounds__(SCAN_BLOCK) void k_loc_ds_count(const float *__restrict__ rows, int64_t ld, int n_max,
+                                                              const int *__restrict__ n_dev, double leaf, HashTable h,
+                                                              int *__restrict__ block_sums) {
+  __shared__ int lds[SCAN_BLOCK / 64];
+  const int n = min(n_max, max(*n_dev, 0));
+  const int p = blockIdx.x * SCAN_BLOCK + threadIdx.x;
+  const int flag = loc_ds_survives(rows, ld, p, n, leaf, h);
+  const int tot = block_reduce_sum(flag, lds);
+  if (threadIdx.x == 0) block_sums[blockIdx.x] = tot;
+}
+
+// the survivor of rank k (ascending row index) becomes out[k] = (double)(x, y, z); ranks >= cap are dropped and the
+// count saturates at cap
+__global__ __launch_bounds__(SCAN_BLOCK) void k_loc_ds_write(const float *__restrict__ rows, int64_t ld, int n_max,
+                                                              const int *__restrict__ n_dev, double leaf, HashTable h,
+                                                              const int *__restrict__ block_sums, double *__restrict__ out,
+                                                              int cap, int *__restrict__ count_out) {
+  __shared__ int lds[SCAN_BLOCK / 64];
+  __shared__ int wave_off[SCAN_BLOCK / 64];
+  int part = 0;
+  for (int i = threadIdx.x; i < (int)blockIdx.x; i += SCAN_BLOCK) part += block_sums[i];
+  const int base = block_reduce_sum(part, lds);
+  const int n = min(n_max, max(*n_dev, 0));
+  const int p = blockIdx.x * SCAN_BLOCK + threadIdx.x;
+  const int flag = loc_ds_survives(rows, ld, p, n, leaf, h);
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const unsigned long long bal = __ballot(flag);
+  const int in_wave = __popcll(bal & ((1ull << lane) - 1ull));
+  if (lane == 0) wave_off[wave] = __popcll(bal);
+  __syncthreads();
+  int off = 0, tot = 0;
+  for (int i = 0; i < SCAN_BLOCK / 64; ++i) {
+    const int c = wave_off[i];
+    if (i < wave) off += c;
+    tot += c;
+  }
+  const int k = base + off + in_wave;
+  if (flag && k < cap) {
+    const float *r = rows + (size_t)p * ld;
+    double *o = out + (size_t)k * 3;
+    o[0] = (double)r[0], o[1] = (double)r[1], o[2] = (double)r[2];
+  }
+  if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) *count_out = min(base + tot, cap);
+}
+
+// ---- alignment -------------------------------------------------------------------------------------------------------
+struct LocPose {
+  double m[16];
+};
+constexpr int LOC_TERMS = 29;       // 21 upper-triangle entries of H, 6 of g = sum J^T e, sum d^2, the count
+constexpr int LOC_PTS = 32;         // scan points of one workgroup of launch A (one wave per point, 8 rounds of 4)
+constexpr int LOC_SEG = 8;          // launch B sums the partial rows as LOC_SEG runs of consecutive blocks
+
+__global__ void k_loc_init(LocPose T, double *__restrict__ T_out, int *__restrict__ status, int *__restrict__ done) {
+  const int t = threadIdx.x;
+  if (t < 16) T_out[t] = T.m[t];
+  if (t < 4) status[t] = t == 0 ? 1 : 0;  // 1 = iterations exhausted, unless an iteration says otherwise
+  if (t == 0) *done = 0;
+}
+
+// column i of J = [ -[q]x | I ] (the three residual rows)
+__device__ inline void loc_jcol(int i, double qx, double qy, double qz, double c[3]) {
+  c[0] = c[1] = c[2] = 0.0;
+  switch (i) {
+    case 0: c[1] = -qz, c[2] = qy; break;
+    case 1: c[0] = qz, c[2] = -qx; break;
+    case 2: c[0] = -qy, c[1] = qx; break;
+    case 3: c[0] = 1.0; break;
+    case 4: c[1] = 1.0; break;
+    default: c[2] = 1.0; break;
+  }
+}
+__device__ inline double loc_dot3(const double a[3], const double b[3]) {
+  return loc_add(loc_add(loc_mul(a[0], b[0]), loc_mul(a[1], b[1])), loc_mul(a[2], b[2]));
+}
+
+// Launch A.  One wave per scan point: q = R p + t; lanes 0..26 look up the 27 cells around q, then all 64 lanes stride
+// over the cells' map points with the exact test d2 = (ex*ex + ey*ey) + ez*ez <= r2; the wave's minimum is taken over
+// (d2, map index), so ties go to the lowest map index.  Lane l < 29 then forms term l of the point, the workgroup adds
+// its LOC_PTS points in point order, and thread l writes entry l of the workgroup's partial row.
+__global__ __launch_bounds__(256) void k_loc_assoc(const double *__restrict__ pts, const int *__restrict__ n_dev, int cap,
+                                                    RadiusGrid g, const double *__restrict__ T, const int *__restrict__ done,
+                                                    double *__restrict__ partial) {
+  __shared__ double terms[LOC_PTS][LOC_TERMS];
+  if (*done) return;
+  const int n = min(cap, max(*n_dev, 0));
+  const int base = blockIdx.x * LOC_PTS;
+  if (base >= n) return;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  double R[12];
+#pragma unroll
+  for (int i = 0; i < 12; ++i) R[i] = T[i];
+  for (int k = wave; k < LOC_PTS; k += 4) {
+    const int i = base + k;
+    double term = 0.0;
+    if (i < n) {
+      const double px = pts[(size_t)i * 3], py = pts[(size_t)i * 3 + 1], pz = pts[(size_t)i * 3 + 2];
+      double q[3];
+#pragma unroll
+      for (int a = 0; a < 3; ++a)
+        q[a] = loc_add(loc_add(loc_add(loc_mul(R[4 * a], px), loc_mul(R[4 * a + 1], py)), loc_mul(R[4 * a + 2], pz)),
+                         R[4 * a + 3]);
+      long long cx, cy, cz;
+      int c_lo = 0, c_hi = 0;
+      if (lane < 27 && radius_cell(q[0], g.inv_cell, cx) && radius_cell(q[1], g.inv_cell, cy) && radius_cell(q[2], g.inv_cell, cz)) {
+        const int s = hash_find_slot(g.h, radius_key(cx + (lane % 3 - 1), cy + ((lane / 3) % 3 - 1), cz + (lane / 9 - 1)));
+        if (s >= 0) {
+          const int c = g.h.rank[s];
+          c_lo = g.cell_start[c], c_hi = g.cell_start[c + 1];
+        }
+      }
+      double best = INFINITY;
+      int best_j = 0x7FFFFFFF;
+      for (int c = 0; c < 27; ++c) {
+        const int lo = __shfl(c_lo, c, 64), hi = __shfl(c_hi, c, 64);
+        for (int t = lo + lane; t < hi; t += 64) {
+          const int j = g.cell_pts[t];
+          const double ex = q[0] - g.xyz[(size_t)j * 3], ey = q[1] - g.xyz[(size_t)j * 3 + 1], ez = q[2] - g.xyz[(size_t)j * 3 + 2];
+          const double d2 = loc_add(loc_add(loc_mul(ex, ex), loc_mul(ey, ey)), loc_mul(ez, ez));
+          if (d2 <= g.r2 && (d2 < best || (d2 == best && j < best_j))) best = d2, best_j = j;
+        }
+      }
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) {
+        const double od = __shfl_xor(best, o, 64);
+        const int oj = __shfl_xor(best_j, o, 64);
+        if (od < best || (od == best && oj < best_j)) best = od, best_j = oj;
+      }
+      if (best_j != 0x7FFFFFFF && lane < LOC_TERMS) {
+        const int j = best_j;
+        const double e[3] = {q[0] - g.xyz[(size_t)j * 3], q[1] - g.xyz[(size_t)j * 3 + 1], q[2] - g.xyz[(size_t)j * 3 + 2]};
+        if (lane < 21) {
+          int r = 0, l = lane;
+          while (l >= 6 - r) l -= 6 - r, ++r;   // upper triangle, row-major: (r, r + l)
+          double a[3], b[3];
+          loc_jcol(r, q[0], q[1], q[2], a);
+          loc_jcol(r + l, q[0], q[1], q[2], b);
+          term = loc_dot3(a, b);
+        } else if (lane < 27) {
+          double a[3];
+          loc_jcol(lane - 21, q[0], q[1], q[2], a);
+          term = loc_dot3(a, e);
+        } else if (lane == 27) {
+          term = loc_dot3(e, e);
+        } else {
+          term = 1.0;
+        }
+      }
+    }
+    if (lane < LOC_TERMS) terms[k][lane] = term;
+  }
+  __syncthreads();
+  if (threadIdx.x < LOC_TERMS) {
+    double s = 0.0;
+    for (int k = 0; k < LOC_PTS; ++k) s = loc_add(s, terms[k][threadIdx.x]);
+    partial[(size_t)blockIdx.x * LOC_TERMS + threadIdx.x] = s;
+  }
+}
+
+// Launch B, one workgroup of 256.  Thread (seg, col) adds the rows of its run of consecutive blocks in order, thread
+// col adds the LOC_SEG runs in order; thread 0 does the rest.
+__global__ __launch_bounds__(256) void k_loc_solve(const double *__restrict__ partial, const int *__restrict__ n_dev, int cap,
+                                                    int iter, int min_corr, double tol_t, double tol_r, LocPose T_init,
+                                                    double *__restrict__ T, int *__restrict__ status, int *__restrict__ done,
+                                                    double *__restrict__ trace, double *__restrict__ normal) {
+  __shared__ double seg[LOC_SEG][32];
+  __shared__ double tot[32];
+  if (*done) return;
+  const int n = min(cap, max(*n_dev, 0));
+  const int nb = (n + LOC_PTS - 1) / LOC_PTS;
+  const int col = threadIdx.x & 31, sg = threadIdx.x >> 5;
+  if (col < LOC_TERMS) {
+    const int per = (nb + LOC_SEG - 1) / LOC_SEG;
+    const int b1 = min(nb, (sg + 1) * per);
+    double s = 0.0;
+    for (int b = sg * per; b < b1; ++b) s = loc_add(s, partial[(size_t)b * LOC_TERMS + col]);
+    seg[sg][col] = s;
+  }
+  __syncthreads();
+  if (threadIdx.x < LOC_TERMS) {
+    double s = 0.0;
+    for (int i = 0; i < LOC_SEG; ++i) s = loc_add(s, seg[i][threadIdx.x]);
+    tot[threadIdx.x] = s;
+  }
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  const int n_corr = (int)tot[28];
+  const double sum_d2 = tot[27];
+  double b[6];
+  for (int i = 0; i < 6; ++i) b[i] = -tot[21 + i];
+  if (normal) {
+    double *o = normal + (size_t)iter * 28;
+    for (int i = 0; i < 21; ++i) o[i] = tot[i];
+    for (int i = 0; i < 6; ++i) o[21 + i] = b[i];
+    o[27] = sum_d2;
+  }
+  double *tr = trace + (size_t)iter * 4;
+  tr[0] = (double)n_corr, tr[1] = sum_d2, tr[2] = 0.0, tr[3] = 0.0;
+  status[1] = iter + 1;
+  status[2] = n_corr;
+  int code = -1;
+  double L[6][6], y[6], x[6];
+  if (n_corr < min_corr) {
+    code = 2;
+  } else {
+    double H[6][6];
+    for (int i = 0, k = 0; i < 6; ++i)
+      for (int j = i; j < 6; ++j, ++k) H[i][j] = H[j][i] = tot[k];
+    for (int j = 0; j < 6 && code < 0; ++j) {
+      double d = H[j][j];
+      for (int k = 0; k < j; ++k) d = loc_add(d, -loc_mul(L[j][k], L[j][k]));
+      if (!(d > 0.0)) {
+        code = 3;
+        break;
+      }
+      const double ljj = __dsqrt_rn(d);
+      L[j][j] = ljj;
+      for (int i = j + 1; i < 6; ++i) {
+        double s = H[i][j];
+        for (int k = 0; k < j; ++k) s = loc_add(s, -loc_mul(L[i][k], L[j][k]));
+        L[i][j] = __ddiv_rn(s, ljj);
+      }
+    }
+  }
+  if (code < 0) {
+    for (int i = 0; i < 6; ++i) {
+      double s = b[i];
+      for (int k = 0; k < i; ++k) s = loc_add(s, -loc_mul(L[i][k], y[k]));
+      y[i] = __ddiv_rn(s, L[i][i]);
+    }
+    for (int i = 5; i >= 0; --i) {
+      double s = y[i];
+      for (int k = i + 1; k < 6; ++k) s = loc_add(s, -loc_mul(L[k][i], x[k]));
+      x[i] = __ddiv_rn(s, L[i][i]);
+    }
+    bool finite = true;
+    for (int i = 0; i < 6; ++i) finite = finite && isfinite(x[i]);
+    if (!finite) code = 3;   // an overflowing solve is a singular system too
+  }
+  if (code >= 0) {
+    for (int i = 0; i < 16; ++i) T[i] = T_init.m[i];
+    status[0] = code;
+    *done = 1;
+    return;
+  }
+  const double wx = x[0], wy = x[1], wz = x[2];
+  const double th2 = loc_add(loc_add(loc_mul(wx, wx), loc_mul(wy, wy)), loc_mul(wz, wz));
+  const double th = __dsqrt_rn(th2);
+  const double vn = __dsqrt_rn(loc_add(loc_add(loc_mul(x[3], x[3]), loc_mul(x[4], x[4])), loc_mul(x[5], x[5])));
+  // Exp(w) = I + a K + c K^2, K = [w]x, a = sin(th) / th, c = 2 sin^2(th / 2) / th^2; first order below 1e-12
+  double a = 1.0, c = 0.0;
+  if (th >= 1e-12) {
+    const double sh = sin(loc_mul(0.5, th));
+    a = __ddiv_rn(sin(th), th);
+    c = __ddiv_rn(loc_mul(2.0, loc_mul(sh, sh)), th2);
+  }
+  const double K[3][3] = {{0.0, -wz, wy}, {wz, 0.0, -wx}, {-wy, wx, 0.0}};
+  double E[3][3];
+  for (int i = 0; i < 3; ++i)
+    for (int j = 0; j < 3; ++j) {
+      const double k2 = loc_add(loc_add(loc_mul(K[i][0], K[0][j]), loc_mul(K[i][1], K[1][j])), loc_mul(K[i][2], K[2][j]));
+      E[i][j] = loc_add(loc_add(i == j ? 1.0 : 0.0, loc_mul(a, K[i][j])), loc_mul(c, k2));
+    }
+  double Tn[12];
+  for (int i = 0; i < 3; ++i)
+    for (int j = 0; j < 4; ++j) {
+      double s = loc_add(loc_add(loc_mul(E[i][0], T[j]), loc_mul(E[i][1], T[4 + j])), loc_mul(E[i][2], T[8 + j]));
+      if (j == 3) s = loc_add(s, x[3 + i]);
+      Tn[4 * i + j] = s;
+    }
+  for (int i = 0; i < 12; ++i) T[i] = Tn[i];
+  tr[2] = vn, tr[3] = th;
+  if (vn < tol_t && th < tol_r) {
+    status[0] = 0;
+    *done = 1;
+  }
+}
+
+#pragma clang fp contract(fast)

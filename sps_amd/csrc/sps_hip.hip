@@ -147,6 +147,7 @@ int fail(int code, const char *fmt, ...) {
 #include "lts_kernels.inc.h"
 #include "baseline_kernels.inc.h"
 #include "sps_filter_kernels.inc.h"
+#include "loc_kernels.inc.h"
 
 // ------------------------------------------------------------------------------------------
 // context
@@ -2224,5 +2225,6 @@ int sps_get_feature(sps_ctx *c, const char *name, float *out_dev, int64_t *rows,
 
 #include "lts_host.inc.h"
 #include "baseline_host.inc.h"
+#include "loc_host.inc.h"
 
 }  // extern "C"

@@ -153,6 +153,19 @@ class BacchusDataset(Dataset):
         return np.concatenate([np.asarray(h, dtype=np.int64) for h in hits]).astype(int)
 
 
+def radius_grid_cells(xyz: torch.Tensor, cell: float):
+    """The cell arrays of sps_radius_grid_upload for float64 map points [M, 3] on a device: (cell keys [C] ascending,
+    cell_start int32 [C + 1], cell_pts int32 [M]: map indices grouped by cell, ascending inside a cell)."""
+    c = torch.floor(xyz / cell).to(torch.int64)
+    assert int(c.abs().max()) < (1 << 20) - 1, "map extent exceeds the radius grid"
+    keys = ((c[:, 2] + (1 << 20)) << 42) | ((c[:, 1] + (1 << 20)) << 21) | (c[:, 0] + (1 << 20))
+    skeys, order = torch.sort(keys, stable=True)        # grouped by cell, ascending map index inside a cell
+    ukeys, counts = torch.unique_consecutive(skeys, return_counts=True)
+    start = torch.zeros(len(ukeys) + 1, dtype=torch.int32, device=xyz.device)
+    start[1:] = torch.cumsum(counts, 0).to(torch.int32)
+    return ukeys, start, order.to(torch.int32).contiguous()
+
+
 class DeviceRadiusSubmap:
     """select_closest_points (:258-271) on the MI355X: a uniform grid over the map (cell size just above
     r), exact float64 radius test over the 27 neighbour cells (C ABI: sps_radius_*).  Returns, like the
@@ -166,14 +179,7 @@ class DeviceRadiusSubmap:
         self.device = torch.device(device)
         xyz = torch.as_tensor(np.ascontiguousarray(np.asarray(map_xyz)[:, :3], dtype=np.float64)).to(self.device)
         cell = self.radius * (1.0 + 1e-7)                   # >= r, so every hit lies in the 27 cells around the query
-        c = torch.floor(xyz / cell).to(torch.int64)
-        assert int(c.abs().max()) < (1 << 20) - 1, "map extent exceeds the radius grid"
-        keys = ((c[:, 2] + (1 << 20)) << 42) | ((c[:, 1] + (1 << 20)) << 21) | (c[:, 0] + (1 << 20))
-        skeys, order = torch.sort(keys, stable=True)        # grouped by cell, ascending map index inside a cell
-        ukeys, counts = torch.unique_consecutive(skeys, return_counts=True)
-        start = torch.zeros(len(ukeys) + 1, dtype=torch.int32, device=self.device)
-        start[1:] = torch.cumsum(counts, 0).to(torch.int32)
-        pts = order.to(torch.int32).contiguous()
+        ukeys, start, pts = radius_grid_cells(xyz, cell)
         with torch.cuda.device(self.device):
             self.stream = torch.cuda.current_stream().cuda_stream
             # the context that owns the grid's device copies (others attach to it: Context.radius_grid_attach)

@@ -1,0 +1,229 @@
+"""Scan-to-map localiser and the closed loop around a scan filter.
+
+In the reference's localisation experiment (c_ws/src/sps_filter/scripts/exp_pipeline/loc_exp_general.bash) the chosen
+filter publishes a filtered cloud, hdl_localization (an external package) registers it against the map, and the
+corrected pose goes back into the filter (sps_node.py reads it as odometry, sps_node_cvm.py:112-114 appends it to the
+constant-velocity pose list) and is recorded for evo_ape.
+
+``ScanToMapLocaliser`` plays the role of that package.  It is NOT a port of it -- no NDT, no UKF, no IMU -- but a
+deterministic point-to-point ICP on the device (C ABI: the "localiser" section of include/sps_hip.h; DESIGN.md
+"Localiser"): voxel-grid thinning of the kept rows, then ``iterations`` rounds of nearest-neighbour association within
+``max_distance`` (ties to the lowest map index) and a 6 x 6 Gauss-Newton step, all in float64 with fixed-order sums, so
+the same input gives the same bits.  ``submit()`` issues everything on the caller's current stream and never
+synchronises; ``PendingPose.result()`` is the one synchronisation.  A scan that misses the map is an ordinary result
+(status 2), never an error.
+
+``LocalisationLoop`` closes the loop for any of the seven filters of scripts/filter_sequence.py.
+"""
+from __future__ import annotations
+
+import math
+from dataclasses import dataclass
+
+import numpy as np
+import torch
+
+from . import _native
+from .baseline_filters import _device_of, _pose
+
+CONVERGED, EXHAUSTED, FEW_CORRESPONDENCES, SINGULAR = 0, 1, 2, 3
+STATUS_NAMES = {CONVERGED: "converged", EXHAUSTED: "iterations exhausted", FEW_CORRESPONDENCES: "too few correspondences",
+                SINGULAR: "singular system"}
+
+
+@dataclass
+class PoseResult:
+    pose: np.ndarray           # 4x4 float64; the initial guess, bit for bit, on status 2 and 3
+    status: int                # 0 converged, 1 iterations exhausted, 2 too few correspondences, 3 singular system
+    iterations: int            # iterations run
+    n_corr: int                # correspondences of the last iteration run
+    rmse: float                # sqrt(sum d^2 / n_corr) of the last iteration run, before its update (NaN without one)
+    trace: np.ndarray          # [iterations, 4] (n_corr, sum d^2, |v|, |omega|) per iteration run
+    normal: np.ndarray = None  # [iterations, 28] H (upper triangle), b, sum d^2 -- only with with_normal=True
+    n_points: int = 0          # scan points that entered the alignment (after thinning)
+
+    @property
+    def ok(self) -> bool:
+        return self.status in (CONVERGED, EXHAUSTED)
+
+
+class PendingPose:
+    """A localisation whose work has been issued; everything lives on the device until result()."""
+
+    def __init__(self, iters, with_normal, host, event, keep):
+        self._iters, self._with_normal, self._host, self._event, self._keep = iters, with_normal, host, event, keep
+
+    def result(self) -> PoseResult:
+        self._event.synchronize()                                    # the one host synchronisation
+        h = self._host.numpy()
+        K = self._iters
+        code, it, n_corr, _ = (int(x) for x in h[16:18].view(np.int32))
+        n_points = int(h[18:19].view(np.int32)[0])
+        trace = h[19:19 + 4 * K].reshape(K, 4)[:it].copy()
+        normal = h[19 + 4 * K:19 + 32 * K].reshape(K, 28)[:it].copy() if self._with_normal else None
+        rmse = math.sqrt(trace[-1, 1] / n_corr) if it and n_corr > 0 else float("nan")
+        return PoseResult(h[:16].reshape(4, 4).copy(), code, it, n_corr, rmse, trace, normal, n_points)
+
+
+class ScanToMapLocaliser:
+    """``ScanToMapLocaliser(map_points)(rows, count, T_init)`` -> PoseResult.  The map's uniform grid (cell size =
+    ``max_distance``) lives in a native context of the localiser's own, so the grid of the offline item path
+    (datasets.blt_dataset.DeviceRadiusSubmap, r = voxel size) is untouched.  ``capacity`` bounds the points that enter
+    the alignment: survivors of the thinning beyond it are dropped."""
+
+    def __init__(self, map_points, max_distance: float = 1.0, leaf: float = 0.2, iterations: int = 30,
+                 min_correspondences: int = 50, tol_t: float = 1e-4, tol_r: float = 1e-5, device="cuda",
+                 capacity: int = 1 << 16):
+        from .datasets.blt_dataset import radius_grid_cells
+        if not (math.isfinite(max_distance) and max_distance > 0 and math.isfinite(leaf) and leaf > 0):
+            raise ValueError("max_distance and leaf must be finite and > 0")
+        if iterations < 0 or capacity < 1:
+            raise ValueError("iterations must be >= 0 and capacity >= 1")
+        self.max_distance, self.leaf, self.iterations = float(max_distance), float(leaf), int(iterations)
+        self.min_correspondences, self.tol_t, self.tol_r = int(min_correspondences), float(tol_t), float(tol_r)
+        self.capacity = int(capacity)
+        self.device = _device_of(device)
+        mp = map_points.detach().cpu().numpy() if torch.is_tensor(map_points) else np.asarray(map_points)
+        xyz = torch.as_tensor(np.ascontiguousarray(mp[:, :3], dtype=np.float64)).to(self.device)
+        self.n_map = len(xyz)
+        with torch.cuda.device(self.device):
+            self.stream = torch.cuda.current_stream()
+            self.ctx = _native.Context(self.device.index)
+            if self.n_map:
+                keys, start, pts = radius_grid_cells(xyz, self.max_distance)
+                self.ctx.radius_grid_upload(keys.contiguous().data_ptr(), start.data_ptr(), pts.data_ptr(), xyz.data_ptr(),
+                                            len(keys), self.n_map, self.max_distance, self.max_distance, self.stream.cuda_stream)
+            else:
+                self.ctx.radius_grid_upload(None, None, None, None, 0, 0, self.max_distance, self.max_distance,
+                                            self.stream.cuda_stream)
+            self._pts = torch.empty((self.capacity, 3), dtype=torch.float64, device=self.device)
+            self._align_scratch = torch.empty(_native.lib.sps_loc_align_scratch(self.capacity), dtype=torch.uint8, device=self.device)
+            self._ds_scratch, self._ds_rows = None, -1
+
+    def _downsample_scratch(self, n_max):
+        if n_max > self._ds_rows:                                    # grows with the largest scan seen (stream-ordered reuse)
+            rows = max(n_max, 1024)
+            self._ds_scratch = torch.empty(_native.lib.sps_loc_downsample_scratch(rows), dtype=torch.uint8, device=self.device)
+            self._ds_rows = rows
+        return self._ds_scratch
+
+    @torch.no_grad()
+    def submit(self, rows, count, T_init, with_normal: bool = False, iterations: int = None) -> PendingPose:
+        """rows: device tensor [n_max, >= 3] (float32; other dtypes are converted); count: an int or a device int32 tensor
+        holding the number of valid rows; T_init: 4x4.  Issued on the current stream."""
+        if not (torch.is_tensor(rows) and rows.is_cuda and rows.device == self.device):
+            raise TypeError("ScanToMapLocaliser.submit needs a tensor on the localiser's device")
+        if rows.dim() != 2 or rows.shape[1] < 3:
+            raise ValueError(f"rows must be [n, >=3], got {tuple(rows.shape)}")
+        T = _pose(T_init)
+        if T is None or not np.isfinite(T).all():
+            raise ValueError("T_init must be a finite 4x4 matrix")
+        if rows.dtype != torch.float32:
+            rows = rows.to(torch.float32)
+        if rows.shape[0] and rows.stride(1) != 1:
+            rows = rows.contiguous()
+        n_max, dev = rows.shape[0], self.device
+        K = self.iterations if iterations is None else int(iterations)
+        with torch.cuda.device(dev):
+            st = torch.cuda.current_stream()
+            s = st.cuda_stream
+            if torch.is_tensor(count):
+                if count.dtype != torch.int32 or count.device != dev or count.numel() < 1:
+                    raise TypeError("count must be an int or an int32 tensor on the localiser's device")
+                n_dev = count
+            else:
+                if not 0 <= int(count) <= n_max:
+                    raise ValueError(f"count must be in [0, {n_max}], got {count}")
+                n_dev = torch.full((1,), int(count), dtype=torch.int32, device=dev)
+            # one float64 buffer per frame: T_out[16] | status int32[4] | n_points int32 (+ pad) | trace[K][4] | normal[K][28]
+            out = torch.zeros(19 + 32 * K if with_normal else 19 + 4 * K, dtype=torch.float64, device=dev)
+            base = out.data_ptr()
+            scratch = self._downsample_scratch(n_max)
+            self.ctx.loc_downsample(rows.data_ptr() if n_max else None, rows.stride(0) if n_max else 3, n_max,
+                                    n_dev.data_ptr(), self.leaf, self._pts.data_ptr(), self.capacity, base + 18 * 8,
+                                    scratch.data_ptr(), s)
+            self.ctx.loc_align(self._pts.data_ptr(), base + 18 * 8, self.capacity, T, K, self.min_correspondences,
+                               self.tol_t, self.tol_r, base, base + 16 * 8, base + 19 * 8 if K else None,
+                               base + (19 + 4 * K) * 8 if with_normal and K else None, self._align_scratch.data_ptr(), s)
+            host = torch.empty(out.numel(), dtype=torch.float64).pin_memory()
+            host.copy_(out, non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record(st)
+        return PendingPose(K, with_normal, host, ev, (rows, n_dev, out))
+
+    def submit_filtered(self, pending, T_init, **kw) -> PendingPose:
+        """The kept rows of a pending SPSFilter / SPSCVMFilter frame and their device count go straight in, without the
+        frame's result()."""
+        return self.submit(pending._filtered, pending.count_dev, T_init, **kw)
+
+    def __call__(self, rows, count, T_init, **kw) -> PoseResult:
+        return self.submit(rows, count, T_init, **kw).result()
+
+
+@dataclass
+class LoopStep:
+    filter_result: object      # what the filter's result() returned
+    pose_result: PoseResult
+    guess: np.ndarray          # the pose the frame started from
+    pose: np.ndarray           # the corrected pose handed on (the guess when flagged)
+    flagged: bool              # the localiser reported status 2 or 3
+
+
+class LocalisationLoop:
+    """filter -> localiser -> pose back into the filter, one frame per ``step(scan)``:
+
+      1. the guess: the loop's own constant-velocity prediction once its model holds four corrected poses, before that
+         the last corrected pose, before that ``initial_pose`` (the loop's model holds corrected poses only: it starts
+         without the leading identity of the node's list, so its first prediction averages three real motions);
+      2. the filter: filters that take a pose get the guess, SPSCVMFilter predicts for itself as its node does,
+         LTSFilter takes none;
+      3. the localiser registers the filter's kept rows (sensor frame, as received) from the guess;
+      4. the corrected pose goes to the loop's model and to the filter's ``add_pose`` where it has one; on status 2 or 3
+         the guess is taken as the corrected pose and the step is flagged.
+
+    One host synchronisation per frame where the filter's pending frame exposes its device rows (``_filtered`` and
+    ``count_dev``: SPSFilter, SPSCVMFilter), two otherwise."""
+
+    def __init__(self, filter, localiser, initial_pose):
+        from .sps_filters import ConstantVelocityModel
+        self.filter, self.localiser = filter, localiser
+        self.initial_pose = np.array(_pose(initial_pose), dtype=np.float64)
+        self.model = ConstantVelocityModel()
+        self.model.poses = []                                        # corrected poses only
+        self.poses = []                                              # the corrected pose of every frame
+
+    def guess(self) -> np.ndarray:
+        if len(self.model.poses) >= 4:
+            return self.model.predict()
+        if self.model.poses:
+            return self.model.poses[-1].copy()
+        return self.initial_pose.copy()
+
+    def _submit_filter(self, scan, guess):
+        f = self.filter
+        if hasattr(f, "add_pose"):                                   # SPSCVMFilter: the pose is its own prediction
+            return f.submit(scan)
+        if type(f).__name__ == "LTSFilter" or getattr(f, "takes_pose", True) is False:
+            if not torch.is_tensor(scan):
+                scan = torch.from_numpy(np.ascontiguousarray(np.asarray(scan)[:, :4], dtype=np.float32)).to(self.localiser.device)
+            return f.submit(scan)
+        return f.submit(scan, guess)
+
+    def step(self, scan) -> LoopStep:
+        guess = self.guess()
+        pend = self._submit_filter(scan, guess)
+        if hasattr(pend, "count_dev") and hasattr(pend, "_filtered"):
+            pose_pend = self.localiser.submit_filtered(pend, guess)  # no synchronisation between filter and localiser
+            fres = pend.result()
+            pres = pose_pend.result()
+        else:
+            fres = pend.result()
+            kept = fres.filtered
+            pres = self.localiser.submit(kept, len(kept), guess).result()
+        flagged = pres.status in (FEW_CORRESPONDENCES, SINGULAR)
+        pose = guess if flagged else pres.pose
+        self.model.add_pose(pose)
+        if hasattr(self.filter, "add_pose"):
+            self.filter.add_pose(pose)
+        self.poses.append(np.array(pose, dtype=np.float64))
+        return LoopStep(fres, pres, guess, self.poses[-1], flagged)

@@ -92,6 +92,12 @@ class PendingSPS:
         self._scores, self._labels, self._filtered, self._cloud_tr, self._submap = scores, labels, filtered, cloud_tr, submap
         self._counts_host, self._sums_host, self._ev, self._stream, self._t0 = counts_host, sums_host, ev, stream, t0
 
+    @property
+    def count_dev(self) -> torch.Tensor:
+        """int32 [1] on the device: the number of kept rows, valid in stream order (for a stage that follows the filter
+        without waiting for result(), e.g. localiser.ScanToMapLocaliser.submit_filtered)."""
+        return self._keep[3][3:4]
+
     def result(self) -> SPSResult:
         self._stream.synchronize()                                   # the one host synchronisation of the frame
         self._o.ctx.check_errors(self._stream.cuda_stream)           # SPS_ERR_RANGE etc.
