@@ -369,6 +369,10 @@ int sps_get_nbr(sps_ctx *ctx, int which, int32_t *nbr_dev);
  * the RULEBOOK the pair-exact convolutions read; *n_entries (may be NULL) = number of pairs it holds (malformed or duplicate
  * entries fail the call). */
 int sps_get_kernel_map(sps_ctx *ctx, int which, int source, int32_t *out_dev, int64_t *n_entries);
+/* Chunks of the rulebook of level `which` (a pair-exact level) per 64-row supertile and time slice, int32
+ * [n_supertiles][3] on the host: what the pair-exact convolutions execute (one chunk = 16 pair slots).  chunks_host may be
+ * NULL (only *n_supertiles is set). */
+int sps_get_rulebook_chunks(sps_ctx *ctx, int which, int32_t *chunks_host, int64_t *n_supertiles);
 /* Per-voxel logits of the last forward, float32 [V_0]. */
 int sps_get_logits(sps_ctx *ctx, float *logits_dev);
 /* Named intermediate feature maps: "out_p1","block1".."block8"; copies [V,C] row-major

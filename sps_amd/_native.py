@@ -107,6 +107,7 @@ def _load() -> C.CDLL:
         "sps_get_tile_masks": (i32, [vp, i32, vp, C.POINTER(i64)]),
         "sps_get_nbr": (i32, [vp, i32, vp]),
         "sps_get_kernel_map": (i32, [vp, i32, i32, vp, C.POINTER(i64)]),
+        "sps_get_rulebook_chunks": (i32, [vp, i32, vp, C.POINTER(i64)]),
         "sps_get_logits": (i32, [vp, vp]),
         "sps_get_feature": (i32, [vp, C.c_char_p, vp, C.POINTER(i64), C.POINTER(i64)]),
         "sps_lts_num_tensors": (i32, []),
@@ -150,7 +151,7 @@ EXPORTS = ["sps_last_error", "sps_version", "sps_ctx_create", "sps_ctx_destroy",
            "sps_submap_voxel", "sps_submap_voxel_ijk", "sps_transform_points", "sps_filter_prepare", "sps_forward_n",
            "sps_compact_stable", "sps_filter_finish", "sps_train_forward", "sps_train_backward", "sps_train_generation", "sps_train_backward_at", "sps_scan_mse", "sps_scan_mse_backward", "sps_radius_grid_upload", "sps_radius_count",
            "sps_radius_fill", "sps_radius_grid_attach", "sps_radius_item", "sps_forward_metrics_n", "sps_level_counts", "sps_get_voxels",
-           "sps_get_inverse", "sps_get_parent", "sps_get_map_pairs", "sps_get_tile_masks", "sps_get_nbr", "sps_get_kernel_map", "sps_get_logits", "sps_get_feature",
+           "sps_get_inverse", "sps_get_parent", "sps_get_map_pairs", "sps_get_tile_masks", "sps_get_nbr", "sps_get_kernel_map", "sps_get_rulebook_chunks", "sps_get_logits", "sps_get_feature",
            "sps_lts_num_tensors", "sps_lts_tensor_info", "sps_lts_numel", "sps_lts_lidar_info", "sps_lts_create",
            "sps_lts_destroy", "sps_lts_project", "sps_lts_forward", "sps_lts_check", "sps_lts_tap",
            "sps_forward_head_n", "sps_transform_rows", "sps_transform_points_n", "sps_radius_crop", "sps_label_filter",
@@ -443,6 +444,16 @@ class Context:
         n = C.c_int64()
         check(lib.sps_get_kernel_map(self.handle, which, source, out.data_ptr(), C.byref(n)))
         return (out, n.value) if source == 1 else out
+
+    def rulebook_chunks(self, which: int):
+        """int32 numpy [supertiles, 3]: 16-slot chunks of the level's rulebook per 64-row supertile and time slice."""
+        import numpy as np
+        n = C.c_int64()
+        check(lib.sps_get_rulebook_chunks(self.handle, which, None, C.byref(n)))
+        out = np.zeros((n.value, 3), np.int32)
+        if n.value:
+            check(lib.sps_get_rulebook_chunks(self.handle, which, out.ctypes.data, C.byref(n)))
+        return out
 
     def map_pairs(self, which: int):
         out = (C.c_int64 * 125)()

@@ -595,6 +595,17 @@ __global__ __launch_bounds__((S == 8 ? 512 : 256) * CG, MINW) void k_conv(ConvAr
 //   Rulebook entry: (input row << 7) | output row inside the supertile; PAD entries (row 2^23 | 64) gather zeros (OOR) into a
 //   dummy accumulator row.  Per supertile: three segments (time slices), each with its chunk count, the offset of every
 //   chunk (1 byte) and 16 entries per chunk (map_kernels.inc.h).
+//   HALF (C_out = 8 layers of an 8-pair level: level 0): with C_out = 8 the rows co = 8..15 of D^T are zero padding, half
+//   of every MFMA.  The A operand (weights) is per ROW, so rows 8..15 hold the 8 channels of a SECOND offset: the rulebook
+//   pads an offset's pairs to 8, pairs 0..7 of a chunk belong to offset k0 and pairs 8..15 to offset k1 (one byte each in
+//   the offset table), and the two diagonal 8 x 8 blocks of D^T are the two products -- lanes (q < 2, n < 8) and
+//   (q >= 2, n >= 8) accumulate theirs, the off-diagonal lanes take the dummy slots.  An output row may occur in BOTH
+//   halves of a chunk (once per offset), so the two halves must not meet in one read-add-write: the accumulator row is 16
+//   floats wide, the first offset's channels in floats 0..7 and the second's in floats 8..15 (lane (q, n) -> floats 4 q ..,
+//   as for C_out = 16), and the epilogue adds the two.  The per-lane dummy slots are the four padding floats of the 64 rows
+//   (stride 20), so a wave's accumulator is 5.1 KB against 4 KB and seven workgroups still share a CU.  A chunk costs what it
+//   cost (one gather, one weight wave-load, the same MFMAs, 32 accumulating lanes) and padding drops from 16 to 8 pairs per
+//   (supertile, offset): 12 % fewer chunks at level 0.
 typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 
 #if defined(SPS_WAVE_TRACE)
@@ -611,14 +622,16 @@ struct PxOperands {  // gathered rows + weight fragments of a group of G chunks
 };
 // UP: the transposed convolution that follows the layer (C_out = 16 -> <= 16 channels, block7.conv2 -> convtr7p2s2) runs in
 // the epilogue on the supertile's 64 finished rows, which stay in the first accumulator (see the epilogue).
-template <int NW, int CIN, bool C8, bool DS, bool FIN, int MINW, bool UP = false>
+template <int NW, int CIN, bool C8, bool DS, bool FIN, int MINW, bool UP = false, bool HALF = false>
 __global__ __launch_bounds__(NW * 64, MINW) void k_conv_px(ConvArgs a) {
+  static_assert(!HALF || C8, "two offsets per chunk: the 8 output channels of each fill half of the MFMA rows");
   static_assert(!UP || (!C8 && !FIN && NW == 4), "fused transposed convolution: 16-channel rows, four waves");
-  constexpr int AST = C8 ? 12 : 20;    // floats per accumulator row: 16-byte aligned, strides 48 / 80 B spread the banks
+  constexpr int AST = (C8 && !HALF) ? 12 : 20;  // floats per accumulator row: 16-byte aligned, strides 48 / 80 B spread the banks
   // + dummy slots (PAD entries; C_out <= 8: also the lane groups 2, 3 that hold the zero-padded channels 8..15).  C8: one
   // 16-byte slot PER LANE, so that every lane runs the same branch-free read-add-write (round 4: the exec-masked update cost
   // two mask regions and a branch per chunk, and the kernel is bound by instruction issue)
-  constexpr int ACCN = 64 * AST + (C8 ? 256 : 16);
+  // HALF: the per-lane slot is floats 16..19 of row `lane`
+  constexpr int ACCN = 64 * AST + ((C8 && !HALF) ? 256 : 16);
   constexpr bool W128 = CIN >= 16, W64 = CIN != 16;  // 16-byte part (channels 0..15), 8-byte part (8 channels)
   constexpr uint32_t OFF64 = CIN == 24 ? 64u : 0u;   // byte offset of the 8-byte part inside a row
   constexpr uint32_t U64 = CIN == 24 ? 4u : 0u;      // first weight unit of the 8-byte part
@@ -656,14 +669,18 @@ __global__ __launch_bounds__(NW * 64, MINW) void k_conv_px(ConvArgs a) {
   // weight fragment offsets inside an offset's block: unit q / channels 2q, 2q+1 of the 8-byte part, column n.  C_out <= 8: the
   // columns 8..15 are zero padding -- their lanes ask for an out-of-range address (zeros, no cache access)
   // (bit 31 set: the offset stays beyond the buffer after the offset's base is added)
-  const uint32_t wpad = (C8 && n >= 8) ? 0x80000000u : 0u;
-  const uint32_t wk128 = ((uint32_t)n * 16u + (uint32_t)q * 256u) | wpad;
-  const uint32_t wk64 = ((uint32_t)n * 16u + (U64 + (uint32_t)(q >> 1)) * 256u + (uint32_t)(q & 1) * 8u) | wpad;
+  // HALF: the lanes n >= 8 load column n - 8 of the chunk's second offset instead (issue())
+  const uint32_t wpad = (C8 && !HALF && n >= 8) ? 0x80000000u : 0u;
+  const uint32_t wcol = (uint32_t)(HALF ? n & 7 : n) * 16u;
+  const uint32_t wk128 = (wcol + (uint32_t)q * 256u) | wpad;
+  const uint32_t wk64 = (wcol + (U64 + (uint32_t)(q >> 1)) * 256u + (uint32_t)(q & 1) * 8u) | wpad;
   const uint32_t ga128 = (uint32_t)q * 16u, ga64 = OFF64 + (uint32_t)q * 8u;
   const uint32_t kwbytes = (uint32_t)a.upk * 256u;  // weights of one offset
   float *acc = acc_s[wave];
-  const bool rmw = !C8 || q < 2;  // C_out <= 8: lane groups 2, 3 hold the zero-padded channels 8..15
-  const uint32_t accmul = rmw ? (uint32_t)AST : 0u, accadd = rmw ? 4u * (uint32_t)q : (uint32_t)(64 * AST + 4 * lane);
+  const bool chan = !C8 || q < 2;  // C_out <= 8: lane groups 2, 3 hold the zero-padded channels 8..15
+  // HALF: D^T rows 0..7 x pairs 0..7 (first offset) and rows 8..15 x pairs 8..15 (second offset) are the products
+  const bool rmw = HALF ? (q < 2) == (n < 8) : chan;
+  const uint32_t accmul = rmw ? (uint32_t)AST : 0u, accadd = rmw ? 4u * (uint32_t)q : (uint32_t)(HALF ? lane * AST + 16 : 64 * AST + 4 * lane);
 
   // epilogue roles: NW threads per row, CPT consecutive columns each
   constexpr int EP_TPR = NW, EP_CPT = (C8 ? 8 : 16) / EP_TPR;
@@ -722,7 +739,7 @@ __global__ __launch_bounds__(NW * 64, MINW) void k_conv_px(ConvArgs a) {
         d = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(vb.z), __uint_as_float(va.z), d, 0, 0, 0);
         d = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(vb.w), __uint_as_float(va.w), d, 0, 0, 0);
       }
-      if (rmw) *reinterpret_cast<floatx4 *>(acc + (16 * wave + n) * AST + 4 * q) = d;  // the row is still zero
+      if (chan) *reinterpret_cast<floatx4 *>(acc + (16 * wave + n) * AST + 4 * q) = d;  // the row is still zero
     }
     PX_STAMP(2);
     PX_STAMP(3);
@@ -741,11 +758,18 @@ __global__ __launch_bounds__(NW * 64, MINW) void k_conv_px(ConvArgs a) {
       const bool on = t < nbw && c < nch;
       ev = __builtin_amdgcn_raw_buffer_load_b32(rsE, on ? (uint32_t)((seg * PX_SEG_CH + lc) * 16 + n) * 4u : OOR, 0, 0);
       ev = on ? ev : PX_PAD;  // chunks past the end of the list: padding (decided once per block, not per chunk)
+      if constexpr (HALF) {
+        // every lane fetches the offset byte of ITS half (n < 8: first, n >= 8: second) of its lane group's chunk: the byte
+        // offset of the weights then travels with the rulebook word, through the same ds_bpermute pattern (issue())
+        kv = (uint32_t)__builtin_amdgcn_raw_buffer_load_b8(rsK, on ? (uint32_t)(seg * PX_KSEG + 2 * lc + (n >> 3)) : OOR, 0, 0);
+        kv = on ? kv * kwbytes : 0x80000000u;
+        return;
+      }
       const int ck = 4 * (wave + NW * t) + lane;  // lanes 0..3: the block's four offset bytes
       const int segk = ck < n0 ? 0 : (ck < n01 ? 1 : 2);
       const int lck = ck - (ck < n0 ? 0 : (ck < n01 ? n0 : n01));
       const bool onk = lane < 4 && t < nbw && ck < nch;
-      kv = (uint32_t)__builtin_amdgcn_raw_buffer_load_b8(rsK, onk ? (uint32_t)(segk * 112 + lck) : OOR, 0, 0);
+      kv = (uint32_t)__builtin_amdgcn_raw_buffer_load_b8(rsK, onk ? (uint32_t)(segk * PX_KSEG + lck) : OOR, 0, 0);
       kv = onk ? kv * kwbytes : 0x80000000u;  // byte offset of the chunk's weights (out of range for a chunk that is not there)
     };
     auto issue = [&](PxOperands<1> &r, uint32_t ev, uint32_t kv, int t, int j) {
@@ -753,7 +777,10 @@ __global__ __launch_bounds__(NW * 64, MINW) void k_conv_px(ConvArgs a) {
       // no test for padding or for "is there a chunk": a PAD entry's row 2^23 is out of range by construction (zeros), its
       // accumulator row 64 is the dummy, and fetch() turned chunks past the end into PAD entries / out-of-range weights
       r.e[0] = (uint32_t)__shfl((int)ev, 16 * j + n, 64);
-      const uint32_t wk = (uint32_t)__builtin_amdgcn_readlane((int)kv, j);
+      // HALF: the weights of the first offset for the lanes n < 8, of the second for n >= 8 -- a per-lane value, moved like
+      // the rulebook word (two readlanes and a select between two scalars cost four vector instructions per chunk more; a
+      // readlane inside an arm of `?:` even an exec-masked block with a branch)
+      const uint32_t wk = HALF ? (uint32_t)__shfl((int)kv, 16 * j + n, 64) : (uint32_t)__builtin_amdgcn_readlane((int)kv, j);
       const uint32_t ioff = __umul24(r.e[0] >> 7, ldi4);  // (rows <= 2^23, row bytes < 2^9)
       if (W128) {
         if (QUAD) {
@@ -776,7 +803,8 @@ __global__ __launch_bounds__(NW * 64, MINW) void k_conv_px(ConvArgs a) {
     };
     auto compute = [&](const PxOperands<1> &r) {
       // every lane updates SOME slot: row (e & 127) of the accumulator -- 64 = the dummy row of a PAD entry -- at its four
-      // channels; C_out <= 8: the lane groups 2, 3 (zero-padded channels) their own dummy slot (row multiplier 0)
+      // channels; C_out <= 8: the lane groups 2, 3 (zero-padded channels; HALF: the off-diagonal lanes) their own dummy slot
+      // (row multiplier 0)
       floatx4 *ap = reinterpret_cast<floatx4 *>(acc + __umul24(r.e[0] & 127u, accmul) + accadd);
       floatx4 cur = *ap;
       floatx4 d = floatx4{0.f, 0.f, 0.f, 0.f};
@@ -842,8 +870,12 @@ __global__ __launch_bounds__(NW * 64, MINW) void k_conv_px(ConvArgs a) {
       for (int i = 0; i < EP_CPT; ++i) {
         const int col = c0 + i;
         float sum = acc_s[0][rr * AST + col];
+        if constexpr (HALF) sum += acc_s[0][rr * AST + col + 8];  // (the second offsets of the chunks)
 #pragma unroll
-        for (int w = 1; w < NW; ++w) sum += acc_s[w][rr * AST + col];
+        for (int w = 1; w < NW; ++w) {
+          sum += acc_s[w][rr * AST + col];
+          if constexpr (HALF) sum += acc_s[w][rr * AST + col + 8];
+        }
         const bool cv = col < a.cout;
         float y = 0.f;
         if (cv) {

@@ -49,14 +49,25 @@ struct MapsArgs {
 };
 
 // Rulebook layout per SUPERTILE of 64 output rows: three segments (one per time slice dt = -1, 0, +1) of up to PX_SEG_CH
-// chunks; a chunk = 16 entries (input row << 7 | output row inside the supertile, 0..63) of ONE offset, padded with PX_PAD.
+// chunks; a chunk = 16 entries (input row << 7 | output row inside the supertile, 0..63), padded with PX_PAD.
+//   16-pair levels: a chunk holds pairs of ONE offset (the pairs of an offset are padded to a multiple of 16); the chunk ->
+//     offset table has one byte per chunk.
+//   8-pair levels (PX_HALF_LEVELS: level 0, whose layers all have C_out = 8): the pairs of an offset are padded to a multiple
+//     of 8 -- a HALF-CHUNK -- and the half-chunks of a segment follow each other without gaps: chunk c = halves 2c, 2c + 1,
+//     which may belong to two offsets (k_conv_px<..., HALF> multiplies the two with one MFMA set).  The table has one byte
+//     per half-chunk.  A segment with an odd number of halves ends with one all-PX_PAD half that repeats the offset byte
+//     before it, so segments still end on whole chunks and rb_cnt counts whole chunks at every level.
 // PX_PAD = input row 2^23 (rows < 2^23: its byte offset lies beyond any feature buffer, the gather returns zeros) and
 // output row 64 (the dummy accumulator row): k_conv_px needs NO test for padding (round 4).
 constexpr uint32_t PX_PAD = (1u << 30) | 64u;
 static_assert(SPS_MAX_POINTS <= (1 << 23), "PX_PAD's input row 2^23 must lie beyond every feature buffer (row capacity <= SPS_MAX_POINTS)");
 constexpr int PX_SEG_CH = 108;   // chunks of a segment: 27 offsets x (64 rows / 16)
 constexpr int PX_CH_MAX = 324;   // chunks of a supertile
-constexpr int PX_KSTRIDE = 336;  // bytes of the chunk -> offset table of a supertile (3 x 112)
+constexpr int PX_KSEG = 224;     // bytes of a segment of the (half-)chunk -> offset table: up to 27 x 8 = 216 half-chunks
+constexpr int PX_KSTRIDE = 3 * PX_KSEG;  // bytes of the table of a supertile
+constexpr int PX_HALF_LEVELS = 1;  // bit l: level l's rulebook is padded per 8 pairs (only C_out = 8 layers may read it)
+constexpr bool px_half_level(int l) { return (PX_HALF_LEVELS >> l) & 1; }
+static_assert(PX_KSEG >= 2 * PX_SEG_CH && PX_KSEG % 4 == 0, "one offset byte per half-chunk");
 constexpr int PX_LEVELS = 3;     // levels that may run pair-exact (0..2)
 
 __device__ inline int level_of_chunk(const MapsArgs &a, int first_level, int &local, int bid) {
@@ -112,13 +123,16 @@ __device__ inline void lookup_run(const LevelView &L, int u, int dy, int dz, int
 // popcounts behind an exec-masked branch per offset; an offset no row of the wave has skips the rulebook code; and the
 // chunk -> offset table is written by lanes 0..26 at the end (lane j = offset j: first chunk and chunk count collected with
 // one compare-and-select per offset) instead of two compare-and-add pairs per offset and lane.
-template <bool TM, bool RB>
+// GR: pairs per padding granule of the level's rulebook (16 = a chunk, 8 = a half-chunk).
+template <bool TM, bool RB, int GR = 16>
 __device__ inline void build_nbr3_t(const MapsArgs &a, int l, int local, int nchunks, int slice) {
   const int n = a.counts[l];
   const LevelView L = a.L[l];
   int *__restrict__ nbr = a.nbr3[l];
   uint32_t *__restrict__ tmask = a.tm3[l];
   const int64_t ldn = a.ldn[l];
+  static_assert(GR == 16 || GR == 8, "rulebook padding granule: a chunk or a half-chunk");
+  constexpr int GM = GR - 1, GS = GR == 16 ? 4 : 3;
   const int lane = threadIdx.x & 63;
   const int nround = (n + 63) & ~63;  // whole waves take part in the ballots
   // rulebook (pair-exact layers): a wave = the 64 rows of one supertile; the pairs of each of the slice's 27 offsets are
@@ -185,10 +199,10 @@ __device__ inline void build_nbr3_t(const MapsArgs &a, int l, int local, int nch
       txm[d] = (1u << txl[d]) - 1u;
     }
     uint32_t m = 0u;
-    int cb = 0;            // chunks written to the segment so far (wave-uniform)
-    uint32_t kinfo = 0u;   // lane j < 27: first chunk | chunk count << 16 of offset j of this slice
+    int cb = 0;            // granules (chunks / half-chunks) written to the segment so far (wave-uniform)
+    uint32_t kinfo = 0u;   // lane j < 27: first granule | granule count << 16 of offset j of this slice
     uint32_t *__restrict__ eb = RB ? rbe + ((size_t)(u >> 6) * PX_CH_MAX + (size_t)slice * PX_SEG_CH) * 16 : nullptr;
-    unsigned char *__restrict__ kb = RB ? rbk + (size_t)(u >> 6) * PX_KSTRIDE + slice * 112 : nullptr;
+    unsigned char *__restrict__ kb = RB ? rbk + (size_t)(u >> 6) * PX_KSTRIDE + slice * PX_KSEG : nullptr;
     // (all 27 offsets unrolled: 125 VGPRs + spilled SGPRs, 29 us instead of 22.  Measured and dropped as well: 32-bit halves of
     //  the masks + the per-tile bits kept in scalar registers -- fewer VALU instructions, 98 VGPRs, 27 us)
 #pragma unroll 1
@@ -232,27 +246,36 @@ __device__ inline void build_nbr3_t(const MapsArgs &a, int l, int local, int nch
           }
           if constexpr (RB) {
             if (bal != 0ull) {  // wave-uniform: an offset no row of the supertile has costs nothing further
-              // ONE store per offset: lanes with a pair write their entry at its compacted slot, the first (-cnt & 15) lanes
-              // without one write the padding behind the entries (there are always enough: cnt > 48 => 64 - cnt = the padding)
+              // ONE store per offset: lanes with a pair write their entry at its compacted slot, the first (-cnt & GM) lanes
+              // without one write the padding behind the entries (there are always enough: cnt > 64 - GR => 64 - cnt = the padding)
               const int cnt = __popcll(bal);
               // lanes below this one WITH a pair: two v_mbcnt (no lane mask, no branch); those WITHOUT one are the rest of them
               const int below = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal, 0u));
               const int pos = present ? below : cnt + lane - below;
-              if ((present || pos < ((cnt + 15) & ~15)) && !(SPS_ABLATE_FE & 64)) eb[cb * 16 + pos] = present ? ((uint32_t)row << 7) | (uint32_t)lane : PX_PAD;
-              const int nch = (cnt + 15) >> 4;
-              kinfo = lane == j ? (uint32_t)cb | ((uint32_t)nch << 16) : kinfo;  // (lane j keeps its offset's first chunk and chunk count)
-              cb += nch;
+              if ((present || pos < ((cnt + GM) & ~GM)) && !(SPS_ABLATE_FE & 64)) eb[cb * GR + pos] = present ? ((uint32_t)row << 7) | (uint32_t)lane : PX_PAD;
+              const int ng = (cnt + GM) >> GS;
+              kinfo = lane == j ? (uint32_t)cb | ((uint32_t)ng << 16) : kinfo;  // (lane j keeps its offset's first granule and granule count)
+              cb += ng;
             }
           }
         }
       }
     }
     if constexpr (RB) {
-      // chunk -> offset table: lane j < 27 writes the byte of its offset to the offset's 0..4 chunks
-      const int first = (int)(kinfo & 0xFFFFu), nch = lane < 27 ? (int)(kinfo >> 16) : 0;
+      // (half-)chunk -> offset table: lane j < 27 writes the byte of its offset to the offset's 0..64 / GR granules
+      const int first = (int)(kinfo & 0xFFFFu), ng = lane < 27 ? (int)(kinfo >> 16) : 0;
 #pragma unroll
-      for (int i = 0; i < 4; ++i)
-        if (i < nch) kb[first + i] = (unsigned char)(27 * slice + lane);
+      for (int i = 0; i < 64 / GR; ++i)
+        if (i < ng) kb[first + i] = (unsigned char)(27 * slice + lane);
+      if constexpr (GR == 8) {
+        // the segment ends on a whole chunk: an odd half count gets one all-PAD half (<= 215 halves before it: inside the
+        // segment), whose offset byte repeats the last one -- written by the lane of the offset that ends the list
+        if (cb & 1) {
+          if (lane < 8 && !(SPS_ABLATE_FE & 64)) eb[cb * 8 + lane] = PX_PAD;
+          if (ng > 0 && first + ng == cb) kb[cb] = (unsigned char)(27 * slice + lane);
+        }
+        cb = (cb + 1) >> 1;  // rb_cnt counts whole chunks
+      }
       if (lane == 0) rbc[(size_t)(u >> 6) * 4 + slice] = (SPS_ABLATE_FE & 64) ? 0 : cb;  // (ablation bit 6: nothing was stored: no chunks to read)
     }
     if (TM && (lane & 15) == 0 && ok) tmask[(size_t)(u >> 4) * 4 + slice] = m;
@@ -266,7 +289,11 @@ __device__ inline void build_nbr3(const MapsArgs &a, int bid, int slice) {
   // tile masks say which entries of the neighbour table were written: a level that keeps only the rulebook (inference-only
   // context, pair-exact layers) needs neither (round 5: five vector instructions per offset less for 87 % of the rows)
   const bool rb = a.rb_e[l] != nullptr, tm = a.nbr3[l] != nullptr || !rb;
-  if (rb && tm) build_nbr3_t<true, true>(a, l, local, nchunks, slice);
+  if (rb && px_half_level(l)) {  // (the 8-pair level: level 0)
+    if (tm) build_nbr3_t<true, true, 8>(a, l, local, nchunks, slice);
+    else build_nbr3_t<false, true, 8>(a, l, local, nchunks, slice);
+  }
+  else if (rb && tm) build_nbr3_t<true, true>(a, l, local, nchunks, slice);
   else if (rb) build_nbr3_t<false, true>(a, l, local, nchunks, slice);
   else build_nbr3_t<true, false>(a, l, local, nchunks, slice);
 }
@@ -352,7 +379,7 @@ __device__ inline void build_stride_maps(const MapsArgs &a, int bid) {
 #if defined(SPS_FE_TRACE)  // DIAGNOSTIC build only (tools/fe_trace.py)
 __device__ unsigned long long g_maps_trace[2 * 16384];
 #endif
-__global__ __launch_bounds__(256) void k_maps(MapsArgs ma, int nchunk, int n_nbr) {
+__global__ __launch_bounds__(256, 6) void k_maps(MapsArgs ma, int nchunk, int n_nbr) {
   if (ma.counts[ABORT]) return;
   const int bid = (int)blockIdx.x;
 #if defined(SPS_FE_TRACE)
@@ -372,10 +399,11 @@ __global__ __launch_bounds__(256) void k_maps(MapsArgs ma, int nchunk, int n_nbr
 }
 
 // pairs per offset from the rulebook (inference-only contexts keep no neighbour table at the pair-exact levels):
-// one thread per chunk slot of every (supertile, time slice) segment
+// one thread per chunk slot of every (supertile, time slice) segment.  half: the level's rulebook is padded per 8 pairs
+// (one offset byte per half-chunk)
 __global__ void k_count_pairs_rb(const uint32_t *__restrict__ rb_e, const unsigned char *__restrict__ rb_k,
                                  const int *__restrict__ rb_cnt, const int *__restrict__ n_ptr,
-                                 unsigned long long *__restrict__ pairs) {
+                                 unsigned long long *__restrict__ pairs, int half) {
   const int nst = (*n_ptr + 63) >> 6;
   const int64_t total = (int64_t)nst * 3 * PX_SEG_CH;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
@@ -383,9 +411,15 @@ __global__ void k_count_pairs_rb(const uint32_t *__restrict__ rb_e, const unsign
     const int seg = r / PX_SEG_CH, lc = r - seg * PX_SEG_CH;
     if (lc >= rb_cnt[(size_t)st * 4 + seg]) continue;
     const uint32_t *e = rb_e + ((size_t)st * PX_CH_MAX + (size_t)seg * PX_SEG_CH + lc) * 16;
-    int c = 0;
-    for (int j = 0; j < 16; ++j) c += e[j] != PX_PAD;
-    atomicAdd(&pairs[rb_k[(size_t)st * PX_KSTRIDE + seg * 112 + lc]], (unsigned long long)c);
+    const unsigned char *kb = rb_k + (size_t)st * PX_KSTRIDE + seg * PX_KSEG;
+    int c0 = 0, c1 = 0;
+    for (int j = 0; j < 8; ++j) c0 += e[j] != PX_PAD, c1 += e[8 + j] != PX_PAD;
+    if (half) {
+      if (c0) atomicAdd(&pairs[kb[2 * lc]], (unsigned long long)c0);
+      if (c1) atomicAdd(&pairs[kb[2 * lc + 1]], (unsigned long long)c1);
+    } else {
+      atomicAdd(&pairs[kb[lc]], (unsigned long long)(c0 + c1));
+    }
   }
 }
 
@@ -403,7 +437,7 @@ __global__ void k_export_table(const int *__restrict__ nbr, int64_t ldn, int K, 
 // pairs, `dups` the (offset, output row) slots that were written twice: must stay 0)
 __global__ void k_export_rulebook(const uint32_t *__restrict__ rb_e, const unsigned char *__restrict__ rb_k,
                                   const int *__restrict__ rb_cnt, const int *__restrict__ n_ptr, int *__restrict__ out,
-                                  unsigned long long *__restrict__ entries) {
+                                  unsigned long long *__restrict__ entries, int half) {
   const int n = *n_ptr;
   const int nst = (n + 63) >> 6;
   const int64_t total = (int64_t)nst * 3 * PX_SEG_CH * 16;
@@ -415,7 +449,7 @@ __global__ void k_export_rulebook(const uint32_t *__restrict__ rb_e, const unsig
     if (lc >= rb_cnt[(size_t)st * 4 + seg]) continue;
     const uint32_t e = rb_e[((size_t)st * PX_CH_MAX + (size_t)seg * PX_SEG_CH + lc) * 16 + j];
     if (e == PX_PAD) continue;
-    const int k = rb_k[(size_t)st * PX_KSTRIDE + seg * 112 + lc];
+    const int k = rb_k[(size_t)st * PX_KSTRIDE + seg * PX_KSEG + (half ? 2 * lc + (j >> 3) : lc)];
     const int u = st * 64 + (int)(e & 127u);
     atomicAdd(&entries[0], 1ull);
     if (u >= n || k >= 81 || k / 27 != seg) {  // malformed entry

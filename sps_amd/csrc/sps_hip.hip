@@ -646,9 +646,9 @@ Geometry conv_geometry(int level, int K, int cin, int nt, int64_t cap = 0, bool 
   return g;
 }
 
-template <int NW, int CIN, bool C8, bool DS, bool FIN, int MINW, bool UP = false>
+template <int NW, int CIN, bool C8, bool DS, bool FIN, int MINW, bool UP = false, bool HALF = false>
 void launch_px(dim3 grid, hipStream_t st, const ConvArgs &a) {
-  hipLaunchKernelGGL((k_conv_px<NW, CIN, C8, DS, FIN, MINW, UP>), grid, dim3(NW * 64), 0, st, a);
+  hipLaunchKernelGGL((k_conv_px<NW, CIN, C8, DS, FIN, MINW, UP, HALF>), grid, dim3(NW * 64), 0, st, a);
 }
 
 // k_conv instantiation for a launch geometry (column tiles per wave x splits) -- shared by inference and training
@@ -867,10 +867,14 @@ int run_conv(sps_ctx *c, const ConvCall &cc, hipStream_t st) {
     a.rb_supertiles = (int)(c->capl[cc.level_out] / 64);
     const int key = cs.cin * 100 + (cs.cout == 8 ? 10 : 0) + (cc.fin ? 2 : (ds ? 1 : 0));
     c->last_kernel = "k_conv_px";
+    // the level-0 rulebook is padded per 8 pairs: only the C_out = 8 instantiations (HALF) can read it
+    static_assert(PX_HALF_LEVELS == 1, "SPS_PX_LAUNCH picks the HALF instantiations for level 0 alone");
+    if (px_half_level(cc.level_out) && cs.cout != 8)
+      return fail(SPS_ERR_INVALID, "%s: C_out = %d cannot read the 8-pair rulebook of level %d", cc.name, cs.cout, cc.level_out);
 #define SPS_PX_LAUNCH(CIN_, C8_, DS_, FIN_)                                                                  \
   do {                                                                                                       \
     if (cc.level_out == 0)                                                                                   \
-      launch_px<SPS_PX0, CIN_, C8_, DS_, FIN_, SPS_PX0_W>(gridp, st, a);                                     \
+      launch_px<SPS_PX0, CIN_, C8_, DS_, FIN_, SPS_PX0_W, false, C8_>(gridp, st, a);                         \
     else                                                                                                     \
       launch_px<SPS_PX1, CIN_, C8_, DS_, FIN_, SPS_PX1_W>(gridp, st, a);                                     \
   } while (0)
@@ -2066,7 +2070,7 @@ int sps_get_map_pairs(sps_ctx *c, int which, int64_t *pairs_host) {
     const Level &L = c->lv[which];
     if (!L.rb_e) return fail(SPS_ERR_INVALID, "level %d has neither a neighbour table nor a rulebook", which);
     HIP_TRY(hipMemset(c->pairs, 0, 128 * sizeof(unsigned long long)));
-    hipLaunchKernelGGL(k_count_pairs_rb, dim3(1024), dim3(256), 0, 0, L.rb_e, L.rb_k, L.rb_cnt, c->counts + which, c->pairs);
+    hipLaunchKernelGGL(k_count_pairs_rb, dim3(1024), dim3(256), 0, 0, L.rb_e, L.rb_k, L.rb_cnt, c->counts + which, c->pairs, px_half_level(which) ? 1 : 0);
     unsigned long long hr[128];
     HIP_TRY(hipMemcpy(hr, c->pairs, sizeof hr, hipMemcpyDeviceToHost));
     for (int k = 0; k < K; ++k) pairs_host[k] = (int64_t)hr[k];
@@ -2083,6 +2087,22 @@ int sps_get_map_pairs(sps_ctx *c, int which, int64_t *pairs_host) {
   unsigned long long h[128];
   HIP_TRY(hipMemcpy(h, c->pairs, sizeof h, hipMemcpyDeviceToHost));
   for (int k = 0; k < K; ++k) pairs_host[k] = (int64_t)h[k];
+  return SPS_OK;
+}
+
+int sps_get_rulebook_chunks(sps_ctx *c, int which, int32_t *chunks_host, int64_t *n_supertiles) {
+  if (!c || !n_supertiles || which < 0 || which >= SPS_NUM_LEVELS) return fail(SPS_ERR_INVALID, "bad arguments");
+  int64_t cnt[SPS_NUM_LEVELS];
+  int rc = sps_level_counts(c, cnt);
+  if (rc != SPS_OK) return rc;
+  const Level &L = c->lv[which];
+  if (!L.rb_cnt) return fail(SPS_ERR_INVALID, "level %d keeps no rulebook (its layers run output-stationary)", which);
+  *n_supertiles = (cnt[which] + 63) / 64;
+  if (!chunks_host || *n_supertiles == 0) return SPS_OK;
+  std::vector<int> h((size_t)*n_supertiles * 4);
+  HIP_TRY(hipMemcpy(h.data(), L.rb_cnt, h.size() * sizeof(int), hipMemcpyDeviceToHost));
+  for (int64_t s = 0; s < *n_supertiles; ++s)
+    for (int j = 0; j < 3; ++j) chunks_host[s * 3 + j] = h[(size_t)s * 4 + j];
   return SPS_OK;
 }
 
@@ -2130,7 +2150,7 @@ int sps_get_kernel_map(sps_ctx *c, int which, int source, int32_t *out_dev, int6
     if (!L.rb_e) return fail(SPS_ERR_INVALID, "level %d keeps no rulebook (its layers run output-stationary)", which);
     HIP_TRY(hipMemset(out_dev, 0xFF, (size_t)K * n * sizeof(int)));
     HIP_TRY(hipMemset(c->pairs, 0, 128 * sizeof(unsigned long long)));
-    hipLaunchKernelGGL(k_export_rulebook, dim3(1024), dim3(256), 0, 0, L.rb_e, L.rb_k, L.rb_cnt, c->counts + which, out_dev, c->pairs);
+    hipLaunchKernelGGL(k_export_rulebook, dim3(1024), dim3(256), 0, 0, L.rb_e, L.rb_k, L.rb_cnt, c->counts + which, out_dev, c->pairs, px_half_level(which) ? 1 : 0);
     unsigned long long h[2];
     HIP_TRY(hipMemcpy(h, c->pairs, sizeof h, hipMemcpyDeviceToHost));
     if (h[1]) return fail(SPS_ERR_INVALID, "rulebook of level %d: %llu malformed or duplicate entries", which, h[1]);
