@@ -499,6 +499,47 @@ int sps_loc_align(sps_ctx *ctx, const double *pts_dev, const int32_t *n_dev, int
                   int iters, int min_corr, double tol_t, double tol_r, double *T_out_dev, int32_t *status_dev,
                   double *trace_dev, double *normal_dev, void *scratch_dev, void *stream);
 
+/* ---- NDT localiser (scan-to-map point-to-distribution registration) --------------------------------------------------
+ * The registration hdl_localization runs in the reference's experiment is NDT (ndt_omp: 1 m cells, DIRECT7).  These
+ * calls give the localiser above a second association: every map cell carries a mean and an inverse covariance, and a
+ * scan point is pulled towards the Gaussians of its own cell and of its six face neighbours.  Thinning
+ * (sps_loc_downsample), launch B, the outputs and the status codes are those of sps_loc_align.  Still no UKF, no IMU.
+ *
+ * sps_ndt_map_build: the map's points grouped by cell of edge `resolution` (cell index floor(v / resolution) per axis;
+ *   key, start and cell-ordered point indices as for sps_radius_grid_upload; all device pointers, f64 [n_map][3] points).
+ *   Hashes the keys into storage owned by the context and computes per cell, in float64 with sums in the order of the
+ *   cell's list: n; the mean; the sample covariance sum (p - mean)(p - mean)^T / (n - 1); its eigen-decomposition by 8
+ *   cyclic Jacobi sweeps ((0,1), (0,2), (1,2)); eigenvalues below eig_ratio * lambda_max raised to that value; the
+ *   inverse V diag(1 / lambda) V^T as 6 entries (xx, xy, xz, yy, yz, zz).  A cell is valid iff n >= min_points, n >= 2,
+ *   lambda_max > 0 and everything is finite; invalid cells stay in the table, flagged, and contribute nothing.  Allocates
+ *   and synchronises (like sps_radius_grid_upload); n_map = 0 builds an empty map (every alignment ends with status 2).
+ * sps_ndt_map_cells: debug getter -- per cell, in the order of the uploaded keys, the key, n, the mean [3], the inverse
+ *   covariance [6] and the valid flag into device arrays (any may be NULL).  Synchronises.
+ * sps_ndt_align: as sps_loc_align, with launch A replaced.  Host constants (PCL's), float64: c1 = 10 (1 - outlier_ratio),
+ *   c2 = outlier_ratio / resolution^3, d3 = -log c2, d1 = -log(c1 + c2) - d3,
+ *   d2 = -2 log((-log(c1 exp(-1/2) + c2) - d3) / d1).
+ *     A: q = R p + t as in sps_loc_align; cell of q = floor(q / resolution); lookups in the order own cell, +x, -x, +y,
+ *        -y, +z, -z (neighbours = 7) or the own cell alone (neighbours = 1).  For a valid cell: x = q - mean,
+ *        y = icov x (rows as (m0*x0 + m1*x1) + m2*x2), s = (x0*y0 + x1*y1) + x2*y2, e = exp(-0.5 * (d2 * s)), w = d2 * e;
+ *        the cell is skipped unless 0 <= w <= 1 (NaN skips).  With a = (-d1) * w and J = [ -[q]x | I ]:
+ *        H(r, c) += a * (J_r . (icov J_c)), g(r) += a * (J_r . y), score += (-d1) * e, every dot product as above; a
+ *        point with at least one contributing cell counts once.  Cells are added in lookup order within a point, points
+ *        in index order within a workgroup of 32, workgroups as launch B adds them.
+ *   H is the positive-semidefinite part of the NDT Hessian and the step H delta = -g is taken at unit length.
+ *   trace_dev holds (points counted, score, |v|, |omega|) per iteration, normal_dev the 21 + 6 + 1 sums (b = -g, score).
+ *   Status 2: fewer than min_corr points counted.  scratch_dev: sps_ndt_align_scratch(cap) bytes.  Never allocates,
+ *   never synchronises, never raises the sticky error. */
+int64_t sps_ndt_align_scratch(int64_t cap);
+int sps_ndt_map_build(sps_ctx *ctx, const uint64_t *cell_keys_dev, const int32_t *cell_start_dev,
+                      const int32_t *cell_pts_dev, const double *map_xyz_dev, int64_t n_cells, int64_t n_map,
+                      double resolution, int min_points, double eig_ratio, void *stream);
+int sps_ndt_map_cells(sps_ctx *ctx, uint64_t *key_out_dev, int32_t *count_out_dev, double *mean_out_dev,
+                      double *icov_out_dev, int32_t *valid_out_dev);
+int sps_ndt_align(sps_ctx *ctx, const double *pts_dev, const int32_t *n_dev, int64_t cap, const double *T_init_host,
+                  int iters, int neighbours, int min_corr, double outlier_ratio, double tol_t, double tol_r,
+                  double *T_out_dev, int32_t *status_dev, double *trace_dev, double *normal_dev, void *scratch_dev,
+                  void *stream);
+
 #ifdef __cplusplus
 }
 #endif

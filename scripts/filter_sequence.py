@@ -18,7 +18,8 @@ random initialisation.
 ``--localise`` closes the loop of the experiment (sps_amd.localiser.LocalisationLoop, seeded with the first replayed
 pose): the filter's kept rows are registered against the map by a device point-to-point ICP (the stand-in for
 hdl_localization; not a port of it), the corrected pose goes back into the filter, and the replayed poses only score
-the result.  Frames then run one at a time; behind each frame's lines comes
+the result.  ``--localiser ndt`` registers with sps_amd.localiser.NDTLocaliser instead: the normal-distributions transform
+hdl_localization itself runs (1 m cells, DIRECT7), still without its UKF and IMU.  Frames then run one at a time; behind each frame's lines comes
 ``loc: status iterations n_corr rmse | err_t err_r`` (metres, degrees, against the replayed pose map_tr @ pose) and at
 the end the absolute pose error evo_ape prints by default.  ``--traj-out FILE`` writes the estimated trajectory
 (stamp + the top three rows of the pose per line).
@@ -113,11 +114,11 @@ def submit(name, f, scan, T, prev_pose):
     return f.submit(scan, T)
 
 
-def closed_loop(name, f, pc_map, replay, finish, traj_out):
+def closed_loop(name, f, pc_map, replay, finish, traj_out, which="icp"):
     """--localise: one LocalisationLoop step per frame, scored against the replayed poses."""
-    from sps_amd.localiser import LocalisationLoop, ScanToMapLocaliser
+    from sps_amd.localiser import LocalisationLoop, NDTLocaliser, ScanToMapLocaliser
     from sps_amd.trajectory import ape_translation, rotation_angle, write_trajectory
-    localiser = ScanToMapLocaliser(pc_map[:, :3])
+    localiser = NDTLocaliser(pc_map[:, :3]) if which == "ndt" else ScanToMapLocaliser(pc_map[:, :3])
     loop, stamps, ref = None, [], []
     for stamp, scan, pose, map_tr in replay:
         T = map_tr @ pose
@@ -148,8 +149,12 @@ def closed_loop(name, f, pc_map, replay, finish, traj_out):
 @click.option("--out", "out_dir", type=str, default=None, help="write the filtered clouds as DIR/<stamp>.npy")
 @click.option("--synthetic", "n_synth", type=int, default=0, help="replay N synthetic scans instead of $DATA")
 @click.option("--localise", is_flag=True, help="close the loop: localise every filtered cloud and feed the pose back")
+@click.option("--localiser", "which", type=click.Choice(("icp", "ndt")), default=None,
+              help="with --localise: point-to-point ICP (default) or NDT")
 @click.option("--traj-out", "traj_out", type=str, default=None, help="with --localise: write the estimated trajectory")
-def main(name, weights, sequence, config, epsilon, out_dir, n_synth, localise, traj_out):
+def main(name, weights, sequence, config, epsilon, out_dir, n_synth, localise, which, traj_out):
+    if which is not None and not localise:
+        raise click.UsageError("--localiser needs --localise")
     cfg = yaml.safe_load(open(config))
     if epsilon is None:
         epsilon = float(cfg.get("FILTER", {}).get("THRESHOLD", 0.84))
@@ -184,7 +189,7 @@ def main(name, weights, sequence, config, epsilon, out_dir, n_synth, localise, t
         n_done += 1
 
     if localise:
-        closed_loop(name, f, pc_map, replay, finish, traj_out)
+        closed_loop(name, f, pc_map, replay, finish, traj_out, which or "icp")
     elif traj_out:
         raise click.UsageError("--traj-out needs --localise")
     in_flight, prev_pose = None, None

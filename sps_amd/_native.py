@@ -129,6 +129,11 @@ def _load() -> C.CDLL:
         "sps_loc_align_scratch": (i64, [i64]),
         "sps_loc_downsample": (i32, [vp, vp, i64, i64, vp, C.c_double, vp, i64, vp, vp, vp]),
         "sps_loc_align": (i32, [vp, vp, vp, i64, vp, i32, i32, C.c_double, C.c_double, vp, vp, vp, vp, vp, vp]),
+        "sps_ndt_align_scratch": (i64, [i64]),
+        "sps_ndt_map_build": (i32, [vp, vp, vp, vp, vp, i64, i64, C.c_double, i32, C.c_double, vp]),
+        "sps_ndt_map_cells": (i32, [vp, vp, vp, vp, vp, vp]),
+        "sps_ndt_align": (i32, [vp, vp, vp, i64, vp, i32, i32, i32, C.c_double, C.c_double, C.c_double, vp, vp, vp, vp, vp,
+                                vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)          # AttributeError here = header/library mismatch: fail loudly
@@ -155,7 +160,8 @@ EXPORTS = ["sps_last_error", "sps_version", "sps_ctx_create", "sps_ctx_destroy",
            "sps_lts_num_tensors", "sps_lts_tensor_info", "sps_lts_numel", "sps_lts_lidar_info", "sps_lts_create",
            "sps_lts_destroy", "sps_lts_project", "sps_lts_forward", "sps_lts_check", "sps_lts_tap",
            "sps_forward_head_n", "sps_transform_rows", "sps_transform_points_n", "sps_radius_crop", "sps_label_filter",
-           "sps_loc_downsample_scratch", "sps_loc_align_scratch", "sps_loc_downsample", "sps_loc_align"]
+           "sps_loc_downsample_scratch", "sps_loc_align_scratch", "sps_loc_downsample", "sps_loc_align",
+           "sps_ndt_align_scratch", "sps_ndt_map_build", "sps_ndt_map_cells", "sps_ndt_align"]
 CROP_BLOCK = 1024          # SPS_CROP_BLOCK: map rows per int of sps_radius_crop's scratch
 
 
@@ -409,6 +415,22 @@ class Context:
                   T_out_ptr: int, status_ptr: int, trace_ptr, normal_ptr, scratch_ptr: int, stream: int):
         check(lib.sps_loc_align(self.handle, pts_ptr, n_dev_ptr, int(cap), self._mat(T_init), int(iters), int(min_corr),
                                 float(tol_t), float(tol_r), T_out_ptr, status_ptr, trace_ptr, normal_ptr, scratch_ptr, stream))
+
+    # ---- NDT localiser (include/sps_hip.h, "NDT localiser") ----
+    def ndt_map_build(self, keys_ptr, start_ptr, pts_ptr, xyz_ptr, n_cells: int, n_map: int, resolution: float,
+                      min_points: int, eig_ratio: float, stream: int):
+        check(lib.sps_ndt_map_build(self.handle, keys_ptr, start_ptr, pts_ptr, xyz_ptr, int(n_cells), int(n_map),
+                                    float(resolution), int(min_points), float(eig_ratio), stream))
+
+    def ndt_map_cells(self, key_ptr, count_ptr, mean_ptr, icov_ptr, valid_ptr):
+        check(lib.sps_ndt_map_cells(self.handle, key_ptr, count_ptr, mean_ptr, icov_ptr, valid_ptr))
+
+    def ndt_align(self, pts_ptr, n_dev_ptr: int, cap: int, T_init, iters: int, neighbours: int, min_corr: int,
+                  outlier_ratio: float, tol_t: float, tol_r: float, T_out_ptr: int, status_ptr: int, trace_ptr, normal_ptr,
+                  scratch_ptr: int, stream: int):
+        check(lib.sps_ndt_align(self.handle, pts_ptr, n_dev_ptr, int(cap), self._mat(T_init), int(iters), int(neighbours),
+                                int(min_corr), float(outlier_ratio), float(tol_t), float(tol_r), T_out_ptr, status_ptr,
+                                trace_ptr, normal_ptr, scratch_ptr, stream))
 
     def train_forward(self, params_ptr: int, numel: int, coords_ptr: int, ld: int, n: int, voxel_size: float,
                       scores_ptr: int, batch_stats_ptr, stream: int):

@@ -1,0 +1,109 @@
+// ndt_host.inc.h -- part of sps_hip.hip (included inside its extern "C" block): the entry points of the NDT localiser
+// (ABI: the "NDT localiser" section of include/sps_hip.h; kernels: ndt_kernels.inc.h).  sps_ndt_map_build allocates and
+// synchronises, like sps_radius_grid_upload; sps_ndt_align does neither: its scratch is the caller's.
+
+int64_t sps_ndt_align_scratch(int64_t cap) { return sps_loc_align_scratch(cap); }   // the partial rows of k_loc_solve
+
+int sps_ndt_map_build(sps_ctx *c, const uint64_t *cell_keys_dev, const int32_t *cell_start_dev, const int32_t *cell_pts_dev,
+                      const double *map_xyz_dev, int64_t n_cells, int64_t n_map, double resolution, int min_points,
+                      double eig_ratio, void *stream) {
+  if (!c || n_cells < 0 || n_map < 0 || n_cells > n_map) return fail(SPS_ERR_INVALID, "bad arguments");
+  if (!(resolution > 0.0) || std::isinf(resolution)) return fail(SPS_ERR_INVALID, "resolution must be finite and > 0");
+  if (!(eig_ratio > 0.0) || !(eig_ratio <= 1.0)) return fail(SPS_ERR_INVALID, "eig_ratio must be in (0, 1]");
+  if (min_points < 0) return fail(SPS_ERR_INVALID, "min_points must be >= 0");
+  if (n_map > 0 && (!cell_keys_dev || !cell_start_dev || !cell_pts_dev || !map_xyz_dev)) return fail(SPS_ERR_INVALID, "null argument");
+  if (n_map >= (1ll << 31) || n_cells >= (1ll << 30)) return fail(SPS_ERR_INVALID, "map too large");
+  HIP_TRY(hipSetDevice(c->device));
+  hipStream_t st = (hipStream_t)stream;
+  HIP_TRY(hipDeviceSynchronize());
+  for (void *p : c->ndt_allocs) (void)hipFree(p);
+  c->ndt_allocs.clear();
+  c->ndt = NdtMap{};
+  auto alloc = [&](void **p, size_t bytes) -> hipError_t {
+    hipError_t e = hipMalloc(p, bytes ? bytes : 16);
+    if (e == hipSuccess) c->ndt_allocs.push_back(*p);
+    return e;
+  };
+  const int64_t hcap = next_pow2(2 * (n_cells < 512 ? 512 : n_cells));
+  void *keys = nullptr, *rank = nullptr, *rec = nullptr, *count = nullptr, *ckeys = nullptr;
+  if (alloc(&keys, (size_t)hcap * 8) != hipSuccess || alloc(&rank, (size_t)hcap * 4) != hipSuccess ||
+      alloc(&rec, (size_t)n_cells * NDT_REC * 8) != hipSuccess || alloc(&count, (size_t)n_cells * 4) != hipSuccess ||
+      alloc(&ckeys, (size_t)n_cells * 8) != hipSuccess)
+    return fail(SPS_ERR_NOMEM, "hipMalloc for the NDT map failed");
+  HIP_TRY(hipMemsetAsync(keys, 0xFF, (size_t)hcap * 8, st));
+  NdtMap m{};
+  m.h.keys = (uint64_t *)keys;
+  m.h.first = nullptr;
+  m.h.rank = (int *)rank;
+  m.h.mask = (uint32_t)(hcap - 1);
+  m.rec = (const double *)rec;
+  m.count = (const int *)count;
+  m.keys = (const uint64_t *)ckeys;
+  m.n_cells = (int)n_cells;
+  m.resolution = resolution;
+  if (n_cells > 0) {
+    const unsigned nb = (unsigned)((n_cells + 255) / 256);
+    HIP_TRY(hipMemcpyAsync(ckeys, cell_keys_dev, (size_t)n_cells * 8, hipMemcpyDeviceToDevice, st));
+    hipLaunchKernelGGL(k_radius_cells_insert, dim3(nb), dim3(256), 0, st, (const unsigned long long *)cell_keys_dev, (int)n_cells, m.h);
+    hipLaunchKernelGGL(k_ndt_cells, dim3(nb), dim3(256), 0, st, (const int *)cell_start_dev, (const int *)cell_pts_dev, map_xyz_dev,
+                       (int)n_cells, (int)n_map, min_points, eig_ratio, (double *)rec, (int *)count);
+  }
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipStreamSynchronize(st));
+  c->ndt = m;
+  return SPS_OK;
+}
+
+int sps_ndt_map_cells(sps_ctx *c, uint64_t *key_out_dev, int32_t *count_out_dev, double *mean_out_dev, double *icov_out_dev,
+                      int32_t *valid_out_dev) {
+  if (!c) return fail(SPS_ERR_INVALID, "ctx is null");
+  if (!c->ndt.h.keys) return fail(SPS_ERR_INVALID, "sps_ndt_map_build has not been called");
+  HIP_TRY(hipSetDevice(c->device));
+  HIP_TRY(hipDeviceSynchronize());
+  if (c->ndt.n_cells > 0)
+    hipLaunchKernelGGL(k_ndt_cells_get, dim3((unsigned)((c->ndt.n_cells + 255) / 256)), dim3(256), 0, 0, c->ndt,
+                       (unsigned long long *)key_out_dev, count_out_dev, mean_out_dev, icov_out_dev, valid_out_dev);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipDeviceSynchronize());
+  return SPS_OK;
+}
+
+int sps_ndt_align(sps_ctx *c, const double *pts_dev, const int32_t *n_dev, int64_t cap, const double *T_init_host, int iters,
+                  int neighbours, int min_corr, double outlier_ratio, double tol_t, double tol_r, double *T_out_dev,
+                  int32_t *status_dev, double *trace_dev, double *normal_dev, void *scratch_dev, void *stream) {
+  if (!c || !n_dev || !T_init_host || !T_out_dev || !status_dev || !scratch_dev || cap < 0 || iters < 0 ||
+      (cap > 0 && !pts_dev) || (iters > 0 && !trace_dev))
+    return fail(SPS_ERR_INVALID, "bad arguments");
+  if (!c->ndt.h.keys) return fail(SPS_ERR_INVALID, "sps_ndt_map_build has not been called");
+  if (neighbours != 1 && neighbours != 7) return fail(SPS_ERR_INVALID, "neighbours must be 1 or 7");
+  if (cap > SPS_MAX_POINTS || iters > 10000) return fail(SPS_ERR_INVALID, "too many points or iterations");
+  if (std::isnan(tol_t) || std::isnan(tol_r)) return fail(SPS_ERR_INVALID, "tolerances must not be NaN");
+  if (!(outlier_ratio > 0.0) || !(outlier_ratio < 1.0)) return fail(SPS_ERR_INVALID, "outlier_ratio must be in (0, 1)");
+  // the Gaussian fit of the mixture (Magnusson 2009, eq. 6.8; PCL's gauss_d1_ / gauss_d2_), in float64 on the host
+  const double res = c->ndt.resolution;
+  const double c1 = 10.0 * (1.0 - outlier_ratio), c2 = outlier_ratio / (res * res * res);
+  const double d3 = -std::log(c2);
+  const double d1 = -std::log(c1 + c2) - d3;
+  const double d2 = -2.0 * std::log((-std::log(c1 * std::exp(-0.5) + c2) - d3) / d1);
+  if (!std::isfinite(d1) || !std::isfinite(d2) || !(d1 < 0.0) || !(d2 > 0.0))
+    return fail(SPS_ERR_INVALID, "outlier_ratio and resolution give no usable Gaussian fit");
+  HIP_TRY(hipSetDevice(c->device));
+  hipStream_t st = (hipStream_t)stream;
+  LocPose T0;
+  for (int i = 0; i < 16; ++i) T0.m[i] = T_init_host[i];
+  const NdtGauss gs{-d1, d2};
+  const int nb = (int)loc_align_blocks(cap);
+  double *partial = (double *)scratch_dev;
+  int *done = (int *)(partial + (size_t)nb * LOC_TERMS);
+  if (iters > 0) HIP_TRY(hipMemsetAsync(trace_dev, 0, (size_t)iters * 4 * sizeof(double), st));
+  if (iters > 0 && normal_dev) HIP_TRY(hipMemsetAsync(normal_dev, 0, (size_t)iters * 28 * sizeof(double), st));
+  hipLaunchKernelGGL(k_loc_init, dim3(1), dim3(64), 0, st, T0, T_out_dev, status_dev, done);
+  for (int it = 0; it < iters; ++it) {
+    hipLaunchKernelGGL(k_ndt_assoc, dim3(nb), dim3(256), 0, st, pts_dev, n_dev, (int)cap, c->ndt, gs, neighbours,
+                       (const double *)T_out_dev, (const int *)done, partial);
+    hipLaunchKernelGGL(k_loc_solve, dim3(1), dim3(256), 0, st, (const double *)partial, n_dev, (int)cap, it, min_corr, tol_t,
+                       tol_r, T0, T_out_dev, status_dev, done, trace_dev, normal_dev);
+  }
+  HIP_TRY(hipGetLastError());
+  return SPS_OK;
+}

@@ -1,0 +1,250 @@
+// ndt_kernels.inc.h -- part of sps_hip.hip (included inside its anonymous namespace, after loc_kernels.inc.h): the NDT
+// (point-to-distribution) scan-to-map localiser (host side: ndt_host.inc.h; ABI: the "NDT localiser" section of
+// include/sps_hip.h).
+//
+//   k_ndt_cells   (map build)                 per map cell: n, mean, sample covariance, Jacobi eigen-decomposition, floored
+//                                             eigenvalues, inverse covariance -> one 80-byte record
+//   k_ndt_assoc   (launch A of an iteration)  q = R p + t, the records of q's cell and its face neighbours, the
+//                                             normal-equation terms of every contributing cell
+//
+// Launch B is k_loc_solve unchanged: the partial rows have its layout (21 of H, 6 of g, the score, the count; one row per
+// LOC_PTS points).  As in loc_kernels.inc.h everything is float64, every operation is rounded on its own (contraction is
+// off, products and sums go through loc_mul / loc_add) and no sum depends on the order in which threads arrive.
+
+#pragma clang fp contract(off)
+
+constexpr int NDT_REC = 10;      // doubles of a cell record: mean[3], icov[6] (xx, xy, xz, yy, yz, zz), valid (1.0 / 0.0)
+constexpr int NDT_SWEEPS = 8;    // cyclic Jacobi sweeps of the 3 x 3 eigen-decomposition (fixed: no convergence test)
+constexpr int NDT_LANES = 8;     // lanes of one scan point in k_ndt_assoc
+constexpr int NDT_HIT = 11;      // doubles a contributing cell leaves in LDS: a = -d1 w, icov[6], y = icov x [3], the score
+static_assert(LOC_PTS * NDT_LANES == 256, "k_ndt_assoc: one workgroup of 256 covers LOC_PTS points");
+
+struct NdtMap {
+  HashTable h;             // cell key -> cell id (rank); keys == nullptr: no map built
+  const double *rec;       // [C][NDT_REC]
+  const int *count;        // [C] points of the cell
+  const uint64_t *keys;    // [C] the cell keys as uploaded (debug getter)
+  int n_cells;
+  double resolution;
+};
+
+struct NdtGauss {
+  double nd1, d2;          // -d1 and d2 of the mixture's Gaussian fit (host, float64)
+};
+
+// ---- the map -----------------------------------------------------------------------------------------------------------
+// One Jacobi rotation that zeroes a[p][q].  t = sign(theta) / (|theta| + sqrt(theta^2 + 1)), theta = (aqq - app) / (2 apq).
+__device__ inline void ndt_rotate(double a[3][3], double v[3][3], int p, int q) {
+  const double apq = a[p][q];
+  if (apq == 0.0) return;
+  const int r = 3 - p - q;
+  const double theta = __ddiv_rn(loc_add(a[q][q], -a[p][p]), loc_mul(2.0, apq));
+  const double at = fabs(theta);
+  double t = __ddiv_rn(1.0, loc_add(at, __dsqrt_rn(loc_add(loc_mul(theta, theta), 1.0))));
+  if (theta < 0.0) t = -t;
+  const double c = __ddiv_rn(1.0, __dsqrt_rn(loc_add(loc_mul(t, t), 1.0)));
+  const double s = loc_mul(t, c);
+  a[p][p] = loc_add(a[p][p], -loc_mul(t, apq));
+  a[q][q] = loc_add(a[q][q], loc_mul(t, apq));
+  a[p][q] = a[q][p] = 0.0;
+  const double arp = a[r][p], arq = a[r][q];
+  a[r][p] = a[p][r] = loc_add(loc_mul(c, arp), -loc_mul(s, arq));
+  a[r][q] = a[q][r] = loc_add(loc_mul(s, arp), loc_mul(c, arq));
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    const double vkp = v[k][p], vkq = v[k][q];
+    v[k][p] = loc_add(loc_mul(c, vkp), -loc_mul(s, vkq));
+    v[k][q] = loc_add(loc_mul(s, vkp), loc_mul(c, vkq));
+  }
+}
+
+// One thread per cell; the cell's points are read in the order of its list (ascending map index).
+__global__ __launch_bounds__(256) void k_ndt_cells(const int *__restrict__ cell_start, const int *__restrict__ cell_pts,
+                                                    const double *__restrict__ xyz, int n_cells, int n_map, int min_points,
+                                                    double eig_ratio, double *__restrict__ rec, int *__restrict__ count) {
+  const int c = blockIdx.x * 256 + threadIdx.x;
+  if (c >= n_cells) return;
+  const int lo = max(cell_start[c], 0), hi = min(cell_start[c + 1], n_map);
+  const int n = max(hi - lo, 0);
+  double sum[3] = {0.0, 0.0, 0.0};
+  for (int t = lo; t < hi; ++t) {
+    const int j = cell_pts[t];
+    if (j < 0 || j >= n_map) continue;   // a malformed list reads nothing out of bounds
+#pragma unroll
+    for (int a = 0; a < 3; ++a) sum[a] = loc_add(sum[a], xyz[(size_t)j * 3 + a]);
+  }
+  double mu[3] = {0.0, 0.0, 0.0};
+  if (n > 0)
+    for (int a = 0; a < 3; ++a) mu[a] = __ddiv_rn(sum[a], (double)n);
+  double cv[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};   // xx, xy, xz, yy, yz, zz
+  for (int t = lo; t < hi; ++t) {
+    const int j = cell_pts[t];
+    if (j < 0 || j >= n_map) continue;
+    const double dx = loc_add(xyz[(size_t)j * 3], -mu[0]), dy = loc_add(xyz[(size_t)j * 3 + 1], -mu[1]),
+                 dz = loc_add(xyz[(size_t)j * 3 + 2], -mu[2]);
+    cv[0] = loc_add(cv[0], loc_mul(dx, dx)), cv[1] = loc_add(cv[1], loc_mul(dx, dy)), cv[2] = loc_add(cv[2], loc_mul(dx, dz));
+    cv[3] = loc_add(cv[3], loc_mul(dy, dy)), cv[4] = loc_add(cv[4], loc_mul(dy, dz)), cv[5] = loc_add(cv[5], loc_mul(dz, dz));
+  }
+  double icov[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  bool valid = n >= min_points && n >= 2;
+  if (n >= 2) {
+    const double nm1 = (double)(n - 1);
+#pragma unroll
+    for (int i = 0; i < 6; ++i) cv[i] = __ddiv_rn(cv[i], nm1);
+    double a[3][3] = {{cv[0], cv[1], cv[2]}, {cv[1], cv[3], cv[4]}, {cv[2], cv[4], cv[5]}};
+    double v[3][3] = {{1.0, 0.0, 0.0}, {0.0, 1.0, 0.0}, {0.0, 0.0, 1.0}};
+    for (int sweep = 0; sweep < NDT_SWEEPS; ++sweep) {
+      ndt_rotate(a, v, 0, 1);
+      ndt_rotate(a, v, 0, 2);
+      ndt_rotate(a, v, 1, 2);
+    }
+    double lam[3] = {a[0][0], a[1][1], a[2][2]};
+    const double lmax = fmax(fmax(lam[0], lam[1]), lam[2]);
+    const double lfloor = loc_mul(eig_ratio, lmax);
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+      if (lam[i] < lfloor) lam[i] = lfloor;
+    valid = valid && lmax > 0.0;
+    int k = 0;
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+      for (int j = i; j < 3; ++j, ++k)
+        icov[k] = loc_add(loc_add(__ddiv_rn(loc_mul(v[i][0], v[j][0]), lam[0]), __ddiv_rn(loc_mul(v[i][1], v[j][1]), lam[1])),
+                          __ddiv_rn(loc_mul(v[i][2], v[j][2]), lam[2]));
+  }
+  for (int a = 0; a < 3; ++a) valid = valid && isfinite(mu[a]);
+  for (int i = 0; i < 6; ++i) valid = valid && isfinite(icov[i]);
+  double *o = rec + (size_t)c * NDT_REC;
+  o[0] = mu[0], o[1] = mu[1], o[2] = mu[2];
+#pragma unroll
+  for (int i = 0; i < 6; ++i) o[3 + i] = icov[i];
+  o[9] = valid ? 1.0 : 0.0;
+  count[c] = n;
+}
+
+// debug getter: the records split into the arrays the parity tests compare (any output may be null)
+__global__ void k_ndt_cells_get(NdtMap m, unsigned long long *__restrict__ key_out, int *__restrict__ count_out,
+                                double *__restrict__ mean_out, double *__restrict__ icov_out, int *__restrict__ valid_out) {
+  const int c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= m.n_cells) return;
+  const double *r = m.rec + (size_t)c * NDT_REC;
+  if (key_out) key_out[c] = m.keys[c];
+  if (count_out) count_out[c] = m.count[c];
+  if (mean_out)
+    for (int a = 0; a < 3; ++a) mean_out[(size_t)c * 3 + a] = r[a];
+  if (icov_out)
+    for (int i = 0; i < 6; ++i) icov_out[(size_t)c * 6 + i] = r[3 + i];
+  if (valid_out) valid_out[c] = r[9] != 0.0;
+}
+
+// ---- alignment -------------------------------------------------------------------------------------------------------
+// row i of the symmetric 3 x 3 matrix stored as (xx, xy, xz, yy, yz, zz), times b
+__device__ inline double ndt_symrow(const double *m, int i, const double b[3]) {
+  const double r[3] = {i == 0 ? m[0] : (i == 1 ? m[1] : m[2]), i == 0 ? m[1] : (i == 1 ? m[3] : m[4]),
+                       i == 0 ? m[2] : (i == 1 ? m[4] : m[5])};
+  return loc_dot3(r, b);
+}
+
+// Launch A.  NDT_LANES lanes per scan point, LOC_PTS points per workgroup.
+//   phase 1: lane c < neighbours looks up cell c of the point (0: q's own cell, then +x, -x, +y, -y, +z, -z), reads its
+//            record and, where the cell is valid and the weight passes the guard, leaves a, icov, y = icov x and the score
+//            in LDS;
+//   phase 2: lane l forms terms l, l + 8, l + 16, l + 24 of the point, adding the contributing cells in lookup order;
+//   phase 3: thread l < LOC_TERMS adds the workgroup's points in point order and writes entry l of the partial row.
+__global__ __launch_bounds__(256) void k_ndt_assoc(const double *__restrict__ pts, const int *__restrict__ n_dev, int cap,
+                                                    NdtMap m, NdtGauss gs, int neighbours, const double *__restrict__ T,
+                                                    const int *__restrict__ done, double *__restrict__ partial) {
+  __shared__ double hit[LOC_PTS][7][NDT_HIT];
+  __shared__ int hit_ok[LOC_PTS][NDT_LANES];
+  __shared__ double terms[LOC_PTS][LOC_TERMS];
+  if (*done) return;
+  const int n = min(cap, max(*n_dev, 0));
+  const int base = blockIdx.x * LOC_PTS;
+  if (base >= n) return;
+  const int k = threadIdx.x / NDT_LANES, sub = threadIdx.x % NDT_LANES;
+  const int i = base + k;
+  double q[3] = {0.0, 0.0, 0.0};
+  int ok = 0;
+  if (i < n) {
+    const double px = pts[(size_t)i * 3], py = pts[(size_t)i * 3 + 1], pz = pts[(size_t)i * 3 + 2];
+#pragma unroll
+    for (int a = 0; a < 3; ++a)
+      q[a] = loc_add(loc_add(loc_add(loc_mul(T[4 * a], px), loc_mul(T[4 * a + 1], py)), loc_mul(T[4 * a + 2], pz)), T[4 * a + 3]);
+    if (sub < neighbours) {
+      long long cc[3];
+      bool in = true;
+#pragma unroll
+      for (int a = 0; a < 3; ++a) {
+        const double f = floor(__ddiv_rn(q[a], m.resolution));
+        in = in && f >= -1048575.0 && f <= 1048575.0;   // NaN compares false
+        cc[a] = in ? (long long)f : 0;
+      }
+      if (sub > 0) cc[(sub - 1) >> 1] += (sub & 1) ? 1 : -1;
+      in = in && cc[0] >= -1048575 && cc[0] <= 1048575 && cc[1] >= -1048575 && cc[1] <= 1048575 && cc[2] >= -1048575 &&
+           cc[2] <= 1048575;
+      const int s = in ? hash_find_slot(m.h, radius_key(cc[0], cc[1], cc[2])) : -1;
+      const int cell = s >= 0 ? m.h.rank[s] : -1;
+      if (cell >= 0 && cell < m.n_cells) {
+        double r[NDT_REC];
+        const double *src = m.rec + (size_t)cell * NDT_REC;   // one contiguous 80-byte record
+#pragma unroll
+        for (int j = 0; j < NDT_REC; ++j) r[j] = src[j];
+        if (r[9] != 0.0) {
+          const double x[3] = {loc_add(q[0], -r[0]), loc_add(q[1], -r[1]), loc_add(q[2], -r[2])};
+          const double y[3] = {ndt_symrow(r + 3, 0, x), ndt_symrow(r + 3, 1, x), ndt_symrow(r + 3, 2, x)};
+          const double sq = loc_dot3(x, y);
+          const double e = exp(loc_mul(-0.5, loc_mul(gs.d2, sq)));
+          const double w = loc_mul(gs.d2, e);
+          if (w >= 0.0 && w <= 1.0) {                       // NaN fails both: the guard of ndt_omp
+            double *o = hit[k][sub];
+            o[0] = loc_mul(gs.nd1, w);
+#pragma unroll
+            for (int j = 0; j < 6; ++j) o[1 + j] = r[3 + j];
+            o[7] = y[0], o[8] = y[1], o[9] = y[2];
+            o[10] = loc_mul(gs.nd1, e);
+            ok = 1;
+          }
+        }
+      }
+    }
+  }
+  hit_ok[k][sub] = ok;
+  __syncthreads();
+  for (int l = sub; l < LOC_TERMS; l += NDT_LANES) {
+    double term = 0.0;
+    int any = 0;
+    for (int c = 0; c < neighbours; ++c) {
+      if (!hit_ok[k][c]) continue;
+      any = 1;
+      const double *o = hit[k][c];
+      double v;
+      if (l < 21) {
+        int r = 0, cl = l;
+        while (cl >= 6 - r) cl -= 6 - r, ++r;   // upper triangle, row-major: (r, r + cl)
+        double ja[3], jb[3];
+        loc_jcol(r, q[0], q[1], q[2], ja);
+        loc_jcol(r + cl, q[0], q[1], q[2], jb);
+        const double u[3] = {ndt_symrow(o + 1, 0, jb), ndt_symrow(o + 1, 1, jb), ndt_symrow(o + 1, 2, jb)};
+        v = loc_mul(o[0], loc_dot3(ja, u));
+      } else if (l < 27) {
+        double ja[3];
+        loc_jcol(l - 21, q[0], q[1], q[2], ja);
+        v = loc_mul(o[0], loc_dot3(ja, o + 7));
+      } else {
+        v = o[10];
+      }
+      term = loc_add(term, v);
+    }
+    if (l == 28) term = any ? 1.0 : 0.0;
+    terms[k][l] = term;
+  }
+  __syncthreads();
+  if (threadIdx.x < LOC_TERMS) {
+    double s = 0.0;
+    for (int p = 0; p < LOC_PTS; ++p) s = loc_add(s, terms[p][threadIdx.x]);
+    partial[(size_t)blockIdx.x * LOC_TERMS + threadIdx.x] = s;
+  }
+}
+
+#pragma clang fp contract(fast)

@@ -148,6 +148,7 @@ int fail(int code, const char *fmt, ...) {
 #include "baseline_kernels.inc.h"
 #include "sps_filter_kernels.inc.h"
 #include "loc_kernels.inc.h"
+#include "ndt_kernels.inc.h"
 
 // ------------------------------------------------------------------------------------------
 // context
@@ -300,6 +301,9 @@ struct sps_ctx {
   // variant-A radius grid (device copies owned by the ctx)
   RadiusGrid rg{};
   std::vector<void *> rg_allocs;
+  // NDT localiser map (sps_ndt_map_build): cell hash + one 80-byte record per cell, owned by the ctx
+  NdtMap ndt{};
+  std::vector<void *> ndt_allocs;
   // variant-A item scratch (sps_radius_item): per (scan point, neighbour cell) hit counts and their prefix sums
   int *item_counts = nullptr, *item_offsets = nullptr, *item_bsum = nullptr, *item_base = nullptr;
   int64_t item_cap = 0;
@@ -1050,6 +1054,7 @@ int sps_ctx_destroy(sps_ctx *c) {
   c->weights.reset();
   if (c->map_keys_alloc) (void)hipFree(c->map_keys_alloc);
   for (void *p : c->rg_allocs) (void)hipFree(p);
+  for (void *p : c->ndt_allocs) (void)hipFree(p);
   for (void *p : {(void *)c->item_counts, (void *)c->item_offsets, (void *)c->item_bsum, (void *)c->item_base}) (void)hipFree(p);
   delete c;
   return SPS_OK;
@@ -2246,5 +2251,6 @@ int sps_get_feature(sps_ctx *c, const char *name, float *out_dev, int64_t *rows,
 #include "lts_host.inc.h"
 #include "baseline_host.inc.h"
 #include "loc_host.inc.h"
+#include "ndt_host.inc.h"
 
 }  // extern "C"

@@ -13,7 +13,11 @@ the same input gives the same bits.  ``submit()`` issues everything on the calle
 synchronises; ``PendingPose.result()`` is the one synchronisation.  A scan that misses the map is an ordinary result
 (status 2), never an error.
 
-``LocalisationLoop`` closes the loop for any of the seven filters of scripts/filter_sequence.py.
+``NDTLocaliser`` is the same stage with the registration the experiment actually runs: a normal-distributions
+transform (ndt_omp's 1 m cells and DIRECT7 neighbourhood by default; C ABI: the "NDT localiser" section; DESIGN.md
+"NDT localiser").  Thinning, the 6 x 6 solve, the outputs and the status codes are the ICP's; still no UKF, no IMU.
+
+``LocalisationLoop`` closes the loop for any of the seven filters of scripts/filter_sequence.py, around either localiser.
 """
 from __future__ import annotations
 
@@ -112,7 +116,7 @@ class ScanToMapLocaliser:
         """rows: device tensor [n_max, >= 3] (float32; other dtypes are converted); count: an int or a device int32 tensor
         holding the number of valid rows; T_init: 4x4.  Issued on the current stream."""
         if not (torch.is_tensor(rows) and rows.is_cuda and rows.device == self.device):
-            raise TypeError("ScanToMapLocaliser.submit needs a tensor on the localiser's device")
+            raise TypeError(f"{type(self).__name__}.submit needs a tensor on the localiser's device")
         if rows.dim() != 2 or rows.shape[1] < 3:
             raise ValueError(f"rows must be [n, >=3], got {tuple(rows.shape)}")
         T = _pose(T_init)
@@ -142,14 +146,17 @@ class ScanToMapLocaliser:
             self.ctx.loc_downsample(rows.data_ptr() if n_max else None, rows.stride(0) if n_max else 3, n_max,
                                     n_dev.data_ptr(), self.leaf, self._pts.data_ptr(), self.capacity, base + 18 * 8,
                                     scratch.data_ptr(), s)
-            self.ctx.loc_align(self._pts.data_ptr(), base + 18 * 8, self.capacity, T, K, self.min_correspondences,
-                               self.tol_t, self.tol_r, base, base + 16 * 8, base + 19 * 8 if K else None,
-                               base + (19 + 4 * K) * 8 if with_normal and K else None, self._align_scratch.data_ptr(), s)
+            self._align(base + 18 * 8, T, K, base, base + 16 * 8, base + 19 * 8 if K else None,
+                        base + (19 + 4 * K) * 8 if with_normal and K else None, s)
             host = torch.empty(out.numel(), dtype=torch.float64).pin_memory()
             host.copy_(out, non_blocking=True)
             ev = torch.cuda.Event()
             ev.record(st)
         return PendingPose(K, with_normal, host, ev, (rows, n_dev, out))
+
+    def _align(self, n_ptr, T, K, T_out_ptr, status_ptr, trace_ptr, normal_ptr, s):
+        self.ctx.loc_align(self._pts.data_ptr(), n_ptr, self.capacity, T, K, self.min_correspondences, self.tol_t, self.tol_r,
+                           T_out_ptr, status_ptr, trace_ptr, normal_ptr, self._align_scratch.data_ptr(), s)
 
     def submit_filtered(self, pending, T_init, **kw) -> PendingPose:
         """The kept rows of a pending SPSFilter / SPSCVMFilter frame and their device count go straight in, without the
@@ -158,6 +165,71 @@ class ScanToMapLocaliser:
 
     def __call__(self, rows, count, T_init, **kw) -> PoseResult:
         return self.submit(rows, count, T_init, **kw).result()
+
+
+class NDTLocaliser(ScanToMapLocaliser):
+    """``NDTLocaliser(map_points)(rows, count, T_init)`` -> PoseResult, by point-to-distribution registration.  The map
+    becomes one Gaussian (mean, inverse covariance) per cell of edge ``resolution`` in a native context of the
+    localiser's own; a scan point is scored against its own cell and, with ``neighbours=7``, the six face neighbours.
+    ``submit``, ``submit_filtered`` and ``__call__`` are ScanToMapLocaliser's.  In the result ``n_corr`` counts the scan
+    points with at least one contributing cell, ``trace[:, 1]`` and ``normal[:, 27]`` hold the NDT score
+    sum -d1 exp(-d2 s / 2) (larger is better) and ``rmse`` is sqrt(score / n_corr), not a distance."""
+
+    def __init__(self, map_points, resolution: float = 1.0, neighbours: int = 7, leaf: float = 0.2, iterations: int = 30,
+                 min_correspondences: int = 50, min_points_per_cell: int = 6, outlier_ratio: float = 0.55,
+                 eig_ratio: float = 0.01, tol_t: float = 1e-4, tol_r: float = 1e-5, device="cuda", capacity: int = 1 << 16):
+        from .datasets.blt_dataset import radius_grid_cells
+        if not (math.isfinite(resolution) and resolution > 0 and math.isfinite(leaf) and leaf > 0):
+            raise ValueError("resolution and leaf must be finite and > 0")
+        if neighbours not in (1, 7):
+            raise ValueError("neighbours must be 1 or 7")
+        if iterations < 0 or capacity < 1:
+            raise ValueError("iterations must be >= 0 and capacity >= 1")
+        if not (0.0 < outlier_ratio < 1.0 and 0.0 < eig_ratio <= 1.0 and min_points_per_cell >= 0):
+            raise ValueError("outlier_ratio must be in (0, 1), eig_ratio in (0, 1] and min_points_per_cell >= 0")
+        self.resolution, self.neighbours, self.leaf = float(resolution), int(neighbours), float(leaf)
+        self.iterations, self.min_correspondences = int(iterations), int(min_correspondences)
+        self.min_points_per_cell, self.outlier_ratio, self.eig_ratio = int(min_points_per_cell), float(outlier_ratio), float(eig_ratio)
+        self.tol_t, self.tol_r, self.capacity = float(tol_t), float(tol_r), int(capacity)
+        self.device = _device_of(device)
+        mp = map_points.detach().cpu().numpy() if torch.is_tensor(map_points) else np.asarray(map_points)
+        xyz = torch.as_tensor(np.ascontiguousarray(mp[:, :3], dtype=np.float64)).to(self.device)
+        self.n_map = len(xyz)
+        with torch.cuda.device(self.device):
+            self.stream = torch.cuda.current_stream()
+            self.ctx = _native.Context(self.device.index)
+            if self.n_map:
+                keys, start, pts = radius_grid_cells(xyz, self.resolution)
+                self.n_cells = len(keys)
+                self.ctx.ndt_map_build(keys.contiguous().data_ptr(), start.data_ptr(), pts.data_ptr(), xyz.data_ptr(),
+                                       self.n_cells, self.n_map, self.resolution, self.min_points_per_cell, self.eig_ratio,
+                                       self.stream.cuda_stream)
+            else:
+                self.n_cells = 0
+                self.ctx.ndt_map_build(None, None, None, None, 0, 0, self.resolution, self.min_points_per_cell,
+                                       self.eig_ratio, self.stream.cuda_stream)
+            self._pts = torch.empty((self.capacity, 3), dtype=torch.float64, device=self.device)
+            self._align_scratch = torch.empty(_native.lib.sps_ndt_align_scratch(self.capacity), dtype=torch.uint8, device=self.device)
+            self._ds_scratch, self._ds_rows = None, -1
+
+    def _align(self, n_ptr, T, K, T_out_ptr, status_ptr, trace_ptr, normal_ptr, s):
+        self.ctx.ndt_align(self._pts.data_ptr(), n_ptr, self.capacity, T, K, self.neighbours, self.min_correspondences,
+                           self.outlier_ratio, self.tol_t, self.tol_r, T_out_ptr, status_ptr, trace_ptr, normal_ptr,
+                           self._align_scratch.data_ptr(), s)
+
+    def map_cells(self):
+        """Debug: (keys uint64 [C], counts int32 [C], means [C, 3], inverse covariances [C, 6] as (xx, xy, xz, yy, yz, zz),
+        valid bool [C]) of the device map, in ascending key order, as numpy arrays."""
+        C = self.n_cells
+        with torch.cuda.device(self.device):
+            key = torch.zeros(C, dtype=torch.int64, device=self.device)
+            cnt = torch.zeros(C, dtype=torch.int32, device=self.device)
+            mean = torch.zeros((C, 3), dtype=torch.float64, device=self.device)
+            icov = torch.zeros((C, 6), dtype=torch.float64, device=self.device)
+            valid = torch.zeros(C, dtype=torch.int32, device=self.device)
+            self.ctx.ndt_map_cells(key.data_ptr(), cnt.data_ptr(), mean.data_ptr(), icov.data_ptr(), valid.data_ptr())
+        return (key.cpu().numpy().view(np.uint64), cnt.cpu().numpy(), mean.cpu().numpy(), icov.cpu().numpy(),
+                valid.cpu().numpy().astype(bool))
 
 
 @dataclass

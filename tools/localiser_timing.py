@@ -10,6 +10,11 @@ synthetic.build_map() map, max_distance 1 m, leaf 0.2 m):
               SPSFilter alone on the same scans
 
     python tools/localiser_timing.py [--frames 200] [--warmup 20] [--cpu-frames 1] [--one-frame] [--cpu-only]
+                                     [--localiser {icp,ndt}]
+
+``--localiser ndt`` times sps_amd.localiser.NDTLocaliser (1 m cells, 7 neighbours) on the same frames and from the same
+start, prints the ICP's per-frame figures of the same session beside it and the build time of both maps; the
+restatement is then tests/ndt_reference.py.
 
 ``--one-frame`` runs a warm-up and ONE localiser frame: the target of a ``rocprofv3 --kernel-trace --stats`` run.
 """
@@ -26,18 +31,57 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 from oracle import sps_oracle as O  # noqa: E402
 from sps_amd import synthetic  # noqa: E402
-from sps_amd.localiser import LocalisationLoop, ScanToMapLocaliser  # noqa: E402
+from sps_amd.localiser import LocalisationLoop, NDTLocaliser, ScanToMapLocaliser  # noqa: E402
 from sps_amd.sps_filters import SPSCVMFilter, SPSFilter  # noqa: E402
 from tests import localiser_reference as LR  # noqa: E402
+from tests import ndt_reference as NR  # noqa: E402
 from tests.helpers import CFG, net_from_params  # noqa: E402
 
 VS, EPS = CFG["MODEL"]["VOXEL_SIZE"], CFG["FILTER"]["THRESHOLD"]
 
 
+def timed_frames(loc, dscans, T_init, warmup, frames):
+    """hipEvent time around submit() per frame -> (ms, iterations, points, errors against the true pose I)"""
+    st = torch.cuda.current_stream()
+    ms, iters, npts, errs = [], [], [], []
+    for k in range(warmup + frames):
+        s = dscans[k % len(dscans)]
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(st)
+        pend = loc.submit(s, len(s), T_init)
+        e1.record(st)
+        r = pend.result()
+        e1.synchronize()
+        if k >= warmup:
+            ms.append(e0.elapsed_time(e1))
+            iters.append(r.iterations)
+            npts.append(r.n_points)
+            errs.append(LR.pose_difference(r.pose, np.eye(4))[0])
+    return ms, iters, npts, errs
+
+
+def build_ms(make):
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    loc = make()
+    torch.cuda.synchronize()
+    return loc, (time.perf_counter() - t0) * 1e3
+
+
 def restatement_only(a):
     mp = synthetic.build_map()
-    index = LR.MapIndex(mp, 1.0)
     T_init = LR.perturbation(0.15, 0.12, 0.05, 1.0)
+    if a.localiser == "ndt":
+        cmap = NR.cells(mp[:, :3].astype(np.float64), 1.0)
+        for k in range(max(a.cpu_frames, 1)):
+            s = synthetic.lidar_scan(seed=40 + (a.warmup + k) % 12, n_beams=64, n_azimuth=1750)
+            t0 = time.perf_counter()
+            _, pts = LR.downsample(s, len(s), 0.2, 1 << 16)
+            r = NR.align(pts, cmap, T_init)
+            print(f"NDT restatement frame {k}: {time.perf_counter() - t0:.1f} s, {len(pts)} points, {r['iterations']} iterations, "
+                  f"status {r['status']}", flush=True)
+        return
+    index = LR.MapIndex(mp, 1.0)
     for k in range(max(a.cpu_frames, 1)):
         s = synthetic.lidar_scan(seed=40 + (a.warmup + k) % 12, n_beams=64, n_azimuth=1750)
         t0 = time.perf_counter()
@@ -54,6 +98,7 @@ def main():
     ap.add_argument("--cpu-frames", type=int, default=1)
     ap.add_argument("--one-frame", action="store_true")
     ap.add_argument("--cpu-only", action="store_true", help="only the restatement's CPU time (needs no GPU)")
+    ap.add_argument("--localiser", choices=("icp", "ndt"), default="icp")
     a = ap.parse_args()
     if a.cpu_only:
         return restatement_only(a)
@@ -61,8 +106,10 @@ def main():
     scans = [synthetic.lidar_scan(seed=40 + i, n_beams=64, n_azimuth=1750) for i in range(12)]   # world frame = sensor at I
     dscans = [torch.from_numpy(s).cuda() for s in scans]
     mp = synthetic.build_map()
-    loc = ScanToMapLocaliser(mp[:, :3])
     T_init = LR.perturbation(0.15, 0.12, 0.05, 1.0)
+    if a.localiser == "ndt":
+        return ndt_main(a, scans, dscans, mp, T_init)
+    loc = ScanToMapLocaliser(mp[:, :3])
 
     def frame(k):
         s = dscans[k % len(dscans)]
@@ -130,6 +177,59 @@ def main():
     out["loop_flagged_frames"] = int(flagged)
     print(f"SPSFilter alone {out['sps_filter_ms']:.3f} ms, LocalisationLoop(sps_cvm) {out['loop_sps_cvm_ms']:.3f} ms per frame "
           f"({flagged} flagged)")
+    print(json.dumps(out))
+
+
+def ndt_main(a, scans, dscans, mp, T_init):
+    map64 = mp[:, :3].astype(np.float64)
+    ScanToMapLocaliser(map64[:1000])                                  # first context of the process: not part of a build time
+    icp, icp_build = build_ms(lambda: ScanToMapLocaliser(map64))
+    ndt, ndt_build = build_ms(lambda: NDTLocaliser(map64))
+    if a.one_frame:
+        for k in range(a.warmup):
+            ndt.submit(dscans[k % len(dscans)], len(dscans[k % len(dscans)]), T_init).result()
+        torch.cuda.synchronize()
+        s = dscans[a.warmup % len(dscans)]
+        r = ndt.submit(s, len(s), T_init).result()
+        print(json.dumps({"one_frame": True, "localiser": "ndt", "status": r.status, "iterations": r.iterations,
+                          "n_points": r.n_points}))
+        return
+    out = {"n_scan": int(np.mean([len(s) for s in scans])), "n_map": len(mp), "n_cells": ndt.n_cells, "frames": a.frames,
+           "warmup": a.warmup, "map_build_ms": {"ndt": round(ndt_build, 3), "icp": round(icp_build, 3)}}
+    for name, loc in (("ndt", ndt), ("icp", icp)):
+        ms, iters, npts, errs = timed_frames(loc, dscans, T_init, a.warmup, a.frames)
+        med, it = float(np.median(ms)), float(np.median(iters))
+        out[name] = {"ms": {"median": round(med, 4), "min": round(min(ms), 4), "max": round(max(ms), 4)},
+                     "iterations": {"median": it, "min": min(iters), "max": max(iters)},
+                     "ms_per_iteration": round(med / max(it, 1), 4), "points_after_thinning": int(np.mean(npts)),
+                     "max_error_m": round(max(errs), 5), "median_error_m": round(float(np.median(errs)), 5)}
+        print(f"{name}  median {med:.3f} ms (min {min(ms):.3f} max {max(ms):.3f}) per frame, iterations median {it:.0f}, "
+              f"{out[name]['ms_per_iteration']:.4f} ms per iteration, error median {out[name]['median_error_m']:.4f} m "
+              f"max {out[name]['max_error_m']:.4f} m", flush=True)
+    print(f"map build: ndt {ndt_build:.2f} ms ({ndt.n_cells} cells), icp grid {icp_build:.2f} ms (host grouping included in both)")
+    cmap = NR.cells(map64, ndt.resolution) if a.cpu_frames else None
+    for k in range(a.cpu_frames):
+        s = scans[(a.warmup + k) % len(scans)]
+        t0 = time.perf_counter()
+        _, pts = LR.downsample(s, len(s), ndt.leaf, ndt.capacity)
+        r = NR.align(pts, cmap, T_init, ndt.iterations, ndt.neighbours, ndt.min_correspondences, ndt.outlier_ratio, ndt.tol_t,
+                     ndt.tol_r)
+        out["restatement_s"] = round(time.perf_counter() - t0, 2)
+        print(f"NDT restatement frame {k}: {out['restatement_s']:.1f} s, {r['iterations']} iterations, status {r['status']}", flush=True)
+    net = net_from_params(O.random_params(seed=0)).cuda().eval().freeze()
+    mpt = torch.from_numpy(mp)
+    for name, loc in (("ndt", ndt), ("icp", icp)):
+        loop = LocalisationLoop(SPSCVMFilter(net, mpt, voxel_size=VS, epsilon=EPS), loc, np.eye(4))
+        t_loop, flagged = [], 0
+        for k in range(a.warmup + a.frames):
+            t0 = time.perf_counter()
+            step = loop.step(scans[k % len(scans)])
+            if k >= a.warmup:
+                t_loop.append(time.perf_counter() - t0)
+                flagged += step.flagged
+        out[name]["loop_sps_cvm_ms"] = round(float(np.median(t_loop)) * 1e3, 4)
+        out[name]["loop_flagged_frames"] = int(flagged)
+        print(f"LocalisationLoop(sps_cvm, {name}) {out[name]['loop_sps_cvm_ms']:.3f} ms per frame ({flagged} flagged)", flush=True)
     print(json.dumps(out))
 
 
