@@ -540,6 +540,34 @@ int sps_ndt_align(sps_ctx *ctx, const double *pts_dev, const int32_t *n_dev, int
                   double *T_out_dev, int32_t *status_dev, double *trace_dev, double *normal_dev, void *scratch_dev,
                   void *stream);
 
+/* ---- NDT localiser, several hypotheses ------------------------------------------------------------------------------
+ * sps_ndt_align from n_hyp start poses in the same launches, and the choice among the end poses by the NDT score.  An
+ * alignment that starts in the wrong basin converges there with status 0; the score at the end poses tells the basins
+ * apart.  In the reference the registration sits in the hdl() step of exp_pipeline/loc_exp_general.bash
+ * (hdl_localization, which ships with a global re-localisation companion for the same need).
+ *
+ * sps_ndt_align_batch: hypothesis k starts from the row-major 4x4 T_init_dev[k] (a device array: 64 poses do not fit in
+ *   a kernel-argument block; the caller leaves it unchanged until the stream has passed the call) and is, operation for
+ *   operation and sum for sum, sps_ndt_align from that pose: T_out_dev[k], status_dev[k], trace_dev[k] and normal_dev[k]
+ *   have the bits of the single call, T_out_dev[k] is T_init_dev[k] bit for bit on status 2 and 3, and a hypothesis whose
+ *   status is final sits out the remaining iterations while the others go on.  The scan points and the map are shared.
+ *   Launches: 1 (initialise) + 2 * iters (A with grid (ceil(cap / 32), n_hyp), B with grid n_hyp) + 2:
+ *     A once more, for every hypothesis at its final pose whatever its status: final_dev[k] = (score, points counted),
+ *        the partial rows added in launch B's block order;
+ *     select: the hypothesis with the highest final score among those with status 0 or 1 and at least min_corr points
+ *        counted at the final pose; equal scores go to the lowest k.  best_dev = (k, status of k, points counted at its
+ *        final pose, n_hyp) and T_best_dev = T_out_dev[k]; where no hypothesis qualifies best_dev = (-1, -1, 0, n_hyp)
+ *        and T_best_dev = T_init_dev[0].
+ *   Arguments are checked as for sps_ndt_align, and 1 <= n_hyp <= SPS_NDT_MAX_HYP.  trace_dev double[n_hyp][iters][4],
+ *   normal_dev (may be NULL) double[n_hyp][iters][28].  scratch_dev: sps_ndt_align_batch_scratch(cap, n_hyp) bytes
+ *   (-1 for arguments out of range).  Never allocates, never synchronises, never raises the sticky error. */
+#define SPS_NDT_MAX_HYP 64
+int64_t sps_ndt_align_batch_scratch(int64_t cap, int n_hyp);
+int sps_ndt_align_batch(sps_ctx *ctx, const double *pts_dev, const int32_t *n_dev, int64_t cap, const double *T_init_dev,
+                        int n_hyp, int iters, int neighbours, int min_corr, double outlier_ratio, double tol_t, double tol_r,
+                        double *T_out_dev, int32_t *status_dev, double *trace_dev, double *normal_dev, double *final_dev,
+                        int32_t *best_dev, double *T_best_dev, void *scratch_dev, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -114,7 +114,25 @@ def submit(name, f, scan, T, prev_pose):
     return f.submit(scan, T)
 
 
-def closed_loop(name, f, pc_map, replay, finish, traj_out, which="icp"):
+def hypothesis_grid(counts, steps):
+    """--hypotheses NA,NB,NYAW / --hypothesis-step DA,DB,DYAW_DEG -> offsets [K, 4, 4]: a grid symmetric around 0 (odd
+    counts) along, across and in yaw, with the identity moved to index 0."""
+    from sps_amd.localiser import pose_grid
+    try:
+        n = [int(v) for v in counts.split(",")]
+        d = [float(v) for v in steps.split(",")]
+    except ValueError:
+        raise click.UsageError("--hypotheses takes three integers, --hypothesis-step three numbers")
+    if len(n) != 3 or len(d) != 3 or any(v < 1 or v % 2 == 0 for v in n):
+        raise click.UsageError("--hypotheses takes three odd counts >= 1 (NA,NB,NYAW), --hypothesis-step three steps")
+    if n[0] * n[1] * n[2] > 64:
+        raise click.UsageError("--hypotheses: at most 64 hypotheses in all")
+    g = pose_grid(*[[(i - c // 2) * step for i in range(c)] for c, step in zip(n, d)])
+    centre = ((n[0] // 2) * n[1] + n[1] // 2) * n[2] + n[2] // 2
+    return np.concatenate([g[[centre]], np.delete(g, centre, axis=0)])
+
+
+def closed_loop(name, f, pc_map, replay, finish, traj_out, which="icp", hypotheses=None):
     """--localise: one LocalisationLoop step per frame, scored against the replayed poses."""
     from sps_amd.localiser import LocalisationLoop, NDTLocaliser, ScanToMapLocaliser
     from sps_amd.trajectory import ape_translation, rotation_angle, write_trajectory
@@ -123,7 +141,7 @@ def closed_loop(name, f, pc_map, replay, finish, traj_out, which="icp"):
     for stamp, scan, pose, map_tr in replay:
         T = map_tr @ pose
         if loop is None:
-            loop = LocalisationLoop(f, localiser, T)
+            loop = LocalisationLoop(f, localiser, T, hypotheses=hypotheses)
         step = loop.step(scan)
         finish(stamp, None, step.filter_result)
         p = step.pose_result
@@ -131,6 +149,10 @@ def closed_loop(name, f, pc_map, replay, finish, traj_out, which="icp"):
         err_r = float(np.degrees(rotation_angle(step.pose, T)))
         print(f"[{stamp}] loc: {p.status:d} {p.iterations:d} {p.n_corr:d} {p.rmse:.4f} | {err_t:.4f} {err_r:.4f}"
               + (" (flagged: the guess is kept)" if step.flagged else ""))
+        if step.batch is not None:
+            b = step.batch
+            print(f"[{stamp}] hypotheses: best {b.best:d} of {len(b.results):d} | scores "
+                  + " ".join(f"{v:.1f}" for v in b.scores) + " | status " + " ".join(str(r.status) for r in b.results))
         stamps.append(stamp)
         ref.append(T)
     if loop is not None and stamps:
@@ -152,9 +174,16 @@ def closed_loop(name, f, pc_map, replay, finish, traj_out, which="icp"):
 @click.option("--localiser", "which", type=click.Choice(("icp", "ndt")), default=None,
               help="with --localise: point-to-point ICP (default) or NDT")
 @click.option("--traj-out", "traj_out", type=str, default=None, help="with --localise: write the estimated trajectory")
-def main(name, weights, sequence, config, epsilon, out_dir, n_synth, localise, which, traj_out):
+@click.option("--hypotheses", "hyp_counts", type=str, default=None,
+              help="with --localiser ndt: NA,NB,NYAW start poses (odd counts) along, across and in yaw around the guess")
+@click.option("--hypothesis-step", "hyp_steps", type=str, default="0.5,0.5,5",
+              help="with --hypotheses: DA,DB,DYAW_DEG, the grid's spacing in m, m and degrees")
+def main(name, weights, sequence, config, epsilon, out_dir, n_synth, localise, which, traj_out, hyp_counts, hyp_steps):
     if which is not None and not localise:
         raise click.UsageError("--localiser needs --localise")
+    if hyp_counts is not None and which != "ndt":
+        raise click.UsageError("--hypotheses needs --localise --localiser ndt")
+    hypotheses = hypothesis_grid(hyp_counts, hyp_steps) if hyp_counts is not None else None
     cfg = yaml.safe_load(open(config))
     if epsilon is None:
         epsilon = float(cfg.get("FILTER", {}).get("THRESHOLD", 0.84))
@@ -189,7 +218,7 @@ def main(name, weights, sequence, config, epsilon, out_dir, n_synth, localise, w
         n_done += 1
 
     if localise:
-        closed_loop(name, f, pc_map, replay, finish, traj_out, which or "icp")
+        closed_loop(name, f, pc_map, replay, finish, traj_out, which or "icp", hypotheses)
     elif traj_out:
         raise click.UsageError("--traj-out needs --localise")
     in_flight, prev_pose = None, None

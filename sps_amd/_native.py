@@ -134,6 +134,9 @@ def _load() -> C.CDLL:
         "sps_ndt_map_cells": (i32, [vp, vp, vp, vp, vp, vp]),
         "sps_ndt_align": (i32, [vp, vp, vp, i64, vp, i32, i32, i32, C.c_double, C.c_double, C.c_double, vp, vp, vp, vp, vp,
                                 vp]),
+        "sps_ndt_align_batch_scratch": (i64, [i64, i32]),
+        "sps_ndt_align_batch": (i32, [vp, vp, vp, i64, vp, i32, i32, i32, i32, C.c_double, C.c_double, C.c_double, vp, vp, vp, vp,
+                                      vp, vp, vp, vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)          # AttributeError here = header/library mismatch: fail loudly
@@ -161,7 +164,8 @@ EXPORTS = ["sps_last_error", "sps_version", "sps_ctx_create", "sps_ctx_destroy",
            "sps_lts_destroy", "sps_lts_project", "sps_lts_forward", "sps_lts_check", "sps_lts_tap",
            "sps_forward_head_n", "sps_transform_rows", "sps_transform_points_n", "sps_radius_crop", "sps_label_filter",
            "sps_loc_downsample_scratch", "sps_loc_align_scratch", "sps_loc_downsample", "sps_loc_align",
-           "sps_ndt_align_scratch", "sps_ndt_map_build", "sps_ndt_map_cells", "sps_ndt_align"]
+           "sps_ndt_align_scratch", "sps_ndt_map_build", "sps_ndt_map_cells", "sps_ndt_align",
+           "sps_ndt_align_batch_scratch", "sps_ndt_align_batch"]
 CROP_BLOCK = 1024          # SPS_CROP_BLOCK: map rows per int of sps_radius_crop's scratch
 
 
@@ -431,6 +435,14 @@ class Context:
         check(lib.sps_ndt_align(self.handle, pts_ptr, n_dev_ptr, int(cap), self._mat(T_init), int(iters), int(neighbours),
                                 int(min_corr), float(outlier_ratio), float(tol_t), float(tol_r), T_out_ptr, status_ptr,
                                 trace_ptr, normal_ptr, scratch_ptr, stream))
+
+    def ndt_align_batch(self, pts_ptr, n_dev_ptr: int, cap: int, T_init_ptr, n_hyp: int, iters: int, neighbours: int,
+                        min_corr: int, outlier_ratio: float, tol_t: float, tol_r: float, T_out_ptr: int, status_ptr: int,
+                        trace_ptr, normal_ptr, final_ptr: int, best_ptr: int, T_best_ptr: int, scratch_ptr: int, stream: int):
+        check(lib.sps_ndt_align_batch(self.handle, pts_ptr, n_dev_ptr, int(cap), T_init_ptr, int(n_hyp), int(iters),
+                                      int(neighbours), int(min_corr), float(outlier_ratio), float(tol_t), float(tol_r),
+                                      T_out_ptr, status_ptr, trace_ptr, normal_ptr, final_ptr, best_ptr, T_best_ptr,
+                                      scratch_ptr, stream))
 
     def train_forward(self, params_ptr: int, numel: int, coords_ptr: int, ld: int, n: int, voxel_size: float,
                       scores_ptr: int, batch_stats_ptr, stream: int):

@@ -210,18 +210,11 @@ __global__ __launch_bounds__(256) void k_loc_assoc(const double *__restrict__ pt
   }
 }
 
-// Launch B, one workgroup of 256.  Thread (seg, col) adds the rows of its run of consecutive blocks in order, thread
-// col adds the LOC_SEG runs in order; thread 0 does the rest.
-__global__ __launch_bounds__(256) void k_loc_solve(const double *__restrict__ partial, const int *__restrict__ n_dev, int cap,
-                                                    int iter, int min_corr, double tol_t, double tol_r, LocPose T_init,
-                                                    double *__restrict__ T, int *__restrict__ status, int *__restrict__ done,
-                                                    double *__restrict__ trace, double *__restrict__ normal) {
-  __shared__ double seg[LOC_SEG][32];
-  __shared__ double tot[32];
-  if (*done) return;
-  const int n = min(cap, max(*n_dev, 0));
-  const int nb = (n + LOC_PTS - 1) / LOC_PTS;
-  const int col = threadIdx.x & 31, sg = threadIdx.x >> 5;
+// The partial rows of `nb` workgroups added in block order by 256 threads t = 0 .. 255 (every thread of the workgroup must
+// call, for the barriers): thread (sg, col) adds the rows of its run of consecutive blocks in order, thread col adds the
+// LOC_SEG runs in order.  tot[0 .. LOC_TERMS) holds the sums once the workgroup has passed the barrier at the end.
+__device__ inline void loc_sum_rows(const double *__restrict__ partial, int nb, int t, double (*seg)[32], double *tot) {
+  const int col = t & 31, sg = t >> 5;
   if (col < LOC_TERMS) {
     const int per = (nb + LOC_SEG - 1) / LOC_SEG;
     const int b1 = min(nb, (sg + 1) * per);
@@ -230,12 +223,24 @@ __global__ __launch_bounds__(256) void k_loc_solve(const double *__restrict__ pa
     seg[sg][col] = s;
   }
   __syncthreads();
-  if (threadIdx.x < LOC_TERMS) {
+  if (t < LOC_TERMS) {
     double s = 0.0;
-    for (int i = 0; i < LOC_SEG; ++i) s = loc_add(s, seg[i][threadIdx.x]);
-    tot[threadIdx.x] = s;
+    for (int i = 0; i < LOC_SEG; ++i) s = loc_add(s, seg[i][t]);
+    tot[t] = s;
   }
   __syncthreads();
+}
+
+// Launch B for one pose, by one workgroup of 256 (k_loc_solve; k_loc_solve_batch in ndt_batch_kernels.inc.h runs it once per
+// hypothesis): loc_sum_rows, then thread 0 does the rest.  T_init is read only when the status becomes 2 or 3.
+__device__ inline void loc_solve_body(const double *__restrict__ partial, const int *__restrict__ n_dev, int cap, int iter,
+                                      int min_corr, double tol_t, double tol_r, const double *__restrict__ T_init,
+                                      double *__restrict__ T, int *__restrict__ status, int *__restrict__ done,
+                                      double *__restrict__ trace, double *__restrict__ normal, double (*seg)[32],
+                                      double *tot) {
+  if (*done) return;
+  const int n = min(cap, max(*n_dev, 0));
+  loc_sum_rows(partial, (n + LOC_PTS - 1) / LOC_PTS, threadIdx.x, seg, tot);
   if (threadIdx.x != 0) return;
   const int n_corr = (int)tot[28];
   const double sum_d2 = tot[27];
@@ -291,7 +296,7 @@ __global__ __launch_bounds__(256) void k_loc_solve(const double *__restrict__ pa
     if (!finite) code = 3;   // an overflowing solve is a singular system too
   }
   if (code >= 0) {
-    for (int i = 0; i < 16; ++i) T[i] = T_init.m[i];
+    for (int i = 0; i < 16; ++i) T[i] = T_init[i];
     status[0] = code;
     *done = 1;
     return;
@@ -327,6 +332,16 @@ __global__ __launch_bounds__(256) void k_loc_solve(const double *__restrict__ pa
     status[0] = 0;
     *done = 1;
   }
+}
+
+// Launch B, one workgroup of 256.
+__global__ __launch_bounds__(256) void k_loc_solve(const double *__restrict__ partial, const int *__restrict__ n_dev, int cap,
+                                                    int iter, int min_corr, double tol_t, double tol_r, LocPose T_init,
+                                                    double *__restrict__ T, int *__restrict__ status, int *__restrict__ done,
+                                                    double *__restrict__ trace, double *__restrict__ normal) {
+  __shared__ double seg[LOC_SEG][32];
+  __shared__ double tot[32];
+  loc_solve_body(partial, n_dev, cap, iter, min_corr, tol_t, tol_r, T_init.m, T, status, done, trace, normal, seg, tot);
 }
 
 #pragma clang fp contract(fast)

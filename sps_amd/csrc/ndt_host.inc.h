@@ -2,6 +2,22 @@
 // (ABI: the "NDT localiser" section of include/sps_hip.h; kernels: ndt_kernels.inc.h).  sps_ndt_map_build allocates and
 // synchronises, like sps_radius_grid_upload; sps_ndt_align does neither: its scratch is the caller's.
 
+namespace {
+// the Gaussian fit of the mixture (Magnusson 2009, eq. 6.8; PCL's gauss_d1_ / gauss_d2_), in float64 on the host; false
+// (and the error text set) where outlier_ratio and the resolution give none
+inline bool ndt_gauss_fit(double res, double outlier_ratio, NdtGauss &gs) {
+  if (!(outlier_ratio > 0.0) || !(outlier_ratio < 1.0)) return fail(SPS_ERR_INVALID, "outlier_ratio must be in (0, 1)"), false;
+  const double c1 = 10.0 * (1.0 - outlier_ratio), c2 = outlier_ratio / (res * res * res);
+  const double d3 = -std::log(c2);
+  const double d1 = -std::log(c1 + c2) - d3;
+  const double d2 = -2.0 * std::log((-std::log(c1 * std::exp(-0.5) + c2) - d3) / d1);
+  if (!std::isfinite(d1) || !std::isfinite(d2) || !(d1 < 0.0) || !(d2 > 0.0))
+    return fail(SPS_ERR_INVALID, "outlier_ratio and resolution give no usable Gaussian fit"), false;
+  gs = NdtGauss{-d1, d2};
+  return true;
+}
+}  // namespace
+
 int64_t sps_ndt_align_scratch(int64_t cap) { return sps_loc_align_scratch(cap); }   // the partial rows of k_loc_solve
 
 int sps_ndt_map_build(sps_ctx *c, const uint64_t *cell_keys_dev, const int32_t *cell_start_dev, const int32_t *cell_pts_dev,
@@ -78,20 +94,12 @@ int sps_ndt_align(sps_ctx *c, const double *pts_dev, const int32_t *n_dev, int64
   if (neighbours != 1 && neighbours != 7) return fail(SPS_ERR_INVALID, "neighbours must be 1 or 7");
   if (cap > SPS_MAX_POINTS || iters > 10000) return fail(SPS_ERR_INVALID, "too many points or iterations");
   if (std::isnan(tol_t) || std::isnan(tol_r)) return fail(SPS_ERR_INVALID, "tolerances must not be NaN");
-  if (!(outlier_ratio > 0.0) || !(outlier_ratio < 1.0)) return fail(SPS_ERR_INVALID, "outlier_ratio must be in (0, 1)");
-  // the Gaussian fit of the mixture (Magnusson 2009, eq. 6.8; PCL's gauss_d1_ / gauss_d2_), in float64 on the host
-  const double res = c->ndt.resolution;
-  const double c1 = 10.0 * (1.0 - outlier_ratio), c2 = outlier_ratio / (res * res * res);
-  const double d3 = -std::log(c2);
-  const double d1 = -std::log(c1 + c2) - d3;
-  const double d2 = -2.0 * std::log((-std::log(c1 * std::exp(-0.5) + c2) - d3) / d1);
-  if (!std::isfinite(d1) || !std::isfinite(d2) || !(d1 < 0.0) || !(d2 > 0.0))
-    return fail(SPS_ERR_INVALID, "outlier_ratio and resolution give no usable Gaussian fit");
+  NdtGauss gs;
+  if (!ndt_gauss_fit(c->ndt.resolution, outlier_ratio, gs)) return SPS_ERR_INVALID;
   HIP_TRY(hipSetDevice(c->device));
   hipStream_t st = (hipStream_t)stream;
   LocPose T0;
   for (int i = 0; i < 16; ++i) T0.m[i] = T_init_host[i];
-  const NdtGauss gs{-d1, d2};
   const int nb = (int)loc_align_blocks(cap);
   double *partial = (double *)scratch_dev;
   int *done = (int *)(partial + (size_t)nb * LOC_TERMS);

@@ -152,13 +152,20 @@ __device__ inline double ndt_symrow(const double *m, int i, const double b[3]) {
 //            in LDS;
 //   phase 2: lane l forms terms l, l + 8, l + 16, l + 24 of the point, adding the contributing cells in lookup order;
 //   phase 3: thread l < LOC_TERMS adds the workgroup's points in point order and writes entry l of the partial row.
-__global__ __launch_bounds__(256) void k_ndt_assoc(const double *__restrict__ pts, const int *__restrict__ n_dev, int cap,
-                                                    NdtMap m, NdtGauss gs, int neighbours, const double *__restrict__ T,
-                                                    const int *__restrict__ done, double *__restrict__ partial) {
-  __shared__ double hit[LOC_PTS][7][NDT_HIT];
-  __shared__ int hit_ok[LOC_PTS][NDT_LANES];
-  __shared__ double terms[LOC_PTS][LOC_TERMS];
-  if (*done) return;
+// The body is shared with k_ndt_assoc_batch (ndt_batch_kernels.inc.h), which runs it once per hypothesis: T is the pose,
+// partial the rows of that pose, blockIdx.x the workgroup's place among them.
+struct NdtAssocLds {
+  double hit[LOC_PTS][7][NDT_HIT];
+  int hit_ok[LOC_PTS][NDT_LANES];
+  double terms[LOC_PTS][LOC_TERMS];
+};
+
+__device__ inline void ndt_assoc_body(const double *__restrict__ pts, const int *__restrict__ n_dev, int cap, const NdtMap &m,
+                                      const NdtGauss &gs, int neighbours, const double *__restrict__ T,
+                                      double *__restrict__ partial, NdtAssocLds &lds) {
+  double(*hit)[7][NDT_HIT] = lds.hit;
+  int(*hit_ok)[NDT_LANES] = lds.hit_ok;
+  double(*terms)[LOC_TERMS] = lds.terms;
   const int n = min(cap, max(*n_dev, 0));
   const int base = blockIdx.x * LOC_PTS;
   if (base >= n) return;
@@ -245,6 +252,14 @@ __global__ __launch_bounds__(256) void k_ndt_assoc(const double *__restrict__ pt
     for (int p = 0; p < LOC_PTS; ++p) s = loc_add(s, terms[p][threadIdx.x]);
     partial[(size_t)blockIdx.x * LOC_TERMS + threadIdx.x] = s;
   }
+}
+
+__global__ __launch_bounds__(256) void k_ndt_assoc(const double *__restrict__ pts, const int *__restrict__ n_dev, int cap,
+                                                    NdtMap m, NdtGauss gs, int neighbours, const double *__restrict__ T,
+                                                    const int *__restrict__ done, double *__restrict__ partial) {
+  __shared__ NdtAssocLds lds;
+  if (*done) return;
+  ndt_assoc_body(pts, n_dev, cap, m, gs, neighbours, T, partial, lds);
 }
 
 #pragma clang fp contract(fast)

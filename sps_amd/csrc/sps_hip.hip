@@ -149,6 +149,7 @@ int fail(int code, const char *fmt, ...) {
 #include "sps_filter_kernels.inc.h"
 #include "loc_kernels.inc.h"
 #include "ndt_kernels.inc.h"
+#include "ndt_batch_kernels.inc.h"
 
 // ------------------------------------------------------------------------------------------
 // context
@@ -2252,5 +2253,6 @@ int sps_get_feature(sps_ctx *c, const char *name, float *out_dev, int64_t *rows,
 #include "baseline_host.inc.h"
 #include "loc_host.inc.h"
 #include "ndt_host.inc.h"
+#include "ndt_batch_host.inc.h"
 
 }  // extern "C"

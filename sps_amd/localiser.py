@@ -17,6 +17,10 @@ synchronises; ``PendingPose.result()`` is the one synchronisation.  A scan that 
 transform (ndt_omp's 1 m cells and DIRECT7 neighbourhood by default; C ABI: the "NDT localiser" section; DESIGN.md
 "NDT localiser").  Thinning, the 6 x 6 solve, the outputs and the status codes are the ICP's; still no UKF, no IMU.
 
+``NDTLocaliser.submit_batch`` registers one scan from several start poses in the same launches and selects among the
+end poses by the NDT score at each (C ABI: "NDT localiser, several hypotheses"): a start in the wrong basin
+converges there with status 0, and only the score tells.  ``pose_grid`` builds the offsets.
+
 ``LocalisationLoop`` closes the loop for any of the seven filters of scripts/filter_sequence.py, around either localiser.
 """
 from __future__ import annotations
@@ -69,6 +73,76 @@ class PendingPose:
         return PoseResult(h[:16].reshape(4, 4).copy(), code, it, n_corr, rmse, trace, normal, n_points)
 
 
+@dataclass
+class BatchPoseResult:
+    results: list              # K PoseResult, hypothesis k as a single alignment from its start pose would give it
+    scores: np.ndarray         # [K] the NDT score at the final pose of every hypothesis
+    counts: np.ndarray         # [K] int, the scan points counted at that pose
+    best: int                  # the hypothesis selected, or -1 where none has status 0 / 1 and enough points counted
+    pose: np.ndarray           # 4x4: results[best].pose, or the first start pose when best is -1
+
+
+class PendingPoses:
+    """A batch of localisations whose work has been issued; everything lives on the device until result()."""
+
+    def __init__(self, n_hyp, iters, with_normal, host, event, keep):
+        self._n_hyp, self._iters, self._with_normal, self._host, self._event, self._keep = n_hyp, iters, with_normal, host, event, keep
+
+    def result(self) -> BatchPoseResult:
+        self._event.synchronize()                                    # the one host synchronisation
+        h = self._host.numpy()
+        K, I = self._n_hyp, self._iters
+        o = _batch_layout(K, I, self._with_normal)
+        T_out = h[o["T_out"]:o["T_out"] + 16 * K].reshape(K, 4, 4)
+        status = h[o["status"]:o["status"] + 2 * K].view(np.int32).reshape(K, 4)
+        n_points = int(h[o["n_points"]:o["n_points"] + 1].view(np.int32)[0])
+        best = h[o["best"]:o["best"] + 2].view(np.int32)
+        final = h[o["final"]:o["final"] + 2 * K].reshape(K, 2)
+        trace = h[o["trace"]:o["trace"] + 4 * K * I].reshape(K, I, 4)
+        normal = h[o["normal"]:o["normal"] + 28 * K * I].reshape(K, I, 28) if self._with_normal else None
+        results = []
+        for k in range(K):
+            code, it, n_corr, _ = (int(x) for x in status[k])
+            tr = trace[k, :it].copy()
+            rmse = math.sqrt(tr[-1, 1] / n_corr) if it and n_corr > 0 else float("nan")
+            results.append(PoseResult(T_out[k].copy(), code, it, n_corr, rmse, tr,
+                                      normal[k, :it].copy() if normal is not None else None, n_points))
+        return BatchPoseResult(results, final[:, 0].copy(), final[:, 1].astype(np.int64), int(best[0]),
+                               h[o["T_best"]:o["T_best"] + 16].reshape(4, 4).copy())
+
+
+def _batch_layout(K, I, with_normal):
+    """offsets (in doubles) of a batch's one float64 buffer: T_out[K][16] | status int32[K][4] | n_points int32 (+ pad) |
+    best int32[4] | T_best[16] | final[K][2] | trace[K][I][4] | normal[K][I][28]"""
+    o, at = {}, 0
+    for name, size in (("T_out", 16 * K), ("status", 2 * K), ("n_points", 1), ("best", 2), ("T_best", 16), ("final", 2 * K),
+                       ("trace", 4 * K * I), ("normal", 28 * K * I if with_normal else 0)):
+        o[name] = at
+        at += size
+    o["size"] = at
+    return o
+
+
+def pose_grid(along, across, yaw_deg) -> np.ndarray:
+    """Body-frame offsets D(a, b, psi) = [[Rz(psi), (a, b, 0)^T], [0, 1]] as float64 [K, 4, 4], a in ``along`` (m), b in
+    ``across`` (m), psi in ``yaw_deg`` (degrees), k = (ia * len(across) + ib) * len(yaw_deg) + ipsi.  The start pose of
+    hypothesis k is ``T_center @ D_k``."""
+    along, across, yaw_deg = (np.atleast_1d(np.asarray(v, dtype=np.float64)) for v in (along, across, yaw_deg))
+    out = np.tile(np.eye(4), (len(along) * len(across) * len(yaw_deg), 1, 1))
+    k = 0
+    for a in along:
+        for b in across:
+            for psi in yaw_deg:
+                c, sn = math.cos(math.radians(psi)), math.sin(math.radians(psi))
+                out[k, :2, :2] = [[c, 0.0 - sn], [sn, c]]                     # 0.0 - 0.0 is +0.0: psi = 0 gives the identity, bit for bit
+                out[k, :2, 3] = [a, b]
+                k += 1
+    return out
+
+
+MAX_HYPOTHESES = 64            # SPS_NDT_MAX_HYP
+
+
 class ScanToMapLocaliser:
     """``ScanToMapLocaliser(map_points)(rows, count, T_init)`` -> PoseResult.  The map's uniform grid (cell size =
     ``max_distance``) lives in a native context of the localiser's own, so the grid of the offline item path
@@ -111,34 +185,40 @@ class ScanToMapLocaliser:
             self._ds_rows = rows
         return self._ds_scratch
 
-    @torch.no_grad()
-    def submit(self, rows, count, T_init, with_normal: bool = False, iterations: int = None) -> PendingPose:
-        """rows: device tensor [n_max, >= 3] (float32; other dtypes are converted); count: an int or a device int32 tensor
-        holding the number of valid rows; T_init: 4x4.  Issued on the current stream."""
+    def _checked_rows(self, rows):
         if not (torch.is_tensor(rows) and rows.is_cuda and rows.device == self.device):
             raise TypeError(f"{type(self).__name__}.submit needs a tensor on the localiser's device")
         if rows.dim() != 2 or rows.shape[1] < 3:
             raise ValueError(f"rows must be [n, >=3], got {tuple(rows.shape)}")
-        T = _pose(T_init)
-        if T is None or not np.isfinite(T).all():
-            raise ValueError("T_init must be a finite 4x4 matrix")
         if rows.dtype != torch.float32:
             rows = rows.to(torch.float32)
         if rows.shape[0] and rows.stride(1) != 1:
             rows = rows.contiguous()
+        return rows
+
+    def _count_on_device(self, count, n_max):
+        if torch.is_tensor(count):
+            if count.dtype != torch.int32 or count.device != self.device or count.numel() < 1:
+                raise TypeError("count must be an int or an int32 tensor on the localiser's device")
+            return count
+        if not 0 <= int(count) <= n_max:
+            raise ValueError(f"count must be in [0, {n_max}], got {count}")
+        return torch.full((1,), int(count), dtype=torch.int32, device=self.device)
+
+    @torch.no_grad()
+    def submit(self, rows, count, T_init, with_normal: bool = False, iterations: int = None) -> PendingPose:
+        """rows: device tensor [n_max, >= 3] (float32; other dtypes are converted); count: an int or a device int32 tensor
+        holding the number of valid rows; T_init: 4x4.  Issued on the current stream."""
+        rows = self._checked_rows(rows)
+        T = _pose(T_init)
+        if T is None or not np.isfinite(T).all():
+            raise ValueError("T_init must be a finite 4x4 matrix")
         n_max, dev = rows.shape[0], self.device
         K = self.iterations if iterations is None else int(iterations)
         with torch.cuda.device(dev):
             st = torch.cuda.current_stream()
             s = st.cuda_stream
-            if torch.is_tensor(count):
-                if count.dtype != torch.int32 or count.device != dev or count.numel() < 1:
-                    raise TypeError("count must be an int or an int32 tensor on the localiser's device")
-                n_dev = count
-            else:
-                if not 0 <= int(count) <= n_max:
-                    raise ValueError(f"count must be in [0, {n_max}], got {count}")
-                n_dev = torch.full((1,), int(count), dtype=torch.int32, device=dev)
+            n_dev = self._count_on_device(count, n_max)
             # one float64 buffer per frame: T_out[16] | status int32[4] | n_points int32 (+ pad) | trace[K][4] | normal[K][28]
             out = torch.zeros(19 + 32 * K if with_normal else 19 + 4 * K, dtype=torch.float64, device=dev)
             base = out.data_ptr()
@@ -211,11 +291,55 @@ class NDTLocaliser(ScanToMapLocaliser):
             self._pts = torch.empty((self.capacity, 3), dtype=torch.float64, device=self.device)
             self._align_scratch = torch.empty(_native.lib.sps_ndt_align_scratch(self.capacity), dtype=torch.uint8, device=self.device)
             self._ds_scratch, self._ds_rows = None, -1
+            self._batch_scratch, self._batch_hyp = None, 0
 
     def _align(self, n_ptr, T, K, T_out_ptr, status_ptr, trace_ptr, normal_ptr, s):
         self.ctx.ndt_align(self._pts.data_ptr(), n_ptr, self.capacity, T, K, self.neighbours, self.min_correspondences,
                            self.outlier_ratio, self.tol_t, self.tol_r, T_out_ptr, status_ptr, trace_ptr, normal_ptr,
                            self._align_scratch.data_ptr(), s)
+
+    @torch.no_grad()
+    def submit_batch(self, rows, count, T_inits, with_normal: bool = False, iterations: int = None) -> PendingPoses:
+        """``submit`` from the K start poses ``T_inits`` [K, 4, 4] (1 <= K <= 64) at once: the scan is thinned once, every
+        hypothesis is registered as ``submit`` would register it from its pose, and the hypothesis with the highest NDT
+        score at its final pose is selected among those with status 0 / 1 and at least ``min_correspondences`` points
+        counted there (equal scores: the lowest index).  Issued on the current stream; ``result()`` -> BatchPoseResult."""
+        rows = self._checked_rows(rows)
+        T = np.ascontiguousarray(np.asarray(T_inits, dtype=np.float64))
+        if T.ndim != 3 or T.shape[1:] != (4, 4) or not 1 <= len(T) <= MAX_HYPOTHESES or not np.isfinite(T).all():
+            raise ValueError(f"T_inits must be finite, [K, 4, 4] with 1 <= K <= {MAX_HYPOTHESES}")
+        n_max, dev, K = rows.shape[0], self.device, len(T)
+        I = self.iterations if iterations is None else int(iterations)
+        o = _batch_layout(K, I, with_normal)
+        with torch.cuda.device(dev):
+            st = torch.cuda.current_stream()
+            s = st.cuda_stream
+            n_dev = self._count_on_device(count, n_max)
+            T_host = torch.from_numpy(T).pin_memory()
+            T_dev = T_host.to(dev, non_blocking=True)                # on the caller's stream; both stay with the pending object
+            out = torch.zeros(o["size"], dtype=torch.float64, device=dev)
+            base = out.data_ptr()
+            self.ctx.loc_downsample(rows.data_ptr() if n_max else None, rows.stride(0) if n_max else 3, n_max,
+                                    n_dev.data_ptr(), self.leaf, self._pts.data_ptr(), self.capacity, base + o["n_points"] * 8,
+                                    self._downsample_scratch(n_max).data_ptr(), s)
+            if K > self._batch_hyp:                                  # grows with the largest batch seen (stream-ordered reuse)
+                self._batch_scratch = torch.empty(_native.lib.sps_ndt_align_batch_scratch(self.capacity, K), dtype=torch.uint8,
+                                                  device=dev)
+                self._batch_hyp = K
+            self.ctx.ndt_align_batch(self._pts.data_ptr(), base + o["n_points"] * 8, self.capacity, T_dev.data_ptr(), K, I,
+                                     self.neighbours, self.min_correspondences, self.outlier_ratio, self.tol_t, self.tol_r,
+                                     base + o["T_out"] * 8, base + o["status"] * 8, base + o["trace"] * 8 if I else None,
+                                     base + o["normal"] * 8 if with_normal and I else None, base + o["final"] * 8,
+                                     base + o["best"] * 8, base + o["T_best"] * 8, self._batch_scratch.data_ptr(), s)
+            host = torch.empty(out.numel(), dtype=torch.float64).pin_memory()
+            host.copy_(out, non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record(st)
+        return PendingPoses(K, I, with_normal, host, ev, (rows, n_dev, out, T_host, T_dev))
+
+    def submit_filtered_batch(self, pending, T_inits, **kw) -> PendingPoses:
+        """``submit_batch`` of the kept rows of a pending SPSFilter / SPSCVMFilter frame, without the frame's result()."""
+        return self.submit_batch(pending._filtered, pending.count_dev, T_inits, **kw)
 
     def map_cells(self):
         """Debug: (keys uint64 [C], counts int32 [C], means [C, 3], inverse covariances [C, 6] as (xx, xy, xz, yy, yz, zz),
@@ -238,7 +362,8 @@ class LoopStep:
     pose_result: PoseResult
     guess: np.ndarray          # the pose the frame started from
     pose: np.ndarray           # the corrected pose handed on (the guess when flagged)
-    flagged: bool              # the localiser reported status 2 or 3
+    flagged: bool              # the localiser reported status 2 or 3 (with hypotheses: none of them was selected)
+    batch: BatchPoseResult = None   # with hypotheses: every hypothesis of the frame (pose_result is the selected one's)
 
 
 class LocalisationLoop:
@@ -254,11 +379,26 @@ class LocalisationLoop:
          the guess is taken as the corrected pose and the step is flagged.
 
     One host synchronisation per frame where the filter's pending frame exposes its device rows (``_filtered`` and
-    ``count_dev``: SPSFilter, SPSCVMFilter), two otherwise."""
+    ``count_dev``: SPSFilter, SPSCVMFilter), two otherwise.
 
-    def __init__(self, filter, localiser, initial_pose):
+    ``hypotheses`` (NDTLocaliser only; None: one registration from the guess): offsets [K, 4, 4] with ``hypotheses[0]``
+    the identity, e.g. from ``pose_grid``.  A frame is then registered from ``guess @ hypotheses[k]`` for every k at once
+    (``submit_batch``) and the selected pose is handed on; a frame in which no hypothesis is selected (best = -1) is
+    flagged and keeps the guess, as status 2 / 3 does without hypotheses."""
+
+    def __init__(self, filter, localiser, initial_pose, hypotheses=None):
         from .sps_filters import ConstantVelocityModel
         self.filter, self.localiser = filter, localiser
+        self.hypotheses = None
+        if hypotheses is not None:
+            H = np.array(hypotheses, dtype=np.float64)
+            if H.ndim != 3 or H.shape[1:] != (4, 4) or not 1 <= len(H) <= MAX_HYPOTHESES or not np.isfinite(H).all():
+                raise ValueError(f"hypotheses must be finite, [K, 4, 4] with 1 <= K <= {MAX_HYPOTHESES}")
+            if not np.array_equal(H[0], np.eye(4)):
+                raise ValueError("hypotheses[0] must be the identity")
+            if not hasattr(localiser, "submit_batch"):
+                raise TypeError("hypotheses need a localiser with submit_batch (NDTLocaliser)")
+            self.hypotheses = H
         self.initial_pose = np.array(_pose(initial_pose), dtype=np.float64)
         self.model = ConstantVelocityModel()
         self.model.poses = []                                        # corrected poses only
@@ -281,8 +421,33 @@ class LocalisationLoop:
             return f.submit(scan)
         return f.submit(scan, guess)
 
+    def start_poses(self, guess) -> np.ndarray:
+        """[K, 4, 4]: ``guess @ hypotheses[k]``"""
+        return np.stack([guess @ h for h in self.hypotheses])
+
+    def _step_batch(self, scan, guess) -> LoopStep:
+        pend = self._submit_filter(scan, guess)
+        starts = self.start_poses(guess)
+        if hasattr(pend, "count_dev") and hasattr(pend, "_filtered"):
+            pose_pend = self.localiser.submit_filtered_batch(pend, starts)
+            fres = pend.result()
+            bres = pose_pend.result()
+        else:
+            fres = pend.result()
+            kept = fres.filtered
+            bres = self.localiser.submit_batch(kept, len(kept), starts).result()
+        flagged = bres.best < 0
+        pose = guess if flagged else bres.pose
+        self.model.add_pose(pose)
+        if hasattr(self.filter, "add_pose"):
+            self.filter.add_pose(pose)
+        self.poses.append(np.array(pose, dtype=np.float64))
+        return LoopStep(fres, bres.results[max(bres.best, 0)], guess, self.poses[-1], flagged, bres)
+
     def step(self, scan) -> LoopStep:
         guess = self.guess()
+        if self.hypotheses is not None:
+            return self._step_batch(scan, guess)
         pend = self._submit_filter(scan, guess)
         if hasattr(pend, "count_dev") and hasattr(pend, "_filtered"):
             pose_pend = self.localiser.submit_filtered(pend, guess)  # no synchronisation between filter and localiser

@@ -10,11 +10,14 @@ synthetic.build_map() map, max_distance 1 m, leaf 0.2 m):
               SPSFilter alone on the same scans
 
     python tools/localiser_timing.py [--frames 200] [--warmup 20] [--cpu-frames 1] [--one-frame] [--cpu-only]
-                                     [--localiser {icp,ndt}]
+                                     [--localiser {icp,ndt}] [--hypotheses K]
 
 ``--localiser ndt`` times sps_amd.localiser.NDTLocaliser (1 m cells, 7 neighbours) on the same frames and from the same
 start, prints the ICP's per-frame figures of the same session beside it and the build time of both maps; the
 restatement is then tests/ndt_reference.py.
+
+``--localiser ndt --hypotheses K`` times NDTLocaliser.submit_batch from K start poses (the guess and offsets 0.5 m apart
+around it) against K back-to-back submit calls from the same poses, and against one submit.
 
 ``--one-frame`` runs a warm-up and ONE localiser frame: the target of a ``rocprofv3 --kernel-trace --stats`` run.
 """
@@ -99,7 +102,11 @@ def main():
     ap.add_argument("--one-frame", action="store_true")
     ap.add_argument("--cpu-only", action="store_true", help="only the restatement's CPU time (needs no GPU)")
     ap.add_argument("--localiser", choices=("icp", "ndt"), default="icp")
+    ap.add_argument("--hypotheses", type=int, default=0, help="with --localiser ndt: time submit_batch of K start poses "
+                    "against K back-to-back submit calls")
     a = ap.parse_args()
+    if a.hypotheses and (a.localiser != "ndt" or not 1 <= a.hypotheses <= 64):
+        ap.error("--hypotheses K needs --localiser ndt and 1 <= K <= 64")
     if a.cpu_only:
         return restatement_only(a)
     assert torch.cuda.is_available(), "localiser_timing needs the MI355X"
@@ -107,6 +114,8 @@ def main():
     dscans = [torch.from_numpy(s).cuda() for s in scans]
     mp = synthetic.build_map()
     T_init = LR.perturbation(0.15, 0.12, 0.05, 1.0)
+    if a.localiser == "ndt" and a.hypotheses:
+        return ndt_batch_main(a, dscans, mp, T_init)
     if a.localiser == "ndt":
         return ndt_main(a, scans, dscans, mp, T_init)
     loc = ScanToMapLocaliser(mp[:, :3])
@@ -230,6 +239,74 @@ def ndt_main(a, scans, dscans, mp, T_init):
         out[name]["loop_sps_cvm_ms"] = round(float(np.median(t_loop)) * 1e3, 4)
         out[name]["loop_flagged_frames"] = int(flagged)
         print(f"LocalisationLoop(sps_cvm, {name}) {out[name]['loop_sps_cvm_ms']:.3f} ms per frame ({flagged} flagged)", flush=True)
+    print(json.dumps(out))
+
+
+def hypothesis_starts(T_init, K):
+    """K start poses around T_init: the guess itself, then offsets 0.5 m apart along and across, outwards, in the order
+    pose_grid gives a 9 x 9 grid sorted by distance (so a smaller K is a prefix of a larger one)."""
+    from sps_amd.localiser import pose_grid
+    g = pose_grid([0.5 * i for i in range(-4, 5)], [0.5 * i for i in range(-4, 5)], 0.0)
+    order = np.argsort(np.hypot(g[:, 0, 3], g[:, 1, 3]), kind="stable")
+    return np.stack([T_init @ g[k] for k in order[:K]])
+
+
+def ndt_batch_main(a, dscans, mp, T_init):
+    """--hypotheses K: hipEvent time around one submit_batch of K start poses against K back-to-back submit calls from the
+    same poses, interleaved frame by frame in one run."""
+    K = a.hypotheses
+    ndt = NDTLocaliser(mp[:, :3].astype(np.float64))
+    starts = hypothesis_starts(T_init, K)
+    st = torch.cuda.current_stream()
+    if a.one_frame:
+        for k in range(a.warmup):
+            ndt.submit_batch(dscans[k % len(dscans)], len(dscans[k % len(dscans)]), starts).result()
+        torch.cuda.synchronize()
+        s = dscans[a.warmup % len(dscans)]
+        r = ndt.submit_batch(s, len(s), starts).result()
+        print(json.dumps({"one_frame": True, "localiser": "ndt", "hypotheses": K, "best": r.best,
+                          "iterations": [p.iterations for p in r.results], "n_points": r.results[0].n_points}))
+        return
+    t_batch, t_single, t_one, iters, best, errs = [], [], [], [], [], []
+    for k in range(a.warmup + a.frames):
+        s = dscans[k % len(dscans)]
+        e = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
+        e[0].record(st)
+        pend = ndt.submit_batch(s, len(s), starts)
+        e[1].record(st)
+        r = pend.result()
+        e[2].record(st)
+        singles = [ndt.submit(s, len(s), T) for T in starts]
+        e[3].record(st)
+        singles = [p.result() for p in singles]
+        e[3].synchronize()
+        assert all(x.pose.tobytes() == y.pose.tobytes() and x.iterations == y.iterations for x, y in zip(r.results, singles))
+        if k >= a.warmup:
+            t_batch.append(e[0].elapsed_time(e[1]))
+            t_single.append(e[2].elapsed_time(e[3]))
+            iters.append(max(p.iterations for p in r.results))
+            best.append(r.best)
+            errs.append(LR.pose_difference(r.pose, np.eye(4))[0])
+    for k in range(a.warmup + a.frames):                                   # one submit from the guess: the K = 1 yardstick
+        s = dscans[k % len(dscans)]
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(st)
+        pend = ndt.submit(s, len(s), starts[0])
+        e1.record(st)
+        pend.result()
+        e1.synchronize()
+        if k >= a.warmup:
+            t_one.append(e0.elapsed_time(e1))
+    mb, ms, m1, it = float(np.median(t_batch)), float(np.median(t_single)), float(np.median(t_one)), float(np.median(iters))
+    out = {"hypotheses": K, "frames": a.frames, "warmup": a.warmup,
+           "batch_ms": {"median": round(mb, 4), "min": round(min(t_batch), 4), "max": round(max(t_batch), 4)},
+           "k_single_ms": {"median": round(ms, 4), "min": round(min(t_single), 4), "max": round(max(t_single), 4)},
+           "one_submit_ms": {"median": round(m1, 4), "min": round(min(t_one), 4), "max": round(max(t_one), 4)},
+           "iterations_max_over_hypotheses_median": it, "batch_ms_per_iteration": round(mb / max(it, 1), 4),
+           "speedup": round(ms / mb, 3), "best": sorted(set(best)), "max_error_m": round(max(errs), 5)}
+    print(f"K = {K}: submit_batch median {mb:.3f} ms (min {min(t_batch):.3f} max {max(t_batch):.3f}), {K} x submit median "
+          f"{ms:.3f} ms, one submit {m1:.3f} ms; {it:.0f} iterations (longest hypothesis), {out['batch_ms_per_iteration']:.4f} ms "
+          f"per iteration; best {out['best']}, error of the selected pose max {out['max_error_m']:.4f} m", flush=True)
     print(json.dumps(out))
 
 
