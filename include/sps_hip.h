@@ -249,7 +249,10 @@ int sps_filter_finish(sps_ctx *ctx, const float *scores_dev, int64_t n, const fl
  * order is the tree's traversal order, i.e. unspecified).
  * The map is binned by the caller into cells of size cell_size >= r: cell_keys (u64, see
  * sps_amd/datasets/blt_dataset.py), cell_start [n_cells+1], cell_pts [m] (map indices grouped by cell),
- * map_xyz float64 [m,3] compact.  The ctx keeps device copies.  Synchronises. */
+ * map_xyz float64 [m,3] compact.  The ctx keeps device copies.  Synchronises.
+ * Cell index: floor(v / cell_size) per axis, a float64 division -- the keys must be built with that rule, and every
+ * query (sps_radius_count / _fill / _item, sps_loc_align) finds the cell of its point with it, as the uploaded keys.
+ * (A product with 1 / cell_size is NOT the same rule: it differs by one cell next to a face.) */
 int sps_radius_grid_upload(sps_ctx *ctx, const uint64_t *cell_keys_dev, const int32_t *cell_start_dev,
                            const int32_t *cell_pts_dev, const double *map_xyz_dev, int64_t n_cells, int64_t m,
                            double cell_size, double r, void *stream);
@@ -478,7 +481,8 @@ int sps_label_filter(sps_ctx *ctx, const float *logits_dev, int64_t ld_logits, i
  * sps_loc_align: `iters` iterations of point-to-point ICP of pts_dev (f64 [cap][3], the first min(*n_dev, cap) used)
  *   against the map of the context's radius grid (sps_radius_grid_upload with cell_size = r = the correspondence
  *   distance), starting from the row-major 4x4 T_init_host.  Two launches per iteration:
- *     A: q = R p + t as ((r0*x + r1*y) + r2*z) + t; the nearest map point m over the 27 cells around q with
+ *     A: q = R p + t as ((r0*x + r1*y) + r2*z) + t; the nearest map point m over the 27 cells around q (cell index
+ *        floor(v / cell_size) per axis, as the uploaded keys) with
  *        d2 = (ex*ex + ey*ey) + ez*ez <= r*r, e = q - m, ties to the lowest map index; the terms of H = sum J^T J and
  *        g = sum J^T e with J = [ -[q]x | I ] (unknown delta = (omega, v)), each entry as (a0*b0 + a1*b1) + a2*b2 over
  *        the three residual rows; one partial row per workgroup, added in point order.

@@ -377,17 +377,21 @@ __global__ __launch_bounds__(SCAN_BLOCK) void k_stable_write(const float *__rest
 // The map is binned once into a uniform grid of cell size >= r (sorted by cell, ascending point index
 // inside a cell); a query visits the 27 cells around the scan point and applies the exact float64 test
 // dx*dx + dy*dy + dz*dz <= r*r (no FMA contraction: same arithmetic as scipy's cKDTree leaf test).
+// The cell of a coordinate is floor(v / cell_size), a true division, as the caller's keys (radius_grid_cells:
+// torch.floor of xyz divided by a device tensor holding cell), loc_voxel_key and the NDT kernels compute it.  floor(v * (1 / cell_size)) differs from it by
+// one on values next to a face when cell_size is not a power of two; a map point at distance ~ r then lies two cells
+// from the cell the query believes it is in and the 27-cell lookup never visits it (tests/test_hip_boundaries.py).
 // ------------------------------------------------------------------------------------------
 struct RadiusGrid {
   HashTable h;             // cell key -> cell id (rank)
   const int *cell_start;   // [C + 1]
   const int *cell_pts;     // [M] map point indices, grouped by cell
   const double *xyz;       // [M, 3] map points (compact)
-  double inv_cell, r2;
+  double cell_size, r2;
 };
 
-__device__ inline bool radius_cell(double v, double inv_cell, long long &c) {
-  const double f = floor(v * inv_cell);
+__device__ inline bool radius_cell(double v, double cell_size, long long &c) {
+  const double f = floor(__ddiv_rn(v, cell_size));
   if (!(f >= -1048575.0 && f <= 1048575.0)) return false;
   c = (long long)f;
   return true;
@@ -428,7 +432,7 @@ __global__ void k_radius_query(const TIN *__restrict__ scan, int64_t ld, int n, 
   int cnt = 0;
   int64_t *dst = MODE == 1 ? out + offsets[tid] : nullptr;
   const int rb = MODE == 2 ? *io.row_base + offsets32[tid] : 0;
-  if (radius_cell(px, g.inv_cell, cx) && radius_cell(py, g.inv_cell, cy) && radius_cell(pz, g.inv_cell, cz)) {
+  if (radius_cell(px, g.cell_size, cx) && radius_cell(py, g.cell_size, cy) && radius_cell(pz, g.cell_size, cz)) {
     const int s = hash_find_slot(g.h, radius_key(cx + (c27 % 3 - 1), cy + ((c27 / 3) % 3 - 1), cz + (c27 / 9 - 1)));
     if (s >= 0) {
       const int c = g.h.rank[s];

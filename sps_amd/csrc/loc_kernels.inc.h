@@ -155,7 +155,7 @@ __global__ __launch_bounds__(256) void k_loc_assoc(const double *__restrict__ pt
                          R[4 * a + 3]);
       long long cx, cy, cz;
       int c_lo = 0, c_hi = 0;
-      if (lane < 27 && radius_cell(q[0], g.inv_cell, cx) && radius_cell(q[1], g.inv_cell, cy) && radius_cell(q[2], g.inv_cell, cz)) {
+      if (lane < 27 && radius_cell(q[0], g.cell_size, cx) && radius_cell(q[1], g.cell_size, cy) && radius_cell(q[2], g.cell_size, cz)) {
         const int s = hash_find_slot(g.h, radius_key(cx + (lane % 3 - 1), cy + ((lane / 3) % 3 - 1), cz + (lane / 9 - 1)));
         if (s >= 0) {
           const int c = g.h.rank[s];

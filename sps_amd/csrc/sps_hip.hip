@@ -1938,7 +1938,7 @@ int sps_radius_grid_upload(sps_ctx *c, const uint64_t *cell_keys_dev, const int3
   c->rg.cell_start = (const int *)start;
   c->rg.cell_pts = (const int *)pts;
   c->rg.xyz = (const double *)xyz;
-  c->rg.inv_cell = 1.0 / cell_size;
+  c->rg.cell_size = cell_size;
   c->rg.r2 = r * r;
   if (n_cells > 0)
     hipLaunchKernelGGL(k_radius_cells_insert, dim3((unsigned)((n_cells + 255) / 256)), dim3(256), 0, st,

@@ -155,8 +155,11 @@ class BacchusDataset(Dataset):
 
 def radius_grid_cells(xyz: torch.Tensor, cell: float):
     """The cell arrays of sps_radius_grid_upload for float64 map points [M, 3] on a device: (cell keys [C] ascending,
-    cell_start int32 [C + 1], cell_pts int32 [M]: map indices grouped by cell, ascending inside a cell)."""
-    c = torch.floor(xyz / cell).to(torch.int64)
+    cell_start int32 [C + 1], cell_pts int32 [M]: map indices grouped by cell, ascending inside a cell).
+    Cell index: floor(v / cell), a float64 division, as the kernels compute it (radius_cell, the NDT kernels).  The divisor
+    is a tensor on xyz's device: for a Python number torch's device kernel multiplies by 1 / cell instead, which differs
+    by one cell next to a face when cell is not a power of two."""
+    c = torch.floor(xyz / torch.full((), float(cell), dtype=torch.float64, device=xyz.device)).to(torch.int64)
     assert int(c.abs().max()) < (1 << 20) - 1, "map extent exceeds the radius grid"
     keys = ((c[:, 2] + (1 << 20)) << 42) | ((c[:, 1] + (1 << 20)) << 21) | (c[:, 0] + (1 << 20))
     skeys, order = torch.sort(keys, stable=True)        # grouped by cell, ascending map index inside a cell
