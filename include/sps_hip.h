@@ -572,6 +572,37 @@ int sps_ndt_align_batch(sps_ctx *ctx, const double *pts_dev, const int32_t *n_de
                         double *T_out_dev, int32_t *status_dev, double *trace_dev, double *normal_dev, double *final_dev,
                         int32_t *best_dev, double *T_best_dev, void *scratch_dev, void *stream);
 
+/* ---- NDT localiser, pose search --------------------------------------------------------------------------------------
+ * For a pose known to a few metres and a few tens of degrees (the first frame, the frame after a flagged one, a
+ * kidnapped sensor): score a grid of poses, keep the best K <= SPS_NDT_MAX_HYP and hand them to sps_ndt_align_batch,
+ * all on the device.  In the reference this is the job of hdl_localization's global re-localisation companion.
+ *
+ * sps_ndt_score_poses: score_dev[p] = (score, points counted) of the row-major 4x4 pose T_dev[p] for the points
+ *   pts_dev[min(*n_dev, cap)][3].  Per point and pose this is step A of sps_ndt_align restricted to its last two sums
+ *   (score += (-d1) * e; a point with at least one contributing cell counts once), with its operations, its guards and
+ *   its orders: cells in lookup order within a point, points in index order within a workgroup of 32, workgroups as
+ *   launch B adds them.  score_dev[p] therefore has the bits of final_dev[k] of sps_ndt_align_batch(iters = 0) started
+ *   at T_dev[p].  A pose with a NaN entry, or one that puts every point off the map, scores (0, 0).  An empty map and
+ *   *n_dev = 0 are legal: every pose scores (0, 0).  1 <= n_pose <= SPS_NDT_MAX_POSES; neighbours, outlier_ratio and cap
+ *   are checked as for sps_ndt_align.  Launches: 2 per chunk of poses.  scratch_dev: sps_ndt_score_scratch(cap, n_pose)
+ *   bytes (-1 for arguments out of range) = 16 * ceil(cap / 32) bytes per pose of a chunk; the poses are walked in
+ *   chunks so that this stays at or below 64 MiB, or the 32 poses of one tile (512 * ceil(cap / 32) bytes) where those
+ *   need more.
+ * sps_ndt_top_poses: the k best of n_pose poses by score_dev.  A pose qualifies with count >= min_corr and a score that
+ *   is not NaN; the order is (score descending, index ascending), so equal scores keep the lowest index first.
+ *   top_index_dev[j] and T_top_dev[j] = T_dev[top_index_dev[j]] for slot j < *n_top_dev = min(k, qualifying poses);
+ *   the slots after them get index -1 and the pose of slot 0, and T_dev[0] where nobody qualifies, so that
+ *   sps_ndt_align_batch from T_top_dev with n_hyp = k is always well defined.  1 <= k <= SPS_NDT_MAX_HYP.  One launch.
+ * Both: never allocate, never synchronise, never raise the sticky error; T_dev stays unchanged until the stream has
+ * passed the call. */
+#define SPS_NDT_MAX_POSES 65536
+int64_t sps_ndt_score_scratch(int64_t cap, int64_t n_pose);
+int sps_ndt_score_poses(sps_ctx *ctx, const double *pts_dev, const int32_t *n_dev, int64_t cap, const double *T_dev,
+                        int64_t n_pose, int neighbours, double outlier_ratio, double *score_dev, void *scratch_dev,
+                        void *stream);
+int sps_ndt_top_poses(sps_ctx *ctx, const double *score_dev, const double *T_dev, int64_t n_pose, int min_corr, int k,
+                      int32_t *top_index_dev, double *T_top_dev, int32_t *n_top_dev, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

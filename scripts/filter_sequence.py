@@ -114,25 +114,26 @@ def submit(name, f, scan, T, prev_pose):
     return f.submit(scan, T)
 
 
-def hypothesis_grid(counts, steps):
+def hypothesis_grid(counts, steps, option="--hypotheses", step_option="--hypothesis-step", limit=64, what="hypotheses"):
     """--hypotheses NA,NB,NYAW / --hypothesis-step DA,DB,DYAW_DEG -> offsets [K, 4, 4]: a grid symmetric around 0 (odd
-    counts) along, across and in yaw, with the identity moved to index 0."""
+    counts) along, across and in yaw, with the identity moved to index 0.  --search / --search-step build theirs the same
+    way, up to 65536 poses."""
     from sps_amd.localiser import pose_grid
     try:
         n = [int(v) for v in counts.split(",")]
         d = [float(v) for v in steps.split(",")]
     except ValueError:
-        raise click.UsageError("--hypotheses takes three integers, --hypothesis-step three numbers")
+        raise click.UsageError(f"{option} takes three integers, {step_option} three numbers")
     if len(n) != 3 or len(d) != 3 or any(v < 1 or v % 2 == 0 for v in n):
-        raise click.UsageError("--hypotheses takes three odd counts >= 1 (NA,NB,NYAW), --hypothesis-step three steps")
-    if n[0] * n[1] * n[2] > 64:
-        raise click.UsageError("--hypotheses: at most 64 hypotheses in all")
+        raise click.UsageError(f"{option} takes three odd counts >= 1 (NA,NB,NYAW), {step_option} three steps")
+    if n[0] * n[1] * n[2] > limit:
+        raise click.UsageError(f"{option}: at most {limit} {what} in all")
     g = pose_grid(*[[(i - c // 2) * step for i in range(c)] for c, step in zip(n, d)])
     centre = ((n[0] // 2) * n[1] + n[1] // 2) * n[2] + n[2] // 2
     return np.concatenate([g[[centre]], np.delete(g, centre, axis=0)])
 
 
-def closed_loop(name, f, pc_map, replay, finish, traj_out, which="icp", hypotheses=None):
+def closed_loop(name, f, pc_map, replay, finish, traj_out, which="icp", hypotheses=None, search=None):
     """--localise: one LocalisationLoop step per frame, scored against the replayed poses."""
     from sps_amd.localiser import LocalisationLoop, NDTLocaliser, ScanToMapLocaliser
     from sps_amd.trajectory import ape_translation, rotation_angle, write_trajectory
@@ -141,7 +142,7 @@ def closed_loop(name, f, pc_map, replay, finish, traj_out, which="icp", hypothes
     for stamp, scan, pose, map_tr in replay:
         T = map_tr @ pose
         if loop is None:
-            loop = LocalisationLoop(f, localiser, T, hypotheses=hypotheses)
+            loop = LocalisationLoop(f, localiser, T, hypotheses=hypotheses, search=search)
         step = loop.step(scan)
         finish(stamp, None, step.filter_result)
         p = step.pose_result
@@ -149,6 +150,10 @@ def closed_loop(name, f, pc_map, replay, finish, traj_out, which="icp", hypothes
         err_r = float(np.degrees(rotation_angle(step.pose, T)))
         print(f"[{stamp}] loc: {p.status:d} {p.iterations:d} {p.n_corr:d} {p.rmse:.4f} | {err_t:.4f} {err_r:.4f}"
               + (" (flagged: the guess is kept)" if step.flagged else ""))
+        if step.search is not None:
+            r = step.search
+            print(f"[{stamp}] search: pose {r.index:d} of {len(r.scores):d} | candidates " + " ".join(str(int(k)) for k in r.candidates)
+                  + " | grid scores " + " ".join(f"{r.scores[k]:.1f}" for k in r.candidates if k >= 0))
         if step.batch is not None:
             b = step.batch
             print(f"[{stamp}] hypotheses: best {b.best:d} of {len(b.results):d} | scores "
@@ -178,12 +183,22 @@ def closed_loop(name, f, pc_map, replay, finish, traj_out, which="icp", hypothes
               help="with --localiser ndt: NA,NB,NYAW start poses (odd counts) along, across and in yaw around the guess")
 @click.option("--hypothesis-step", "hyp_steps", type=str, default="0.5,0.5,5",
               help="with --hypotheses: DA,DB,DYAW_DEG, the grid's spacing in m, m and degrees")
-def main(name, weights, sequence, config, epsilon, out_dir, n_synth, localise, which, traj_out, hyp_counts, hyp_steps):
+@click.option("--search", "search_counts", type=str, default=None,
+              help="with --localiser ndt: NA,NB,NYAW poses (odd counts) scored around the guess at the first frame and after "
+                   "every flagged frame; the best 8 are registered")
+@click.option("--search-step", "search_steps", type=str, default="1,0.5,5",
+              help="with --search: DA,DB,DYAW_DEG, the grid's spacing in m, m and degrees")
+def main(name, weights, sequence, config, epsilon, out_dir, n_synth, localise, which, traj_out, hyp_counts, hyp_steps,
+         search_counts, search_steps):
     if which is not None and not localise:
         raise click.UsageError("--localiser needs --localise")
     if hyp_counts is not None and which != "ndt":
         raise click.UsageError("--hypotheses needs --localise --localiser ndt")
+    if search_counts is not None and which != "ndt":
+        raise click.UsageError("--search needs --localise --localiser ndt")
     hypotheses = hypothesis_grid(hyp_counts, hyp_steps) if hyp_counts is not None else None
+    search = hypothesis_grid(search_counts, search_steps, "--search", "--search-step", 65536, "poses") \
+        if search_counts is not None else None
     cfg = yaml.safe_load(open(config))
     if epsilon is None:
         epsilon = float(cfg.get("FILTER", {}).get("THRESHOLD", 0.84))
@@ -218,7 +233,7 @@ def main(name, weights, sequence, config, epsilon, out_dir, n_synth, localise, w
         n_done += 1
 
     if localise:
-        closed_loop(name, f, pc_map, replay, finish, traj_out, which or "icp", hypotheses)
+        closed_loop(name, f, pc_map, replay, finish, traj_out, which or "icp", hypotheses, search)
     elif traj_out:
         raise click.UsageError("--traj-out needs --localise")
     in_flight, prev_pose = None, None

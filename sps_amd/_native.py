@@ -137,6 +137,9 @@ def _load() -> C.CDLL:
         "sps_ndt_align_batch_scratch": (i64, [i64, i32]),
         "sps_ndt_align_batch": (i32, [vp, vp, vp, i64, vp, i32, i32, i32, i32, C.c_double, C.c_double, C.c_double, vp, vp, vp, vp,
                                       vp, vp, vp, vp, vp]),
+        "sps_ndt_score_scratch": (i64, [i64, i64]),
+        "sps_ndt_score_poses": (i32, [vp, vp, vp, i64, vp, i64, i32, C.c_double, vp, vp, vp]),
+        "sps_ndt_top_poses": (i32, [vp, vp, vp, i64, i32, i32, vp, vp, vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)          # AttributeError here = header/library mismatch: fail loudly
@@ -165,7 +168,8 @@ EXPORTS = ["sps_last_error", "sps_version", "sps_ctx_create", "sps_ctx_destroy",
            "sps_forward_head_n", "sps_transform_rows", "sps_transform_points_n", "sps_radius_crop", "sps_label_filter",
            "sps_loc_downsample_scratch", "sps_loc_align_scratch", "sps_loc_downsample", "sps_loc_align",
            "sps_ndt_align_scratch", "sps_ndt_map_build", "sps_ndt_map_cells", "sps_ndt_align",
-           "sps_ndt_align_batch_scratch", "sps_ndt_align_batch"]
+           "sps_ndt_align_batch_scratch", "sps_ndt_align_batch",
+           "sps_ndt_score_scratch", "sps_ndt_score_poses", "sps_ndt_top_poses"]
 CROP_BLOCK = 1024          # SPS_CROP_BLOCK: map rows per int of sps_radius_crop's scratch
 
 
@@ -443,6 +447,17 @@ class Context:
                                       int(neighbours), int(min_corr), float(outlier_ratio), float(tol_t), float(tol_r),
                                       T_out_ptr, status_ptr, trace_ptr, normal_ptr, final_ptr, best_ptr, T_best_ptr,
                                       scratch_ptr, stream))
+
+    # ---- NDT localiser, pose search (include/sps_hip.h, "NDT localiser, pose search") ----
+    def ndt_score_poses(self, pts_ptr, n_dev_ptr: int, cap: int, T_ptr, n_pose: int, neighbours: int, outlier_ratio: float,
+                        score_ptr: int, scratch_ptr: int, stream: int):
+        check(lib.sps_ndt_score_poses(self.handle, pts_ptr, n_dev_ptr, int(cap), T_ptr, int(n_pose), int(neighbours),
+                                      float(outlier_ratio), score_ptr, scratch_ptr, stream))
+
+    def ndt_top_poses(self, score_ptr: int, T_ptr, n_pose: int, min_corr: int, k: int, top_index_ptr: int, T_top_ptr: int,
+                      n_top_ptr: int, stream: int):
+        check(lib.sps_ndt_top_poses(self.handle, score_ptr, T_ptr, int(n_pose), int(min_corr), int(k), top_index_ptr, T_top_ptr,
+                                    n_top_ptr, stream))
 
     def train_forward(self, params_ptr: int, numel: int, coords_ptr: int, ld: int, n: int, voxel_size: float,
                       scores_ptr: int, batch_stats_ptr, stream: int):

@@ -150,6 +150,7 @@ int fail(int code, const char *fmt, ...) {
 #include "loc_kernels.inc.h"
 #include "ndt_kernels.inc.h"
 #include "ndt_batch_kernels.inc.h"
+#include "ndt_search_kernels.inc.h"
 
 // ------------------------------------------------------------------------------------------
 // context
@@ -2254,5 +2255,6 @@ int sps_get_feature(sps_ctx *c, const char *name, float *out_dev, int64_t *rows,
 #include "loc_host.inc.h"
 #include "ndt_host.inc.h"
 #include "ndt_batch_host.inc.h"
+#include "ndt_search_host.inc.h"
 
 }  // extern "C"

@@ -21,6 +21,10 @@ transform (ndt_omp's 1 m cells and DIRECT7 neighbourhood by default; C ABI: the 
 end poses by the NDT score at each (C ABI: "NDT localiser, several hypotheses"): a start in the wrong basin
 converges there with status 0, and only the score tells.  ``pose_grid`` builds the offsets.
 
+``NDTLocaliser.score_poses`` gives the NDT score of up to 65536 poses, and ``NDTLocaliser.relocalise`` scores such a grid,
+keeps the best ``keep`` <= 64 on the device and registers from those (C ABI: "NDT localiser, pose search"):
+for a pose known to a few metres and a few tens of degrees only.
+
 ``LocalisationLoop`` closes the loop for any of the seven filters of scripts/filter_sequence.py, around either localiser.
 """
 from __future__ import annotations
@@ -85,12 +89,13 @@ class BatchPoseResult:
 class PendingPoses:
     """A batch of localisations whose work has been issued; everything lives on the device until result()."""
 
-    def __init__(self, n_hyp, iters, with_normal, host, event, keep):
+    def __init__(self, n_hyp, iters, with_normal, host, event, keep, at=0):
         self._n_hyp, self._iters, self._with_normal, self._host, self._event, self._keep = n_hyp, iters, with_normal, host, event, keep
+        self._at = at                                                # doubles in front of the batch's part of the buffer
 
     def result(self) -> BatchPoseResult:
         self._event.synchronize()                                    # the one host synchronisation
-        h = self._host.numpy()
+        h = self._host.numpy()[self._at:]
         K, I = self._n_hyp, self._iters
         o = _batch_layout(K, I, self._with_normal)
         T_out = h[o["T_out"]:o["T_out"] + 16 * K].reshape(K, 4, 4)
@@ -141,6 +146,70 @@ def pose_grid(along, across, yaw_deg) -> np.ndarray:
 
 
 MAX_HYPOTHESES = 64            # SPS_NDT_MAX_HYP
+MAX_POSES = 65536              # SPS_NDT_MAX_POSES
+
+
+def _checked_poses(poses, what="poses"):
+    T = np.ascontiguousarray(np.asarray(poses, dtype=np.float64))
+    if T.ndim != 3 or T.shape[1:] != (4, 4) or not 1 <= len(T) <= MAX_POSES or not np.isfinite(T).all():
+        raise ValueError(f"{what} must be finite, [P, 4, 4] with 1 <= P <= {MAX_POSES}")
+    return T
+
+
+class PendingScores:
+    """The scores of a pose grid whose work has been issued; ``result()`` -> (scores [P] float64, counts [P] int64)."""
+
+    def __init__(self, n_pose, host, event, keep):
+        self._n_pose, self._host, self._event, self._keep = n_pose, host, event, keep
+
+    def result(self):
+        self._event.synchronize()                                    # the one host synchronisation
+        sc = self._host.numpy()[:2 * self._n_pose].reshape(self._n_pose, 2)
+        return sc[:, 0].copy(), sc[:, 1].astype(np.int64)
+
+
+@dataclass
+class RelocalisationResult:
+    scores: np.ndarray         # [P] the NDT score of every pose of the grid
+    counts: np.ndarray         # [P] int, the scan points counted at that pose
+    candidates: np.ndarray     # [keep] int, indices into the grid by (score descending, index ascending); -1: slot not filled
+    batch: BatchPoseResult     # the ``keep`` alignments, hypothesis j started from the pose of candidates[j]
+    index: int                 # the grid index of the selected alignment's start pose, or -1 where none was selected
+    pose: np.ndarray           # 4x4: batch.pose
+
+    @property
+    def ok(self) -> bool:
+        return self.index >= 0
+
+
+def _search_layout(P, K):
+    """offsets (in doubles) of the search's part of a relocalisation's buffer, in front of the batch's:
+    score[P][2] | top int32[K] (+ pad) | n_top int32 (+ pad) | T_top[K][16]"""
+    o, at = {}, 0
+    for name, size in (("score", 2 * P), ("top", (K + 1) // 2), ("n_top", 1), ("T_top", 16 * K)):
+        o[name] = at
+        at += size
+    o["size"] = at
+    return o
+
+
+class PendingRelocalisation:
+    """A pose search and the alignments of its candidates, issued; everything lives on the device until result()."""
+
+    def __init__(self, n_pose, batch_pending):
+        self._n_pose, self._batch = n_pose, batch_pending
+
+    def result(self) -> RelocalisationResult:
+        b = self._batch
+        K, P = b._n_hyp, self._n_pose
+        o = _search_layout(P, K)
+        h = b._host.numpy()
+        b._event.synchronize()                                       # the one host synchronisation
+        sc = h[o["score"]:o["score"] + 2 * P].reshape(P, 2)
+        cand = h[o["top"]:o["top"] + (K + 1) // 2].view(np.int32)[:K].astype(np.int64)
+        batch = b.result()
+        index = int(cand[batch.best]) if batch.best >= 0 else -1
+        return RelocalisationResult(sc[:, 0].copy(), sc[:, 1].astype(np.int64), cand, batch, index, batch.pose)
 
 
 class ScanToMapLocaliser:
@@ -292,6 +361,7 @@ class NDTLocaliser(ScanToMapLocaliser):
             self._align_scratch = torch.empty(_native.lib.sps_ndt_align_scratch(self.capacity), dtype=torch.uint8, device=self.device)
             self._ds_scratch, self._ds_rows = None, -1
             self._batch_scratch, self._batch_hyp = None, 0
+            self._score_scratch, self._score_poses = None, 0
 
     def _align(self, n_ptr, T, K, T_out_ptr, status_ptr, trace_ptr, normal_ptr, s):
         self.ctx.ndt_align(self._pts.data_ptr(), n_ptr, self.capacity, T, K, self.neighbours, self.min_correspondences,
@@ -322,15 +392,11 @@ class NDTLocaliser(ScanToMapLocaliser):
             self.ctx.loc_downsample(rows.data_ptr() if n_max else None, rows.stride(0) if n_max else 3, n_max,
                                     n_dev.data_ptr(), self.leaf, self._pts.data_ptr(), self.capacity, base + o["n_points"] * 8,
                                     self._downsample_scratch(n_max).data_ptr(), s)
-            if K > self._batch_hyp:                                  # grows with the largest batch seen (stream-ordered reuse)
-                self._batch_scratch = torch.empty(_native.lib.sps_ndt_align_batch_scratch(self.capacity, K), dtype=torch.uint8,
-                                                  device=dev)
-                self._batch_hyp = K
             self.ctx.ndt_align_batch(self._pts.data_ptr(), base + o["n_points"] * 8, self.capacity, T_dev.data_ptr(), K, I,
                                      self.neighbours, self.min_correspondences, self.outlier_ratio, self.tol_t, self.tol_r,
                                      base + o["T_out"] * 8, base + o["status"] * 8, base + o["trace"] * 8 if I else None,
                                      base + o["normal"] * 8 if with_normal and I else None, base + o["final"] * 8,
-                                     base + o["best"] * 8, base + o["T_best"] * 8, self._batch_scratch.data_ptr(), s)
+                                     base + o["best"] * 8, base + o["T_best"] * 8, self._batch_scratch_for(K).data_ptr(), s)
             host = torch.empty(out.numel(), dtype=torch.float64).pin_memory()
             host.copy_(out, non_blocking=True)
             ev = torch.cuda.Event()
@@ -340,6 +406,91 @@ class NDTLocaliser(ScanToMapLocaliser):
     def submit_filtered_batch(self, pending, T_inits, **kw) -> PendingPoses:
         """``submit_batch`` of the kept rows of a pending SPSFilter / SPSCVMFilter frame, without the frame's result()."""
         return self.submit_batch(pending._filtered, pending.count_dev, T_inits, **kw)
+
+    def _batch_scratch_for(self, K):
+        if K > self._batch_hyp:                                      # grows with the largest batch seen (stream-ordered reuse)
+            self._batch_scratch = torch.empty(_native.lib.sps_ndt_align_batch_scratch(self.capacity, K), dtype=torch.uint8,
+                                              device=self.device)
+            self._batch_hyp = K
+        return self._batch_scratch
+
+    def _score(self, rows, n_dev, n_max, T_dev, P, n_points_ptr, score_ptr, s):
+        """thin the rows into self._pts (count to n_points_ptr), then the scores of the P poses of T_dev"""
+        self.ctx.loc_downsample(rows.data_ptr() if n_max else None, rows.stride(0) if n_max else 3, n_max, n_dev.data_ptr(),
+                                self.leaf, self._pts.data_ptr(), self.capacity, n_points_ptr,
+                                self._downsample_scratch(n_max).data_ptr(), s)
+        if P > self._score_poses:                                    # grows with the largest grid seen (stream-ordered reuse)
+            self._score_scratch = torch.empty(_native.lib.sps_ndt_score_scratch(self.capacity, P), dtype=torch.uint8,
+                                              device=self.device)
+            self._score_poses = P
+        self.ctx.ndt_score_poses(self._pts.data_ptr(), n_points_ptr, self.capacity, T_dev.data_ptr(), P, self.neighbours,
+                                 self.outlier_ratio, score_ptr, self._score_scratch.data_ptr(), s)
+
+    @torch.no_grad()
+    def score_poses(self, rows, count, poses) -> PendingScores:
+        """The NDT score and the points counted at each of the P poses ``poses`` [P, 4, 4] (1 <= P <= 65536), with no
+        alignment: the scan is thinned once as ``submit`` thins it, and pose p scores what ``submit_batch`` reports as the
+        final score of a hypothesis that starts there with ``iterations=0``, bit for bit.  Issued on the current stream."""
+        rows = self._checked_rows(rows)
+        T = _checked_poses(poses)
+        n_max, dev, P = rows.shape[0], self.device, len(T)
+        with torch.cuda.device(dev):
+            st = torch.cuda.current_stream()
+            s = st.cuda_stream
+            n_dev = self._count_on_device(count, n_max)
+            T_host = torch.from_numpy(T).pin_memory()
+            T_dev = T_host.to(dev, non_blocking=True)                # on the caller's stream; both stay with the pending object
+            out = torch.zeros(2 * P + 1, dtype=torch.float64, device=dev)   # score[P][2] | n_points int32 (+ pad)
+            base = out.data_ptr()
+            self._score(rows, n_dev, n_max, T_dev, P, base + 2 * P * 8, base, s)
+            host = torch.empty(out.numel(), dtype=torch.float64).pin_memory()
+            host.copy_(out, non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record(st)
+        return PendingScores(P, host, ev, (rows, n_dev, out, T_host, T_dev))
+
+    @torch.no_grad()
+    def relocalise(self, rows, count, poses, keep: int = 8, with_normal: bool = False,
+                   iterations: int = None) -> PendingRelocalisation:
+        """Thin, score the P poses ``poses`` [P, 4, 4] (e.g. ``T_center @ pose_grid(...)``), keep the best ``keep`` (1..64)
+        by (score descending, index ascending) among those with at least ``min_correspondences`` points counted, register
+        from these as ``submit_batch`` does and select among the end poses as it selects.  Everything is issued on the
+        current stream with no synchronisation in between; ``result()`` -> RelocalisationResult."""
+        rows = self._checked_rows(rows)
+        T = _checked_poses(poses)
+        K = int(keep)
+        if not 1 <= K <= MAX_HYPOTHESES:
+            raise ValueError(f"keep must be in [1, {MAX_HYPOTHESES}]")
+        n_max, dev, P = rows.shape[0], self.device, len(T)
+        I = self.iterations if iterations is None else int(iterations)
+        so, o = _search_layout(P, K), _batch_layout(K, I, with_normal)
+        with torch.cuda.device(dev):
+            st = torch.cuda.current_stream()
+            s = st.cuda_stream
+            n_dev = self._count_on_device(count, n_max)
+            T_host = torch.from_numpy(T).pin_memory()
+            T_dev = T_host.to(dev, non_blocking=True)
+            out = torch.zeros(so["size"] + o["size"], dtype=torch.float64, device=dev)
+            sbase = out.data_ptr()
+            base = sbase + so["size"] * 8
+            n_ptr = base + o["n_points"] * 8
+            self._score(rows, n_dev, n_max, T_dev, P, n_ptr, sbase + so["score"] * 8, s)
+            self.ctx.ndt_top_poses(sbase + so["score"] * 8, T_dev.data_ptr(), P, self.min_correspondences, K,
+                                   sbase + so["top"] * 8, sbase + so["T_top"] * 8, sbase + so["n_top"] * 8, s)
+            self.ctx.ndt_align_batch(self._pts.data_ptr(), n_ptr, self.capacity, sbase + so["T_top"] * 8, K, I,
+                                     self.neighbours, self.min_correspondences, self.outlier_ratio, self.tol_t, self.tol_r,
+                                     base + o["T_out"] * 8, base + o["status"] * 8, base + o["trace"] * 8 if I else None,
+                                     base + o["normal"] * 8 if with_normal and I else None, base + o["final"] * 8,
+                                     base + o["best"] * 8, base + o["T_best"] * 8, self._batch_scratch_for(K).data_ptr(), s)
+            host = torch.empty(out.numel(), dtype=torch.float64).pin_memory()
+            host.copy_(out, non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record(st)
+        return PendingRelocalisation(P, PendingPoses(K, I, with_normal, host, ev, (rows, n_dev, out, T_host, T_dev), so["size"]))
+
+    def relocalise_filtered(self, pending, poses, **kw) -> PendingRelocalisation:
+        """``relocalise`` of the kept rows of a pending SPSFilter / SPSCVMFilter frame, without the frame's result()."""
+        return self.relocalise(pending._filtered, pending.count_dev, poses, **kw)
 
     def map_cells(self):
         """Debug: (keys uint64 [C], counts int32 [C], means [C, 3], inverse covariances [C, 6] as (xx, xy, xz, yy, yz, zz),
@@ -364,6 +515,7 @@ class LoopStep:
     pose: np.ndarray           # the corrected pose handed on (the guess when flagged)
     flagged: bool              # the localiser reported status 2 or 3 (with hypotheses: none of them was selected)
     batch: BatchPoseResult = None   # with hypotheses: every hypothesis of the frame (pose_result is the selected one's)
+    search: RelocalisationResult = None   # a frame registered by the pose search (batch is then its candidates' batch)
 
 
 class LocalisationLoop:
@@ -384,12 +536,30 @@ class LocalisationLoop:
     ``hypotheses`` (NDTLocaliser only; None: one registration from the guess): offsets [K, 4, 4] with ``hypotheses[0]``
     the identity, e.g. from ``pose_grid``.  A frame is then registered from ``guess @ hypotheses[k]`` for every k at once
     (``submit_batch``) and the selected pose is handed on; a frame in which no hypothesis is selected (best = -1) is
-    flagged and keeps the guess, as status 2 / 3 does without hypotheses."""
+    flagged and keeps the guess, as status 2 / 3 does without hypotheses.
 
-    def __init__(self, filter, localiser, initial_pose, hypotheses=None):
+    ``search`` (NDTLocaliser only; None: no pose search): offsets [P, 4, 4] (P <= 65536) with ``search[0]`` the identity.
+    The first frame and every frame directly after a flagged frame are then registered by
+    ``relocalise(guess @ search[k], keep=search_keep)`` instead of the plain or batch registration: the grid is scored, its
+    best ``search_keep`` poses are aligned and the best end pose is handed on; a frame in which none is selected is flagged
+    and keeps the guess."""
+
+    def __init__(self, filter, localiser, initial_pose, hypotheses=None, search=None, search_keep: int = 8):
         from .sps_filters import ConstantVelocityModel
         self.filter, self.localiser = filter, localiser
         self.hypotheses = None
+        self.search, self.search_keep, self._search_next = None, int(search_keep), True
+        if search is not None:
+            S = np.array(search, dtype=np.float64)
+            if S.ndim != 3 or S.shape[1:] != (4, 4) or not 1 <= len(S) <= MAX_POSES or not np.isfinite(S).all():
+                raise ValueError(f"search must be finite, [P, 4, 4] with 1 <= P <= {MAX_POSES}")
+            if not np.array_equal(S[0], np.eye(4)):
+                raise ValueError("search[0] must be the identity")
+            if not 1 <= self.search_keep <= MAX_HYPOTHESES:
+                raise ValueError(f"search_keep must be in [1, {MAX_HYPOTHESES}]")
+            if not hasattr(localiser, "relocalise"):
+                raise TypeError("search needs a localiser with relocalise (NDTLocaliser)")
+            self.search = S
         if hypotheses is not None:
             H = np.array(hypotheses, dtype=np.float64)
             if H.ndim != 3 or H.shape[1:] != (4, 4) or not 1 <= len(H) <= MAX_HYPOTHESES or not np.isfinite(H).all():
@@ -444,7 +614,41 @@ class LocalisationLoop:
         self.poses.append(np.array(pose, dtype=np.float64))
         return LoopStep(fres, bres.results[max(bres.best, 0)], guess, self.poses[-1], flagged, bres)
 
+    def search_poses(self, guess) -> np.ndarray:
+        """[P, 4, 4]: ``guess @ search[k]``"""
+        return np.stack([guess @ d for d in self.search])
+
+    def _step_search(self, scan, guess) -> LoopStep:
+        pend = self._submit_filter(scan, guess)
+        poses = self.search_poses(guess)
+        if hasattr(pend, "count_dev") and hasattr(pend, "_filtered"):
+            pose_pend = self.localiser.relocalise_filtered(pend, poses, keep=self.search_keep)
+            fres = pend.result()
+            sres = pose_pend.result()
+        else:
+            fres = pend.result()
+            kept = fres.filtered
+            sres = self.localiser.relocalise(kept, len(kept), poses, keep=self.search_keep).result()
+        bres = sres.batch
+        flagged = sres.index < 0
+        pose = guess if flagged else sres.pose
+        self._search_next = flagged
+        self.model.add_pose(pose)
+        if hasattr(self.filter, "add_pose"):
+            self.filter.add_pose(pose)
+        self.poses.append(np.array(pose, dtype=np.float64))
+        return LoopStep(fres, bres.results[max(bres.best, 0)], guess, self.poses[-1], flagged, bres, sres)
+
     def step(self, scan) -> LoopStep:
+        if self.search is not None:
+            if self._search_next:
+                return self._step_search(scan, self.guess())
+            out = self._step_registered(scan)
+            self._search_next = out.flagged
+            return out
+        return self._step_registered(scan)
+
+    def _step_registered(self, scan) -> LoopStep:
         guess = self.guess()
         if self.hypotheses is not None:
             return self._step_batch(scan, guess)

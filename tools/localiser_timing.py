@@ -10,7 +10,7 @@ synthetic.build_map() map, max_distance 1 m, leaf 0.2 m):
               SPSFilter alone on the same scans
 
     python tools/localiser_timing.py [--frames 200] [--warmup 20] [--cpu-frames 1] [--one-frame] [--cpu-only]
-                                     [--localiser {icp,ndt}] [--hypotheses K]
+                                     [--localiser {icp,ndt}] [--hypotheses K] [--search P]
 
 ``--localiser ndt`` times sps_amd.localiser.NDTLocaliser (1 m cells, 7 neighbours) on the same frames and from the same
 start, prints the ICP's per-frame figures of the same session beside it and the build time of both maps; the
@@ -18,6 +18,9 @@ restatement is then tests/ndt_reference.py.
 
 ``--localiser ndt --hypotheses K`` times NDTLocaliser.submit_batch from K start poses (the guess and offsets 0.5 m apart
 around it) against K back-to-back submit calls from the same poses, and against one submit.
+
+``--localiser ndt --search P`` times NDTLocaliser.score_poses of P poses against ceil(P / 64) calls of
+submit_batch(iterations=0) over the same poses and checks that the two agree bit for bit.
 
 ``--one-frame`` runs a warm-up and ONE localiser frame: the target of a ``rocprofv3 --kernel-trace --stats`` run.
 """
@@ -104,7 +107,11 @@ def main():
     ap.add_argument("--localiser", choices=("icp", "ndt"), default="icp")
     ap.add_argument("--hypotheses", type=int, default=0, help="with --localiser ndt: time submit_batch of K start poses "
                     "against K back-to-back submit calls")
+    ap.add_argument("--search", type=int, default=0, help="with --localiser ndt: time score_poses of P poses against "
+                    "ceil(P / 64) submit_batch(iterations=0) calls, the only way to score poses without it")
     a = ap.parse_args()
+    if a.search and (a.localiser != "ndt" or not 1 <= a.search <= 65536):
+        ap.error("--search P needs --localiser ndt and 1 <= P <= 65536")
     if a.hypotheses and (a.localiser != "ndt" or not 1 <= a.hypotheses <= 64):
         ap.error("--hypotheses K needs --localiser ndt and 1 <= K <= 64")
     if a.cpu_only:
@@ -114,6 +121,8 @@ def main():
     dscans = [torch.from_numpy(s).cuda() for s in scans]
     mp = synthetic.build_map()
     T_init = LR.perturbation(0.15, 0.12, 0.05, 1.0)
+    if a.localiser == "ndt" and a.search:
+        return ndt_search_main(a, dscans, mp, T_init)
     if a.localiser == "ndt" and a.hypotheses:
         return ndt_batch_main(a, dscans, mp, T_init)
     if a.localiser == "ndt":
@@ -307,6 +316,54 @@ def ndt_batch_main(a, dscans, mp, T_init):
     print(f"K = {K}: submit_batch median {mb:.3f} ms (min {min(t_batch):.3f} max {max(t_batch):.3f}), {K} x submit median "
           f"{ms:.3f} ms, one submit {m1:.3f} ms; {it:.0f} iterations (longest hypothesis), {out['batch_ms_per_iteration']:.4f} ms "
           f"per iteration; best {out['best']}, error of the selected pose max {out['max_error_m']:.4f} m", flush=True)
+    print(json.dumps(out))
+
+
+def search_poses(T_init, P):
+    """P poses T_init @ D(a, b, psi) of a planar grid of +-3 m along, +-1 m across and +-15 degrees"""
+    from sps_amd.localiser import pose_grid
+    side = max(int(np.ceil((P / 3.0) ** 0.5)), 1)
+    g = pose_grid(np.linspace(-3.0, 3.0, side), np.linspace(-1.0, 1.0, 3), np.linspace(-15.0, 15.0, side))
+    return np.stack([T_init @ d for d in g[:P]])
+
+
+def ndt_search_main(a, dscans, mp, T_init):
+    """--search P: hipEvent time around one score_poses of P poses against ceil(P / 64) submit_batch(iterations=0) calls
+    over the same poses (each thins the scan again: there is no other way to reach the batch's final scores), interleaved
+    frame by frame in one run; the two must agree bit for bit.  Both windows include their host staging (the pinned copy of
+    the poses and the zeroed output buffer: once for P poses on one side, once per 64 poses on the other), so the ratio is
+    that of the calls as a user makes them, not of the kernels alone; a kernel trace gives those."""
+    P = a.search
+    ndt = NDTLocaliser(mp[:, :3].astype(np.float64))
+    poses = search_poses(T_init, P)
+    st = torch.cuda.current_stream()
+    t_score, t_batch, npts = [], [], 0
+    for k in range(a.warmup + a.frames):
+        s = dscans[k % len(dscans)]
+        e = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
+        e[0].record(st)
+        pend = ndt.score_poses(s, len(s), poses)
+        e[1].record(st)
+        scores, counts = pend.result()
+        e[2].record(st)
+        batches = [ndt.submit_batch(s, len(s), poses[lo:lo + 64], iterations=0) for lo in range(0, P, 64)]
+        e[3].record(st)
+        batches = [b.result() for b in batches]
+        e[3].synchronize()
+        assert np.concatenate([b.scores for b in batches]).tobytes() == scores.tobytes()
+        assert np.concatenate([b.counts for b in batches]).tobytes() == counts.tobytes()
+        npts = batches[0].results[0].n_points
+        if k >= a.warmup:
+            t_score.append(e[0].elapsed_time(e[1]))
+            t_batch.append(e[2].elapsed_time(e[3]))
+    ms, mb = float(np.median(t_score)), float(np.median(t_batch))
+    out = {"search": P, "frames": a.frames, "warmup": a.warmup, "n_points": npts,
+           "score_poses_ms": {"median": round(ms, 4), "min": round(min(t_score), 4), "max": round(max(t_score), 4)},
+           "batch0_ms": {"median": round(mb, 4), "min": round(min(t_batch), 4), "max": round(max(t_batch), 4)},
+           "batch0_calls": (P + 63) // 64, "ratio_batch0_over_score": round(mb / ms, 3), "bits_agree": True}
+    print(f"P = {P}: score_poses median {ms:.3f} ms (min {min(t_score):.3f} max {max(t_score):.3f}), {(P + 63) // 64} x "
+          f"submit_batch(iterations=0) median {mb:.3f} ms (min {min(t_batch):.3f} max {max(t_batch):.3f}); {npts} points; the "
+          f"bits agree", flush=True)
     print(json.dumps(out))
 
 
