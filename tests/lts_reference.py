@@ -3,7 +3,7 @@ numpy / torch: the checker of the HIP path (sps_amd/models/lts.py, sps_amd/datas
 
   lts_project(data, lidar)   range image [beams, 1024, 4] (+ the pre-floor row / column values of every kept row)
   lts_windows(frame, lidar)  network input [windows, 3, N] and cell labels [windows, N]
-  lts_forward(sd, x, dtype)  SPCTReg scores [B, N] and taps, in float32 or float64, on x's device
+  lts_forward(sd, x, dtype)  SPCTReg scores [B, N] and taps, in float32 or float64, on the given device
   lts_metrics(scores, labels, eps)   the node's loss / R2 / calculate_metrics
 """
 from __future__ import annotations
@@ -73,8 +73,10 @@ def _conv(sd, p, x, dt, bias=True):
     return y
 
 
-def _window(sd, x, dt):
-    """One window x [3, N] -> (scores [N], taps)."""
+def _window(sd, x, dt, probes=False):
+    """One window x [3, N] -> (scores [N], taps).  probes: the taps also hold, per attention layer k, the energies
+    ``energy{k}`` [query, key] and the key columns' sums over the queries ``colsum{k}`` [key], and linear1's
+    pre-activation ``linear1_pre`` [2048, N] (what the edge tests state their conditions on)."""
     taps = {}
     h = torch.relu(_bn(sd, "embedding.bn1", _conv(sd, "embedding.conv1", x, dt), dt))
     h = torch.relu(_bn(sd, "embedding.bn2", _conv(sd, "embedding.conv2", h, dt), dt))
@@ -85,6 +87,8 @@ def _window(sd, x, dt):
         q = _conv(sd, f"{p}.k_conv", h, dt)           # the shared q / k weight (k_conv's value after a load)
         energy = q.t() @ q                            # [query, key]
         att = torch.softmax(energy, dim=1)            # over keys
+        if probes:
+            taps[f"energy{k}"], taps[f"colsum{k}"] = energy, att.sum(dim=0)
         att = att / (1e-9 + att.sum(dim=0, keepdim=True))   # each key column over its queries
         v = _conv(sd, f"{p}.v_conv", h, dt)
         xr = v @ att
@@ -92,6 +96,8 @@ def _window(sd, x, dt):
         taps[p] = h
         outs.append(h)
     y = _bn(sd, "linear1.1", _conv(sd, "linear1.0", torch.cat(outs, 0), dt, bias=False), dt)
+    if probes:
+        taps["linear1_pre"] = y
     y = torch.nn.functional.leaky_relu(y, 0.2)
     mx, mean = y.max(dim=1).values, y.mean(dim=1)
     taps["max"], taps["mean"] = mx, mean
@@ -103,12 +109,12 @@ def _window(sd, x, dt):
 
 
 @torch.no_grad()
-def lts_forward(sd, x, dtype=torch.float64, device=None):
-    """x [B, 3, N] -> scores [B, N] (numpy, dtype) and taps {name: [B, ...]} (numpy)."""
+def lts_forward(sd, x, dtype=torch.float64, device=None, probes=False):
+    """x [B, 3, N] -> scores [B, N] (numpy, dtype) and taps {name: [B, ...]} (numpy; probes: see _window)."""
     xt = torch.as_tensor(np.asarray(x)).to(device=device or "cpu", dtype=dtype)
     scores, taps = [], {}
     for b in range(xt.shape[0]):
-        s, t = _window(sd, xt[b], dtype)
+        s, t = _window(sd, xt[b], dtype, probes)
         scores.append(s.cpu().numpy())
         for k, v in t.items():
             taps.setdefault(k, []).append(v.cpu().numpy())

@@ -26,9 +26,13 @@ def _isqrt(k: int) -> float:
             2048: 0.02209708691207961, 6144: 0.012757759685074, 256: 0.0625}[k]
 
 
-def lts_state_dict(seed: int = 1, head_bias: float = HEAD_BIAS["hdl-32"], qk_differ: bool = False) -> dict:
+def lts_state_dict(seed: int = 1, head_bias: float = HEAD_BIAS["hdl-32"], qk_differ: bool = False,
+                   qk_gain: float = 0.35, linear1_bn_bias_override: dict[int, float] | None = None) -> dict:
     """Full SPCTReg state_dict (reference keys and order).  qk_differ: q_conv.weight gets its own values (a checkpoint
-    whose shared q / k Parameter was written twice with different values; the reference loads the k_conv one)."""
+    whose shared q / k Parameter was written twice with different values; the reference loads the k_conv one).
+    qk_gain: scale of the q / k kernels (the energies grow with its square: a larger gain peaks the softmax).
+    linear1_bn_bias_override: {channel: value} written over linear1's BN beta (channels whose pool is all negative).
+    The defaults give the bits tests/golden/lts_forward.npz was captured with (tests/test_lts_cpu.py pins them)."""
     from sps_amd.models.lts import SPCTReg
     keys = SPCTReg().state_dict()
     sd = {}
@@ -54,10 +58,13 @@ def lts_state_dict(seed: int = 1, head_bias: float = HEAD_BIAS["hdl-32"], qk_dif
         else:                                          # conv kernel [out, in, 1]
             gain = 1.7320508075688772 * _isqrt(shape[1])  # uniform with unit variance gain
             if ".q_conv." in name or ".k_conv." in name:
-                gain *= 0.35                           # energies O(1..10): a non-degenerate softmax
+                gain *= qk_gain                        # 0.35: energies O(1..10), a non-degenerate softmax
             if name == "convs.weight":
                 gain *= 4.0
             v = u * gain
+        if name == "linear1.1.bias" and linear1_bn_bias_override:
+            for ch, val in linear1_bn_bias_override.items():
+                v[ch] = val
         sd[name] = torch.from_numpy(v.astype(np.float32).reshape(shape))
     return sd
 
@@ -89,3 +96,47 @@ def lts_cloud(lidar: str, seed: int, n_rays: int = 20000, centred: bool = True, 
     near[:, :3] *= 0.97                              # same direction, other range: same cell
     near[:, 3] = u[5][:k]
     return np.r_[pts, near].astype(np.float32)
+
+
+_WINDOWS = {}
+
+
+def lts_inputs(B: int, N: int) -> np.ndarray:
+    """Network input [B, 3, N]: the 16 windows of one projected hdl-32 frame and their point-reversed copies, cut to
+    B windows of N points (the input of the forward tests).  N > 2048: window b continues with the points of window
+    b - 1."""
+    from tests.lts_reference import lts_project, lts_windows
+    if "x" not in _WINDOWS:
+        fr, _ = lts_project(lts_cloud("hdl-32", 50, n_rays=60000), "hdl-32")
+        x, _ = lts_windows(fr, "hdl-32")                              # [16, 3, 2048]
+        xx = np.concatenate([x, x[:, :, ::-1]], axis=0)
+        _WINDOWS["x"] = np.concatenate([xx, np.roll(xx, 1, axis=0)], axis=2)
+    return np.ascontiguousarray(_WINDOWS["x"][:B, :, :N])
+
+
+# ---- the edge tests' models and inputs (tests/test_hip_lts_edges.py; the conditions they rest on are asserted on the
+# f64 restatement by tests/test_lts_cpu.py) ----------------------------------------------------------------------------
+PEAKED_K = 4                                  # qk_gain = 0.35 * PEAKED_K: the smallest integer multiple that peaks the softmax
+PEAKED_QK_GAIN = 0.35 * PEAKED_K
+PEAKED_SHAPE = (2, 1000)                      # (B, N) of the peaked-softmax inputs
+NEG_POOL_CHANNELS = (0, 31, 32, 127, 128, 1023, 2047)   # first / last column of a lane group, a wave, a 128-tile, the tensor
+NEG_POOL_BIAS = -20.0                         # linear1's BN beta there: every pre-activation of these channels < -1
+NEG_POOL_SHAPES = ((2, 1), (2, 129), (2, 1000))
+
+
+def lts_dup_inputs() -> np.ndarray:
+    """PEAKED_SHAPE input whose windows are half one point repeated (identical q rows: energies that tie exactly, as the
+    duplicated cells of a real projection give) and half spread points; the repeated half leads in window 0 and trails
+    in window 1."""
+    B, N = PEAKED_SHAPE
+    x = lts_inputs(B, N).copy()
+    for b in range(B):
+        p = x[b][:, np.flatnonzero(np.any(x[b] != 0, axis=0))[7]].copy()     # a measured point, not an empty cell
+        x[b][:, lts_dup_rows(b)] = p[:, None]
+    return x
+
+
+def lts_dup_rows(b: int) -> slice:
+    """The repeated half of window b of lts_dup_inputs()."""
+    N = PEAKED_SHAPE[1]
+    return slice(0, N // 2) if b == 0 else slice(N // 2, N)

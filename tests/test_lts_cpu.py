@@ -9,7 +9,8 @@ import pytest
 import torch
 
 from tests.lts_reference import lts_forward, lts_project
-from tests.lts_weights import HEAD_BIAS, lts_state_dict
+from tests.lts_weights import (HEAD_BIAS, NEG_POOL_BIAS, NEG_POOL_CHANNELS, NEG_POOL_SHAPES, PEAKED_K, PEAKED_SHAPE,
+                               lts_dup_inputs, lts_dup_rows, lts_inputs, lts_state_dict)
 
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
@@ -95,3 +96,81 @@ def test_loader_rejects_unknown_lidar():
     from sps_amd.datasets.lts_loader import Loader
     with pytest.raises(AssertionError, match="lidar type should be 'vlp-16' or 'hdl-32'"):
         Loader(np.zeros((1, 4), np.float32), "os-64")
+
+
+# ---- what the edge tests of the HIP forward rest on (tests/test_hip_lts_edges.py) -----------------------------------
+def test_default_state_dict_bits_are_pinned():
+    """lts_state_dict() without its later keyword arguments: the bytes tests/golden/lts_forward.npz was captured with
+    (sha256 of the tensors' bytes in state_dict order, taken from the function before it had qk_gain)."""
+    import hashlib
+
+    def digest(sd):
+        return hashlib.sha256(b"".join(v.numpy().tobytes() for v in sd.values())).hexdigest()
+
+    assert digest(lts_state_dict()) == "b757510e1136ac229d923cb254dc243e4f98c41995c8496d02ee6f8d8542c818"
+    assert digest(lts_state_dict(qk_differ=True)) == "98b3d91c0eec88d7344f94f0ba1117174ccb2ed4de8ca206e0d1270e7959e4e9"
+    assert digest(lts_state_dict(qk_gain=0.35, linear1_bn_bias_override={})) == digest(lts_state_dict())
+    sd, ov = lts_state_dict(), lts_state_dict(qk_gain=0.7, linear1_bn_bias_override={5: -3.0})
+    for k in sd:                                   # the two arguments touch the q / k kernels and one beta, nothing else
+        if ".q_conv." in k or ".k_conv." in k:
+            np.testing.assert_array_equal(ov[k].numpy(), (sd[k].double() / 0.35 * 0.7).float().numpy())   # one rounding
+        elif k == "linear1.1.bias":
+            assert ov[k][5] == -3.0 and torch.equal(ov[k][:5], sd[k][:5]) and torch.equal(ov[k][6:], sd[k][6:])
+        else:
+            assert torch.equal(ov[k], sd[k]), k
+
+
+def _peaked_conditions(k, x):
+    """(a), (b), (c) of the peaked-softmax case for qk_gain = 0.35 k on input x, from the f64 restatement alone."""
+    scores, taps = lts_forward(lts_state_dict(qk_gain=0.35 * k), x, torch.float64, probes=True)
+    a = b = True
+    c = bool(np.isfinite(scores).all()) and all(np.isfinite(v).all() for v in taps.values())
+    for layer in range(1, 5):
+        E = taps[f"energy{layer}"]                                     # [B, query, key]
+        a &= float((E.max(-1) - np.median(E, -1) >= 30).mean()) >= 0.25
+        b &= float((E.argmax(-1) >= 32).mean()) >= 0.10
+        c &= float(np.abs(E).max()) < 3e4
+    return a, b, c
+
+
+def test_peaked_gain_is_the_smallest_that_peaks_every_layer():
+    """PEAKED_K is the smallest integer k for which, with qk_gain = 0.35 k, in each of the four attention layers (a) a
+    quarter of the query rows have max_j E - median_j E >= 30, (b) a tenth have their arg-max key past the first
+    32-key tile (the running maximum of pass A rises late), (c) everything stays finite and |E| < 3e4."""
+    x = lts_inputs(*PEAKED_SHAPE)
+    for k in range(1, PEAKED_K):
+        assert not all(_peaked_conditions(k, x)), k
+    assert _peaked_conditions(PEAKED_K, x) == (True, True, True)
+
+
+def test_duplicate_point_input_ties_and_reaches_the_denominator_floor():
+    """lts_dup_inputs() under the peaked model: finite, |E| < 3e4, the repeated rows' energies tie, and in some
+    layer key columns of every window sum to less than the 1e-9 of the column normalisation (so the floor decides)."""
+    x = lts_dup_inputs()
+    for b in range(x.shape[0]):
+        assert (x[b][:, lts_dup_rows(b)] == x[b][:, lts_dup_rows(b)][:, :1]).all()
+    scores, taps = lts_forward(lts_state_dict(qk_gain=0.35 * PEAKED_K), x, torch.float64, probes=True)
+    assert np.isfinite(scores).all() and all(np.isfinite(v).all() for v in taps.values())
+    for b in range(x.shape[0]):
+        rows = lts_dup_rows(b)
+        floor = False
+        for layer in range(1, 5):
+            E = taps[f"energy{layer}"][b]
+            assert np.abs(E).max() < 3e4
+            tie = E[rows][:, rows]                 # equal but for the BLAS's blocking (identical q rows on the device)
+            assert np.ptp(tie) <= 1e-13 * np.abs(tie).max()
+            floor |= bool((taps[f"colsum{layer}"][b] < 1e-9).any())
+        assert floor
+
+
+def test_negative_pool_bias_keeps_every_preactivation_below_minus_one():
+    over = {c: NEG_POOL_BIAS for c in NEG_POOL_CHANNELS}
+    sd = lts_state_dict(linear1_bn_bias_override=over)
+    for B, N in NEG_POOL_SHAPES:
+        _, taps = lts_forward(sd, lts_inputs(B, N), torch.float64, probes=True)
+        pre = taps["linear1_pre"][:, list(NEG_POOL_CHANNELS)]
+        assert pre.shape == (B, len(NEG_POOL_CHANNELS), N) and pre.max() < -1.0, (N, pre.max())
+        np.testing.assert_array_equal(taps["max"][:, list(NEG_POOL_CHANNELS)], 0.2 * pre.max(-1))
+        assert (taps["max"][:, list(NEG_POOL_CHANNELS)] < 0).all()
+        rest = np.setdiff1d(np.arange(2048), NEG_POOL_CHANNELS)
+        assert (taps["linear1_pre"][:, rest].max(-1) > 0).mean() > 0.3      # the other columns still see positive values
