@@ -603,6 +603,51 @@ int sps_ndt_score_poses(sps_ctx *ctx, const double *pts_dev, const int32_t *n_de
 int sps_ndt_top_poses(sps_ctx *ctx, const double *score_dev, const double *T_dev, int64_t n_pose, int min_corr, int k,
                       int32_t *top_index_dev, double *T_top_dev, int32_t *n_top_dev, void *stream);
 
+/* ---- NDT localiser, online map ----------------------------------------------------------------------------------------
+ * A map that grows: the stable points a filter keeps are folded into the cells at the frame's corrected pose, on the
+ * frame's stream, so that a localiser can start from an empty map and a scene that changed is learnt.  
+ *
+ * sps_ndt_map_build_dynamic: sps_ndt_map_build's arguments and checks, plus cell_capacity >= max(n_cells, 1).  Records,
+ *   counts and keys are allocated for cell_capacity cells and the hash for next_pow2(2 * max(512, cell_capacity)) slots (it
+ *   never holds more than cell_capacity keys: load <= 0.5).  Per cell the map keeps the moments n (the count), the mean
+ *   (the record's) and S = sum (p - mean)(p - mean)^T (6 entries, before the division by n - 1), and a device counter of
+ *   the cells assigned.  The first n_cells records have the bits sps_ndt_map_build writes for the same arguments; the
+ *   records of unassigned cells are zero (valid = 0) and their keys empty (all bits set), so sps_ndt_align and the batch
+ *   and search calls run unchanged.  n_map = 0 builds an empty map to grow from.  Allocates and synchronises.
+ *   sps_ndt_map_cells then writes cell_capacity rows.  A map built by sps_ndt_map_build refuses the update (INVALID).
+ * sps_ndt_map_update: folds pts_dev[0 .. min(cap, *n_dev)) (f64 [cap][3], sensor frame) into the map at the row-major
+ *   4x4 pose T_dev (16 doubles on the device, e.g. T_out_dev of sps_ndt_align) where that is not NULL, else T_host.
+ *   gate_dev (may be NULL) points at a device int32: unless it holds 0 or 1 (status_dev[0] of an alignment, best_dev[1]
+ *   of a batch) the call changes no byte of the map and info_dev = (cells assigned, 0, 0, 0).  Per point
+ *   q = ((r0*x + r1*y) + r2*z) + t; its cell is floor(q / resolution) per axis; a non-finite coordinate or a cell index
+ *   beyond +-1048575 skips the point.
+ *     New cells: a cell that is not in the map is founded by the lowest point index that falls in it; founders get
+ *       consecutive cell ids in ascending founder index from the current count; a founder whose id would reach
+ *       cell_capacity founds nothing and the points of its cell are dropped for this update.
+ *     Batch: per touched cell n_b, mean_b, S_b over its points in ascending point index, in the operation order of
+ *       sps_ndt_map_build (sum, divide, second pass of outer products).
+ *     Forgetting (max_cell_points = m; 0 and 1: off): if m >= 2 and the stored n > m, S *= (m - 1) / (n - 1) (one division,
+ *       six products) and n = m, before the merge.
+ *     Merge: stored n = 0 takes (n_b, mean_b, S_b).  Otherwise n' = n + n_b, delta = mean_b - mean, f = n_b / n',
+ *       mean' = mean + delta * f, g = (n * n_b) / n', S'_ij = (S_ij + S_b,ij) + (delta_i * delta_j) * g.  The record is then
+ *       written from (n', mean', S') as sps_ndt_map_build writes it (S' / (n' - 1), Jacobi, eigenvalue floor, inverse,
+ *       validity with the build's min_points and eig_ratio).  Untouched cells keep every bit.
+ *   info_dev int32[4] = (cells assigned after the update, cells founded, cells dropped for capacity in this update,
+ *   points integrated).  Seven launches and two memsets of the scratch whatever the data; cap <=
+ *   SPS_NDT_UPDATE_MAX_POINTS.  scratch_dev: sps_ndt_map_update_scratch(cap) bytes (-1 for cap out of range), 256-byte
+ *   aligned.  The result depends on the points, their order and the pose only.  Never allocates, never synchronises, never
+ *   raises the sticky error.
+ * sps_ndt_map_info: debug -- out_host = (cells assigned, cell_capacity, cells dropped since the build, 0).  Synchronises. */
+#define SPS_NDT_UPDATE_MAX_POINTS 65536
+int sps_ndt_map_build_dynamic(sps_ctx *ctx, const uint64_t *cell_keys_dev, const int32_t *cell_start_dev,
+                              const int32_t *cell_pts_dev, const double *map_xyz_dev, int64_t n_cells, int64_t n_map,
+                              double resolution, int min_points, double eig_ratio, int64_t cell_capacity, void *stream);
+int64_t sps_ndt_map_update_scratch(int64_t cap);
+int sps_ndt_map_update(sps_ctx *ctx, const double *pts_dev, const int32_t *n_dev, int64_t cap, const double *T_host,
+                       const double *T_dev, const int32_t *gate_dev, int max_cell_points, int32_t *info_dev,
+                       void *scratch_dev, void *stream);
+int sps_ndt_map_info(sps_ctx *ctx, int64_t *out_host);
+
 #ifdef __cplusplus
 }
 #endif

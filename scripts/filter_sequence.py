@@ -133,16 +133,22 @@ def hypothesis_grid(counts, steps, option="--hypotheses", step_option="--hypothe
     return np.concatenate([g[[centre]], np.delete(g, centre, axis=0)])
 
 
-def closed_loop(name, f, pc_map, replay, finish, traj_out, which="icp", hypotheses=None, search=None):
+def closed_loop(name, f, pc_map, replay, finish, traj_out, which="icp", hypotheses=None, search=None, update_map=False,
+                cell_capacity=None, max_cell_points=0):
     """--localise: one LocalisationLoop step per frame, scored against the replayed poses."""
     from sps_amd.localiser import LocalisationLoop, NDTLocaliser, ScanToMapLocaliser
     from sps_amd.trajectory import ape_translation, rotation_angle, write_trajectory
-    localiser = NDTLocaliser(pc_map[:, :3]) if which == "ndt" else ScanToMapLocaliser(pc_map[:, :3])
+    if update_map:                                               # an online map: room for twice the map's cells by default
+        n_cells = NDTLocaliser(pc_map[:, :3]).n_cells
+        localiser = NDTLocaliser(pc_map[:, :3], cell_capacity=cell_capacity or max(2 * n_cells, 4096))
+    else:
+        localiser = NDTLocaliser(pc_map[:, :3]) if which == "ndt" else ScanToMapLocaliser(pc_map[:, :3])
     loop, stamps, ref = None, [], []
     for stamp, scan, pose, map_tr in replay:
         T = map_tr @ pose
         if loop is None:
-            loop = LocalisationLoop(f, localiser, T, hypotheses=hypotheses, search=search)
+            loop = LocalisationLoop(f, localiser, T, hypotheses=hypotheses, search=search, update_map=update_map,
+                                    max_cell_points=max_cell_points)
         step = loop.step(scan)
         finish(stamp, None, step.filter_result)
         p = step.pose_result
@@ -150,6 +156,10 @@ def closed_loop(name, f, pc_map, replay, finish, traj_out, which="icp", hypothes
         err_r = float(np.degrees(rotation_angle(step.pose, T)))
         print(f"[{stamp}] loc: {p.status:d} {p.iterations:d} {p.n_corr:d} {p.rmse:.4f} | {err_t:.4f} {err_r:.4f}"
               + (" (flagged: the guess is kept)" if step.flagged else ""))
+        u = step.batch.map_update if step.batch is not None else p.map_update
+        if u is not None:
+            print(f"[{stamp}] map: {u.cells:d} cells | founded {u.founded:d} dropped {u.dropped:d} | {u.points:d} of {u.n_points:d} "
+                  f"points integrated")
         if step.search is not None:
             r = step.search
             print(f"[{stamp}] search: pose {r.index:d} of {len(r.scores):d} | candidates " + " ".join(str(int(k)) for k in r.candidates)
@@ -188,8 +198,18 @@ def closed_loop(name, f, pc_map, replay, finish, traj_out, which="icp", hypothes
                    "every flagged frame; the best 8 are registered")
 @click.option("--search-step", "search_steps", type=str, default="1,0.5,5",
               help="with --search: DA,DB,DYAW_DEG, the grid's spacing in m, m and degrees")
+@click.option("--update-map", "update_map", is_flag=True,
+              help="with --localiser ndt: fold every frame's kept points into the NDT map at its corrected pose")
+@click.option("--cell-capacity", "cell_capacity", type=int, default=None,
+              help="with --update-map: cells the online map has room for (default: twice the map's, at least 4096)")
+@click.option("--max-cell-points", "max_cell_points", type=int, default=0,
+              help="with --update-map: cap on the weight of a cell's history (0: none)")
 def main(name, weights, sequence, config, epsilon, out_dir, n_synth, localise, which, traj_out, hyp_counts, hyp_steps,
-         search_counts, search_steps):
+         search_counts, search_steps, update_map, cell_capacity, max_cell_points):
+    if update_map and which != "ndt":
+        raise click.UsageError("--update-map needs --localise --localiser ndt")
+    if (cell_capacity is not None or max_cell_points) and not update_map:
+        raise click.UsageError("--cell-capacity and --max-cell-points need --update-map")
     if which is not None and not localise:
         raise click.UsageError("--localiser needs --localise")
     if hyp_counts is not None and which != "ndt":
@@ -233,7 +253,8 @@ def main(name, weights, sequence, config, epsilon, out_dir, n_synth, localise, w
         n_done += 1
 
     if localise:
-        closed_loop(name, f, pc_map, replay, finish, traj_out, which or "icp", hypotheses, search)
+        closed_loop(name, f, pc_map, replay, finish, traj_out, which or "icp", hypotheses, search, update_map, cell_capacity,
+                    max_cell_points)
     elif traj_out:
         raise click.UsageError("--traj-out needs --localise")
     in_flight, prev_pose = None, None

@@ -140,6 +140,10 @@ def _load() -> C.CDLL:
         "sps_ndt_score_scratch": (i64, [i64, i64]),
         "sps_ndt_score_poses": (i32, [vp, vp, vp, i64, vp, i64, i32, C.c_double, vp, vp, vp]),
         "sps_ndt_top_poses": (i32, [vp, vp, vp, i64, i32, i32, vp, vp, vp, vp]),
+        "sps_ndt_map_build_dynamic": (i32, [vp, vp, vp, vp, vp, i64, i64, C.c_double, i32, C.c_double, i64, vp]),
+        "sps_ndt_map_update_scratch": (i64, [i64]),
+        "sps_ndt_map_update": (i32, [vp, vp, vp, i64, vp, vp, vp, i32, vp, vp, vp]),
+        "sps_ndt_map_info": (i32, [vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)          # AttributeError here = header/library mismatch: fail loudly
@@ -169,7 +173,8 @@ EXPORTS = ["sps_last_error", "sps_version", "sps_ctx_create", "sps_ctx_destroy",
            "sps_loc_downsample_scratch", "sps_loc_align_scratch", "sps_loc_downsample", "sps_loc_align",
            "sps_ndt_align_scratch", "sps_ndt_map_build", "sps_ndt_map_cells", "sps_ndt_align",
            "sps_ndt_align_batch_scratch", "sps_ndt_align_batch",
-           "sps_ndt_score_scratch", "sps_ndt_score_poses", "sps_ndt_top_poses"]
+           "sps_ndt_score_scratch", "sps_ndt_score_poses", "sps_ndt_top_poses",
+           "sps_ndt_map_build_dynamic", "sps_ndt_map_update_scratch", "sps_ndt_map_update", "sps_ndt_map_info"]
 CROP_BLOCK = 1024          # SPS_CROP_BLOCK: map rows per int of sps_radius_crop's scratch
 
 
@@ -458,6 +463,23 @@ class Context:
                       n_top_ptr: int, stream: int):
         check(lib.sps_ndt_top_poses(self.handle, score_ptr, T_ptr, int(n_pose), int(min_corr), int(k), top_index_ptr, T_top_ptr,
                                     n_top_ptr, stream))
+
+    # ---- NDT localiser, online map (include/sps_hip.h, "NDT localiser, online map") ----
+    def ndt_map_build_dynamic(self, keys_ptr, start_ptr, pts_ptr, xyz_ptr, n_cells: int, n_map: int, resolution: float,
+                              min_points: int, eig_ratio: float, cell_capacity: int, stream: int):
+        check(lib.sps_ndt_map_build_dynamic(self.handle, keys_ptr, start_ptr, pts_ptr, xyz_ptr, int(n_cells), int(n_map),
+                                            float(resolution), int(min_points), float(eig_ratio), int(cell_capacity), stream))
+
+    def ndt_map_update(self, pts_ptr, n_dev_ptr: int, cap: int, T_host, T_dev_ptr, gate_ptr, max_cell_points: int,
+                       info_ptr: int, scratch_ptr: int, stream: int):
+        check(lib.sps_ndt_map_update(self.handle, pts_ptr, n_dev_ptr, int(cap), self._mat(T_host) if T_host is not None else None,
+                                     T_dev_ptr, gate_ptr, int(max_cell_points), info_ptr, scratch_ptr, stream))
+
+    def ndt_map_info(self):
+        """(cells assigned, cell capacity, cells dropped for capacity since the build); synchronises"""
+        out = (C.c_int64 * 4)()
+        check(lib.sps_ndt_map_info(self.handle, out))
+        return int(out[0]), int(out[1]), int(out[2])
 
     def train_forward(self, params_ptr: int, numel: int, coords_ptr: int, ld: int, n: int, voxel_size: float,
                       scores_ptr: int, batch_stats_ptr, stream: int):

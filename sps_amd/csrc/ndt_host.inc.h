@@ -35,6 +35,7 @@ int sps_ndt_map_build(sps_ctx *c, const uint64_t *cell_keys_dev, const int32_t *
   for (void *p : c->ndt_allocs) (void)hipFree(p);
   c->ndt_allocs.clear();
   c->ndt = NdtMap{};
+  c->ndt_dyn = NdtDyn{};   // a static map replaces a dynamic one
   auto alloc = [&](void **p, size_t bytes) -> hipError_t {
     hipError_t e = hipMalloc(p, bytes ? bytes : 16);
     if (e == hipSuccess) c->ndt_allocs.push_back(*p);

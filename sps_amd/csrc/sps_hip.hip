@@ -151,6 +151,7 @@ int fail(int code, const char *fmt, ...) {
 #include "ndt_kernels.inc.h"
 #include "ndt_batch_kernels.inc.h"
 #include "ndt_search_kernels.inc.h"
+#include "ndt_update_kernels.inc.h"
 
 // ------------------------------------------------------------------------------------------
 // context
@@ -306,6 +307,7 @@ struct sps_ctx {
   // NDT localiser map (sps_ndt_map_build): cell hash + one 80-byte record per cell, owned by the ctx
   NdtMap ndt{};
   std::vector<void *> ndt_allocs;
+  NdtDyn ndt_dyn{};                      // capacity > 0: the map is dynamic (sps_ndt_map_build_dynamic)
   // variant-A item scratch (sps_radius_item): per (scan point, neighbour cell) hit counts and their prefix sums
   int *item_counts = nullptr, *item_offsets = nullptr, *item_bsum = nullptr, *item_base = nullptr;
   int64_t item_cap = 0;
@@ -2256,5 +2258,6 @@ int sps_get_feature(sps_ctx *c, const char *name, float *out_dev, int64_t *rows,
 #include "ndt_host.inc.h"
 #include "ndt_batch_host.inc.h"
 #include "ndt_search_host.inc.h"
+#include "ndt_update_host.inc.h"
 
 }  // extern "C"

@@ -25,6 +25,10 @@ converges there with status 0, and only the score tells.  ``pose_grid`` builds t
 keeps the best ``keep`` <= 64 on the device and registers from those (C ABI: "NDT localiser, pose search"):
 for a pose known to a few metres and a few tens of degrees only.
 
+``NDTLocaliser(..., cell_capacity=N)`` keeps an online map (C ABI: "NDT localiser, online map"): per-cell
+moments for up to N cells, and ``integrate`` / ``submit(..., integrate=True)`` fold a frame's thinned points into them at
+a host pose or at the frame's own corrected pose, on the frame's stream and gated by its status on the device.
+
 ``LocalisationLoop`` closes the loop for any of the seven filters of scripts/filter_sequence.py, around either localiser.
 """
 from __future__ import annotations
@@ -53,17 +57,44 @@ class PoseResult:
     trace: np.ndarray          # [iterations, 4] (n_corr, sum d^2, |v|, |omega|) per iteration run
     normal: np.ndarray = None  # [iterations, 28] H (upper triangle), b, sum d^2 -- only with with_normal=True
     n_points: int = 0          # scan points that entered the alignment (after thinning)
+    map_update: object = None  # MapUpdateResult of the frame, with integrate=True
 
     @property
     def ok(self) -> bool:
         return self.status in (CONVERGED, EXHAUSTED)
 
 
+@dataclass
+class MapUpdateResult:
+    cells: int                 # cells assigned after the update
+    founded: int               # cells founded by this update
+    dropped: int               # cells this update could not found for lack of capacity (their points were dropped)
+    points: int                # points integrated; 0 with founded = dropped = 0 also where the gate was closed
+    n_points: int = 0          # points that were offered (after thinning)
+
+
+def _map_update_of(words, n_points) -> MapUpdateResult:
+    return MapUpdateResult(int(words[0]), int(words[1]), int(words[2]), int(words[3]), int(n_points))
+
+
+class PendingMapUpdate:
+    """A map update whose work has been issued; ``result()`` -> MapUpdateResult."""
+
+    def __init__(self, host, event, keep):
+        self._host, self._event, self._keep = host, event, keep
+
+    def result(self) -> MapUpdateResult:
+        self._event.synchronize()                                    # the one host synchronisation
+        h = self._host.numpy()
+        return _map_update_of(h[4:8], h[0])
+
+
 class PendingPose:
     """A localisation whose work has been issued; everything lives on the device until result()."""
 
-    def __init__(self, iters, with_normal, host, event, keep):
+    def __init__(self, iters, with_normal, host, event, keep, upd_at=None):
         self._iters, self._with_normal, self._host, self._event, self._keep = iters, with_normal, host, event, keep
+        self._upd_at = upd_at                                        # doubles in front of the map update's info words
 
     def result(self) -> PoseResult:
         self._event.synchronize()                                    # the one host synchronisation
@@ -74,7 +105,8 @@ class PendingPose:
         trace = h[19:19 + 4 * K].reshape(K, 4)[:it].copy()
         normal = h[19 + 4 * K:19 + 32 * K].reshape(K, 28)[:it].copy() if self._with_normal else None
         rmse = math.sqrt(trace[-1, 1] / n_corr) if it and n_corr > 0 else float("nan")
-        return PoseResult(h[:16].reshape(4, 4).copy(), code, it, n_corr, rmse, trace, normal, n_points)
+        upd = None if self._upd_at is None else _map_update_of(h[self._upd_at:self._upd_at + 2].view(np.int32), n_points)
+        return PoseResult(h[:16].reshape(4, 4).copy(), code, it, n_corr, rmse, trace, normal, n_points, upd)
 
 
 @dataclass
@@ -84,14 +116,16 @@ class BatchPoseResult:
     counts: np.ndarray         # [K] int, the scan points counted at that pose
     best: int                  # the hypothesis selected, or -1 where none has status 0 / 1 and enough points counted
     pose: np.ndarray           # 4x4: results[best].pose, or the first start pose when best is -1
+    map_update: object = None  # MapUpdateResult of the frame, with integrate=True
 
 
 class PendingPoses:
     """A batch of localisations whose work has been issued; everything lives on the device until result()."""
 
-    def __init__(self, n_hyp, iters, with_normal, host, event, keep, at=0):
+    def __init__(self, n_hyp, iters, with_normal, host, event, keep, at=0, upd=False):
         self._n_hyp, self._iters, self._with_normal, self._host, self._event, self._keep = n_hyp, iters, with_normal, host, event, keep
         self._at = at                                                # doubles in front of the batch's part of the buffer
+        self._upd = upd                                              # the map update's info words follow the batch's part
 
     def result(self) -> BatchPoseResult:
         self._event.synchronize()                                    # the one host synchronisation
@@ -112,8 +146,9 @@ class PendingPoses:
             rmse = math.sqrt(tr[-1, 1] / n_corr) if it and n_corr > 0 else float("nan")
             results.append(PoseResult(T_out[k].copy(), code, it, n_corr, rmse, tr,
                                       normal[k, :it].copy() if normal is not None else None, n_points))
+        upd = _map_update_of(h[o["size"]:o["size"] + 2].view(np.int32), n_points) if self._upd else None
         return BatchPoseResult(results, final[:, 0].copy(), final[:, 1].astype(np.int64), int(best[0]),
-                               h[o["T_best"]:o["T_best"] + 16].reshape(4, 4).copy())
+                               h[o["T_best"]:o["T_best"] + 16].reshape(4, 4).copy(), upd)
 
 
 def _batch_layout(K, I, with_normal):
@@ -147,6 +182,7 @@ def pose_grid(along, across, yaw_deg) -> np.ndarray:
 
 MAX_HYPOTHESES = 64            # SPS_NDT_MAX_HYP
 MAX_POSES = 65536              # SPS_NDT_MAX_POSES
+MAX_UPDATE_POINTS = 65536      # SPS_NDT_UPDATE_MAX_POINTS
 
 
 def _checked_poses(poses, what="poses"):
@@ -176,6 +212,7 @@ class RelocalisationResult:
     batch: BatchPoseResult     # the ``keep`` alignments, hypothesis j started from the pose of candidates[j]
     index: int                 # the grid index of the selected alignment's start pose, or -1 where none was selected
     pose: np.ndarray           # 4x4: batch.pose
+    map_update: object = None  # MapUpdateResult of the frame, with integrate=True (batch.map_update)
 
     @property
     def ok(self) -> bool:
@@ -209,7 +246,7 @@ class PendingRelocalisation:
         cand = h[o["top"]:o["top"] + (K + 1) // 2].view(np.int32)[:K].astype(np.int64)
         batch = b.result()
         index = int(cand[batch.best]) if batch.best >= 0 else -1
-        return RelocalisationResult(sc[:, 0].copy(), sc[:, 1].astype(np.int64), cand, batch, index, batch.pose)
+        return RelocalisationResult(sc[:, 0].copy(), sc[:, 1].astype(np.int64), cand, batch, index, batch.pose, batch.map_update)
 
 
 class ScanToMapLocaliser:
@@ -275,9 +312,13 @@ class ScanToMapLocaliser:
         return torch.full((1,), int(count), dtype=torch.int32, device=self.device)
 
     @torch.no_grad()
-    def submit(self, rows, count, T_init, with_normal: bool = False, iterations: int = None) -> PendingPose:
+    def submit(self, rows, count, T_init, with_normal: bool = False, iterations: int = None, integrate: bool = False,
+               max_cell_points: int = 0) -> PendingPose:
         """rows: device tensor [n_max, >= 3] (float32; other dtypes are converted); count: an int or a device int32 tensor
-        holding the number of valid rows; T_init: 4x4.  Issued on the current stream."""
+        holding the number of valid rows; T_init: 4x4.  Issued on the current stream.  ``integrate`` (a localiser with an
+        online map only): the thinned points are then folded into the map at the corrected pose, behind the alignment on
+        the same stream and only where its status is 0 or 1; the result's ``map_update`` tells what happened."""
+        self._check_integrate(integrate, max_cell_points)
         rows = self._checked_rows(rows)
         T = _pose(T_init)
         if T is None or not np.isfinite(T).all():
@@ -289,7 +330,8 @@ class ScanToMapLocaliser:
             s = st.cuda_stream
             n_dev = self._count_on_device(count, n_max)
             # one float64 buffer per frame: T_out[16] | status int32[4] | n_points int32 (+ pad) | trace[K][4] | normal[K][28]
-            out = torch.zeros(19 + 32 * K if with_normal else 19 + 4 * K, dtype=torch.float64, device=dev)
+            size = 19 + 32 * K if with_normal else 19 + 4 * K
+            out = torch.zeros(size + 2 if integrate else size, dtype=torch.float64, device=dev)   # | info int32[4]
             base = out.data_ptr()
             scratch = self._downsample_scratch(n_max)
             self.ctx.loc_downsample(rows.data_ptr() if n_max else None, rows.stride(0) if n_max else 3, n_max,
@@ -297,11 +339,19 @@ class ScanToMapLocaliser:
                                     scratch.data_ptr(), s)
             self._align(base + 18 * 8, T, K, base, base + 16 * 8, base + 19 * 8 if K else None,
                         base + (19 + 4 * K) * 8 if with_normal and K else None, s)
+            if integrate:
+                self._update(base + 18 * 8, None, base, base + 16 * 8, max_cell_points, base + size * 8, s)
             host = torch.empty(out.numel(), dtype=torch.float64).pin_memory()
             host.copy_(out, non_blocking=True)
             ev = torch.cuda.Event()
             ev.record(st)
-        return PendingPose(K, with_normal, host, ev, (rows, n_dev, out))
+        return PendingPose(K, with_normal, host, ev, (rows, n_dev, out), size if integrate else None)
+
+    def _check_integrate(self, integrate, max_cell_points=0):
+        if integrate and getattr(self, "cell_capacity", None) is None:
+            raise ValueError("integrate needs a localiser with an online map: NDTLocaliser(..., cell_capacity=N)")
+        if integrate and int(max_cell_points) < 0:
+            raise ValueError("max_cell_points must be >= 0")
 
     def _align(self, n_ptr, T, K, T_out_ptr, status_ptr, trace_ptr, normal_ptr, s):
         self.ctx.loc_align(self._pts.data_ptr(), n_ptr, self.capacity, T, K, self.min_correspondences, self.tol_t, self.tol_r,
@@ -326,8 +376,11 @@ class NDTLocaliser(ScanToMapLocaliser):
 
     def __init__(self, map_points, resolution: float = 1.0, neighbours: int = 7, leaf: float = 0.2, iterations: int = 30,
                  min_correspondences: int = 50, min_points_per_cell: int = 6, outlier_ratio: float = 0.55,
-                 eig_ratio: float = 0.01, tol_t: float = 1e-4, tol_r: float = 1e-5, device="cuda", capacity: int = 1 << 16):
+                 eig_ratio: float = 0.01, tol_t: float = 1e-4, tol_r: float = 1e-5, device="cuda", capacity: int = 1 << 16,
+                 cell_capacity: int = None):
         from .datasets.blt_dataset import radius_grid_cells
+        if cell_capacity is not None and (int(cell_capacity) < 1 or capacity > MAX_UPDATE_POINTS):
+            raise ValueError(f"cell_capacity must be >= 1 and, with it, capacity <= {MAX_UPDATE_POINTS}")
         if not (math.isfinite(resolution) and resolution > 0 and math.isfinite(leaf) and leaf > 0):
             raise ValueError("resolution and leaf must be finite and > 0")
         if neighbours not in (1, 7):
@@ -340,6 +393,7 @@ class NDTLocaliser(ScanToMapLocaliser):
         self.iterations, self.min_correspondences = int(iterations), int(min_correspondences)
         self.min_points_per_cell, self.outlier_ratio, self.eig_ratio = int(min_points_per_cell), float(outlier_ratio), float(eig_ratio)
         self.tol_t, self.tol_r, self.capacity = float(tol_t), float(tol_r), int(capacity)
+        self.cell_capacity = None if cell_capacity is None else int(cell_capacity)
         self.device = _device_of(device)
         mp = map_points.detach().cpu().numpy() if torch.is_tensor(map_points) else np.asarray(map_points)
         xyz = torch.as_tensor(np.ascontiguousarray(mp[:, :3], dtype=np.float64)).to(self.device)
@@ -347,7 +401,22 @@ class NDTLocaliser(ScanToMapLocaliser):
         with torch.cuda.device(self.device):
             self.stream = torch.cuda.current_stream()
             self.ctx = _native.Context(self.device.index)
-            if self.n_map:
+            if self.cell_capacity is not None:
+                keys = start = pts = None
+                self.n_cells = 0
+                if self.n_map:
+                    keys, start, pts = radius_grid_cells(xyz, self.resolution)
+                    self.n_cells = len(keys)
+                if self.cell_capacity < max(self.n_cells, 1):
+                    raise ValueError(f"cell_capacity {self.cell_capacity} is below the map's {self.n_cells} cells")
+                self.ctx.ndt_map_build_dynamic(keys.contiguous().data_ptr() if self.n_map else None,
+                                               start.data_ptr() if self.n_map else None, pts.data_ptr() if self.n_map else None,
+                                               xyz.data_ptr() if self.n_map else None, self.n_cells, self.n_map, self.resolution,
+                                               self.min_points_per_cell, self.eig_ratio, self.cell_capacity,
+                                               self.stream.cuda_stream)
+                self._update_scratch = torch.empty(_native.lib.sps_ndt_map_update_scratch(self.capacity), dtype=torch.uint8,
+                                                   device=self.device)
+            elif self.n_map:
                 keys, start, pts = radius_grid_cells(xyz, self.resolution)
                 self.n_cells = len(keys)
                 self.ctx.ndt_map_build(keys.contiguous().data_ptr(), start.data_ptr(), pts.data_ptr(), xyz.data_ptr(),
@@ -368,12 +437,52 @@ class NDTLocaliser(ScanToMapLocaliser):
                            self.outlier_ratio, self.tol_t, self.tol_r, T_out_ptr, status_ptr, trace_ptr, normal_ptr,
                            self._align_scratch.data_ptr(), s)
 
+    def _update(self, n_ptr, T_host, T_dev_ptr, gate_ptr, max_cell_points, info_ptr, s):
+        self.ctx.ndt_map_update(self._pts.data_ptr(), n_ptr, self.capacity, T_host, T_dev_ptr, gate_ptr, max_cell_points,
+                                info_ptr, self._update_scratch.data_ptr(), s)
+
     @torch.no_grad()
-    def submit_batch(self, rows, count, T_inits, with_normal: bool = False, iterations: int = None) -> PendingPoses:
+    def integrate(self, rows, count, T, max_cell_points: int = 0) -> PendingMapUpdate:
+        """Fold the rows into the online map at the host pose ``T`` (4x4, sensor -> map): they are thinned with the
+        localiser's ``leaf`` as ``submit`` thins them, then every point joins the moments of its cell; cells the map does
+        not have yet are founded while ``cell_capacity`` lasts.  ``max_cell_points`` (0: off) caps the weight of a cell's
+        history, so that a changed scene is forgotten.  Issued on the current stream; ``result()`` -> MapUpdateResult."""
+        self._check_integrate(True, max_cell_points)
+        rows = self._checked_rows(rows)
+        Th = _pose(T)
+        if Th is None or not np.isfinite(Th).all():
+            raise ValueError("T must be a finite 4x4 matrix")
+        n_max, dev = rows.shape[0], self.device
+        with torch.cuda.device(dev):
+            st = torch.cuda.current_stream()
+            s = st.cuda_stream
+            n_dev = self._count_on_device(count, n_max)
+            out = torch.zeros(8, dtype=torch.int32, device=dev)      # n_points (+ pad) | info[4]
+            base = out.data_ptr()
+            self.ctx.loc_downsample(rows.data_ptr() if n_max else None, rows.stride(0) if n_max else 3, n_max,
+                                    n_dev.data_ptr(), self.leaf, self._pts.data_ptr(), self.capacity, base,
+                                    self._downsample_scratch(n_max).data_ptr(), s)
+            self._update(base, Th, None, None, max_cell_points, base + 16, s)
+            host = torch.empty(8, dtype=torch.int32).pin_memory()
+            host.copy_(out, non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record(st)
+        return PendingMapUpdate(host, ev, (rows, n_dev, out))
+
+    def map_info(self):
+        """Debug: (cells assigned, cell capacity, cells dropped for capacity since the build) of the online map; synchronises."""
+        self._check_integrate(True)
+        return self.ctx.ndt_map_info()
+
+    @torch.no_grad()
+    def submit_batch(self, rows, count, T_inits, with_normal: bool = False, iterations: int = None, integrate: bool = False,
+                     max_cell_points: int = 0) -> PendingPoses:
         """``submit`` from the K start poses ``T_inits`` [K, 4, 4] (1 <= K <= 64) at once: the scan is thinned once, every
         hypothesis is registered as ``submit`` would register it from its pose, and the hypothesis with the highest NDT
         score at its final pose is selected among those with status 0 / 1 and at least ``min_correspondences`` points
-        counted there (equal scores: the lowest index).  Issued on the current stream; ``result()`` -> BatchPoseResult."""
+        counted there (equal scores: the lowest index).  Issued on the current stream; ``result()`` -> BatchPoseResult.
+        ``integrate``: as for ``submit``, at the selected pose and only where a hypothesis was selected."""
+        self._check_integrate(integrate, max_cell_points)
         rows = self._checked_rows(rows)
         T = np.ascontiguousarray(np.asarray(T_inits, dtype=np.float64))
         if T.ndim != 3 or T.shape[1:] != (4, 4) or not 1 <= len(T) <= MAX_HYPOTHESES or not np.isfinite(T).all():
@@ -387,7 +496,7 @@ class NDTLocaliser(ScanToMapLocaliser):
             n_dev = self._count_on_device(count, n_max)
             T_host = torch.from_numpy(T).pin_memory()
             T_dev = T_host.to(dev, non_blocking=True)                # on the caller's stream; both stay with the pending object
-            out = torch.zeros(o["size"], dtype=torch.float64, device=dev)
+            out = torch.zeros(o["size"] + 2 if integrate else o["size"], dtype=torch.float64, device=dev)   # | info int32[4]
             base = out.data_ptr()
             self.ctx.loc_downsample(rows.data_ptr() if n_max else None, rows.stride(0) if n_max else 3, n_max,
                                     n_dev.data_ptr(), self.leaf, self._pts.data_ptr(), self.capacity, base + o["n_points"] * 8,
@@ -397,11 +506,14 @@ class NDTLocaliser(ScanToMapLocaliser):
                                      base + o["T_out"] * 8, base + o["status"] * 8, base + o["trace"] * 8 if I else None,
                                      base + o["normal"] * 8 if with_normal and I else None, base + o["final"] * 8,
                                      base + o["best"] * 8, base + o["T_best"] * 8, self._batch_scratch_for(K).data_ptr(), s)
+            if integrate:                                            # best[1]: the selected hypothesis' status, -1 where none
+                self._update(base + o["n_points"] * 8, None, base + o["T_best"] * 8, base + o["best"] * 8 + 4, max_cell_points,
+                             base + o["size"] * 8, s)
             host = torch.empty(out.numel(), dtype=torch.float64).pin_memory()
             host.copy_(out, non_blocking=True)
             ev = torch.cuda.Event()
             ev.record(st)
-        return PendingPoses(K, I, with_normal, host, ev, (rows, n_dev, out, T_host, T_dev))
+        return PendingPoses(K, I, with_normal, host, ev, (rows, n_dev, out, T_host, T_dev), upd=integrate)
 
     def submit_filtered_batch(self, pending, T_inits, **kw) -> PendingPoses:
         """``submit_batch`` of the kept rows of a pending SPSFilter / SPSCVMFilter frame, without the frame's result()."""
@@ -450,12 +562,14 @@ class NDTLocaliser(ScanToMapLocaliser):
         return PendingScores(P, host, ev, (rows, n_dev, out, T_host, T_dev))
 
     @torch.no_grad()
-    def relocalise(self, rows, count, poses, keep: int = 8, with_normal: bool = False,
-                   iterations: int = None) -> PendingRelocalisation:
+    def relocalise(self, rows, count, poses, keep: int = 8, with_normal: bool = False, iterations: int = None,
+                   integrate: bool = False, max_cell_points: int = 0) -> PendingRelocalisation:
         """Thin, score the P poses ``poses`` [P, 4, 4] (e.g. ``T_center @ pose_grid(...)``), keep the best ``keep`` (1..64)
         by (score descending, index ascending) among those with at least ``min_correspondences`` points counted, register
         from these as ``submit_batch`` does and select among the end poses as it selects.  Everything is issued on the
-        current stream with no synchronisation in between; ``result()`` -> RelocalisationResult."""
+        current stream with no synchronisation in between; ``result()`` -> RelocalisationResult.  ``integrate``: as for
+        ``submit_batch``."""
+        self._check_integrate(integrate, max_cell_points)
         rows = self._checked_rows(rows)
         T = _checked_poses(poses)
         K = int(keep)
@@ -470,7 +584,7 @@ class NDTLocaliser(ScanToMapLocaliser):
             n_dev = self._count_on_device(count, n_max)
             T_host = torch.from_numpy(T).pin_memory()
             T_dev = T_host.to(dev, non_blocking=True)
-            out = torch.zeros(so["size"] + o["size"], dtype=torch.float64, device=dev)
+            out = torch.zeros(so["size"] + o["size"] + (2 if integrate else 0), dtype=torch.float64, device=dev)
             sbase = out.data_ptr()
             base = sbase + so["size"] * 8
             n_ptr = base + o["n_points"] * 8
@@ -482,11 +596,14 @@ class NDTLocaliser(ScanToMapLocaliser):
                                      base + o["T_out"] * 8, base + o["status"] * 8, base + o["trace"] * 8 if I else None,
                                      base + o["normal"] * 8 if with_normal and I else None, base + o["final"] * 8,
                                      base + o["best"] * 8, base + o["T_best"] * 8, self._batch_scratch_for(K).data_ptr(), s)
+            if integrate:
+                self._update(n_ptr, None, base + o["T_best"] * 8, base + o["best"] * 8 + 4, max_cell_points, base + o["size"] * 8, s)
             host = torch.empty(out.numel(), dtype=torch.float64).pin_memory()
             host.copy_(out, non_blocking=True)
             ev = torch.cuda.Event()
             ev.record(st)
-        return PendingRelocalisation(P, PendingPoses(K, I, with_normal, host, ev, (rows, n_dev, out, T_host, T_dev), so["size"]))
+        return PendingRelocalisation(P, PendingPoses(K, I, with_normal, host, ev, (rows, n_dev, out, T_host, T_dev), so["size"],
+                                                     upd=integrate))
 
     def relocalise_filtered(self, pending, poses, **kw) -> PendingRelocalisation:
         """``relocalise`` of the kept rows of a pending SPSFilter / SPSCVMFilter frame, without the frame's result()."""
@@ -494,8 +611,10 @@ class NDTLocaliser(ScanToMapLocaliser):
 
     def map_cells(self):
         """Debug: (keys uint64 [C], counts int32 [C], means [C, 3], inverse covariances [C, 6] as (xx, xy, xz, yy, yz, zz),
-        valid bool [C]) of the device map, in ascending key order, as numpy arrays."""
-        C = self.n_cells
+        valid bool [C]) of the device map, in ascending key order, as numpy arrays.  An online map gives its assigned
+        cells in the order of their ids: the cells of the build in ascending key order, then the founded cells in the order
+        they were founded."""
+        C = self.n_cells if self.cell_capacity is None else self.cell_capacity
         with torch.cuda.device(self.device):
             key = torch.zeros(C, dtype=torch.int64, device=self.device)
             cnt = torch.zeros(C, dtype=torch.int32, device=self.device)
@@ -503,8 +622,9 @@ class NDTLocaliser(ScanToMapLocaliser):
             icov = torch.zeros((C, 6), dtype=torch.float64, device=self.device)
             valid = torch.zeros(C, dtype=torch.int32, device=self.device)
             self.ctx.ndt_map_cells(key.data_ptr(), cnt.data_ptr(), mean.data_ptr(), icov.data_ptr(), valid.data_ptr())
-        return (key.cpu().numpy().view(np.uint64), cnt.cpu().numpy(), mean.cpu().numpy(), icov.cpu().numpy(),
-                valid.cpu().numpy().astype(bool))
+        n = C if self.cell_capacity is None else self.ctx.ndt_map_info()[0]
+        return (key.cpu().numpy().view(np.uint64)[:n], cnt.cpu().numpy()[:n], mean.cpu().numpy()[:n], icov.cpu().numpy()[:n],
+                valid.cpu().numpy().astype(bool)[:n])
 
 
 @dataclass
@@ -542,11 +662,23 @@ class LocalisationLoop:
     The first frame and every frame directly after a flagged frame are then registered by
     ``relocalise(guess @ search[k], keep=search_keep)`` instead of the plain or batch registration: the grid is scored, its
     best ``search_keep`` poses are aligned and the best end pose is handed on; a frame in which none is selected is flagged
-    and keeps the guess."""
+    and keeps the guess.
 
-    def __init__(self, filter, localiser, initial_pose, hypotheses=None, search=None, search_keep: int = 8):
+    ``update_map`` (a localiser with an online map: ``NDTLocaliser(..., cell_capacity=N)``): every frame's kept points, as
+    thinned for the registration, are folded into the map at the frame's corrected pose, behind the registration on its
+    stream.  The device gates the update on the registration's status, so a flagged frame leaves the map alone; the
+    frame's ``pose_result.map_update`` (``batch.map_update``) tells what happened.  ``max_cell_points``: the forgetting
+    cap of ``NDTLocaliser.integrate``."""
+
+    def __init__(self, filter, localiser, initial_pose, hypotheses=None, search=None, search_keep: int = 8,
+                 update_map: bool = False, max_cell_points: int = 0):
         from .sps_filters import ConstantVelocityModel
         self.filter, self.localiser = filter, localiser
+        self.update_map, self.max_cell_points = bool(update_map), int(max_cell_points)
+        if self.update_map and getattr(localiser, "cell_capacity", None) is None:
+            raise ValueError("update_map needs a localiser with an online map: NDTLocaliser(..., cell_capacity=N)")
+        # the keyword arguments every registration of the loop gets: none unless the map is updated
+        self._kw = dict(integrate=True, max_cell_points=self.max_cell_points) if self.update_map else {}
         self.hypotheses = None
         self.search, self.search_keep, self._search_next = None, int(search_keep), True
         if search is not None:
@@ -599,13 +731,13 @@ class LocalisationLoop:
         pend = self._submit_filter(scan, guess)
         starts = self.start_poses(guess)
         if hasattr(pend, "count_dev") and hasattr(pend, "_filtered"):
-            pose_pend = self.localiser.submit_filtered_batch(pend, starts)
+            pose_pend = self.localiser.submit_filtered_batch(pend, starts, **self._kw)
             fres = pend.result()
             bres = pose_pend.result()
         else:
             fres = pend.result()
             kept = fres.filtered
-            bres = self.localiser.submit_batch(kept, len(kept), starts).result()
+            bres = self.localiser.submit_batch(kept, len(kept), starts, **self._kw).result()
         flagged = bres.best < 0
         pose = guess if flagged else bres.pose
         self.model.add_pose(pose)
@@ -622,13 +754,13 @@ class LocalisationLoop:
         pend = self._submit_filter(scan, guess)
         poses = self.search_poses(guess)
         if hasattr(pend, "count_dev") and hasattr(pend, "_filtered"):
-            pose_pend = self.localiser.relocalise_filtered(pend, poses, keep=self.search_keep)
+            pose_pend = self.localiser.relocalise_filtered(pend, poses, keep=self.search_keep, **self._kw)
             fres = pend.result()
             sres = pose_pend.result()
         else:
             fres = pend.result()
             kept = fres.filtered
-            sres = self.localiser.relocalise(kept, len(kept), poses, keep=self.search_keep).result()
+            sres = self.localiser.relocalise(kept, len(kept), poses, keep=self.search_keep, **self._kw).result()
         bres = sres.batch
         flagged = sres.index < 0
         pose = guess if flagged else sres.pose
@@ -654,13 +786,13 @@ class LocalisationLoop:
             return self._step_batch(scan, guess)
         pend = self._submit_filter(scan, guess)
         if hasattr(pend, "count_dev") and hasattr(pend, "_filtered"):
-            pose_pend = self.localiser.submit_filtered(pend, guess)  # no synchronisation between filter and localiser
+            pose_pend = self.localiser.submit_filtered(pend, guess, **self._kw)  # no synchronisation between filter and localiser
             fres = pend.result()
             pres = pose_pend.result()
         else:
             fres = pend.result()
             kept = fres.filtered
-            pres = self.localiser.submit(kept, len(kept), guess).result()
+            pres = self.localiser.submit(kept, len(kept), guess, **self._kw).result()
         flagged = pres.status in (FEW_CORRESPONDENCES, SINGULAR)
         pose = guess if flagged else pres.pose
         self.model.add_pose(pose)

@@ -10,7 +10,7 @@ synthetic.build_map() map, max_distance 1 m, leaf 0.2 m):
               SPSFilter alone on the same scans
 
     python tools/localiser_timing.py [--frames 200] [--warmup 20] [--cpu-frames 1] [--one-frame] [--cpu-only]
-                                     [--localiser {icp,ndt}] [--hypotheses K] [--search P]
+                                     [--localiser {icp,ndt}] [--hypotheses K] [--search P] [--update-map]
 
 ``--localiser ndt`` times sps_amd.localiser.NDTLocaliser (1 m cells, 7 neighbours) on the same frames and from the same
 start, prints the ICP's per-frame figures of the same session beside it and the build time of both maps; the
@@ -21,6 +21,10 @@ around it) against K back-to-back submit calls from the same poses, and against 
 
 ``--localiser ndt --search P`` times NDTLocaliser.score_poses of P poses against ceil(P / 64) calls of
 submit_batch(iterations=0) over the same poses and checks that the two agree bit for bit.
+
+``--localiser ndt --update-map`` times the online map (NDTLocaliser(..., cell_capacity=N)): sps_ndt_map_update alone and
+submit(integrate=True) against submit, interleaved frame by frame with the only alternative a static map offers, a new
+NDTLocaliser over map + frame.
 
 ``--one-frame`` runs a warm-up and ONE localiser frame: the target of a ``rocprofv3 --kernel-trace --stats`` run.
 """
@@ -109,7 +113,11 @@ def main():
                     "against K back-to-back submit calls")
     ap.add_argument("--search", type=int, default=0, help="with --localiser ndt: time score_poses of P poses against "
                     "ceil(P / 64) submit_batch(iterations=0) calls, the only way to score poses without it")
+    ap.add_argument("--update-map", action="store_true", help="with --localiser ndt: time the online map's update against "
+                    "rebuilding the localiser over map + frame")
     a = ap.parse_args()
+    if a.update_map and a.localiser != "ndt":
+        ap.error("--update-map needs --localiser ndt")
     if a.search and (a.localiser != "ndt" or not 1 <= a.search <= 65536):
         ap.error("--search P needs --localiser ndt and 1 <= P <= 65536")
     if a.hypotheses and (a.localiser != "ndt" or not 1 <= a.hypotheses <= 64):
@@ -121,6 +129,8 @@ def main():
     dscans = [torch.from_numpy(s).cuda() for s in scans]
     mp = synthetic.build_map()
     T_init = LR.perturbation(0.15, 0.12, 0.05, 1.0)
+    if a.localiser == "ndt" and a.update_map:
+        return ndt_update_main(a, dscans, mp, T_init)
     if a.localiser == "ndt" and a.search:
         return ndt_search_main(a, dscans, mp, T_init)
     if a.localiser == "ndt" and a.hypotheses:
@@ -364,6 +374,70 @@ def ndt_search_main(a, dscans, mp, T_init):
     print(f"P = {P}: score_poses median {ms:.3f} ms (min {min(t_score):.3f} max {max(t_score):.3f}), {(P + 63) // 64} x "
           f"submit_batch(iterations=0) median {mb:.3f} ms (min {min(t_batch):.3f} max {max(t_batch):.3f}); {npts} points; the "
           f"bits agree", flush=True)
+    print(json.dumps(out))
+
+
+def ndt_update_main(a, dscans, mp, T_init):
+    """--update-map: per frame, in one run and in this order: submit (hipEvents), sps_ndt_map_update alone on the points that
+    submit left thinned, at the true pose (hipEvents), submit(integrate=True) (hipEvents), and a new NDTLocaliser over the
+    map and the frame's thinned points (host wall clock between two device synchronisations: the constructor groups on the
+    host and synchronises; the union is prepared outside the window).  The online map keeps growing over the run: the same
+    12 scans come back, so after the first round every update merges into existing cells."""
+    map64 = mp[:, :3].astype(np.float64)
+    static = NDTLocaliser(map64)
+    cap_cells = 2 * static.n_cells
+    ndt, build = build_ms(lambda: NDTLocaliser(map64, cell_capacity=cap_cells))
+    st = torch.cuda.current_stream()
+    I4 = np.eye(4)
+    info = torch.zeros(4, dtype=torch.int32, device="cuda")
+    n_pts = torch.zeros(1, dtype=torch.int32, device="cuda")
+    if a.one_frame:
+        for k in range(a.warmup):
+            ndt.submit(dscans[k % len(dscans)], len(dscans[k % len(dscans)]), T_init, integrate=True).result()
+        torch.cuda.synchronize()
+        s = dscans[a.warmup % len(dscans)]
+        r = ndt.submit(s, len(s), T_init, integrate=True).result()
+        print(json.dumps({"one_frame": True, "localiser": "ndt", "update_map": True, "status": r.status, "iterations": r.iterations,
+                          "n_points": r.n_points, "map_update": vars(r.map_update)}))
+        return
+    t_submit, t_update, t_both, t_rebuild, last = [], [], [], [], None
+    for k in range(a.warmup + a.frames):
+        s = dscans[k % len(dscans)]
+        e = [torch.cuda.Event(enable_timing=True) for _ in range(6)]
+        e[0].record(st)
+        pend = ndt.submit(s, len(s), T_init)
+        e[1].record(st)
+        r = pend.result()
+        n_pts.fill_(r.n_points)
+        e[2].record(st)
+        ndt._update(n_pts.data_ptr(), I4, None, None, 0, info.data_ptr(), st.cuda_stream)
+        e[3].record(st)
+        union = np.concatenate([map64, ndt._pts[:r.n_points].cpu().numpy()])   # the sensor sits at I: sensor frame = map frame
+        e[4].record(st)
+        pend = ndt.submit(s, len(s), T_init, integrate=True)
+        e[5].record(st)
+        last = pend.result()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        rebuilt = NDTLocaliser(union)
+        torch.cuda.synchronize()
+        t1 = time.perf_counter()
+        del rebuilt
+        if k >= a.warmup:
+            t_submit.append(e[0].elapsed_time(e[1]))
+            t_update.append(e[2].elapsed_time(e[3]))
+            t_both.append(e[4].elapsed_time(e[5]))
+            t_rebuild.append((t1 - t0) * 1e3)
+
+    def stats(v):
+        return {"median": round(float(np.median(v)), 4), "min": round(min(v), 4), "max": round(max(v), 4)}
+    out = {"frames": a.frames, "warmup": a.warmup, "n_map": len(mp), "cells_at_build": static.n_cells, "cell_capacity": cap_cells,
+           "dynamic_build_ms": round(build, 3), "n_points": last.n_points, "map_info": ndt.map_info(),
+           "last_update": vars(last.map_update), "submit_ms": stats(t_submit), "update_alone_ms": stats(t_update),
+           "submit_integrate_ms": stats(t_both), "rebuild_wall_ms": stats(t_rebuild)}
+    out["rebuild_over_update"] = round(out["rebuild_wall_ms"]["median"] / out["update_alone_ms"]["median"], 1)
+    for name in ("submit_ms", "update_alone_ms", "submit_integrate_ms", "rebuild_wall_ms"):
+        print(f"{name:22s} median {out[name]['median']:.4f} (min {out[name]['min']:.4f} max {out[name]['max']:.4f})", flush=True)
     print(json.dumps(out))
 
 
