@@ -378,7 +378,8 @@ __global__ __launch_bounds__(SCAN_BLOCK) void k_stable_write(const float *__rest
 // inside a cell); a query visits the 27 cells around the scan point and applies the exact float64 test
 // dx*dx + dy*dy + dz*dz <= r*r (no FMA contraction: same arithmetic as scipy's cKDTree leaf test).
 // The cell of a coordinate is floor(v / cell_size), a true division, as the caller's keys (radius_grid_cells:
-// torch.floor of xyz divided by a device tensor holding cell), loc_voxel_key and the NDT kernels compute it.  floor(v * (1 / cell_size)) differs from it by
+// torch.floor of xyz divided by a device tensor holding cell) and loc_voxel_key compute it; the NDT kernels call
+// radius_cell itself (ndt_cell_key, ndt_kernels.inc.h).  floor(v * (1 / cell_size)) differs from it by
 // one on values next to a face when cell_size is not a power of two; a map point at distance ~ r then lies two cells
 // from the cell the query believes it is in and the 27-cell lookup never visits it (tests/test_hip_boundaries.py).
 // ------------------------------------------------------------------------------------------
@@ -390,9 +391,11 @@ struct RadiusGrid {
   double cell_size, r2;
 };
 
+constexpr long long RADIUS_CELL_MAX = 1048575;   // |cell index| of an axis that radius_key can pack (21 bits each)
+
 __device__ inline bool radius_cell(double v, double cell_size, long long &c) {
   const double f = floor(__ddiv_rn(v, cell_size));
-  if (!(f >= -1048575.0 && f <= 1048575.0)) return false;
+  if (!(f >= -(double)RADIUS_CELL_MAX && f <= (double)RADIUS_CELL_MAX)) return false;   // NaN and infinities compare false
   c = (long long)f;
   return true;
 }

@@ -17,6 +17,14 @@
 __device__ inline double loc_mul(double a, double b) { return a * b; }
 __device__ inline double loc_add(double a, double b) { return a + b; }
 
+// q = R p + t of the pose T (row-major, its first 12 entries), per axis ((T0 px + T1 py) + T2 pz) + T3: the one definition
+// behind k_loc_assoc and every NDT kernel that moves a scan point into the map frame
+__device__ inline void loc_transform(const double *T, double px, double py, double pz, double q[3]) {
+#pragma unroll
+  for (int a = 0; a < 3; ++a)
+    q[a] = loc_add(loc_add(loc_add(loc_mul(T[4 * a], px), loc_mul(T[4 * a + 1], py)), loc_mul(T[4 * a + 2], pz)), T[4 * a + 3]);
+}
+
 // ---- voxel-grid thinning ---------------------------------------------------------------------------------------------
 // voxel of a row: floor(double(v) / leaf) per axis; a coordinate whose voxel index leaves the key range (NaN included)
 // skips the row.  There is no sticky error: a localiser must survive a bad point.
@@ -149,10 +157,7 @@ __global__ __launch_bounds__(256) void k_loc_assoc(const double *__restrict__ pt
     if (i < n) {
       const double px = pts[(size_t)i * 3], py = pts[(size_t)i * 3 + 1], pz = pts[(size_t)i * 3 + 2];
       double q[3];
-#pragma unroll
-      for (int a = 0; a < 3; ++a)
-        q[a] = loc_add(loc_add(loc_add(loc_mul(R[4 * a], px), loc_mul(R[4 * a + 1], py)), loc_mul(R[4 * a + 2], pz)),
-                         R[4 * a + 3]);
+      loc_transform(R, px, py, pz, q);
       long long cx, cy, cz;
       int c_lo = 0, c_hi = 0;
       if (lane < 27 && radius_cell(q[0], g.cell_size, cx) && radius_cell(q[1], g.cell_size, cy) && radius_cell(q[2], g.cell_size, cz)) {

@@ -20,12 +20,8 @@ int sps_ndt_align_batch(sps_ctx *c, const double *pts_dev, const int32_t *n_dev,
       cap < 0 || iters < 0 || (cap > 0 && !pts_dev) || (iters > 0 && !trace_dev))
     return fail(SPS_ERR_INVALID, "bad arguments");
   if (n_hyp < 1 || n_hyp > SPS_NDT_MAX_HYP) return fail(SPS_ERR_INVALID, "n_hyp must be in [1, %d]", SPS_NDT_MAX_HYP);
-  if (!c->ndt.h.keys) return fail(SPS_ERR_INVALID, "sps_ndt_map_build has not been called");
-  if (neighbours != 1 && neighbours != 7) return fail(SPS_ERR_INVALID, "neighbours must be 1 or 7");
-  if (cap > SPS_MAX_POINTS || iters > 10000) return fail(SPS_ERR_INVALID, "too many points or iterations");
-  if (std::isnan(tol_t) || std::isnan(tol_r)) return fail(SPS_ERR_INVALID, "tolerances must not be NaN");
   NdtGauss gs;
-  if (!ndt_gauss_fit(c->ndt.resolution, outlier_ratio, gs)) return SPS_ERR_INVALID;
+  if (int e = ndt_check_scan_args(c, neighbours, cap, outlier_ratio, gs, true, iters, tol_t, tol_r)) return e;
   HIP_TRY(hipSetDevice(c->device));
   hipStream_t st = (hipStream_t)stream;
   const int nb = (int)loc_align_blocks(cap);

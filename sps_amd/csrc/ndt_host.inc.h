@@ -1,6 +1,8 @@
 // ndt_host.inc.h -- part of sps_hip.hip (included inside its extern "C" block): the entry points of the NDT localiser
 // (ABI: the "NDT localiser" section of include/sps_hip.h; kernels: ndt_kernels.inc.h).  sps_ndt_map_build allocates and
-// synchronises, like sps_radius_grid_upload; sps_ndt_align does neither: its scratch is the caller's.
+// synchronises, like sps_radius_grid_upload; sps_ndt_align does neither: its scratch is the caller's.  Two helpers here
+// serve the later NDT files too: ndt_map_build_impl (the static and the dynamic build) and ndt_check_scan_args (the checks
+// that the alignment, the batch and the pose score share).
 
 namespace {
 // the Gaussian fit of the mixture (Magnusson 2009, eq. 6.8; PCL's gauss_d1_ / gauss_d2_), in float64 on the host; false
@@ -16,6 +18,95 @@ inline bool ndt_gauss_fit(double res, double outlier_ratio, NdtGauss &gs) {
   gs = NdtGauss{-d1, d2};
   return true;
 }
+// what sps_ndt_align, sps_ndt_align_batch and sps_ndt_score_poses ask alike of the context's map and of the scan, and the
+// Gaussian fit.  aligns: the call iterates, so it also has an iteration limit and tolerances (sps_ndt_score_poses has
+// neither, and its own text for the point limit); the checks stay in the order every entry point always made them
+inline int ndt_check_scan_args(const sps_ctx *c, int neighbours, int64_t cap, double outlier_ratio, NdtGauss &gs, bool aligns,
+                               int iters = 0, double tol_t = 0.0, double tol_r = 0.0) {
+  if (!c->ndt.h.keys) return fail(SPS_ERR_INVALID, "sps_ndt_map_build has not been called");
+  if (neighbours != 1 && neighbours != 7) return fail(SPS_ERR_INVALID, "neighbours must be 1 or 7");
+  if (cap > SPS_MAX_POINTS || (aligns && iters > 10000))
+    return aligns ? fail(SPS_ERR_INVALID, "too many points or iterations")
+                  : fail(SPS_ERR_INVALID, "too many points (limit %d)", SPS_MAX_POINTS);
+  if (aligns && (std::isnan(tol_t) || std::isnan(tol_r))) return fail(SPS_ERR_INVALID, "tolerances must not be NaN");
+  return ndt_gauss_fit(c->ndt.resolution, outlier_ratio, gs) ? SPS_OK : SPS_ERR_INVALID;
+}
+
+inline int64_t ndt_hash_slots(int64_t cells) { return next_pow2(2 * (cells < 512 ? 512 : cells)); }
+
+// The map of the context, static (room for the n_cells of the build; cell_capacity is not read) or dynamic (room for
+// cell_capacity cells, their moments S and the update's per-cell state beside the records).  Either replaces whatever map
+// the context had.  Allocates and synchronises.
+int ndt_map_build_impl(sps_ctx *c, const uint64_t *cell_keys_dev, const int32_t *cell_start_dev, const int32_t *cell_pts_dev,
+                       const double *map_xyz_dev, int64_t n_cells, int64_t n_map, double resolution, int min_points,
+                       double eig_ratio, bool dynamic, int64_t cell_capacity, void *stream) {
+  if (!c || n_cells < 0 || n_map < 0 || n_cells > n_map) return fail(SPS_ERR_INVALID, "bad arguments");
+  if (!(resolution > 0.0) || std::isinf(resolution)) return fail(SPS_ERR_INVALID, "resolution must be finite and > 0");
+  if (!(eig_ratio > 0.0) || !(eig_ratio <= 1.0)) return fail(SPS_ERR_INVALID, "eig_ratio must be in (0, 1]");
+  if (min_points < 0) return fail(SPS_ERR_INVALID, "min_points must be >= 0");
+  if (n_map > 0 && (!cell_keys_dev || !cell_start_dev || !cell_pts_dev || !map_xyz_dev)) return fail(SPS_ERR_INVALID, "null argument");
+  if (n_map >= (1ll << 31) || n_cells >= (1ll << 30)) return fail(SPS_ERR_INVALID, "map too large");
+  if (dynamic && (cell_capacity < 1 || cell_capacity < n_cells)) return fail(SPS_ERR_INVALID, "cell_capacity must be >= max(n_cells, 1)");
+  if (dynamic && cell_capacity >= (1ll << 30)) return fail(SPS_ERR_INVALID, "cell_capacity too large");
+  HIP_TRY(hipSetDevice(c->device));
+  hipStream_t st = (hipStream_t)stream;
+  HIP_TRY(hipDeviceSynchronize());
+  for (void *p : c->ndt_allocs) (void)hipFree(p);
+  c->ndt_allocs.clear();
+  c->ndt = NdtMap{};
+  c->ndt_dyn = NdtDyn{};
+  bool nomem = false;
+  auto alloc = [&](size_t bytes) -> void * {
+    void *p = nullptr;
+    if (nomem || hipMalloc(&p, bytes ? bytes : 16) != hipSuccess) return nomem = true, nullptr;
+    c->ndt_allocs.push_back(p);
+    return p;
+  };
+  const size_t C = (size_t)(dynamic ? cell_capacity : n_cells);
+  const int64_t hcap = ndt_hash_slots((int64_t)C);
+  NdtMap m{};
+  NdtDyn d{};
+  m.h.keys = (uint64_t *)alloc((size_t)hcap * 8);
+  m.h.first = nullptr;
+  m.h.rank = (int *)alloc((size_t)hcap * 4);
+  m.h.mask = (uint32_t)(hcap - 1);
+  m.rec = d.rec = (double *)alloc(C * NDT_REC * 8);
+  m.count = d.count = (int *)alloc(C * 4);
+  m.keys = d.keys = (uint64_t *)alloc(C * 8);
+  m.n_cells = (int)C;
+  m.resolution = resolution;
+  if (dynamic) {
+    d.capacity = (int)cell_capacity, d.min_points = min_points, d.eig_ratio = eig_ratio;
+    d.S = (double *)alloc(C * 6 * 8), d.bcnt = (int *)alloc(C * 4), d.lead = (int *)alloc(C * 4);
+    d.cstart = (int *)alloc(C * 4), d.state = (int *)alloc(16);
+  }
+  if (nomem) return fail(SPS_ERR_NOMEM, "hipMalloc for the NDT map failed");
+  HIP_TRY(hipMemsetAsync(m.h.keys, 0xFF, (size_t)hcap * 8, st));
+  HIP_TRY(hipMemsetAsync(m.h.rank, 0xFF, (size_t)hcap * 4, st));
+  const int32_t state0[4] = {(int32_t)n_cells, 0, 0, 0};
+  if (dynamic) {   // the rest values of the cells that the updates will found
+    HIP_TRY(hipMemsetAsync(d.rec, 0, C * NDT_REC * 8, st));
+    HIP_TRY(hipMemsetAsync(d.count, 0, C * 4, st));
+    HIP_TRY(hipMemsetAsync(d.keys, 0xFF, C * 8, st));
+    HIP_TRY(hipMemsetAsync(d.S, 0, C * 6 * 8, st));
+    HIP_TRY(hipMemsetAsync(d.bcnt, 0, C * 4, st));
+    HIP_TRY(hipMemsetAsync(d.lead, 0x7F, C * 4, st));
+    HIP_TRY(hipMemsetAsync(d.cstart, 0, C * 4, st));
+    HIP_TRY(hipMemcpyAsync(d.state, state0, sizeof(state0), hipMemcpyHostToDevice, st));
+  }
+  if (n_cells > 0) {
+    const unsigned nb = (unsigned)((n_cells + 255) / 256);
+    HIP_TRY(hipMemcpyAsync(d.keys, cell_keys_dev, (size_t)n_cells * 8, hipMemcpyDeviceToDevice, st));
+    hipLaunchKernelGGL(k_radius_cells_insert, dim3(nb), dim3(256), 0, st, (const unsigned long long *)cell_keys_dev, (int)n_cells, m.h);
+    hipLaunchKernelGGL(k_ndt_cells, dim3(nb), dim3(256), 0, st, (const int *)cell_start_dev, (const int *)cell_pts_dev, map_xyz_dev,
+                       (int)n_cells, (int)n_map, min_points, eig_ratio, d.rec, d.count, d.S);
+  }
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipStreamSynchronize(st));   // state0 is on this frame
+  c->ndt = m;
+  if (dynamic) c->ndt_dyn = d;
+  return SPS_OK;
+}
 }  // namespace
 
 int64_t sps_ndt_align_scratch(int64_t cap) { return sps_loc_align_scratch(cap); }   // the partial rows of k_loc_solve
@@ -23,52 +114,8 @@ int64_t sps_ndt_align_scratch(int64_t cap) { return sps_loc_align_scratch(cap); 
 int sps_ndt_map_build(sps_ctx *c, const uint64_t *cell_keys_dev, const int32_t *cell_start_dev, const int32_t *cell_pts_dev,
                       const double *map_xyz_dev, int64_t n_cells, int64_t n_map, double resolution, int min_points,
                       double eig_ratio, void *stream) {
-  if (!c || n_cells < 0 || n_map < 0 || n_cells > n_map) return fail(SPS_ERR_INVALID, "bad arguments");
-  if (!(resolution > 0.0) || std::isinf(resolution)) return fail(SPS_ERR_INVALID, "resolution must be finite and > 0");
-  if (!(eig_ratio > 0.0) || !(eig_ratio <= 1.0)) return fail(SPS_ERR_INVALID, "eig_ratio must be in (0, 1]");
-  if (min_points < 0) return fail(SPS_ERR_INVALID, "min_points must be >= 0");
-  if (n_map > 0 && (!cell_keys_dev || !cell_start_dev || !cell_pts_dev || !map_xyz_dev)) return fail(SPS_ERR_INVALID, "null argument");
-  if (n_map >= (1ll << 31) || n_cells >= (1ll << 30)) return fail(SPS_ERR_INVALID, "map too large");
-  HIP_TRY(hipSetDevice(c->device));
-  hipStream_t st = (hipStream_t)stream;
-  HIP_TRY(hipDeviceSynchronize());
-  for (void *p : c->ndt_allocs) (void)hipFree(p);
-  c->ndt_allocs.clear();
-  c->ndt = NdtMap{};
-  c->ndt_dyn = NdtDyn{};   // a static map replaces a dynamic one
-  auto alloc = [&](void **p, size_t bytes) -> hipError_t {
-    hipError_t e = hipMalloc(p, bytes ? bytes : 16);
-    if (e == hipSuccess) c->ndt_allocs.push_back(*p);
-    return e;
-  };
-  const int64_t hcap = next_pow2(2 * (n_cells < 512 ? 512 : n_cells));
-  void *keys = nullptr, *rank = nullptr, *rec = nullptr, *count = nullptr, *ckeys = nullptr;
-  if (alloc(&keys, (size_t)hcap * 8) != hipSuccess || alloc(&rank, (size_t)hcap * 4) != hipSuccess ||
-      alloc(&rec, (size_t)n_cells * NDT_REC * 8) != hipSuccess || alloc(&count, (size_t)n_cells * 4) != hipSuccess ||
-      alloc(&ckeys, (size_t)n_cells * 8) != hipSuccess)
-    return fail(SPS_ERR_NOMEM, "hipMalloc for the NDT map failed");
-  HIP_TRY(hipMemsetAsync(keys, 0xFF, (size_t)hcap * 8, st));
-  NdtMap m{};
-  m.h.keys = (uint64_t *)keys;
-  m.h.first = nullptr;
-  m.h.rank = (int *)rank;
-  m.h.mask = (uint32_t)(hcap - 1);
-  m.rec = (const double *)rec;
-  m.count = (const int *)count;
-  m.keys = (const uint64_t *)ckeys;
-  m.n_cells = (int)n_cells;
-  m.resolution = resolution;
-  if (n_cells > 0) {
-    const unsigned nb = (unsigned)((n_cells + 255) / 256);
-    HIP_TRY(hipMemcpyAsync(ckeys, cell_keys_dev, (size_t)n_cells * 8, hipMemcpyDeviceToDevice, st));
-    hipLaunchKernelGGL(k_radius_cells_insert, dim3(nb), dim3(256), 0, st, (const unsigned long long *)cell_keys_dev, (int)n_cells, m.h);
-    hipLaunchKernelGGL(k_ndt_cells, dim3(nb), dim3(256), 0, st, (const int *)cell_start_dev, (const int *)cell_pts_dev, map_xyz_dev,
-                       (int)n_cells, (int)n_map, min_points, eig_ratio, (double *)rec, (int *)count);
-  }
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipStreamSynchronize(st));
-  c->ndt = m;
-  return SPS_OK;
+  return ndt_map_build_impl(c, cell_keys_dev, cell_start_dev, cell_pts_dev, map_xyz_dev, n_cells, n_map, resolution, min_points,
+                            eig_ratio, false, 0, stream);
 }
 
 int sps_ndt_map_cells(sps_ctx *c, uint64_t *key_out_dev, int32_t *count_out_dev, double *mean_out_dev, double *icov_out_dev,
@@ -91,12 +138,8 @@ int sps_ndt_align(sps_ctx *c, const double *pts_dev, const int32_t *n_dev, int64
   if (!c || !n_dev || !T_init_host || !T_out_dev || !status_dev || !scratch_dev || cap < 0 || iters < 0 ||
       (cap > 0 && !pts_dev) || (iters > 0 && !trace_dev))
     return fail(SPS_ERR_INVALID, "bad arguments");
-  if (!c->ndt.h.keys) return fail(SPS_ERR_INVALID, "sps_ndt_map_build has not been called");
-  if (neighbours != 1 && neighbours != 7) return fail(SPS_ERR_INVALID, "neighbours must be 1 or 7");
-  if (cap > SPS_MAX_POINTS || iters > 10000) return fail(SPS_ERR_INVALID, "too many points or iterations");
-  if (std::isnan(tol_t) || std::isnan(tol_r)) return fail(SPS_ERR_INVALID, "tolerances must not be NaN");
   NdtGauss gs;
-  if (!ndt_gauss_fit(c->ndt.resolution, outlier_ratio, gs)) return SPS_ERR_INVALID;
+  if (int e = ndt_check_scan_args(c, neighbours, cap, outlier_ratio, gs, true, iters, tol_t, tol_r)) return e;
   HIP_TRY(hipSetDevice(c->device));
   hipStream_t st = (hipStream_t)stream;
   LocPose T0;

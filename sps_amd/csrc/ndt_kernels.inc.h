@@ -3,9 +3,15 @@
 // include/sps_hip.h).
 //
 //   k_ndt_cells   (map build)                 per map cell: n, mean, sample covariance, Jacobi eigen-decomposition, floored
-//                                             eigenvalues, inverse covariance -> one 80-byte record
+//                                             eigenvalues, inverse covariance -> one 80-byte record (and S for an online map)
 //   k_ndt_assoc   (launch A of an iteration)  q = R p + t, the records of q's cell and its face neighbours, the
 //                                             normal-equation terms of every contributing cell
+//
+// This file also holds the one definition of what the batch, search and update kernels share with these two:
+//   ndt_list_moments, ndt_record_from_moments   a cell's moments from its point list; its record from (n, mean, S)
+//   ndt_cell_key, ndt_cell_of                   the cell of a point (radius_cell of aux_kernels.inc.h) and its id in the map
+//   ndt_cell_hit                                one cell's contribution to one point
+// with loc_transform of loc_kernels.inc.h in front.  That the entry points agree bit for bit follows from that.
 //
 // Launch B is k_loc_solve unchanged: the partial rows have its layout (21 of H, 6 of g, the score, the count; one row per
 // LOC_PTS points).  As in loc_kernels.inc.h everything is float64, every operation is rounded on its own (contraction is
@@ -58,14 +64,10 @@ __device__ inline void ndt_rotate(double a[3][3], double v[3][3], int p, int q) 
   }
 }
 
-// One thread per cell; the cell's points are read in the order of its list (ascending map index).
-__global__ __launch_bounds__(256) void k_ndt_cells(const int *__restrict__ cell_start, const int *__restrict__ cell_pts,
-                                                    const double *__restrict__ xyz, int n_cells, int n_map, int min_points,
-                                                    double eig_ratio, double *__restrict__ rec, int *__restrict__ count) {
-  const int c = blockIdx.x * 256 + threadIdx.x;
-  if (c >= n_cells) return;
-  const int lo = max(cell_start[c], 0), hi = min(cell_start[c + 1], n_map);
-  const int n = max(hi - lo, 0);
+// n points (list entries [lo, hi) of cell_pts, read in list order: ascending map index) -> their mean and
+// S = sum (p - mean)(p - mean)^T as (xx, xy, xz, yy, yz, zz): one pass for the mean, one for the six sums
+__device__ inline void ndt_list_moments(const int *__restrict__ cell_pts, const double *__restrict__ xyz, int lo, int hi,
+                                        int n_map, int n, double mu[3], double S[6]) {
   double sum[3] = {0.0, 0.0, 0.0};
   for (int t = lo; t < hi; ++t) {
     const int j = cell_pts[t];
@@ -73,24 +75,30 @@ __global__ __launch_bounds__(256) void k_ndt_cells(const int *__restrict__ cell_
 #pragma unroll
     for (int a = 0; a < 3; ++a) sum[a] = loc_add(sum[a], xyz[(size_t)j * 3 + a]);
   }
-  double mu[3] = {0.0, 0.0, 0.0};
-  if (n > 0)
-    for (int a = 0; a < 3; ++a) mu[a] = __ddiv_rn(sum[a], (double)n);
-  double cv[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};   // xx, xy, xz, yy, yz, zz
+  for (int a = 0; a < 3; ++a) mu[a] = n > 0 ? __ddiv_rn(sum[a], (double)n) : 0.0;
+  for (int i = 0; i < 6; ++i) S[i] = 0.0;
   for (int t = lo; t < hi; ++t) {
     const int j = cell_pts[t];
     if (j < 0 || j >= n_map) continue;
     const double dx = loc_add(xyz[(size_t)j * 3], -mu[0]), dy = loc_add(xyz[(size_t)j * 3 + 1], -mu[1]),
                  dz = loc_add(xyz[(size_t)j * 3 + 2], -mu[2]);
-    cv[0] = loc_add(cv[0], loc_mul(dx, dx)), cv[1] = loc_add(cv[1], loc_mul(dx, dy)), cv[2] = loc_add(cv[2], loc_mul(dx, dz));
-    cv[3] = loc_add(cv[3], loc_mul(dy, dy)), cv[4] = loc_add(cv[4], loc_mul(dy, dz)), cv[5] = loc_add(cv[5], loc_mul(dz, dz));
+    S[0] = loc_add(S[0], loc_mul(dx, dx)), S[1] = loc_add(S[1], loc_mul(dx, dy)), S[2] = loc_add(S[2], loc_mul(dx, dz));
+    S[3] = loc_add(S[3], loc_mul(dy, dy)), S[4] = loc_add(S[4], loc_mul(dy, dz)), S[5] = loc_add(S[5], loc_mul(dz, dz));
   }
+}
+
+// The record of a cell from (n, mean, S): sample covariance S / (n - 1), NDT_SWEEPS Jacobi sweeps, eigenvalues floored at
+// eig_ratio times the largest, inverse covariance, the validity flag.  The map build (k_ndt_cells) and the online update
+// (k_ndt_upd_merge, ndt_update_kernels.inc.h) both end here.
+__device__ inline void ndt_record_from_moments(int n, const double mu[3], const double S[6], int min_points, double eig_ratio,
+                                               double *__restrict__ o) {
   double icov[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
   bool valid = n >= min_points && n >= 2;
   if (n >= 2) {
     const double nm1 = (double)(n - 1);
+    double cv[6];
 #pragma unroll
-    for (int i = 0; i < 6; ++i) cv[i] = __ddiv_rn(cv[i], nm1);
+    for (int i = 0; i < 6; ++i) cv[i] = __ddiv_rn(S[i], nm1);
     double a[3][3] = {{cv[0], cv[1], cv[2]}, {cv[1], cv[3], cv[4]}, {cv[2], cv[4], cv[5]}};
     double v[3][3] = {{1.0, 0.0, 0.0}, {0.0, 1.0, 0.0}, {0.0, 0.0, 1.0}};
     for (int sweep = 0; sweep < NDT_SWEEPS; ++sweep) {
@@ -115,11 +123,26 @@ __global__ __launch_bounds__(256) void k_ndt_cells(const int *__restrict__ cell_
   }
   for (int a = 0; a < 3; ++a) valid = valid && isfinite(mu[a]);
   for (int i = 0; i < 6; ++i) valid = valid && isfinite(icov[i]);
-  double *o = rec + (size_t)c * NDT_REC;
   o[0] = mu[0], o[1] = mu[1], o[2] = mu[2];
 #pragma unroll
   for (int i = 0; i < 6; ++i) o[3 + i] = icov[i];
   o[9] = valid ? 1.0 : 0.0;
+}
+
+// One thread per cell.  S_out (null: a static map) keeps the cell's S beside the record, for the online update to merge into.
+__global__ __launch_bounds__(256) void k_ndt_cells(const int *__restrict__ cell_start, const int *__restrict__ cell_pts,
+                                                    const double *__restrict__ xyz, int n_cells, int n_map, int min_points,
+                                                    double eig_ratio, double *__restrict__ rec, int *__restrict__ count,
+                                                    double *__restrict__ S_out) {
+  const int c = blockIdx.x * 256 + threadIdx.x;
+  if (c >= n_cells) return;
+  const int lo = max(cell_start[c], 0), hi = min(cell_start[c + 1], n_map);
+  const int n = max(hi - lo, 0);
+  double mu[3], S[6];
+  ndt_list_moments(cell_pts, xyz, lo, hi, n_map, n, mu, S);
+  if (S_out)
+    for (int i = 0; i < 6; ++i) S_out[(size_t)c * 6 + i] = S[i];
+  ndt_record_from_moments(n, mu, S, min_points, eig_ratio, rec + (size_t)c * NDT_REC);
   count[c] = n;
 }
 
@@ -146,10 +169,51 @@ __device__ inline double ndt_symrow(const double *m, int i, const double b[3]) {
   return loc_dot3(r, b);
 }
 
+// The key of the cell of q (radius_cell per axis: floor of a true division, the key range) moved to face neighbour `sub`
+// (0: q's own cell, then +x, -x, +y, -y, +z, -z); false where q or the neighbour leaves the key range.
+__device__ inline bool ndt_cell_key(const double q[3], double res, int sub, uint64_t &key) {
+  long long c[3] = {0, 0, 0};
+  // all three axes are evaluated (& and not &&), as in the code of the kernels that this one definition replaced
+  if (!(radius_cell(q[0], res, c[0]) & radius_cell(q[1], res, c[1]) & radius_cell(q[2], res, c[2]))) return false;
+  if (sub > 0) {
+    long long &s = c[(sub - 1) >> 1];
+    s += (sub & 1) ? 1 : -1;
+    if (s < -RADIUS_CELL_MAX || s > RADIUS_CELL_MAX) return false;
+  }
+  key = radius_key(c[0], c[1], c[2]);
+  return true;
+}
+
+// the id of that cell in the map, -1 where the map has none
+__device__ inline int ndt_cell_of(const NdtMap &m, const double q[3], int sub) {
+  uint64_t key;
+  if (!ndt_cell_key(q, m.resolution, sub, key)) return -1;
+  const int s = hash_find_slot(m.h, key);
+  const int cell = s >= 0 ? m.h.rank[s] : -1;
+  return cell >= 0 && cell < m.n_cells ? cell : -1;
+}
+
+// One cell's contribution to the point q, from the cell's record: x = q - mean, y = icov x, e = exp(-d2 x.y / 2), w = d2 e.
+// False where the cell is not valid or w fails the guard; true hands back e, w, y and the record's icov.
+__device__ inline bool ndt_cell_hit(const double q[3], const double *__restrict__ rec, const NdtGauss &gs, double &e, double &w,
+                                    double y[3], double icov[6]) {
+  double r[NDT_REC];   // one contiguous 80-byte record
+#pragma unroll
+  for (int j = 0; j < NDT_REC; ++j) r[j] = rec[j];
+  if (r[9] == 0.0) return false;
+  const double x[3] = {loc_add(q[0], -r[0]), loc_add(q[1], -r[1]), loc_add(q[2], -r[2])};
+#pragma unroll
+  for (int a = 0; a < 3; ++a) y[a] = ndt_symrow(r + 3, a, x);
+  e = exp(loc_mul(-0.5, loc_mul(gs.d2, loc_dot3(x, y))));
+  w = loc_mul(gs.d2, e);
+#pragma unroll
+  for (int j = 0; j < 6; ++j) icov[j] = r[3 + j];
+  return w >= 0.0 && w <= 1.0;   // NaN fails both: the guard of ndt_omp
+}
+
 // Launch A.  NDT_LANES lanes per scan point, LOC_PTS points per workgroup.
-//   phase 1: lane c < neighbours looks up cell c of the point (0: q's own cell, then +x, -x, +y, -y, +z, -z), reads its
-//            record and, where the cell is valid and the weight passes the guard, leaves a, icov, y = icov x and the score
-//            in LDS;
+//   phase 1: lane c < neighbours looks up cell c of the point (ndt_cell_of) and, where the cell contributes
+//            (ndt_cell_hit), leaves a, icov, y = icov x and the score in LDS;
 //   phase 2: lane l forms terms l, l + 8, l + 16, l + 24 of the point, adding the contributing cells in lookup order;
 //   phase 3: thread l < LOC_TERMS adds the workgroup's points in point order and writes entry l of the partial row.
 // The body is shared with k_ndt_assoc_batch (ndt_batch_kernels.inc.h), which runs it once per hypothesis: T is the pose,
@@ -174,46 +238,17 @@ __device__ inline void ndt_assoc_body(const double *__restrict__ pts, const int 
   double q[3] = {0.0, 0.0, 0.0};
   int ok = 0;
   if (i < n) {
-    const double px = pts[(size_t)i * 3], py = pts[(size_t)i * 3 + 1], pz = pts[(size_t)i * 3 + 2];
+    loc_transform(T, pts[(size_t)i * 3], pts[(size_t)i * 3 + 1], pts[(size_t)i * 3 + 2], q);
+    const int cell = sub < neighbours ? ndt_cell_of(m, q, sub) : -1;
+    double e, w, y[3], icov[6];
+    if (cell >= 0 && ndt_cell_hit(q, m.rec + (size_t)cell * NDT_REC, gs, e, w, y, icov)) {
+      double *o = hit[k][sub];
+      o[0] = loc_mul(gs.nd1, w);
 #pragma unroll
-    for (int a = 0; a < 3; ++a)
-      q[a] = loc_add(loc_add(loc_add(loc_mul(T[4 * a], px), loc_mul(T[4 * a + 1], py)), loc_mul(T[4 * a + 2], pz)), T[4 * a + 3]);
-    if (sub < neighbours) {
-      long long cc[3];
-      bool in = true;
-#pragma unroll
-      for (int a = 0; a < 3; ++a) {
-        const double f = floor(__ddiv_rn(q[a], m.resolution));
-        in = in && f >= -1048575.0 && f <= 1048575.0;   // NaN compares false
-        cc[a] = in ? (long long)f : 0;
-      }
-      if (sub > 0) cc[(sub - 1) >> 1] += (sub & 1) ? 1 : -1;
-      in = in && cc[0] >= -1048575 && cc[0] <= 1048575 && cc[1] >= -1048575 && cc[1] <= 1048575 && cc[2] >= -1048575 &&
-           cc[2] <= 1048575;
-      const int s = in ? hash_find_slot(m.h, radius_key(cc[0], cc[1], cc[2])) : -1;
-      const int cell = s >= 0 ? m.h.rank[s] : -1;
-      if (cell >= 0 && cell < m.n_cells) {
-        double r[NDT_REC];
-        const double *src = m.rec + (size_t)cell * NDT_REC;   // one contiguous 80-byte record
-#pragma unroll
-        for (int j = 0; j < NDT_REC; ++j) r[j] = src[j];
-        if (r[9] != 0.0) {
-          const double x[3] = {loc_add(q[0], -r[0]), loc_add(q[1], -r[1]), loc_add(q[2], -r[2])};
-          const double y[3] = {ndt_symrow(r + 3, 0, x), ndt_symrow(r + 3, 1, x), ndt_symrow(r + 3, 2, x)};
-          const double sq = loc_dot3(x, y);
-          const double e = exp(loc_mul(-0.5, loc_mul(gs.d2, sq)));
-          const double w = loc_mul(gs.d2, e);
-          if (w >= 0.0 && w <= 1.0) {                       // NaN fails both: the guard of ndt_omp
-            double *o = hit[k][sub];
-            o[0] = loc_mul(gs.nd1, w);
-#pragma unroll
-            for (int j = 0; j < 6; ++j) o[1 + j] = r[3 + j];
-            o[7] = y[0], o[8] = y[1], o[9] = y[2];
-            o[10] = loc_mul(gs.nd1, e);
-            ok = 1;
-          }
-        }
-      }
+      for (int j = 0; j < 6; ++j) o[1 + j] = icov[j];
+      o[7] = y[0], o[8] = y[1], o[9] = y[2];
+      o[10] = loc_mul(gs.nd1, e);
+      ok = 1;
     }
   }
   hit_ok[k][sub] = ok;

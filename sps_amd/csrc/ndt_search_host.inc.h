@@ -24,11 +24,8 @@ int sps_ndt_score_poses(sps_ctx *c, const double *pts_dev, const int32_t *n_dev,
   if (!c || !n_dev || !T_dev || !score_dev || !scratch_dev || cap < 0 || (cap > 0 && !pts_dev))
     return fail(SPS_ERR_INVALID, "bad arguments");
   if (n_pose < 1 || n_pose > SPS_NDT_MAX_POSES) return fail(SPS_ERR_INVALID, "n_pose must be in [1, %d]", SPS_NDT_MAX_POSES);
-  if (!c->ndt.h.keys) return fail(SPS_ERR_INVALID, "sps_ndt_map_build has not been called");
-  if (neighbours != 1 && neighbours != 7) return fail(SPS_ERR_INVALID, "neighbours must be 1 or 7");
-  if (cap > SPS_MAX_POINTS) return fail(SPS_ERR_INVALID, "too many points (limit %d)", SPS_MAX_POINTS);
   NdtGauss gs;
-  if (!ndt_gauss_fit(c->ndt.resolution, outlier_ratio, gs)) return SPS_ERR_INVALID;
+  if (int e = ndt_check_scan_args(c, neighbours, cap, outlier_ratio, gs, false)) return e;
   HIP_TRY(hipSetDevice(c->device));
   hipStream_t st = (hipStream_t)stream;
   const int nb = (int)loc_align_blocks(cap);

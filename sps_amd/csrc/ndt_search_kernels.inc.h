@@ -7,9 +7,10 @@
 //   k_ndt_score_reduce   score[pose] = the blocks of the pose added in loc_sum_rows' order
 //   k_ndt_top            one workgroup: the K best poses by (score descending, index ascending)
 //
-// Per point and pose the arithmetic is phase 1 of ndt_assoc_body (ndt_kernels.inc.h), operation for operation, and of
-// its 29 terms only the score (27) and the count (28) are formed; the sums run in the orders of k_ndt_assoc and
-// loc_sum_rows, so score[pose] has the bits of final_dev[k] of sps_ndt_align_batch(iters = 0) started at that pose.
+// Per point and pose k_ndt_score calls what phase 1 of ndt_assoc_body calls (loc_transform, ndt_cell_of, ndt_cell_hit:
+// ndt_kernels.inc.h), and of the 29 terms only the score (27) and the count (28) are formed; the sums run in the orders of
+// k_ndt_assoc and loc_sum_rows, so score[pose] has the bits of final_dev[k] of sps_ndt_align_batch(iters = 0) started at
+// that pose.
 // Everything is float64, every operation is rounded on its own, stores are plain vector stores, nothing is atomic.
 
 #pragma clang fp contract(off)
@@ -43,43 +44,15 @@ __global__ __launch_bounds__(256) void k_ndt_score(const double *__restrict__ pt
   if (i < n) px = pts[(size_t)i * 3], py = pts[(size_t)i * 3 + 1], pz = pts[(size_t)i * 3 + 2];
   __syncthreads();
   for (int j = 0; j < tile; ++j) {
-    const double *Tj = pose[j];
     double v = 0.0;
     int ok = 0;
     if (live) {
-      double q[3];
-#pragma unroll
-      for (int a = 0; a < 3; ++a)
-        q[a] = loc_add(loc_add(loc_add(loc_mul(Tj[4 * a], px), loc_mul(Tj[4 * a + 1], py)), loc_mul(Tj[4 * a + 2], pz)), Tj[4 * a + 3]);
-      long long cc[3];
-      bool in = true;
-#pragma unroll
-      for (int a = 0; a < 3; ++a) {
-        const double f = floor(__ddiv_rn(q[a], m.resolution));
-        in = in && f >= -1048575.0 && f <= 1048575.0;   // NaN compares false
-        cc[a] = in ? (long long)f : 0;
-      }
-      if (sub > 0) cc[(sub - 1) >> 1] += (sub & 1) ? 1 : -1;
-      in = in && cc[0] >= -1048575 && cc[0] <= 1048575 && cc[1] >= -1048575 && cc[1] <= 1048575 && cc[2] >= -1048575 &&
-           cc[2] <= 1048575;
-      const int s = in ? hash_find_slot(m.h, radius_key(cc[0], cc[1], cc[2])) : -1;
-      const int cell = s >= 0 ? m.h.rank[s] : -1;
-      if (cell >= 0 && cell < m.n_cells) {
-        double r[NDT_REC];
-        const double *src = m.rec + (size_t)cell * NDT_REC;   // one contiguous 80-byte record
-#pragma unroll
-        for (int c = 0; c < NDT_REC; ++c) r[c] = src[c];
-        if (r[9] != 0.0) {
-          const double x[3] = {loc_add(q[0], -r[0]), loc_add(q[1], -r[1]), loc_add(q[2], -r[2])};
-          const double y[3] = {ndt_symrow(r + 3, 0, x), ndt_symrow(r + 3, 1, x), ndt_symrow(r + 3, 2, x)};
-          const double sq = loc_dot3(x, y);
-          const double e = exp(loc_mul(-0.5, loc_mul(gs.d2, sq)));
-          const double w = loc_mul(gs.d2, e);
-          if (w >= 0.0 && w <= 1.0) {                         // NaN fails both: the guard of ndt_omp
-            v = loc_mul(gs.nd1, e);
-            ok = 1;
-          }
-        }
+      double q[3], e, w, y[3], icov[6];
+      loc_transform(pose[j], px, py, pz, q);
+      const int cell = ndt_cell_of(m, q, sub);
+      if (cell >= 0 && ndt_cell_hit(q, m.rec + (size_t)cell * NDT_REC, gs, e, w, y, icov)) {
+        v = loc_mul(gs.nd1, e);
+        ok = 1;
       }
     }
     // the point's cells in lookup order (every lane of the wave takes part in the shuffles)

@@ -1,14 +1,14 @@
 // ndt_update_host.inc.h -- part of sps_hip.hip (included inside its extern "C" block, after ndt_search_host.inc.h): the
 // online NDT map (ABI: the "NDT localiser, online map" section of include/sps_hip.h; kernels: ndt_update_kernels.inc.h).
-// sps_ndt_map_build_dynamic allocates and synchronises, like sps_ndt_map_build; sps_ndt_map_update does neither.
+// sps_ndt_map_build_dynamic is sps_ndt_map_build with a cell capacity (ndt_map_build_impl, ndt_host.inc.h): it allocates and
+// synchronises; sps_ndt_map_update does neither.
 
 namespace {
-inline int64_t ndt_upd_hash_slots(int64_t cap) { return next_pow2(2 * (cap < 512 ? 512 : cap)); }
 inline size_t ndt_upd_align(size_t v) { return (v + 255) & ~(size_t)255; }
 
 // the caller's scratch cut into its arrays (base == nullptr: only the size is wanted)
 inline size_t ndt_upd_layout(int64_t cap, char *base, NdtUpdScratch *s) {
-  const size_t n = (size_t)(cap < 1 ? 1 : cap), hs = (size_t)ndt_upd_hash_slots(cap);
+  const size_t n = (size_t)(cap < 1 ? 1 : cap), hs = (size_t)ndt_hash_slots(cap);
   size_t at = 0;
   auto take = [&](size_t bytes) {
     char *p = base ? base + at : nullptr;
@@ -29,72 +29,8 @@ inline size_t ndt_upd_layout(int64_t cap, char *base, NdtUpdScratch *s) {
 int sps_ndt_map_build_dynamic(sps_ctx *c, const uint64_t *cell_keys_dev, const int32_t *cell_start_dev,
                               const int32_t *cell_pts_dev, const double *map_xyz_dev, int64_t n_cells, int64_t n_map,
                               double resolution, int min_points, double eig_ratio, int64_t cell_capacity, void *stream) {
-  if (!c || n_cells < 0 || n_map < 0 || n_cells > n_map) return fail(SPS_ERR_INVALID, "bad arguments");
-  if (!(resolution > 0.0) || std::isinf(resolution)) return fail(SPS_ERR_INVALID, "resolution must be finite and > 0");
-  if (!(eig_ratio > 0.0) || !(eig_ratio <= 1.0)) return fail(SPS_ERR_INVALID, "eig_ratio must be in (0, 1]");
-  if (min_points < 0) return fail(SPS_ERR_INVALID, "min_points must be >= 0");
-  if (n_map > 0 && (!cell_keys_dev || !cell_start_dev || !cell_pts_dev || !map_xyz_dev)) return fail(SPS_ERR_INVALID, "null argument");
-  if (n_map >= (1ll << 31) || n_cells >= (1ll << 30)) return fail(SPS_ERR_INVALID, "map too large");
-  if (cell_capacity < 1 || cell_capacity < n_cells) return fail(SPS_ERR_INVALID, "cell_capacity must be >= max(n_cells, 1)");
-  if (cell_capacity >= (1ll << 30)) return fail(SPS_ERR_INVALID, "cell_capacity too large");
-  HIP_TRY(hipSetDevice(c->device));
-  hipStream_t st = (hipStream_t)stream;
-  HIP_TRY(hipDeviceSynchronize());
-  for (void *p : c->ndt_allocs) (void)hipFree(p);
-  c->ndt_allocs.clear();
-  c->ndt = NdtMap{};
-  c->ndt_dyn = NdtDyn{};
-  auto alloc = [&](void **p, size_t bytes) -> hipError_t {
-    hipError_t e = hipMalloc(p, bytes ? bytes : 16);
-    if (e == hipSuccess) c->ndt_allocs.push_back(*p);
-    return e;
-  };
-  const size_t C = (size_t)cell_capacity;
-  const int64_t hcap = ndt_upd_hash_slots(cell_capacity);
-  void *keys = nullptr, *rank = nullptr, *rec = nullptr, *count = nullptr, *ckeys = nullptr, *S = nullptr, *bcnt = nullptr,
-       *lead = nullptr, *cstart = nullptr, *state = nullptr;
-  if (alloc(&keys, (size_t)hcap * 8) != hipSuccess || alloc(&rank, (size_t)hcap * 4) != hipSuccess ||
-      alloc(&rec, C * NDT_REC * 8) != hipSuccess || alloc(&count, C * 4) != hipSuccess || alloc(&ckeys, C * 8) != hipSuccess ||
-      alloc(&S, C * 6 * 8) != hipSuccess || alloc(&bcnt, C * 4) != hipSuccess || alloc(&lead, C * 4) != hipSuccess ||
-      alloc(&cstart, C * 4) != hipSuccess || alloc(&state, 16) != hipSuccess)
-    return fail(SPS_ERR_NOMEM, "hipMalloc for the NDT map failed");
-  HIP_TRY(hipMemsetAsync(keys, 0xFF, (size_t)hcap * 8, st));
-  HIP_TRY(hipMemsetAsync(rank, 0xFF, (size_t)hcap * 4, st));
-  HIP_TRY(hipMemsetAsync(rec, 0, C * NDT_REC * 8, st));
-  HIP_TRY(hipMemsetAsync(count, 0, C * 4, st));
-  HIP_TRY(hipMemsetAsync(ckeys, 0xFF, C * 8, st));
-  HIP_TRY(hipMemsetAsync(S, 0, C * 6 * 8, st));
-  HIP_TRY(hipMemsetAsync(bcnt, 0, C * 4, st));
-  HIP_TRY(hipMemsetAsync(lead, 0x7F, C * 4, st));
-  HIP_TRY(hipMemsetAsync(cstart, 0, C * 4, st));
-  const int32_t state0[4] = {(int32_t)n_cells, 0, 0, 0};
-  HIP_TRY(hipMemcpyAsync(state, state0, sizeof(state0), hipMemcpyHostToDevice, st));
-  NdtMap m{};
-  m.h.keys = (uint64_t *)keys;
-  m.h.first = nullptr;
-  m.h.rank = (int *)rank;
-  m.h.mask = (uint32_t)(hcap - 1);
-  m.rec = (const double *)rec;
-  m.count = (const int *)count;
-  m.keys = (const uint64_t *)ckeys;
-  m.n_cells = (int)cell_capacity;
-  m.resolution = resolution;
-  if (n_cells > 0) {
-    const unsigned nb = (unsigned)((n_cells + 255) / 256);
-    HIP_TRY(hipMemcpyAsync(ckeys, cell_keys_dev, (size_t)n_cells * 8, hipMemcpyDeviceToDevice, st));
-    hipLaunchKernelGGL(k_radius_cells_insert, dim3(nb), dim3(256), 0, st, (const unsigned long long *)cell_keys_dev, (int)n_cells, m.h);
-    hipLaunchKernelGGL(k_ndt_cells_dyn, dim3(nb), dim3(256), 0, st, (const int *)cell_start_dev, (const int *)cell_pts_dev,
-                       map_xyz_dev, (int)n_cells, (int)n_map, min_points, eig_ratio, (double *)rec, (int *)count, (double *)S);
-  }
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipStreamSynchronize(st));   // state0 is on this frame
-  c->ndt = m;
-  NdtDyn d{};
-  d.capacity = (int)cell_capacity, d.min_points = min_points, d.eig_ratio = eig_ratio;
-  d.rec = (double *)rec, d.count = (int *)count, d.keys = (uint64_t *)ckeys, d.S = (double *)S;
-  d.bcnt = (int *)bcnt, d.lead = (int *)lead, d.cstart = (int *)cstart, d.state = (int *)state;
-  c->ndt_dyn = d;
-  return SPS_OK;
+  return ndt_map_build_impl(c, cell_keys_dev, cell_start_dev, cell_pts_dev, map_xyz_dev, n_cells, n_map, resolution, min_points,
+                            eig_ratio, true, cell_capacity, stream);
 }
 
 int64_t sps_ndt_map_update_scratch(int64_t cap) {

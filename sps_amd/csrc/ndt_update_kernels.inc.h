@@ -2,15 +2,16 @@
 // the online NDT map (host side: ndt_update_host.inc.h; ABI: the "NDT localiser, online map" section of include/sps_hip.h;
 // DESIGN.md 8f).
 //
-//   k_ndt_cells_dyn     (dynamic build)  k_ndt_cells restated, keeping S = sum (p - mean)(p - mean)^T beside the record
-//   k_ndt_upd_lookup    (update, 1)      q = R p + t, the cell of q in the map's hash; misses meet in the update's own hash
+//   (dynamic build: k_ndt_cells of ndt_kernels.inc.h with its S_out set, S = sum (p - mean)(p - mean)^T beside the record)
+//   k_ndt_upd_lookup    (update, 1)      q = R p + t (loc_transform), the cell of q (ndt_cell_key) in the map's hash; misses
+//                                        meet in the update's own hash
 //   k_ndt_upd_found     (update, 2)      one workgroup: founders ranked by point index, ids up to the capacity, info[0..2]
 //   k_ndt_upd_resolve   (update, 3)      every point learns its cell id; admitted founders enter the map's hash; per cell
 //                                        the batch count and the lowest point index
 //   k_ndt_upd_offsets   (update, 4)      one workgroup: the touched cells in order of their lowest point, list offsets
 //   k_ndt_upd_fill      (update, 5)      the cells' index lists (any order inside a cell)
 //   k_ndt_upd_stats     (update, 6)      one wave per touched cell: indices into ascending order, n_b, mean_b, S_b
-//   k_ndt_upd_merge     (update, 7)      one thread per touched cell: forgetting, merge, k_ndt_cells' tail, the record
+//   k_ndt_upd_merge     (update, 7)      one thread per touched cell: forgetting, merge, ndt_record_from_moments
 //
 // The rules of ndt_kernels.inc.h hold: float64, contraction off, loc_mul / loc_add / __ddiv_rn, no float atomics.  The integer
 // atomics are a compare-and-swap on a key, atomicMin of a point index and atomicAdd of a count: none of their results
@@ -51,80 +52,6 @@ struct NdtUpdScratch {
 
 __device__ inline bool ndt_upd_gate_open(const int *__restrict__ gate) { return !gate || (unsigned)*gate <= 1u; }
 
-// k_ndt_cells' tail: the record of a cell from (n, mean, S)
-__device__ inline void ndt_record_from_moments(int n, const double mu[3], const double S[6], int min_points, double eig_ratio,
-                                               double *__restrict__ o) {
-  double icov[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-  bool valid = n >= min_points && n >= 2;
-  if (n >= 2) {
-    const double nm1 = (double)(n - 1);
-    double cv[6];
-#pragma unroll
-    for (int i = 0; i < 6; ++i) cv[i] = __ddiv_rn(S[i], nm1);
-    double a[3][3] = {{cv[0], cv[1], cv[2]}, {cv[1], cv[3], cv[4]}, {cv[2], cv[4], cv[5]}};
-    double v[3][3] = {{1.0, 0.0, 0.0}, {0.0, 1.0, 0.0}, {0.0, 0.0, 1.0}};
-    for (int sweep = 0; sweep < NDT_SWEEPS; ++sweep) {
-      ndt_rotate(a, v, 0, 1);
-      ndt_rotate(a, v, 0, 2);
-      ndt_rotate(a, v, 1, 2);
-    }
-    double lam[3] = {a[0][0], a[1][1], a[2][2]};
-    const double lmax = fmax(fmax(lam[0], lam[1]), lam[2]);
-    const double lfloor = loc_mul(eig_ratio, lmax);
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-      if (lam[i] < lfloor) lam[i] = lfloor;
-    valid = valid && lmax > 0.0;
-    int k = 0;
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-      for (int j = i; j < 3; ++j, ++k)
-        icov[k] = loc_add(loc_add(__ddiv_rn(loc_mul(v[i][0], v[j][0]), lam[0]), __ddiv_rn(loc_mul(v[i][1], v[j][1]), lam[1])),
-                          __ddiv_rn(loc_mul(v[i][2], v[j][2]), lam[2]));
-  }
-  for (int a = 0; a < 3; ++a) valid = valid && isfinite(mu[a]);
-  for (int i = 0; i < 6; ++i) valid = valid && isfinite(icov[i]);
-  o[0] = mu[0], o[1] = mu[1], o[2] = mu[2];
-#pragma unroll
-  for (int i = 0; i < 6; ++i) o[3 + i] = icov[i];
-  o[9] = valid ? 1.0 : 0.0;
-}
-
-// One thread per cell, as k_ndt_cells: the same reads, the same sums in the same order, then the tail above.
-__global__ __launch_bounds__(256) void k_ndt_cells_dyn(const int *__restrict__ cell_start, const int *__restrict__ cell_pts,
-                                                        const double *__restrict__ xyz, int n_cells, int n_map, int min_points,
-                                                        double eig_ratio, double *__restrict__ rec, int *__restrict__ count,
-                                                        double *__restrict__ S_out) {
-  const int c = blockIdx.x * 256 + threadIdx.x;
-  if (c >= n_cells) return;
-  const int lo = max(cell_start[c], 0), hi = min(cell_start[c + 1], n_map);
-  const int n = max(hi - lo, 0);
-  double sum[3] = {0.0, 0.0, 0.0};
-  for (int t = lo; t < hi; ++t) {
-    const int j = cell_pts[t];
-    if (j < 0 || j >= n_map) continue;
-#pragma unroll
-    for (int a = 0; a < 3; ++a) sum[a] = loc_add(sum[a], xyz[(size_t)j * 3 + a]);
-  }
-  double mu[3] = {0.0, 0.0, 0.0};
-  if (n > 0)
-    for (int a = 0; a < 3; ++a) mu[a] = __ddiv_rn(sum[a], (double)n);
-  double cv[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-  for (int t = lo; t < hi; ++t) {
-    const int j = cell_pts[t];
-    if (j < 0 || j >= n_map) continue;
-    const double dx = loc_add(xyz[(size_t)j * 3], -mu[0]), dy = loc_add(xyz[(size_t)j * 3 + 1], -mu[1]),
-                 dz = loc_add(xyz[(size_t)j * 3 + 2], -mu[2]);
-    cv[0] = loc_add(cv[0], loc_mul(dx, dx)), cv[1] = loc_add(cv[1], loc_mul(dx, dy)), cv[2] = loc_add(cv[2], loc_mul(dx, dz));
-    cv[3] = loc_add(cv[3], loc_mul(dy, dy)), cv[4] = loc_add(cv[4], loc_mul(dy, dz)), cv[5] = loc_add(cv[5], loc_mul(dz, dz));
-  }
-#pragma unroll
-  for (int i = 0; i < 6; ++i) S_out[(size_t)c * 6 + i] = cv[i];
-  ndt_record_from_moments(n, mu, cv, min_points, eig_ratio, rec + (size_t)c * NDT_REC);
-  count[c] = n;
-}
-
 // ---- the update ----------------------------------------------------------------------------------------------------------
 // exclusive prefix of v over the NDT_UPD_BLOCK threads of the workgroup (every thread must call); lds: NDT_UPD_BLOCK / 64 ints
 __device__ inline int ndt_upd_scan(int v, int *lds, int &total) {
@@ -156,21 +83,15 @@ __global__ __launch_bounds__(256) void k_ndt_upd_lookup(const double *__restrict
   const int n = min(cap, max(*n_dev, 0));
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
-  const double *T = T_dev ? T_dev : Th.m;
   const double px = pts[(size_t)i * 3], py = pts[(size_t)i * 3 + 1], pz = pts[(size_t)i * 3 + 2];
-  long long cc[3];
-  bool in = true;
+  double q[3];
+  if (T_dev) loc_transform(T_dev, px, py, pz, q);   // one uniform branch, not a choice of address per entry of the pose
+  else loc_transform(Th.m, px, py, pz, q);
 #pragma unroll
-  for (int a = 0; a < 3; ++a) {
-    const double q = loc_add(loc_add(loc_add(loc_mul(T[4 * a], px), loc_mul(T[4 * a + 1], py)), loc_mul(T[4 * a + 2], pz)), T[4 * a + 3]);
-    s.q[(size_t)i * 3 + a] = q;
-    const double f = floor(__ddiv_rn(q, m.resolution));
-    in = in && f >= -1048575.0 && f <= 1048575.0;   // NaN and infinities compare false
-    cc[a] = in ? (long long)f : 0;
-  }
+  for (int a = 0; a < 3; ++a) s.q[(size_t)i * 3 + a] = q[a];
   int cell = -1, slot = -1;
-  if (in) {
-    const uint64_t key = radius_key(cc[0], cc[1], cc[2]);
+  uint64_t key;
+  if (ndt_cell_key(q, m.resolution, 0, key)) {
     const int ms = hash_find_slot(m.h, key);
     if (ms >= 0) {
       cell = m.h.rank[ms];
@@ -286,6 +207,15 @@ __global__ __launch_bounds__(256) void k_ndt_upd_fill(const int *__restrict__ n_
   if (pos >= 0 && pos < cap) s.list[pos] = i;
 }
 
+// lane l's point of a chunk of m <= 64 entries of the ordered list that starts at entry `at` (zeros for l >= m)
+__device__ inline void ndt_upd_chunk_point(const NdtUpdScratch &s, int at, int m, int n, double &x, double &y, double &z) {
+  x = y = z = 0.0;
+  if ((int)threadIdx.x < m) {
+    const int j = min(max(s.list[at + (int)threadIdx.x], 0), n - 1);
+    x = s.q[(size_t)j * 3], y = s.q[(size_t)j * 3 + 1], z = s.q[(size_t)j * 3 + 2];
+  }
+}
+
 // 6: one wave (a workgroup of 64) per touched cell.  The cell's indices are distinct values below n, so a bitmap of n bits
 // in LDS orders them: set the bits (an integer atomicOr), count the words' bits, write the indices back in ascending order.
 // Then the sums of k_ndt_cells over that order: 64 points at a time, lane l holds point l of the chunk and every lane adds
@@ -332,11 +262,8 @@ __global__ __launch_bounds__(64) void k_ndt_upd_stats(const int *__restrict__ n_
     double sum[3] = {0.0, 0.0, 0.0};
     for (int k0 = 0; k0 < nb; k0 += 64) {
       const int m = min(64, nb - k0);
-      double x = 0.0, y = 0.0, z = 0.0;
-      if (lane < m) {
-        const int j = min(max(s.list[st + k0 + lane], 0), n - 1);
-        x = s.q[(size_t)j * 3], y = s.q[(size_t)j * 3 + 1], z = s.q[(size_t)j * 3 + 2];
-      }
+      double x, y, z;
+      ndt_upd_chunk_point(s, st + k0, m, n, x, y, z);
       for (int l = 0; l < m; ++l) {
         sum[0] = loc_add(sum[0], __shfl(x, l, 64));
         sum[1] = loc_add(sum[1], __shfl(y, l, 64));
@@ -348,11 +275,8 @@ __global__ __launch_bounds__(64) void k_ndt_upd_stats(const int *__restrict__ n_
     double cv[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
     for (int k0 = 0; k0 < nb; k0 += 64) {
       const int m = min(64, nb - k0);
-      double x = 0.0, y = 0.0, z = 0.0;
-      if (lane < m) {
-        const int j = min(max(s.list[st + k0 + lane], 0), n - 1);
-        x = s.q[(size_t)j * 3], y = s.q[(size_t)j * 3 + 1], z = s.q[(size_t)j * 3 + 2];
-      }
+      double x, y, z;
+      ndt_upd_chunk_point(s, st + k0, m, n, x, y, z);
       for (int l = 0; l < m; ++l) {
         const double dx = loc_add(__shfl(x, l, 64), -mu[0]), dy = loc_add(__shfl(y, l, 64), -mu[1]),
                      dz = loc_add(__shfl(z, l, 64), -mu[2]);

@@ -291,6 +291,21 @@ class ScanToMapLocaliser:
             self._ds_rows = rows
         return self._ds_scratch
 
+    def _thin(self, rows, n_dev, n_max, n_points_ptr, s):
+        """voxel-grid thinning of the rows into self._pts on stream s; the survivors' count goes to n_points_ptr"""
+        self.ctx.loc_downsample(rows.data_ptr() if n_max else None, rows.stride(0) if n_max else 3, n_max, n_dev.data_ptr(),
+                                self.leaf, self._pts.data_ptr(), self.capacity, n_points_ptr,
+                                self._downsample_scratch(n_max).data_ptr(), s)
+
+    @staticmethod
+    def _to_host(out, st):
+        """the frame's device buffer into a pinned host buffer of its own, behind everything issued on st -> (host, event)"""
+        host = torch.empty(out.numel(), dtype=out.dtype).pin_memory()
+        host.copy_(out, non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record(st)
+        return host, ev
+
     def _checked_rows(self, rows):
         if not (torch.is_tensor(rows) and rows.is_cuda and rows.device == self.device):
             raise TypeError(f"{type(self).__name__}.submit needs a tensor on the localiser's device")
@@ -333,18 +348,12 @@ class ScanToMapLocaliser:
             size = 19 + 32 * K if with_normal else 19 + 4 * K
             out = torch.zeros(size + 2 if integrate else size, dtype=torch.float64, device=dev)   # | info int32[4]
             base = out.data_ptr()
-            scratch = self._downsample_scratch(n_max)
-            self.ctx.loc_downsample(rows.data_ptr() if n_max else None, rows.stride(0) if n_max else 3, n_max,
-                                    n_dev.data_ptr(), self.leaf, self._pts.data_ptr(), self.capacity, base + 18 * 8,
-                                    scratch.data_ptr(), s)
+            self._thin(rows, n_dev, n_max, base + 18 * 8, s)
             self._align(base + 18 * 8, T, K, base, base + 16 * 8, base + 19 * 8 if K else None,
                         base + (19 + 4 * K) * 8 if with_normal and K else None, s)
             if integrate:
                 self._update(base + 18 * 8, None, base, base + 16 * 8, max_cell_points, base + size * 8, s)
-            host = torch.empty(out.numel(), dtype=torch.float64).pin_memory()
-            host.copy_(out, non_blocking=True)
-            ev = torch.cuda.Event()
-            ev.record(st)
+            host, ev = self._to_host(out, st)
         return PendingPose(K, with_normal, host, ev, (rows, n_dev, out), size if integrate else None)
 
     def _check_integrate(self, integrate, max_cell_points=0):
@@ -401,31 +410,20 @@ class NDTLocaliser(ScanToMapLocaliser):
         with torch.cuda.device(self.device):
             self.stream = torch.cuda.current_stream()
             self.ctx = _native.Context(self.device.index)
-            if self.cell_capacity is not None:
-                keys = start = pts = None
-                self.n_cells = 0
-                if self.n_map:
-                    keys, start, pts = radius_grid_cells(xyz, self.resolution)
-                    self.n_cells = len(keys)
+            self.n_cells, cells = 0, (None, None, None, None)
+            if self.n_map:
+                keys, start, pts = radius_grid_cells(xyz, self.resolution)
+                keys = keys.contiguous()
+                self.n_cells, cells = len(keys), (keys.data_ptr(), start.data_ptr(), pts.data_ptr(), xyz.data_ptr())
+            args = (*cells, self.n_cells, self.n_map, self.resolution, self.min_points_per_cell, self.eig_ratio)
+            if self.cell_capacity is None:
+                self.ctx.ndt_map_build(*args, self.stream.cuda_stream)
+            else:
                 if self.cell_capacity < max(self.n_cells, 1):
                     raise ValueError(f"cell_capacity {self.cell_capacity} is below the map's {self.n_cells} cells")
-                self.ctx.ndt_map_build_dynamic(keys.contiguous().data_ptr() if self.n_map else None,
-                                               start.data_ptr() if self.n_map else None, pts.data_ptr() if self.n_map else None,
-                                               xyz.data_ptr() if self.n_map else None, self.n_cells, self.n_map, self.resolution,
-                                               self.min_points_per_cell, self.eig_ratio, self.cell_capacity,
-                                               self.stream.cuda_stream)
+                self.ctx.ndt_map_build_dynamic(*args, self.cell_capacity, self.stream.cuda_stream)
                 self._update_scratch = torch.empty(_native.lib.sps_ndt_map_update_scratch(self.capacity), dtype=torch.uint8,
                                                    device=self.device)
-            elif self.n_map:
-                keys, start, pts = radius_grid_cells(xyz, self.resolution)
-                self.n_cells = len(keys)
-                self.ctx.ndt_map_build(keys.contiguous().data_ptr(), start.data_ptr(), pts.data_ptr(), xyz.data_ptr(),
-                                       self.n_cells, self.n_map, self.resolution, self.min_points_per_cell, self.eig_ratio,
-                                       self.stream.cuda_stream)
-            else:
-                self.n_cells = 0
-                self.ctx.ndt_map_build(None, None, None, None, 0, 0, self.resolution, self.min_points_per_cell,
-                                       self.eig_ratio, self.stream.cuda_stream)
             self._pts = torch.empty((self.capacity, 3), dtype=torch.float64, device=self.device)
             self._align_scratch = torch.empty(_native.lib.sps_ndt_align_scratch(self.capacity), dtype=torch.uint8, device=self.device)
             self._ds_scratch, self._ds_rows = None, -1
@@ -459,14 +457,9 @@ class NDTLocaliser(ScanToMapLocaliser):
             n_dev = self._count_on_device(count, n_max)
             out = torch.zeros(8, dtype=torch.int32, device=dev)      # n_points (+ pad) | info[4]
             base = out.data_ptr()
-            self.ctx.loc_downsample(rows.data_ptr() if n_max else None, rows.stride(0) if n_max else 3, n_max,
-                                    n_dev.data_ptr(), self.leaf, self._pts.data_ptr(), self.capacity, base,
-                                    self._downsample_scratch(n_max).data_ptr(), s)
+            self._thin(rows, n_dev, n_max, base, s)
             self._update(base, Th, None, None, max_cell_points, base + 16, s)
-            host = torch.empty(8, dtype=torch.int32).pin_memory()
-            host.copy_(out, non_blocking=True)
-            ev = torch.cuda.Event()
-            ev.record(st)
+            host, ev = self._to_host(out, st)
         return PendingMapUpdate(host, ev, (rows, n_dev, out))
 
     def map_info(self):
@@ -498,26 +491,25 @@ class NDTLocaliser(ScanToMapLocaliser):
             T_dev = T_host.to(dev, non_blocking=True)                # on the caller's stream; both stay with the pending object
             out = torch.zeros(o["size"] + 2 if integrate else o["size"], dtype=torch.float64, device=dev)   # | info int32[4]
             base = out.data_ptr()
-            self.ctx.loc_downsample(rows.data_ptr() if n_max else None, rows.stride(0) if n_max else 3, n_max,
-                                    n_dev.data_ptr(), self.leaf, self._pts.data_ptr(), self.capacity, base + o["n_points"] * 8,
-                                    self._downsample_scratch(n_max).data_ptr(), s)
-            self.ctx.ndt_align_batch(self._pts.data_ptr(), base + o["n_points"] * 8, self.capacity, T_dev.data_ptr(), K, I,
-                                     self.neighbours, self.min_correspondences, self.outlier_ratio, self.tol_t, self.tol_r,
-                                     base + o["T_out"] * 8, base + o["status"] * 8, base + o["trace"] * 8 if I else None,
-                                     base + o["normal"] * 8 if with_normal and I else None, base + o["final"] * 8,
-                                     base + o["best"] * 8, base + o["T_best"] * 8, self._batch_scratch_for(K).data_ptr(), s)
-            if integrate:                                            # best[1]: the selected hypothesis' status, -1 where none
-                self._update(base + o["n_points"] * 8, None, base + o["T_best"] * 8, base + o["best"] * 8 + 4, max_cell_points,
-                             base + o["size"] * 8, s)
-            host = torch.empty(out.numel(), dtype=torch.float64).pin_memory()
-            host.copy_(out, non_blocking=True)
-            ev = torch.cuda.Event()
-            ev.record(st)
+            self._thin(rows, n_dev, n_max, base + o["n_points"] * 8, s)
+            self._align_batch(base + o["n_points"] * 8, T_dev.data_ptr(), K, I, with_normal, base, o, s, integrate, max_cell_points)
+            host, ev = self._to_host(out, st)
         return PendingPoses(K, I, with_normal, host, ev, (rows, n_dev, out, T_host, T_dev), upd=integrate)
 
     def submit_filtered_batch(self, pending, T_inits, **kw) -> PendingPoses:
         """``submit_batch`` of the kept rows of a pending SPSFilter / SPSCVMFilter frame, without the frame's result()."""
         return self.submit_batch(pending._filtered, pending.count_dev, T_inits, **kw)
+
+    def _align_batch(self, n_ptr, T_ptr, K, I, with_normal, base, o, s, integrate=False, max_cell_points=0):
+        """the K alignments of self._pts from the device poses at T_ptr into the batch's buffer at ``base`` (layout ``o``);
+        ``integrate``: then the map update at the selected pose, its info words behind the batch's part"""
+        self.ctx.ndt_align_batch(self._pts.data_ptr(), n_ptr, self.capacity, T_ptr, K, I, self.neighbours,
+                                 self.min_correspondences, self.outlier_ratio, self.tol_t, self.tol_r, base + o["T_out"] * 8,
+                                 base + o["status"] * 8, base + o["trace"] * 8 if I else None,
+                                 base + o["normal"] * 8 if with_normal and I else None, base + o["final"] * 8,
+                                 base + o["best"] * 8, base + o["T_best"] * 8, self._batch_scratch_for(K).data_ptr(), s)
+        if integrate:                                                # best[1]: the selected hypothesis' status, -1 where none
+            self._update(n_ptr, None, base + o["T_best"] * 8, base + o["best"] * 8 + 4, max_cell_points, base + o["size"] * 8, s)
 
     def _batch_scratch_for(self, K):
         if K > self._batch_hyp:                                      # grows with the largest batch seen (stream-ordered reuse)
@@ -528,9 +520,7 @@ class NDTLocaliser(ScanToMapLocaliser):
 
     def _score(self, rows, n_dev, n_max, T_dev, P, n_points_ptr, score_ptr, s):
         """thin the rows into self._pts (count to n_points_ptr), then the scores of the P poses of T_dev"""
-        self.ctx.loc_downsample(rows.data_ptr() if n_max else None, rows.stride(0) if n_max else 3, n_max, n_dev.data_ptr(),
-                                self.leaf, self._pts.data_ptr(), self.capacity, n_points_ptr,
-                                self._downsample_scratch(n_max).data_ptr(), s)
+        self._thin(rows, n_dev, n_max, n_points_ptr, s)
         if P > self._score_poses:                                    # grows with the largest grid seen (stream-ordered reuse)
             self._score_scratch = torch.empty(_native.lib.sps_ndt_score_scratch(self.capacity, P), dtype=torch.uint8,
                                               device=self.device)
@@ -555,10 +545,7 @@ class NDTLocaliser(ScanToMapLocaliser):
             out = torch.zeros(2 * P + 1, dtype=torch.float64, device=dev)   # score[P][2] | n_points int32 (+ pad)
             base = out.data_ptr()
             self._score(rows, n_dev, n_max, T_dev, P, base + 2 * P * 8, base, s)
-            host = torch.empty(out.numel(), dtype=torch.float64).pin_memory()
-            host.copy_(out, non_blocking=True)
-            ev = torch.cuda.Event()
-            ev.record(st)
+            host, ev = self._to_host(out, st)
         return PendingScores(P, host, ev, (rows, n_dev, out, T_host, T_dev))
 
     @torch.no_grad()
@@ -591,17 +578,8 @@ class NDTLocaliser(ScanToMapLocaliser):
             self._score(rows, n_dev, n_max, T_dev, P, n_ptr, sbase + so["score"] * 8, s)
             self.ctx.ndt_top_poses(sbase + so["score"] * 8, T_dev.data_ptr(), P, self.min_correspondences, K,
                                    sbase + so["top"] * 8, sbase + so["T_top"] * 8, sbase + so["n_top"] * 8, s)
-            self.ctx.ndt_align_batch(self._pts.data_ptr(), n_ptr, self.capacity, sbase + so["T_top"] * 8, K, I,
-                                     self.neighbours, self.min_correspondences, self.outlier_ratio, self.tol_t, self.tol_r,
-                                     base + o["T_out"] * 8, base + o["status"] * 8, base + o["trace"] * 8 if I else None,
-                                     base + o["normal"] * 8 if with_normal and I else None, base + o["final"] * 8,
-                                     base + o["best"] * 8, base + o["T_best"] * 8, self._batch_scratch_for(K).data_ptr(), s)
-            if integrate:
-                self._update(n_ptr, None, base + o["T_best"] * 8, base + o["best"] * 8 + 4, max_cell_points, base + o["size"] * 8, s)
-            host = torch.empty(out.numel(), dtype=torch.float64).pin_memory()
-            host.copy_(out, non_blocking=True)
-            ev = torch.cuda.Event()
-            ev.record(st)
+            self._align_batch(n_ptr, sbase + so["T_top"] * 8, K, I, with_normal, base, o, s, integrate, max_cell_points)
+            host, ev = self._to_host(out, st)
         return PendingRelocalisation(P, PendingPoses(K, I, with_normal, host, ev, (rows, n_dev, out, T_host, T_dev), so["size"],
                                                      upd=integrate))
 

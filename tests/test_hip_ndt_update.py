@@ -40,9 +40,9 @@ def cells_of(loc):
     return dict(zip(FIELDS, loc.map_cells()))
 
 
-def raw_cells(loc):
+def raw_cells(loc, C=None):
     """sps_ndt_map_cells itself: every row the context holds (the capacity, for an online map)"""
-    C = loc.cell_capacity
+    C = loc.cell_capacity if C is None else C
     key = torch.zeros(C, dtype=torch.int64, device="cuda")
     cnt = torch.zeros(C, dtype=torch.int32, device="cuda")
     mean = torch.zeros((C, 3), dtype=torch.float64, device="cuda")
@@ -157,6 +157,34 @@ def test_one_update_matches_the_restatement(map_xyz, scans):
     assert (got.cells, got.founded, got.dropped, got.points, got.n_points) == (*want, len(pts))
     assert want[1] > 100 and want[3] == len(pts) and want[0] - n0 == want[1]  # founded cells follow in founder order
     assert (m["count"][:n0] != UR.build(map_xyz, CAPACITY)["count"]).sum() > 100   # and existing cells were merged into
+    assert_map_is(dyn, m)
+    dyn.ctx.check_errors(stream())
+
+
+def test_one_context_rebuilt_dynamic_static_dynamic():
+    """Both builds own the context's map through one routine: each replaces what the other left."""
+    from sps_amd import _native
+    from sps_amd.datasets.blt_dataset import radius_grid_cells
+    rng = np.random.default_rng(11)
+    mp = 0.05 + 1.9 * rng.random((300, 3))                                     # the 8 cells of [0, 2)^3
+    pts = 0.05 + np.array([2.9, 1.9, 1.9]) * rng.random((50, 3))               # those and the 4 cells at 2 <= x < 3
+    dyn = make(mp, capacity=16)                                                # the first dynamic build
+    xyz = dev(mp)
+    keys, start, idx = radius_grid_cells(xyz, RES)
+    keys = keys.contiguous()
+    args = (keys.data_ptr(), start.data_ptr(), idx.data_ptr(), xyz.data_ptr(), len(keys), len(mp), RES, 6, 0.01)
+    assert len(keys) == 8 and dyn.map_info() == (8, 16, 0)
+    dyn.ctx.ndt_map_build(*args, stream())
+    with pytest.raises(_native.SpsError):
+        raw_update(dyn, pts, len(pts), len(pts), np.eye(4))
+    with pytest.raises(_native.SpsError):
+        dyn.ctx.ndt_map_info()
+    assert_same_cells(raw_cells(dyn, 8), NR.cells(mp, RES))                    # the static map holds its 8 rows
+    dyn.ctx.ndt_map_build_dynamic(*args, 16, stream())
+    m = UR.build(mp, 16)
+    assert_map_is(dyn, m)
+    want = UR.update(m, pts, np.eye(4))
+    assert raw_update(dyn, pts, len(pts), len(pts), np.eye(4)) == want and want[1] == 4 and want[3] == 50
     assert_map_is(dyn, m)
     dyn.ctx.check_errors(stream())
 
