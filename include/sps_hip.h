@@ -648,6 +648,50 @@ int sps_ndt_map_update(sps_ctx *ctx, const double *pts_dev, const int32_t *n_dev
                        void *scratch_dev, void *stream);
 int sps_ndt_map_info(sps_ctx *ctx, int64_t *out_host);
 
+/* ---- NDT localiser, multi-resolution pyramid --------------------------------------------------------------------------
+ * One alignment registered coarse to fine: coarse cells give a wide basin, fine cells the accuracy, and the pose is handed
+ * from level to level on the device, so the host issues the same launches whatever the data does.    Additive:
+ * sps_version() is unchanged, and neither the context's single map nor any call above is touched.
+ *
+ * sps_ndt_pyramid_build: n_levels (1 .. SPS_NDT_PYR_MAX_LEVELS) static cell maps of the same map points, coarsest first:
+ *   level l groups map_xyz_dev[n_map][3] by cells of edge resolution[l] (host arrays of n_levels entries: cell_keys_dev[l],
+ *   cell_start_dev[l], cell_pts_dev[l] device pointers as for sps_ndt_map_build, n_cells[l], resolution[l]).  Level l holds,
+ *   bit for bit, the map sps_ndt_map_build makes from the same arguments; a level may have no cells.  Every level is checked
+ *   as sps_ndt_map_build checks; resolutions must be strictly decreasing.  (-d1, d2) of the Gaussian fit is made here per
+ *   level from outlier_ratio and resolution[l], as sps_ndt_align makes it per call.  The levels live in the context beside
+ *   its single map; a second build replaces the first.  Allocates and synchronises.
+ * sps_ndt_pyramid_cells: sps_ndt_map_cells of level `level`.
+ * sps_ndt_pyramid_align: up to `iters` slots, a slot being one iteration of sps_ndt_align (launch A, launch B) against the
+ *   map of the current level.  The call starts at level 0.  After a step at level l that level's count of used slots goes
+ *   up by one; then
+ *     |v| < tol_t and |omega| < tol_r:  on the last level status 0 and the call is done; otherwise the current level becomes
+ *       l + 1 and nothing else changes: the pose carries over;
+ *     else, the count has reached level_iters[l] (host int32[n_levels], each >= 1):  on the last level the call is done with
+ *       status 1; otherwise the current level becomes l + 1.
+ *   Fewer than min_corr points counted (status 2) and a failed Cholesky or non-finite solution (status 3) are final at any
+ *   level, and T_out_dev is then T_init_host bit for bit.  Slots beyond `iters` do not exist: a call that has not reached
+ *   status 0 by then has status 1, whatever level it is at.
+ *   status_dev int32[4] = (code, slots used, points counted in the last live slot, level of the last live slot).
+ *   trace_dev double[iters][4] and normal_dev (may be NULL) double[iters][28] are sps_ndt_align's rows, one per slot;
+ *   level_dev int32[iters] is the level slot s ran at, -1 for a slot that did no work.  Per slot the operations and the
+ *   order of the sums are sps_ndt_align's, so one level gives its bits and several levels give those of as many
+ *   sps_ndt_align calls with iters = level_iters[l], each started from the end pose of the one before (while every one of
+ *   them ends with status 0 or 1).  neighbours, cap, iters and the tolerances are checked as for sps_ndt_align.
+ *   Launches: 1 + 2 * iters, no memset.  scratch_dev: sps_ndt_pyramid_align_scratch(cap) bytes (-1 for cap out of range).
+ *   Never allocates, never synchronises, never raises the sticky error. */
+#define SPS_NDT_PYR_MAX_LEVELS 4
+int sps_ndt_pyramid_build(sps_ctx *ctx, int n_levels, const uint64_t *const *cell_keys_dev, const int32_t *const *cell_start_dev,
+                          const int32_t *const *cell_pts_dev, const int64_t *n_cells, const double *resolution,
+                          const double *map_xyz_dev, int64_t n_map, int min_points, double eig_ratio, double outlier_ratio,
+                          void *stream);
+int sps_ndt_pyramid_cells(sps_ctx *ctx, int level, uint64_t *key_out_dev, int32_t *count_out_dev, double *mean_out_dev,
+                          double *icov_out_dev, int32_t *valid_out_dev);
+int64_t sps_ndt_pyramid_align_scratch(int64_t cap);
+int sps_ndt_pyramid_align(sps_ctx *ctx, const double *pts_dev, const int32_t *n_dev, int64_t cap, const double *T_init_host,
+                          int iters, const int32_t *level_iters, int neighbours, int min_corr, double tol_t, double tol_r,
+                          double *T_out_dev, int32_t *status_dev, double *trace_dev, double *normal_dev, int32_t *level_dev,
+                          void *scratch_dev, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

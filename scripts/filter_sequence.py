@@ -19,7 +19,9 @@ random initialisation.
 pose): the filter's kept rows are registered against the map by a device point-to-point ICP (the stand-in for
 hdl_localization; not a port of it), the corrected pose goes back into the filter, and the replayed poses only score
 the result.  ``--localiser ndt`` registers with sps_amd.localiser.NDTLocaliser instead: the normal-distributions transform
-hdl_localization itself runs (1 m cells, DIRECT7), still without its UKF and IMU.  Frames then run one at a time; behind each frame's lines comes
+hdl_localization itself runs (1 m cells, DIRECT7), still without its UKF and IMU; with ``--resolutions 2,1,0.5`` it
+registers every frame coarse to fine over a pyramid of cell maps (``--level-iterations`` caps each level; a ``levels:``
+line then tells the iterations per level).  Frames then run one at a time; behind each frame's lines comes
 ``loc: status iterations n_corr rmse | err_t err_r`` (metres, degrees, against the replayed pose map_tr @ pose) and at
 the end the absolute pose error evo_ape prints by default.  ``--traj-out FILE`` writes the estimated trajectory
 (stamp + the top three rows of the pose per line).
@@ -134,13 +136,16 @@ def hypothesis_grid(counts, steps, option="--hypotheses", step_option="--hypothe
 
 
 def closed_loop(name, f, pc_map, replay, finish, traj_out, which="icp", hypotheses=None, search=None, update_map=False,
-                cell_capacity=None, max_cell_points=0):
+                cell_capacity=None, max_cell_points=0, resolutions=None, level_iterations=None):
     """--localise: one LocalisationLoop step per frame, scored against the replayed poses."""
     from sps_amd.localiser import LocalisationLoop, NDTLocaliser, ScanToMapLocaliser
     from sps_amd.trajectory import ape_translation, rotation_angle, write_trajectory
     if update_map:                                               # an online map: room for twice the map's cells by default
         n_cells = NDTLocaliser(pc_map[:, :3]).n_cells
         localiser = NDTLocaliser(pc_map[:, :3], cell_capacity=cell_capacity or max(2 * n_cells, 4096))
+    elif resolutions is not None:                                # coarse to fine; hypotheses and search keep the single map
+        caps = level_iterations or (30,) * len(resolutions)       # the budget is their sum: it cuts no level short
+        localiser = NDTLocaliser(pc_map[:, :3], resolutions=resolutions, iterations=sum(caps), level_iterations=caps)
     else:
         localiser = NDTLocaliser(pc_map[:, :3]) if which == "ndt" else ScanToMapLocaliser(pc_map[:, :3])
     loop, stamps, ref = None, [], []
@@ -156,6 +161,8 @@ def closed_loop(name, f, pc_map, replay, finish, traj_out, which="icp", hypothes
         err_r = float(np.degrees(rotation_angle(step.pose, T)))
         print(f"[{stamp}] loc: {p.status:d} {p.iterations:d} {p.n_corr:d} {p.rmse:.4f} | {err_t:.4f} {err_r:.4f}"
               + (" (flagged: the guess is kept)" if step.flagged else ""))
+        if p.levels is not None:
+            print(f"[{stamp}] levels: slots per level " + " ".join(str(int((p.levels == l).sum())) for l in range(len(resolutions))))
         u = step.batch.map_update if step.batch is not None else p.map_update
         if u is not None:
             print(f"[{stamp}] map: {u.cells:d} cells | founded {u.founded:d} dropped {u.dropped:d} | {u.points:d} of {u.n_points:d} "
@@ -204,8 +211,24 @@ def closed_loop(name, f, pc_map, replay, finish, traj_out, which="icp", hypothes
               help="with --update-map: cells the online map has room for (default: twice the map's, at least 4096)")
 @click.option("--max-cell-points", "max_cell_points", type=int, default=0,
               help="with --update-map: cap on the weight of a cell's history (0: none)")
+@click.option("--resolutions", "resolutions", type=str, default=None,
+              help="with --localiser ndt: R0,R1,... cell edges in m, strictly decreasing (at most 4): register coarse to fine")
+@click.option("--level-iterations", "level_iterations", type=str, default=None,
+              help="with --resolutions: N0,N1,... the most iterations each level may use (default: 30 each); their sum is the "
+                   "frame's budget")
 def main(name, weights, sequence, config, epsilon, out_dir, n_synth, localise, which, traj_out, hyp_counts, hyp_steps,
-         search_counts, search_steps, update_map, cell_capacity, max_cell_points):
+         search_counts, search_steps, update_map, cell_capacity, max_cell_points, resolutions, level_iterations):
+    if resolutions is not None and which != "ndt":
+        raise click.UsageError("--resolutions needs --localise --localiser ndt")
+    if resolutions is not None and update_map:
+        raise click.UsageError("--resolutions and --update-map exclude each other: the online map is single-resolution")
+    if level_iterations is not None and resolutions is None:
+        raise click.UsageError("--level-iterations needs --resolutions")
+    try:
+        resolutions = None if resolutions is None else tuple(float(v) for v in resolutions.split(","))
+        level_iterations = None if level_iterations is None else tuple(int(v) for v in level_iterations.split(","))
+    except ValueError:
+        raise click.UsageError("--resolutions takes numbers, --level-iterations integers, separated by commas")
     if update_map and which != "ndt":
         raise click.UsageError("--update-map needs --localise --localiser ndt")
     if (cell_capacity is not None or max_cell_points) and not update_map:
@@ -254,7 +277,7 @@ def main(name, weights, sequence, config, epsilon, out_dir, n_synth, localise, w
 
     if localise:
         closed_loop(name, f, pc_map, replay, finish, traj_out, which or "icp", hypotheses, search, update_map, cell_capacity,
-                    max_cell_points)
+                    max_cell_points, resolutions, level_iterations)
     elif traj_out:
         raise click.UsageError("--traj-out needs --localise")
     in_flight, prev_pose = None, None

@@ -144,6 +144,11 @@ def _load() -> C.CDLL:
         "sps_ndt_map_update_scratch": (i64, [i64]),
         "sps_ndt_map_update": (i32, [vp, vp, vp, i64, vp, vp, vp, i32, vp, vp, vp]),
         "sps_ndt_map_info": (i32, [vp, vp]),
+        "sps_ndt_pyramid_build": (i32, [vp, i32, vp, vp, vp, vp, vp, vp, i64, i32, C.c_double, C.c_double, vp]),
+        "sps_ndt_pyramid_cells": (i32, [vp, i32, vp, vp, vp, vp, vp]),
+        "sps_ndt_pyramid_align_scratch": (i64, [i64]),
+        "sps_ndt_pyramid_align": (i32, [vp, vp, vp, i64, vp, i32, vp, i32, i32, C.c_double, C.c_double, vp, vp, vp, vp, vp, vp,
+                                        vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)          # AttributeError here = header/library mismatch: fail loudly
@@ -174,7 +179,8 @@ EXPORTS = ["sps_last_error", "sps_version", "sps_ctx_create", "sps_ctx_destroy",
            "sps_ndt_align_scratch", "sps_ndt_map_build", "sps_ndt_map_cells", "sps_ndt_align",
            "sps_ndt_align_batch_scratch", "sps_ndt_align_batch",
            "sps_ndt_score_scratch", "sps_ndt_score_poses", "sps_ndt_top_poses",
-           "sps_ndt_map_build_dynamic", "sps_ndt_map_update_scratch", "sps_ndt_map_update", "sps_ndt_map_info"]
+           "sps_ndt_map_build_dynamic", "sps_ndt_map_update_scratch", "sps_ndt_map_update", "sps_ndt_map_info",
+           "sps_ndt_pyramid_build", "sps_ndt_pyramid_cells", "sps_ndt_pyramid_align_scratch", "sps_ndt_pyramid_align"]
 CROP_BLOCK = 1024          # SPS_CROP_BLOCK: map rows per int of sps_radius_crop's scratch
 
 
@@ -480,6 +486,28 @@ class Context:
         out = (C.c_int64 * 4)()
         check(lib.sps_ndt_map_info(self.handle, out))
         return int(out[0]), int(out[1]), int(out[2])
+
+    # ---- NDT localiser, multi-resolution pyramid (include/sps_hip.h, "NDT localiser, multi-resolution pyramid") ----
+    def ndt_pyramid_build(self, levels, xyz_ptr, n_map: int, min_points: int, eig_ratio: float, outlier_ratio: float,
+                          stream: int):
+        """levels: per level, coarsest first, (keys_ptr, start_ptr, pts_ptr, n_cells, resolution)"""
+        L = len(levels)
+        keys, start, pts = ((C.c_void_p * L)(*[lv[i] for lv in levels]) for i in range(3))
+        n_cells = (C.c_int64 * L)(*[int(lv[3]) for lv in levels])
+        res = (C.c_double * L)(*[float(lv[4]) for lv in levels])
+        check(lib.sps_ndt_pyramid_build(self.handle, L, keys, start, pts, n_cells, res, xyz_ptr, int(n_map), int(min_points),
+                                        float(eig_ratio), float(outlier_ratio), stream))
+
+    def ndt_pyramid_cells(self, level: int, key_ptr, count_ptr, mean_ptr, icov_ptr, valid_ptr):
+        check(lib.sps_ndt_pyramid_cells(self.handle, int(level), key_ptr, count_ptr, mean_ptr, icov_ptr, valid_ptr))
+
+    def ndt_pyramid_align(self, pts_ptr, n_dev_ptr: int, cap: int, T_init, iters: int, level_iters, neighbours: int,
+                          min_corr: int, tol_t: float, tol_r: float, T_out_ptr: int, status_ptr: int, trace_ptr, normal_ptr,
+                          level_ptr, scratch_ptr: int, stream: int):
+        caps = (C.c_int32 * len(level_iters))(*[int(v) for v in level_iters])
+        check(lib.sps_ndt_pyramid_align(self.handle, pts_ptr, n_dev_ptr, int(cap), self._mat(T_init), int(iters), caps,
+                                        int(neighbours), int(min_corr), float(tol_t), float(tol_r), T_out_ptr, status_ptr,
+                                        trace_ptr, normal_ptr, level_ptr, scratch_ptr, stream))
 
     def train_forward(self, params_ptr: int, numel: int, coords_ptr: int, ld: int, n: int, voxel_size: float,
                       scores_ptr: int, batch_stats_ptr, stream: int):

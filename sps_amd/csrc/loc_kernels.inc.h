@@ -236,17 +236,13 @@ __device__ inline void loc_sum_rows(const double *__restrict__ partial, int nb, 
   __syncthreads();
 }
 
-// Launch B for one pose, by one workgroup of 256 (k_loc_solve; k_loc_solve_batch in ndt_batch_kernels.inc.h runs it once per
-// hypothesis): loc_sum_rows, then thread 0 does the rest.  T_init is read only when the status becomes 2 or 3.
-__device__ inline void loc_solve_body(const double *__restrict__ partial, const int *__restrict__ n_dev, int cap, int iter,
-                                      int min_corr, double tol_t, double tol_r, const double *__restrict__ T_init,
-                                      double *__restrict__ T, int *__restrict__ status, int *__restrict__ done,
-                                      double *__restrict__ trace, double *__restrict__ normal, double (*seg)[32],
-                                      double *tot) {
-  if (*done) return;
-  const int n = min(cap, max(*n_dev, 0));
-  loc_sum_rows(partial, (n + LOC_PTS - 1) / LOC_PTS, threadIdx.x, seg, tot);
-  if (threadIdx.x != 0) return;
+// One Gauss-Newton step from the summed row tot, by one thread: the normal and trace rows of `iter`, status[1] and
+// status[2], the 6 x 6 Cholesky solve, Rodrigues, the pose update.  Returns -1 after a step (vn = |v|, th = |omega|, also in
+// the trace row), or the final code 2 (too few correspondences) / 3 (singular) with T = T_init and status[0] = the code.
+// What a step means for the call is the caller's: loc_solve_body below, k_ndt_pyr_solve in ndt_pyramid_kernels.inc.h.
+__device__ inline int loc_solve_step(const double *tot, int iter, int min_corr, const double *__restrict__ T_init,
+                                     double *__restrict__ T, int *__restrict__ status, double *__restrict__ trace,
+                                     double *__restrict__ normal, double &vn_out, double &th_out) {
   const int n_corr = (int)tot[28];
   const double sum_d2 = tot[27];
   double b[6];
@@ -303,8 +299,7 @@ __device__ inline void loc_solve_body(const double *__restrict__ partial, const 
   if (code >= 0) {
     for (int i = 0; i < 16; ++i) T[i] = T_init[i];
     status[0] = code;
-    *done = 1;
-    return;
+    return code;
   }
   const double wx = x[0], wy = x[1], wz = x[2];
   const double th2 = loc_add(loc_add(loc_mul(wx, wx), loc_mul(wy, wy)), loc_mul(wz, wz));
@@ -333,6 +328,26 @@ __device__ inline void loc_solve_body(const double *__restrict__ partial, const 
     }
   for (int i = 0; i < 12; ++i) T[i] = Tn[i];
   tr[2] = vn, tr[3] = th;
+  vn_out = vn, th_out = th;
+  return -1;
+}
+
+// Launch B for one pose, by one workgroup of 256 (k_loc_solve; k_loc_solve_batch in ndt_batch_kernels.inc.h runs it once per
+// hypothesis): loc_sum_rows, then thread 0 does the rest.  T_init is read only when the status becomes 2 or 3.
+__device__ inline void loc_solve_body(const double *__restrict__ partial, const int *__restrict__ n_dev, int cap, int iter,
+                                      int min_corr, double tol_t, double tol_r, const double *__restrict__ T_init,
+                                      double *__restrict__ T, int *__restrict__ status, int *__restrict__ done,
+                                      double *__restrict__ trace, double *__restrict__ normal, double (*seg)[32],
+                                      double *tot) {
+  if (*done) return;
+  const int n = min(cap, max(*n_dev, 0));
+  loc_sum_rows(partial, (n + LOC_PTS - 1) / LOC_PTS, threadIdx.x, seg, tot);
+  if (threadIdx.x != 0) return;
+  double vn, th;
+  if (loc_solve_step(tot, iter, min_corr, T_init, T, status, trace, normal, vn, th) >= 0) {
+    *done = 1;
+    return;
+  }
   if (vn < tol_t && th < tol_r) {
     status[0] = 0;
     *done = 1;

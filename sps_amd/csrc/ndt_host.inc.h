@@ -1,8 +1,8 @@
 // ndt_host.inc.h -- part of sps_hip.hip (included inside its extern "C" block): the entry points of the NDT localiser
 // (ABI: the "NDT localiser" section of include/sps_hip.h; kernels: ndt_kernels.inc.h).  sps_ndt_map_build allocates and
 // synchronises, like sps_radius_grid_upload; sps_ndt_align does neither: its scratch is the caller's.  Two helpers here
-// serve the later NDT files too: ndt_map_build_impl (the static and the dynamic build) and ndt_check_scan_args (the checks
-// that the alignment, the batch and the pose score share).
+// serve the later NDT files too: ndt_map_build_impl (the static and the dynamic build; ndt_map_make under it also builds the
+// levels of a pyramid) and ndt_check_scan_args (the checks that the alignment, the batch and the pose score share).
 
 namespace {
 // the Gaussian fit of the mixture (Magnusson 2009, eq. 6.8; PCL's gauss_d1_ / gauss_d2_), in float64 on the host; false
@@ -21,25 +21,29 @@ inline bool ndt_gauss_fit(double res, double outlier_ratio, NdtGauss &gs) {
 // what sps_ndt_align, sps_ndt_align_batch and sps_ndt_score_poses ask alike of the context's map and of the scan, and the
 // Gaussian fit.  aligns: the call iterates, so it also has an iteration limit and tolerances (sps_ndt_score_poses has
 // neither, and its own text for the point limit); the checks stay in the order every entry point always made them
-inline int ndt_check_scan_args(const sps_ctx *c, int neighbours, int64_t cap, double outlier_ratio, NdtGauss &gs, bool aligns,
-                               int iters = 0, double tol_t = 0.0, double tol_r = 0.0) {
-  if (!c->ndt.h.keys) return fail(SPS_ERR_INVALID, "sps_ndt_map_build has not been called");
+// (the part that does not look at a map is ndt_check_scan_limits: sps_ndt_pyramid_align, whose Gaussian fits were made
+// by its build, asks the same of its scan)
+inline int ndt_check_scan_limits(int neighbours, int64_t cap, bool aligns, int iters, double tol_t, double tol_r) {
   if (neighbours != 1 && neighbours != 7) return fail(SPS_ERR_INVALID, "neighbours must be 1 or 7");
   if (cap > SPS_MAX_POINTS || (aligns && iters > 10000))
     return aligns ? fail(SPS_ERR_INVALID, "too many points or iterations")
                   : fail(SPS_ERR_INVALID, "too many points (limit %d)", SPS_MAX_POINTS);
   if (aligns && (std::isnan(tol_t) || std::isnan(tol_r))) return fail(SPS_ERR_INVALID, "tolerances must not be NaN");
+  return SPS_OK;
+}
+inline int ndt_check_scan_args(const sps_ctx *c, int neighbours, int64_t cap, double outlier_ratio, NdtGauss &gs, bool aligns,
+                               int iters = 0, double tol_t = 0.0, double tol_r = 0.0) {
+  if (!c->ndt.h.keys) return fail(SPS_ERR_INVALID, "sps_ndt_map_build has not been called");
+  if (int e = ndt_check_scan_limits(neighbours, cap, aligns, iters, tol_t, tol_r)) return e;
   return ndt_gauss_fit(c->ndt.resolution, outlier_ratio, gs) ? SPS_OK : SPS_ERR_INVALID;
 }
 
 inline int64_t ndt_hash_slots(int64_t cells) { return next_pow2(2 * (cells < 512 ? 512 : cells)); }
 
-// The map of the context, static (room for the n_cells of the build; cell_capacity is not read) or dynamic (room for
-// cell_capacity cells, their moments S and the update's per-cell state beside the records).  Either replaces whatever map
-// the context had.  Allocates and synchronises.
-int ndt_map_build_impl(sps_ctx *c, const uint64_t *cell_keys_dev, const int32_t *cell_start_dev, const int32_t *cell_pts_dev,
-                       const double *map_xyz_dev, int64_t n_cells, int64_t n_map, double resolution, int min_points,
-                       double eig_ratio, bool dynamic, int64_t cell_capacity, void *stream) {
+// what every map build asks of its arguments (cell_capacity is read for a dynamic map only)
+inline int ndt_map_check_args(const sps_ctx *c, const uint64_t *cell_keys_dev, const int32_t *cell_start_dev,
+                              const int32_t *cell_pts_dev, const double *map_xyz_dev, int64_t n_cells, int64_t n_map,
+                              double resolution, int min_points, double eig_ratio, bool dynamic, int64_t cell_capacity) {
   if (!c || n_cells < 0 || n_map < 0 || n_cells > n_map) return fail(SPS_ERR_INVALID, "bad arguments");
   if (!(resolution > 0.0) || std::isinf(resolution)) return fail(SPS_ERR_INVALID, "resolution must be finite and > 0");
   if (!(eig_ratio > 0.0) || !(eig_ratio <= 1.0)) return fail(SPS_ERR_INVALID, "eig_ratio must be in (0, 1]");
@@ -48,18 +52,21 @@ int ndt_map_build_impl(sps_ctx *c, const uint64_t *cell_keys_dev, const int32_t 
   if (n_map >= (1ll << 31) || n_cells >= (1ll << 30)) return fail(SPS_ERR_INVALID, "map too large");
   if (dynamic && (cell_capacity < 1 || cell_capacity < n_cells)) return fail(SPS_ERR_INVALID, "cell_capacity must be >= max(n_cells, 1)");
   if (dynamic && cell_capacity >= (1ll << 30)) return fail(SPS_ERR_INVALID, "cell_capacity too large");
-  HIP_TRY(hipSetDevice(c->device));
-  hipStream_t st = (hipStream_t)stream;
-  HIP_TRY(hipDeviceSynchronize());
-  for (void *p : c->ndt_allocs) (void)hipFree(p);
-  c->ndt_allocs.clear();
-  c->ndt = NdtMap{};
-  c->ndt_dyn = NdtDyn{};
+  return SPS_OK;
+}
+
+// One cell map from checked arguments, its memory added to `allocs`: the hash, the records, the counts and the keys (and
+// for a dynamic map the moments S and the update's per-cell state), filled on stream st.  Does not synchronise: state0 (the
+// caller's, four words) is read by a copy still in flight on return.  m and d are written only on success.
+int ndt_map_make(std::vector<void *> &allocs, const uint64_t *cell_keys_dev, const int32_t *cell_start_dev,
+                 const int32_t *cell_pts_dev, const double *map_xyz_dev, int64_t n_cells, int64_t n_map, double resolution,
+                 int min_points, double eig_ratio, bool dynamic, int64_t cell_capacity, hipStream_t st, int32_t *state0,
+                 NdtMap &m_out, NdtDyn &d_out) {
   bool nomem = false;
   auto alloc = [&](size_t bytes) -> void * {
     void *p = nullptr;
     if (nomem || hipMalloc(&p, bytes ? bytes : 16) != hipSuccess) return nomem = true, nullptr;
-    c->ndt_allocs.push_back(p);
+    allocs.push_back(p);
     return p;
   };
   const size_t C = (size_t)(dynamic ? cell_capacity : n_cells);
@@ -83,7 +90,7 @@ int ndt_map_build_impl(sps_ctx *c, const uint64_t *cell_keys_dev, const int32_t 
   if (nomem) return fail(SPS_ERR_NOMEM, "hipMalloc for the NDT map failed");
   HIP_TRY(hipMemsetAsync(m.h.keys, 0xFF, (size_t)hcap * 8, st));
   HIP_TRY(hipMemsetAsync(m.h.rank, 0xFF, (size_t)hcap * 4, st));
-  const int32_t state0[4] = {(int32_t)n_cells, 0, 0, 0};
+  state0[0] = (int32_t)n_cells, state0[1] = state0[2] = state0[3] = 0;
   if (dynamic) {   // the rest values of the cells that the updates will found
     HIP_TRY(hipMemsetAsync(d.rec, 0, C * NDT_REC * 8, st));
     HIP_TRY(hipMemsetAsync(d.count, 0, C * 4, st));
@@ -92,7 +99,7 @@ int ndt_map_build_impl(sps_ctx *c, const uint64_t *cell_keys_dev, const int32_t 
     HIP_TRY(hipMemsetAsync(d.bcnt, 0, C * 4, st));
     HIP_TRY(hipMemsetAsync(d.lead, 0x7F, C * 4, st));
     HIP_TRY(hipMemsetAsync(d.cstart, 0, C * 4, st));
-    HIP_TRY(hipMemcpyAsync(d.state, state0, sizeof(state0), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(d.state, state0, 4 * sizeof(int32_t), hipMemcpyHostToDevice, st));
   }
   if (n_cells > 0) {
     const unsigned nb = (unsigned)((n_cells + 255) / 256);
@@ -102,6 +109,32 @@ int ndt_map_build_impl(sps_ctx *c, const uint64_t *cell_keys_dev, const int32_t 
                        (int)n_cells, (int)n_map, min_points, eig_ratio, d.rec, d.count, d.S);
   }
   HIP_TRY(hipGetLastError());
+  m_out = m, d_out = d;
+  return SPS_OK;
+}
+
+// The map of the context, static (room for the n_cells of the build; cell_capacity is not read) or dynamic (room for
+// cell_capacity cells, their moments S and the update's per-cell state beside the records).  Either replaces whatever map
+// the context had.  Allocates and synchronises.
+int ndt_map_build_impl(sps_ctx *c, const uint64_t *cell_keys_dev, const int32_t *cell_start_dev, const int32_t *cell_pts_dev,
+                       const double *map_xyz_dev, int64_t n_cells, int64_t n_map, double resolution, int min_points,
+                       double eig_ratio, bool dynamic, int64_t cell_capacity, void *stream) {
+  if (int e = ndt_map_check_args(c, cell_keys_dev, cell_start_dev, cell_pts_dev, map_xyz_dev, n_cells, n_map, resolution,
+                                 min_points, eig_ratio, dynamic, cell_capacity))
+    return e;
+  HIP_TRY(hipSetDevice(c->device));
+  hipStream_t st = (hipStream_t)stream;
+  HIP_TRY(hipDeviceSynchronize());
+  for (void *p : c->ndt_allocs) (void)hipFree(p);
+  c->ndt_allocs.clear();
+  c->ndt = NdtMap{};
+  c->ndt_dyn = NdtDyn{};
+  NdtMap m{};
+  NdtDyn d{};
+  int32_t state0[4];
+  if (int e = ndt_map_make(c->ndt_allocs, cell_keys_dev, cell_start_dev, cell_pts_dev, map_xyz_dev, n_cells, n_map, resolution,
+                           min_points, eig_ratio, dynamic, cell_capacity, st, state0, m, d))
+    return e;
   HIP_TRY(hipStreamSynchronize(st));   // state0 is on this frame
   c->ndt = m;
   if (dynamic) c->ndt_dyn = d;

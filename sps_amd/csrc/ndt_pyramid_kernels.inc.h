@@ -1,0 +1,113 @@
+// ndt_pyramid_kernels.inc.h -- part of sps_hip.hip (included inside its anonymous namespace, after ndt_update_kernels.inc.h):
+// the NDT localiser registering coarse to fine over a pyramid of static cell maps (host side: ndt_pyramid_host.inc.h; ABI:
+// the "NDT localiser, multi-resolution pyramid" section of include/sps_hip.h).
+//
+//   k_ndt_pyr_init    T_out = T_init, status = (1, 0, 0, 0), the state words 0, level[s] = -1, trace and normal rows 0
+//   k_ndt_pyr_assoc   (launch A of a slot)  ndt_assoc_body against the map of the level the state names
+//   k_ndt_pyr_solve   (launch B of a slot)  loc_sum_rows + loc_solve_step, then the handoff rule
+//
+// The levels are the maps k_radius_cells_insert and k_ndt_cells build, one NdtPyrLevel (map + Gaussian fit) each in a device
+// array.  Which level a slot runs at is decided on the device: the state words live in the caller's scratch behind the
+// partial rows, launch B of a slot writes them and both launches of the next slot read them, so the host issues the same
+// launches whatever happens.  Per slot every operation and the order of every sum are those of k_ndt_assoc / k_loc_solve,
+// whose bodies these kernels call: a pyramid of one level has the bits of sps_ndt_align, and one of several levels those of
+// as many sps_ndt_align calls chained through their end poses.  Stores are plain vector stores; nothing here is atomic.
+
+#pragma clang fp contract(off)
+
+constexpr int NDT_PYR_MAX = 4;        // SPS_NDT_PYR_MAX_LEVELS
+constexpr int NDT_PYR_STATE = 8;      // ints of state: done, level, slots used at each level, two spare
+static_assert(NDT_PYR_MAX == SPS_NDT_PYR_MAX_LEVELS, "include/sps_hip.h states the level limit");
+
+struct NdtPyrLevel {
+  NdtMap m;
+  NdtGauss gs;
+};
+
+struct NdtPyrCaps {
+  int v[NDT_PYR_MAX];      // level_iters: the most slots a level may use
+};
+
+// the pyramid of a context (sps_ndt_pyramid_build): the levels on the host, for the getter, and their device copy
+struct NdtPyramid {
+  int n_levels = 0;        // 0: none built
+  NdtPyrLevel lv[NDT_PYR_MAX]{};
+  const NdtPyrLevel *dev = nullptr;   // [NDT_PYR_MAX]
+};
+
+// Block 0 sets the pose, the status and the state; all blocks clear the per-slot rows (normal and level may be null / empty).
+__global__ __launch_bounds__(256) void k_ndt_pyr_init(LocPose T, int iters, double *__restrict__ T_out, int *__restrict__ status,
+                                                       int *__restrict__ state, double *__restrict__ trace,
+                                                       double *__restrict__ normal, int *__restrict__ level) {
+  const int t = threadIdx.x;
+  if (blockIdx.x == 0) {
+    if (t < 16) T_out[t] = T.m[t];
+    if (t < 4) status[t] = t == 0 ? 1 : 0;  // 1 = slots exhausted, unless a slot says otherwise
+    if (t < NDT_PYR_STATE) state[t] = 0;
+  }
+  const int stride = gridDim.x * 256;
+  for (int i = blockIdx.x * 256 + t; i < iters * 28; i += stride) {
+    if (i < iters) level[i] = -1;
+    if (i < iters * 4) trace[i] = 0.0;
+    if (normal) normal[i] = 0.0;
+  }
+}
+
+// Launch A.  Grid and workgroup of k_ndt_assoc.  The level is the same for every thread of the grid: it goes through a
+// scalar register, and the level's descriptor is read from the device array (a by-value array indexed by it would live in
+// scratch).
+__global__ __launch_bounds__(256) void k_ndt_pyr_assoc(const double *__restrict__ pts, const int *__restrict__ n_dev, int cap,
+                                                        const NdtPyrLevel *__restrict__ levels, int n_levels, int neighbours,
+                                                        const double *__restrict__ T, const int *__restrict__ state,
+                                                        double *__restrict__ partial) {
+  __shared__ NdtAssocLds lds;
+  if (state[0]) return;
+  const int l = __builtin_amdgcn_readfirstlane(min(max(state[1], 0), n_levels - 1));
+  const NdtPyrLevel d = levels[l];
+  ndt_assoc_body(pts, n_dev, cap, d.m, d.gs, neighbours, T, partial, lds);
+}
+
+// Launch B, one workgroup of 256.  After a step at level l that level's count of used slots goes up; a converged step
+// (|v| < tol_t and |omega| < tol_r) ends the call with status 0 on the last level and hands the pose to level l + 1
+// otherwise; a step that is not converged does the same once the level has used its cap, except that the status stays 1.
+// Status 2 and 3 are final at any level.  status = (code, slots used, count of the last live slot, its level).
+__global__ __launch_bounds__(256) void k_ndt_pyr_solve(const double *__restrict__ partial, const int *__restrict__ n_dev, int cap,
+                                                        int slot, int n_levels, NdtPyrCaps caps, int min_corr, double tol_t,
+                                                        double tol_r, LocPose T_init, double *__restrict__ T,
+                                                        int *__restrict__ status, int *__restrict__ state,
+                                                        double *__restrict__ trace, double *__restrict__ normal,
+                                                        int *__restrict__ level) {
+  __shared__ double seg[LOC_SEG][32];
+  __shared__ double tot[32];
+  if (state[0]) return;
+  const int n = min(cap, max(*n_dev, 0));
+  loc_sum_rows(partial, (n + LOC_PTS - 1) / LOC_PTS, threadIdx.x, seg, tot);
+  if (threadIdx.x != 0) return;
+  const int l = min(max(state[1], 0), n_levels - 1);
+  level[slot] = l;
+  status[3] = l;
+  double vn, th;
+  if (loc_solve_step(tot, slot, min_corr, T_init.m, T, status, trace, normal, vn, th) >= 0) {
+    state[0] = 1;
+    return;
+  }
+  const int used = state[2 + l] + 1;
+  state[2 + l] = used;
+  const int cap_l = l == 0 ? caps.v[0] : (l == 1 ? caps.v[1] : (l == 2 ? caps.v[2] : caps.v[3]));
+  const bool last = l == n_levels - 1;
+  if (vn < tol_t && th < tol_r) {
+    if (last) {
+      status[0] = 0;
+      state[0] = 1;
+    } else {
+      state[1] = l + 1;
+    }
+  } else if (used >= cap_l) {
+    if (last)
+      state[0] = 1;
+    else
+      state[1] = l + 1;
+  }
+}
+
+#pragma clang fp contract(fast)

@@ -152,6 +152,7 @@ int fail(int code, const char *fmt, ...) {
 #include "ndt_batch_kernels.inc.h"
 #include "ndt_search_kernels.inc.h"
 #include "ndt_update_kernels.inc.h"
+#include "ndt_pyramid_kernels.inc.h"
 
 // ------------------------------------------------------------------------------------------
 // context
@@ -308,6 +309,9 @@ struct sps_ctx {
   NdtMap ndt{};
   std::vector<void *> ndt_allocs;
   NdtDyn ndt_dyn{};                      // capacity > 0: the map is dynamic (sps_ndt_map_build_dynamic)
+  // NDT pyramid (sps_ndt_pyramid_build): static maps of its own beside the one above, coarse to fine
+  NdtPyramid ndt_pyr{};
+  std::vector<void *> ndt_pyr_allocs;
   // variant-A item scratch (sps_radius_item): per (scan point, neighbour cell) hit counts and their prefix sums
   int *item_counts = nullptr, *item_offsets = nullptr, *item_bsum = nullptr, *item_base = nullptr;
   int64_t item_cap = 0;
@@ -1059,6 +1063,7 @@ int sps_ctx_destroy(sps_ctx *c) {
   if (c->map_keys_alloc) (void)hipFree(c->map_keys_alloc);
   for (void *p : c->rg_allocs) (void)hipFree(p);
   for (void *p : c->ndt_allocs) (void)hipFree(p);
+  for (void *p : c->ndt_pyr_allocs) (void)hipFree(p);
   for (void *p : {(void *)c->item_counts, (void *)c->item_offsets, (void *)c->item_bsum, (void *)c->item_base}) (void)hipFree(p);
   delete c;
   return SPS_OK;
@@ -2259,5 +2264,6 @@ int sps_get_feature(sps_ctx *c, const char *name, float *out_dev, int64_t *rows,
 #include "ndt_batch_host.inc.h"
 #include "ndt_search_host.inc.h"
 #include "ndt_update_host.inc.h"
+#include "ndt_pyramid_host.inc.h"
 
 }  // extern "C"

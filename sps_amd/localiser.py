@@ -29,6 +29,10 @@ for a pose known to a few metres and a few tens of degrees only.
 moments for up to N cells, and ``integrate`` / ``submit(..., integrate=True)`` fold a frame's thinned points into them at
 a host pose or at the frame's own corrected pose, on the frame's stream and gated by its status on the device.
 
+``NDTLocaliser(..., resolutions=(2.0, 1.0, 0.5))`` registers coarse to fine (C ABI: "NDT localiser, multi-resolution
+pyramid"): one static map per resolution beside the single one, and ``submit`` / ``submit_filtered`` /
+``__call__`` run one alignment that starts on the coarsest map and hands its pose to the next finer one on the device.
+
 ``LocalisationLoop`` closes the loop for any of the seven filters of scripts/filter_sequence.py, around either localiser.
 """
 from __future__ import annotations
@@ -58,6 +62,7 @@ class PoseResult:
     normal: np.ndarray = None  # [iterations, 28] H (upper triangle), b, sum d^2 -- only with with_normal=True
     n_points: int = 0          # scan points that entered the alignment (after thinning)
     map_update: object = None  # MapUpdateResult of the frame, with integrate=True
+    levels: np.ndarray = None  # [iterations] int, the pyramid level every slot ran at (None without a pyramid)
 
     @property
     def ok(self) -> bool:
@@ -92,9 +97,10 @@ class PendingMapUpdate:
 class PendingPose:
     """A localisation whose work has been issued; everything lives on the device until result()."""
 
-    def __init__(self, iters, with_normal, host, event, keep, upd_at=None):
+    def __init__(self, iters, with_normal, host, event, keep, upd_at=None, levels_at=None):
         self._iters, self._with_normal, self._host, self._event, self._keep = iters, with_normal, host, event, keep
         self._upd_at = upd_at                                        # doubles in front of the map update's info words
+        self._levels_at = levels_at                                  # doubles in front of a pyramid's per-slot levels
 
     def result(self) -> PoseResult:
         self._event.synchronize()                                    # the one host synchronisation
@@ -106,7 +112,10 @@ class PendingPose:
         normal = h[19 + 4 * K:19 + 32 * K].reshape(K, 28)[:it].copy() if self._with_normal else None
         rmse = math.sqrt(trace[-1, 1] / n_corr) if it and n_corr > 0 else float("nan")
         upd = None if self._upd_at is None else _map_update_of(h[self._upd_at:self._upd_at + 2].view(np.int32), n_points)
-        return PoseResult(h[:16].reshape(4, 4).copy(), code, it, n_corr, rmse, trace, normal, n_points, upd)
+        levels = None
+        if self._levels_at is not None:
+            levels = h[self._levels_at:self._levels_at + (K + 1) // 2].view(np.int32)[:it].astype(np.int64)
+        return PoseResult(h[:16].reshape(4, 4).copy(), code, it, n_corr, rmse, trace, normal, n_points, upd, levels)
 
 
 @dataclass
@@ -183,6 +192,7 @@ def pose_grid(along, across, yaw_deg) -> np.ndarray:
 MAX_HYPOTHESES = 64            # SPS_NDT_MAX_HYP
 MAX_POSES = 65536              # SPS_NDT_MAX_POSES
 MAX_UPDATE_POINTS = 65536      # SPS_NDT_UPDATE_MAX_POINTS
+MAX_LEVELS = 4                 # SPS_NDT_PYR_MAX_LEVELS
 
 
 def _checked_poses(poses, what="poses"):
@@ -346,17 +356,22 @@ class ScanToMapLocaliser:
             n_dev = self._count_on_device(count, n_max)
             # one float64 buffer per frame: T_out[16] | status int32[4] | n_points int32 (+ pad) | trace[K][4] | normal[K][28]
             size = 19 + 32 * K if with_normal else 19 + 4 * K
-            out = torch.zeros(size + 2 if integrate else size, dtype=torch.float64, device=dev)   # | info int32[4]
+            pyramid = getattr(self, "resolutions", None) is not None
+            # | info int32[4] with integrate, or | level int32[K] (+ pad) with a pyramid (never both)
+            out = torch.zeros(size + (2 if integrate else (K + 1) // 2 if pyramid else 0), dtype=torch.float64, device=dev)
             base = out.data_ptr()
             self._thin(rows, n_dev, n_max, base + 18 * 8, s)
+            kw = dict(level_ptr=base + size * 8 if K else None) if pyramid else {}
             self._align(base + 18 * 8, T, K, base, base + 16 * 8, base + 19 * 8 if K else None,
-                        base + (19 + 4 * K) * 8 if with_normal and K else None, s)
+                        base + (19 + 4 * K) * 8 if with_normal and K else None, s, **kw)
             if integrate:
                 self._update(base + 18 * 8, None, base, base + 16 * 8, max_cell_points, base + size * 8, s)
             host, ev = self._to_host(out, st)
-        return PendingPose(K, with_normal, host, ev, (rows, n_dev, out), size if integrate else None)
+        return PendingPose(K, with_normal, host, ev, (rows, n_dev, out), size if integrate else None, size if pyramid else None)
 
     def _check_integrate(self, integrate, max_cell_points=0):
+        if integrate and getattr(self, "resolutions", None) is not None:
+            raise ValueError("integrate needs a single-resolution localiser: the online map has no pyramid")
         if integrate and getattr(self, "cell_capacity", None) is None:
             raise ValueError("integrate needs a localiser with an online map: NDTLocaliser(..., cell_capacity=N)")
         if integrate and int(max_cell_points) < 0:
@@ -381,13 +396,22 @@ class NDTLocaliser(ScanToMapLocaliser):
     localiser's own; a scan point is scored against its own cell and, with ``neighbours=7``, the six face neighbours.
     ``submit``, ``submit_filtered`` and ``__call__`` are ScanToMapLocaliser's.  In the result ``n_corr`` counts the scan
     points with at least one contributing cell, ``trace[:, 1]`` and ``normal[:, 27]`` hold the NDT score
-    sum -d1 exp(-d2 s / 2) (larger is better) and ``rmse`` is sqrt(score / n_corr), not a distance."""
+    sum -d1 exp(-d2 s / 2) (larger is better) and ``rmse`` is sqrt(score / n_corr), not a distance.
+
+    ``resolutions`` (None: no pyramid; up to 4 cell edges, strictly decreasing, e.g. ``(2.0, 1.0, 0.5)``): one more static
+    map per entry, and ``submit`` / ``submit_filtered`` / ``__call__`` then register coarse to fine in one call.
+    ``iterations`` is the budget of slots (one slot = one iteration at some level) and ``level_iterations`` the most slots
+    each level may use (None: ``iterations`` each).  A level hands its pose to the next when it converges or has used its
+    slots; only the last level's convergence is status 0, and the result's ``levels`` tells the level of every slot.
+    Status 2 / 3 at any level are final and give the guess back.  ``submit_batch``, ``score_poses``, ``relocalise`` and
+    ``map_cells`` keep using the single map of edge ``resolution``; ``pyramid_cells(level)`` shows a level."""
 
     def __init__(self, map_points, resolution: float = 1.0, neighbours: int = 7, leaf: float = 0.2, iterations: int = 30,
                  min_correspondences: int = 50, min_points_per_cell: int = 6, outlier_ratio: float = 0.55,
                  eig_ratio: float = 0.01, tol_t: float = 1e-4, tol_r: float = 1e-5, device="cuda", capacity: int = 1 << 16,
-                 cell_capacity: int = None):
+                 cell_capacity: int = None, resolutions=None, level_iterations=None):
         from .datasets.blt_dataset import radius_grid_cells
+        self.resolutions, self.level_iterations = self._checked_pyramid(resolutions, level_iterations, cell_capacity)
         if cell_capacity is not None and (int(cell_capacity) < 1 or capacity > MAX_UPDATE_POINTS):
             raise ValueError(f"cell_capacity must be >= 1 and, with it, capacity <= {MAX_UPDATE_POINTS}")
         if not (math.isfinite(resolution) and resolution > 0 and math.isfinite(leaf) and leaf > 0):
@@ -424,13 +448,56 @@ class NDTLocaliser(ScanToMapLocaliser):
                 self.ctx.ndt_map_build_dynamic(*args, self.cell_capacity, self.stream.cuda_stream)
                 self._update_scratch = torch.empty(_native.lib.sps_ndt_map_update_scratch(self.capacity), dtype=torch.uint8,
                                                    device=self.device)
+            self.level_cells = None
+            if self.resolutions is not None:
+                levels, keep = [], []                                # one radius_grid_cells call per level
+                for r in self.resolutions:
+                    if self.n_map:
+                        k, st_, p = radius_grid_cells(xyz, r)
+                        k = k.contiguous()
+                        keep.append((k, st_, p))
+                        levels.append((k.data_ptr(), st_.data_ptr(), p.data_ptr(), len(k), r))
+                    else:
+                        levels.append((None, None, None, 0, r))
+                self.level_cells = tuple(lv[3] for lv in levels)
+                self.ctx.ndt_pyramid_build(levels, xyz.data_ptr() if self.n_map else None, self.n_map, self.min_points_per_cell,
+                                           self.eig_ratio, self.outlier_ratio, self.stream.cuda_stream)
+                self._pyr_scratch = torch.empty(_native.lib.sps_ndt_pyramid_align_scratch(self.capacity), dtype=torch.uint8,
+                                                device=self.device)
             self._pts = torch.empty((self.capacity, 3), dtype=torch.float64, device=self.device)
             self._align_scratch = torch.empty(_native.lib.sps_ndt_align_scratch(self.capacity), dtype=torch.uint8, device=self.device)
             self._ds_scratch, self._ds_rows = None, -1
             self._batch_scratch, self._batch_hyp = None, 0
             self._score_scratch, self._score_poses = None, 0
 
-    def _align(self, n_ptr, T, K, T_out_ptr, status_ptr, trace_ptr, normal_ptr, s):
+    @staticmethod
+    def _checked_pyramid(resolutions, level_iterations, cell_capacity):
+        """(resolutions as a tuple of floats or None, level_iterations as a tuple of ints or None), before any device work"""
+        if resolutions is None:
+            if level_iterations is not None:
+                raise ValueError("level_iterations needs resolutions")
+            return None, None
+        if cell_capacity is not None:
+            raise ValueError("resolutions and cell_capacity exclude each other: the online map is single-resolution")
+        res = tuple(float(r) for r in resolutions)
+        if not 1 <= len(res) <= MAX_LEVELS:
+            raise ValueError(f"resolutions must have 1 to {MAX_LEVELS} entries")
+        if not all(math.isfinite(r) and r > 0 for r in res) or any(b >= a for a, b in zip(res, res[1:])):
+            raise ValueError("resolutions must be finite, > 0 and strictly decreasing")
+        if level_iterations is None:
+            return res, None
+        caps = tuple(int(v) for v in level_iterations)
+        if len(caps) != len(res) or min(caps) < 1:
+            raise ValueError("level_iterations needs one entry >= 1 per resolution")
+        return res, caps
+
+    def _align(self, n_ptr, T, K, T_out_ptr, status_ptr, trace_ptr, normal_ptr, s, level_ptr=None):
+        if self.resolutions is not None:
+            caps = self.level_iterations or (max(K, 1),) * len(self.resolutions)
+            self.ctx.ndt_pyramid_align(self._pts.data_ptr(), n_ptr, self.capacity, T, K, caps, self.neighbours,
+                                       self.min_correspondences, self.tol_t, self.tol_r, T_out_ptr, status_ptr, trace_ptr,
+                                       normal_ptr, level_ptr, self._pyr_scratch.data_ptr(), s)
+            return
         self.ctx.ndt_align(self._pts.data_ptr(), n_ptr, self.capacity, T, K, self.neighbours, self.min_correspondences,
                            self.outlier_ratio, self.tol_t, self.tol_r, T_out_ptr, status_ptr, trace_ptr, normal_ptr,
                            self._align_scratch.data_ptr(), s)
@@ -603,6 +670,24 @@ class NDTLocaliser(ScanToMapLocaliser):
         n = C if self.cell_capacity is None else self.ctx.ndt_map_info()[0]
         return (key.cpu().numpy().view(np.uint64)[:n], cnt.cpu().numpy()[:n], mean.cpu().numpy()[:n], icov.cpu().numpy()[:n],
                 valid.cpu().numpy().astype(bool)[:n])
+
+    def pyramid_cells(self, level: int):
+        """Debug: ``map_cells()`` of level ``level`` of the pyramid (0: the coarsest)."""
+        if self.resolutions is None:
+            raise ValueError("pyramid_cells needs a localiser with resolutions")
+        if not 0 <= int(level) < len(self.resolutions):
+            raise ValueError(f"level must be in [0, {len(self.resolutions)})")
+        C = self.level_cells[int(level)]
+        with torch.cuda.device(self.device):
+            key = torch.zeros(C, dtype=torch.int64, device=self.device)
+            cnt = torch.zeros(C, dtype=torch.int32, device=self.device)
+            mean = torch.zeros((C, 3), dtype=torch.float64, device=self.device)
+            icov = torch.zeros((C, 6), dtype=torch.float64, device=self.device)
+            valid = torch.zeros(C, dtype=torch.int32, device=self.device)
+            self.ctx.ndt_pyramid_cells(int(level), key.data_ptr(), cnt.data_ptr(), mean.data_ptr(), icov.data_ptr(),
+                                       valid.data_ptr())
+        return (key.cpu().numpy().view(np.uint64), cnt.cpu().numpy(), mean.cpu().numpy(), icov.cpu().numpy(),
+                valid.cpu().numpy().astype(bool))
 
 
 @dataclass

@@ -22,6 +22,9 @@ around it) against K back-to-back submit calls from the same poses, and against 
 ``--localiser ndt --search P`` times NDTLocaliser.score_poses of P poses against ceil(P / 64) calls of
 submit_batch(iterations=0) over the same poses and checks that the two agree bit for bit.
 
+``--localiser ndt --resolutions 2,1,0.5`` times the coarse-to-fine pyramid (NDTLocaliser(..., resolutions=...)) beside the
+single-map localiser on the same frames in one session: per-frame time, live and idle slots, and the map builds.
+
 ``--localiser ndt --update-map`` times the online map (NDTLocaliser(..., cell_capacity=N)): sps_ndt_map_update alone and
 submit(integrate=True) against submit, interleaved frame by frame with the only alternative a static map offers, a new
 NDTLocaliser over map + frame.
@@ -115,7 +118,13 @@ def main():
                     "ceil(P / 64) submit_batch(iterations=0) calls, the only way to score poses without it")
     ap.add_argument("--update-map", action="store_true", help="with --localiser ndt: time the online map's update against "
                     "rebuilding the localiser over map + frame")
+    ap.add_argument("--resolutions", type=str, default=None, help="with --localiser ndt: R0,R1,... time the coarse-to-fine "
+                    "pyramid beside the single-map localiser, in the same session")
+    ap.add_argument("--iterations", type=int, default=30, help="with --resolutions: the pyramid's budget of slots")
+    ap.add_argument("--level-iterations", type=str, default=None, help="with --resolutions: N0,N1,... the cap of every level")
     a = ap.parse_args()
+    if a.resolutions and (a.localiser != "ndt" or a.hypotheses or a.search or a.update_map):
+        ap.error("--resolutions needs --localiser ndt and none of --hypotheses, --search, --update-map")
     if a.update_map and a.localiser != "ndt":
         ap.error("--update-map needs --localiser ndt")
     if a.search and (a.localiser != "ndt" or not 1 <= a.search <= 65536):
@@ -135,6 +144,8 @@ def main():
         return ndt_search_main(a, dscans, mp, T_init)
     if a.localiser == "ndt" and a.hypotheses:
         return ndt_batch_main(a, dscans, mp, T_init)
+    if a.localiser == "ndt" and a.resolutions:
+        return ndt_pyramid_main(a, dscans, mp, T_init)
     if a.localiser == "ndt":
         return ndt_main(a, scans, dscans, mp, T_init)
     loc = ScanToMapLocaliser(mp[:, :3])
@@ -258,6 +269,62 @@ def ndt_main(a, scans, dscans, mp, T_init):
         out[name]["loop_sps_cvm_ms"] = round(float(np.median(t_loop)) * 1e3, 4)
         out[name]["loop_flagged_frames"] = int(flagged)
         print(f"LocalisationLoop(sps_cvm, {name}) {out[name]['loop_sps_cvm_ms']:.3f} ms per frame ({flagged} flagged)", flush=True)
+    print(json.dumps(out))
+
+
+def ndt_pyramid_main(a, dscans, mp, T_init):
+    """--resolutions: the pyramid localiser and the single-map one on the same frames, alternating in blocks within one
+    session, from the tool's usual start and from a start 0.5 m behind along the corridor (the case the pyramid is for).
+    Per frame: hipEvent time around submit(), the live slots (those that did work) and the idle ones (budget - live, whose
+    launches return at once), the slots per level, the error against the true pose.  Then the build times: every level's
+    map alone (a single-map localiser at that resolution) and the pyramid localiser (its single map + the levels)."""
+    res = tuple(float(v) for v in a.resolutions.split(","))
+    caps = tuple(int(v) for v in a.level_iterations.split(",")) if a.level_iterations else None
+    map64 = mp[:, :3].astype(np.float64)
+    ScanToMapLocaliser(map64[:1000])                                  # first context of the process: not part of a build time
+    single, single_build = build_ms(lambda: NDTLocaliser(map64))
+    pyr, pyr_build = build_ms(lambda: NDTLocaliser(map64, resolutions=res, iterations=a.iterations, level_iterations=caps))
+    level_build = []
+    for r in res:
+        one, ms = build_ms(lambda: NDTLocaliser(map64, resolution=r))
+        level_build.append({"resolution": r, "cells": one.n_cells, "ms": round(ms, 3)})
+        del one
+    out = {"n_map": len(mp), "frames": a.frames, "warmup": a.warmup, "resolutions": res, "budget": a.iterations,
+           "level_iterations": caps, "level_cells": pyr.level_cells,
+           "build_ms": {"single": round(single_build, 3), "pyramid_localiser": round(pyr_build, 3), "levels": level_build}}
+    st = torch.cuda.current_stream()
+    for start_name, T0 in (("usual", T_init), ("lag_0.5m", LR.perturbation(0.5, 0.0, 0.0, 0.0))):
+        rec = {"single": [], "pyramid": []}
+        for k in range(a.warmup + a.frames):
+            s = dscans[k % len(dscans)]
+            for name, loc in (("single", single), ("pyramid", pyr)):   # alternating: both see the same machine state
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record(st)
+                pend = loc.submit(s, len(s), T0)
+                e1.record(st)
+                r = pend.result()
+                e1.synchronize()
+                if k >= a.warmup:
+                    lv = np.bincount(r.levels, minlength=len(res)) if r.levels is not None else None
+                    rec[name].append((e0.elapsed_time(e1), r.iterations, r.status, LR.pose_difference(r.pose, np.eye(4))[0], lv))
+        out[start_name] = {}
+        for name, rows in rec.items():
+            ms, live = [v[0] for v in rows], [v[1] for v in rows]
+            budget = a.iterations if name == "pyramid" else single.iterations
+            d = {"ms": {"median": round(float(np.median(ms)), 4), "min": round(min(ms), 4), "max": round(max(ms), 4)},
+                 "live_slots": {"median": float(np.median(live)), "min": min(live), "max": max(live)},
+                 "idle_slots_median": float(budget - np.median(live)),
+                 "status_counts": {str(c): int(sum(v[2] == c for v in rows)) for c in sorted({v[2] for v in rows})},
+                 "error_m": {"median": round(float(np.median([v[3] for v in rows])), 5), "max": round(max(v[3] for v in rows), 5)}}
+            if name == "pyramid":
+                d["slots_per_level_median"] = [float(x) for x in np.median(np.stack([v[4] for v in rows]), axis=0)]
+            out[start_name][name] = d
+            print(f"{start_name:9s} {name:8s} median {d['ms']['median']:.3f} ms (min {d['ms']['min']:.3f} max {d['ms']['max']:.3f}) per "
+                  f"frame, live slots median {d['live_slots']['median']:.0f} of {budget} (idle {d['idle_slots_median']:.0f}), status "
+                  f"{d['status_counts']}, error median {d['error_m']['median']:.4f} m max {d['error_m']['max']:.4f} m"
+                  + (f", slots per level {d['slots_per_level_median']}" if name == "pyramid" else ""), flush=True)
+    print("map builds (host grouping included): single localiser " + f"{single_build:.2f} ms, pyramid localiser {pyr_build:.2f} ms; "
+          + ", ".join(f"{b['resolution']} m: {b['ms']:.2f} ms ({b['cells']} cells)" for b in level_build))
     print(json.dumps(out))
 
 
