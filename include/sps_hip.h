@@ -648,6 +648,57 @@ int sps_ndt_map_update(sps_ctx *ctx, const double *pts_dev, const int32_t *n_dev
                        void *scratch_dev, void *stream);
 int sps_ndt_map_info(sps_ctx *ctx, int64_t *out_host);
 
+/* ---- NDT localiser, online map: free-space carving ---------------------------------------------------------------------
+ * The other half of a changed scene: what disappeared.  Every point of a frame is the end of a ray from the sensor; a
+ * Gaussian that rays pass straight through, frame after frame, while no ray ends in its cell is cleared (the ray-tracing
+ * update of NDT occupancy maps, Saarinen et al., reduced to integer counts).    Additive: sps_version() is
+ * unchanged.
+ *
+ * Per-cell state: a map built by sps_ndt_map_build_dynamic also holds three int32[cell_capacity] arrays, zero after the
+ *   build: pass and hit, the counts of the last carve whose gate was open, and miss, the consecutive carves in which the
+ *   cell was seen through.  sps_ndt_map_build drops them with the rest of the dynamic state.
+ * sps_ndt_map_carve: pts_dev, n_dev, cap, T_host, T_dev and gate_dev are sps_ndt_map_update's and are checked as there
+ *   (cap <= SPS_NDT_UPDATE_MAX_POINTS; a map built by sps_ndt_map_build is refused with INVALID).  end_margin >= 0 and
+ *   finite, through_sigma > 0 and finite, min_pass >= 1, miss_frames >= 1, 1 <= max_steps <= 4096, else INVALID.
+ *   Gate: unless *gate_dev holds 0 or 1 (NULL: open) no byte of the map and none of the three arrays changes and
+ *   info_dev = (0, 0, 0, 0).  With the gate open pass and hit are first set to 0 for every cell.
+ *     Ray i < min(cap, *n_dev): origin o = (T[3], T[7], T[11]), end q = ((r0*x + r1*y) + r2*z) + t of point i, direction
+ *       d = q - o per axis.  The ray is skipped, and not counted, if a coordinate of q or o is not finite or the cell of q
+ *       or of o (floor(v / resolution) per axis, a true division) leaves +-1048575.  Otherwise it is cast: the cell of q,
+ *       if the map's hash has it with a cell id in range, gets hit += 1.  L = sqrt((dx*dx + dy*dy) + dz*dz).  L <=
+ *       end_margin: nothing is traversed.  Otherwise s_end = 1 - end_margin / L.
+ *     Traversal (Amanatides-Woo in the ray parameter s in [0, s_end)): the start cell c is the cell of o; per axis
+ *       step_a = sign(d_a), tMax_a = ((c_a + (step_a > 0)) * resolution - o_a) / d_a, tDelta_a = resolution / |d_a|, and
+ *       tMax_a = tDelta_a = +inf where d_a = 0.  s_in = 0.  Each step: (1) the axis of the smallest tMax, ties to the lowest
+ *       axis index; (2) the current cell covers [s_in, s_out], s_out = min(tMax_axis, s_end); (3) the cell is evaluated over
+ *       that segment; (4) stop if tMax_axis >= s_end; (5) stop after max_steps cells, the ray then counts as cut;
+ *       (6) c_axis += step_axis, and a cell index beyond +-1048575 ends the ray (not cut); s_in = tMax_axis,
+ *       tMax_axis += tDelta_axis.
+ *     Evaluation: a cell that is not in the map, or whose record is not valid (a valid record has count >= 2), does
+ *       nothing; the record is read only.  With A the record's inverse covariance and mu its mean: y = A d (row i as
+ *       (A_i0*d0 + A_i1*d1) + A_i2*d2), a = d . y, b = y . (mu - o), s* = b / a.  If not a > 0, or s* is NaN, the ray does
+ *       not pass.  Otherwise s = min(max(s*, s_in), s_out), x = (o + s*d) - mu per axis, l = x . (A x), and the ray passes
+ *       iff l <= through_sigma * through_sigma (one product, on the host).  Every dot product is (u0*v0 + u1*v1) + u2*v2,
+ *       every operation is rounded on its own.  A passing ray does pass[cell] += 1.
+ *     Decision, per assigned cell with count > 0 and a valid record: hit >= 1 sets miss = 0; else pass >= min_pass does
+ *       miss += 1 and the cell counts as seen through; else miss keeps its value.  Then miss >= miss_frames clears the
+ *       cell: count = 0, the six entries of S are 0.0, the 80-byte record is all zero (valid = 0), miss = 0.  A cleared
+ *       cell keeps its key, its hash entry and its cell id: capacity is NOT reclaimed.  A later sps_ndt_map_update that
+ *       puts points into it takes its stored-n = 0 branch, so the refilled cell has the bits of a founded cell.  Every
+ *       other cell keeps every bit, miss included.
+ *   info_dev int32[4] = (rays cast, cells seen through, cells cleared, rays cut at max_steps).  The results are integer
+ *   counts and comparisons of individually rounded doubles: they depend on the set of rays and the pose only, not on the
+ *   order of the rays or of the threads.  Three launches whatever the data; the only atomics are integer adds.
+ *   scratch_dev: sps_ndt_map_carve_scratch(cap) bytes, which is 0 (scratch_dev may be NULL; -1 for cap out of range).
+ *   Never allocates, never synchronises, never raises the sticky error.
+ * sps_ndt_map_carve_cells: debug -- pass, hit and miss, cell_capacity entries each (any output may be NULL).
+ *   Synchronises. */
+int64_t sps_ndt_map_carve_scratch(int64_t cap);
+int sps_ndt_map_carve(sps_ctx *ctx, const double *pts_dev, const int32_t *n_dev, int64_t cap, const double *T_host,
+                      const double *T_dev, const int32_t *gate_dev, double end_margin, double through_sigma, int min_pass,
+                      int miss_frames, int max_steps, int32_t *info_dev, void *scratch_dev, void *stream);
+int sps_ndt_map_carve_cells(sps_ctx *ctx, int32_t *pass_out_dev, int32_t *hit_out_dev, int32_t *miss_out_dev);
+
 /* ---- NDT localiser, multi-resolution pyramid --------------------------------------------------------------------------
  * One alignment registered coarse to fine: coarse cells give a wide basin, fine cells the accuracy, and the pose is handed
  * from level to level on the device, so the host issues the same launches whatever the data does.    Additive:

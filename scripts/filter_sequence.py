@@ -136,11 +136,12 @@ def hypothesis_grid(counts, steps, option="--hypotheses", step_option="--hypothe
 
 
 def closed_loop(name, f, pc_map, replay, finish, traj_out, which="icp", hypotheses=None, search=None, update_map=False,
-                cell_capacity=None, max_cell_points=0, resolutions=None, level_iterations=None):
+                cell_capacity=None, max_cell_points=0, resolutions=None, level_iterations=None, carve_map=False,
+                carve_options=None):
     """--localise: one LocalisationLoop step per frame, scored against the replayed poses."""
     from sps_amd.localiser import LocalisationLoop, NDTLocaliser, ScanToMapLocaliser
     from sps_amd.trajectory import ape_translation, rotation_angle, write_trajectory
-    if update_map:                                               # an online map: room for twice the map's cells by default
+    if update_map or carve_map:                                  # an online map: room for twice the map's cells by default
         n_cells = NDTLocaliser(pc_map[:, :3]).n_cells
         localiser = NDTLocaliser(pc_map[:, :3], cell_capacity=cell_capacity or max(2 * n_cells, 4096))
     elif resolutions is not None:                                # coarse to fine; hypotheses and search keep the single map
@@ -153,7 +154,7 @@ def closed_loop(name, f, pc_map, replay, finish, traj_out, which="icp", hypothes
         T = map_tr @ pose
         if loop is None:
             loop = LocalisationLoop(f, localiser, T, hypotheses=hypotheses, search=search, update_map=update_map,
-                                    max_cell_points=max_cell_points)
+                                    max_cell_points=max_cell_points, carve_map=carve_map, carve_options=carve_options)
         step = loop.step(scan)
         finish(stamp, None, step.filter_result)
         p = step.pose_result
@@ -167,6 +168,9 @@ def closed_loop(name, f, pc_map, replay, finish, traj_out, which="icp", hypothes
         if u is not None:
             print(f"[{stamp}] map: {u.cells:d} cells | founded {u.founded:d} dropped {u.dropped:d} | {u.points:d} of {u.n_points:d} "
                   f"points integrated")
+        c = step.batch.map_carve if step.batch is not None else p.map_carve
+        if c is not None:
+            print(f"[{stamp}] carve: {c.rays:d} rays | seen through {c.seen_through:d} cleared {c.cleared:d} | cut {c.cut:d}")
         if step.search is not None:
             r = step.search
             print(f"[{stamp}] search: pose {r.index:d} of {len(r.scores):d} | candidates " + " ".join(str(int(k)) for k in r.candidates)
@@ -208,16 +212,35 @@ def closed_loop(name, f, pc_map, replay, finish, traj_out, which="icp", hypothes
 @click.option("--update-map", "update_map", is_flag=True,
               help="with --localiser ndt: fold every frame's kept points into the NDT map at its corrected pose")
 @click.option("--cell-capacity", "cell_capacity", type=int, default=None,
-              help="with --update-map: cells the online map has room for (default: twice the map's, at least 4096)")
+              help="with --update-map or --carve-map: cells the online map has room for (default: twice the map's, at least 4096)")
 @click.option("--max-cell-points", "max_cell_points", type=int, default=0,
               help="with --update-map: cap on the weight of a cell's history (0: none)")
+@click.option("--carve-map", "carve_map", is_flag=True,
+              help="with --localiser ndt: cast every frame's kept points as rays from its corrected pose and clear the cells "
+                   "of the NDT map that they keep passing through")
+@click.option("--carve-miss-frames", "carve_miss_frames", type=int, default=None,
+              help="with --carve-map: consecutive frames a cell must be seen through before it is cleared (default: 3)")
+@click.option("--carve-sigma", "carve_sigma", type=float, default=None,
+              help="with --carve-map: a ray passes through a cell within this many standard deviations of its mean (default: 1)")
 @click.option("--resolutions", "resolutions", type=str, default=None,
               help="with --localiser ndt: R0,R1,... cell edges in m, strictly decreasing (at most 4): register coarse to fine")
 @click.option("--level-iterations", "level_iterations", type=str, default=None,
               help="with --resolutions: N0,N1,... the most iterations each level may use (default: 30 each); their sum is the "
                    "frame's budget")
 def main(name, weights, sequence, config, epsilon, out_dir, n_synth, localise, which, traj_out, hyp_counts, hyp_steps,
-         search_counts, search_steps, update_map, cell_capacity, max_cell_points, resolutions, level_iterations):
+         search_counts, search_steps, update_map, cell_capacity, max_cell_points, carve_map, carve_miss_frames, carve_sigma,
+         resolutions, level_iterations):
+    if carve_map and which != "ndt":
+        raise click.UsageError("--carve-map needs --localise --localiser ndt")
+    if carve_map and resolutions is not None:
+        raise click.UsageError("--resolutions and --carve-map exclude each other: the online map is single-resolution")
+    if (carve_miss_frames is not None or carve_sigma is not None) and not carve_map:
+        raise click.UsageError("--carve-miss-frames and --carve-sigma need --carve-map")
+    carve_options = {}
+    if carve_miss_frames is not None:
+        carve_options["miss_frames"] = carve_miss_frames
+    if carve_sigma is not None:
+        carve_options["through_sigma"] = carve_sigma
     if resolutions is not None and which != "ndt":
         raise click.UsageError("--resolutions needs --localise --localiser ndt")
     if resolutions is not None and update_map:
@@ -231,8 +254,10 @@ def main(name, weights, sequence, config, epsilon, out_dir, n_synth, localise, w
         raise click.UsageError("--resolutions takes numbers, --level-iterations integers, separated by commas")
     if update_map and which != "ndt":
         raise click.UsageError("--update-map needs --localise --localiser ndt")
-    if (cell_capacity is not None or max_cell_points) and not update_map:
-        raise click.UsageError("--cell-capacity and --max-cell-points need --update-map")
+    if max_cell_points and not update_map:
+        raise click.UsageError("--max-cell-points needs --update-map")
+    if cell_capacity is not None and not (update_map or carve_map):
+        raise click.UsageError("--cell-capacity needs --update-map or --carve-map")
     if which is not None and not localise:
         raise click.UsageError("--localiser needs --localise")
     if hyp_counts is not None and which != "ndt":
@@ -277,7 +302,7 @@ def main(name, weights, sequence, config, epsilon, out_dir, n_synth, localise, w
 
     if localise:
         closed_loop(name, f, pc_map, replay, finish, traj_out, which or "icp", hypotheses, search, update_map, cell_capacity,
-                    max_cell_points, resolutions, level_iterations)
+                    max_cell_points, resolutions, level_iterations, carve_map, carve_options or None)
     elif traj_out:
         raise click.UsageError("--traj-out needs --localise")
     in_flight, prev_pose = None, None

@@ -144,6 +144,9 @@ def _load() -> C.CDLL:
         "sps_ndt_map_update_scratch": (i64, [i64]),
         "sps_ndt_map_update": (i32, [vp, vp, vp, i64, vp, vp, vp, i32, vp, vp, vp]),
         "sps_ndt_map_info": (i32, [vp, vp]),
+        "sps_ndt_map_carve_scratch": (i64, [i64]),
+        "sps_ndt_map_carve": (i32, [vp, vp, vp, i64, vp, vp, vp, C.c_double, C.c_double, i32, i32, i32, vp, vp, vp]),
+        "sps_ndt_map_carve_cells": (i32, [vp, vp, vp, vp]),
         "sps_ndt_pyramid_build": (i32, [vp, i32, vp, vp, vp, vp, vp, vp, i64, i32, C.c_double, C.c_double, vp]),
         "sps_ndt_pyramid_cells": (i32, [vp, i32, vp, vp, vp, vp, vp]),
         "sps_ndt_pyramid_align_scratch": (i64, [i64]),
@@ -180,6 +183,7 @@ EXPORTS = ["sps_last_error", "sps_version", "sps_ctx_create", "sps_ctx_destroy",
            "sps_ndt_align_batch_scratch", "sps_ndt_align_batch",
            "sps_ndt_score_scratch", "sps_ndt_score_poses", "sps_ndt_top_poses",
            "sps_ndt_map_build_dynamic", "sps_ndt_map_update_scratch", "sps_ndt_map_update", "sps_ndt_map_info",
+           "sps_ndt_map_carve_scratch", "sps_ndt_map_carve", "sps_ndt_map_carve_cells",
            "sps_ndt_pyramid_build", "sps_ndt_pyramid_cells", "sps_ndt_pyramid_align_scratch", "sps_ndt_pyramid_align"]
 CROP_BLOCK = 1024          # SPS_CROP_BLOCK: map rows per int of sps_radius_crop's scratch
 
@@ -486,6 +490,18 @@ class Context:
         out = (C.c_int64 * 4)()
         check(lib.sps_ndt_map_info(self.handle, out))
         return int(out[0]), int(out[1]), int(out[2])
+
+    # ---- free-space carving (include/sps_hip.h, "NDT localiser, online map: free-space carving") ----
+    def ndt_map_carve(self, pts_ptr, n_dev_ptr: int, cap: int, T_host, T_dev_ptr, gate_ptr, end_margin: float,
+                      through_sigma: float, min_pass: int, miss_frames: int, max_steps: int, info_ptr: int, scratch_ptr,
+                      stream: int):
+        check(lib.sps_ndt_map_carve(self.handle, pts_ptr, n_dev_ptr, int(cap), self._mat(T_host) if T_host is not None else None,
+                                    T_dev_ptr, gate_ptr, float(end_margin), float(through_sigma), int(min_pass), int(miss_frames),
+                                    int(max_steps), info_ptr, scratch_ptr, stream))
+
+    def ndt_map_carve_cells(self, pass_ptr, hit_ptr, miss_ptr):
+        """pass, hit and miss of every cell of the capacity into int32 device arrays (any may be None); synchronises"""
+        check(lib.sps_ndt_map_carve_cells(self.handle, pass_ptr, hit_ptr, miss_ptr))
 
     # ---- NDT localiser, multi-resolution pyramid (include/sps_hip.h, "NDT localiser, multi-resolution pyramid") ----
     def ndt_pyramid_build(self, levels, xyz_ptr, n_map: int, min_points: int, eig_ratio: float, outlier_ratio: float,

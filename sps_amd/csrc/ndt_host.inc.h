@@ -56,8 +56,9 @@ inline int ndt_map_check_args(const sps_ctx *c, const uint64_t *cell_keys_dev, c
 }
 
 // One cell map from checked arguments, its memory added to `allocs`: the hash, the records, the counts and the keys (and
-// for a dynamic map the moments S and the update's per-cell state), filled on stream st.  Does not synchronise: state0 (the
-// caller's, four words) is read by a copy still in flight on return.  m and d are written only on success.
+// for a dynamic map the moments S, the update's per-cell state and the carving's three counters), filled on stream st.
+// Does not synchronise: state0 (the caller's, four words) is read by a copy still in flight on return.  m and d are
+// written only on success.
 int ndt_map_make(std::vector<void *> &allocs, const uint64_t *cell_keys_dev, const int32_t *cell_start_dev,
                  const int32_t *cell_pts_dev, const double *map_xyz_dev, int64_t n_cells, int64_t n_map, double resolution,
                  int min_points, double eig_ratio, bool dynamic, int64_t cell_capacity, hipStream_t st, int32_t *state0,
@@ -86,6 +87,7 @@ int ndt_map_make(std::vector<void *> &allocs, const uint64_t *cell_keys_dev, con
     d.capacity = (int)cell_capacity, d.min_points = min_points, d.eig_ratio = eig_ratio;
     d.S = (double *)alloc(C * 6 * 8), d.bcnt = (int *)alloc(C * 4), d.lead = (int *)alloc(C * 4);
     d.cstart = (int *)alloc(C * 4), d.state = (int *)alloc(16);
+    d.pass = (int *)alloc(C * 4), d.hit = (int *)alloc(C * 4), d.miss = (int *)alloc(C * 4);
   }
   if (nomem) return fail(SPS_ERR_NOMEM, "hipMalloc for the NDT map failed");
   HIP_TRY(hipMemsetAsync(m.h.keys, 0xFF, (size_t)hcap * 8, st));
@@ -99,6 +101,9 @@ int ndt_map_make(std::vector<void *> &allocs, const uint64_t *cell_keys_dev, con
     HIP_TRY(hipMemsetAsync(d.bcnt, 0, C * 4, st));
     HIP_TRY(hipMemsetAsync(d.lead, 0x7F, C * 4, st));
     HIP_TRY(hipMemsetAsync(d.cstart, 0, C * 4, st));
+    HIP_TRY(hipMemsetAsync(d.pass, 0, C * 4, st));
+    HIP_TRY(hipMemsetAsync(d.hit, 0, C * 4, st));
+    HIP_TRY(hipMemsetAsync(d.miss, 0, C * 4, st));
     HIP_TRY(hipMemcpyAsync(d.state, state0, 4 * sizeof(int32_t), hipMemcpyHostToDevice, st));
   }
   if (n_cells > 0) {

@@ -28,14 +28,18 @@ struct NdtDyn {
   int capacity;            // 0: the map of this context is static
   int min_points;
   double eig_ratio;
-  double *rec;             // the arrays of NdtMap, writable
-  int *count;
+  double *rec;             // the arrays of NdtMap, writable.  Invariant kept by every writer (ndt_record_from_moments: valid
+  int *count;              // needs n >= 2; the carve's clear zeroes record and count together): rec valid => count >= 2, so
+                           // a reader that skips records that are not valid (k_ndt_carve_rays) also skips count = 0
   uint64_t *keys;
   double *S;               // [capacity][6] sum (p - mean)(p - mean)^T (xx, xy, xz, yy, yz, zz)
   int *bcnt;               // [capacity] points of the cell in the running update (0 between updates)
   int *lead;               // [capacity] lowest point index of the cell in the running update (NDT_UPD_NONE between updates)
   int *cstart;             // [capacity] offset of the cell's list in the running update
   int *state;              // [0] cells assigned, [1] cells dropped for capacity since the build
+  int *pass;               // [capacity] carving (ndt_carve_kernels.inc.h): rays through the cell's Gaussian, last open carve
+  int *hit;                // [capacity] carving: rays that ended in the cell, last open carve
+  int *miss;               // [capacity] carving: consecutive carves in which the cell was seen through
 };
 
 // the caller's scratch for one update of at most `cap` points

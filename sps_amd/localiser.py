@@ -28,6 +28,9 @@ for a pose known to a few metres and a few tens of degrees only.
 ``NDTLocaliser(..., cell_capacity=N)`` keeps an online map (C ABI: "NDT localiser, online map"): per-cell
 moments for up to N cells, and ``integrate`` / ``submit(..., integrate=True)`` fold a frame's thinned points into them at
 a host pose or at the frame's own corrected pose, on the frame's stream and gated by its status on the device.
+``carve`` / ``submit(..., carve=True)`` do the opposite for what left the scene (C ABI: "NDT localiser, online map: free-space
+carving"): the frame's points are the ends of rays from the sensor, and a cell whose Gaussian such rays pass
+through for ``miss_frames`` frames on end while none ends in it is cleared.
 
 ``NDTLocaliser(..., resolutions=(2.0, 1.0, 0.5))`` registers coarse to fine (C ABI: "NDT localiser, multi-resolution
 pyramid"): one static map per resolution beside the single one, and ``submit`` / ``submit_filtered`` /
@@ -63,6 +66,7 @@ class PoseResult:
     n_points: int = 0          # scan points that entered the alignment (after thinning)
     map_update: object = None  # MapUpdateResult of the frame, with integrate=True
     levels: np.ndarray = None  # [iterations] int, the pyramid level every slot ran at (None without a pyramid)
+    map_carve: object = None   # MapCarveResult of the frame, with carve=True
 
     @property
     def ok(self) -> bool:
@@ -82,6 +86,35 @@ def _map_update_of(words, n_points) -> MapUpdateResult:
     return MapUpdateResult(int(words[0]), int(words[1]), int(words[2]), int(words[3]), int(n_points))
 
 
+@dataclass
+class MapCarveResult:
+    rays: int                  # rays cast: the offered points whose end and origin have a cell; 0 where the gate was closed
+    seen_through: int          # valid cells that rays passed through (>= min_pass of them) while none ended there
+    cleared: int               # cells cleared by this carve (seen through miss_frames times on end)
+    cut: int                   # rays stopped at max_steps cells before they reached their end margin
+    n_points: int = 0          # points that were offered (after thinning)
+
+
+def _map_carve_of(words, n_points) -> MapCarveResult:
+    return MapCarveResult(int(words[0]), int(words[1]), int(words[2]), int(words[3]), int(n_points))
+
+
+CARVE_DEFAULTS = dict(end_margin=None, through_sigma=1.0, min_pass=2, miss_frames=3, max_steps=512)
+MAX_CARVE_STEPS = 4096
+
+
+class PendingMapCarve:
+    """A carve whose work has been issued; ``result()`` -> MapCarveResult."""
+
+    def __init__(self, host, event, keep):
+        self._host, self._event, self._keep = host, event, keep
+
+    def result(self) -> MapCarveResult:
+        self._event.synchronize()                                    # the one host synchronisation
+        h = self._host.numpy()
+        return _map_carve_of(h[4:8], h[0])
+
+
 class PendingMapUpdate:
     """A map update whose work has been issued; ``result()`` -> MapUpdateResult."""
 
@@ -97,10 +130,11 @@ class PendingMapUpdate:
 class PendingPose:
     """A localisation whose work has been issued; everything lives on the device until result()."""
 
-    def __init__(self, iters, with_normal, host, event, keep, upd_at=None, levels_at=None):
+    def __init__(self, iters, with_normal, host, event, keep, upd_at=None, levels_at=None, carve_at=None):
         self._iters, self._with_normal, self._host, self._event, self._keep = iters, with_normal, host, event, keep
         self._upd_at = upd_at                                        # doubles in front of the map update's info words
         self._levels_at = levels_at                                  # doubles in front of a pyramid's per-slot levels
+        self._carve_at = carve_at                                    # doubles in front of the carve's info words
 
     def result(self) -> PoseResult:
         self._event.synchronize()                                    # the one host synchronisation
@@ -115,7 +149,8 @@ class PendingPose:
         levels = None
         if self._levels_at is not None:
             levels = h[self._levels_at:self._levels_at + (K + 1) // 2].view(np.int32)[:it].astype(np.int64)
-        return PoseResult(h[:16].reshape(4, 4).copy(), code, it, n_corr, rmse, trace, normal, n_points, upd, levels)
+        carved = None if self._carve_at is None else _map_carve_of(h[self._carve_at:self._carve_at + 2].view(np.int32), n_points)
+        return PoseResult(h[:16].reshape(4, 4).copy(), code, it, n_corr, rmse, trace, normal, n_points, upd, levels, carved)
 
 
 @dataclass
@@ -126,15 +161,17 @@ class BatchPoseResult:
     best: int                  # the hypothesis selected, or -1 where none has status 0 / 1 and enough points counted
     pose: np.ndarray           # 4x4: results[best].pose, or the first start pose when best is -1
     map_update: object = None  # MapUpdateResult of the frame, with integrate=True
+    map_carve: object = None   # MapCarveResult of the frame, with carve=True
 
 
 class PendingPoses:
     """A batch of localisations whose work has been issued; everything lives on the device until result()."""
 
-    def __init__(self, n_hyp, iters, with_normal, host, event, keep, at=0, upd=False):
+    def __init__(self, n_hyp, iters, with_normal, host, event, keep, at=0, upd=False, carve=False):
         self._n_hyp, self._iters, self._with_normal, self._host, self._event, self._keep = n_hyp, iters, with_normal, host, event, keep
         self._at = at                                                # doubles in front of the batch's part of the buffer
         self._upd = upd                                              # the map update's info words follow the batch's part
+        self._carve = carve                                          # the carve's info words come last
 
     def result(self) -> BatchPoseResult:
         self._event.synchronize()                                    # the one host synchronisation
@@ -156,8 +193,10 @@ class PendingPoses:
             results.append(PoseResult(T_out[k].copy(), code, it, n_corr, rmse, tr,
                                       normal[k, :it].copy() if normal is not None else None, n_points))
         upd = _map_update_of(h[o["size"]:o["size"] + 2].view(np.int32), n_points) if self._upd else None
+        cat = o["size"] + (2 if self._upd else 0)
+        carved = _map_carve_of(h[cat:cat + 2].view(np.int32), n_points) if self._carve else None
         return BatchPoseResult(results, final[:, 0].copy(), final[:, 1].astype(np.int64), int(best[0]),
-                               h[o["T_best"]:o["T_best"] + 16].reshape(4, 4).copy(), upd)
+                               h[o["T_best"]:o["T_best"] + 16].reshape(4, 4).copy(), upd, carved)
 
 
 def _batch_layout(K, I, with_normal):
@@ -223,6 +262,7 @@ class RelocalisationResult:
     index: int                 # the grid index of the selected alignment's start pose, or -1 where none was selected
     pose: np.ndarray           # 4x4: batch.pose
     map_update: object = None  # MapUpdateResult of the frame, with integrate=True (batch.map_update)
+    map_carve: object = None   # MapCarveResult of the frame, with carve=True (batch.map_carve)
 
     @property
     def ok(self) -> bool:
@@ -256,7 +296,8 @@ class PendingRelocalisation:
         cand = h[o["top"]:o["top"] + (K + 1) // 2].view(np.int32)[:K].astype(np.int64)
         batch = b.result()
         index = int(cand[batch.best]) if batch.best >= 0 else -1
-        return RelocalisationResult(sc[:, 0].copy(), sc[:, 1].astype(np.int64), cand, batch, index, batch.pose, batch.map_update)
+        return RelocalisationResult(sc[:, 0].copy(), sc[:, 1].astype(np.int64), cand, batch, index, batch.pose, batch.map_update,
+                                    batch.map_carve)
 
 
 class ScanToMapLocaliser:
@@ -338,12 +379,16 @@ class ScanToMapLocaliser:
 
     @torch.no_grad()
     def submit(self, rows, count, T_init, with_normal: bool = False, iterations: int = None, integrate: bool = False,
-               max_cell_points: int = 0) -> PendingPose:
+               max_cell_points: int = 0, carve: bool = False, carve_options: dict = None) -> PendingPose:
         """rows: device tensor [n_max, >= 3] (float32; other dtypes are converted); count: an int or a device int32 tensor
         holding the number of valid rows; T_init: 4x4.  Issued on the current stream.  ``integrate`` (a localiser with an
         online map only): the thinned points are then folded into the map at the corrected pose, behind the alignment on
-        the same stream and only where its status is 0 or 1; the result's ``map_update`` tells what happened."""
+        the same stream and only where its status is 0 or 1; the result's ``map_update`` tells what happened.  ``carve``
+        (the same localisers; ``carve_options``: the keywords of ``NDTLocaliser.carve``): the thinned points are cast as
+        rays from the corrected pose and the map is carved, behind the alignment, under the same gate and before the
+        update, so a cell cleared and observed again in one frame is refilled by it; the result's ``map_carve`` tells."""
         self._check_integrate(integrate, max_cell_points)
+        copts = self._check_carve(carve, carve_options)
         rows = self._checked_rows(rows)
         T = _pose(T_init)
         if T is None or not np.isfinite(T).all():
@@ -358,16 +403,22 @@ class ScanToMapLocaliser:
             size = 19 + 32 * K if with_normal else 19 + 4 * K
             pyramid = getattr(self, "resolutions", None) is not None
             # | info int32[4] with integrate, or | level int32[K] (+ pad) with a pyramid (never both)
-            out = torch.zeros(size + (2 if integrate else (K + 1) // 2 if pyramid else 0), dtype=torch.float64, device=dev)
+            # | info int32[4] of the carve, last
+            carve_at = size + (2 if integrate else 0)
+            out = torch.zeros(size + (2 if integrate else (K + 1) // 2 if pyramid else 0) + (2 if carve else 0), dtype=torch.float64,
+                              device=dev)
             base = out.data_ptr()
             self._thin(rows, n_dev, n_max, base + 18 * 8, s)
             kw = dict(level_ptr=base + size * 8 if K else None) if pyramid else {}
             self._align(base + 18 * 8, T, K, base, base + 16 * 8, base + 19 * 8 if K else None,
                         base + (19 + 4 * K) * 8 if with_normal and K else None, s, **kw)
+            if carve:
+                self._carve(base + 18 * 8, None, base, base + 16 * 8, copts, base + carve_at * 8, s)
             if integrate:
                 self._update(base + 18 * 8, None, base, base + 16 * 8, max_cell_points, base + size * 8, s)
             host, ev = self._to_host(out, st)
-        return PendingPose(K, with_normal, host, ev, (rows, n_dev, out), size if integrate else None, size if pyramid else None)
+        return PendingPose(K, with_normal, host, ev, (rows, n_dev, out), size if integrate else None, size if pyramid else None,
+                           carve_at if carve else None)
 
     def _check_integrate(self, integrate, max_cell_points=0):
         if integrate and getattr(self, "resolutions", None) is not None:
@@ -376,6 +427,30 @@ class ScanToMapLocaliser:
             raise ValueError("integrate needs a localiser with an online map: NDTLocaliser(..., cell_capacity=N)")
         if integrate and int(max_cell_points) < 0:
             raise ValueError("max_cell_points must be >= 0")
+
+    def _check_carve(self, carve, carve_options=None):
+        """the carve's options with the defaults filled in (None without ``carve``), before any device work"""
+        if not carve:
+            if carve_options is not None:
+                raise ValueError("carve_options needs carve=True")
+            return None
+        if getattr(self, "resolutions", None) is not None:
+            raise ValueError("carve needs a single-resolution localiser: the online map has no pyramid")
+        if getattr(self, "cell_capacity", None) is None:
+            raise ValueError("carve needs a localiser with an online map: NDTLocaliser(..., cell_capacity=N)")
+        unknown = set(carve_options or ()) - set(CARVE_DEFAULTS)
+        if unknown:
+            raise ValueError(f"unknown carve options {sorted(unknown)}")
+        o = dict(CARVE_DEFAULTS, **(carve_options or {}))
+        if o["end_margin"] is None:
+            o["end_margin"] = self.resolution
+        o["end_margin"], o["through_sigma"] = float(o["end_margin"]), float(o["through_sigma"])
+        o["min_pass"], o["miss_frames"], o["max_steps"] = int(o["min_pass"]), int(o["miss_frames"]), int(o["max_steps"])
+        if not (math.isfinite(o["end_margin"]) and o["end_margin"] >= 0 and math.isfinite(o["through_sigma"]) and o["through_sigma"] > 0):
+            raise ValueError("end_margin must be finite and >= 0, through_sigma finite and > 0")
+        if o["min_pass"] < 1 or o["miss_frames"] < 1 or not 1 <= o["max_steps"] <= MAX_CARVE_STEPS:
+            raise ValueError(f"min_pass and miss_frames must be >= 1 and max_steps in [1, {MAX_CARVE_STEPS}]")
+        return o
 
     def _align(self, n_ptr, T, K, T_out_ptr, status_ptr, trace_ptr, normal_ptr, s):
         self.ctx.loc_align(self._pts.data_ptr(), n_ptr, self.capacity, T, K, self.min_correspondences, self.tol_t, self.tol_r,
@@ -506,6 +581,51 @@ class NDTLocaliser(ScanToMapLocaliser):
         self.ctx.ndt_map_update(self._pts.data_ptr(), n_ptr, self.capacity, T_host, T_dev_ptr, gate_ptr, max_cell_points,
                                 info_ptr, self._update_scratch.data_ptr(), s)
 
+    def _carve(self, n_ptr, T_host, T_dev_ptr, gate_ptr, o, info_ptr, s):
+        self.ctx.ndt_map_carve(self._pts.data_ptr(), n_ptr, self.capacity, T_host, T_dev_ptr, gate_ptr, o["end_margin"],
+                               o["through_sigma"], o["min_pass"], o["miss_frames"], o["max_steps"], info_ptr, None, s)
+
+    @torch.no_grad()
+    def carve(self, rows, count, T, end_margin: float = None, through_sigma: float = 1.0, min_pass: int = 2, miss_frames: int = 3,
+              max_steps: int = 512) -> PendingMapCarve:
+        """Carve the online map with the rows as ray ends seen from the host pose ``T`` (4x4, sensor -> map): they are
+        thinned with the localiser's ``leaf`` as ``submit`` thins them; every ray gives the cell it ends in a hit and walks
+        the cells from the sensor to ``end_margin`` (None: ``resolution``) before its end, at most ``max_steps`` of them,
+        and passes through a valid cell where it comes within ``through_sigma`` standard deviations of the cell's Gaussian.
+        A cell with no hit and at least ``min_pass`` passing rays was seen through; ``miss_frames`` such frames on end clear
+        it (count 0, not valid) until an update refills it; a hit starts the count again.  Issued on the current stream;
+        ``result()`` -> MapCarveResult."""
+        o = self._check_carve(True, dict(end_margin=end_margin, through_sigma=through_sigma, min_pass=min_pass,
+                                         miss_frames=miss_frames, max_steps=max_steps))
+        rows = self._checked_rows(rows)
+        Th = _pose(T)
+        if Th is None or not np.isfinite(Th).all():
+            raise ValueError("T must be a finite 4x4 matrix")
+        n_max, dev = rows.shape[0], self.device
+        with torch.cuda.device(dev):
+            st = torch.cuda.current_stream()
+            s = st.cuda_stream
+            n_dev = self._count_on_device(count, n_max)
+            out = torch.zeros(8, dtype=torch.int32, device=dev)      # n_points (+ pad) | info[4]
+            base = out.data_ptr()
+            self._thin(rows, n_dev, n_max, base, s)
+            self._carve(base, Th, None, None, o, base + 16, s)
+            host, ev = self._to_host(out, st)
+        return PendingMapCarve(host, ev, (rows, n_dev, out))
+
+    def carve_state(self):
+        """Debug: (pass, hit, miss) int32 arrays of the online map's assigned cells, in the order of ``map_cells()``: the
+        rays that passed through and that ended in every cell in the last carve whose gate was open, and the consecutive
+        carves in which the cell was seen through.  Synchronises."""
+        self._check_carve(True)
+        C = self.cell_capacity
+        with torch.cuda.device(self.device):
+            out = torch.zeros((3, C), dtype=torch.int32, device=self.device)
+            self.ctx.ndt_map_carve_cells(out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr())
+        n = self.ctx.ndt_map_info()[0]
+        h = out.cpu().numpy()
+        return h[0, :n].copy(), h[1, :n].copy(), h[2, :n].copy()
+
     @torch.no_grad()
     def integrate(self, rows, count, T, max_cell_points: int = 0) -> PendingMapUpdate:
         """Fold the rows into the online map at the host pose ``T`` (4x4, sensor -> map): they are thinned with the
@@ -536,13 +656,14 @@ class NDTLocaliser(ScanToMapLocaliser):
 
     @torch.no_grad()
     def submit_batch(self, rows, count, T_inits, with_normal: bool = False, iterations: int = None, integrate: bool = False,
-                     max_cell_points: int = 0) -> PendingPoses:
+                     max_cell_points: int = 0, carve: bool = False, carve_options: dict = None) -> PendingPoses:
         """``submit`` from the K start poses ``T_inits`` [K, 4, 4] (1 <= K <= 64) at once: the scan is thinned once, every
         hypothesis is registered as ``submit`` would register it from its pose, and the hypothesis with the highest NDT
         score at its final pose is selected among those with status 0 / 1 and at least ``min_correspondences`` points
         counted there (equal scores: the lowest index).  Issued on the current stream; ``result()`` -> BatchPoseResult.
-        ``integrate``: as for ``submit``, at the selected pose and only where a hypothesis was selected."""
+        ``integrate`` and ``carve``: as for ``submit``, at the selected pose and only where a hypothesis was selected."""
         self._check_integrate(integrate, max_cell_points)
+        copts = self._check_carve(carve, carve_options)
         rows = self._checked_rows(rows)
         T = np.ascontiguousarray(np.asarray(T_inits, dtype=np.float64))
         if T.ndim != 3 or T.shape[1:] != (4, 4) or not 1 <= len(T) <= MAX_HYPOTHESES or not np.isfinite(T).all():
@@ -556,26 +677,32 @@ class NDTLocaliser(ScanToMapLocaliser):
             n_dev = self._count_on_device(count, n_max)
             T_host = torch.from_numpy(T).pin_memory()
             T_dev = T_host.to(dev, non_blocking=True)                # on the caller's stream; both stay with the pending object
-            out = torch.zeros(o["size"] + 2 if integrate else o["size"], dtype=torch.float64, device=dev)   # | info int32[4]
+            # | info int32[4] of the update | info int32[4] of the carve
+            out = torch.zeros(o["size"] + (2 if integrate else 0) + (2 if carve else 0), dtype=torch.float64, device=dev)
             base = out.data_ptr()
             self._thin(rows, n_dev, n_max, base + o["n_points"] * 8, s)
-            self._align_batch(base + o["n_points"] * 8, T_dev.data_ptr(), K, I, with_normal, base, o, s, integrate, max_cell_points)
+            self._align_batch(base + o["n_points"] * 8, T_dev.data_ptr(), K, I, with_normal, base, o, s, integrate, max_cell_points,
+                              copts)
             host, ev = self._to_host(out, st)
-        return PendingPoses(K, I, with_normal, host, ev, (rows, n_dev, out, T_host, T_dev), upd=integrate)
+        return PendingPoses(K, I, with_normal, host, ev, (rows, n_dev, out, T_host, T_dev), upd=integrate, carve=carve)
 
     def submit_filtered_batch(self, pending, T_inits, **kw) -> PendingPoses:
         """``submit_batch`` of the kept rows of a pending SPSFilter / SPSCVMFilter frame, without the frame's result()."""
         return self.submit_batch(pending._filtered, pending.count_dev, T_inits, **kw)
 
-    def _align_batch(self, n_ptr, T_ptr, K, I, with_normal, base, o, s, integrate=False, max_cell_points=0):
+    def _align_batch(self, n_ptr, T_ptr, K, I, with_normal, base, o, s, integrate=False, max_cell_points=0, carve_opts=None):
         """the K alignments of self._pts from the device poses at T_ptr into the batch's buffer at ``base`` (layout ``o``);
-        ``integrate``: then the map update at the selected pose, its info words behind the batch's part"""
+        ``carve_opts``: then the carve at the selected pose, its info words last; ``integrate``: then the map update at the
+        selected pose, its info words behind the batch's part"""
         self.ctx.ndt_align_batch(self._pts.data_ptr(), n_ptr, self.capacity, T_ptr, K, I, self.neighbours,
                                  self.min_correspondences, self.outlier_ratio, self.tol_t, self.tol_r, base + o["T_out"] * 8,
                                  base + o["status"] * 8, base + o["trace"] * 8 if I else None,
                                  base + o["normal"] * 8 if with_normal and I else None, base + o["final"] * 8,
                                  base + o["best"] * 8, base + o["T_best"] * 8, self._batch_scratch_for(K).data_ptr(), s)
-        if integrate:                                                # best[1]: the selected hypothesis' status, -1 where none
+        if carve_opts is not None:                                   # best[1]: the selected hypothesis' status, -1 where none
+            self._carve(n_ptr, None, base + o["T_best"] * 8, base + o["best"] * 8 + 4, carve_opts,
+                        base + (o["size"] + (2 if integrate else 0)) * 8, s)
+        if integrate:
             self._update(n_ptr, None, base + o["T_best"] * 8, base + o["best"] * 8 + 4, max_cell_points, base + o["size"] * 8, s)
 
     def _batch_scratch_for(self, K):
@@ -617,13 +744,15 @@ class NDTLocaliser(ScanToMapLocaliser):
 
     @torch.no_grad()
     def relocalise(self, rows, count, poses, keep: int = 8, with_normal: bool = False, iterations: int = None,
-                   integrate: bool = False, max_cell_points: int = 0) -> PendingRelocalisation:
+                   integrate: bool = False, max_cell_points: int = 0, carve: bool = False,
+                   carve_options: dict = None) -> PendingRelocalisation:
         """Thin, score the P poses ``poses`` [P, 4, 4] (e.g. ``T_center @ pose_grid(...)``), keep the best ``keep`` (1..64)
         by (score descending, index ascending) among those with at least ``min_correspondences`` points counted, register
         from these as ``submit_batch`` does and select among the end poses as it selects.  Everything is issued on the
-        current stream with no synchronisation in between; ``result()`` -> RelocalisationResult.  ``integrate``: as for
-        ``submit_batch``."""
+        current stream with no synchronisation in between; ``result()`` -> RelocalisationResult.  ``integrate`` and
+        ``carve``: as for ``submit_batch``."""
         self._check_integrate(integrate, max_cell_points)
+        copts = self._check_carve(carve, carve_options)
         rows = self._checked_rows(rows)
         T = _checked_poses(poses)
         K = int(keep)
@@ -638,17 +767,17 @@ class NDTLocaliser(ScanToMapLocaliser):
             n_dev = self._count_on_device(count, n_max)
             T_host = torch.from_numpy(T).pin_memory()
             T_dev = T_host.to(dev, non_blocking=True)
-            out = torch.zeros(so["size"] + o["size"] + (2 if integrate else 0), dtype=torch.float64, device=dev)
+            out = torch.zeros(so["size"] + o["size"] + (2 if integrate else 0) + (2 if carve else 0), dtype=torch.float64, device=dev)
             sbase = out.data_ptr()
             base = sbase + so["size"] * 8
             n_ptr = base + o["n_points"] * 8
             self._score(rows, n_dev, n_max, T_dev, P, n_ptr, sbase + so["score"] * 8, s)
             self.ctx.ndt_top_poses(sbase + so["score"] * 8, T_dev.data_ptr(), P, self.min_correspondences, K,
                                    sbase + so["top"] * 8, sbase + so["T_top"] * 8, sbase + so["n_top"] * 8, s)
-            self._align_batch(n_ptr, sbase + so["T_top"] * 8, K, I, with_normal, base, o, s, integrate, max_cell_points)
+            self._align_batch(n_ptr, sbase + so["T_top"] * 8, K, I, with_normal, base, o, s, integrate, max_cell_points, copts)
             host, ev = self._to_host(out, st)
         return PendingRelocalisation(P, PendingPoses(K, I, with_normal, host, ev, (rows, n_dev, out, T_host, T_dev), so["size"],
-                                                     upd=integrate))
+                                                     upd=integrate, carve=carve))
 
     def relocalise_filtered(self, pending, poses, **kw) -> PendingRelocalisation:
         """``relocalise`` of the kept rows of a pending SPSFilter / SPSCVMFilter frame, without the frame's result()."""
@@ -731,10 +860,14 @@ class LocalisationLoop:
     thinned for the registration, are folded into the map at the frame's corrected pose, behind the registration on its
     stream.  The device gates the update on the registration's status, so a flagged frame leaves the map alone; the
     frame's ``pose_result.map_update`` (``batch.map_update``) tells what happened.  ``max_cell_points``: the forgetting
-    cap of ``NDTLocaliser.integrate``."""
+    cap of ``NDTLocaliser.integrate``.
+
+    ``carve_map`` (the same localisers): every frame's kept points are also cast as rays from the corrected pose and the
+    map is carved (``NDTLocaliser.carve``; ``carve_options``: its keywords), under the same gate and before the update;
+    the frame's ``pose_result.map_carve`` (``batch.map_carve``) tells what happened."""
 
     def __init__(self, filter, localiser, initial_pose, hypotheses=None, search=None, search_keep: int = 8,
-                 update_map: bool = False, max_cell_points: int = 0):
+                 update_map: bool = False, max_cell_points: int = 0, carve_map: bool = False, carve_options: dict = None):
         from .sps_filters import ConstantVelocityModel
         self.filter, self.localiser = filter, localiser
         self.update_map, self.max_cell_points = bool(update_map), int(max_cell_points)
@@ -742,6 +875,13 @@ class LocalisationLoop:
             raise ValueError("update_map needs a localiser with an online map: NDTLocaliser(..., cell_capacity=N)")
         # the keyword arguments every registration of the loop gets: none unless the map is updated
         self._kw = dict(integrate=True, max_cell_points=self.max_cell_points) if self.update_map else {}
+        self.carve_map = bool(carve_map)
+        if self.carve_map:
+            if getattr(localiser, "cell_capacity", None) is None:
+                raise ValueError("carve_map needs a localiser with an online map: NDTLocaliser(..., cell_capacity=N)")
+            self._kw.update(carve=True, carve_options=carve_options)
+        elif carve_options is not None:
+            raise ValueError("carve_options needs carve_map=True")
         self.hypotheses = None
         self.search, self.search_keep, self._search_next = None, int(search_keep), True
         if search is not None:

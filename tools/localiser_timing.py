@@ -10,7 +10,7 @@ synthetic.build_map() map, max_distance 1 m, leaf 0.2 m):
               SPSFilter alone on the same scans
 
     python tools/localiser_timing.py [--frames 200] [--warmup 20] [--cpu-frames 1] [--one-frame] [--cpu-only]
-                                     [--localiser {icp,ndt}] [--hypotheses K] [--search P] [--update-map]
+                                     [--localiser {icp,ndt}] [--hypotheses K] [--search P] [--update-map] [--carve]
 
 ``--localiser ndt`` times sps_amd.localiser.NDTLocaliser (1 m cells, 7 neighbours) on the same frames and from the same
 start, prints the ICP's per-frame figures of the same session beside it and the build time of both maps; the
@@ -28,6 +28,10 @@ single-map localiser on the same frames in one session: per-frame time, live and
 ``--localiser ndt --update-map`` times the online map (NDTLocaliser(..., cell_capacity=N)): sps_ndt_map_update alone and
 submit(integrate=True) against submit, interleaved frame by frame with the only alternative a static map offers, a new
 NDTLocaliser over map + frame.
+
+``--localiser ndt --carve`` times the free-space carving of the online map: sps_ndt_map_carve alone, sps_ndt_map_update alone,
+submit and submit(integrate=True, carve=True), interleaved frame by frame, and (with --cpu-frames >= 1) the restatement's
+count of the cells a ray visits on one frame.
 
 ``--one-frame`` runs a warm-up and ONE localiser frame: the target of a ``rocprofv3 --kernel-trace --stats`` run.
 """
@@ -118,13 +122,17 @@ def main():
                     "ceil(P / 64) submit_batch(iterations=0) calls, the only way to score poses without it")
     ap.add_argument("--update-map", action="store_true", help="with --localiser ndt: time the online map's update against "
                     "rebuilding the localiser over map + frame")
+    ap.add_argument("--carve", action="store_true", help="with --localiser ndt: time the online map's free-space carving beside "
+                    "its update and the registration")
     ap.add_argument("--resolutions", type=str, default=None, help="with --localiser ndt: R0,R1,... time the coarse-to-fine "
                     "pyramid beside the single-map localiser, in the same session")
     ap.add_argument("--iterations", type=int, default=30, help="with --resolutions: the pyramid's budget of slots")
     ap.add_argument("--level-iterations", type=str, default=None, help="with --resolutions: N0,N1,... the cap of every level")
     a = ap.parse_args()
-    if a.resolutions and (a.localiser != "ndt" or a.hypotheses or a.search or a.update_map):
-        ap.error("--resolutions needs --localiser ndt and none of --hypotheses, --search, --update-map")
+    if a.resolutions and (a.localiser != "ndt" or a.hypotheses or a.search or a.update_map or a.carve):
+        ap.error("--resolutions needs --localiser ndt and none of --hypotheses, --search, --update-map, --carve")
+    if a.carve and (a.localiser != "ndt" or a.hypotheses or a.search or a.update_map):
+        ap.error("--carve needs --localiser ndt and none of --hypotheses, --search, --update-map")
     if a.update_map and a.localiser != "ndt":
         ap.error("--update-map needs --localiser ndt")
     if a.search and (a.localiser != "ndt" or not 1 <= a.search <= 65536):
@@ -140,6 +148,8 @@ def main():
     T_init = LR.perturbation(0.15, 0.12, 0.05, 1.0)
     if a.localiser == "ndt" and a.update_map:
         return ndt_update_main(a, dscans, mp, T_init)
+    if a.localiser == "ndt" and a.carve:
+        return ndt_carve_main(a, scans, dscans, mp, T_init)
     if a.localiser == "ndt" and a.search:
         return ndt_search_main(a, dscans, mp, T_init)
     if a.localiser == "ndt" and a.hypotheses:
@@ -505,6 +515,77 @@ def ndt_update_main(a, dscans, mp, T_init):
     out["rebuild_over_update"] = round(out["rebuild_wall_ms"]["median"] / out["update_alone_ms"]["median"], 1)
     for name in ("submit_ms", "update_alone_ms", "submit_integrate_ms", "rebuild_wall_ms"):
         print(f"{name:22s} median {out[name]['median']:.4f} (min {out[name]['min']:.4f} max {out[name]['max']:.4f})", flush=True)
+    print(json.dumps(out))
+
+
+def ndt_carve_main(a, scans, dscans, mp, T_init):
+    """--carve: per frame, in one run and in this order (hipEvents around each): submit; sps_ndt_map_carve alone on the points
+    that submit left thinned, at the true pose; sps_ndt_map_update alone on the same points; submit(integrate=True,
+    carve=True).  The 12 scans come back, so the map and the carve's counters reach a steady state within the warm-up."""
+    from sps_amd.localiser import CARVE_DEFAULTS
+    map64 = mp[:, :3].astype(np.float64)
+    n_cells = NDTLocaliser(map64).n_cells
+    ndt = NDTLocaliser(map64, cell_capacity=2 * n_cells)
+    opts = ndt._check_carve(True, dict(CARVE_DEFAULTS))
+    st = torch.cuda.current_stream()
+    I4 = np.eye(4)
+    info = torch.zeros(8, dtype=torch.int32, device="cuda")
+    n_pts = torch.zeros(1, dtype=torch.int32, device="cuda")
+    if a.one_frame:
+        for k in range(a.warmup):
+            ndt.submit(dscans[k % len(dscans)], len(dscans[k % len(dscans)]), T_init, integrate=True, carve=True).result()
+        torch.cuda.synchronize()
+        s = dscans[a.warmup % len(dscans)]
+        r = ndt.submit(s, len(s), T_init, integrate=True, carve=True).result()
+        print(json.dumps({"one_frame": True, "localiser": "ndt", "carve": True, "status": r.status, "iterations": r.iterations,
+                          "n_points": r.n_points, "map_carve": vars(r.map_carve), "map_update": vars(r.map_update)}))
+        return
+    t = {"submit_ms": [], "carve_alone_ms": [], "update_alone_ms": [], "submit_integrate_carve_ms": []}
+    cut, cleared, last = 0, 0, None
+    for k in range(a.warmup + a.frames):
+        s = dscans[k % len(dscans)]
+        e = [torch.cuda.Event(enable_timing=True) for _ in range(8)]
+        e[0].record(st)
+        pend = ndt.submit(s, len(s), T_init)
+        e[1].record(st)
+        r = pend.result()
+        n_pts.fill_(r.n_points)
+        e[2].record(st)
+        ndt._carve(n_pts.data_ptr(), I4, None, None, opts, info.data_ptr(), st.cuda_stream)
+        e[3].record(st)
+        e[4].record(st)
+        ndt._update(n_pts.data_ptr(), I4, None, None, 0, info.data_ptr() + 16, st.cuda_stream)
+        e[5].record(st)
+        alone = info.cpu().numpy()
+        e[6].record(st)
+        pend = ndt.submit(s, len(s), T_init, integrate=True, carve=True)
+        e[7].record(st)
+        last = pend.result()
+        torch.cuda.synchronize()
+        if k >= a.warmup:
+            for i, name in enumerate(t):
+                t[name].append(e[2 * i].elapsed_time(e[2 * i + 1]))
+            cut += int(alone[3]) + last.map_carve.cut
+            cleared += int(alone[2]) + last.map_carve.cleared
+
+    def stats(v):
+        return {"median": round(float(np.median(v)), 4), "min": round(min(v), 4), "max": round(max(v), 4)}
+    out = {"frames": a.frames, "warmup": a.warmup, "n_map": len(mp), "cells_at_build": n_cells, "n_points": last.n_points,
+           "carve_options": opts, "map_info": ndt.map_info(), "last_carve": vars(last.map_carve), "rays_cut_in_all_timed_carves": cut,
+           "cells_cleared_in_all_timed_carves": cleared}
+    for name, v in t.items():
+        out[name] = stats(v)
+        print(f"{name:26s} median {out[name]['median']:.4f} (min {out[name]['min']:.4f} max {out[name]['max']:.4f})", flush=True)
+    if a.cpu_frames:
+        from tests import ndt_carve_reference as CR
+        from tests import ndt_update_reference as UR
+        sc = scans[a.warmup % len(scans)]
+        _, pts = LR.downsample(sc, len(sc), ndt.leaf, ndt.capacity)
+        visited = []
+        ref = CR.carve(UR.build(map64, 2 * n_cells), pts, I4, visited=visited)
+        out["restatement_one_frame"] = {"info": ref, "cells_per_ray_mean": round(float(np.mean(visited)), 2),
+                                        "cells_per_ray_max": int(max(visited))}
+        print(f"restatement, one frame on the built map: info {ref}, cells per ray mean {np.mean(visited):.2f} max {max(visited)}", flush=True)
     print(json.dumps(out))
 
 
