@@ -743,6 +743,52 @@ int sps_ndt_pyramid_align(sps_ctx *ctx, const double *pts_dev, const int32_t *n_
                           double *T_out_dev, int32_t *status_dev, double *trace_dev, double *normal_dev, int32_t *level_dev,
                           void *scratch_dev, void *stream);
 
+/* ---- NDT localiser, online pyramid ------------------------------------------------------------------------------------
+ * The pyramid above with the online map's two operations: every level is a dynamic map (moments, capacity, carve counters),
+ * and one call updates, one call carves, all levels in the same launches, the level being a grid dimension.  
+ * Additive: sps_version() is unchanged; the context's single map and every call above keep their behaviour and their bits.
+ *
+ * sps_ndt_pyramid_build_dynamic: sps_ndt_pyramid_build with cell_capacity (host int64[n_levels]).  Level l is the map that
+ *   sps_ndt_map_build_dynamic makes from the same arguments at resolution[l] with cell_capacity[l]: its first n_cells[l]
+ *   records, counts, keys, moments S and its state are those bits; the unassigned records are zero, their keys empty, and
+ *   pass / hit / miss are zero.  Every level is checked as sps_ndt_map_build_dynamic checks (cell_capacity[l] >=
+ *   max(n_cells[l], 1)).  n_map = 0 builds an empty pyramid to grow from.  Either pyramid build replaces whatever pyramid
+ *   the context had; neither touches the context's single map.  Allocates and synchronises.
+ *   sps_ndt_pyramid_align runs unchanged on dynamic levels (a level's n_cells is then its capacity, as for the single
+ *   dynamic map), and sps_ndt_pyramid_cells(level) writes cell_capacity[level] rows.
+ * sps_ndt_pyramid_update: sps_ndt_map_update on every level.  Level l ends with the bits that sps_ndt_map_update leaves on
+ *   a single dynamic map of resolution[l] and cell_capacity[l] given the same points, pose, gate and max_cell_points: every
+ *   byte of the records, counts, keys, S and state, and info_dev[l] (int32[n_levels][4], sps_ndt_map_update's four words per
+ *   level, coarsest first).  Pose and gate rules are sps_ndt_map_update's: T_dev wins over T_host where both are given;
+ *   gate_dev NULL or pointing at a status word that is 0 or 1 opens the gate (status_dev of sps_ndt_pyramid_align is a
+ *   valid gate); a closed gate changes no byte of any level and gives info (assigned, 0, 0, 0) per level.  A context whose
+ *   pyramid is static, or that has none, is refused with SPS_ERR_INVALID.
+ *   Launches: seven and two memsets, whatever n_levels and the data.  scratch_dev: sps_ndt_pyramid_update_scratch(cap,
+ *   n_levels) bytes (-1 for cap or n_levels out of range; cap <= SPS_NDT_UPDATE_MAX_POINTS), n_levels being the pyramid's.
+ *   Never allocates, never synchronises, never raises the sticky error.
+ * sps_ndt_pyramid_carve: sps_ndt_map_carve on every level, with end_margin a host double[n_levels] and info_dev
+ *   int32[n_levels][4].  Level l ends with the pass, hit, miss, map and info that sps_ndt_map_carve leaves on the single
+ *   map of that resolution with end_margin[l]; the other options are shared and checked as sps_ndt_map_carve checks them.
+ *   Launches: three, no memset, whatever n_levels.  sps_ndt_pyramid_carve_scratch is 0 (-1 out of range); scratch_dev may
+ *   be NULL.  Never allocates, never synchronises, never raises the sticky error.
+ * sps_ndt_pyramid_info: sps_ndt_map_info of level `level` (out_host int64[4]: assigned, capacity, dropped since the build,
+ *   0).  sps_ndt_pyramid_carve_cells: sps_ndt_map_carve_cells of level `level`, cell_capacity[level] entries each.  Both
+ *   are debug getters and synchronise. */
+int sps_ndt_pyramid_build_dynamic(sps_ctx *ctx, int n_levels, const uint64_t *const *cell_keys_dev,
+                                  const int32_t *const *cell_start_dev, const int32_t *const *cell_pts_dev, const int64_t *n_cells,
+                                  const double *resolution, const double *map_xyz_dev, int64_t n_map, int min_points,
+                                  double eig_ratio, double outlier_ratio, const int64_t *cell_capacity, void *stream);
+int64_t sps_ndt_pyramid_update_scratch(int64_t cap, int n_levels);
+int sps_ndt_pyramid_update(sps_ctx *ctx, const double *pts_dev, const int32_t *n_dev, int64_t cap, const double *T_host,
+                           const double *T_dev, const int32_t *gate_dev, int max_cell_points, int32_t *info_dev,
+                           void *scratch_dev, void *stream);
+int64_t sps_ndt_pyramid_carve_scratch(int64_t cap, int n_levels);
+int sps_ndt_pyramid_carve(sps_ctx *ctx, const double *pts_dev, const int32_t *n_dev, int64_t cap, const double *T_host,
+                          const double *T_dev, const int32_t *gate_dev, const double *end_margin, double through_sigma,
+                          int min_pass, int miss_frames, int max_steps, int32_t *info_dev, void *scratch_dev, void *stream);
+int sps_ndt_pyramid_info(sps_ctx *ctx, int level, int64_t *out_host);
+int sps_ndt_pyramid_carve_cells(sps_ctx *ctx, int level, int32_t *pass_out_dev, int32_t *hit_out_dev, int32_t *miss_out_dev);
+
 #ifdef __cplusplus
 }
 #endif

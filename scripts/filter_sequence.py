@@ -21,7 +21,9 @@ hdl_localization; not a port of it), the corrected pose goes back into the filte
 the result.  ``--localiser ndt`` registers with sps_amd.localiser.NDTLocaliser instead: the normal-distributions transform
 hdl_localization itself runs (1 m cells, DIRECT7), still without its UKF and IMU; with ``--resolutions 2,1,0.5`` it
 registers every frame coarse to fine over a pyramid of cell maps (``--level-iterations`` caps each level; a ``levels:``
-line then tells the iterations per level).  Frames then run one at a time; behind each frame's lines comes
+line then tells the iterations per level); with ``--update-map`` / ``--carve-map`` as well the pyramid is an online one
+(``--level-capacities``), every level is updated and carved in the same launches and the ``map`` / ``carve`` lines come once
+per level.  Frames then run one at a time; behind each frame's lines comes
 ``loc: status iterations n_corr rmse | err_t err_r`` (metres, degrees, against the replayed pose map_tr @ pose) and at
 the end the absolute pose error evo_ape prints by default.  ``--traj-out FILE`` writes the estimated trajectory
 (stamp + the top three rows of the pose per line).
@@ -137,11 +139,18 @@ def hypothesis_grid(counts, steps, option="--hypotheses", step_option="--hypothe
 
 def closed_loop(name, f, pc_map, replay, finish, traj_out, which="icp", hypotheses=None, search=None, update_map=False,
                 cell_capacity=None, max_cell_points=0, resolutions=None, level_iterations=None, carve_map=False,
-                carve_options=None):
+                carve_options=None, level_capacities=None):
     """--localise: one LocalisationLoop step per frame, scored against the replayed poses."""
     from sps_amd.localiser import LocalisationLoop, NDTLocaliser, ScanToMapLocaliser
     from sps_amd.trajectory import ape_translation, rotation_angle, write_trajectory
-    if update_map or carve_map:                                  # an online map: room for twice the map's cells by default
+    if resolutions is not None and (update_map or carve_map):    # an online pyramid: per level, room for twice its cells
+        caps = level_iterations or (30,) * len(resolutions)
+        if level_capacities is None:
+            xyz = np.ascontiguousarray(pc_map[:, :3], dtype=np.float64)
+            level_capacities = tuple(max(2 * len(np.unique(np.floor(xyz / r).astype(np.int64), axis=0)), 4096) for r in resolutions)
+        localiser = NDTLocaliser(pc_map[:, :3], resolutions=resolutions, iterations=sum(caps), level_iterations=caps,
+                                 level_capacities=level_capacities)
+    elif update_map or carve_map:                                # an online map: room for twice the map's cells by default
         n_cells = NDTLocaliser(pc_map[:, :3]).n_cells
         localiser = NDTLocaliser(pc_map[:, :3], cell_capacity=cell_capacity or max(2 * n_cells, 4096))
     elif resolutions is not None:                                # coarse to fine; hypotheses and search keep the single map
@@ -165,12 +174,14 @@ def closed_loop(name, f, pc_map, replay, finish, traj_out, which="icp", hypothes
         if p.levels is not None:
             print(f"[{stamp}] levels: slots per level " + " ".join(str(int((p.levels == l).sum())) for l in range(len(resolutions))))
         u = step.batch.map_update if step.batch is not None else p.map_update
-        if u is not None:
-            print(f"[{stamp}] map: {u.cells:d} cells | founded {u.founded:d} dropped {u.dropped:d} | {u.points:d} of {u.n_points:d} "
-                  f"points integrated")
+        for l, ul in enumerate(u if isinstance(u, tuple) else () if u is None else (u,)):   # an online pyramid: one per level
+            tag = f"map level {l}" if isinstance(u, tuple) else "map"
+            print(f"[{stamp}] {tag}: {ul.cells:d} cells | founded {ul.founded:d} dropped {ul.dropped:d} | {ul.points:d} of "
+                  f"{ul.n_points:d} points integrated")
         c = step.batch.map_carve if step.batch is not None else p.map_carve
-        if c is not None:
-            print(f"[{stamp}] carve: {c.rays:d} rays | seen through {c.seen_through:d} cleared {c.cleared:d} | cut {c.cut:d}")
+        for l, cl in enumerate(c if isinstance(c, tuple) else () if c is None else (c,)):
+            tag = f"carve level {l}" if isinstance(c, tuple) else "carve"
+            print(f"[{stamp}] {tag}: {cl.rays:d} rays | seen through {cl.seen_through:d} cleared {cl.cleared:d} | cut {cl.cut:d}")
         if step.search is not None:
             r = step.search
             print(f"[{stamp}] search: pose {r.index:d} of {len(r.scores):d} | candidates " + " ".join(str(int(k)) for k in r.candidates)
@@ -227,13 +238,14 @@ def closed_loop(name, f, pc_map, replay, finish, traj_out, which="icp", hypothes
 @click.option("--level-iterations", "level_iterations", type=str, default=None,
               help="with --resolutions: N0,N1,... the most iterations each level may use (default: 30 each); their sum is the "
                    "frame's budget")
+@click.option("--level-capacities", "level_capacities", type=str, default=None,
+              help="with --resolutions and --update-map or --carve-map: C0,C1,... cells every level of the online pyramid has "
+                   "room for (default per level: twice its cells, at least 4096)")
 def main(name, weights, sequence, config, epsilon, out_dir, n_synth, localise, which, traj_out, hyp_counts, hyp_steps,
          search_counts, search_steps, update_map, cell_capacity, max_cell_points, carve_map, carve_miss_frames, carve_sigma,
-         resolutions, level_iterations):
+         resolutions, level_iterations, level_capacities):
     if carve_map and which != "ndt":
         raise click.UsageError("--carve-map needs --localise --localiser ndt")
-    if carve_map and resolutions is not None:
-        raise click.UsageError("--resolutions and --carve-map exclude each other: the online map is single-resolution")
     if (carve_miss_frames is not None or carve_sigma is not None) and not carve_map:
         raise click.UsageError("--carve-miss-frames and --carve-sigma need --carve-map")
     carve_options = {}
@@ -243,15 +255,24 @@ def main(name, weights, sequence, config, epsilon, out_dir, n_synth, localise, w
         carve_options["through_sigma"] = carve_sigma
     if resolutions is not None and which != "ndt":
         raise click.UsageError("--resolutions needs --localise --localiser ndt")
-    if resolutions is not None and update_map:
-        raise click.UsageError("--resolutions and --update-map exclude each other: the online map is single-resolution")
     if level_iterations is not None and resolutions is None:
         raise click.UsageError("--level-iterations needs --resolutions")
+    if level_capacities is not None and resolutions is None:
+        raise click.UsageError("--level-capacities needs --resolutions")
+    if level_capacities is not None and not (update_map or carve_map):
+        raise click.UsageError("--level-capacities needs --update-map or --carve-map")
     try:
         resolutions = None if resolutions is None else tuple(float(v) for v in resolutions.split(","))
         level_iterations = None if level_iterations is None else tuple(int(v) for v in level_iterations.split(","))
+        level_capacities = None if level_capacities is None else tuple(int(v) for v in level_capacities.split(","))
     except ValueError:
-        raise click.UsageError("--resolutions takes numbers, --level-iterations integers, separated by commas")
+        raise click.UsageError("--resolutions takes numbers, --level-iterations and --level-capacities integers, separated by commas")
+    if resolutions is not None and (update_map or carve_map):
+        if cell_capacity is not None:
+            raise click.UsageError("--cell-capacity is the single map's: with --resolutions give --level-capacities")
+        if hyp_counts is not None or search_counts is not None:
+            raise click.UsageError("--resolutions with --update-map or --carve-map takes no --hypotheses and no --search: they "
+                                   "register on the single map, which stays static")
     if update_map and which != "ndt":
         raise click.UsageError("--update-map needs --localise --localiser ndt")
     if max_cell_points and not update_map:
@@ -302,7 +323,7 @@ def main(name, weights, sequence, config, epsilon, out_dir, n_synth, localise, w
 
     if localise:
         closed_loop(name, f, pc_map, replay, finish, traj_out, which or "icp", hypotheses, search, update_map, cell_capacity,
-                    max_cell_points, resolutions, level_iterations, carve_map, carve_options or None)
+                    max_cell_points, resolutions, level_iterations, carve_map, carve_options or None, level_capacities)
     elif traj_out:
         raise click.UsageError("--traj-out needs --localise")
     in_flight, prev_pose = None, None

@@ -152,6 +152,13 @@ def _load() -> C.CDLL:
         "sps_ndt_pyramid_align_scratch": (i64, [i64]),
         "sps_ndt_pyramid_align": (i32, [vp, vp, vp, i64, vp, i32, vp, i32, i32, C.c_double, C.c_double, vp, vp, vp, vp, vp, vp,
                                         vp]),
+        "sps_ndt_pyramid_build_dynamic": (i32, [vp, i32, vp, vp, vp, vp, vp, vp, i64, i32, C.c_double, C.c_double, vp, vp]),
+        "sps_ndt_pyramid_update_scratch": (i64, [i64, i32]),
+        "sps_ndt_pyramid_update": (i32, [vp, vp, vp, i64, vp, vp, vp, i32, vp, vp, vp]),
+        "sps_ndt_pyramid_carve_scratch": (i64, [i64, i32]),
+        "sps_ndt_pyramid_carve": (i32, [vp, vp, vp, i64, vp, vp, vp, vp, C.c_double, i32, i32, i32, vp, vp, vp]),
+        "sps_ndt_pyramid_info": (i32, [vp, i32, vp]),
+        "sps_ndt_pyramid_carve_cells": (i32, [vp, i32, vp, vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)          # AttributeError here = header/library mismatch: fail loudly
@@ -184,7 +191,9 @@ EXPORTS = ["sps_last_error", "sps_version", "sps_ctx_create", "sps_ctx_destroy",
            "sps_ndt_score_scratch", "sps_ndt_score_poses", "sps_ndt_top_poses",
            "sps_ndt_map_build_dynamic", "sps_ndt_map_update_scratch", "sps_ndt_map_update", "sps_ndt_map_info",
            "sps_ndt_map_carve_scratch", "sps_ndt_map_carve", "sps_ndt_map_carve_cells",
-           "sps_ndt_pyramid_build", "sps_ndt_pyramid_cells", "sps_ndt_pyramid_align_scratch", "sps_ndt_pyramid_align"]
+           "sps_ndt_pyramid_build", "sps_ndt_pyramid_cells", "sps_ndt_pyramid_align_scratch", "sps_ndt_pyramid_align",
+           "sps_ndt_pyramid_build_dynamic", "sps_ndt_pyramid_update_scratch", "sps_ndt_pyramid_update",
+           "sps_ndt_pyramid_carve_scratch", "sps_ndt_pyramid_carve", "sps_ndt_pyramid_info", "sps_ndt_pyramid_carve_cells"]
 CROP_BLOCK = 1024          # SPS_CROP_BLOCK: map rows per int of sps_radius_crop's scratch
 
 
@@ -505,14 +514,48 @@ class Context:
 
     # ---- NDT localiser, multi-resolution pyramid (include/sps_hip.h, "NDT localiser, multi-resolution pyramid") ----
     def ndt_pyramid_build(self, levels, xyz_ptr, n_map: int, min_points: int, eig_ratio: float, outlier_ratio: float,
-                          stream: int):
-        """levels: per level, coarsest first, (keys_ptr, start_ptr, pts_ptr, n_cells, resolution)"""
+                          stream: int, cell_capacity=None):
+        """levels: per level, coarsest first, (keys_ptr, start_ptr, pts_ptr, n_cells, resolution); cell_capacity (one int
+        per level): the dynamic pyramid of the "NDT localiser, online pyramid" section"""
         L = len(levels)
         keys, start, pts = ((C.c_void_p * L)(*[lv[i] for lv in levels]) for i in range(3))
         n_cells = (C.c_int64 * L)(*[int(lv[3]) for lv in levels])
         res = (C.c_double * L)(*[float(lv[4]) for lv in levels])
-        check(lib.sps_ndt_pyramid_build(self.handle, L, keys, start, pts, n_cells, res, xyz_ptr, int(n_map), int(min_points),
-                                        float(eig_ratio), float(outlier_ratio), stream))
+        if cell_capacity is None:
+            check(lib.sps_ndt_pyramid_build(self.handle, L, keys, start, pts, n_cells, res, xyz_ptr, int(n_map), int(min_points),
+                                            float(eig_ratio), float(outlier_ratio), stream))
+            return
+        if len(cell_capacity) != L:
+            raise ValueError("cell_capacity needs one entry per level")
+        caps = (C.c_int64 * L)(*[int(v) for v in cell_capacity])
+        check(lib.sps_ndt_pyramid_build_dynamic(self.handle, L, keys, start, pts, n_cells, res, xyz_ptr, int(n_map),
+                                                int(min_points), float(eig_ratio), float(outlier_ratio), caps, stream))
+
+    # ---- NDT localiser, online pyramid (include/sps_hip.h, "NDT localiser, online pyramid") ----
+    def ndt_pyramid_update(self, pts_ptr, n_dev_ptr: int, cap: int, T_host, T_dev_ptr, gate_ptr, max_cell_points: int,
+                           info_ptr: int, scratch_ptr: int, stream: int):
+        """info_ptr: int32[n_levels][4]"""
+        check(lib.sps_ndt_pyramid_update(self.handle, pts_ptr, n_dev_ptr, int(cap), self._mat(T_host) if T_host is not None else None,
+                                         T_dev_ptr, gate_ptr, int(max_cell_points), info_ptr, scratch_ptr, stream))
+
+    def ndt_pyramid_carve(self, pts_ptr, n_dev_ptr: int, cap: int, T_host, T_dev_ptr, gate_ptr, end_margins,
+                          through_sigma: float, min_pass: int, miss_frames: int, max_steps: int, info_ptr: int, scratch_ptr,
+                          stream: int):
+        """end_margins: one float per level; info_ptr: int32[n_levels][4]"""
+        em = (C.c_double * len(end_margins))(*[float(v) for v in end_margins])
+        check(lib.sps_ndt_pyramid_carve(self.handle, pts_ptr, n_dev_ptr, int(cap), self._mat(T_host) if T_host is not None else None,
+                                        T_dev_ptr, gate_ptr, em, float(through_sigma), int(min_pass), int(miss_frames),
+                                        int(max_steps), info_ptr, scratch_ptr, stream))
+
+    def ndt_pyramid_info(self, level: int):
+        """(cells assigned, cell capacity, cells dropped for capacity since the build) of a level; synchronises"""
+        out = (C.c_int64 * 4)()
+        check(lib.sps_ndt_pyramid_info(self.handle, int(level), out))
+        return int(out[0]), int(out[1]), int(out[2])
+
+    def ndt_pyramid_carve_cells(self, level: int, pass_ptr, hit_ptr, miss_ptr):
+        """pass, hit and miss of every cell of a level's capacity into int32 device arrays (any may be None); synchronises"""
+        check(lib.sps_ndt_pyramid_carve_cells(self.handle, int(level), pass_ptr, hit_ptr, miss_ptr))
 
     def ndt_pyramid_cells(self, level: int, key_ptr, count_ptr, mean_ptr, icov_ptr, valid_ptr):
         check(lib.sps_ndt_pyramid_cells(self.handle, int(level), key_ptr, count_ptr, mean_ptr, icov_ptr, valid_ptr))

@@ -25,13 +25,19 @@ __device__ inline void ndt_carve_count(int flag, int *word) {
   if (b && (threadIdx.x & 63) == 0) atomicAdd(word, __popcll(b));
 }
 
+// The bodies of the three kernels: one definition for the single map here and for the levels of the online pyramid
+// (ndt_pyramid_update_kernels.inc.h).  Every body indexes by blockIdx.x only; blockIdx.y is the caller's.
+
 // 1: one thread per cell of the capacity
-__global__ __launch_bounds__(256) void k_ndt_carve_begin(const int *__restrict__ gate, NdtDyn d, int *__restrict__ info) {
+__device__ inline void ndt_carve_begin_body(const int *__restrict__ gate, const NdtDyn &d, int *__restrict__ info) {
   const int c = blockIdx.x * 256 + threadIdx.x;
   if (c < 4) info[c] = 0;
   if (!ndt_upd_gate_open(gate) || c >= d.capacity) return;
   d.pass[c] = 0;
   d.hit[c] = 0;
+}
+__global__ __launch_bounds__(256) void k_ndt_carve_begin(const int *__restrict__ gate, NdtDyn d, int *__restrict__ info) {
+  ndt_carve_begin_body(gate, d, info);
 }
 
 // Does the ray o + s d come within the gate of the cell's Gaussian for some s in [s_in, s_out]?  The point of the line
@@ -57,10 +63,9 @@ __device__ inline bool ndt_carve_passes(const double *__restrict__ rec, const do
 }
 
 // 2: one ray per lane.  Lanes whose ray is over wait for the longest ray of their wave.
-__global__ __launch_bounds__(256) void k_ndt_carve_rays(const double *__restrict__ pts, const int *__restrict__ n_dev, int cap,
-                                                         LocPose Th, const double *__restrict__ T_dev,
-                                                         const int *__restrict__ gate, NdtMap m, NdtDyn dy, NdtCarveParams p,
-                                                         int *__restrict__ info) {
+__device__ inline void ndt_carve_rays_body(const double *__restrict__ pts, const int *__restrict__ n_dev, int cap,
+                                           const LocPose &Th, const double *__restrict__ T_dev, const int *__restrict__ gate,
+                                           const NdtMap &m, const NdtDyn &dy, const NdtCarveParams &p, int *__restrict__ info) {
   if (!ndt_upd_gate_open(gate)) return;
   const int n = min(cap, max(*n_dev, 0));
   const int i = blockIdx.x * 256 + threadIdx.x;
@@ -133,10 +138,16 @@ __global__ __launch_bounds__(256) void k_ndt_carve_rays(const double *__restrict
   ndt_carve_count(cast, &info[0]);
   ndt_carve_count(cut, &info[3]);
 }
+__global__ __launch_bounds__(256) void k_ndt_carve_rays(const double *__restrict__ pts, const int *__restrict__ n_dev, int cap,
+                                                         LocPose Th, const double *__restrict__ T_dev,
+                                                         const int *__restrict__ gate, NdtMap m, NdtDyn dy, NdtCarveParams p,
+                                                         int *__restrict__ info) {
+  ndt_carve_rays_body(pts, n_dev, cap, Th, T_dev, gate, m, dy, p, info);
+}
 
 // 3: one thread per cell of the capacity; the cells below the assigned count decide
-__global__ __launch_bounds__(256) void k_ndt_carve_decide(const int *__restrict__ gate, NdtDyn d, NdtCarveParams p,
-                                                           int *__restrict__ info) {
+__device__ inline void ndt_carve_decide_body(const int *__restrict__ gate, const NdtDyn &d, const NdtCarveParams &p,
+                                             int *__restrict__ info) {
   if (!ndt_upd_gate_open(gate)) return;
   const int c = blockIdx.x * 256 + threadIdx.x;
   const int assigned = min(max(d.state[0], 0), d.capacity);
@@ -159,6 +170,10 @@ __global__ __launch_bounds__(256) void k_ndt_carve_decide(const int *__restrict_
   }
   ndt_carve_count(seen, &info[1]);
   ndt_carve_count(cleared, &info[2]);
+}
+__global__ __launch_bounds__(256) void k_ndt_carve_decide(const int *__restrict__ gate, NdtDyn d, NdtCarveParams p,
+                                                           int *__restrict__ info) {
+  ndt_carve_decide_body(gate, d, p, info);
 }
 
 #pragma clang fp contract(fast)

@@ -1,6 +1,6 @@
 // ndt_pyramid_kernels.inc.h -- part of sps_hip.hip (included inside its anonymous namespace, after ndt_update_kernels.inc.h):
-// the NDT localiser registering coarse to fine over a pyramid of static cell maps (host side: ndt_pyramid_host.inc.h; ABI:
-// the "NDT localiser, multi-resolution pyramid" section of include/sps_hip.h).
+// the NDT localiser registering coarse to fine over a pyramid of cell maps, static or (ndt_pyramid_update_kernels.inc.h)
+// dynamic (host side: ndt_pyramid_host.inc.h; ABI: the "NDT localiser, multi-resolution pyramid" section of include/sps_hip.h).
 //
 //   k_ndt_pyr_init    T_out = T_init, status = (1, 0, 0, 0), the state words 0, level[s] = -1, trace and normal rows 0
 //   k_ndt_pyr_assoc   (launch A of a slot)  ndt_assoc_body against the map of the level the state names
@@ -28,11 +28,15 @@ struct NdtPyrCaps {
   int v[NDT_PYR_MAX];      // level_iters: the most slots a level may use
 };
 
-// the pyramid of a context (sps_ndt_pyramid_build): the levels on the host, for the getter, and their device copy
+// the pyramid of a context (sps_ndt_pyramid_build, sps_ndt_pyramid_build_dynamic): the levels on the host, for the getters,
+// and their device copy; a dynamic pyramid also has every level's NdtDyn, in a device array beside the levels'
 struct NdtPyramid {
   int n_levels = 0;        // 0: none built
   NdtPyrLevel lv[NDT_PYR_MAX]{};
   const NdtPyrLevel *dev = nullptr;   // [NDT_PYR_MAX]
+  bool dynamic = false;    // built by sps_ndt_pyramid_build_dynamic
+  NdtDyn dyn[NDT_PYR_MAX]{};
+  const NdtDyn *dyn_dev = nullptr;    // [NDT_PYR_MAX], dynamic only
 };
 
 // Block 0 sets the pose, the status and the state; all blocks clear the per-slot rows (normal and level may be null / empty).

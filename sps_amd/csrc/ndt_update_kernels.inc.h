@@ -79,10 +79,14 @@ __device__ inline int ndt_upd_scan(int v, int *lds, int &total) {
   return off + inc - v;
 }
 
-// 1: one thread per point
-__global__ __launch_bounds__(256) void k_ndt_upd_lookup(const double *__restrict__ pts, const int *__restrict__ n_dev, int cap,
-                                                         LocPose Th, const double *__restrict__ T_dev,
-                                                         const int *__restrict__ gate, NdtMap m, NdtUpdScratch s) {
+// The bodies of the seven kernels: one definition for the single map here and for the levels of the online pyramid
+// (ndt_pyramid_update_kernels.inc.h), which passes a level's map, state, scratch slice and info words.  Every body indexes
+// by blockIdx.x / gridDim.x only; blockIdx.y is the caller's.
+
+// 1: one thread per point.  store_q: q goes to s.q (it does not depend on the map: of several levels that share s.q one stores)
+__device__ inline void ndt_upd_lookup_body(const double *__restrict__ pts, const int *__restrict__ n_dev, int cap,
+                                           const LocPose &Th, const double *__restrict__ T_dev, const int *__restrict__ gate,
+                                           const NdtMap &m, const NdtUpdScratch &s, bool store_q) {
   if (!ndt_upd_gate_open(gate)) return;
   const int n = min(cap, max(*n_dev, 0));
   const int i = blockIdx.x * 256 + threadIdx.x;
@@ -91,8 +95,10 @@ __global__ __launch_bounds__(256) void k_ndt_upd_lookup(const double *__restrict
   double q[3];
   if (T_dev) loc_transform(T_dev, px, py, pz, q);   // one uniform branch, not a choice of address per entry of the pose
   else loc_transform(Th.m, px, py, pz, q);
+  if (store_q) {
 #pragma unroll
-  for (int a = 0; a < 3; ++a) s.q[(size_t)i * 3 + a] = q[a];
+    for (int a = 0; a < 3; ++a) s.q[(size_t)i * 3 + a] = q[a];
+  }
   int cell = -1, slot = -1;
   uint64_t key;
   if (ndt_cell_key(q, m.resolution, 0, key)) {
@@ -108,13 +114,16 @@ __global__ __launch_bounds__(256) void k_ndt_upd_lookup(const double *__restrict
   s.cell_of[i] = cell;
   s.slot_of[i] = slot;
 }
+__global__ __launch_bounds__(256) void k_ndt_upd_lookup(const double *__restrict__ pts, const int *__restrict__ n_dev, int cap,
+                                                         LocPose Th, const double *__restrict__ T_dev,
+                                                         const int *__restrict__ gate, NdtMap m, NdtUpdScratch s) {
+  ndt_upd_lookup_body(pts, n_dev, cap, Th, T_dev, gate, m, s, true);
+}
 
 // 2: one workgroup.  A founder is the lowest point index of a missed key; founder r (ascending index) gets the cell id
 // assigned + r while that is below the capacity.  Writes info[0..2], the cell counter and the dropped total.
-__global__ __launch_bounds__(NDT_UPD_BLOCK) void k_ndt_upd_found(const int *__restrict__ n_dev, int cap,
-                                                                  const int *__restrict__ gate, NdtDyn d, NdtUpdScratch s,
-                                                                  int *__restrict__ info) {
-  __shared__ int lds[NDT_UPD_BLOCK / 64];
+__device__ inline void ndt_upd_found_body(const int *__restrict__ n_dev, int cap, const int *__restrict__ gate, const NdtDyn &d,
+                                          const NdtUpdScratch &s, int *__restrict__ info, int *lds) {
   const int n0 = min(max(d.state[0], 0), d.capacity);
   if (!ndt_upd_gate_open(gate)) {
     if (threadIdx.x < 4) info[threadIdx.x] = threadIdx.x == 0 ? n0 : 0;
@@ -139,10 +148,16 @@ __global__ __launch_bounds__(NDT_UPD_BLOCK) void k_ndt_upd_found(const int *__re
     info[0] = n0 + founded, info[1] = founded, info[2] = base - founded;
   }
 }
+__global__ __launch_bounds__(NDT_UPD_BLOCK) void k_ndt_upd_found(const int *__restrict__ n_dev, int cap,
+                                                                  const int *__restrict__ gate, NdtDyn d, NdtUpdScratch s,
+                                                                  int *__restrict__ info) {
+  __shared__ int lds[NDT_UPD_BLOCK / 64];
+  ndt_upd_found_body(n_dev, cap, gate, d, s, info, lds);
+}
 
 // 3: one thread per point
-__global__ __launch_bounds__(256) void k_ndt_upd_resolve(const int *__restrict__ n_dev, int cap, const int *__restrict__ gate,
-                                                          NdtMap m, NdtDyn d, NdtUpdScratch s) {
+__device__ inline void ndt_upd_resolve_body(const int *__restrict__ n_dev, int cap, const int *__restrict__ gate,
+                                            const NdtMap &m, const NdtDyn &d, const NdtUpdScratch &s) {
   if (!ndt_upd_gate_open(gate)) return;
   const int n = min(cap, max(*n_dev, 0));
   const int i = blockIdx.x * 256 + threadIdx.x;
@@ -165,12 +180,14 @@ __global__ __launch_bounds__(256) void k_ndt_upd_resolve(const int *__restrict__
     atomicMin(&d.lead[cell], i);
   }
 }
+__global__ __launch_bounds__(256) void k_ndt_upd_resolve(const int *__restrict__ n_dev, int cap, const int *__restrict__ gate,
+                                                          NdtMap m, NdtDyn d, NdtUpdScratch s) {
+  ndt_upd_resolve_body(n_dev, cap, gate, m, d, s);
+}
 
 // 4: one workgroup.  The touched cells in ascending order of their lowest point, the offsets of their lists, info[3].
-__global__ __launch_bounds__(NDT_UPD_BLOCK) void k_ndt_upd_offsets(const int *__restrict__ n_dev, int cap,
-                                                                    const int *__restrict__ gate, NdtDyn d, NdtUpdScratch s,
-                                                                    int *__restrict__ info) {
-  __shared__ int lds[NDT_UPD_BLOCK / 64];
+__device__ inline void ndt_upd_offsets_body(const int *__restrict__ n_dev, int cap, const int *__restrict__ gate, const NdtDyn &d,
+                                            const NdtUpdScratch &s, int *__restrict__ info, int *lds) {
   if (!ndt_upd_gate_open(gate)) {
     if (threadIdx.x == 0) *s.n_touched = 0;
     return;
@@ -197,10 +214,16 @@ __global__ __launch_bounds__(NDT_UPD_BLOCK) void k_ndt_upd_offsets(const int *__
     info[3] = base;
   }
 }
+__global__ __launch_bounds__(NDT_UPD_BLOCK) void k_ndt_upd_offsets(const int *__restrict__ n_dev, int cap,
+                                                                    const int *__restrict__ gate, NdtDyn d, NdtUpdScratch s,
+                                                                    int *__restrict__ info) {
+  __shared__ int lds[NDT_UPD_BLOCK / 64];
+  ndt_upd_offsets_body(n_dev, cap, gate, d, s, info, lds);
+}
 
 // 5: one thread per point
-__global__ __launch_bounds__(256) void k_ndt_upd_fill(const int *__restrict__ n_dev, int cap, const int *__restrict__ gate,
-                                                       NdtDyn d, NdtUpdScratch s) {
+__device__ inline void ndt_upd_fill_body(const int *__restrict__ n_dev, int cap, const int *__restrict__ gate, const NdtDyn &d,
+                                         const NdtUpdScratch &s) {
   if (!ndt_upd_gate_open(gate)) return;
   const int n = min(cap, max(*n_dev, 0));
   const int i = blockIdx.x * 256 + threadIdx.x;
@@ -209,6 +232,10 @@ __global__ __launch_bounds__(256) void k_ndt_upd_fill(const int *__restrict__ n_
   if (cell < 0) return;
   const int pos = d.cstart[cell] + atomicAdd(&d.bcnt[cell], 1);
   if (pos >= 0 && pos < cap) s.list[pos] = i;
+}
+__global__ __launch_bounds__(256) void k_ndt_upd_fill(const int *__restrict__ n_dev, int cap, const int *__restrict__ gate,
+                                                       NdtDyn d, NdtUpdScratch s) {
+  ndt_upd_fill_body(n_dev, cap, gate, d, s);
 }
 
 // lane l's point of a chunk of m <= 64 entries of the ordered list that starts at entry `at` (zeros for l >= m)
@@ -224,9 +251,8 @@ __device__ inline void ndt_upd_chunk_point(const NdtUpdScratch &s, int at, int m
 // in LDS orders them: set the bits (an integer atomicOr), count the words' bits, write the indices back in ascending order.
 // Then the sums of k_ndt_cells over that order: 64 points at a time, lane l holds point l of the chunk and every lane adds
 // the chunk's points in order (the same value on every lane).  Linear in n_b + n / 32 whatever the points' spread.
-__global__ __launch_bounds__(64) void k_ndt_upd_stats(const int *__restrict__ n_dev, int cap, const int *__restrict__ gate,
-                                                       NdtDyn d, NdtUpdScratch s) {
-  __shared__ unsigned bits[NDT_UPD_MAX_POINTS / 32];
+__device__ inline void ndt_upd_stats_body(const int *__restrict__ n_dev, int cap, const int *__restrict__ gate, const NdtDyn &d,
+                                          const NdtUpdScratch &s, unsigned *bits) {
   if (!ndt_upd_gate_open(gate)) return;
   const int n = min(min(cap, max(*n_dev, 0)), NDT_UPD_MAX_POINTS);
   const int lane = threadIdx.x;
@@ -296,10 +322,15 @@ __global__ __launch_bounds__(64) void k_ndt_upd_stats(const int *__restrict__ n_
     __syncthreads();   // the bitmap is cleared for the next cell only after every lane has read it
   }
 }
+__global__ __launch_bounds__(64) void k_ndt_upd_stats(const int *__restrict__ n_dev, int cap, const int *__restrict__ gate,
+                                                       NdtDyn d, NdtUpdScratch s) {
+  __shared__ unsigned bits[NDT_UPD_MAX_POINTS / 32];
+  ndt_upd_stats_body(n_dev, cap, gate, d, s, bits);
+}
 
 // 7: one thread per touched cell: forgetting, merge, the record; the cell's update counters go back to their rest values.
-__global__ __launch_bounds__(256) void k_ndt_upd_merge(const int *__restrict__ n_dev, int cap, const int *__restrict__ gate,
-                                                        int max_cell_points, NdtDyn d, NdtUpdScratch s) {
+__device__ inline void ndt_upd_merge_body(const int *__restrict__ n_dev, int cap, const int *__restrict__ gate,
+                                          int max_cell_points, const NdtDyn &d, const NdtUpdScratch &s) {
   if (!ndt_upd_gate_open(gate)) return;
   const int nt = min(max(*s.n_touched, 0), min(cap, max(*n_dev, 0)));
   const int t = blockIdx.x * 256 + threadIdx.x;
@@ -338,6 +369,10 @@ __global__ __launch_bounds__(256) void k_ndt_upd_merge(const int *__restrict__ n
   for (int i = 0; i < 6; ++i) Sg[i] = S[i];
   ndt_record_from_moments(n2, mu, S, d.min_points, d.eig_ratio, rec);
   d.count[cell] = n2;
+}
+__global__ __launch_bounds__(256) void k_ndt_upd_merge(const int *__restrict__ n_dev, int cap, const int *__restrict__ gate,
+                                                        int max_cell_points, NdtDyn d, NdtUpdScratch s) {
+  ndt_upd_merge_body(n_dev, cap, gate, max_cell_points, d, s);
 }
 
 #pragma clang fp contract(fast)

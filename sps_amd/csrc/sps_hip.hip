@@ -154,6 +154,7 @@ int fail(int code, const char *fmt, ...) {
 #include "ndt_update_kernels.inc.h"
 #include "ndt_carve_kernels.inc.h"
 #include "ndt_pyramid_kernels.inc.h"
+#include "ndt_pyramid_update_kernels.inc.h"
 
 // ------------------------------------------------------------------------------------------
 // context
@@ -310,7 +311,7 @@ struct sps_ctx {
   NdtMap ndt{};
   std::vector<void *> ndt_allocs;
   NdtDyn ndt_dyn{};                      // capacity > 0: the map is dynamic (sps_ndt_map_build_dynamic)
-  // NDT pyramid (sps_ndt_pyramid_build): static maps of its own beside the one above, coarse to fine
+  // NDT pyramid (sps_ndt_pyramid_build, sps_ndt_pyramid_build_dynamic): maps of its own beside the one above, coarse to fine
   NdtPyramid ndt_pyr{};
   std::vector<void *> ndt_pyr_allocs;
   // variant-A item scratch (sps_radius_item): per (scan point, neighbour cell) hit counts and their prefix sums
@@ -2267,5 +2268,6 @@ int sps_get_feature(sps_ctx *c, const char *name, float *out_dev, int64_t *rows,
 #include "ndt_update_host.inc.h"
 #include "ndt_carve_host.inc.h"
 #include "ndt_pyramid_host.inc.h"
+#include "ndt_pyramid_update_host.inc.h"
 
 }  // extern "C"

@@ -36,6 +36,11 @@ through for ``miss_frames`` frames on end while none ends in it is cleared.
 pyramid"): one static map per resolution beside the single one, and ``submit`` / ``submit_filtered`` /
 ``__call__`` run one alignment that starts on the coarsest map and hands its pose to the next finer one on the device.
 
+``NDTLocaliser(..., resolutions=(2.0, 1.0, 0.5), level_capacities=(c0, c1, c2))`` makes that pyramid an online one (C ABI:
+"NDT localiser, online pyramid"): every level is a dynamic map, and ``integrate`` / ``carve`` / ``submit(...,
+integrate=True, carve=True)`` update and carve all levels in one set of launches; their results are then tuples, one entry per
+level, coarsest first.  The single map at ``resolution`` stays static.
+
 ``LocalisationLoop`` closes the loop for any of the seven filters of scripts/filter_sequence.py, around either localiser.
 """
 from __future__ import annotations
@@ -64,9 +69,9 @@ class PoseResult:
     trace: np.ndarray          # [iterations, 4] (n_corr, sum d^2, |v|, |omega|) per iteration run
     normal: np.ndarray = None  # [iterations, 28] H (upper triangle), b, sum d^2 -- only with with_normal=True
     n_points: int = 0          # scan points that entered the alignment (after thinning)
-    map_update: object = None  # MapUpdateResult of the frame, with integrate=True
+    map_update: object = None  # MapUpdateResult of the frame, with integrate=True (an online pyramid: a tuple, one per level)
     levels: np.ndarray = None  # [iterations] int, the pyramid level every slot ran at (None without a pyramid)
-    map_carve: object = None   # MapCarveResult of the frame, with carve=True
+    map_carve: object = None   # MapCarveResult of the frame, with carve=True (an online pyramid: a tuple, one per level)
 
     @property
     def ok(self) -> bool:
@@ -99,39 +104,47 @@ def _map_carve_of(words, n_points) -> MapCarveResult:
     return MapCarveResult(int(words[0]), int(words[1]), int(words[2]), int(words[3]), int(n_points))
 
 
+def _per_level(make, words, n_points, n_levels):
+    """one result from four info words (n_levels None), or a tuple of them from int32[n_levels][4], coarsest first"""
+    if n_levels is None:
+        return make(words[:4], n_points)
+    return tuple(make(words[4 * l:4 * l + 4], n_points) for l in range(n_levels))
+
+
 CARVE_DEFAULTS = dict(end_margin=None, through_sigma=1.0, min_pass=2, miss_frames=3, max_steps=512)
 MAX_CARVE_STEPS = 4096
 
 
 class PendingMapCarve:
-    """A carve whose work has been issued; ``result()`` -> MapCarveResult."""
+    """A carve whose work has been issued; ``result()`` -> MapCarveResult (an online pyramid: a tuple, one per level)."""
 
-    def __init__(self, host, event, keep):
-        self._host, self._event, self._keep = host, event, keep
+    def __init__(self, host, event, keep, n_levels=None):
+        self._host, self._event, self._keep, self._n_levels = host, event, keep, n_levels
 
-    def result(self) -> MapCarveResult:
+    def result(self):
         self._event.synchronize()                                    # the one host synchronisation
         h = self._host.numpy()
-        return _map_carve_of(h[4:8], h[0])
+        return _per_level(_map_carve_of, h[4:], h[0], self._n_levels)
 
 
 class PendingMapUpdate:
-    """A map update whose work has been issued; ``result()`` -> MapUpdateResult."""
+    """A map update whose work has been issued; ``result()`` -> MapUpdateResult (an online pyramid: a tuple, one per level)."""
 
-    def __init__(self, host, event, keep):
-        self._host, self._event, self._keep = host, event, keep
+    def __init__(self, host, event, keep, n_levels=None):
+        self._host, self._event, self._keep, self._n_levels = host, event, keep, n_levels
 
-    def result(self) -> MapUpdateResult:
+    def result(self):
         self._event.synchronize()                                    # the one host synchronisation
         h = self._host.numpy()
-        return _map_update_of(h[4:8], h[0])
+        return _per_level(_map_update_of, h[4:], h[0], self._n_levels)
 
 
 class PendingPose:
     """A localisation whose work has been issued; everything lives on the device until result()."""
 
-    def __init__(self, iters, with_normal, host, event, keep, upd_at=None, levels_at=None, carve_at=None):
+    def __init__(self, iters, with_normal, host, event, keep, upd_at=None, levels_at=None, carve_at=None, n_levels=None):
         self._iters, self._with_normal, self._host, self._event, self._keep = iters, with_normal, host, event, keep
+        self._n_levels = n_levels                                    # an online pyramid: info words per level, tuples out
         self._upd_at = upd_at                                        # doubles in front of the map update's info words
         self._levels_at = levels_at                                  # doubles in front of a pyramid's per-slot levels
         self._carve_at = carve_at                                    # doubles in front of the carve's info words
@@ -145,11 +158,15 @@ class PendingPose:
         trace = h[19:19 + 4 * K].reshape(K, 4)[:it].copy()
         normal = h[19 + 4 * K:19 + 32 * K].reshape(K, 28)[:it].copy() if self._with_normal else None
         rmse = math.sqrt(trace[-1, 1] / n_corr) if it and n_corr > 0 else float("nan")
-        upd = None if self._upd_at is None else _map_update_of(h[self._upd_at:self._upd_at + 2].view(np.int32), n_points)
+        L = self._n_levels
+        w = 2 if L is None else 2 * L                                # doubles of one call's info words
+        upd = None if self._upd_at is None else _per_level(_map_update_of, h[self._upd_at:self._upd_at + w].view(np.int32),
+                                                           n_points, L)
         levels = None
         if self._levels_at is not None:
             levels = h[self._levels_at:self._levels_at + (K + 1) // 2].view(np.int32)[:it].astype(np.int64)
-        carved = None if self._carve_at is None else _map_carve_of(h[self._carve_at:self._carve_at + 2].view(np.int32), n_points)
+        carved = None if self._carve_at is None else _per_level(_map_carve_of, h[self._carve_at:self._carve_at + w].view(np.int32),
+                                                                n_points, L)
         return PoseResult(h[:16].reshape(4, 4).copy(), code, it, n_corr, rmse, trace, normal, n_points, upd, levels, carved)
 
 
@@ -402,11 +419,14 @@ class ScanToMapLocaliser:
             # one float64 buffer per frame: T_out[16] | status int32[4] | n_points int32 (+ pad) | trace[K][4] | normal[K][28]
             size = 19 + 32 * K if with_normal else 19 + 4 * K
             pyramid = getattr(self, "resolutions", None) is not None
-            # | info int32[4] with integrate, or | level int32[K] (+ pad) with a pyramid (never both)
-            # | info int32[4] of the carve, last
-            carve_at = size + (2 if integrate else 0)
-            out = torch.zeros(size + (2 if integrate else (K + 1) // 2 if pyramid else 0) + (2 if carve else 0), dtype=torch.float64,
-                              device=dev)
+            caps = getattr(self, "level_capacities", None)
+            L = None if caps is None else len(caps)
+            w = 2 if L is None else 2 * L
+            # | level int32[K] (+ pad) with a pyramid | info int32[4] of the update | info int32[4] of the carve, last
+            # (an online pyramid: int32[L][4] each)
+            upd_at = size + ((K + 1) // 2 if pyramid else 0)
+            carve_at = upd_at + (w if integrate else 0)
+            out = torch.zeros(carve_at + (w if carve else 0), dtype=torch.float64, device=dev)
             base = out.data_ptr()
             self._thin(rows, n_dev, n_max, base + 18 * 8, s)
             kw = dict(level_ptr=base + size * 8 if K else None) if pyramid else {}
@@ -415,38 +435,52 @@ class ScanToMapLocaliser:
             if carve:
                 self._carve(base + 18 * 8, None, base, base + 16 * 8, copts, base + carve_at * 8, s)
             if integrate:
-                self._update(base + 18 * 8, None, base, base + 16 * 8, max_cell_points, base + size * 8, s)
+                self._update(base + 18 * 8, None, base, base + 16 * 8, max_cell_points, base + upd_at * 8, s)
             host, ev = self._to_host(out, st)
-        return PendingPose(K, with_normal, host, ev, (rows, n_dev, out), size if integrate else None, size if pyramid else None,
-                           carve_at if carve else None)
+        return PendingPose(K, with_normal, host, ev, (rows, n_dev, out), upd_at if integrate else None, size if pyramid else None,
+                           carve_at if carve else None, L)
 
-    def _check_integrate(self, integrate, max_cell_points=0):
-        if integrate and getattr(self, "resolutions", None) is not None:
+    def _check_integrate(self, integrate, max_cell_points=0, single_map=False):
+        """``single_map``: the caller works on the single map at ``resolution`` (batch, search, ``map_info``), which an
+        online pyramid's ``level_capacities`` do not make dynamic"""
+        caps = getattr(self, "level_capacities", None)
+        if integrate and caps is None and getattr(self, "resolutions", None) is not None:
             raise ValueError("integrate needs a single-resolution localiser: the online map has no pyramid")
-        if integrate and getattr(self, "cell_capacity", None) is None:
+        if integrate and (caps is None or single_map) and getattr(self, "cell_capacity", None) is None:
             raise ValueError("integrate needs a localiser with an online map: NDTLocaliser(..., cell_capacity=N)")
         if integrate and int(max_cell_points) < 0:
             raise ValueError("max_cell_points must be >= 0")
 
-    def _check_carve(self, carve, carve_options=None):
-        """the carve's options with the defaults filled in (None without ``carve``), before any device work"""
+    def _check_carve(self, carve, carve_options=None, single_map=False):
+        """the carve's options with the defaults filled in (None without ``carve``), before any device work; on an online
+        pyramid ``end_margin`` comes back as a tuple, one float per level.  ``single_map``: as for ``_check_integrate``"""
         if not carve:
             if carve_options is not None:
                 raise ValueError("carve_options needs carve=True")
             return None
-        if getattr(self, "resolutions", None) is not None:
+        caps = getattr(self, "level_capacities", None)
+        if caps is None and getattr(self, "resolutions", None) is not None:
             raise ValueError("carve needs a single-resolution localiser: the online map has no pyramid")
-        if getattr(self, "cell_capacity", None) is None:
+        if (caps is None or single_map) and getattr(self, "cell_capacity", None) is None:
             raise ValueError("carve needs a localiser with an online map: NDTLocaliser(..., cell_capacity=N)")
         unknown = set(carve_options or ()) - set(CARVE_DEFAULTS)
         if unknown:
             raise ValueError(f"unknown carve options {sorted(unknown)}")
         o = dict(CARVE_DEFAULTS, **(carve_options or {}))
-        if o["end_margin"] is None:
-            o["end_margin"] = self.resolution
-        o["end_margin"], o["through_sigma"] = float(o["end_margin"]), float(o["through_sigma"])
+        if caps is not None and not single_map:                      # None: each level's resolution; a scalar: every level
+            em = o["end_margin"]
+            em = self.resolutions if em is None else (em,) * len(caps) if np.ndim(em) == 0 else tuple(em)
+            if len(em) != len(caps):
+                raise ValueError("end_margin needs one value per level")
+            margins = o["end_margin"] = tuple(float(v) for v in em)
+        else:
+            if o["end_margin"] is None:
+                o["end_margin"] = self.resolution
+            o["end_margin"] = float(o["end_margin"])
+            margins = (o["end_margin"],)
+        o["through_sigma"] = float(o["through_sigma"])
         o["min_pass"], o["miss_frames"], o["max_steps"] = int(o["min_pass"]), int(o["miss_frames"]), int(o["max_steps"])
-        if not (math.isfinite(o["end_margin"]) and o["end_margin"] >= 0 and math.isfinite(o["through_sigma"]) and o["through_sigma"] > 0):
+        if not (all(math.isfinite(v) and v >= 0 for v in margins) and math.isfinite(o["through_sigma"]) and o["through_sigma"] > 0):
             raise ValueError("end_margin must be finite and >= 0, through_sigma finite and > 0")
         if o["min_pass"] < 1 or o["miss_frames"] < 1 or not 1 <= o["max_steps"] <= MAX_CARVE_STEPS:
             raise ValueError(f"min_pass and miss_frames must be >= 1 and max_steps in [1, {MAX_CARVE_STEPS}]")
@@ -479,14 +513,22 @@ class NDTLocaliser(ScanToMapLocaliser):
     each level may use (None: ``iterations`` each).  A level hands its pose to the next when it converges or has used its
     slots; only the last level's convergence is status 0, and the result's ``levels`` tells the level of every slot.
     Status 2 / 3 at any level are final and give the guess back.  ``submit_batch``, ``score_poses``, ``relocalise`` and
-    ``map_cells`` keep using the single map of edge ``resolution``; ``pyramid_cells(level)`` shows a level."""
+    ``map_cells`` keep using the single map of edge ``resolution``; ``pyramid_cells(level)`` shows a level.
+
+    ``level_capacities`` (with ``resolutions``; one cell capacity per level, each at least the level's cells): the pyramid's
+    levels are online maps, ``integrate`` / ``carve`` and ``submit(..., integrate=True, carve=True)`` work on all of them
+    at once and report one result per level; ``pyramid_info(level)`` and ``carve_state(level)`` show a level.  The single
+    map stays static, so the batch and the search refuse ``integrate`` and ``carve``.  ``capacity`` is then at most 65536."""
 
     def __init__(self, map_points, resolution: float = 1.0, neighbours: int = 7, leaf: float = 0.2, iterations: int = 30,
                  min_correspondences: int = 50, min_points_per_cell: int = 6, outlier_ratio: float = 0.55,
                  eig_ratio: float = 0.01, tol_t: float = 1e-4, tol_r: float = 1e-5, device="cuda", capacity: int = 1 << 16,
-                 cell_capacity: int = None, resolutions=None, level_iterations=None):
+                 cell_capacity: int = None, resolutions=None, level_iterations=None, level_capacities=None):
         from .datasets.blt_dataset import radius_grid_cells
+        if level_capacities is not None and cell_capacity is not None:
+            raise ValueError("level_capacities and cell_capacity exclude each other: the single map beside an online pyramid is static")
         self.resolutions, self.level_iterations = self._checked_pyramid(resolutions, level_iterations, cell_capacity)
+        self.level_capacities = self._checked_level_capacities(self.resolutions, level_capacities, capacity, map_points)
         if cell_capacity is not None and (int(cell_capacity) < 1 or capacity > MAX_UPDATE_POINTS):
             raise ValueError(f"cell_capacity must be >= 1 and, with it, capacity <= {MAX_UPDATE_POINTS}")
         if not (math.isfinite(resolution) and resolution > 0 and math.isfinite(leaf) and leaf > 0):
@@ -536,7 +578,11 @@ class NDTLocaliser(ScanToMapLocaliser):
                         levels.append((None, None, None, 0, r))
                 self.level_cells = tuple(lv[3] for lv in levels)
                 self.ctx.ndt_pyramid_build(levels, xyz.data_ptr() if self.n_map else None, self.n_map, self.min_points_per_cell,
-                                           self.eig_ratio, self.outlier_ratio, self.stream.cuda_stream)
+                                           self.eig_ratio, self.outlier_ratio, self.stream.cuda_stream, self.level_capacities)
+                if self.level_capacities is not None:
+                    self._pyr_update_scratch = torch.empty(
+                        _native.lib.sps_ndt_pyramid_update_scratch(self.capacity, len(self.resolutions)), dtype=torch.uint8,
+                        device=self.device)
                 self._pyr_scratch = torch.empty(_native.lib.sps_ndt_pyramid_align_scratch(self.capacity), dtype=torch.uint8,
                                                 device=self.device)
             self._pts = torch.empty((self.capacity, 3), dtype=torch.float64, device=self.device)
@@ -566,6 +612,29 @@ class NDTLocaliser(ScanToMapLocaliser):
             raise ValueError("level_iterations needs one entry >= 1 per resolution")
         return res, caps
 
+    @staticmethod
+    def _checked_level_capacities(resolutions, level_capacities, capacity, map_points):
+        """level_capacities as a tuple of ints or None, before any device work: the cells of every level are counted on the
+        host, floor(v / r) in float64 as radius_grid_cells and the kernels divide"""
+        if level_capacities is None:
+            return None
+        if resolutions is None:
+            raise ValueError("level_capacities needs resolutions")
+        caps = tuple(int(v) for v in level_capacities)
+        if len(caps) != len(resolutions):
+            raise ValueError("level_capacities needs one entry per resolution")
+        if min(caps) < 1:
+            raise ValueError("level_capacities must be >= 1")
+        if capacity > MAX_UPDATE_POINTS:
+            raise ValueError(f"with level_capacities, capacity must be <= {MAX_UPDATE_POINTS}")
+        mp = map_points.detach().cpu().numpy() if torch.is_tensor(map_points) else np.asarray(map_points)
+        xyz = np.ascontiguousarray(mp[:, :3], dtype=np.float64)
+        for l, (r, c) in enumerate(zip(resolutions, caps)):
+            n = len(np.unique(np.floor(xyz / np.float64(r)).astype(np.int64), axis=0)) if len(xyz) else 0
+            if c < n:
+                raise ValueError(f"level_capacities[{l}] = {c} is below the {n} cells of the map at {r} m")
+        return caps
+
     def _align(self, n_ptr, T, K, T_out_ptr, status_ptr, trace_ptr, normal_ptr, s, level_ptr=None):
         if self.resolutions is not None:
             caps = self.level_iterations or (max(K, 1),) * len(self.resolutions)
@@ -578,15 +647,23 @@ class NDTLocaliser(ScanToMapLocaliser):
                            self._align_scratch.data_ptr(), s)
 
     def _update(self, n_ptr, T_host, T_dev_ptr, gate_ptr, max_cell_points, info_ptr, s):
+        if self.level_capacities is not None:                        # every level, info_ptr: int32[L][4]
+            self.ctx.ndt_pyramid_update(self._pts.data_ptr(), n_ptr, self.capacity, T_host, T_dev_ptr, gate_ptr, max_cell_points,
+                                        info_ptr, self._pyr_update_scratch.data_ptr(), s)
+            return
         self.ctx.ndt_map_update(self._pts.data_ptr(), n_ptr, self.capacity, T_host, T_dev_ptr, gate_ptr, max_cell_points,
                                 info_ptr, self._update_scratch.data_ptr(), s)
 
     def _carve(self, n_ptr, T_host, T_dev_ptr, gate_ptr, o, info_ptr, s):
+        if self.level_capacities is not None:                        # every level, info_ptr: int32[L][4]
+            self.ctx.ndt_pyramid_carve(self._pts.data_ptr(), n_ptr, self.capacity, T_host, T_dev_ptr, gate_ptr, o["end_margin"],
+                                       o["through_sigma"], o["min_pass"], o["miss_frames"], o["max_steps"], info_ptr, None, s)
+            return
         self.ctx.ndt_map_carve(self._pts.data_ptr(), n_ptr, self.capacity, T_host, T_dev_ptr, gate_ptr, o["end_margin"],
                                o["through_sigma"], o["min_pass"], o["miss_frames"], o["max_steps"], info_ptr, None, s)
 
     @torch.no_grad()
-    def carve(self, rows, count, T, end_margin: float = None, through_sigma: float = 1.0, min_pass: int = 2, miss_frames: int = 3,
+    def carve(self, rows, count, T, end_margin=None, through_sigma: float = 1.0, min_pass: int = 2, miss_frames: int = 3,
               max_steps: int = 512) -> PendingMapCarve:
         """Carve the online map with the rows as ray ends seen from the host pose ``T`` (4x4, sensor -> map): they are
         thinned with the localiser's ``leaf`` as ``submit`` thins them; every ray gives the cell it ends in a hit and walks
@@ -594,7 +671,9 @@ class NDTLocaliser(ScanToMapLocaliser):
         and passes through a valid cell where it comes within ``through_sigma`` standard deviations of the cell's Gaussian.
         A cell with no hit and at least ``min_pass`` passing rays was seen through; ``miss_frames`` such frames on end clear
         it (count 0, not valid) until an update refills it; a hit starts the count again.  Issued on the current stream;
-        ``result()`` -> MapCarveResult."""
+        ``result()`` -> MapCarveResult.  An online pyramid (``level_capacities``) carves every level in the same launches:
+        ``end_margin`` is then None (each level's resolution), one value for all levels or one per level, and ``result()``
+        gives a tuple of MapCarveResult, coarsest level first."""
         o = self._check_carve(True, dict(end_margin=end_margin, through_sigma=through_sigma, min_pass=min_pass,
                                          miss_frames=miss_frames, max_steps=max_steps))
         rows = self._checked_rows(rows)
@@ -606,18 +685,29 @@ class NDTLocaliser(ScanToMapLocaliser):
             st = torch.cuda.current_stream()
             s = st.cuda_stream
             n_dev = self._count_on_device(count, n_max)
-            out = torch.zeros(8, dtype=torch.int32, device=dev)      # n_points (+ pad) | info[4]
+            L = None if self.level_capacities is None else len(self.level_capacities)
+            out = torch.zeros(4 + 4 * (L or 1), dtype=torch.int32, device=dev)   # n_points (+ pad) | info[4] (a pyramid: [L][4])
             base = out.data_ptr()
             self._thin(rows, n_dev, n_max, base, s)
             self._carve(base, Th, None, None, o, base + 16, s)
             host, ev = self._to_host(out, st)
-        return PendingMapCarve(host, ev, (rows, n_dev, out))
+        return PendingMapCarve(host, ev, (rows, n_dev, out), L)
 
-    def carve_state(self):
+    def carve_state(self, level: int = None):
         """Debug: (pass, hit, miss) int32 arrays of the online map's assigned cells, in the order of ``map_cells()``: the
         rays that passed through and that ended in every cell in the last carve whose gate was open, and the consecutive
-        carves in which the cell was seen through.  Synchronises."""
-        self._check_carve(True)
+        carves in which the cell was seen through.  ``level``: of that level of an online pyramid instead, in the order of
+        ``pyramid_cells(level)``.  Synchronises."""
+        if level is not None:
+            level = self._checked_online_level(level)
+            C = self.level_capacities[level]
+            with torch.cuda.device(self.device):
+                out = torch.zeros((3, C), dtype=torch.int32, device=self.device)
+                self.ctx.ndt_pyramid_carve_cells(level, out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr())
+            n = self.ctx.ndt_pyramid_info(level)[0]
+            h = out.cpu().numpy()
+            return h[0, :n].copy(), h[1, :n].copy(), h[2, :n].copy()
+        self._check_carve(True, single_map=True)
         C = self.cell_capacity
         with torch.cuda.device(self.device):
             out = torch.zeros((3, C), dtype=torch.int32, device=self.device)
@@ -631,7 +721,9 @@ class NDTLocaliser(ScanToMapLocaliser):
         """Fold the rows into the online map at the host pose ``T`` (4x4, sensor -> map): they are thinned with the
         localiser's ``leaf`` as ``submit`` thins them, then every point joins the moments of its cell; cells the map does
         not have yet are founded while ``cell_capacity`` lasts.  ``max_cell_points`` (0: off) caps the weight of a cell's
-        history, so that a changed scene is forgotten.  Issued on the current stream; ``result()`` -> MapUpdateResult."""
+        history, so that a changed scene is forgotten.  Issued on the current stream; ``result()`` -> MapUpdateResult.  An
+        online pyramid (``level_capacities``) updates every level in the same launches, each within its own capacity, and
+        ``result()`` gives a tuple of MapUpdateResult, coarsest level first."""
         self._check_integrate(True, max_cell_points)
         rows = self._checked_rows(rows)
         Th = _pose(T)
@@ -642,17 +734,30 @@ class NDTLocaliser(ScanToMapLocaliser):
             st = torch.cuda.current_stream()
             s = st.cuda_stream
             n_dev = self._count_on_device(count, n_max)
-            out = torch.zeros(8, dtype=torch.int32, device=dev)      # n_points (+ pad) | info[4]
+            L = None if self.level_capacities is None else len(self.level_capacities)
+            out = torch.zeros(4 + 4 * (L or 1), dtype=torch.int32, device=dev)   # n_points (+ pad) | info[4] (a pyramid: [L][4])
             base = out.data_ptr()
             self._thin(rows, n_dev, n_max, base, s)
             self._update(base, Th, None, None, max_cell_points, base + 16, s)
             host, ev = self._to_host(out, st)
-        return PendingMapUpdate(host, ev, (rows, n_dev, out))
+        return PendingMapUpdate(host, ev, (rows, n_dev, out), L)
 
     def map_info(self):
         """Debug: (cells assigned, cell capacity, cells dropped for capacity since the build) of the online map; synchronises."""
-        self._check_integrate(True)
+        self._check_integrate(True, single_map=True)
         return self.ctx.ndt_map_info()
+
+    def _checked_online_level(self, level):
+        if getattr(self, "level_capacities", None) is None:
+            raise ValueError("needs a localiser with an online pyramid: NDTLocaliser(..., resolutions=..., level_capacities=...)")
+        if not 0 <= int(level) < len(self.level_capacities):
+            raise ValueError(f"level must be in [0, {len(self.level_capacities)})")
+        return int(level)
+
+    def pyramid_info(self, level: int):
+        """Debug: ``map_info()`` of level ``level`` of an online pyramid (0: the coarsest); synchronises."""
+        level = self._checked_online_level(level)
+        return self.ctx.ndt_pyramid_info(level)
 
     @torch.no_grad()
     def submit_batch(self, rows, count, T_inits, with_normal: bool = False, iterations: int = None, integrate: bool = False,
@@ -662,8 +767,8 @@ class NDTLocaliser(ScanToMapLocaliser):
         score at its final pose is selected among those with status 0 / 1 and at least ``min_correspondences`` points
         counted there (equal scores: the lowest index).  Issued on the current stream; ``result()`` -> BatchPoseResult.
         ``integrate`` and ``carve``: as for ``submit``, at the selected pose and only where a hypothesis was selected."""
-        self._check_integrate(integrate, max_cell_points)
-        copts = self._check_carve(carve, carve_options)
+        self._check_integrate(integrate, max_cell_points, single_map=True)
+        copts = self._check_carve(carve, carve_options, single_map=True)
         rows = self._checked_rows(rows)
         T = np.ascontiguousarray(np.asarray(T_inits, dtype=np.float64))
         if T.ndim != 3 or T.shape[1:] != (4, 4) or not 1 <= len(T) <= MAX_HYPOTHESES or not np.isfinite(T).all():
@@ -751,8 +856,8 @@ class NDTLocaliser(ScanToMapLocaliser):
         from these as ``submit_batch`` does and select among the end poses as it selects.  Everything is issued on the
         current stream with no synchronisation in between; ``result()`` -> RelocalisationResult.  ``integrate`` and
         ``carve``: as for ``submit_batch``."""
-        self._check_integrate(integrate, max_cell_points)
-        copts = self._check_carve(carve, carve_options)
+        self._check_integrate(integrate, max_cell_points, single_map=True)
+        copts = self._check_carve(carve, carve_options, single_map=True)
         rows = self._checked_rows(rows)
         T = _checked_poses(poses)
         K = int(keep)
@@ -801,12 +906,14 @@ class NDTLocaliser(ScanToMapLocaliser):
                 valid.cpu().numpy().astype(bool)[:n])
 
     def pyramid_cells(self, level: int):
-        """Debug: ``map_cells()`` of level ``level`` of the pyramid (0: the coarsest)."""
+        """Debug: ``map_cells()`` of level ``level`` of the pyramid (0: the coarsest); an online pyramid gives the level's
+        assigned cells in the order of their ids, as ``map_cells()`` does for an online map."""
         if self.resolutions is None:
             raise ValueError("pyramid_cells needs a localiser with resolutions")
         if not 0 <= int(level) < len(self.resolutions):
             raise ValueError(f"level must be in [0, {len(self.resolutions)})")
-        C = self.level_cells[int(level)]
+        caps = getattr(self, "level_capacities", None)
+        C = self.level_cells[int(level)] if caps is None else caps[int(level)]
         with torch.cuda.device(self.device):
             key = torch.zeros(C, dtype=torch.int64, device=self.device)
             cnt = torch.zeros(C, dtype=torch.int32, device=self.device)
@@ -815,8 +922,9 @@ class NDTLocaliser(ScanToMapLocaliser):
             valid = torch.zeros(C, dtype=torch.int32, device=self.device)
             self.ctx.ndt_pyramid_cells(int(level), key.data_ptr(), cnt.data_ptr(), mean.data_ptr(), icov.data_ptr(),
                                        valid.data_ptr())
-        return (key.cpu().numpy().view(np.uint64), cnt.cpu().numpy(), mean.cpu().numpy(), icov.cpu().numpy(),
-                valid.cpu().numpy().astype(bool))
+        n = C if caps is None else self.ctx.ndt_pyramid_info(int(level))[0]
+        return (key.cpu().numpy().view(np.uint64)[:n], cnt.cpu().numpy()[:n], mean.cpu().numpy()[:n], icov.cpu().numpy()[:n],
+                valid.cpu().numpy().astype(bool)[:n])
 
 
 @dataclass
@@ -856,7 +964,8 @@ class LocalisationLoop:
     best ``search_keep`` poses are aligned and the best end pose is handed on; a frame in which none is selected is flagged
     and keeps the guess.
 
-    ``update_map`` (a localiser with an online map: ``NDTLocaliser(..., cell_capacity=N)``): every frame's kept points, as
+    ``update_map`` (a localiser with an online map: ``NDTLocaliser(..., cell_capacity=N)``, or with an online pyramid:
+    ``level_capacities``, whose frames report one result per level and take no hypotheses and no search): every frame's kept points, as
     thinned for the registration, are folded into the map at the frame's corrected pose, behind the registration on its
     stream.  The device gates the update on the registration's status, so a flagged frame leaves the map alone; the
     frame's ``pose_result.map_update`` (``batch.map_update``) tells what happened.  ``max_cell_points``: the forgetting
@@ -871,13 +980,16 @@ class LocalisationLoop:
         from .sps_filters import ConstantVelocityModel
         self.filter, self.localiser = filter, localiser
         self.update_map, self.max_cell_points = bool(update_map), int(max_cell_points)
-        if self.update_map and getattr(localiser, "cell_capacity", None) is None:
+        online_pyramid = getattr(localiser, "level_capacities", None) is not None
+        if self.update_map and getattr(localiser, "cell_capacity", None) is None and not online_pyramid:
             raise ValueError("update_map needs a localiser with an online map: NDTLocaliser(..., cell_capacity=N)")
+        if online_pyramid and (update_map or carve_map) and (hypotheses is not None or search is not None):
+            raise ValueError("an online pyramid is updated and carved by the plain registration only: no hypotheses, no search")
         # the keyword arguments every registration of the loop gets: none unless the map is updated
         self._kw = dict(integrate=True, max_cell_points=self.max_cell_points) if self.update_map else {}
         self.carve_map = bool(carve_map)
         if self.carve_map:
-            if getattr(localiser, "cell_capacity", None) is None:
+            if getattr(localiser, "cell_capacity", None) is None and not online_pyramid:
                 raise ValueError("carve_map needs a localiser with an online map: NDTLocaliser(..., cell_capacity=N)")
             self._kw.update(carve=True, carve_options=carve_options)
         elif carve_options is not None:

@@ -29,6 +29,11 @@ single-map localiser on the same frames in one session: per-frame time, live and
 submit(integrate=True) against submit, interleaved frame by frame with the only alternative a static map offers, a new
 NDTLocaliser over map + frame.
 
+``--localiser ndt --resolutions 2,1,0.5 --integrate --carve`` times the online pyramid (NDTLocaliser(..., level_capacities=...)):
+sps_ndt_pyramid_update and sps_ndt_pyramid_carve against one sps_ndt_map_update / sps_ndt_map_carve per level on single-map
+localisers of the same resolutions and capacities, frame by frame alternating in one run, and submit(integrate=True,
+carve=True) against the pyramid's plain submit.
+
 ``--localiser ndt --carve`` times the free-space carving of the online map: sps_ndt_map_carve alone, sps_ndt_map_update alone,
 submit and submit(integrate=True, carve=True), interleaved frame by frame, and (with --cpu-frames >= 1) the restatement's
 count of the cells a ray visits on one frame.
@@ -120,7 +125,7 @@ def main():
                     "against K back-to-back submit calls")
     ap.add_argument("--search", type=int, default=0, help="with --localiser ndt: time score_poses of P poses against "
                     "ceil(P / 64) submit_batch(iterations=0) calls, the only way to score poses without it")
-    ap.add_argument("--update-map", action="store_true", help="with --localiser ndt: time the online map's update against "
+    ap.add_argument("--update-map", "--integrate", dest="update_map", action="store_true", help="with --localiser ndt: time the online map's update against "
                     "rebuilding the localiser over map + frame")
     ap.add_argument("--carve", action="store_true", help="with --localiser ndt: time the online map's free-space carving beside "
                     "its update and the registration")
@@ -129,10 +134,10 @@ def main():
     ap.add_argument("--iterations", type=int, default=30, help="with --resolutions: the pyramid's budget of slots")
     ap.add_argument("--level-iterations", type=str, default=None, help="with --resolutions: N0,N1,... the cap of every level")
     a = ap.parse_args()
-    if a.resolutions and (a.localiser != "ndt" or a.hypotheses or a.search or a.update_map or a.carve):
-        ap.error("--resolutions needs --localiser ndt and none of --hypotheses, --search, --update-map, --carve")
-    if a.carve and (a.localiser != "ndt" or a.hypotheses or a.search or a.update_map):
-        ap.error("--carve needs --localiser ndt and none of --hypotheses, --search, --update-map")
+    if a.resolutions and (a.localiser != "ndt" or a.hypotheses or a.search):
+        ap.error("--resolutions needs --localiser ndt and none of --hypotheses, --search")
+    if a.carve and (a.localiser != "ndt" or a.hypotheses or a.search or (a.update_map and not a.resolutions)):
+        ap.error("--carve needs --localiser ndt and none of --hypotheses, --search, --update-map (but with --resolutions)")
     if a.update_map and a.localiser != "ndt":
         ap.error("--update-map needs --localiser ndt")
     if a.search and (a.localiser != "ndt" or not 1 <= a.search <= 65536):
@@ -146,6 +151,8 @@ def main():
     dscans = [torch.from_numpy(s).cuda() for s in scans]
     mp = synthetic.build_map()
     T_init = LR.perturbation(0.15, 0.12, 0.05, 1.0)
+    if a.localiser == "ndt" and a.resolutions and (a.update_map or a.carve):
+        return ndt_online_pyramid_main(a, dscans, mp, T_init)
     if a.localiser == "ndt" and a.update_map:
         return ndt_update_main(a, dscans, mp, T_init)
     if a.localiser == "ndt" and a.carve:
@@ -586,6 +593,98 @@ def ndt_carve_main(a, scans, dscans, mp, T_init):
         out["restatement_one_frame"] = {"info": ref, "cells_per_ray_mean": round(float(np.mean(visited)), 2),
                                         "cells_per_ray_max": int(max(visited))}
         print(f"restatement, one frame on the built map: info {ref}, cells per ray mean {np.mean(visited):.2f} max {max(visited)}", flush=True)
+    print(json.dumps(out))
+
+
+def ndt_online_pyramid_main(a, dscans, mp, T_init):
+    """--resolutions with --integrate / --carve: the online pyramid's fused calls against the only way without them, one
+    single-map online localiser per level doing the same work one after another.  Per frame, in one run and in this order
+    (hipEvents around each): the pyramid's submit; sps_ndt_pyramid_update alone on the points that submit left thinned, at
+    the true pose; the L sps_ndt_map_update calls on the same points; sps_ndt_pyramid_carve alone; the L sps_ndt_map_carve
+    calls; submit(integrate=True, carve=True).  Both sides see the same points at the same poses, so their maps stay equal;
+    the 12 scans come back, so the maps and the carve's counters reach a steady state within the warm-up."""
+    from sps_amd.localiser import CARVE_DEFAULTS
+    map64 = mp[:, :3].astype(np.float64)
+    res = tuple(float(v) for v in a.resolutions.split(","))
+    caps = tuple(int(v) for v in a.level_iterations.split(",")) if a.level_iterations else None
+    cells = [len(np.unique(np.floor(map64 / r).astype(np.int64), axis=0)) for r in res]
+    level_caps = tuple(max(2 * c, 4096) for c in cells)
+    pyr = NDTLocaliser(map64, resolutions=res, iterations=a.iterations, level_iterations=caps, level_capacities=level_caps)
+    singles = [NDTLocaliser(map64, resolution=r, cell_capacity=c) for r, c in zip(res, level_caps)]
+    L = len(res)
+    opts = pyr._check_carve(True, dict(CARVE_DEFAULTS))
+    sopts = [s._check_carve(True, dict(CARVE_DEFAULTS)) for s in singles]
+    st = torch.cuda.current_stream()
+    I4 = np.eye(4)
+    info = torch.zeros(4 * 4 * L, dtype=torch.int32, device="cuda")           # fused update | chained | fused carve | chained
+    n_pts = torch.zeros(1, dtype=torch.int32, device="cuda")
+    kw = {}
+    if a.update_map:
+        kw["integrate"] = True
+    if a.carve:
+        kw["carve"] = True
+    names = ["submit_ms"] + (["update_fused_ms", "update_chained_ms"] if a.update_map else []) + \
+        (["carve_fused_ms", "carve_chained_ms"] if a.carve else []) + ["submit_online_ms"]
+    t = {n: [] for n in names}
+    last = None
+    pts, cap = pyr._pts.data_ptr(), pyr.capacity
+    for k in range(a.warmup + a.frames):
+        s = dscans[k % len(dscans)]
+        ev = {n: (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for n in names}
+        ev["submit_ms"][0].record(st)
+        pend = pyr.submit(s, len(s), T_init)
+        ev["submit_ms"][1].record(st)
+        n_pts.fill_(pend.result().n_points)
+        n_ptr, base = n_pts.data_ptr(), info.data_ptr()
+        if a.carve:                                                  # the carve before the update, as submit orders them
+            ev["carve_fused_ms"][0].record(st)
+            pyr._carve(n_ptr, I4, None, None, opts, base + 2 * 16 * L, st.cuda_stream)
+            ev["carve_fused_ms"][1].record(st)
+            ev["carve_chained_ms"][0].record(st)
+            for l, one in enumerate(singles):
+                o = sopts[l]
+                one.ctx.ndt_map_carve(pts, n_ptr, cap, I4, None, None, o["end_margin"], o["through_sigma"], o["min_pass"],
+                                      o["miss_frames"], o["max_steps"], base + 3 * 16 * L + 16 * l, None, st.cuda_stream)
+            ev["carve_chained_ms"][1].record(st)
+        if a.update_map:
+            ev["update_fused_ms"][0].record(st)
+            pyr._update(n_ptr, I4, None, None, 0, base, st.cuda_stream)
+            ev["update_fused_ms"][1].record(st)
+            ev["update_chained_ms"][0].record(st)
+            for l, one in enumerate(singles):
+                one.ctx.ndt_map_update(pts, n_ptr, cap, I4, None, None, 0, base + 16 * L + 16 * l, one._update_scratch.data_ptr(),
+                                       st.cuda_stream)
+            ev["update_chained_ms"][1].record(st)
+        words = info.cpu().numpy().reshape(4, L, 4)
+        assert (words[0] == words[1]).all() and (words[2] == words[3]).all(), "fused and chained calls disagree"
+        ev["submit_online_ms"][0].record(st)
+        pend = pyr.submit(s, len(s), T_init, **kw)
+        ev["submit_online_ms"][1].record(st)
+        last = pend.result()
+        if last.status in (0, 1):                                    # untimed: the single maps follow, at the pose the device found
+            for l, one in enumerate(singles):
+                o = sopts[l]
+                if a.carve:
+                    one.ctx.ndt_map_carve(pts, n_ptr, cap, last.pose, None, None, o["end_margin"], o["through_sigma"], o["min_pass"],
+                                          o["miss_frames"], o["max_steps"], base + 3 * 16 * L + 16 * l, None, st.cuda_stream)
+                if a.update_map:
+                    one.ctx.ndt_map_update(pts, n_ptr, cap, last.pose, None, None, 0, base + 16 * L + 16 * l,
+                                           one._update_scratch.data_ptr(), st.cuda_stream)
+        torch.cuda.synchronize()
+        if k >= a.warmup:
+            for n in names:
+                t[n].append(ev[n][0].elapsed_time(ev[n][1]))
+
+    def stats(v):
+        return {"median": round(float(np.median(v)), 4), "min": round(min(v), 4), "max": round(max(v), 4)}
+    out = {"frames": a.frames, "warmup": a.warmup, "n_map": len(mp), "resolutions": res, "cells_at_build": cells,
+           "level_capacities": level_caps, "n_points": last.n_points, "slots": last.iterations,
+           "level_info": [pyr.pyramid_info(l) for l in range(L)],
+           "last_update": [vars(u) for u in last.map_update] if last.map_update else None,
+           "last_carve": [vars(c) for c in last.map_carve] if last.map_carve else None}
+    for name, v in t.items():
+        out[name] = stats(v)
+        print(f"{name:22s} median {out[name]['median']:.4f} (min {out[name]['min']:.4f} max {out[name]['max']:.4f})", flush=True)
     print(json.dumps(out))
 
 
