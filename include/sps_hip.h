@@ -789,6 +789,57 @@ int sps_ndt_pyramid_carve(sps_ctx *ctx, const double *pts_dev, const int32_t *n_
 int sps_ndt_pyramid_info(sps_ctx *ctx, int level, int64_t *out_host);
 int sps_ndt_pyramid_carve_cells(sps_ctx *ctx, int level, int32_t *pass_out_dev, int32_t *hit_out_dev, int32_t *miss_out_dev);
 
+/* ---- pose estimator (unscented Kalman filter with IMU prediction) -----------------------------------------------------
+ * hdl_localization's pose system as published, restated: tests/ukf_reference.py is the specification, not that package
+ * (DESIGN.md 8j lists the differences).  Additive: sps_version() is unchanged.  No entry takes a context, allocates,
+ * synchronises or raises a sticky error; each is one launch of one workgroup on `stream`.
+ *
+ * State (n = 16, f64): p 0:3, v 3:6, q 6:10 (w, x, y, z), accelerometer bias 10:13, gyroscope bias 13:16.  The state
+ * block is a caller-owned device buffer of SPS_UKF_STATE_BYTES: x[16] | P[16][16] (row-major, exactly symmetric) |
+ * T[16] (the pose of the mean) | int32 (predictions done, corrections done, 0, 0).
+ *
+ * Process f(x, (a, w), dt): p' = p + v dt; v' = v (the acceleration is accepted in every sample and unused); g = w - bg,
+ *   h = (dt / 2) g, dq = (1, h) / |(1, h)|, q' = (q * dq) / |q * dq| (Hamilton product, body-frame rate); biases unchanged.
+ *   Without an IMU g = 0 and q' = q / |q|.
+ * Prediction: unscented transform with lambda = 1: L = chol(17 P), 33 sigma points x, x + L[:, i], x - L[:, i], weights
+ *   1/17 and 1/34, all through f; mean = sum w_i s_i; P = sum w_i (s_i - mean)(s_i - mean)^T + diag(process_diag) dt; then
+ *   the mean's quaternion is renormalised.
+ * Correction with z = (p, q) of a 4 x 4 pose (q by Shepperd's method: the largest of trace, R00, R11, R22 decides, ties to
+ *   the first; normalised; negated where its dot product with the mean's quaternion is negative): the state is extended by
+ *   the measurement noise (23 entries, 47 sigma points, weights 1/24 and 1/48); the extended covariance is block diagonal,
+ *   so its factor is chol(24 P) and sqrt(24 r_k).  z_i = (p_i, q_i) + noise_i, zbar = sum w_i z_i, Pz = sum w_i dz dz^T,
+ *   Pxz = sum w_i (s_i - x) dz^T, K = Pxz Pz^-1 through chol(Pz) and two triangular solves per row, x += K (z - zbar),
+ *   P -= (K Pz) K^T, the mean's quaternion renormalised.
+ * Arithmetic: every operation an individually rounded f64 one, no transcendental function, no float atomic; sigma points
+ *   summed in index order, Cholesky and substitution inner sums in ascending index, every entry by one thread; P and Pz
+ *   are computed on the lower triangle and mirrored.  Same input, same bits, whatever the launch geometry.
+ * Status (int32): 0 done; 2 the gate was closed (the state block is untouched, every byte); 3 singular: a Cholesky pivot
+ *   <= 0 or anything not finite -- the state is as before the failing step.
+ *
+ * sps_ukf_init: the state from a host pose T_host[16], a host velocity v_host[3] (NULL: zero) and the diagonal of P
+ *   (p0_diag[16], finite, >= 0); the counters are cleared.
+ * sps_ukf_predict: imu_dev is [n_imu][7] f64 rows (dt, ax, ay, az, gx, gy, gz), 0 <= n_imu <= SPS_UKF_MAX_IMU: one launch
+ *   runs every sample in turn.  n_imu = 0 only writes the pose.  T_pred_dev (may be NULL) receives the pose of the mean
+ *   after the call, info_dev (may be NULL) int32 (status, samples done, index of the failing sample or -1, 0).  A sample
+ *   that is not finite, whose dt is not > 0, or whose step is singular ends the call with status 3: the state is that of
+ *   the sample before it and the remaining samples are skipped.  process_diag_host: double[16], finite, >= 0.
+ * sps_ukf_predict_dt: the IMU-less step over dt (finite, > 0, checked before anything is queued), on the same kernel.
+ * sps_ukf_correct: T_meas_dev is a 4 x 4 pose on the device (T_out of an alignment, T_best of a batch); gate_dev (NULL:
+ *   always correct) an int32 on the device: the correction runs where it is 0 or 1 (the status word of an alignment,
+ *   best[1] of a batch: the gate of sps_ndt_map_update and sps_ndt_map_carve).  meas_diag_host: double[7], finite, >= 0.
+ *   info_dev (may be NULL): 8 doubles, the first one's two int32 halves (status, 0), then the innovation z - zbar[7]
+ *   (zeros unless the status is 0). */
+#define SPS_UKF_STATE_BYTES 2320
+#define SPS_UKF_MAX_IMU 256
+int64_t sps_ukf_state_bytes(void);
+int sps_ukf_init(double *state_dev, const double *T_host, const double *v_host, const double *p0_diag, void *stream);
+int sps_ukf_predict(double *state_dev, const double *imu_dev, int32_t n_imu, const double *process_diag_host, double *T_pred_dev,
+                    int32_t *info_dev, void *stream);
+int sps_ukf_predict_dt(double *state_dev, double dt, const double *process_diag_host, double *T_pred_dev, int32_t *info_dev,
+                       void *stream);
+int sps_ukf_correct(double *state_dev, const double *T_meas_dev, const int32_t *gate_dev, const double *meas_diag_host,
+                    double *info_dev, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

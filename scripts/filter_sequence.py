@@ -139,8 +139,9 @@ def hypothesis_grid(counts, steps, option="--hypotheses", step_option="--hypothe
 
 def closed_loop(name, f, pc_map, replay, finish, traj_out, which="icp", hypotheses=None, search=None, update_map=False,
                 cell_capacity=None, max_cell_points=0, resolutions=None, level_iterations=None, carve_map=False,
-                carve_options=None, level_capacities=None):
-    """--localise: one LocalisationLoop step per frame, scored against the replayed poses."""
+                carve_options=None, level_capacities=None, estimator=None):
+    """--localise: one LocalisationLoop step per frame, scored against the replayed poses.  ``estimator``: None, or the
+    options of --estimator ukf (initial_velocity, scan_period, imu: None / a rate in Hz / an array of rows t ax .. gz)."""
     from sps_amd.localiser import LocalisationLoop, NDTLocaliser, ScanToMapLocaliser
     from sps_amd.trajectory import ape_translation, rotation_angle, write_trajectory
     if resolutions is not None and (update_map or carve_map):    # an online pyramid: per level, room for twice its cells
@@ -158,13 +159,24 @@ def closed_loop(name, f, pc_map, replay, finish, traj_out, which="icp", hypothes
         localiser = NDTLocaliser(pc_map[:, :3], resolutions=resolutions, iterations=sum(caps), level_iterations=caps)
     else:
         localiser = NDTLocaliser(pc_map[:, :3]) if which == "ndt" else ScanToMapLocaliser(pc_map[:, :3])
-    loop, stamps, ref = None, [], []
+    loop, stamps, ref, estimates = None, [], [], []
     for stamp, scan, pose, map_tr in replay:
         T = map_tr @ pose
         if loop is None:
+            est = None
+            if estimator is not None:
+                from sps_amd.pose_estimator import PoseEstimator
+                est = PoseEstimator(T, localiser.device, initial_velocity=estimator["initial_velocity"])
             loop = LocalisationLoop(f, localiser, T, hypotheses=hypotheses, search=search, update_map=update_map,
-                                    max_cell_points=max_cell_points, carve_map=carve_map, carve_options=carve_options)
-        step = loop.step(scan)
+                                    max_cell_points=max_cell_points, carve_map=carve_map, carve_options=carve_options,
+                                    estimator=est)
+            if est is not None:
+                print("estimator: ukf  start of the registration: " + ("device pose" if loop.device_guess else "host pose"))
+        if estimator is None:
+            step = loop.step(scan)
+        else:
+            step = loop.step(scan, **frame_motion(estimator, len(stamps)))
+            estimates.append(step.estimate)
         finish(stamp, None, step.filter_result)
         p = step.pose_result
         err_t = float(np.linalg.norm(step.pose[:3, 3] - T[:3, 3]))
@@ -195,8 +207,28 @@ def closed_loop(name, f, pc_map, replay, finish, traj_out, which="icp", hypothes
     if loop is not None and stamps:
         ape = ape_translation(loop.poses, ref)
         print(f"APE translation (m) over {len(stamps)} frames: " + " ".join(f"{k}: {v:.4f}" for k, v in ape.items()))
+        if estimates:
+            ape = ape_translation(estimates, ref)
+            print(f"APE translation (m) of the estimator over {len(stamps)} frames: " + " ".join(f"{k}: {v:.4f}" for k, v in ape.items()))
     if traj_out:
         write_trajectory(traj_out, stamps, loop.poses if loop is not None else [])
+
+
+def frame_motion(estimator, k):
+    """the keywords of LocalisationLoop.step for frame k: the IMU rows of the interval that ends at scan k (scan k is at
+    k * scan_period), or the interval alone"""
+    S, imu = estimator["scan_period"], estimator["imu"]
+    if imu is None or k == 0:
+        return dict(dt=S)
+    if np.ndim(imu) == 0:                                         # a rate: the synthetic sequence's own rows (it moves straight)
+        from sps_amd import synthetic
+        return dict(imu=synthetic.sequence_imu(2, scan_period=S, rate=float(imu))[1])
+    rows = imu[(imu[:, 0] > (k - 1) * S) & (imu[:, 0] <= k * S)]
+    if not len(rows):
+        return dict(dt=S)
+    out = rows.copy()
+    out[:, 0] = np.diff(np.concatenate([[(k - 1) * S], rows[:, 0]]))
+    return dict(imu=out)
 
 
 @click.command()
@@ -241,9 +273,40 @@ def closed_loop(name, f, pc_map, replay, finish, traj_out, which="icp", hypothes
 @click.option("--level-capacities", "level_capacities", type=str, default=None,
               help="with --resolutions and --update-map or --carve-map: C0,C1,... cells every level of the online pyramid has "
                    "room for (default per level: twice its cells, at least 4096)")
+@click.option("--estimator", "estimator", type=click.Choice(("ukf",)), default=None,
+              help="with --localise: the guess of every frame is the prediction of the device UKF pose estimator, which the "
+                   "registered pose corrects; a second APE line is the estimator's")
+@click.option("--initial-velocity", "initial_velocity", type=str, default="0,0,0",
+              help="with --estimator: VX,VY,VZ in m/s, map frame (the filter learns a velocity slowly from zero)")
+@click.option("--scan-period", "scan_period", type=float, default=0.1, help="with --estimator: seconds between scans")
+@click.option("--imu-rate", "imu_rate", type=float, default=None,
+              help="with --estimator and --synthetic: predict with the synthetic sequence's exact IMU rows at this rate in Hz")
+@click.option("--imu", "imu_file", type=str, default=None,
+              help="with --estimator: a text file of rows `t ax ay az gx gy gz`, scan k being at k * scan-period")
 def main(name, weights, sequence, config, epsilon, out_dir, n_synth, localise, which, traj_out, hyp_counts, hyp_steps,
          search_counts, search_steps, update_map, cell_capacity, max_cell_points, carve_map, carve_miss_frames, carve_sigma,
-         resolutions, level_iterations, level_capacities):
+         resolutions, level_iterations, level_capacities, estimator, initial_velocity, scan_period, imu_rate, imu_file):
+    if estimator is None and (initial_velocity != "0,0,0" or imu_rate is not None or imu_file is not None):
+        raise click.UsageError("--initial-velocity, --imu-rate and --imu need --estimator")
+    if estimator is not None:
+        if not localise:
+            raise click.UsageError("--estimator needs --localise")
+        if imu_rate is not None and imu_file is not None:
+            raise click.UsageError("give --imu-rate or --imu, not both")
+        if imu_rate is not None and not n_synth:
+            raise click.UsageError("--imu-rate makes the synthetic sequence's IMU rows: it needs --synthetic")
+        try:
+            vel = tuple(float(v) for v in initial_velocity.split(","))
+        except ValueError:
+            vel = ()
+        if len(vel) != 3 or not scan_period > 0 or (imu_rate is not None and not imu_rate > 0):
+            raise click.UsageError("--initial-velocity takes VX,VY,VZ; --scan-period and --imu-rate must be > 0")
+        imu = imu_rate
+        if imu_file is not None:
+            imu = np.loadtxt(imu_file, dtype=np.float64, ndmin=2)
+            if imu.shape[1] != 7 or not np.isfinite(imu).all() or (np.diff(imu[:, 0]) <= 0).any():
+                raise click.UsageError("--imu: rows `t ax ay az gx gy gz`, finite, t strictly increasing")
+        estimator = dict(initial_velocity=vel, scan_period=float(scan_period), imu=imu)
     if carve_map and which != "ndt":
         raise click.UsageError("--carve-map needs --localise --localiser ndt")
     if (carve_miss_frames is not None or carve_sigma is not None) and not carve_map:
@@ -323,7 +386,8 @@ def main(name, weights, sequence, config, epsilon, out_dir, n_synth, localise, w
 
     if localise:
         closed_loop(name, f, pc_map, replay, finish, traj_out, which or "icp", hypotheses, search, update_map, cell_capacity,
-                    max_cell_points, resolutions, level_iterations, carve_map, carve_options or None, level_capacities)
+                    max_cell_points, resolutions, level_iterations, carve_map, carve_options or None, level_capacities,
+                    estimator)
     elif traj_out:
         raise click.UsageError("--traj-out needs --localise")
     in_flight, prev_pose = None, None

@@ -159,6 +159,11 @@ def _load() -> C.CDLL:
         "sps_ndt_pyramid_carve": (i32, [vp, vp, vp, i64, vp, vp, vp, vp, C.c_double, i32, i32, i32, vp, vp, vp]),
         "sps_ndt_pyramid_info": (i32, [vp, i32, vp]),
         "sps_ndt_pyramid_carve_cells": (i32, [vp, i32, vp, vp, vp]),
+        "sps_ukf_state_bytes": (i64, []),
+        "sps_ukf_init": (i32, [vp, vp, vp, vp, vp]),
+        "sps_ukf_predict": (i32, [vp, vp, i32, vp, vp, vp, vp]),
+        "sps_ukf_predict_dt": (i32, [vp, C.c_double, vp, vp, vp, vp]),
+        "sps_ukf_correct": (i32, [vp, vp, vp, vp, vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)          # AttributeError here = header/library mismatch: fail loudly
@@ -193,7 +198,9 @@ EXPORTS = ["sps_last_error", "sps_version", "sps_ctx_create", "sps_ctx_destroy",
            "sps_ndt_map_carve_scratch", "sps_ndt_map_carve", "sps_ndt_map_carve_cells",
            "sps_ndt_pyramid_build", "sps_ndt_pyramid_cells", "sps_ndt_pyramid_align_scratch", "sps_ndt_pyramid_align",
            "sps_ndt_pyramid_build_dynamic", "sps_ndt_pyramid_update_scratch", "sps_ndt_pyramid_update",
-           "sps_ndt_pyramid_carve_scratch", "sps_ndt_pyramid_carve", "sps_ndt_pyramid_info", "sps_ndt_pyramid_carve_cells"]
+           "sps_ndt_pyramid_carve_scratch", "sps_ndt_pyramid_carve", "sps_ndt_pyramid_info", "sps_ndt_pyramid_carve_cells",
+           "sps_ukf_state_bytes", "sps_ukf_init", "sps_ukf_predict", "sps_ukf_predict_dt", "sps_ukf_correct"]
+UKF_MAX_IMU = 256          # SPS_UKF_MAX_IMU
 CROP_BLOCK = 1024          # SPS_CROP_BLOCK: map rows per int of sps_radius_crop's scratch
 
 

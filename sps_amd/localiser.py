@@ -15,7 +15,9 @@ synchronises; ``PendingPose.result()`` is the one synchronisation.  A scan that 
 
 ``NDTLocaliser`` is the same stage with the registration the experiment actually runs: a normal-distributions
 transform (ndt_omp's 1 m cells and DIRECT7 neighbourhood by default; C ABI: the "NDT localiser" section; DESIGN.md
-"NDT localiser").  Thinning, the 6 x 6 solve, the outputs and the status codes are the ICP's; still no UKF, no IMU.
+"NDT localiser").  Thinning, the 6 x 6 solve, the outputs and the status codes are the ICP's.  The package's other two
+parts, the UKF and its IMU prediction, are ``sps_amd.pose_estimator.PoseEstimator``, which
+``LocalisationLoop(..., estimator=...)`` puts around either localiser.
 
 ``NDTLocaliser.submit_batch`` registers one scan from several start poses in the same launches and selects among the
 end poses by the NDT score at each (C ABI: "NDT localiser, several hypotheses"): a start in the wrong basin
@@ -791,6 +793,36 @@ class NDTLocaliser(ScanToMapLocaliser):
             host, ev = self._to_host(out, st)
         return PendingPoses(K, I, with_normal, host, ev, (rows, n_dev, out, T_host, T_dev), upd=integrate, carve=carve)
 
+    @torch.no_grad()
+    def submit_from_device(self, rows, count, T_init_dev, with_normal: bool = False, iterations: int = None,
+                           integrate: bool = False, max_cell_points: int = 0, carve: bool = False,
+                           carve_options: dict = None) -> PendingPoses:
+        """``submit_batch`` with one hypothesis whose start pose is already on the device: ``T_init_dev`` holds 16 contiguous
+        float64 entries (a row-major 4 x 4, e.g. ``PoseEstimator.pose_dev``) that work issued earlier on the current stream
+        may still be writing.  The host never sees the pose; hypothesis 0 of the result is what ``submit`` gives from the
+        same pose, bit for bit.  A pose that is not finite ends as such a pose does in ``sps_ndt_align_batch``."""
+        self._check_integrate(integrate, max_cell_points, single_map=True)
+        copts = self._check_carve(carve, carve_options, single_map=True)
+        rows = self._checked_rows(rows)
+        T_dev = T_init_dev
+        if not (torch.is_tensor(T_dev) and T_dev.is_cuda and T_dev.device == self.device and T_dev.dtype == torch.float64
+                and T_dev.numel() == 16 and T_dev.is_contiguous()):
+            raise TypeError("T_init_dev must be 16 contiguous float64 entries on the localiser's device")
+        n_max, dev = rows.shape[0], self.device
+        I = self.iterations if iterations is None else int(iterations)
+        o = _batch_layout(1, I, with_normal)
+        with torch.cuda.device(dev):
+            st = torch.cuda.current_stream()
+            s = st.cuda_stream
+            n_dev = self._count_on_device(count, n_max)
+            out = torch.zeros(o["size"] + (2 if integrate else 0) + (2 if carve else 0), dtype=torch.float64, device=dev)
+            base = out.data_ptr()
+            self._thin(rows, n_dev, n_max, base + o["n_points"] * 8, s)
+            self._align_batch(base + o["n_points"] * 8, T_dev.data_ptr(), 1, I, with_normal, base, o, s, integrate, max_cell_points,
+                              copts)
+            host, ev = self._to_host(out, st)
+        return PendingPoses(1, I, with_normal, host, ev, (rows, n_dev, out, None, T_dev), upd=integrate, carve=carve)
+
     def submit_filtered_batch(self, pending, T_inits, **kw) -> PendingPoses:
         """``submit_batch`` of the kept rows of a pending SPSFilter / SPSCVMFilter frame, without the frame's result()."""
         return self.submit_batch(pending._filtered, pending.count_dev, T_inits, **kw)
@@ -936,6 +968,7 @@ class LoopStep:
     flagged: bool              # the localiser reported status 2 or 3 (with hypotheses: none of them was selected)
     batch: BatchPoseResult = None   # with hypotheses: every hypothesis of the frame (pose_result is the selected one's)
     search: RelocalisationResult = None   # a frame registered by the pose search (batch is then its candidates' batch)
+    estimate: np.ndarray = None     # with an estimator: its pose after the frame's correction (None without one)
 
 
 class LocalisationLoop:
@@ -973,10 +1006,26 @@ class LocalisationLoop:
 
     ``carve_map`` (the same localisers): every frame's kept points are also cast as rays from the corrected pose and the
     map is carved (``NDTLocaliser.carve``; ``carve_options``: its keywords), under the same gate and before the update;
-    the frame's ``pose_result.map_carve`` (``batch.map_carve``) tells what happened."""
+    the frame's ``pose_result.map_carve`` (``batch.map_carve``) tells what happened.
+
+    ``estimator`` (a ``PoseEstimator``; None: everything above, unchanged): the guess of a frame is then the estimator's
+    prediction -- ``step(scan, imu=rows)`` or ``step(scan, dt=seconds)`` say over what; frame 0 makes no prediction step
+    and starts from the estimator's initial pose -- and the estimator's correction with the registered pose is queued
+    behind the registration, gated on the device by its status as the map update and the carve are: a flagged frame keeps
+    the guess and leaves the estimator uncorrected.  ``LoopStep.pose`` stays the registration's pose (where the map was
+    updated and carved); ``LoopStep.estimate`` is the estimator's pose after the correction.  The loop's own
+    constant-velocity model still receives the poses but is not asked.
+    ``device_guess`` (None: where possible): the predicted pose starts the registration from the device
+    (predict -> ``submit_from_device`` -> ``correct_from``, the guess read back with the frame's results: the one
+    synchronisation per frame of the loop without an estimator).  That is possible where the filter takes no pose from the
+    loop (SPSCVMFilter, LTSFilter, ``takes_pose`` false) and the localiser is an NDTLocaliser without a pyramid, hypotheses
+    or search; the frame's ``batch`` is then the one-hypothesis batch.  Everywhere else, and with ``device_guess=False``, the
+    predicted pose is fetched to the host first: one more small synchronisation per frame.  ``device_guess=True`` raises
+    where the device path is impossible."""
 
     def __init__(self, filter, localiser, initial_pose, hypotheses=None, search=None, search_keep: int = 8,
-                 update_map: bool = False, max_cell_points: int = 0, carve_map: bool = False, carve_options: dict = None):
+                 update_map: bool = False, max_cell_points: int = 0, carve_map: bool = False, carve_options: dict = None,
+                 estimator=None, device_guess=None):
         from .sps_filters import ConstantVelocityModel
         self.filter, self.localiser = filter, localiser
         self.update_map, self.max_cell_points = bool(update_map), int(max_cell_points)
@@ -1016,12 +1065,30 @@ class LocalisationLoop:
             if not hasattr(localiser, "submit_batch"):
                 raise TypeError("hypotheses need a localiser with submit_batch (NDTLocaliser)")
             self.hypotheses = H
+        self.estimator, self.device_guess = estimator, False
+        if estimator is None:
+            if device_guess:
+                raise ValueError("device_guess needs an estimator")
+        else:
+            if not all(hasattr(estimator, a) for a in ("predict", "predict_imu", "pose_dev", "correct_from", "snapshot")):
+                raise TypeError("estimator must be a PoseEstimator")
+            takes_none = (hasattr(filter, "add_pose") or type(filter).__name__ == "LTSFilter"
+                          or getattr(filter, "takes_pose", True) is False)
+            possible = (takes_none and hasattr(localiser, "submit_from_device") and getattr(localiser, "resolutions", None) is None
+                        and hypotheses is None and search is None)
+            if device_guess and not possible:
+                raise ValueError("device_guess=True needs a filter that takes no pose from the loop and an NDTLocaliser without "
+                                 "a pyramid, hypotheses or search")
+            self.device_guess = possible if device_guess is None else bool(device_guess)
+        self._est_guess, self._est_wait, self._frames = None, None, 0
         self.initial_pose = np.array(_pose(initial_pose), dtype=np.float64)
         self.model = ConstantVelocityModel()
         self.model.poses = []                                        # corrected poses only
         self.poses = []                                              # the corrected pose of every frame
 
     def guess(self) -> np.ndarray:
+        if self.estimator is not None:                               # the prediction step() fetched for this frame
+            return self._est_guess.copy() if self._est_guess is not None else self.initial_pose.copy()
         if len(self.model.poses) >= 4:
             return self.model.predict()
         if self.model.poses:
@@ -1047,19 +1114,22 @@ class LocalisationLoop:
         starts = self.start_poses(guess)
         if hasattr(pend, "count_dev") and hasattr(pend, "_filtered"):
             pose_pend = self.localiser.submit_filtered_batch(pend, starts, **self._kw)
+            self._queue_correction(pose_pend)
             fres = pend.result()
             bres = pose_pend.result()
         else:
             fres = pend.result()
             kept = fres.filtered
-            bres = self.localiser.submit_batch(kept, len(kept), starts, **self._kw).result()
+            pose_pend = self.localiser.submit_batch(kept, len(kept), starts, **self._kw)
+            self._queue_correction(pose_pend)
+            bres = pose_pend.result()
         flagged = bres.best < 0
         pose = guess if flagged else bres.pose
         self.model.add_pose(pose)
         if hasattr(self.filter, "add_pose"):
             self.filter.add_pose(pose)
         self.poses.append(np.array(pose, dtype=np.float64))
-        return LoopStep(fres, bres.results[max(bres.best, 0)], guess, self.poses[-1], flagged, bres)
+        return LoopStep(fres, bres.results[max(bres.best, 0)], guess, self.poses[-1], flagged, bres, estimate=self._estimate())
 
     def search_poses(self, guess) -> np.ndarray:
         """[P, 4, 4]: ``guess @ search[k]``"""
@@ -1070,12 +1140,15 @@ class LocalisationLoop:
         poses = self.search_poses(guess)
         if hasattr(pend, "count_dev") and hasattr(pend, "_filtered"):
             pose_pend = self.localiser.relocalise_filtered(pend, poses, keep=self.search_keep, **self._kw)
+            self._queue_correction(pose_pend)
             fres = pend.result()
             sres = pose_pend.result()
         else:
             fres = pend.result()
             kept = fres.filtered
-            sres = self.localiser.relocalise(kept, len(kept), poses, keep=self.search_keep, **self._kw).result()
+            pose_pend = self.localiser.relocalise(kept, len(kept), poses, keep=self.search_keep, **self._kw)
+            self._queue_correction(pose_pend)
+            sres = pose_pend.result()
         bres = sres.batch
         flagged = sres.index < 0
         pose = guess if flagged else sres.pose
@@ -1084,9 +1157,66 @@ class LocalisationLoop:
         if hasattr(self.filter, "add_pose"):
             self.filter.add_pose(pose)
         self.poses.append(np.array(pose, dtype=np.float64))
-        return LoopStep(fres, bres.results[max(bres.best, 0)], guess, self.poses[-1], flagged, bres, sres)
+        return LoopStep(fres, bres.results[max(bres.best, 0)], guess, self.poses[-1], flagged, bres, sres, self._estimate())
 
-    def step(self, scan) -> LoopStep:
+    def _queue_correction(self, pose_pend):
+        """with an estimator: its correction behind the registration just issued, then a copy of its state for the host"""
+        if self.estimator is not None:
+            self.estimator.correct_from(pose_pend)
+            self._est_wait = self.estimator.snapshot()
+
+    def _estimate(self):
+        if self.estimator is None:
+            return None
+        wait, self._est_wait = self._est_wait, None
+        return wait()[0].pose
+
+    def _predict(self, imu, dt):
+        """the estimator's prediction for this frame, queued; frame 0 makes no step"""
+        est = self.estimator
+        if self._frames == 0 or (imu is not None and len(imu) == 0):
+            est.predict_imu(np.zeros((0, 7)))
+        elif imu is not None:
+            est.predict_imu(imu)
+        elif dt is not None:
+            est.predict(dt)
+        else:
+            raise ValueError("with an estimator every frame after the first needs imu=rows or dt=seconds")
+        self._frames += 1
+
+    def _step_device(self, scan) -> LoopStep:
+        """predict -> filter -> submit_from_device(pose_dev) -> correct_from, then the frame's results and the guess"""
+        est, loc = self.estimator, self.localiser
+        pend = self._submit_filter(scan, None)
+        if hasattr(pend, "count_dev") and hasattr(pend, "_filtered"):
+            pose_pend = loc.submit_from_device(pend._filtered, pend.count_dev, est.pose_dev, **self._kw)
+            self._queue_correction(pose_pend)
+            fres = pend.result()
+        else:
+            fres = pend.result()
+            kept = fres.filtered
+            pose_pend = loc.submit_from_device(kept, len(kept), est.pose_dev, **self._kw)
+            self._queue_correction(pose_pend)
+        bres = pose_pend.result()
+        state, guess = self._est_wait()
+        self._est_wait = None
+        flagged = bres.best < 0
+        pose = guess if flagged else bres.pose
+        self.model.add_pose(pose)
+        if hasattr(self.filter, "add_pose"):
+            self.filter.add_pose(pose)
+        self.poses.append(np.array(pose, dtype=np.float64))
+        return LoopStep(fres, bres.results[0], guess, self.poses[-1], flagged, bres, estimate=state.pose)
+
+    def step(self, scan, imu=None, dt=None) -> LoopStep:
+        if self.estimator is None:
+            if imu is not None or dt is not None:
+                raise ValueError("imu and dt need an estimator")
+        else:
+            self._predict(imu, dt)
+            if self.device_guess:
+                return self._step_device(scan)
+            self._est_guess = self.estimator.pose_dev.cpu().numpy().astype(np.float64)   # the one more synchronisation
         if self.search is not None:
             if self._search_next:
                 return self._step_search(scan, self.guess())
@@ -1102,16 +1232,19 @@ class LocalisationLoop:
         pend = self._submit_filter(scan, guess)
         if hasattr(pend, "count_dev") and hasattr(pend, "_filtered"):
             pose_pend = self.localiser.submit_filtered(pend, guess, **self._kw)  # no synchronisation between filter and localiser
+            self._queue_correction(pose_pend)
             fres = pend.result()
             pres = pose_pend.result()
         else:
             fres = pend.result()
             kept = fres.filtered
-            pres = self.localiser.submit(kept, len(kept), guess, **self._kw).result()
+            pose_pend = self.localiser.submit(kept, len(kept), guess, **self._kw)
+            self._queue_correction(pose_pend)
+            pres = pose_pend.result()
         flagged = pres.status in (FEW_CORRESPONDENCES, SINGULAR)
         pose = guess if flagged else pres.pose
         self.model.add_pose(pose)
         if hasattr(self.filter, "add_pose"):
             self.filter.add_pose(pose)
         self.poses.append(np.array(pose, dtype=np.float64))
-        return LoopStep(fres, pres, guess, self.poses[-1], flagged)
+        return LoopStep(fres, pres, guess, self.poses[-1], flagged, estimate=self._estimate())

@@ -185,3 +185,31 @@ def collate(items, ) -> np.ndarray:
         q[:, 0] = b
         out.append(q)
     return np.concatenate(out, 0)
+
+
+def sequence_imu(n_scans: int, step: float = 0.5, scan_period: float = 0.1, rate: float = 100.0, yaw_rate: float = 0.0):
+    """The exact IMU rows of the synthetic sequence's motion: a list of ``n_scans`` float64 arrays [M, 7] of rows
+    (dt, ax, ay, az, gx, gy, gz) in the body frame, entry k covering the interval that ends at scan k (entry 0 is empty:
+    nothing moves before the first scan).  The sensor advances ``step`` m per ``scan_period`` s at constant speed;
+    ``rate`` Hz samples, M = round(scan_period * rate) >= 1 per interval, each of dt = scan_period / M.  With
+    ``yaw_rate`` (rad/s) the path is a circle driven at that speed: the gyroscope reads (0, 0, yaw_rate) and the
+    accelerometer the centripetal speed * yaw_rate along +y; on the straight line (``make_sequence``) both are zero.
+    Gravity is left out of the accelerometer: the estimator does not use the acceleration."""
+    if not (scan_period > 0 and rate > 0):
+        raise ValueError("scan_period and rate must be > 0")
+    M = max(1, int(round(scan_period * rate)))
+    speed = step / scan_period
+    row = np.array([scan_period / M, 0.0, speed * yaw_rate, 0.0, 0.0, 0.0, yaw_rate], dtype=np.float64)
+    return [np.zeros((0, 7))] + [np.tile(row, (M, 1)) for _ in range(1, n_scans)]
+
+
+def circle_poses(n_scans: int, step: float = 0.5, scan_period: float = 0.1, yaw_rate: float = 0.5) -> np.ndarray:
+    """[n_scans, 4, 4]: the true poses of ``sequence_imu(..., yaw_rate=yaw_rate)`` from the identity, heading along +x"""
+    out = np.tile(np.eye(4), (n_scans, 1, 1))
+    speed = step / scan_period
+    for k in range(n_scans):
+        th = yaw_rate * scan_period * k
+        c, s = np.cos(th), np.sin(th)
+        out[k, :2, :2] = [[c, -s], [s, c]]
+        out[k, :2, 3] = [speed * k * scan_period, 0.0] if yaw_rate == 0 else [speed / yaw_rate * s, speed / yaw_rate * (1.0 - c)]
+    return out

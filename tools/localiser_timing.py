@@ -38,6 +38,12 @@ carve=True) against the pyramid's plain submit.
 submit and submit(integrate=True, carve=True), interleaved frame by frame, and (with --cpu-frames >= 1) the restatement's
 count of the cells a ray visits on one frame.
 
+``--localiser ndt --estimator`` times the pose estimator (sps_amd.pose_estimator.PoseEstimator) beside the registration:
+sps_ukf_predict over M = 1, 10 and 40 IMU rows already on the device, predict_imu of the same rows (with their pinned
+upload), the IMU-less step and the correction (hipEvents around each, a prediction and a correction alternating so the
+state stays that of a running filter); then LocalisationLoop(SPSCVMFilter, NDTLocaliser) per frame (host wall clock)
+without an estimator, with one on the device path and with one on the host path, the three alternating frame by frame.
+
 ``--one-frame`` runs a warm-up and ONE localiser frame: the target of a ``rocprofv3 --kernel-trace --stats`` run.
 """
 import argparse
@@ -133,7 +139,11 @@ def main():
                     "pyramid beside the single-map localiser, in the same session")
     ap.add_argument("--iterations", type=int, default=30, help="with --resolutions: the pyramid's budget of slots")
     ap.add_argument("--level-iterations", type=str, default=None, help="with --resolutions: N0,N1,... the cap of every level")
+    ap.add_argument("--estimator", action="store_true", help="with --localiser ndt: time the UKF pose estimator's calls and the "
+                    "loop with it, on the device path and the host path")
     a = ap.parse_args()
+    if a.estimator and (a.localiser != "ndt" or a.hypotheses or a.search or a.update_map or a.carve or a.resolutions):
+        ap.error("--estimator needs --localiser ndt and none of the other modes")
     if a.resolutions and (a.localiser != "ndt" or a.hypotheses or a.search):
         ap.error("--resolutions needs --localiser ndt and none of --hypotheses, --search")
     if a.carve and (a.localiser != "ndt" or a.hypotheses or a.search or (a.update_map and not a.resolutions)):
@@ -151,6 +161,8 @@ def main():
     dscans = [torch.from_numpy(s).cuda() for s in scans]
     mp = synthetic.build_map()
     T_init = LR.perturbation(0.15, 0.12, 0.05, 1.0)
+    if a.estimator:
+        return ndt_estimator_main(a, scans, dscans, mp, T_init)
     if a.localiser == "ndt" and a.resolutions and (a.update_map or a.carve):
         return ndt_online_pyramid_main(a, dscans, mp, T_init)
     if a.localiser == "ndt" and a.update_map:
@@ -685,6 +697,86 @@ def ndt_online_pyramid_main(a, dscans, mp, T_init):
     for name, v in t.items():
         out[name] = stats(v)
         print(f"{name:22s} median {out[name]['median']:.4f} (min {out[name]['min']:.4f} max {out[name]['max']:.4f})", flush=True)
+    print(json.dumps(out))
+
+
+def ndt_estimator_main(a, scans, dscans, mp, T_init):
+    """--estimator: the estimator's calls under hipEvents, then the loop with and without it (see the module docstring).
+    The sensor stands still at I, so the estimator runs with zero velocity and a 0.1 s scan period."""
+    from sps_amd import _native
+    from sps_amd.pose_estimator import PoseEstimator
+    map64 = mp[:, :3].astype(np.float64)
+    ndt = NDTLocaliser(map64)
+    net = net_from_params(O.random_params(seed=0)).cuda().eval().freeze()
+    mpt = torch.from_numpy(mp)
+    st = torch.cuda.current_stream()
+    I4 = np.eye(4)
+
+    def make_loop(mode):
+        est = None if mode == "none" else PoseEstimator(I4, "cuda")
+        return LocalisationLoop(SPSCVMFilter(net, mpt, voxel_size=VS, epsilon=EPS), ndt, I4, estimator=est,
+                                device_guess=None if mode == "none" else mode == "device")
+
+    if a.one_frame:
+        loop = make_loop("device")
+        for k in range(a.warmup):
+            loop.step(scans[k % len(scans)], dt=0.1)
+        torch.cuda.synchronize()
+        step = loop.step(scans[a.warmup % len(scans)], imu=synthetic.sequence_imu(2, step=0.0, rate=100.0)[1])
+        print(json.dumps({"one_frame": True, "localiser": "ndt", "estimator": True, "status": step.pose_result.status,
+                          "iterations": step.pose_result.iterations, "flagged": bool(step.flagged)}))
+        return
+
+    def stats(v):
+        return {"median": round(float(np.median(v)), 4), "min": round(min(v), 4), "max": round(max(v), 4)}
+    out = {"frames": a.frames, "warmup": a.warmup, "n_map": len(mp)}
+    est = PoseEstimator(I4, "cuda")
+    T_meas = torch.from_numpy(np.ascontiguousarray(LR.perturbation(0.01, -0.01, 0.0, 0.1))).cuda()
+    rows = {M: synthetic.sequence_imu(2, step=0.0, scan_period=0.1, rate=10.0 * M)[1] for M in (1, 10, 40)}
+    drows = {M: torch.from_numpy(r).cuda() for M, r in rows.items()}
+    t = {}
+
+    def kernel_only(M):
+        _native.check(_native.lib.sps_ukf_predict(est._state_ptr, drows[M].data_ptr(), M, est._Q, est._pred_ptr, est._pinfo_ptr,
+                                                  st.cuda_stream))
+    calls = [(f"predict_kernel_M{M}", lambda M=M: kernel_only(M)) for M in (1, 10, 40)]
+    calls += [(f"predict_imu_M{M}", lambda M=M: est.predict_imu(rows[M])) for M in (1, 10, 40)]
+    calls += [("predict_dt", lambda: est.predict(0.1))]
+    for k in range(a.warmup + a.frames):
+        for name, call in calls:                                     # a correction behind every prediction
+            e = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
+            e[0].record(st)
+            call()
+            e[1].record(st)
+            e[2].record(st)
+            est.correct(T_meas)
+            e[3].record(st)
+            e[3].synchronize()
+            if k >= a.warmup:
+                t.setdefault(name, []).append(e[0].elapsed_time(e[1]))
+                t.setdefault("correct", []).append(e[2].elapsed_time(e[3]))
+    s = est.state()
+    assert s.status == 0 and s.predict_status == 0, (s.status, s.predict_status)
+    ms, _, _, _ = timed_frames(ndt, dscans, T_init, a.warmup, a.frames)
+    t["ndt_submit"] = ms
+    for name, v in t.items():
+        out[name + "_ms"] = stats(v)
+        print(f"{name:22s} median {out[name + '_ms']['median']:.4f} ms (min {min(v):.4f} max {max(v):.4f})", flush=True)
+    loops = {m: make_loop(m) for m in ("none", "device", "host")}
+    t_loop, flagged = {m: [] for m in loops}, {m: 0 for m in loops}
+    for k in range(a.warmup + a.frames):
+        for m, loop in loops.items():                                # alternating: all three see the same machine state
+            sc = scans[k % len(scans)]
+            t0 = time.perf_counter()
+            step = loop.step(sc) if m == "none" else loop.step(sc, dt=0.1)
+            if k >= a.warmup:
+                t_loop[m].append((time.perf_counter() - t0) * 1e3)
+                flagged[m] += step.flagged
+    for m in loops:
+        out[f"loop_{m}_ms"] = stats(t_loop[m])
+        out[f"loop_{m}_flagged"] = int(flagged[m])
+        print(f"LocalisationLoop(sps_cvm, ndt), estimator {m:6s} median {out[f'loop_{m}_ms']['median']:.3f} ms per frame "
+              f"(min {min(t_loop[m]):.3f} max {max(t_loop[m]):.3f}; {flagged[m]} flagged)", flush=True)
     print(json.dumps(out))
 
 
