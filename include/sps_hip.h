@@ -789,6 +789,66 @@ int sps_ndt_pyramid_carve(sps_ctx *ctx, const double *pts_dev, const int32_t *n_
 int sps_ndt_pyramid_info(sps_ctx *ctx, int level, int64_t *out_host);
 int sps_ndt_pyramid_carve_cells(sps_ctx *ctx, int level, int32_t *pass_out_dev, int32_t *hit_out_dev, int32_t *miss_out_dev);
 
+/* ---- NDT localiser, distribution to distribution ------------------------------------------------------------------------
+ * hdl_localization's other registration family (reg_method NDT_CUDA_D2D / VGICP): the scan is reduced to Gaussians too, one
+ * per cell of the sensor frame, and Gaussians are registered against Gaussians.    Additive: sps_version()
+ * is unchanged.  The rules of sps_ndt_align hold (float64, every operation rounded on its own, no float atomics, no sum
+ * whose order depends on thread arrival); neither call allocates, synchronises or raises the sticky error.
+ *
+ * sps_ndt_source_build: pts_dev is sps_loc_downsample's output (f64 [cap][3], sensor frame), of which the first
+ *   min(cap, *n_dev) rows are used; cap <= SPS_NDT_UPDATE_MAX_POINTS.
+ *   - The cell of a point is floor(p / source_resolution) per axis (a true division, as the map's); a non-finite coordinate
+ *     or a cell index beyond +-1048575 skips the point.
+ *   - Source cell j is the j-th cell in ascending order of the lowest point index that falls in it (the founder rule of
+ *     sps_ndt_map_update).
+ *   - Per cell: n, mean = (sum of the points in ascending point index) / n, S = sum (p - mean)(p - mean)^T in the same
+ *     order (the operation order of sps_ndt_map_build: sum, divide, second pass of outer products).
+ *   - Record, SPS_NDT_SRC_REC doubles: mean[3], covariance[6] (xx, xy, xz, yy, yz, zz), valid (1.0 / 0.0).  The covariance
+ *     is S / (n - 1), decomposed by the 8 cyclic Jacobi sweeps of the map, its eigenvalues floored at eig_ratio * lambda_max,
+ *     and reassembled, entry (i, j) = ((v_i0 v_j0) l0 + (v_i1 v_j1) l1) + (v_i2 v_j2) l2; zero for n < 2.
+ *   - Valid iff n >= min_points, n >= 2, lambda_max > 0 and every number of the record is finite.  Invalid cells keep their
+ *     slot, flagged.
+ *   - n_src_dev = (cells, valid cells).  src_count_dev (may be NULL): n per cell.  Rows of src_dev and src_count_dev beyond
+ *     the cells are not written.  *n_dev = 0 gives (0, 0); cap = 0 is legal.
+ *   The grouping is the online update's: its kernels' bodies run against an empty map of capacity `cap` in the scratch, at
+ *   the identity pose.  Launches: seven and four memsets, whatever the data.  scratch_dev: sps_ndt_source_scratch(cap)
+ *   bytes (-1 for cap out of range), 256-byte aligned.
+ *
+ * sps_ndt_align_d2d: sps_ndt_align with launch A replaced; launch B, the partial rows (one per 32 sources), the outputs,
+ *   the status codes, "T_out = T_init bit for bit on 2 / 3" and the checks of the arguments are sps_ndt_align's.  It runs
+ *   against the map of the context, static or online; d1 and d2 come from outlier_ratio and the MAP's resolution.
+ *   src_dev [cap_src][SPS_NDT_SRC_REC] and n_src_dev are sps_ndt_source_build's (or hand-made); the first
+ *   min(cap_src, n_src_dev[0]) records are read and the valid ones used.
+ *   Launch A, per valid source (mu, C) at the pose (R, t):
+ *     q = R mu + t, per axis ((R0 mu0 + R1 mu1) + R2 mu2) + t;
+ *     Cw = R C R^T: U = R C first, every entry (a0 b0 + a1 b1) + a2 b2, then Cw = U R^T the same way;
+ *     cells: q's own, then +x, -x, +y, -y, +z, -z (neighbours = 7) or q's own (1), by the map's cell rule;
+ *     per valid map record (mean m, inverse covariance A): Sm = inv3(A), M = Sm + Cw entry by entry, B = inv3(M),
+ *       x = q - m, y = B x (rows as (B0 x0 + B1 x1) + B2 x2), s = (x0 y0 + x1 y1) + x2 y2, e = exp(-0.5 (d2 s)), w = d2 e;
+ *       the cell is skipped unless 0 <= w <= 1 (NaN skips), and if either inv3 met det <= 0 or a non-finite entry;
+ *     inv3 of (m0 .. m5) = (xx, xy, xz, yy, yz, zz): c00 = m3 m5 - m4 m4, c01 = m2 m4 - m1 m5, c02 = m1 m4 - m2 m3,
+ *       c11 = m0 m5 - m2 m2, c12 = m1 m2 - m0 m4, c22 = m0 m3 - m1 m1, det = (m0 c00 + m1 c01) + m2 c02, every entry
+ *       c / det by a true division;
+ *     with a = (-d1) w and J = [-[q]x | I] at q: H(r, c) += a (J_r . (B J_c)), g(r) += a (J_r . y), score += (-d1) e; a
+ *       source with at least one contributing cell counts once.
+ *   Orders: cells in lookup order within a source, sources in index order within a workgroup of 32, workgroups as launch B
+ *   adds them.  The step is the house's: B is held at the current pose (its dependence on R is not differentiated), H is
+ *   the positive-semidefinite part only, H delta = -g is taken at unit length, and sources are not weighted by their point
+ *   counts.  Status 2: fewer than min_corr SOURCES counted.  trace_dev = (sources counted, score, |v|, |omega|) per
+ *   iteration.  The map keeps its layout: its covariance is recovered from the record's inverse covariance, whose
+ *   condition number the eigenvalue floor keeps <= 1 / eig_ratio.  Launches: 1 + 2 * iters and up to two memsets.
+ *   scratch_dev: sps_ndt_align_d2d_scratch(cap_src) bytes (-1 for cap_src out of range). */
+#define SPS_NDT_SRC_REC 10
+int64_t sps_ndt_source_scratch(int64_t cap);
+int sps_ndt_source_build(sps_ctx *ctx, const double *pts_dev, const int32_t *n_dev, int64_t cap, double source_resolution,
+                         int min_points, double eig_ratio, double *src_dev, int32_t *src_count_dev, int32_t *n_src_dev,
+                         void *scratch_dev, void *stream);
+int64_t sps_ndt_align_d2d_scratch(int64_t cap_src);
+int sps_ndt_align_d2d(sps_ctx *ctx, const double *src_dev, const int32_t *n_src_dev, int64_t cap_src,
+                      const double *T_init_host, int iters, int neighbours, int min_corr, double outlier_ratio, double tol_t,
+                      double tol_r, double *T_out_dev, int32_t *status_dev, double *trace_dev, double *normal_dev,
+                      void *scratch_dev, void *stream);
+
 /* ---- pose estimator (unscented Kalman filter with IMU prediction) -----------------------------------------------------
  * hdl_localization's pose system as published, restated: tests/ukf_reference.py is the specification, not that package
  * (DESIGN.md 8j lists the differences).  Additive: sps_version() is unchanged.  No entry takes a context, allocates,

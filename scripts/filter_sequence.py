@@ -23,7 +23,9 @@ hdl_localization itself runs (1 m cells, DIRECT7), still without its UKF and IMU
 registers every frame coarse to fine over a pyramid of cell maps (``--level-iterations`` caps each level; a ``levels:``
 line then tells the iterations per level); with ``--update-map`` / ``--carve-map`` as well the pyramid is an online one
 (``--level-capacities``), every level is updated and carved in the same launches and the ``map`` / ``carve`` lines come once
-per level.  Frames then run one at a time; behind each frame's lines comes
+per level; with ``--source cells`` it registers distribution to distribution (one Gaussian per cell of the scan against
+the map's; ``--source-resolution``, ``--source-min-points``), ``n_corr`` then counts source cells and the ``loc:`` line
+ends with ``| N sources``, the scan's valid cells.  Frames then run one at a time; behind each frame's lines comes
 ``loc: status iterations n_corr rmse | err_t err_r`` (metres, degrees, against the replayed pose map_tr @ pose) and at
 the end the absolute pose error evo_ape prints by default.  ``--traj-out FILE`` writes the estimated trajectory
 (stamp + the top three rows of the pose per line).
@@ -139,11 +141,13 @@ def hypothesis_grid(counts, steps, option="--hypotheses", step_option="--hypothe
 
 def closed_loop(name, f, pc_map, replay, finish, traj_out, which="icp", hypotheses=None, search=None, update_map=False,
                 cell_capacity=None, max_cell_points=0, resolutions=None, level_iterations=None, carve_map=False,
-                carve_options=None, level_capacities=None, estimator=None):
+                carve_options=None, level_capacities=None, estimator=None, source=None):
     """--localise: one LocalisationLoop step per frame, scored against the replayed poses.  ``estimator``: None, or the
-    options of --estimator ukf (initial_velocity, scan_period, imu: None / a rate in Hz / an array of rows t ax .. gz)."""
+    options of --estimator ukf (initial_velocity, scan_period, imu: None / a rate in Hz / an array of rows t ax .. gz).
+    ``source``: None, or the keywords of NDTLocaliser(source="cells", ...) of --source cells."""
     from sps_amd.localiser import LocalisationLoop, NDTLocaliser, ScanToMapLocaliser
     from sps_amd.trajectory import ape_translation, rotation_angle, write_trajectory
+    skw = source or {}
     if resolutions is not None and (update_map or carve_map):    # an online pyramid: per level, room for twice its cells
         caps = level_iterations or (30,) * len(resolutions)
         if level_capacities is None:
@@ -153,12 +157,12 @@ def closed_loop(name, f, pc_map, replay, finish, traj_out, which="icp", hypothes
                                  level_capacities=level_capacities)
     elif update_map or carve_map:                                # an online map: room for twice the map's cells by default
         n_cells = NDTLocaliser(pc_map[:, :3]).n_cells
-        localiser = NDTLocaliser(pc_map[:, :3], cell_capacity=cell_capacity or max(2 * n_cells, 4096))
+        localiser = NDTLocaliser(pc_map[:, :3], cell_capacity=cell_capacity or max(2 * n_cells, 4096), **skw)
     elif resolutions is not None:                                # coarse to fine; hypotheses and search keep the single map
         caps = level_iterations or (30,) * len(resolutions)       # the budget is their sum: it cuts no level short
         localiser = NDTLocaliser(pc_map[:, :3], resolutions=resolutions, iterations=sum(caps), level_iterations=caps)
     else:
-        localiser = NDTLocaliser(pc_map[:, :3]) if which == "ndt" else ScanToMapLocaliser(pc_map[:, :3])
+        localiser = NDTLocaliser(pc_map[:, :3], **skw) if which == "ndt" else ScanToMapLocaliser(pc_map[:, :3])
     loop, stamps, ref, estimates = None, [], [], []
     for stamp, scan, pose, map_tr in replay:
         T = map_tr @ pose
@@ -182,7 +186,7 @@ def closed_loop(name, f, pc_map, replay, finish, traj_out, which="icp", hypothes
         err_t = float(np.linalg.norm(step.pose[:3, 3] - T[:3, 3]))
         err_r = float(np.degrees(rotation_angle(step.pose, T)))
         print(f"[{stamp}] loc: {p.status:d} {p.iterations:d} {p.n_corr:d} {p.rmse:.4f} | {err_t:.4f} {err_r:.4f}"
-              + (" (flagged: the guess is kept)" if step.flagged else ""))
+              + (f" | {p.n_sources:d} sources" if source else "") + (" (flagged: the guess is kept)" if step.flagged else ""))
         if p.levels is not None:
             print(f"[{stamp}] levels: slots per level " + " ".join(str(int((p.levels == l).sum())) for l in range(len(resolutions))))
         u = step.batch.map_update if step.batch is not None else p.map_update
@@ -273,6 +277,13 @@ def frame_motion(estimator, k):
 @click.option("--level-capacities", "level_capacities", type=str, default=None,
               help="with --resolutions and --update-map or --carve-map: C0,C1,... cells every level of the online pyramid has "
                    "room for (default per level: twice its cells, at least 4096)")
+@click.option("--source", "source", type=click.Choice(("points", "cells")), default=None,
+              help="with --localiser ndt: register the scan's points (default) or, distribution to distribution, one Gaussian "
+                   "per cell of the scan; the loc: line then ends with the scan's valid source cells")
+@click.option("--source-resolution", "source_resolution", type=float, default=None,
+              help="with --source cells: edge of the scan's cells in m (default: the map's resolution)")
+@click.option("--source-min-points", "source_min_points", type=int, default=None,
+              help="with --source cells: points a cell of the scan needs to be used (default: the map's)")
 @click.option("--estimator", "estimator", type=click.Choice(("ukf",)), default=None,
               help="with --localise: the guess of every frame is the prediction of the device UKF pose estimator, which the "
                    "registered pose corrects; a second APE line is the estimator's")
@@ -285,7 +296,16 @@ def frame_motion(estimator, k):
               help="with --estimator: a text file of rows `t ax ay az gx gy gz`, scan k being at k * scan-period")
 def main(name, weights, sequence, config, epsilon, out_dir, n_synth, localise, which, traj_out, hyp_counts, hyp_steps,
          search_counts, search_steps, update_map, cell_capacity, max_cell_points, carve_map, carve_miss_frames, carve_sigma,
-         resolutions, level_iterations, level_capacities, estimator, initial_velocity, scan_period, imu_rate, imu_file):
+         resolutions, level_iterations, level_capacities, source, source_resolution, source_min_points, estimator,
+         initial_velocity, scan_period, imu_rate, imu_file):
+    if source is not None and (which != "ndt" or not localise):
+        raise click.UsageError("--source needs --localise --localiser ndt")
+    if (source_resolution is not None or source_min_points is not None) and source != "cells":
+        raise click.UsageError("--source-resolution and --source-min-points need --source cells")
+    if source == "cells" and (resolutions is not None or hyp_counts is not None or search_counts is not None):
+        raise click.UsageError("--source cells takes no --resolutions, --hypotheses or --search: they register points")
+    source = dict(source="cells", source_resolution=source_resolution, source_min_points=source_min_points) \
+        if source == "cells" else None
     if estimator is None and (initial_velocity != "0,0,0" or imu_rate is not None or imu_file is not None):
         raise click.UsageError("--initial-velocity, --imu-rate and --imu need --estimator")
     if estimator is not None:
@@ -387,7 +407,7 @@ def main(name, weights, sequence, config, epsilon, out_dir, n_synth, localise, w
     if localise:
         closed_loop(name, f, pc_map, replay, finish, traj_out, which or "icp", hypotheses, search, update_map, cell_capacity,
                     max_cell_points, resolutions, level_iterations, carve_map, carve_options or None, level_capacities,
-                    estimator)
+                    estimator, source)
     elif traj_out:
         raise click.UsageError("--traj-out needs --localise")
     in_flight, prev_pose = None, None

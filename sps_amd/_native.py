@@ -159,6 +159,11 @@ def _load() -> C.CDLL:
         "sps_ndt_pyramid_carve": (i32, [vp, vp, vp, i64, vp, vp, vp, vp, C.c_double, i32, i32, i32, vp, vp, vp]),
         "sps_ndt_pyramid_info": (i32, [vp, i32, vp]),
         "sps_ndt_pyramid_carve_cells": (i32, [vp, i32, vp, vp, vp]),
+        "sps_ndt_source_scratch": (i64, [i64]),
+        "sps_ndt_source_build": (i32, [vp, vp, vp, i64, C.c_double, i32, C.c_double, vp, vp, vp, vp, vp]),
+        "sps_ndt_align_d2d_scratch": (i64, [i64]),
+        "sps_ndt_align_d2d": (i32, [vp, vp, vp, i64, vp, i32, i32, i32, C.c_double, C.c_double, C.c_double, vp, vp, vp, vp, vp,
+                                    vp]),
         "sps_ukf_state_bytes": (i64, []),
         "sps_ukf_init": (i32, [vp, vp, vp, vp, vp]),
         "sps_ukf_predict": (i32, [vp, vp, i32, vp, vp, vp, vp]),
@@ -199,7 +204,9 @@ EXPORTS = ["sps_last_error", "sps_version", "sps_ctx_create", "sps_ctx_destroy",
            "sps_ndt_pyramid_build", "sps_ndt_pyramid_cells", "sps_ndt_pyramid_align_scratch", "sps_ndt_pyramid_align",
            "sps_ndt_pyramid_build_dynamic", "sps_ndt_pyramid_update_scratch", "sps_ndt_pyramid_update",
            "sps_ndt_pyramid_carve_scratch", "sps_ndt_pyramid_carve", "sps_ndt_pyramid_info", "sps_ndt_pyramid_carve_cells",
+           "sps_ndt_source_scratch", "sps_ndt_source_build", "sps_ndt_align_d2d_scratch", "sps_ndt_align_d2d",
            "sps_ukf_state_bytes", "sps_ukf_init", "sps_ukf_predict", "sps_ukf_predict_dt", "sps_ukf_correct"]
+NDT_SRC_REC = 10           # SPS_NDT_SRC_REC: doubles of a source record
 UKF_MAX_IMU = 256          # SPS_UKF_MAX_IMU
 CROP_BLOCK = 1024          # SPS_CROP_BLOCK: map rows per int of sps_radius_crop's scratch
 
@@ -574,6 +581,19 @@ class Context:
         check(lib.sps_ndt_pyramid_align(self.handle, pts_ptr, n_dev_ptr, int(cap), self._mat(T_init), int(iters), caps,
                                         int(neighbours), int(min_corr), float(tol_t), float(tol_r), T_out_ptr, status_ptr,
                                         trace_ptr, normal_ptr, level_ptr, scratch_ptr, stream))
+
+    # ---- NDT localiser, distribution to distribution (include/sps_hip.h, same title) ----
+    def ndt_source_build(self, pts_ptr, n_dev_ptr: int, cap: int, source_resolution: float, min_points: int, eig_ratio: float,
+                         src_ptr, src_count_ptr, n_src_ptr: int, scratch_ptr: int, stream: int):
+        check(lib.sps_ndt_source_build(self.handle, pts_ptr, n_dev_ptr, int(cap), float(source_resolution), int(min_points),
+                                       float(eig_ratio), src_ptr, src_count_ptr, n_src_ptr, scratch_ptr, stream))
+
+    def ndt_align_d2d(self, src_ptr, n_src_ptr: int, cap_src: int, T_init, iters: int, neighbours: int, min_corr: int,
+                      outlier_ratio: float, tol_t: float, tol_r: float, T_out_ptr: int, status_ptr: int, trace_ptr, normal_ptr,
+                      scratch_ptr: int, stream: int):
+        check(lib.sps_ndt_align_d2d(self.handle, src_ptr, n_src_ptr, int(cap_src), self._mat(T_init), int(iters),
+                                    int(neighbours), int(min_corr), float(outlier_ratio), float(tol_t), float(tol_r), T_out_ptr,
+                                    status_ptr, trace_ptr, normal_ptr, scratch_ptr, stream))
 
     def train_forward(self, params_ptr: int, numel: int, coords_ptr: int, ld: int, n: int, voxel_size: float,
                       scores_ptr: int, batch_stats_ptr, stream: int):

@@ -1,0 +1,124 @@
+// ndt_d2d_host.inc.h -- part of sps_hip.hip (included inside its extern "C" block, after ndt_update_host.inc.h): the entry
+// points of distribution-to-distribution NDT (ABI: the "NDT localiser, distribution to distribution" section of
+// include/sps_hip.h; kernels: ndt_d2d_kernels.inc.h).  Neither call allocates or synchronises: the scratch is the caller's.
+
+namespace {
+// The source build's scratch: the update's own arrays and, beside them, the empty map that the update's bodies found the
+// scan's cells in.  Arrays that start from the same byte lie together, so one memset serves each value:
+//   0xFF  the update's hash keys, the map's hash keys, the map's hash ranks
+//   0x7F  the update's hash `first`, the cells' `lead`
+//   0     the cells' `bcnt`, the map's state words
+struct NdtSrcLayout {
+  NdtUpdScratch s;
+  NdtMap m;
+  NdtDyn d;
+  int *info;
+  char *ff, *sf, *zero;
+  size_t ff_bytes, sf_bytes, zero_bytes;
+};
+inline size_t ndt_src_layout(int64_t cap, double resolution, char *base, NdtSrcLayout *L) {
+  const size_t n = (size_t)(cap < 1 ? 1 : cap), hs = (size_t)ndt_hash_slots(cap);
+  size_t at = 0;
+  auto take = [&](size_t bytes) {
+    char *p = base ? base + at : nullptr;
+    at += ndt_upd_align(bytes);
+    return p;
+  };
+  char *shkeys = take(hs * 8), *mhkeys = take(hs * 8), *mhrank = take(hs * 4);
+  const size_t ff_end = at;
+  char *shfirst = take(hs * 4), *lead = take(n * 4);
+  const size_t sf_end = at;
+  char *bcnt = take(n * 4), *state = take(16);
+  const size_t zero_end = at;
+  char *q = take(n * 3 * 8), *bstat = take(n * 10 * 8), *cell_of = take(n * 4), *slot_of = take(n * 4), *list = take(n * 4),
+       *tcell = take(n * 4), *shrank = take(hs * 4), *nt = take(4), *cstart = take(n * 4), *keys = take(n * 8), *info = take(16);
+  if (L) {
+    NdtUpdScratch &s = L->s;
+    s.q = (double *)q, s.bstat = (double *)bstat, s.cell_of = (int *)cell_of, s.slot_of = (int *)slot_of;
+    s.list = (int *)list, s.tcell = (int *)tcell, s.n_touched = (int *)nt;
+    s.h.keys = (uint64_t *)shkeys, s.h.first = (int *)shfirst, s.h.rank = (int *)shrank, s.h.mask = (uint32_t)(hs - 1);
+    L->m = NdtMap{};
+    L->m.h.keys = (uint64_t *)mhkeys, L->m.h.first = nullptr, L->m.h.rank = (int *)mhrank, L->m.h.mask = (uint32_t)(hs - 1);
+    L->m.n_cells = (int)n, L->m.resolution = resolution;   // rec, count and keys are not read by the bodies used
+    L->d = NdtDyn{};
+    L->d.capacity = (int)n;                                // room for every point's own cell: nothing is ever dropped
+    L->d.keys = (uint64_t *)keys, L->d.bcnt = (int *)bcnt, L->d.lead = (int *)lead, L->d.cstart = (int *)cstart;
+    L->d.state = (int *)state;
+    L->info = (int *)info;
+    L->ff = shkeys, L->ff_bytes = ff_end;
+    L->sf = shfirst, L->sf_bytes = sf_end - ff_end;
+    L->zero = bcnt, L->zero_bytes = zero_end - sf_end;
+  }
+  return at;
+}
+}  // namespace
+
+int64_t sps_ndt_source_scratch(int64_t cap) {
+  if (cap < 0 || cap > SPS_NDT_UPDATE_MAX_POINTS) return -1;
+  return (int64_t)ndt_src_layout(cap, 1.0, nullptr, nullptr);
+}
+
+int sps_ndt_source_build(sps_ctx *c, const double *pts_dev, const int32_t *n_dev, int64_t cap, double source_resolution,
+                         int min_points, double eig_ratio, double *src_dev, int32_t *src_count_dev, int32_t *n_src_dev,
+                         void *scratch_dev, void *stream) {
+  if (!c || !n_dev || !n_src_dev || !scratch_dev || cap < 0 || (cap > 0 && (!pts_dev || !src_dev)))
+    return fail(SPS_ERR_INVALID, "bad arguments");
+  if (cap > SPS_NDT_UPDATE_MAX_POINTS) return fail(SPS_ERR_INVALID, "too many points (limit %d)", SPS_NDT_UPDATE_MAX_POINTS);
+  if (!(source_resolution > 0.0) || std::isinf(source_resolution))
+    return fail(SPS_ERR_INVALID, "source_resolution must be finite and > 0");
+  if (!(eig_ratio > 0.0) || !(eig_ratio <= 1.0)) return fail(SPS_ERR_INVALID, "eig_ratio must be in (0, 1]");
+  if (min_points < 0) return fail(SPS_ERR_INVALID, "min_points must be >= 0");
+  HIP_TRY(hipSetDevice(c->device));
+  hipStream_t st = (hipStream_t)stream;
+  NdtSrcLayout L{};
+  ndt_src_layout(cap, source_resolution, (char *)scratch_dev, &L);
+  LocPose I{};
+  I.m[0] = I.m[5] = I.m[10] = I.m[15] = 1.0;
+  const int nbp = (int)((cap + 255) / 256 > 0 ? (cap + 255) / 256 : 1);
+  const int nbs = (int)std::min<int64_t>(std::max<int64_t>(cap / 4, 1), 2048);
+  HIP_TRY(hipMemsetAsync(L.ff, 0xFF, L.ff_bytes, st));
+  HIP_TRY(hipMemsetAsync(L.sf, 0x7F, L.sf_bytes, st));
+  HIP_TRY(hipMemsetAsync(L.zero, 0, L.zero_bytes, st));
+  HIP_TRY(hipMemsetAsync(n_src_dev, 0, 2 * sizeof(int32_t), st));
+  hipLaunchKernelGGL(k_ndt_src_lookup, dim3(nbp), dim3(256), 0, st, pts_dev, n_dev, (int)cap, I, L.m, L.s);
+  hipLaunchKernelGGL(k_ndt_src_found, dim3(1), dim3(NDT_UPD_BLOCK), 0, st, n_dev, (int)cap, L.d, L.s, L.info);
+  hipLaunchKernelGGL(k_ndt_src_resolve, dim3(nbp), dim3(256), 0, st, n_dev, (int)cap, L.m, L.d, L.s);
+  hipLaunchKernelGGL(k_ndt_src_offsets, dim3(1), dim3(NDT_UPD_BLOCK), 0, st, n_dev, (int)cap, L.d, L.s, L.info);
+  hipLaunchKernelGGL(k_ndt_src_fill, dim3(nbp), dim3(256), 0, st, n_dev, (int)cap, L.d, L.s);
+  hipLaunchKernelGGL(k_ndt_src_stats, dim3(nbs), dim3(64), 0, st, n_dev, (int)cap, L.d, L.s);
+  hipLaunchKernelGGL(k_ndt_src_records, dim3(nbp), dim3(256), 0, st, n_dev, (int)cap, min_points, eig_ratio, L.s, src_dev,
+                     src_count_dev, n_src_dev);
+  HIP_TRY(hipGetLastError());
+  return SPS_OK;
+}
+
+int64_t sps_ndt_align_d2d_scratch(int64_t cap_src) { return sps_loc_align_scratch(cap_src); }   // the partial rows of k_loc_solve
+
+int sps_ndt_align_d2d(sps_ctx *c, const double *src_dev, const int32_t *n_src_dev, int64_t cap_src, const double *T_init_host,
+                      int iters, int neighbours, int min_corr, double outlier_ratio, double tol_t, double tol_r,
+                      double *T_out_dev, int32_t *status_dev, double *trace_dev, double *normal_dev, void *scratch_dev,
+                      void *stream) {
+  if (!c || !n_src_dev || !T_init_host || !T_out_dev || !status_dev || !scratch_dev || cap_src < 0 || iters < 0 ||
+      (cap_src > 0 && !src_dev) || (iters > 0 && !trace_dev))
+    return fail(SPS_ERR_INVALID, "bad arguments");
+  NdtGauss gs;
+  if (int e = ndt_check_scan_args(c, neighbours, cap_src, outlier_ratio, gs, true, iters, tol_t, tol_r)) return e;
+  HIP_TRY(hipSetDevice(c->device));
+  hipStream_t st = (hipStream_t)stream;
+  LocPose T0;
+  for (int i = 0; i < 16; ++i) T0.m[i] = T_init_host[i];
+  const int nb = (int)loc_align_blocks(cap_src);
+  double *partial = (double *)scratch_dev;
+  int *done = (int *)(partial + (size_t)nb * LOC_TERMS);
+  if (iters > 0) HIP_TRY(hipMemsetAsync(trace_dev, 0, (size_t)iters * 4 * sizeof(double), st));
+  if (iters > 0 && normal_dev) HIP_TRY(hipMemsetAsync(normal_dev, 0, (size_t)iters * 28 * sizeof(double), st));
+  hipLaunchKernelGGL(k_loc_init, dim3(1), dim3(64), 0, st, T0, T_out_dev, status_dev, done);
+  for (int it = 0; it < iters; ++it) {
+    hipLaunchKernelGGL(k_ndt_d2d_assoc, dim3(nb), dim3(256), 0, st, src_dev, n_src_dev, (int)cap_src, c->ndt, gs, neighbours,
+                       (const double *)T_out_dev, (const int *)done, partial);
+    hipLaunchKernelGGL(k_loc_solve, dim3(1), dim3(256), 0, st, (const double *)partial, n_src_dev, (int)cap_src, it, min_corr,
+                       tol_t, tol_r, T0, T_out_dev, status_dev, done, trace_dev, normal_dev);
+  }
+  HIP_TRY(hipGetLastError());
+  return SPS_OK;
+}

@@ -9,8 +9,11 @@
 //
 // This file also holds the one definition of what the batch, search and update kernels share with these two:
 //   ndt_list_moments, ndt_record_from_moments   a cell's moments from its point list; its record from (n, mean, S)
+//   ndt_floored_eigen                           the Jacobi sweeps and the eigenvalue floor under every record (also the scan's
+//                                               cells of ndt_d2d_kernels.inc.h)
 //   ndt_cell_key, ndt_cell_of                   the cell of a point (radius_cell of aux_kernels.inc.h) and its id in the map
 //   ndt_cell_hit                                one cell's contribution to one point
+//   ndt_assoc_reduce                            phases 2 and 3 of launch A, from the hits in LDS (also k_ndt_d2d_assoc's)
 // with loc_transform of loc_kernels.inc.h in front.  That the entry points agree bit for bit follows from that.
 //
 // Launch B is k_loc_solve unchanged: the partial rows have its layout (21 of H, 6 of g, the score, the count; one row per
@@ -87,31 +90,42 @@ __device__ inline void ndt_list_moments(const int *__restrict__ cell_pts, const 
   }
 }
 
-// The record of a cell from (n, mean, S): sample covariance S / (n - 1), NDT_SWEEPS Jacobi sweeps, eigenvalues floored at
-// eig_ratio times the largest, inverse covariance, the validity flag.  The map build (k_ndt_cells) and the online update
-// (k_ndt_upd_merge, ndt_update_kernels.inc.h) both end here.
+// The eigen-decomposition that every record is made from, for n >= 2: the sample covariance S / (n - 1), NDT_SWEEPS cyclic
+// Jacobi sweeps (eigenvectors: the columns of v), the eigenvalues floored at eig_ratio times the largest.  lmax is the
+// largest eigenvalue before the floor.  One definition for the map's records (ndt_record_from_moments below: the inverse
+// covariance) and the scan's (ndt_d2d_kernels.inc.h: the covariance itself).
+__device__ inline void ndt_floored_eigen(int n, const double S[6], double eig_ratio, double v[3][3], double lam[3], double &lmax) {
+  const double nm1 = (double)(n - 1);
+  double cv[6];
+#pragma unroll
+  for (int i = 0; i < 6; ++i) cv[i] = __ddiv_rn(S[i], nm1);
+  double a[3][3] = {{cv[0], cv[1], cv[2]}, {cv[1], cv[3], cv[4]}, {cv[2], cv[4], cv[5]}};
+#pragma unroll
+  for (int i = 0; i < 3; ++i)
+#pragma unroll
+    for (int j = 0; j < 3; ++j) v[i][j] = i == j ? 1.0 : 0.0;
+  for (int sweep = 0; sweep < NDT_SWEEPS; ++sweep) {
+    ndt_rotate(a, v, 0, 1);
+    ndt_rotate(a, v, 0, 2);
+    ndt_rotate(a, v, 1, 2);
+  }
+  lam[0] = a[0][0], lam[1] = a[1][1], lam[2] = a[2][2];
+  lmax = fmax(fmax(lam[0], lam[1]), lam[2]);
+  const double lfloor = loc_mul(eig_ratio, lmax);
+#pragma unroll
+  for (int i = 0; i < 3; ++i)
+    if (lam[i] < lfloor) lam[i] = lfloor;
+}
+
+// The record of a cell from (n, mean, S): ndt_floored_eigen, inverse covariance, the validity flag.  The map build
+// (k_ndt_cells) and the online update (k_ndt_upd_merge, ndt_update_kernels.inc.h) both end here.
 __device__ inline void ndt_record_from_moments(int n, const double mu[3], const double S[6], int min_points, double eig_ratio,
                                                double *__restrict__ o) {
   double icov[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
   bool valid = n >= min_points && n >= 2;
   if (n >= 2) {
-    const double nm1 = (double)(n - 1);
-    double cv[6];
-#pragma unroll
-    for (int i = 0; i < 6; ++i) cv[i] = __ddiv_rn(S[i], nm1);
-    double a[3][3] = {{cv[0], cv[1], cv[2]}, {cv[1], cv[3], cv[4]}, {cv[2], cv[4], cv[5]}};
-    double v[3][3] = {{1.0, 0.0, 0.0}, {0.0, 1.0, 0.0}, {0.0, 0.0, 1.0}};
-    for (int sweep = 0; sweep < NDT_SWEEPS; ++sweep) {
-      ndt_rotate(a, v, 0, 1);
-      ndt_rotate(a, v, 0, 2);
-      ndt_rotate(a, v, 1, 2);
-    }
-    double lam[3] = {a[0][0], a[1][1], a[2][2]};
-    const double lmax = fmax(fmax(lam[0], lam[1]), lam[2]);
-    const double lfloor = loc_mul(eig_ratio, lmax);
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-      if (lam[i] < lfloor) lam[i] = lfloor;
+    double v[3][3], lam[3], lmax;
+    ndt_floored_eigen(n, S, eig_ratio, v, lam, lmax);
     valid = valid && lmax > 0.0;
     int k = 0;
 #pragma unroll
@@ -224,34 +238,15 @@ struct NdtAssocLds {
   double terms[LOC_PTS][LOC_TERMS];
 };
 
-__device__ inline void ndt_assoc_body(const double *__restrict__ pts, const int *__restrict__ n_dev, int cap, const NdtMap &m,
-                                      const NdtGauss &gs, int neighbours, const double *__restrict__ T,
-                                      double *__restrict__ partial, NdtAssocLds &lds) {
+// Phases 2 and 3 of launch A, from the hits that phase 1 left in LDS (every thread of the workgroup must call, for the
+// barriers): k is the thread's element of the workgroup, sub its lane, q the element's place in the map frame.  Shared by
+// the point-to-distribution kernels and k_ndt_d2d_assoc (ndt_d2d_kernels.inc.h), whose hit holds the combined inverse
+// covariance where a point's hit holds the cell's.
+__device__ inline void ndt_assoc_reduce(NdtAssocLds &lds, int k, int sub, const double q[3], int neighbours,
+                                        double *__restrict__ partial) {
   double(*hit)[7][NDT_HIT] = lds.hit;
   int(*hit_ok)[NDT_LANES] = lds.hit_ok;
   double(*terms)[LOC_TERMS] = lds.terms;
-  const int n = min(cap, max(*n_dev, 0));
-  const int base = blockIdx.x * LOC_PTS;
-  if (base >= n) return;
-  const int k = threadIdx.x / NDT_LANES, sub = threadIdx.x % NDT_LANES;
-  const int i = base + k;
-  double q[3] = {0.0, 0.0, 0.0};
-  int ok = 0;
-  if (i < n) {
-    loc_transform(T, pts[(size_t)i * 3], pts[(size_t)i * 3 + 1], pts[(size_t)i * 3 + 2], q);
-    const int cell = sub < neighbours ? ndt_cell_of(m, q, sub) : -1;
-    double e, w, y[3], icov[6];
-    if (cell >= 0 && ndt_cell_hit(q, m.rec + (size_t)cell * NDT_REC, gs, e, w, y, icov)) {
-      double *o = hit[k][sub];
-      o[0] = loc_mul(gs.nd1, w);
-#pragma unroll
-      for (int j = 0; j < 6; ++j) o[1 + j] = icov[j];
-      o[7] = y[0], o[8] = y[1], o[9] = y[2];
-      o[10] = loc_mul(gs.nd1, e);
-      ok = 1;
-    }
-  }
-  hit_ok[k][sub] = ok;
   __syncthreads();
   for (int l = sub; l < LOC_TERMS; l += NDT_LANES) {
     double term = 0.0;
@@ -287,6 +282,36 @@ __device__ inline void ndt_assoc_body(const double *__restrict__ pts, const int 
     for (int p = 0; p < LOC_PTS; ++p) s = loc_add(s, terms[p][threadIdx.x]);
     partial[(size_t)blockIdx.x * LOC_TERMS + threadIdx.x] = s;
   }
+}
+
+__device__ inline void ndt_assoc_body(const double *__restrict__ pts, const int *__restrict__ n_dev, int cap, const NdtMap &m,
+                                      const NdtGauss &gs, int neighbours, const double *__restrict__ T,
+                                      double *__restrict__ partial, NdtAssocLds &lds) {
+  double(*hit)[7][NDT_HIT] = lds.hit;
+  int(*hit_ok)[NDT_LANES] = lds.hit_ok;
+  const int n = min(cap, max(*n_dev, 0));
+  const int base = blockIdx.x * LOC_PTS;
+  if (base >= n) return;
+  const int k = threadIdx.x / NDT_LANES, sub = threadIdx.x % NDT_LANES;
+  const int i = base + k;
+  double q[3] = {0.0, 0.0, 0.0};
+  int ok = 0;
+  if (i < n) {
+    loc_transform(T, pts[(size_t)i * 3], pts[(size_t)i * 3 + 1], pts[(size_t)i * 3 + 2], q);
+    const int cell = sub < neighbours ? ndt_cell_of(m, q, sub) : -1;
+    double e, w, y[3], icov[6];
+    if (cell >= 0 && ndt_cell_hit(q, m.rec + (size_t)cell * NDT_REC, gs, e, w, y, icov)) {
+      double *o = hit[k][sub];
+      o[0] = loc_mul(gs.nd1, w);
+#pragma unroll
+      for (int j = 0; j < 6; ++j) o[1 + j] = icov[j];
+      o[7] = y[0], o[8] = y[1], o[9] = y[2];
+      o[10] = loc_mul(gs.nd1, e);
+      ok = 1;
+    }
+  }
+  hit_ok[k][sub] = ok;
+  ndt_assoc_reduce(lds, k, sub, q, neighbours, partial);
 }
 
 __global__ __launch_bounds__(256) void k_ndt_assoc(const double *__restrict__ pts, const int *__restrict__ n_dev, int cap,

@@ -152,6 +152,7 @@ int fail(int code, const char *fmt, ...) {
 #include "ndt_batch_kernels.inc.h"
 #include "ndt_search_kernels.inc.h"
 #include "ndt_update_kernels.inc.h"
+#include "ndt_d2d_kernels.inc.h"
 #include "ndt_carve_kernels.inc.h"
 #include "ndt_pyramid_kernels.inc.h"
 #include "ndt_pyramid_update_kernels.inc.h"
@@ -2267,6 +2268,7 @@ int sps_get_feature(sps_ctx *c, const char *name, float *out_dev, int64_t *rows,
 #include "ndt_batch_host.inc.h"
 #include "ndt_search_host.inc.h"
 #include "ndt_update_host.inc.h"
+#include "ndt_d2d_host.inc.h"
 #include "ndt_carve_host.inc.h"
 #include "ndt_pyramid_host.inc.h"
 #include "ndt_pyramid_update_host.inc.h"

@@ -74,6 +74,7 @@ class PoseResult:
     map_update: object = None  # MapUpdateResult of the frame, with integrate=True (an online pyramid: a tuple, one per level)
     levels: np.ndarray = None  # [iterations] int, the pyramid level every slot ran at (None without a pyramid)
     map_carve: object = None   # MapCarveResult of the frame, with carve=True (an online pyramid: a tuple, one per level)
+    n_sources: int = 0         # valid source cells of the scan (NDTLocaliser(source="cells") only; n_corr then counts sources)
 
     @property
     def ok(self) -> bool:
@@ -156,7 +157,7 @@ class PendingPose:
         h = self._host.numpy()
         K = self._iters
         code, it, n_corr, _ = (int(x) for x in h[16:18].view(np.int32))
-        n_points = int(h[18:19].view(np.int32)[0])
+        n_points, n_sources = (int(x) for x in h[18:19].view(np.int32))
         trace = h[19:19 + 4 * K].reshape(K, 4)[:it].copy()
         normal = h[19 + 4 * K:19 + 32 * K].reshape(K, 28)[:it].copy() if self._with_normal else None
         rmse = math.sqrt(trace[-1, 1] / n_corr) if it and n_corr > 0 else float("nan")
@@ -169,7 +170,8 @@ class PendingPose:
             levels = h[self._levels_at:self._levels_at + (K + 1) // 2].view(np.int32)[:it].astype(np.int64)
         carved = None if self._carve_at is None else _per_level(_map_carve_of, h[self._carve_at:self._carve_at + w].view(np.int32),
                                                                 n_points, L)
-        return PoseResult(h[:16].reshape(4, 4).copy(), code, it, n_corr, rmse, trace, normal, n_points, upd, levels, carved)
+        return PoseResult(h[:16].reshape(4, 4).copy(), code, it, n_corr, rmse, trace, normal, n_points, upd, levels, carved,
+                          n_sources)
 
 
 @dataclass
@@ -434,6 +436,8 @@ class ScanToMapLocaliser:
             kw = dict(level_ptr=base + size * 8 if K else None) if pyramid else {}
             self._align(base + 18 * 8, T, K, base, base + 16 * 8, base + 19 * 8 if K else None,
                         base + (19 + 4 * K) * 8 if with_normal and K else None, s, **kw)
+            if getattr(self, "source", "points") == "cells":         # the valid source cells into the pad behind n_points
+                out.view(torch.int32)[37:38].copy_(self._n_src[1:2])
             if carve:
                 self._carve(base + 18 * 8, None, base, base + 16 * 8, copts, base + carve_at * 8, s)
             if integrate:
@@ -520,13 +524,24 @@ class NDTLocaliser(ScanToMapLocaliser):
     ``level_capacities`` (with ``resolutions``; one cell capacity per level, each at least the level's cells): the pyramid's
     levels are online maps, ``integrate`` / ``carve`` and ``submit(..., integrate=True, carve=True)`` work on all of them
     at once and report one result per level; ``pyramid_info(level)`` and ``carve_state(level)`` show a level.  The single
-    map stays static, so the batch and the search refuse ``integrate`` and ``carve``.  ``capacity`` is then at most 65536."""
+    map stays static, so the batch and the search refuse ``integrate`` and ``carve``.  ``capacity`` is then at most 65536.
+
+    ``source="cells"`` registers distribution to distribution: the thinned scan is reduced to one Gaussian per cell of edge
+    ``source_resolution`` (default: ``resolution``) of the sensor frame, valid from ``source_min_points`` points (default:
+    ``min_points_per_cell``), and these are registered against the map's Gaussians.  ``n_corr`` then counts source cells,
+    ``min_correspondences`` bounds them, and the result's ``n_sources`` tells how many valid ones the scan gave.
+    ``submit`` / ``submit_filtered`` / ``__call__``, ``integrate`` and ``carve`` work as before (the map still takes the
+    thinned points); ``resolutions``, ``submit_batch``, ``submit_from_device``, ``score_poses`` and ``relocalise`` are
+    refused.  ``capacity`` is then at most 65536.  ``source="points"`` (the default) is the point-to-distribution path."""
 
     def __init__(self, map_points, resolution: float = 1.0, neighbours: int = 7, leaf: float = 0.2, iterations: int = 30,
                  min_correspondences: int = 50, min_points_per_cell: int = 6, outlier_ratio: float = 0.55,
                  eig_ratio: float = 0.01, tol_t: float = 1e-4, tol_r: float = 1e-5, device="cuda", capacity: int = 1 << 16,
-                 cell_capacity: int = None, resolutions=None, level_iterations=None, level_capacities=None):
+                 cell_capacity: int = None, resolutions=None, level_iterations=None, level_capacities=None,
+                 source: str = "points", source_resolution: float = None, source_min_points: int = None):
         from .datasets.blt_dataset import radius_grid_cells
+        self.source, self.source_resolution, self.source_min_points = self._checked_source(
+            source, source_resolution, source_min_points, resolution, min_points_per_cell, resolutions, capacity)
         if level_capacities is not None and cell_capacity is not None:
             raise ValueError("level_capacities and cell_capacity exclude each other: the single map beside an online pyramid is static")
         self.resolutions, self.level_iterations = self._checked_pyramid(resolutions, level_iterations, cell_capacity)
@@ -592,6 +607,37 @@ class NDTLocaliser(ScanToMapLocaliser):
             self._ds_scratch, self._ds_rows = None, -1
             self._batch_scratch, self._batch_hyp = None, 0
             self._score_scratch, self._score_poses = None, 0
+            if self.source == "cells":                               # the scan's cells, their counts, (cells, valid cells)
+                self._src = torch.empty((self.capacity, _native.NDT_SRC_REC), dtype=torch.float64, device=self.device)
+                self._src_count = torch.empty(self.capacity, dtype=torch.int32, device=self.device)
+                self._n_src = torch.zeros(2, dtype=torch.int32, device=self.device)
+                self._src_scratch = torch.empty(_native.lib.sps_ndt_source_scratch(self.capacity), dtype=torch.uint8,
+                                                device=self.device)
+                self._d2d_scratch = torch.empty(_native.lib.sps_ndt_align_d2d_scratch(self.capacity), dtype=torch.uint8,
+                                                device=self.device)
+
+    @staticmethod
+    def _checked_source(source, source_resolution, source_min_points, resolution, min_points_per_cell, resolutions, capacity):
+        """(source, source_resolution, source_min_points) with the defaults filled in, before any device work"""
+        if source not in ("points", "cells"):
+            raise ValueError("source must be 'points' or 'cells'")
+        if source == "points":
+            if source_resolution is not None or source_min_points is not None:
+                raise ValueError("source_resolution and source_min_points need source='cells'")
+            return source, None, None
+        if resolutions is not None:
+            raise ValueError("source='cells' and resolutions exclude each other: the pyramid registers points")
+        if capacity > MAX_UPDATE_POINTS:
+            raise ValueError(f"with source='cells', capacity must be <= {MAX_UPDATE_POINTS}")
+        res = float(resolution if source_resolution is None else source_resolution)
+        mp = int(min_points_per_cell if source_min_points is None else source_min_points)
+        if not (math.isfinite(res) and res > 0 and mp >= 0):
+            raise ValueError("source_resolution must be finite and > 0 and source_min_points >= 0")
+        return source, res, mp
+
+    def _refuse_cells(self, what):
+        if getattr(self, "source", "points") == "cells":
+            raise ValueError(f"{what} registers points: it needs an NDTLocaliser with source='points'")
 
     @staticmethod
     def _checked_pyramid(resolutions, level_iterations, cell_capacity):
@@ -644,9 +690,41 @@ class NDTLocaliser(ScanToMapLocaliser):
                                        self.min_correspondences, self.tol_t, self.tol_r, T_out_ptr, status_ptr, trace_ptr,
                                        normal_ptr, level_ptr, self._pyr_scratch.data_ptr(), s)
             return
+        if self.source == "cells":
+            self._build_sources(n_ptr, s)
+            self.ctx.ndt_align_d2d(self._src.data_ptr(), self._n_src.data_ptr(), self.capacity, T, K, self.neighbours,
+                                   self.min_correspondences, self.outlier_ratio, self.tol_t, self.tol_r, T_out_ptr, status_ptr,
+                                   trace_ptr, normal_ptr, self._d2d_scratch.data_ptr(), s)
+            return
         self.ctx.ndt_align(self._pts.data_ptr(), n_ptr, self.capacity, T, K, self.neighbours, self.min_correspondences,
                            self.outlier_ratio, self.tol_t, self.tol_r, T_out_ptr, status_ptr, trace_ptr, normal_ptr,
                            self._align_scratch.data_ptr(), s)
+
+    def _build_sources(self, n_ptr, s):
+        """the cells of the thinned points in self._pts (their count at n_ptr) into self._src, on stream s"""
+        self.ctx.ndt_source_build(self._pts.data_ptr(), n_ptr, self.capacity, self.source_resolution, self.source_min_points,
+                                  self.eig_ratio, self._src.data_ptr(), self._src_count.data_ptr(), self._n_src.data_ptr(),
+                                  self._src_scratch.data_ptr(), s)
+
+    @torch.no_grad()
+    def source_cells(self, rows, count):
+        """Debug (``source="cells"``): the thinning plus the source build of ``submit`` -> dict(mean [C, 3], cov [C, 6] as
+        (xx, xy, xz, yy, yz, zz), count int32 [C], valid bool [C]) in the order of the cells' lowest points, as numpy arrays.
+        Synchronises."""
+        if self.source != "cells":
+            raise ValueError("source_cells needs an NDTLocaliser with source='cells'")
+        rows = self._checked_rows(rows)
+        n_max = rows.shape[0]
+        with torch.cuda.device(self.device):
+            st = torch.cuda.current_stream()
+            n_dev = self._count_on_device(count, n_max)
+            n_pts = torch.zeros(2, dtype=torch.int32, device=self.device)
+            self._thin(rows, n_dev, n_max, n_pts.data_ptr(), st.cuda_stream)
+            self._build_sources(n_pts.data_ptr(), st.cuda_stream)
+            C = int(self._n_src.cpu()[0])                            # synchronises
+            rec = self._src[:C].cpu().numpy()
+            cnt = self._src_count[:C].cpu().numpy()
+        return dict(mean=rec[:, 0:3].copy(), cov=rec[:, 3:9].copy(), count=cnt, valid=rec[:, 9] != 0.0)
 
     def _update(self, n_ptr, T_host, T_dev_ptr, gate_ptr, max_cell_points, info_ptr, s):
         if self.level_capacities is not None:                        # every level, info_ptr: int32[L][4]
@@ -769,6 +847,7 @@ class NDTLocaliser(ScanToMapLocaliser):
         score at its final pose is selected among those with status 0 / 1 and at least ``min_correspondences`` points
         counted there (equal scores: the lowest index).  Issued on the current stream; ``result()`` -> BatchPoseResult.
         ``integrate`` and ``carve``: as for ``submit``, at the selected pose and only where a hypothesis was selected."""
+        self._refuse_cells("submit_batch")
         self._check_integrate(integrate, max_cell_points, single_map=True)
         copts = self._check_carve(carve, carve_options, single_map=True)
         rows = self._checked_rows(rows)
@@ -801,6 +880,7 @@ class NDTLocaliser(ScanToMapLocaliser):
         float64 entries (a row-major 4 x 4, e.g. ``PoseEstimator.pose_dev``) that work issued earlier on the current stream
         may still be writing.  The host never sees the pose; hypothesis 0 of the result is what ``submit`` gives from the
         same pose, bit for bit.  A pose that is not finite ends as such a pose does in ``sps_ndt_align_batch``."""
+        self._refuse_cells("submit_from_device")
         self._check_integrate(integrate, max_cell_points, single_map=True)
         copts = self._check_carve(carve, carve_options, single_map=True)
         rows = self._checked_rows(rows)
@@ -864,6 +944,7 @@ class NDTLocaliser(ScanToMapLocaliser):
         """The NDT score and the points counted at each of the P poses ``poses`` [P, 4, 4] (1 <= P <= 65536), with no
         alignment: the scan is thinned once as ``submit`` thins it, and pose p scores what ``submit_batch`` reports as the
         final score of a hypothesis that starts there with ``iterations=0``, bit for bit.  Issued on the current stream."""
+        self._refuse_cells("score_poses")
         rows = self._checked_rows(rows)
         T = _checked_poses(poses)
         n_max, dev, P = rows.shape[0], self.device, len(T)
@@ -888,6 +969,7 @@ class NDTLocaliser(ScanToMapLocaliser):
         from these as ``submit_batch`` does and select among the end poses as it selects.  Everything is issued on the
         current stream with no synchronisation in between; ``result()`` -> RelocalisationResult.  ``integrate`` and
         ``carve``: as for ``submit_batch``."""
+        self._refuse_cells("relocalise")
         self._check_integrate(integrate, max_cell_points, single_map=True)
         copts = self._check_carve(carve, carve_options, single_map=True)
         rows = self._checked_rows(rows)
@@ -1019,7 +1101,8 @@ class LocalisationLoop:
     (predict -> ``submit_from_device`` -> ``correct_from``, the guess read back with the frame's results: the one
     synchronisation per frame of the loop without an estimator).  That is possible where the filter takes no pose from the
     loop (SPSCVMFilter, LTSFilter, ``takes_pose`` false) and the localiser is an NDTLocaliser without a pyramid, hypotheses
-    or search; the frame's ``batch`` is then the one-hypothesis batch.  Everywhere else, and with ``device_guess=False``, the
+    or search that registers points (``submit_from_device`` takes no source cells); the frame's ``batch`` is then the
+    one-hypothesis batch.  Everywhere else, and with ``device_guess=False``, the
     predicted pose is fetched to the host first: one more small synchronisation per frame.  ``device_guess=True`` raises
     where the device path is impossible."""
 
@@ -1028,6 +1111,9 @@ class LocalisationLoop:
                  estimator=None, device_guess=None):
         from .sps_filters import ConstantVelocityModel
         self.filter, self.localiser = filter, localiser
+        cells = getattr(localiser, "source", "points") == "cells"
+        if cells and (hypotheses is not None or search is not None):
+            raise ValueError("hypotheses and search register points: they need an NDTLocaliser with source='points'")
         self.update_map, self.max_cell_points = bool(update_map), int(max_cell_points)
         online_pyramid = getattr(localiser, "level_capacities", None) is not None
         if self.update_map and getattr(localiser, "cell_capacity", None) is None and not online_pyramid:
@@ -1075,7 +1161,7 @@ class LocalisationLoop:
             takes_none = (hasattr(filter, "add_pose") or type(filter).__name__ == "LTSFilter"
                           or getattr(filter, "takes_pose", True) is False)
             possible = (takes_none and hasattr(localiser, "submit_from_device") and getattr(localiser, "resolutions", None) is None
-                        and hypotheses is None and search is None)
+                        and hypotheses is None and search is None and not cells)
             if device_guess and not possible:
                 raise ValueError("device_guess=True needs a filter that takes no pose from the loop and an NDTLocaliser without "
                                  "a pyramid, hypotheses or search")

@@ -11,6 +11,7 @@ synthetic.build_map() map, max_distance 1 m, leaf 0.2 m):
 
     python tools/localiser_timing.py [--frames 200] [--warmup 20] [--cpu-frames 1] [--one-frame] [--cpu-only]
                                      [--localiser {icp,ndt}] [--hypotheses K] [--search P] [--update-map] [--carve]
+                                     [--source {points,cells}] [--source-resolution R] [--source-min-points N]
 
 ``--localiser ndt`` times sps_amd.localiser.NDTLocaliser (1 m cells, 7 neighbours) on the same frames and from the same
 start, prints the ICP's per-frame figures of the same session beside it and the build time of both maps; the
@@ -43,6 +44,10 @@ sps_ukf_predict over M = 1, 10 and 40 IMU rows already on the device, predict_im
 upload), the IMU-less step and the correction (hipEvents around each, a prediction and a correction alternating so the
 state stays that of a running filter); then LocalisationLoop(SPSCVMFilter, NDTLocaliser) per frame (host wall clock)
 without an estimator, with one on the device path and with one on the host path, the three alternating frame by frame.
+
+``--localiser ndt --source cells`` times distribution-to-distribution registration (NDTLocaliser(..., source="cells")):
+per frame the hipEvent time around submit(), the iterations, the scan's valid source cells and the error against the true
+pose, beside the point path on the same frames, the two alternating frame by frame in one run; then the loop with each.
 
 ``--one-frame`` runs a warm-up and ONE localiser frame: the target of a ``rocprofv3 --kernel-trace --stats`` run.
 """
@@ -141,7 +146,16 @@ def main():
     ap.add_argument("--level-iterations", type=str, default=None, help="with --resolutions: N0,N1,... the cap of every level")
     ap.add_argument("--estimator", action="store_true", help="with --localiser ndt: time the UKF pose estimator's calls and the "
                     "loop with it, on the device path and the host path")
+    ap.add_argument("--source", choices=("points", "cells"), default="points", help="with --localiser ndt: cells times "
+                    "distribution-to-distribution registration beside the point path")
+    ap.add_argument("--source-resolution", type=float, default=None, help="with --source cells: edge of the scan's cells")
+    ap.add_argument("--source-min-points", type=int, default=None, help="with --source cells: points a cell of the scan needs")
     a = ap.parse_args()
+    if a.source == "cells" and (a.localiser != "ndt" or a.hypotheses or a.search or a.update_map or a.carve or a.resolutions
+                                or a.estimator):
+        ap.error("--source cells needs --localiser ndt and none of the other modes")
+    if (a.source_resolution is not None or a.source_min_points is not None) and a.source != "cells":
+        ap.error("--source-resolution and --source-min-points need --source cells")
     if a.estimator and (a.localiser != "ndt" or a.hypotheses or a.search or a.update_map or a.carve or a.resolutions):
         ap.error("--estimator needs --localiser ndt and none of the other modes")
     if a.resolutions and (a.localiser != "ndt" or a.hypotheses or a.search):
@@ -175,6 +189,8 @@ def main():
         return ndt_batch_main(a, dscans, mp, T_init)
     if a.localiser == "ndt" and a.resolutions:
         return ndt_pyramid_main(a, dscans, mp, T_init)
+    if a.localiser == "ndt" and a.source == "cells":
+        return ndt_d2d_main(a, scans, dscans, mp, T_init)
     if a.localiser == "ndt":
         return ndt_main(a, scans, dscans, mp, T_init)
     loc = ScanToMapLocaliser(mp[:, :3])
@@ -298,6 +314,69 @@ def ndt_main(a, scans, dscans, mp, T_init):
         out[name]["loop_sps_cvm_ms"] = round(float(np.median(t_loop)) * 1e3, 4)
         out[name]["loop_flagged_frames"] = int(flagged)
         print(f"LocalisationLoop(sps_cvm, {name}) {out[name]['loop_sps_cvm_ms']:.3f} ms per frame ({flagged} flagged)", flush=True)
+    print(json.dumps(out))
+
+
+def ndt_d2d_main(a, scans, dscans, mp, T_init):
+    """--source cells: the distribution-to-distribution localiser and the point one on the same frames, alternating frame
+    by frame within one run.  Per frame: hipEvent time around submit(), iterations, valid source cells, the error against
+    the true pose.  Then LocalisationLoop(SPSCVMFilter, .) with each (host wall clock)."""
+    map64 = mp[:, :3].astype(np.float64)
+    kw = dict(source="cells", source_resolution=a.source_resolution, source_min_points=a.source_min_points)
+    locs = {"points": NDTLocaliser(map64), "cells": NDTLocaliser(map64, **kw)}
+    if a.one_frame:
+        loc = locs["cells"]
+        for k in range(a.warmup):
+            loc.submit(dscans[k % len(dscans)], len(dscans[k % len(dscans)]), T_init).result()
+        torch.cuda.synchronize()
+        s = dscans[a.warmup % len(dscans)]
+        r = loc.submit(s, len(s), T_init).result()
+        print(json.dumps({"one_frame": True, "localiser": "ndt", "source": "cells", "status": r.status,
+                          "iterations": r.iterations, "n_points": r.n_points, "n_sources": r.n_sources, "n_corr": r.n_corr}))
+        return
+    st = torch.cuda.current_stream()
+    rec = {name: [] for name in locs}
+    for k in range(a.warmup + a.frames):
+        s = dscans[k % len(dscans)]
+        for name, loc in locs.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(st)
+            pend = loc.submit(s, len(s), T_init)
+            e1.record(st)
+            r = pend.result()
+            e1.synchronize()
+            if k >= a.warmup:
+                rec[name].append((e0.elapsed_time(e1), r.iterations, r.n_points, r.n_sources, r.n_corr, r.status,
+                                  LR.pose_difference(r.pose, np.eye(4))[0]))
+    out = {"n_scan": int(np.mean([len(s) for s in scans])), "n_map": len(mp), "n_cells": locs["points"].n_cells,
+           "frames": a.frames, "warmup": a.warmup, "source_resolution": locs["cells"].source_resolution,
+           "source_min_points": locs["cells"].source_min_points}
+    for name, rows in rec.items():
+        ms, iters, npts, nsrc, ncorr, status, errs = (list(c) for c in zip(*rows))
+        med, it = float(np.median(ms)), float(np.median(iters))
+        out[name] = {"ms": {"median": round(med, 4), "min": round(min(ms), 4), "max": round(max(ms), 4)},
+                     "iterations": {"median": it, "min": min(iters), "max": max(iters)},
+                     "ms_per_iteration": round(med / max(it, 1), 4), "points_after_thinning": int(np.mean(npts)),
+                     "n_sources": int(np.median(nsrc)), "n_corr": int(np.median(ncorr)),
+                     "status_not_converged": int(sum(v != 0 for v in status)),
+                     "max_error_m": round(max(errs), 5), "median_error_m": round(float(np.median(errs)), 5)}
+        print(f"{name}  median {med:.3f} ms (min {min(ms):.3f} max {max(ms):.3f}) per frame, iterations median {it:.0f}, "
+              f"{out[name]['ms_per_iteration']:.4f} ms per iteration, {out[name]['n_sources']} sources, error median "
+              f"{out[name]['median_error_m']:.4f} m max {out[name]['max_error_m']:.4f} m", flush=True)
+    net = net_from_params(O.random_params(seed=0)).cuda().eval().freeze()
+    mpt = torch.from_numpy(mp)
+    for name, loc in locs.items():
+        loop = LocalisationLoop(SPSCVMFilter(net, mpt, voxel_size=VS, epsilon=EPS), loc, np.eye(4))
+        t_loop, flagged = [], 0
+        for k in range(a.warmup + a.frames):
+            t0 = time.perf_counter()
+            step = loop.step(scans[k % len(scans)])
+            if k >= a.warmup:
+                t_loop.append(time.perf_counter() - t0)
+                flagged += step.flagged
+        out[name]["loop_sps_cvm_ms"] = round(float(np.median(t_loop)) * 1e3, 4)
+        out[name]["loop_flagged_frames"] = int(flagged)
+        print(f"LocalisationLoop(sps_cvm, ndt {name}) {out[name]['loop_sps_cvm_ms']:.3f} ms per frame ({flagged} flagged)", flush=True)
     print(json.dumps(out))
 
 
