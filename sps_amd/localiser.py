@@ -118,60 +118,117 @@ CARVE_DEFAULTS = dict(end_margin=None, through_sigma=1.0, min_pass=2, miss_frame
 MAX_CARVE_STEPS = 4096
 
 
-class PendingMapCarve:
+def _offsets(parts, tail=()):
+    """offsets (in the words of the buffer) of the named parts of one device buffer, in their order: ``size`` is where
+    ``parts`` end and ``tail`` begins (a part of no words still has its offset), ``total`` where the buffer ends"""
+    o, at = {}, 0
+    for name, size in parts:
+        o[name] = at
+        at += size
+    o["size"] = at
+    for name, size in tail:
+        o[name] = at
+        at += size
+    o["total"] = at
+    return o
+
+
+def _pose_layout(K, with_normal, pyramid=False, L=None, integrate=False, carve=False):
+    """offsets (in doubles) of a frame's one float64 buffer: T_out[16] | status int32[4] | n_points int32 (+ n_sources int32
+    in the pad) | trace[K][4] | normal[K][28] | level int32[K] (+ pad) with a pyramid | info int32[4] of the update | info
+    int32[4] of the carve, last (an online pyramid of L levels: int32[L][4] each).  ``hands_on``: the offsets in bytes of
+    the pose the frame hands on and of the int32 that gates what follows it on the device: ``T_out`` and the status"""
+    w = 2 if L is None else 2 * L                                    # doubles of one call's info words
+    o = _offsets((("T_out", 16), ("status", 2), ("n_points", 1), ("trace", 4 * K), ("normal", 28 * K if with_normal else 0)),
+                 (("levels", (K + 1) // 2 if pyramid else 0), ("update", w if integrate else 0), ("carve", w if carve else 0)))
+    o["hands_on"] = (o["T_out"] * 8, o["status"] * 8)
+    return o
+
+
+def _batch_layout(K, I, with_normal, integrate=False, carve=False):
+    """offsets (in doubles) of a batch's one float64 buffer: T_out[K][16] | status int32[K][4] | n_points int32 (+ pad) |
+    best int32[4] | T_best[16] | final[K][2] | trace[K][I][4] | normal[K][I][28] | info int32[4] of the update | info
+    int32[4] of the carve.  ``hands_on``, as in ``_pose_layout``: ``T_best`` and ``best[1]``, the selected hypothesis' status,
+    -1 where none was selected"""
+    o = _offsets((("T_out", 16 * K), ("status", 2 * K), ("n_points", 1), ("best", 2), ("T_best", 16), ("final", 2 * K),
+                  ("trace", 4 * K * I), ("normal", 28 * K * I if with_normal else 0)),
+                 (("update", 2 if integrate else 0), ("carve", 2 if carve else 0)))
+    o["hands_on"] = (o["T_best"] * 8, o["best"] * 8 + 4)
+    return o
+
+
+def _map_op_layout(L=None):
+    """offsets (in int32 words) of the one int32 buffer of ``integrate`` / ``carve``: n_points (+ pad) | info[4] (an online
+    pyramid of L levels: [L][4])"""
+    return _offsets((("n_points", 4), ("info", 4 * (L or 1))))
+
+
+class _Pending:
+    """Work that has been issued: the pinned host copy of its one device buffer, the event behind that copy, and ``keep``,
+    the tensors the work reads and writes (rows, count, the device buffer, then the poses on the host and the device)."""
+
+    def __init__(self, host, event, keep):
+        self._host, self._event, self._keep = host, event, keep
+
+    def _wait(self) -> np.ndarray:
+        self._event.synchronize()                                    # the one host synchronisation
+        return self._host.numpy()
+
+    def _pose_on_device(self):
+        """(the device buffer, the address in it of the pose the work hands on, the address of that pose's gate), for what
+        is queued behind the work: a registration's ``_layout()`` tells, from double ``_at`` of the buffer on"""
+        out = self._keep[2]
+        return (out,) + tuple(out.data_ptr() + self._at * 8 + b for b in self._layout()["hands_on"])
+
+
+class _PendingMapOp(_Pending):
+    _make = None                                                     # the result of four info words
+
+    def __init__(self, host, event, keep, n_levels=None):
+        super().__init__(host, event, keep)
+        self._n_levels = n_levels
+
+    def result(self):
+        h, o = self._wait(), _map_op_layout(self._n_levels)
+        return _per_level(self._make, h[o["info"]:], h[o["n_points"]], self._n_levels)
+
+
+class PendingMapCarve(_PendingMapOp):
     """A carve whose work has been issued; ``result()`` -> MapCarveResult (an online pyramid: a tuple, one per level)."""
-
-    def __init__(self, host, event, keep, n_levels=None):
-        self._host, self._event, self._keep, self._n_levels = host, event, keep, n_levels
-
-    def result(self):
-        self._event.synchronize()                                    # the one host synchronisation
-        h = self._host.numpy()
-        return _per_level(_map_carve_of, h[4:], h[0], self._n_levels)
+    _make = staticmethod(_map_carve_of)
 
 
-class PendingMapUpdate:
+class PendingMapUpdate(_PendingMapOp):
     """A map update whose work has been issued; ``result()`` -> MapUpdateResult (an online pyramid: a tuple, one per level)."""
-
-    def __init__(self, host, event, keep, n_levels=None):
-        self._host, self._event, self._keep, self._n_levels = host, event, keep, n_levels
-
-    def result(self):
-        self._event.synchronize()                                    # the one host synchronisation
-        h = self._host.numpy()
-        return _per_level(_map_update_of, h[4:], h[0], self._n_levels)
+    _make = staticmethod(_map_update_of)
 
 
-class PendingPose:
+class PendingPose(_Pending):
     """A localisation whose work has been issued; everything lives on the device until result()."""
+    _at = 0
 
-    def __init__(self, iters, with_normal, host, event, keep, upd_at=None, levels_at=None, carve_at=None, n_levels=None):
-        self._iters, self._with_normal, self._host, self._event, self._keep = iters, with_normal, host, event, keep
+    def __init__(self, iters, with_normal, host, event, keep, pyramid=False, n_levels=None, integrate=False, carve=False):
+        super().__init__(host, event, keep)
+        self._iters, self._with_normal, self._pyramid = iters, with_normal, pyramid
         self._n_levels = n_levels                                    # an online pyramid: info words per level, tuples out
-        self._upd_at = upd_at                                        # doubles in front of the map update's info words
-        self._levels_at = levels_at                                  # doubles in front of a pyramid's per-slot levels
-        self._carve_at = carve_at                                    # doubles in front of the carve's info words
+        self._integrate, self._carve = integrate, carve              # the frame's buffer has their info words
+
+    def _layout(self):
+        return _pose_layout(self._iters, self._with_normal, self._pyramid, self._n_levels, self._integrate, self._carve)
 
     def result(self) -> PoseResult:
-        self._event.synchronize()                                    # the one host synchronisation
-        h = self._host.numpy()
-        K = self._iters
-        code, it, n_corr, _ = (int(x) for x in h[16:18].view(np.int32))
-        n_points, n_sources = (int(x) for x in h[18:19].view(np.int32))
-        trace = h[19:19 + 4 * K].reshape(K, 4)[:it].copy()
-        normal = h[19 + 4 * K:19 + 32 * K].reshape(K, 28)[:it].copy() if self._with_normal else None
+        h, o = self._wait(), self._layout()
+        K, L = self._iters, self._n_levels
+        code, it, n_corr, _ = (int(x) for x in h[o["status"]:o["n_points"]].view(np.int32))
+        n_points, n_sources = (int(x) for x in h[o["n_points"]:o["trace"]].view(np.int32))
+        trace = h[o["trace"]:o["normal"]].reshape(K, 4)[:it].copy()
+        normal = h[o["normal"]:o["size"]].reshape(K, 28)[:it].copy() if self._with_normal else None
         rmse = math.sqrt(trace[-1, 1] / n_corr) if it and n_corr > 0 else float("nan")
-        L = self._n_levels
-        w = 2 if L is None else 2 * L                                # doubles of one call's info words
-        upd = None if self._upd_at is None else _per_level(_map_update_of, h[self._upd_at:self._upd_at + w].view(np.int32),
-                                                           n_points, L)
-        levels = None
-        if self._levels_at is not None:
-            levels = h[self._levels_at:self._levels_at + (K + 1) // 2].view(np.int32)[:it].astype(np.int64)
-        carved = None if self._carve_at is None else _per_level(_map_carve_of, h[self._carve_at:self._carve_at + w].view(np.int32),
-                                                                n_points, L)
-        return PoseResult(h[:16].reshape(4, 4).copy(), code, it, n_corr, rmse, trace, normal, n_points, upd, levels, carved,
-                          n_sources)
+        levels = h[o["levels"]:o["update"]].view(np.int32)[:it].astype(np.int64) if self._pyramid else None
+        upd = _per_level(_map_update_of, h[o["update"]:o["carve"]].view(np.int32), n_points, L) if self._integrate else None
+        carved = _per_level(_map_carve_of, h[o["carve"]:o["total"]].view(np.int32), n_points, L) if self._carve else None
+        return PoseResult(h[o["T_out"]:o["status"]].reshape(4, 4).copy(), code, it, n_corr, rmse, trace, normal, n_points, upd,
+                          levels, carved, n_sources)
 
 
 @dataclass
@@ -185,27 +242,31 @@ class BatchPoseResult:
     map_carve: object = None   # MapCarveResult of the frame, with carve=True
 
 
-class PendingPoses:
+class PendingPoses(_Pending):
     """A batch of localisations whose work has been issued; everything lives on the device until result()."""
 
-    def __init__(self, n_hyp, iters, with_normal, host, event, keep, at=0, upd=False, carve=False):
-        self._n_hyp, self._iters, self._with_normal, self._host, self._event, self._keep = n_hyp, iters, with_normal, host, event, keep
+    def __init__(self, n_hyp, iters, with_normal, host, event, keep, at=0, integrate=False, carve=False):
+        super().__init__(host, event, keep)
+        self._n_hyp, self._iters, self._with_normal = n_hyp, iters, with_normal
         self._at = at                                                # doubles in front of the batch's part of the buffer
-        self._upd = upd                                              # the map update's info words follow the batch's part
-        self._carve = carve                                          # the carve's info words come last
+        self._integrate, self._carve = integrate, carve              # the batch's buffer has their info words
+
+    def _layout(self):
+        return _batch_layout(self._n_hyp, self._iters, self._with_normal, self._integrate, self._carve)
 
     def result(self) -> BatchPoseResult:
-        self._event.synchronize()                                    # the one host synchronisation
-        h = self._host.numpy()[self._at:]
+        return self._parse(self._wait())
+
+    def _parse(self, host) -> BatchPoseResult:
+        h, o = host[self._at:], self._layout()
         K, I = self._n_hyp, self._iters
-        o = _batch_layout(K, I, self._with_normal)
-        T_out = h[o["T_out"]:o["T_out"] + 16 * K].reshape(K, 4, 4)
-        status = h[o["status"]:o["status"] + 2 * K].view(np.int32).reshape(K, 4)
-        n_points = int(h[o["n_points"]:o["n_points"] + 1].view(np.int32)[0])
-        best = h[o["best"]:o["best"] + 2].view(np.int32)
-        final = h[o["final"]:o["final"] + 2 * K].reshape(K, 2)
-        trace = h[o["trace"]:o["trace"] + 4 * K * I].reshape(K, I, 4)
-        normal = h[o["normal"]:o["normal"] + 28 * K * I].reshape(K, I, 28) if self._with_normal else None
+        T_out = h[o["T_out"]:o["status"]].reshape(K, 4, 4)
+        status = h[o["status"]:o["n_points"]].view(np.int32).reshape(K, 4)
+        n_points = int(h[o["n_points"]:o["best"]].view(np.int32)[0])
+        best = h[o["best"]:o["T_best"]].view(np.int32)
+        final = h[o["final"]:o["trace"]].reshape(K, 2)
+        trace = h[o["trace"]:o["normal"]].reshape(K, I, 4)
+        normal = h[o["normal"]:o["size"]].reshape(K, I, 28) if self._with_normal else None
         results = []
         for k in range(K):
             code, it, n_corr, _ = (int(x) for x in status[k])
@@ -213,23 +274,10 @@ class PendingPoses:
             rmse = math.sqrt(tr[-1, 1] / n_corr) if it and n_corr > 0 else float("nan")
             results.append(PoseResult(T_out[k].copy(), code, it, n_corr, rmse, tr,
                                       normal[k, :it].copy() if normal is not None else None, n_points))
-        upd = _map_update_of(h[o["size"]:o["size"] + 2].view(np.int32), n_points) if self._upd else None
-        cat = o["size"] + (2 if self._upd else 0)
-        carved = _map_carve_of(h[cat:cat + 2].view(np.int32), n_points) if self._carve else None
+        upd = _map_update_of(h[o["update"]:o["carve"]].view(np.int32), n_points) if self._integrate else None
+        carved = _map_carve_of(h[o["carve"]:o["total"]].view(np.int32), n_points) if self._carve else None
         return BatchPoseResult(results, final[:, 0].copy(), final[:, 1].astype(np.int64), int(best[0]),
-                               h[o["T_best"]:o["T_best"] + 16].reshape(4, 4).copy(), upd, carved)
-
-
-def _batch_layout(K, I, with_normal):
-    """offsets (in doubles) of a batch's one float64 buffer: T_out[K][16] | status int32[K][4] | n_points int32 (+ pad) |
-    best int32[4] | T_best[16] | final[K][2] | trace[K][I][4] | normal[K][I][28]"""
-    o, at = {}, 0
-    for name, size in (("T_out", 16 * K), ("status", 2 * K), ("n_points", 1), ("best", 2), ("T_best", 16), ("final", 2 * K),
-                       ("trace", 4 * K * I), ("normal", 28 * K * I if with_normal else 0)):
-        o[name] = at
-        at += size
-    o["size"] = at
-    return o
+                               h[o["T_best"]:o["final"]].reshape(4, 4).copy(), upd, carved)
 
 
 def pose_grid(along, across, yaw_deg) -> np.ndarray:
@@ -255,22 +303,28 @@ MAX_UPDATE_POINTS = 65536      # SPS_NDT_UPDATE_MAX_POINTS
 MAX_LEVELS = 4                 # SPS_NDT_PYR_MAX_LEVELS
 
 
-def _checked_poses(poses, what="poses"):
+def _checked_poses(poses, what="poses", most=MAX_POSES, n="P"):
     T = np.ascontiguousarray(np.asarray(poses, dtype=np.float64))
-    if T.ndim != 3 or T.shape[1:] != (4, 4) or not 1 <= len(T) <= MAX_POSES or not np.isfinite(T).all():
-        raise ValueError(f"{what} must be finite, [P, 4, 4] with 1 <= P <= {MAX_POSES}")
+    if T.ndim != 3 or T.shape[1:] != (4, 4) or not 1 <= len(T) <= most or not np.isfinite(T).all():
+        raise ValueError(f"{what} must be finite, [{n}, 4, 4] with 1 <= {n} <= {most}")
     return T
 
 
-class PendingScores:
+def _score_layout(P):
+    """offsets (in doubles) of the one float64 buffer of ``score_poses``: score[P][2] | n_points int32 (+ pad)"""
+    return _offsets((("score", 2 * P), ("n_points", 1)))
+
+
+class PendingScores(_Pending):
     """The scores of a pose grid whose work has been issued; ``result()`` -> (scores [P] float64, counts [P] int64)."""
 
     def __init__(self, n_pose, host, event, keep):
-        self._n_pose, self._host, self._event, self._keep = n_pose, host, event, keep
+        super().__init__(host, event, keep)
+        self._n_pose = n_pose
 
     def result(self):
-        self._event.synchronize()                                    # the one host synchronisation
-        sc = self._host.numpy()[:2 * self._n_pose].reshape(self._n_pose, 2)
+        o = _score_layout(self._n_pose)
+        sc = self._wait()[o["score"]:o["n_points"]].reshape(self._n_pose, 2)
         return sc[:, 0].copy(), sc[:, 1].astype(np.int64)
 
 
@@ -293,29 +347,26 @@ class RelocalisationResult:
 def _search_layout(P, K):
     """offsets (in doubles) of the search's part of a relocalisation's buffer, in front of the batch's:
     score[P][2] | top int32[K] (+ pad) | n_top int32 (+ pad) | T_top[K][16]"""
-    o, at = {}, 0
-    for name, size in (("score", 2 * P), ("top", (K + 1) // 2), ("n_top", 1), ("T_top", 16 * K)):
-        o[name] = at
-        at += size
-    o["size"] = at
-    return o
+    return _offsets((("score", 2 * P), ("top", (K + 1) // 2), ("n_top", 1), ("T_top", 16 * K)))
 
 
-class PendingRelocalisation:
+class PendingRelocalisation(_Pending):
     """A pose search and the alignments of its candidates, issued; everything lives on the device until result()."""
 
     def __init__(self, n_pose, batch_pending):
+        super().__init__(batch_pending._host, batch_pending._event, batch_pending._keep)
         self._n_pose, self._batch = n_pose, batch_pending
+
+    def _pose_on_device(self):
+        return self._batch._pose_on_device()
 
     def result(self) -> RelocalisationResult:
         b = self._batch
         K, P = b._n_hyp, self._n_pose
-        o = _search_layout(P, K)
-        h = b._host.numpy()
-        b._event.synchronize()                                       # the one host synchronisation
-        sc = h[o["score"]:o["score"] + 2 * P].reshape(P, 2)
-        cand = h[o["top"]:o["top"] + (K + 1) // 2].view(np.int32)[:K].astype(np.int64)
-        batch = b.result()
+        h, o = self._wait(), _search_layout(P, K)
+        sc = h[o["score"]:o["top"]].reshape(P, 2)
+        cand = h[o["top"]:o["n_top"]].view(np.int32)[:K].astype(np.int64)
+        batch = b._parse(h)
         index = int(cand[batch.best]) if batch.best >= 0 else -1
         return RelocalisationResult(sc[:, 0].copy(), sc[:, 1].astype(np.int64), cand, batch, index, batch.pose, batch.map_update,
                                     batch.map_carve)
@@ -327,33 +378,53 @@ class ScanToMapLocaliser:
     (datasets.blt_dataset.DeviceRadiusSubmap, r = voxel size) is untouched.  ``capacity`` bounds the points that enter
     the alignment: survivors of the thinning beyond it are dropped."""
 
+    # what only an NDTLocaliser can have: no pyramid, no online map, the scan's points registered as they are
+    resolutions = level_iterations = level_capacities = cell_capacity = None
+    source = "points"
+
     def __init__(self, map_points, max_distance: float = 1.0, leaf: float = 0.2, iterations: int = 30,
                  min_correspondences: int = 50, tol_t: float = 1e-4, tol_r: float = 1e-5, device="cuda",
                  capacity: int = 1 << 16):
-        from .datasets.blt_dataset import radius_grid_cells
         if not (math.isfinite(max_distance) and max_distance > 0 and math.isfinite(leaf) and leaf > 0):
             raise ValueError("max_distance and leaf must be finite and > 0")
+        self.max_distance = float(max_distance)
+        self._open(self._map_xyz(map_points), leaf, iterations, min_correspondences, tol_t, tol_r, device, capacity,
+                   _native.lib.sps_loc_align_scratch)
+
+    def _build_map(self, xyz):
+        """the localiser's map from the map's points on the device, in its context"""
+        from .datasets.blt_dataset import radius_grid_cells
+        if self.n_map:
+            keys, start, pts = radius_grid_cells(xyz, self.max_distance)
+            self.ctx.radius_grid_upload(keys.contiguous().data_ptr(), start.data_ptr(), pts.data_ptr(), xyz.data_ptr(),
+                                        len(keys), self.n_map, self.max_distance, self.max_distance, self.stream.cuda_stream)
+        else:
+            self.ctx.radius_grid_upload(None, None, None, None, 0, 0, self.max_distance, self.max_distance,
+                                        self.stream.cuda_stream)
+
+    @staticmethod
+    def _map_xyz(map_points) -> np.ndarray:
+        """the map's coordinates on the host, contiguous float64 [n, 3] (such an array comes back as it is)"""
+        mp = map_points.detach().cpu().numpy() if torch.is_tensor(map_points) else np.asarray(map_points)
+        return np.ascontiguousarray(mp[:, :3], dtype=np.float64)
+
+    def _open(self, xyz, leaf, iterations, min_correspondences, tol_t, tol_r, device, capacity, align_scratch_bytes):
+        """What both constructors do behind their own checks: the settings both have, the map ``xyz`` (float64 [n, 3] on the
+        host) on the device, the native context, ``_build_map``, then the buffer of the thinned points, the alignment's
+        scratch and the thinning's"""
         if iterations < 0 or capacity < 1:
             raise ValueError("iterations must be >= 0 and capacity >= 1")
-        self.max_distance, self.leaf, self.iterations = float(max_distance), float(leaf), int(iterations)
-        self.min_correspondences, self.tol_t, self.tol_r = int(min_correspondences), float(tol_t), float(tol_r)
-        self.capacity = int(capacity)
+        self.leaf, self.iterations, self.min_correspondences = float(leaf), int(iterations), int(min_correspondences)
+        self.tol_t, self.tol_r, self.capacity = float(tol_t), float(tol_r), int(capacity)
         self.device = _device_of(device)
-        mp = map_points.detach().cpu().numpy() if torch.is_tensor(map_points) else np.asarray(map_points)
-        xyz = torch.as_tensor(np.ascontiguousarray(mp[:, :3], dtype=np.float64)).to(self.device)
+        xyz = torch.as_tensor(xyz).to(self.device)
         self.n_map = len(xyz)
         with torch.cuda.device(self.device):
             self.stream = torch.cuda.current_stream()
             self.ctx = _native.Context(self.device.index)
-            if self.n_map:
-                keys, start, pts = radius_grid_cells(xyz, self.max_distance)
-                self.ctx.radius_grid_upload(keys.contiguous().data_ptr(), start.data_ptr(), pts.data_ptr(), xyz.data_ptr(),
-                                            len(keys), self.n_map, self.max_distance, self.max_distance, self.stream.cuda_stream)
-            else:
-                self.ctx.radius_grid_upload(None, None, None, None, 0, 0, self.max_distance, self.max_distance,
-                                            self.stream.cuda_stream)
+            self._build_map(xyz)
             self._pts = torch.empty((self.capacity, 3), dtype=torch.float64, device=self.device)
-            self._align_scratch = torch.empty(_native.lib.sps_loc_align_scratch(self.capacity), dtype=torch.uint8, device=self.device)
+            self._align_scratch = torch.empty(align_scratch_bytes(self.capacity), dtype=torch.uint8, device=self.device)
             self._ds_scratch, self._ds_rows = None, -1
 
     def _downsample_scratch(self, n_max):
@@ -414,45 +485,54 @@ class ScanToMapLocaliser:
         T = _pose(T_init)
         if T is None or not np.isfinite(T).all():
             raise ValueError("T_init must be a finite 4x4 matrix")
-        n_max, dev = rows.shape[0], self.device
         K = self.iterations if iterations is None else int(iterations)
+        pyramid = self.resolutions is not None
+        shape = (K, with_normal, pyramid, None if self.level_capacities is None else len(self.level_capacities), integrate, carve)
+        o = _pose_layout(*shape)
+
+        def work(out, n_ptr, _, s):
+            base = out.data_ptr()
+            T_ptr, gate_ptr = (base + b for b in o["hands_on"])
+            kw = dict(level_ptr=base + o["levels"] * 8 if K else None) if pyramid else {}
+            self._align(n_ptr, T, K, T_ptr, gate_ptr, base + o["trace"] * 8 if K else None,
+                        base + o["normal"] * 8 if with_normal and K else None, s, **kw)
+            if self.source == "cells":                               # the valid source cells into the pad behind n_points
+                at = 2 * o["n_points"] + 1
+                out.view(torch.int32)[at:at + 1].copy_(self._n_src[1:2])
+            if carve:
+                self._carve(n_ptr, None, T_ptr, gate_ptr, copts, base + o["carve"] * 8, s)
+            if integrate:
+                self._update(n_ptr, None, T_ptr, gate_ptr, max_cell_points, base + o["update"] * 8, s)
+        return PendingPose(K, with_normal, *self._issue(rows, count, o["total"], o["n_points"] * 8, work), *shape[2:])
+
+    def _issue(self, rows, count, size, n_points_at, work, poses=None, dtype=torch.float64):
+        """The one path on which every entry point issues its work, on the caller's current stream and with no
+        synchronisation: the count on the device, ``poses`` (a host array: through a pinned buffer; a device tensor: as it
+        is) on the device, the call's one zeroed device buffer of ``size`` words of ``dtype``, the thinning of the checked
+        ``rows`` with the survivors' count at byte ``n_points_at`` of that buffer, then ``work(out, n_ptr, T_dev, s)``, then
+        the buffer's copy into a pinned host buffer and the event behind it -> (host, event, keep) for the pending object"""
+        n_max, dev = rows.shape[0], self.device
         with torch.cuda.device(dev):
             st = torch.cuda.current_stream()
-            s = st.cuda_stream
             n_dev = self._count_on_device(count, n_max)
-            # one float64 buffer per frame: T_out[16] | status int32[4] | n_points int32 (+ pad) | trace[K][4] | normal[K][28]
-            size = 19 + 32 * K if with_normal else 19 + 4 * K
-            pyramid = getattr(self, "resolutions", None) is not None
-            caps = getattr(self, "level_capacities", None)
-            L = None if caps is None else len(caps)
-            w = 2 if L is None else 2 * L
-            # | level int32[K] (+ pad) with a pyramid | info int32[4] of the update | info int32[4] of the carve, last
-            # (an online pyramid: int32[L][4] each)
-            upd_at = size + ((K + 1) // 2 if pyramid else 0)
-            carve_at = upd_at + (w if integrate else 0)
-            out = torch.zeros(carve_at + (w if carve else 0), dtype=torch.float64, device=dev)
-            base = out.data_ptr()
-            self._thin(rows, n_dev, n_max, base + 18 * 8, s)
-            kw = dict(level_ptr=base + size * 8 if K else None) if pyramid else {}
-            self._align(base + 18 * 8, T, K, base, base + 16 * 8, base + 19 * 8 if K else None,
-                        base + (19 + 4 * K) * 8 if with_normal and K else None, s, **kw)
-            if getattr(self, "source", "points") == "cells":         # the valid source cells into the pad behind n_points
-                out.view(torch.int32)[37:38].copy_(self._n_src[1:2])
-            if carve:
-                self._carve(base + 18 * 8, None, base, base + 16 * 8, copts, base + carve_at * 8, s)
-            if integrate:
-                self._update(base + 18 * 8, None, base, base + 16 * 8, max_cell_points, base + upd_at * 8, s)
+            T_host, T_dev = None, poses
+            if isinstance(poses, np.ndarray):
+                T_host = torch.from_numpy(poses).pin_memory()
+                T_dev = T_host.to(dev, non_blocking=True)            # on the caller's stream; both stay with the pending object
+            out = torch.zeros(size, dtype=dtype, device=dev)
+            n_ptr = out.data_ptr() + n_points_at
+            self._thin(rows, n_dev, n_max, n_ptr, st.cuda_stream)
+            work(out, n_ptr, T_dev, st.cuda_stream)
             host, ev = self._to_host(out, st)
-        return PendingPose(K, with_normal, host, ev, (rows, n_dev, out), upd_at if integrate else None, size if pyramid else None,
-                           carve_at if carve else None, L)
+        return host, ev, (rows, n_dev, out, T_host, T_dev)
 
     def _check_integrate(self, integrate, max_cell_points=0, single_map=False):
         """``single_map``: the caller works on the single map at ``resolution`` (batch, search, ``map_info``), which an
         online pyramid's ``level_capacities`` do not make dynamic"""
-        caps = getattr(self, "level_capacities", None)
-        if integrate and caps is None and getattr(self, "resolutions", None) is not None:
+        caps = self.level_capacities
+        if integrate and caps is None and self.resolutions is not None:
             raise ValueError("integrate needs a single-resolution localiser: the online map has no pyramid")
-        if integrate and (caps is None or single_map) and getattr(self, "cell_capacity", None) is None:
+        if integrate and (caps is None or single_map) and self.cell_capacity is None:
             raise ValueError("integrate needs a localiser with an online map: NDTLocaliser(..., cell_capacity=N)")
         if integrate and int(max_cell_points) < 0:
             raise ValueError("max_cell_points must be >= 0")
@@ -464,10 +544,10 @@ class ScanToMapLocaliser:
             if carve_options is not None:
                 raise ValueError("carve_options needs carve=True")
             return None
-        caps = getattr(self, "level_capacities", None)
-        if caps is None and getattr(self, "resolutions", None) is not None:
+        caps = self.level_capacities
+        if caps is None and self.resolutions is not None:
             raise ValueError("carve needs a single-resolution localiser: the online map has no pyramid")
-        if (caps is None or single_map) and getattr(self, "cell_capacity", None) is None:
+        if (caps is None or single_map) and self.cell_capacity is None:
             raise ValueError("carve needs a localiser with an online map: NDTLocaliser(..., cell_capacity=N)")
         unknown = set(carve_options or ()) - set(CARVE_DEFAULTS)
         if unknown:
@@ -539,72 +619,26 @@ class NDTLocaliser(ScanToMapLocaliser):
                  eig_ratio: float = 0.01, tol_t: float = 1e-4, tol_r: float = 1e-5, device="cuda", capacity: int = 1 << 16,
                  cell_capacity: int = None, resolutions=None, level_iterations=None, level_capacities=None,
                  source: str = "points", source_resolution: float = None, source_min_points: int = None):
-        from .datasets.blt_dataset import radius_grid_cells
         self.source, self.source_resolution, self.source_min_points = self._checked_source(
             source, source_resolution, source_min_points, resolution, min_points_per_cell, resolutions, capacity)
         if level_capacities is not None and cell_capacity is not None:
             raise ValueError("level_capacities and cell_capacity exclude each other: the single map beside an online pyramid is static")
         self.resolutions, self.level_iterations = self._checked_pyramid(resolutions, level_iterations, cell_capacity)
-        self.level_capacities = self._checked_level_capacities(self.resolutions, level_capacities, capacity, map_points)
+        xyz = self._map_xyz(map_points)
+        self.level_capacities = self._checked_level_capacities(self.resolutions, level_capacities, capacity, xyz)
         if cell_capacity is not None and (int(cell_capacity) < 1 or capacity > MAX_UPDATE_POINTS):
             raise ValueError(f"cell_capacity must be >= 1 and, with it, capacity <= {MAX_UPDATE_POINTS}")
         if not (math.isfinite(resolution) and resolution > 0 and math.isfinite(leaf) and leaf > 0):
             raise ValueError("resolution and leaf must be finite and > 0")
         if neighbours not in (1, 7):
             raise ValueError("neighbours must be 1 or 7")
-        if iterations < 0 or capacity < 1:
-            raise ValueError("iterations must be >= 0 and capacity >= 1")
         if not (0.0 < outlier_ratio < 1.0 and 0.0 < eig_ratio <= 1.0 and min_points_per_cell >= 0):
             raise ValueError("outlier_ratio must be in (0, 1), eig_ratio in (0, 1] and min_points_per_cell >= 0")
-        self.resolution, self.neighbours, self.leaf = float(resolution), int(neighbours), float(leaf)
-        self.iterations, self.min_correspondences = int(iterations), int(min_correspondences)
+        self.resolution, self.neighbours = float(resolution), int(neighbours)
         self.min_points_per_cell, self.outlier_ratio, self.eig_ratio = int(min_points_per_cell), float(outlier_ratio), float(eig_ratio)
-        self.tol_t, self.tol_r, self.capacity = float(tol_t), float(tol_r), int(capacity)
         self.cell_capacity = None if cell_capacity is None else int(cell_capacity)
-        self.device = _device_of(device)
-        mp = map_points.detach().cpu().numpy() if torch.is_tensor(map_points) else np.asarray(map_points)
-        xyz = torch.as_tensor(np.ascontiguousarray(mp[:, :3], dtype=np.float64)).to(self.device)
-        self.n_map = len(xyz)
+        self._open(xyz, leaf, iterations, min_correspondences, tol_t, tol_r, device, capacity, _native.lib.sps_ndt_align_scratch)
         with torch.cuda.device(self.device):
-            self.stream = torch.cuda.current_stream()
-            self.ctx = _native.Context(self.device.index)
-            self.n_cells, cells = 0, (None, None, None, None)
-            if self.n_map:
-                keys, start, pts = radius_grid_cells(xyz, self.resolution)
-                keys = keys.contiguous()
-                self.n_cells, cells = len(keys), (keys.data_ptr(), start.data_ptr(), pts.data_ptr(), xyz.data_ptr())
-            args = (*cells, self.n_cells, self.n_map, self.resolution, self.min_points_per_cell, self.eig_ratio)
-            if self.cell_capacity is None:
-                self.ctx.ndt_map_build(*args, self.stream.cuda_stream)
-            else:
-                if self.cell_capacity < max(self.n_cells, 1):
-                    raise ValueError(f"cell_capacity {self.cell_capacity} is below the map's {self.n_cells} cells")
-                self.ctx.ndt_map_build_dynamic(*args, self.cell_capacity, self.stream.cuda_stream)
-                self._update_scratch = torch.empty(_native.lib.sps_ndt_map_update_scratch(self.capacity), dtype=torch.uint8,
-                                                   device=self.device)
-            self.level_cells = None
-            if self.resolutions is not None:
-                levels, keep = [], []                                # one radius_grid_cells call per level
-                for r in self.resolutions:
-                    if self.n_map:
-                        k, st_, p = radius_grid_cells(xyz, r)
-                        k = k.contiguous()
-                        keep.append((k, st_, p))
-                        levels.append((k.data_ptr(), st_.data_ptr(), p.data_ptr(), len(k), r))
-                    else:
-                        levels.append((None, None, None, 0, r))
-                self.level_cells = tuple(lv[3] for lv in levels)
-                self.ctx.ndt_pyramid_build(levels, xyz.data_ptr() if self.n_map else None, self.n_map, self.min_points_per_cell,
-                                           self.eig_ratio, self.outlier_ratio, self.stream.cuda_stream, self.level_capacities)
-                if self.level_capacities is not None:
-                    self._pyr_update_scratch = torch.empty(
-                        _native.lib.sps_ndt_pyramid_update_scratch(self.capacity, len(self.resolutions)), dtype=torch.uint8,
-                        device=self.device)
-                self._pyr_scratch = torch.empty(_native.lib.sps_ndt_pyramid_align_scratch(self.capacity), dtype=torch.uint8,
-                                                device=self.device)
-            self._pts = torch.empty((self.capacity, 3), dtype=torch.float64, device=self.device)
-            self._align_scratch = torch.empty(_native.lib.sps_ndt_align_scratch(self.capacity), dtype=torch.uint8, device=self.device)
-            self._ds_scratch, self._ds_rows = None, -1
             self._batch_scratch, self._batch_hyp = None, 0
             self._score_scratch, self._score_poses = None, 0
             if self.source == "cells":                               # the scan's cells, their counts, (cells, valid cells)
@@ -615,6 +649,44 @@ class NDTLocaliser(ScanToMapLocaliser):
                                                 device=self.device)
                 self._d2d_scratch = torch.empty(_native.lib.sps_ndt_align_d2d_scratch(self.capacity), dtype=torch.uint8,
                                                 device=self.device)
+
+    def _build_map(self, xyz):
+        """the single map at ``resolution``, static or online, and the pyramid's levels beside it"""
+        from .datasets.blt_dataset import radius_grid_cells
+        self.n_cells, cells = 0, (None, None, None, None)
+        if self.n_map:
+            keys, start, pts = radius_grid_cells(xyz, self.resolution)
+            keys = keys.contiguous()
+            self.n_cells, cells = len(keys), (keys.data_ptr(), start.data_ptr(), pts.data_ptr(), xyz.data_ptr())
+        args = (*cells, self.n_cells, self.n_map, self.resolution, self.min_points_per_cell, self.eig_ratio)
+        if self.cell_capacity is None:
+            self.ctx.ndt_map_build(*args, self.stream.cuda_stream)
+        else:
+            if self.cell_capacity < max(self.n_cells, 1):
+                raise ValueError(f"cell_capacity {self.cell_capacity} is below the map's {self.n_cells} cells")
+            self.ctx.ndt_map_build_dynamic(*args, self.cell_capacity, self.stream.cuda_stream)
+            self._update_scratch = torch.empty(_native.lib.sps_ndt_map_update_scratch(self.capacity), dtype=torch.uint8,
+                                               device=self.device)
+        self.level_cells = None
+        if self.resolutions is not None:
+            levels, keep = [], []                                # one radius_grid_cells call per level
+            for r in self.resolutions:
+                if self.n_map:
+                    k, st_, p = radius_grid_cells(xyz, r)
+                    k = k.contiguous()
+                    keep.append((k, st_, p))
+                    levels.append((k.data_ptr(), st_.data_ptr(), p.data_ptr(), len(k), r))
+                else:
+                    levels.append((None, None, None, 0, r))
+            self.level_cells = tuple(lv[3] for lv in levels)
+            self.ctx.ndt_pyramid_build(levels, xyz.data_ptr() if self.n_map else None, self.n_map, self.min_points_per_cell,
+                                       self.eig_ratio, self.outlier_ratio, self.stream.cuda_stream, self.level_capacities)
+            if self.level_capacities is not None:
+                self._pyr_update_scratch = torch.empty(
+                    _native.lib.sps_ndt_pyramid_update_scratch(self.capacity, len(self.resolutions)), dtype=torch.uint8,
+                    device=self.device)
+            self._pyr_scratch = torch.empty(_native.lib.sps_ndt_pyramid_align_scratch(self.capacity), dtype=torch.uint8,
+                                            device=self.device)
 
     @staticmethod
     def _checked_source(source, source_resolution, source_min_points, resolution, min_points_per_cell, resolutions, capacity):
@@ -636,7 +708,7 @@ class NDTLocaliser(ScanToMapLocaliser):
         return source, res, mp
 
     def _refuse_cells(self, what):
-        if getattr(self, "source", "points") == "cells":
+        if self.source == "cells":
             raise ValueError(f"{what} registers points: it needs an NDTLocaliser with source='points'")
 
     @staticmethod
@@ -675,8 +747,7 @@ class NDTLocaliser(ScanToMapLocaliser):
             raise ValueError("level_capacities must be >= 1")
         if capacity > MAX_UPDATE_POINTS:
             raise ValueError(f"with level_capacities, capacity must be <= {MAX_UPDATE_POINTS}")
-        mp = map_points.detach().cpu().numpy() if torch.is_tensor(map_points) else np.asarray(map_points)
-        xyz = np.ascontiguousarray(mp[:, :3], dtype=np.float64)
+        xyz = ScanToMapLocaliser._map_xyz(map_points)
         for l, (r, c) in enumerate(zip(resolutions, caps)):
             n = len(np.unique(np.floor(xyz / np.float64(r)).astype(np.int64), axis=0)) if len(xyz) else 0
             if c < n:
@@ -756,22 +827,21 @@ class NDTLocaliser(ScanToMapLocaliser):
         gives a tuple of MapCarveResult, coarsest level first."""
         o = self._check_carve(True, dict(end_margin=end_margin, through_sigma=through_sigma, min_pass=min_pass,
                                          miss_frames=miss_frames, max_steps=max_steps))
+        return self._map_op(rows, count, T, self._carve, o, PendingMapCarve)
+
+    def _map_op(self, rows, count, T, op, options, pending):
+        """``op`` (``_carve`` or ``_update``, with its ``options``) on the thinned rows at the host pose ``T``, ungated, into a
+        small int32 buffer of its own -> ``pending`` of it"""
         rows = self._checked_rows(rows)
         Th = _pose(T)
         if Th is None or not np.isfinite(Th).all():
             raise ValueError("T must be a finite 4x4 matrix")
-        n_max, dev = rows.shape[0], self.device
-        with torch.cuda.device(dev):
-            st = torch.cuda.current_stream()
-            s = st.cuda_stream
-            n_dev = self._count_on_device(count, n_max)
-            L = None if self.level_capacities is None else len(self.level_capacities)
-            out = torch.zeros(4 + 4 * (L or 1), dtype=torch.int32, device=dev)   # n_points (+ pad) | info[4] (a pyramid: [L][4])
-            base = out.data_ptr()
-            self._thin(rows, n_dev, n_max, base, s)
-            self._carve(base, Th, None, None, o, base + 16, s)
-            host, ev = self._to_host(out, st)
-        return PendingMapCarve(host, ev, (rows, n_dev, out), L)
+        L = None if self.level_capacities is None else len(self.level_capacities)
+        o = _map_op_layout(L)
+
+        def work(out, n_ptr, _, s):
+            op(n_ptr, Th, None, None, options, out.data_ptr() + o["info"] * 4, s)
+        return pending(*self._issue(rows, count, o["total"], o["n_points"] * 4, work, dtype=torch.int32), L)
 
     def carve_state(self, level: int = None):
         """Debug: (pass, hit, miss) int32 arrays of the online map's assigned cells, in the order of ``map_cells()``: the
@@ -780,19 +850,17 @@ class NDTLocaliser(ScanToMapLocaliser):
         ``pyramid_cells(level)``.  Synchronises."""
         if level is not None:
             level = self._checked_online_level(level)
-            C = self.level_capacities[level]
-            with torch.cuda.device(self.device):
-                out = torch.zeros((3, C), dtype=torch.int32, device=self.device)
-                self.ctx.ndt_pyramid_carve_cells(level, out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr())
-            n = self.ctx.ndt_pyramid_info(level)[0]
-            h = out.cpu().numpy()
-            return h[0, :n].copy(), h[1, :n].copy(), h[2, :n].copy()
+            return self._read_carve_cells(self.level_capacities[level], self.ctx.ndt_pyramid_carve_cells, self.ctx.ndt_pyramid_info,
+                                          level)
         self._check_carve(True, single_map=True)
-        C = self.cell_capacity
+        return self._read_carve_cells(self.cell_capacity, self.ctx.ndt_map_carve_cells, self.ctx.ndt_map_info)
+
+    def _read_carve_cells(self, C, read, info, *level):
+        """``read([level,] pass, hit, miss)`` of an online map of capacity C, of which ``info([level])[0]`` cells are assigned"""
         with torch.cuda.device(self.device):
             out = torch.zeros((3, C), dtype=torch.int32, device=self.device)
-            self.ctx.ndt_map_carve_cells(out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr())
-        n = self.ctx.ndt_map_info()[0]
+            read(*level, out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr())
+        n = info(*level)[0]
         h = out.cpu().numpy()
         return h[0, :n].copy(), h[1, :n].copy(), h[2, :n].copy()
 
@@ -805,22 +873,7 @@ class NDTLocaliser(ScanToMapLocaliser):
         online pyramid (``level_capacities``) updates every level in the same launches, each within its own capacity, and
         ``result()`` gives a tuple of MapUpdateResult, coarsest level first."""
         self._check_integrate(True, max_cell_points)
-        rows = self._checked_rows(rows)
-        Th = _pose(T)
-        if Th is None or not np.isfinite(Th).all():
-            raise ValueError("T must be a finite 4x4 matrix")
-        n_max, dev = rows.shape[0], self.device
-        with torch.cuda.device(dev):
-            st = torch.cuda.current_stream()
-            s = st.cuda_stream
-            n_dev = self._count_on_device(count, n_max)
-            L = None if self.level_capacities is None else len(self.level_capacities)
-            out = torch.zeros(4 + 4 * (L or 1), dtype=torch.int32, device=dev)   # n_points (+ pad) | info[4] (a pyramid: [L][4])
-            base = out.data_ptr()
-            self._thin(rows, n_dev, n_max, base, s)
-            self._update(base, Th, None, None, max_cell_points, base + 16, s)
-            host, ev = self._to_host(out, st)
-        return PendingMapUpdate(host, ev, (rows, n_dev, out), L)
+        return self._map_op(rows, count, T, self._update, max_cell_points, PendingMapUpdate)
 
     def map_info(self):
         """Debug: (cells assigned, cell capacity, cells dropped for capacity since the build) of the online map; synchronises."""
@@ -828,7 +881,7 @@ class NDTLocaliser(ScanToMapLocaliser):
         return self.ctx.ndt_map_info()
 
     def _checked_online_level(self, level):
-        if getattr(self, "level_capacities", None) is None:
+        if self.level_capacities is None:
             raise ValueError("needs a localiser with an online pyramid: NDTLocaliser(..., resolutions=..., level_capacities=...)")
         if not 0 <= int(level) < len(self.level_capacities):
             raise ValueError(f"level must be in [0, {len(self.level_capacities)})")
@@ -847,30 +900,9 @@ class NDTLocaliser(ScanToMapLocaliser):
         score at its final pose is selected among those with status 0 / 1 and at least ``min_correspondences`` points
         counted there (equal scores: the lowest index).  Issued on the current stream; ``result()`` -> BatchPoseResult.
         ``integrate`` and ``carve``: as for ``submit``, at the selected pose and only where a hypothesis was selected."""
-        self._refuse_cells("submit_batch")
-        self._check_integrate(integrate, max_cell_points, single_map=True)
-        copts = self._check_carve(carve, carve_options, single_map=True)
-        rows = self._checked_rows(rows)
-        T = np.ascontiguousarray(np.asarray(T_inits, dtype=np.float64))
-        if T.ndim != 3 or T.shape[1:] != (4, 4) or not 1 <= len(T) <= MAX_HYPOTHESES or not np.isfinite(T).all():
-            raise ValueError(f"T_inits must be finite, [K, 4, 4] with 1 <= K <= {MAX_HYPOTHESES}")
-        n_max, dev, K = rows.shape[0], self.device, len(T)
-        I = self.iterations if iterations is None else int(iterations)
-        o = _batch_layout(K, I, with_normal)
-        with torch.cuda.device(dev):
-            st = torch.cuda.current_stream()
-            s = st.cuda_stream
-            n_dev = self._count_on_device(count, n_max)
-            T_host = torch.from_numpy(T).pin_memory()
-            T_dev = T_host.to(dev, non_blocking=True)                # on the caller's stream; both stay with the pending object
-            # | info int32[4] of the update | info int32[4] of the carve
-            out = torch.zeros(o["size"] + (2 if integrate else 0) + (2 if carve else 0), dtype=torch.float64, device=dev)
-            base = out.data_ptr()
-            self._thin(rows, n_dev, n_max, base + o["n_points"] * 8, s)
-            self._align_batch(base + o["n_points"] * 8, T_dev.data_ptr(), K, I, with_normal, base, o, s, integrate, max_cell_points,
-                              copts)
-            host, ev = self._to_host(out, st)
-        return PendingPoses(K, I, with_normal, host, ev, (rows, n_dev, out, T_host, T_dev), upd=integrate, carve=carve)
+        rows, copts = self._checked_for_batch("submit_batch", rows, integrate, max_cell_points, carve, carve_options)
+        T = _checked_poses(T_inits, "T_inits", MAX_HYPOTHESES, "K")
+        return self._issue_batch(rows, count, T, len(T), with_normal, iterations, integrate, max_cell_points, copts)
 
     @torch.no_grad()
     def submit_from_device(self, rows, count, T_init_dev, with_normal: bool = False, iterations: int = None,
@@ -880,28 +912,29 @@ class NDTLocaliser(ScanToMapLocaliser):
         float64 entries (a row-major 4 x 4, e.g. ``PoseEstimator.pose_dev``) that work issued earlier on the current stream
         may still be writing.  The host never sees the pose; hypothesis 0 of the result is what ``submit`` gives from the
         same pose, bit for bit.  A pose that is not finite ends as such a pose does in ``sps_ndt_align_batch``."""
-        self._refuse_cells("submit_from_device")
-        self._check_integrate(integrate, max_cell_points, single_map=True)
-        copts = self._check_carve(carve, carve_options, single_map=True)
-        rows = self._checked_rows(rows)
+        rows, copts = self._checked_for_batch("submit_from_device", rows, integrate, max_cell_points, carve, carve_options)
         T_dev = T_init_dev
         if not (torch.is_tensor(T_dev) and T_dev.is_cuda and T_dev.device == self.device and T_dev.dtype == torch.float64
                 and T_dev.numel() == 16 and T_dev.is_contiguous()):
             raise TypeError("T_init_dev must be 16 contiguous float64 entries on the localiser's device")
-        n_max, dev = rows.shape[0], self.device
+        return self._issue_batch(rows, count, T_dev, 1, with_normal, iterations, integrate, max_cell_points, copts)
+
+    def _checked_for_batch(self, what, rows, integrate, max_cell_points, carve, carve_options):
+        """the checks of everything that registers on the single map, in their order -> (the checked rows, the carve's options)"""
+        self._refuse_cells(what)
+        self._check_integrate(integrate, max_cell_points, single_map=True)
+        copts = self._check_carve(carve, carve_options, single_map=True)
+        return self._checked_rows(rows), copts
+
+    def _issue_batch(self, rows, count, poses, K, with_normal, iterations, integrate, max_cell_points, copts):
+        """the batch of the K start poses ``poses``: a host array [K, 4, 4], or 16 float64 entries on the device (K = 1)"""
         I = self.iterations if iterations is None else int(iterations)
-        o = _batch_layout(1, I, with_normal)
-        with torch.cuda.device(dev):
-            st = torch.cuda.current_stream()
-            s = st.cuda_stream
-            n_dev = self._count_on_device(count, n_max)
-            out = torch.zeros(o["size"] + (2 if integrate else 0) + (2 if carve else 0), dtype=torch.float64, device=dev)
-            base = out.data_ptr()
-            self._thin(rows, n_dev, n_max, base + o["n_points"] * 8, s)
-            self._align_batch(base + o["n_points"] * 8, T_dev.data_ptr(), 1, I, with_normal, base, o, s, integrate, max_cell_points,
-                              copts)
-            host, ev = self._to_host(out, st)
-        return PendingPoses(1, I, with_normal, host, ev, (rows, n_dev, out, None, T_dev), upd=integrate, carve=carve)
+        o = _batch_layout(K, I, with_normal, integrate, copts is not None)
+
+        def work(out, n_ptr, T_dev, s):
+            self._align_batch(n_ptr, T_dev.data_ptr(), K, I, with_normal, out.data_ptr(), o, s, integrate, max_cell_points, copts)
+        return PendingPoses(K, I, with_normal, *self._issue(rows, count, o["total"], o["n_points"] * 8, work, poses),
+                            integrate=integrate, carve=copts is not None)
 
     def submit_filtered_batch(self, pending, T_inits, **kw) -> PendingPoses:
         """``submit_batch`` of the kept rows of a pending SPSFilter / SPSCVMFilter frame, without the frame's result()."""
@@ -916,11 +949,11 @@ class NDTLocaliser(ScanToMapLocaliser):
                                  base + o["status"] * 8, base + o["trace"] * 8 if I else None,
                                  base + o["normal"] * 8 if with_normal and I else None, base + o["final"] * 8,
                                  base + o["best"] * 8, base + o["T_best"] * 8, self._batch_scratch_for(K).data_ptr(), s)
-        if carve_opts is not None:                                   # best[1]: the selected hypothesis' status, -1 where none
-            self._carve(n_ptr, None, base + o["T_best"] * 8, base + o["best"] * 8 + 4, carve_opts,
-                        base + (o["size"] + (2 if integrate else 0)) * 8, s)
+        T_best, gate_ptr = (base + b for b in o["hands_on"])
+        if carve_opts is not None:
+            self._carve(n_ptr, None, T_best, gate_ptr, carve_opts, base + o["carve"] * 8, s)
         if integrate:
-            self._update(n_ptr, None, base + o["T_best"] * 8, base + o["best"] * 8 + 4, max_cell_points, base + o["size"] * 8, s)
+            self._update(n_ptr, None, T_best, gate_ptr, max_cell_points, base + o["update"] * 8, s)
 
     def _batch_scratch_for(self, K):
         if K > self._batch_hyp:                                      # grows with the largest batch seen (stream-ordered reuse)
@@ -929,9 +962,8 @@ class NDTLocaliser(ScanToMapLocaliser):
             self._batch_hyp = K
         return self._batch_scratch
 
-    def _score(self, rows, n_dev, n_max, T_dev, P, n_points_ptr, score_ptr, s):
-        """thin the rows into self._pts (count to n_points_ptr), then the scores of the P poses of T_dev"""
-        self._thin(rows, n_dev, n_max, n_points_ptr, s)
+    def _score(self, T_dev, P, n_points_ptr, score_ptr, s):
+        """the scores of the P poses of T_dev for the thinned points in self._pts (their count at n_points_ptr)"""
         if P > self._score_poses:                                    # grows with the largest grid seen (stream-ordered reuse)
             self._score_scratch = torch.empty(_native.lib.sps_ndt_score_scratch(self.capacity, P), dtype=torch.uint8,
                                               device=self.device)
@@ -947,18 +979,12 @@ class NDTLocaliser(ScanToMapLocaliser):
         self._refuse_cells("score_poses")
         rows = self._checked_rows(rows)
         T = _checked_poses(poses)
-        n_max, dev, P = rows.shape[0], self.device, len(T)
-        with torch.cuda.device(dev):
-            st = torch.cuda.current_stream()
-            s = st.cuda_stream
-            n_dev = self._count_on_device(count, n_max)
-            T_host = torch.from_numpy(T).pin_memory()
-            T_dev = T_host.to(dev, non_blocking=True)                # on the caller's stream; both stay with the pending object
-            out = torch.zeros(2 * P + 1, dtype=torch.float64, device=dev)   # score[P][2] | n_points int32 (+ pad)
-            base = out.data_ptr()
-            self._score(rows, n_dev, n_max, T_dev, P, base + 2 * P * 8, base, s)
-            host, ev = self._to_host(out, st)
-        return PendingScores(P, host, ev, (rows, n_dev, out, T_host, T_dev))
+        P = len(T)
+        o = _score_layout(P)
+
+        def work(out, n_ptr, T_dev, s):
+            self._score(T_dev, P, n_ptr, out.data_ptr() + o["score"] * 8, s)
+        return PendingScores(P, *self._issue(rows, count, o["total"], o["n_points"] * 8, work, T))
 
     @torch.no_grad()
     def relocalise(self, rows, count, poses, keep: int = 8, with_normal: bool = False, iterations: int = None,
@@ -969,34 +995,24 @@ class NDTLocaliser(ScanToMapLocaliser):
         from these as ``submit_batch`` does and select among the end poses as it selects.  Everything is issued on the
         current stream with no synchronisation in between; ``result()`` -> RelocalisationResult.  ``integrate`` and
         ``carve``: as for ``submit_batch``."""
-        self._refuse_cells("relocalise")
-        self._check_integrate(integrate, max_cell_points, single_map=True)
-        copts = self._check_carve(carve, carve_options, single_map=True)
-        rows = self._checked_rows(rows)
+        rows, copts = self._checked_for_batch("relocalise", rows, integrate, max_cell_points, carve, carve_options)
         T = _checked_poses(poses)
         K = int(keep)
         if not 1 <= K <= MAX_HYPOTHESES:
             raise ValueError(f"keep must be in [1, {MAX_HYPOTHESES}]")
-        n_max, dev, P = rows.shape[0], self.device, len(T)
+        P = len(T)
         I = self.iterations if iterations is None else int(iterations)
-        so, o = _search_layout(P, K), _batch_layout(K, I, with_normal)
-        with torch.cuda.device(dev):
-            st = torch.cuda.current_stream()
-            s = st.cuda_stream
-            n_dev = self._count_on_device(count, n_max)
-            T_host = torch.from_numpy(T).pin_memory()
-            T_dev = T_host.to(dev, non_blocking=True)
-            out = torch.zeros(so["size"] + o["size"] + (2 if integrate else 0) + (2 if carve else 0), dtype=torch.float64, device=dev)
+        so, o = _search_layout(P, K), _batch_layout(K, I, with_normal, integrate, carve)
+
+        def work(out, n_ptr, T_dev, s):
             sbase = out.data_ptr()
-            base = sbase + so["size"] * 8
-            n_ptr = base + o["n_points"] * 8
-            self._score(rows, n_dev, n_max, T_dev, P, n_ptr, sbase + so["score"] * 8, s)
+            self._score(T_dev, P, n_ptr, sbase + so["score"] * 8, s)
             self.ctx.ndt_top_poses(sbase + so["score"] * 8, T_dev.data_ptr(), P, self.min_correspondences, K,
                                    sbase + so["top"] * 8, sbase + so["T_top"] * 8, sbase + so["n_top"] * 8, s)
-            self._align_batch(n_ptr, sbase + so["T_top"] * 8, K, I, with_normal, base, o, s, integrate, max_cell_points, copts)
-            host, ev = self._to_host(out, st)
-        return PendingRelocalisation(P, PendingPoses(K, I, with_normal, host, ev, (rows, n_dev, out, T_host, T_dev), so["size"],
-                                                     upd=integrate, carve=carve))
+            self._align_batch(n_ptr, sbase + so["T_top"] * 8, K, I, with_normal, sbase + so["size"] * 8, o, s, integrate,
+                              max_cell_points, copts)
+        issued = self._issue(rows, count, so["size"] + o["total"], (so["size"] + o["n_points"]) * 8, work, T)
+        return PendingRelocalisation(P, PendingPoses(K, I, with_normal, *issued, so["size"], integrate, carve))
 
     def relocalise_filtered(self, pending, poses, **kw) -> PendingRelocalisation:
         """``relocalise`` of the kept rows of a pending SPSFilter / SPSCVMFilter frame, without the frame's result()."""
@@ -1007,15 +1023,21 @@ class NDTLocaliser(ScanToMapLocaliser):
         valid bool [C]) of the device map, in ascending key order, as numpy arrays.  An online map gives its assigned
         cells in the order of their ids: the cells of the build in ascending key order, then the founded cells in the order
         they were founded."""
-        C = self.n_cells if self.cell_capacity is None else self.cell_capacity
+        if self.cell_capacity is None:
+            return self._read_cells(self.n_cells, self.ctx.ndt_map_cells)
+        return self._read_cells(self.cell_capacity, self.ctx.ndt_map_cells, self.ctx.ndt_map_info)
+
+    def _read_cells(self, C, read, info=None, *level):
+        """``read([level,] key, count, mean, icov, valid)`` of a map of up to C cells -> what ``map_cells`` gives; ``info``: of
+        an online map, whose ``info([level])[0]`` cells are assigned"""
         with torch.cuda.device(self.device):
             key = torch.zeros(C, dtype=torch.int64, device=self.device)
             cnt = torch.zeros(C, dtype=torch.int32, device=self.device)
             mean = torch.zeros((C, 3), dtype=torch.float64, device=self.device)
             icov = torch.zeros((C, 6), dtype=torch.float64, device=self.device)
             valid = torch.zeros(C, dtype=torch.int32, device=self.device)
-            self.ctx.ndt_map_cells(key.data_ptr(), cnt.data_ptr(), mean.data_ptr(), icov.data_ptr(), valid.data_ptr())
-        n = C if self.cell_capacity is None else self.ctx.ndt_map_info()[0]
+            read(*level, key.data_ptr(), cnt.data_ptr(), mean.data_ptr(), icov.data_ptr(), valid.data_ptr())
+        n = C if info is None else info(*level)[0]
         return (key.cpu().numpy().view(np.uint64)[:n], cnt.cpu().numpy()[:n], mean.cpu().numpy()[:n], icov.cpu().numpy()[:n],
                 valid.cpu().numpy().astype(bool)[:n])
 
@@ -1026,19 +1048,9 @@ class NDTLocaliser(ScanToMapLocaliser):
             raise ValueError("pyramid_cells needs a localiser with resolutions")
         if not 0 <= int(level) < len(self.resolutions):
             raise ValueError(f"level must be in [0, {len(self.resolutions)})")
-        caps = getattr(self, "level_capacities", None)
-        C = self.level_cells[int(level)] if caps is None else caps[int(level)]
-        with torch.cuda.device(self.device):
-            key = torch.zeros(C, dtype=torch.int64, device=self.device)
-            cnt = torch.zeros(C, dtype=torch.int32, device=self.device)
-            mean = torch.zeros((C, 3), dtype=torch.float64, device=self.device)
-            icov = torch.zeros((C, 6), dtype=torch.float64, device=self.device)
-            valid = torch.zeros(C, dtype=torch.int32, device=self.device)
-            self.ctx.ndt_pyramid_cells(int(level), key.data_ptr(), cnt.data_ptr(), mean.data_ptr(), icov.data_ptr(),
-                                       valid.data_ptr())
-        n = C if caps is None else self.ctx.ndt_pyramid_info(int(level))[0]
-        return (key.cpu().numpy().view(np.uint64)[:n], cnt.cpu().numpy()[:n], mean.cpu().numpy()[:n], icov.cpu().numpy()[:n],
-                valid.cpu().numpy().astype(bool)[:n])
+        if self.level_capacities is None:
+            return self._read_cells(self.level_cells[int(level)], self.ctx.ndt_pyramid_cells, None, int(level))
+        return self._read_cells(self.level_capacities[int(level)], self.ctx.ndt_pyramid_cells, self.ctx.ndt_pyramid_info, int(level))
 
 
 @dataclass
@@ -1111,12 +1123,15 @@ class LocalisationLoop:
                  estimator=None, device_guess=None):
         from .sps_filters import ConstantVelocityModel
         self.filter, self.localiser = filter, localiser
-        cells = getattr(localiser, "source", "points") == "cells"
+        # a localiser of the caller's own may have none of these: ScanToMapLocaliser's defaults then stand in
+        source, caps, cell_capacity, resolutions = (getattr(localiser, a, getattr(ScanToMapLocaliser, a)) for a in
+                                                    ("source", "level_capacities", "cell_capacity", "resolutions"))
+        cells = source == "cells"
         if cells and (hypotheses is not None or search is not None):
             raise ValueError("hypotheses and search register points: they need an NDTLocaliser with source='points'")
         self.update_map, self.max_cell_points = bool(update_map), int(max_cell_points)
-        online_pyramid = getattr(localiser, "level_capacities", None) is not None
-        if self.update_map and getattr(localiser, "cell_capacity", None) is None and not online_pyramid:
+        online_pyramid = caps is not None
+        if self.update_map and cell_capacity is None and not online_pyramid:
             raise ValueError("update_map needs a localiser with an online map: NDTLocaliser(..., cell_capacity=N)")
         if online_pyramid and (update_map or carve_map) and (hypotheses is not None or search is not None):
             raise ValueError("an online pyramid is updated and carved by the plain registration only: no hypotheses, no search")
@@ -1124,7 +1139,7 @@ class LocalisationLoop:
         self._kw = dict(integrate=True, max_cell_points=self.max_cell_points) if self.update_map else {}
         self.carve_map = bool(carve_map)
         if self.carve_map:
-            if getattr(localiser, "cell_capacity", None) is None and not online_pyramid:
+            if cell_capacity is None and not online_pyramid:
                 raise ValueError("carve_map needs a localiser with an online map: NDTLocaliser(..., cell_capacity=N)")
             self._kw.update(carve=True, carve_options=carve_options)
         elif carve_options is not None:
@@ -1132,9 +1147,7 @@ class LocalisationLoop:
         self.hypotheses = None
         self.search, self.search_keep, self._search_next = None, int(search_keep), True
         if search is not None:
-            S = np.array(search, dtype=np.float64)
-            if S.ndim != 3 or S.shape[1:] != (4, 4) or not 1 <= len(S) <= MAX_POSES or not np.isfinite(S).all():
-                raise ValueError(f"search must be finite, [P, 4, 4] with 1 <= P <= {MAX_POSES}")
+            S = _checked_poses(search, what="search").copy()
             if not np.array_equal(S[0], np.eye(4)):
                 raise ValueError("search[0] must be the identity")
             if not 1 <= self.search_keep <= MAX_HYPOTHESES:
@@ -1143,9 +1156,7 @@ class LocalisationLoop:
                 raise TypeError("search needs a localiser with relocalise (NDTLocaliser)")
             self.search = S
         if hypotheses is not None:
-            H = np.array(hypotheses, dtype=np.float64)
-            if H.ndim != 3 or H.shape[1:] != (4, 4) or not 1 <= len(H) <= MAX_HYPOTHESES or not np.isfinite(H).all():
-                raise ValueError(f"hypotheses must be finite, [K, 4, 4] with 1 <= K <= {MAX_HYPOTHESES}")
+            H = _checked_poses(hypotheses, "hypotheses", MAX_HYPOTHESES, "K").copy()
             if not np.array_equal(H[0], np.eye(4)):
                 raise ValueError("hypotheses[0] must be the identity")
             if not hasattr(localiser, "submit_batch"):
@@ -1160,7 +1171,7 @@ class LocalisationLoop:
                 raise TypeError("estimator must be a PoseEstimator")
             takes_none = (hasattr(filter, "add_pose") or type(filter).__name__ == "LTSFilter"
                           or getattr(filter, "takes_pose", True) is False)
-            possible = (takes_none and hasattr(localiser, "submit_from_device") and getattr(localiser, "resolutions", None) is None
+            possible = (takes_none and hasattr(localiser, "submit_from_device") and resolutions is None
                         and hypotheses is None and search is None and not cells)
             if device_guess and not possible:
                 raise ValueError("device_guess=True needs a filter that takes no pose from the loop and an NDTLocaliser without "
@@ -1195,67 +1206,15 @@ class LocalisationLoop:
         """[K, 4, 4]: ``guess @ hypotheses[k]``"""
         return np.stack([guess @ h for h in self.hypotheses])
 
-    def _step_batch(self, scan, guess) -> LoopStep:
-        pend = self._submit_filter(scan, guess)
-        starts = self.start_poses(guess)
-        if hasattr(pend, "count_dev") and hasattr(pend, "_filtered"):
-            pose_pend = self.localiser.submit_filtered_batch(pend, starts, **self._kw)
-            self._queue_correction(pose_pend)
-            fres = pend.result()
-            bres = pose_pend.result()
-        else:
-            fres = pend.result()
-            kept = fres.filtered
-            pose_pend = self.localiser.submit_batch(kept, len(kept), starts, **self._kw)
-            self._queue_correction(pose_pend)
-            bres = pose_pend.result()
-        flagged = bres.best < 0
-        pose = guess if flagged else bres.pose
-        self.model.add_pose(pose)
-        if hasattr(self.filter, "add_pose"):
-            self.filter.add_pose(pose)
-        self.poses.append(np.array(pose, dtype=np.float64))
-        return LoopStep(fres, bres.results[max(bres.best, 0)], guess, self.poses[-1], flagged, bres, estimate=self._estimate())
-
     def search_poses(self, guess) -> np.ndarray:
         """[P, 4, 4]: ``guess @ search[k]``"""
         return np.stack([guess @ d for d in self.search])
-
-    def _step_search(self, scan, guess) -> LoopStep:
-        pend = self._submit_filter(scan, guess)
-        poses = self.search_poses(guess)
-        if hasattr(pend, "count_dev") and hasattr(pend, "_filtered"):
-            pose_pend = self.localiser.relocalise_filtered(pend, poses, keep=self.search_keep, **self._kw)
-            self._queue_correction(pose_pend)
-            fres = pend.result()
-            sres = pose_pend.result()
-        else:
-            fres = pend.result()
-            kept = fres.filtered
-            pose_pend = self.localiser.relocalise(kept, len(kept), poses, keep=self.search_keep, **self._kw)
-            self._queue_correction(pose_pend)
-            sres = pose_pend.result()
-        bres = sres.batch
-        flagged = sres.index < 0
-        pose = guess if flagged else sres.pose
-        self._search_next = flagged
-        self.model.add_pose(pose)
-        if hasattr(self.filter, "add_pose"):
-            self.filter.add_pose(pose)
-        self.poses.append(np.array(pose, dtype=np.float64))
-        return LoopStep(fres, bres.results[max(bres.best, 0)], guess, self.poses[-1], flagged, bres, sres, self._estimate())
 
     def _queue_correction(self, pose_pend):
         """with an estimator: its correction behind the registration just issued, then a copy of its state for the host"""
         if self.estimator is not None:
             self.estimator.correct_from(pose_pend)
             self._est_wait = self.estimator.snapshot()
-
-    def _estimate(self):
-        if self.estimator is None:
-            return None
-        wait, self._est_wait = self._est_wait, None
-        return wait()[0].pose
 
     def _predict(self, imu, dt):
         """the estimator's prediction for this frame, queued; frame 0 makes no step"""
@@ -1270,67 +1229,74 @@ class LocalisationLoop:
             raise ValueError("with an estimator every frame after the first needs imu=rows or dt=seconds")
         self._frames += 1
 
-    def _step_device(self, scan) -> LoopStep:
-        """predict -> filter -> submit_from_device(pose_dev) -> correct_from, then the frame's results and the guess"""
-        est, loc = self.estimator, self.localiser
-        pend = self._submit_filter(scan, None)
-        if hasattr(pend, "count_dev") and hasattr(pend, "_filtered"):
-            pose_pend = loc.submit_from_device(pend._filtered, pend.count_dev, est.pose_dev, **self._kw)
-            self._queue_correction(pose_pend)
-            fres = pend.result()
-        else:
-            fres = pend.result()
-            kept = fres.filtered
-            pose_pend = loc.submit_from_device(kept, len(kept), est.pose_dev, **self._kw)
-            self._queue_correction(pose_pend)
-        bres = pose_pend.result()
-        state, guess = self._est_wait()
-        self._est_wait = None
-        flagged = bres.best < 0
-        pose = guess if flagged else bres.pose
-        self.model.add_pose(pose)
-        if hasattr(self.filter, "add_pose"):
-            self.filter.add_pose(pose)
-        self.poses.append(np.array(pose, dtype=np.float64))
-        return LoopStep(fres, bres.results[0], guess, self.poses[-1], flagged, bres, estimate=state.pose)
-
     def step(self, scan, imu=None, dt=None) -> LoopStep:
         if self.estimator is None:
             if imu is not None or dt is not None:
                 raise ValueError("imu and dt need an estimator")
         else:
             self._predict(imu, dt)
-            if self.device_guess:
-                return self._step_device(scan)
+            if self.device_guess:                                    # predict -> filter -> submit_from_device(pose_dev) -> correct_from
+                return self._register(scan, None, "submit_from_device", (self.estimator.pose_dev,), {}, self._read_batch)
             self._est_guess = self.estimator.pose_dev.cpu().numpy().astype(np.float64)   # the one more synchronisation
-        if self.search is not None:
-            if self._search_next:
-                return self._step_search(scan, self.guess())
-            out = self._step_registered(scan)
-            self._search_next = out.flagged
-            return out
-        return self._step_registered(scan)
-
-    def _step_registered(self, scan) -> LoopStep:
         guess = self.guess()
-        if self.hypotheses is not None:
-            return self._step_batch(scan, guess)
+        if self.search is not None and self._search_next:
+            out = self._register(scan, guess, "relocalise", (self.search_poses(guess),), dict(keep=self.search_keep),
+                                 self._read_search)
+        elif self.hypotheses is not None:
+            out = self._register(scan, guess, "submit_batch", (self.start_poses(guess),), {}, self._read_batch)
+        else:
+            out = self._register(scan, guess, "submit", (guess,), {}, self._read_pose)
+        self._search_next = out.flagged
+        return out
+
+    # how a registration's result reads: -> (flagged, the pose it hands on, PoseResult, BatchPoseResult, RelocalisationResult)
+    @staticmethod
+    def _read_pose(pres):
+        return pres.status in (FEW_CORRESPONDENCES, SINGULAR), pres.pose, pres, None, None
+
+    @staticmethod
+    def _read_batch(bres):
+        return bres.best < 0, bres.pose, bres.results[max(bres.best, 0)], bres, None
+
+    @staticmethod
+    def _read_search(sres):
+        return sres.index < 0, sres.pose, sres.batch.results[max(sres.batch.best, 0)], sres.batch, sres
+
+    # the localiser's entry points that take a filter's pending frame in place of (rows, count)
+    _FILTERED = dict(submit="submit_filtered", submit_batch="submit_filtered_batch", relocalise="relocalise_filtered")
+
+    def _register(self, scan, guess, method, args, kw, read) -> LoopStep:
+        """One frame through the filter and ``localiser.<method>(rows, count, *args, **kw)``; ``read`` (above) reads its
+        result.  Where the filter's pending frame exposes its device rows, the registration and the estimator's correction
+        are queued before the filter's ``result()``, so nothing synchronises between filter and localiser; otherwise they
+        follow it.  ``guess`` None: the registration starts from the estimator's device pose, and the guess comes back with
+        the estimator's snapshot, which is waited on last."""
         pend = self._submit_filter(scan, guess)
+        kw = dict(kw, **self._kw)
         if hasattr(pend, "count_dev") and hasattr(pend, "_filtered"):
-            pose_pend = self.localiser.submit_filtered(pend, guess, **self._kw)  # no synchronisation between filter and localiser
+            if method in self._FILTERED:
+                pose_pend = getattr(self.localiser, self._FILTERED[method])(pend, *args, **kw)
+            else:
+                pose_pend = getattr(self.localiser, method)(pend._filtered, pend.count_dev, *args, **kw)
             self._queue_correction(pose_pend)
             fres = pend.result()
-            pres = pose_pend.result()
         else:
             fres = pend.result()
             kept = fres.filtered
-            pose_pend = self.localiser.submit(kept, len(kept), guess, **self._kw)
+            pose_pend = getattr(self.localiser, method)(kept, len(kept), *args, **kw)
             self._queue_correction(pose_pend)
-            pres = pose_pend.result()
-        flagged = pres.status in (FEW_CORRESPONDENCES, SINGULAR)
-        pose = guess if flagged else pres.pose
+        flagged, pose, pres, bres, sres = read(pose_pend.result())
+        estimate = None
+        if self.estimator is not None:
+            wait, self._est_wait = self._est_wait, None
+            state, predicted = wait()
+            estimate, guess = state.pose, predicted if guess is None else guess
+        self._hand_on(guess if flagged else pose)
+        return LoopStep(fres, pres, guess, self.poses[-1], flagged, bres, sres, estimate)
+
+    def _hand_on(self, pose):
+        """the frame's corrected pose to the loop's model, to the filter's ``add_pose`` where it has one, and to ``poses``"""
         self.model.add_pose(pose)
         if hasattr(self.filter, "add_pose"):
             self.filter.add_pose(pose)
         self.poses.append(np.array(pose, dtype=np.float64))
-        return LoopStep(fres, pres, guess, self.poses[-1], flagged, estimate=self._estimate())

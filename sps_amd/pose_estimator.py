@@ -156,19 +156,10 @@ class PoseEstimator:
         """the correction with the pose of a pending registration, read from its device buffer and gated by its status on
         the device: ``T_out`` / status of a PendingPose, ``T_best`` / ``best[1]`` of a PendingPoses or a
         PendingRelocalisation -- the gate of the map update and the carve.  A failed registration leaves the state alone."""
-        from .localiser import PendingPose, PendingPoses, PendingRelocalisation, _batch_layout
-        if isinstance(pending, PendingRelocalisation):
-            pending = pending._batch
-        if isinstance(pending, PendingPose):
-            out = pending._keep[2]
-            T_ptr, gate_ptr = out.data_ptr(), out.data_ptr() + 16 * 8
-        elif isinstance(pending, PendingPoses):
-            out = pending._keep[2]
-            o = _batch_layout(pending._n_hyp, pending._iters, pending._with_normal)
-            base = out.data_ptr() + pending._at * 8
-            T_ptr, gate_ptr = base + o["T_best"] * 8, base + o["best"] * 8 + 4
-        else:
+        from .localiser import PendingPose, PendingPoses, PendingRelocalisation
+        if not isinstance(pending, (PendingPose, PendingPoses, PendingRelocalisation)):
             raise TypeError("correct_from needs a PendingPose, PendingPoses or PendingRelocalisation")
+        out, T_ptr, gate_ptr = pending._pose_on_device()
         if out.device != self.device:
             raise ValueError("the pending registration lives on another device")
         self._keep_pose = out

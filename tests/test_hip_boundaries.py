@@ -42,17 +42,18 @@ def rows32(xyz):
 def align_points(loc, pts, T, iters):
     """sps_loc_align / sps_ndt_align on float64 points as given (the wrapper's thinning takes float32 rows; this is its
     submit() without that step) -> PoseResult with the normal rows"""
-    from sps_amd.localiser import PendingPose
+    from sps_amd.localiser import PendingPose, _pose_layout
     pts = np.ascontiguousarray(pts, dtype=np.float64).reshape(-1, 3)
     n, K = len(pts), int(iters)
     assert n <= loc.capacity
     if n:
         loc._pts[:n].copy_(torch.from_numpy(pts))
     n_dev = torch.full((1,), n, dtype=torch.int32, device="cuda")
-    out = torch.zeros(19 + 32 * K, dtype=torch.float64, device="cuda")
+    o = _pose_layout(K, True)
+    out = torch.zeros(o["total"], dtype=torch.float64, device="cuda")
     base = out.data_ptr()
-    loc._align(n_dev.data_ptr(), np.asarray(T, dtype=np.float64), K, base, base + 16 * 8, base + 19 * 8 if K else None,
-               base + (19 + 4 * K) * 8 if K else None, stream())
+    loc._align(n_dev.data_ptr(), np.asarray(T, dtype=np.float64), K, base + o["T_out"] * 8, base + o["status"] * 8,
+               base + o["trace"] * 8 if K else None, base + o["normal"] * 8 if K else None, stream())
     torch.cuda.synchronize()
     loc.ctx.check_errors(stream())
     ev = torch.cuda.Event()

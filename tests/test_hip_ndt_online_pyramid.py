@@ -390,7 +390,7 @@ def test_a_closed_gate_changes_no_byte_of_any_level(phantom, scans):
     empty = make(np.zeros((0, 3)))
     pend = empty.submit(dev(scan), len(scan), T_INIT)
     assert pend.result().status == 2
-    gate = pend._keep[2].data_ptr() + 16 * 8
+    gate = pend._pose_on_device()[2]
     assert raw_update(pyr, pts, len(pts), len(pts), T_TRUE, gate_ptr=gate) == [[PHANTOM_CELLS[l], 0, 0, 0] for l in range(3)]
     assert raw_carve(pyr, pts, len(pts), len(pts), T_TRUE, gate_ptr=gate, min_pass=1, miss_frames=1) == [[0, 0, 0, 0]] * 3
     # the same through a frame that fails its own alignment

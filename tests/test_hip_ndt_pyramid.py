@@ -85,7 +85,8 @@ def status_words(loc, scan, T, **kw):
     """the four status words of a call, which PoseResult does not show in full: (code, slots, count, level)"""
     pend = loc.submit(scan, len(scan), T, **kw)
     res = pend.result()
-    return res, [int(v) for v in pend._host.numpy()[16:18].view(np.int32)]
+    o = pend._layout()
+    return res, [int(v) for v in pend._host.numpy()[o["status"]:o["n_points"]].view(np.int32)]
 
 
 # ---- the maps --------------------------------------------------------------------------------------------------------------

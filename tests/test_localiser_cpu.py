@@ -189,6 +189,119 @@ def test_loop_feeds_add_pose_the_corrected_pose_and_falls_back_on_status_2():
     np.testing.assert_array_equal(steps[0].pose, shift @ T0)
 
 
+# ---- the device buffers' layouts and their parsing ---------------------------------------------------------------------
+def test_the_layouts_are_the_formulas_the_buffers_were_written_with():
+    from sps_amd.localiser import _batch_layout, _pose_layout
+    for K in (0, 1, 2, 5):
+        for with_normal in (False, True):
+            size = 19 + 32 * K if with_normal else 19 + 4 * K
+            for pyramid in (False, True):
+                for L in (None, 1, 3):
+                    w = 2 if L is None else 2 * L
+                    for integrate in (False, True):
+                        for carve in (False, True):
+                            o = _pose_layout(K, with_normal, pyramid, L, integrate, carve)
+                            case = (K, with_normal, pyramid, L, integrate, carve)
+                            assert (o["T_out"], o["status"], o["n_points"], o["trace"], o["normal"]) == (0, 16, 18, 19, 19 + 4 * K), case
+                            assert o["size"] == o["levels"] == size, case
+                            upd_at = size + ((K + 1) // 2 if pyramid else 0)
+                            carve_at = upd_at + (w if integrate else 0)
+                            assert (o["update"], o["carve"], o["total"]) == (upd_at, carve_at, carve_at + (w if carve else 0)), case
+                            assert o["hands_on"] == (0, 16 * 8), case              # T_out and the status word, in bytes
+    for K, I in ((1, 0), (1, 5), (3, 2), (64, 30)):
+        for with_normal in (False, True):
+            for integrate in (False, True):
+                for carve in (False, True):
+                    o = _batch_layout(K, I, with_normal, integrate, carve)
+                    at = [0, 16 * K, 18 * K, 18 * K + 1, 18 * K + 3, 18 * K + 19, 20 * K + 19, 20 * K + 19 + 4 * K * I]
+                    assert [o[k] for k in ("T_out", "status", "n_points", "best", "T_best", "final", "trace", "normal")] == at
+                    size = at[-1] + (28 * K * I if with_normal else 0)
+                    assert o["size"] == o["update"] == size and o["carve"] == size + (2 if integrate else 0)
+                    assert o["total"] == size + (2 if integrate else 0) + (2 if carve else 0)
+                    assert _batch_layout(K, I, with_normal)["total"] == size
+                    assert o["hands_on"] == ((18 * K + 3) * 8, (18 * K + 1) * 8 + 4)   # T_best and best[1], in bytes
+
+
+class _DoneEvent:
+    def __init__(self):
+        self.waits = 0
+
+    def synchronize(self):
+        self.waits += 1
+
+
+def _words(h, at, values):
+    """int32 ``values`` from double ``at`` of the float64 buffer h on"""
+    h[at:].view(np.int32)[:len(values)] = values
+
+
+@pytest.mark.parametrize("L", [None, 3])
+def test_the_pending_objects_parse_buffers_filled_by_hand(L):
+    import torch
+    from sps_amd.localiser import (MapCarveResult, MapUpdateResult, PendingMapCarve, PendingMapUpdate, PendingPose, PendingPoses)
+    n = L or 1
+    upd_words, carve_words = np.arange(100, 100 + 4 * n), np.arange(200, 200 + 4 * n)
+    upds = [MapUpdateResult(*(int(v) for v in upd_words[4 * l:4 * l + 4]), 77) for l in range(n)]
+    carves = [MapCarveResult(*(int(v) for v in carve_words[4 * l:4 * l + 4]), 77) for l in range(n)]
+    want_upd, want_carve = (upds[0], carves[0]) if L is None else (tuple(upds), tuple(carves))
+    # ---- a frame: K = 5 slots of which 3 ran, normal rows, a pyramid's levels, update and carve ----
+    K, w = 5, 2 * n
+    h = np.zeros(19 + 32 * K + 3 + 2 * w)
+    h[:16] = np.arange(16) + 0.5
+    _words(h, 16, [1, 3, 60, 9])                                      # status, slots run, n_corr, (level)
+    _words(h, 18, [77, 12])                                           # n_points, n_sources in the pad
+    h[19:19 + 4 * K] = np.arange(4 * K) + 1000.0
+    h[19 + 4 * K:19 + 32 * K] = np.arange(28 * K) + 2000.0
+    _words(h, 19 + 32 * K, [0, 1, 2, -1, -1])                         # levels: (K + 1) // 2 = 3 doubles
+    _words(h, 19 + 32 * K + 3, upd_words)
+    _words(h, 19 + 32 * K + 3 + w, carve_words)
+    ev = _DoneEvent()
+    r = PendingPose(K, True, torch.from_numpy(h), ev, None, True, L, True, True).result()
+    assert ev.waits == 1
+    assert np.array_equal(r.pose, (np.arange(16) + 0.5).reshape(4, 4))
+    assert (r.status, r.iterations, r.n_corr, r.n_points, r.n_sources) == (1, 3, 60, 77, 12)
+    assert np.array_equal(r.trace, (np.arange(4 * K) + 1000.0).reshape(K, 4)[:3])
+    assert np.array_equal(r.normal, (np.arange(28 * K) + 2000.0).reshape(K, 28)[:3])
+    assert r.rmse == np.sqrt(1009.0 / 60) and r.levels.tolist() == [0, 1, 2]
+    assert r.map_update == want_upd and r.map_carve == want_carve
+    # the plain frame: no normal rows, no pyramid, no map work
+    r = PendingPose(K, False, torch.from_numpy(h[:19 + 4 * K].copy()), _DoneEvent(), None).result()
+    assert (r.status, r.iterations, r.n_points) == (1, 3, 77) and r.normal is None and r.levels is None
+    assert r.map_update is None and r.map_carve is None and np.array_equal(r.trace, (np.arange(4 * K) + 1000.0).reshape(K, 4)[:3])
+    # ---- integrate / carve: int32, n_points (+ pad) | info ----
+    m = np.zeros(4 + 4 * n, dtype=np.int32)
+    m[0] = 77
+    m[4:] = upd_words
+    assert PendingMapUpdate(torch.from_numpy(m), _DoneEvent(), None, L).result() == want_upd
+    m[4:] = carve_words
+    assert PendingMapCarve(torch.from_numpy(m), _DoneEvent(), None, L).result() == want_carve
+    if L is not None:
+        return                                                        # the batch works on the single map: four words each
+    # ---- a batch of 2 hypotheses, 3 slots, behind 7 doubles of something else ----
+    K, I, at = 2, 3, 7
+    b = np.zeros(at + 20 * K + 19 + 32 * K * I + 4)
+    v = b[at:]
+    v[:16 * K] = np.arange(16 * K) + 0.25
+    _words(v, 16 * K, [0, 2, 55, 0, 2, 0, 0, 0])                      # hypothesis 0: status 0 after 2 slots; 1: status 2, none run
+    _words(v, 18 * K, [77])
+    _words(v, 18 * K + 1, [0, 0])                                     # best, its status
+    v[18 * K + 3:18 * K + 19] = np.arange(16) + 0.75
+    v[18 * K + 19:20 * K + 19] = [9.5, 70.0, 1.5, 3.0]
+    v[20 * K + 19:20 * K + 19 + 4 * K * I] = np.arange(4 * K * I) + 1000.0
+    v[20 * K + 19 + 4 * K * I:20 * K + 19 + 32 * K * I] = np.arange(28 * K * I) + 2000.0
+    _words(v, 20 * K + 19 + 32 * K * I, upd_words)
+    _words(v, 20 * K + 19 + 32 * K * I + 2, carve_words)
+    r = PendingPoses(K, I, True, torch.from_numpy(b), _DoneEvent(), None, at, True, True).result()
+    assert r.best == 0 and np.array_equal(r.pose, (np.arange(16) + 0.75).reshape(4, 4))
+    assert r.scores.tolist() == [9.5, 1.5] and r.counts.tolist() == [70, 3]
+    assert r.map_update == want_upd and r.map_carve == want_carve
+    a, c = r.results
+    assert (a.status, a.iterations, a.n_corr, a.n_points) == (0, 2, 55, 77) and (c.status, c.iterations, c.n_corr) == (2, 0, 0)
+    assert np.array_equal(a.pose, (np.arange(16) + 0.25).reshape(4, 4)) and np.array_equal(c.pose, (np.arange(16) + 16.25).reshape(4, 4))
+    assert np.array_equal(a.trace, (np.arange(8) + 1000.0).reshape(2, 4)) and c.trace.shape == (0, 4) and np.isnan(c.rmse)
+    assert np.array_equal(a.normal, (np.arange(56) + 2000.0).reshape(2, 28)) and a.rmse == np.sqrt(1005.0 / 55)
+
+
 # ---- C ABI -----------------------------------------------------------------------------------------------------------------
 def test_localiser_symbols_are_declared_and_exported():
     from sps_amd import _native
