@@ -789,6 +789,44 @@ int sps_ndt_pyramid_carve(sps_ctx *ctx, const double *pts_dev, const int32_t *n_
 int sps_ndt_pyramid_info(sps_ctx *ctx, int level, int64_t *out_host);
 int sps_ndt_pyramid_carve_cells(sps_ctx *ctx, int level, int32_t *pass_out_dev, int32_t *hit_out_dev, int32_t *miss_out_dev);
 
+/* ---- NDT localiser, pyramid, several hypotheses ------------------------------------------------------------------------
+ * sps_ndt_pyramid_align from n_hyp start poses that live on the device, in the same launches, and sps_ndt_align_batch's
+ * choice among the end poses.    Additive: sps_version() is unchanged, and every call above keeps its
+ * behaviour and its bits.
+ *
+ * sps_ndt_pyramid_align_batch: hypothesis k starts from the row-major 4x4 T_init_dev[k] (the caller leaves it unchanged
+ *   until the stream has passed the call; work issued earlier on the stream may still be writing it) and is, operation for
+ *   operation and sum for sum, sps_ndt_pyramid_align from that pose: T_out_dev[k], status_dev[k] (int32[n_hyp][4]: code,
+ *   slots used, points counted in the last live slot, its level), trace_dev[k] (double[n_hyp][iters][4]), normal_dev[k]
+ *   (may be NULL; double[n_hyp][iters][28]) and level_dev[k] (int32[n_hyp][iters]) have the bits of the single call, the
+ *   zero rows and the -1 levels of slots that did no work included, and T_out_dev[k] is T_init_dev[k] bit for bit on status
+ *   2 and 3.  Every hypothesis has state words of its own in the scratch (done, level, slots used per level): hypotheses
+ *   stand at different levels in the same slot, and one whose status is final sits out the remaining slots while the others
+ *   go on.  The scan points and the levels are shared.  With a pyramid of one level every output, final_dev, best_dev and
+ *   T_best_dev included, has the bits of sps_ndt_align_batch on a single map of that resolution.
+ *   Launches: 1 (initialise: poses, statuses, state words and the per-slot rows) + 2 * iters (A with grid
+ *   (ceil(cap / 32), n_hyp), B with grid n_hyp) + 2, whatever the data, no memset:
+ *     A once more, sps_ndt_align_batch's, for every hypothesis at its final pose whatever its status, against the map and
+ *        the Gaussian fit of the finest level (so the scores compare however far a hypothesis got): final_dev[k] = (score,
+ *        points counted), the partial rows added in launch B's block order;
+ *     select, sps_ndt_align_batch's: the highest final score among the hypotheses with status 0 or 1 (one that used up
+ *        `iters` on a coarse level is eligible) and at least min_corr points counted at the final pose; equal scores go to
+ *        the lowest k; NaN never wins.  best_dev = (k, status of k, points counted at its final pose, n_hyp) and T_best_dev
+ *        = T_out_dev[k]; where no hypothesis qualifies best_dev = (-1, -1, 0, n_hyp) and T_best_dev = T_init_dev[0].
+ *   iters = 0 is legal: final_dev[k] is then what sps_ndt_score_poses gives for T_init_dev[k] on a single map of the finest
+ *   resolution.  T_best_dev and best_dev + 1 serve as T_dev and gate_dev of sps_ndt_pyramid_update / sps_ndt_pyramid_carve.
+ *   Arguments are checked as for sps_ndt_pyramid_align (level_iters: host int32[n_levels], each >= 1), and 1 <= n_hyp <=
+ *   SPS_NDT_MAX_HYP.  A context without a pyramid is refused with SPS_ERR_INVALID; a static and a dynamic pyramid are both
+ *   accepted.  scratch_dev: sps_ndt_pyramid_align_batch_scratch(cap, n_hyp) bytes, the partial rows of every hypothesis
+ *   and then NDT_PYR_STATE = 8 state words each (-1 for arguments out of range).  Never allocates, never synchronises, never
+ *   raises the sticky error. */
+int64_t sps_ndt_pyramid_align_batch_scratch(int64_t cap, int n_hyp);
+int sps_ndt_pyramid_align_batch(sps_ctx *ctx, const double *pts_dev, const int32_t *n_dev, int64_t cap, const double *T_init_dev,
+                                int n_hyp, int iters, const int32_t *level_iters, int neighbours, int min_corr, double tol_t,
+                                double tol_r, double *T_out_dev, int32_t *status_dev, double *trace_dev, double *normal_dev,
+                                int32_t *level_dev, double *final_dev, int32_t *best_dev, double *T_best_dev, void *scratch_dev,
+                                void *stream);
+
 /* ---- NDT localiser, distribution to distribution ------------------------------------------------------------------------
  * hdl_localization's other registration family (reg_method NDT_CUDA_D2D / VGICP): the scan is reduced to Gaussians too, one
  * per cell of the sensor frame, and Gaussians are registered against Gaussians.    Additive: sps_version()

@@ -141,10 +141,11 @@ def hypothesis_grid(counts, steps, option="--hypotheses", step_option="--hypothe
 
 def closed_loop(name, f, pc_map, replay, finish, traj_out, which="icp", hypotheses=None, search=None, update_map=False,
                 cell_capacity=None, max_cell_points=0, resolutions=None, level_iterations=None, carve_map=False,
-                carve_options=None, level_capacities=None, estimator=None, source=None):
+                carve_options=None, level_capacities=None, estimator=None, source=None, coarse_to_fine=False):
     """--localise: one LocalisationLoop step per frame, scored against the replayed poses.  ``estimator``: None, or the
     options of --estimator ukf (initial_velocity, scan_period, imu: None / a rate in Hz / an array of rows t ax .. gz).
-    ``source``: None, or the keywords of NDTLocaliser(source="cells", ...) of --source cells."""
+    ``source``: None, or the keywords of NDTLocaliser(source="cells", ...) of --source cells.  ``coarse_to_fine``: hypotheses,
+    search and the estimator's device path register on the pyramid of --resolutions."""
     from sps_amd.localiser import LocalisationLoop, NDTLocaliser, ScanToMapLocaliser
     from sps_amd.trajectory import ape_translation, rotation_angle, write_trajectory
     skw = source or {}
@@ -159,6 +160,7 @@ def closed_loop(name, f, pc_map, replay, finish, traj_out, which="icp", hypothes
         n_cells = NDTLocaliser(pc_map[:, :3]).n_cells
         localiser = NDTLocaliser(pc_map[:, :3], cell_capacity=cell_capacity or max(2 * n_cells, 4096), **skw)
     elif resolutions is not None:                                # coarse to fine; hypotheses and search keep the single map
+                                                                 # unless --coarse-to-fine sends them to the pyramid too
         caps = level_iterations or (30,) * len(resolutions)       # the budget is their sum: it cuts no level short
         localiser = NDTLocaliser(pc_map[:, :3], resolutions=resolutions, iterations=sum(caps), level_iterations=caps)
     else:
@@ -173,7 +175,7 @@ def closed_loop(name, f, pc_map, replay, finish, traj_out, which="icp", hypothes
                 est = PoseEstimator(T, localiser.device, initial_velocity=estimator["initial_velocity"])
             loop = LocalisationLoop(f, localiser, T, hypotheses=hypotheses, search=search, update_map=update_map,
                                     max_cell_points=max_cell_points, carve_map=carve_map, carve_options=carve_options,
-                                    estimator=est)
+                                    estimator=est, coarse_to_fine=coarse_to_fine)
             if est is not None:
                 print("estimator: ukf  start of the registration: " + ("device pose" if loop.device_guess else "host pose"))
         if estimator is None:
@@ -274,6 +276,9 @@ def frame_motion(estimator, k):
 @click.option("--level-iterations", "level_iterations", type=str, default=None,
               help="with --resolutions: N0,N1,... the most iterations each level may use (default: 30 each); their sum is the "
                    "frame's budget")
+@click.option("--coarse-to-fine", "coarse_to_fine", is_flag=True,
+              help="with --resolutions and one of --hypotheses, --search, --estimator ukf: these register on the pyramid too, "
+                   "from start poses on the device (default: on the single 1 m map beside it)")
 @click.option("--level-capacities", "level_capacities", type=str, default=None,
               help="with --resolutions and --update-map or --carve-map: C0,C1,... cells every level of the online pyramid has "
                    "room for (default per level: twice its cells, at least 4096)")
@@ -296,8 +301,10 @@ def frame_motion(estimator, k):
               help="with --estimator: a text file of rows `t ax ay az gx gy gz`, scan k being at k * scan-period")
 def main(name, weights, sequence, config, epsilon, out_dir, n_synth, localise, which, traj_out, hyp_counts, hyp_steps,
          search_counts, search_steps, update_map, cell_capacity, max_cell_points, carve_map, carve_miss_frames, carve_sigma,
-         resolutions, level_iterations, level_capacities, source, source_resolution, source_min_points, estimator,
-         initial_velocity, scan_period, imu_rate, imu_file):
+         resolutions, level_iterations, coarse_to_fine, level_capacities, source, source_resolution, source_min_points,
+         estimator, initial_velocity, scan_period, imu_rate, imu_file):
+    if coarse_to_fine and (resolutions is None or (hyp_counts is None and search_counts is None and estimator is None)):
+        raise click.UsageError("--coarse-to-fine needs --resolutions and one of --hypotheses, --search, --estimator ukf")
     if source is not None and (which != "ndt" or not localise):
         raise click.UsageError("--source needs --localise --localiser ndt")
     if (source_resolution is not None or source_min_points is not None) and source != "cells":
@@ -353,7 +360,7 @@ def main(name, weights, sequence, config, epsilon, out_dir, n_synth, localise, w
     if resolutions is not None and (update_map or carve_map):
         if cell_capacity is not None:
             raise click.UsageError("--cell-capacity is the single map's: with --resolutions give --level-capacities")
-        if hyp_counts is not None or search_counts is not None:
+        if (hyp_counts is not None or search_counts is not None) and not coarse_to_fine:
             raise click.UsageError("--resolutions with --update-map or --carve-map takes no --hypotheses and no --search: they "
                                    "register on the single map, which stays static")
     if update_map and which != "ndt":
@@ -407,7 +414,7 @@ def main(name, weights, sequence, config, epsilon, out_dir, n_synth, localise, w
     if localise:
         closed_loop(name, f, pc_map, replay, finish, traj_out, which or "icp", hypotheses, search, update_map, cell_capacity,
                     max_cell_points, resolutions, level_iterations, carve_map, carve_options or None, level_capacities,
-                    estimator, source)
+                    estimator, source, coarse_to_fine)
     elif traj_out:
         raise click.UsageError("--traj-out needs --localise")
     in_flight, prev_pose = None, None

@@ -159,6 +159,9 @@ def _load() -> C.CDLL:
         "sps_ndt_pyramid_carve": (i32, [vp, vp, vp, i64, vp, vp, vp, vp, C.c_double, i32, i32, i32, vp, vp, vp]),
         "sps_ndt_pyramid_info": (i32, [vp, i32, vp]),
         "sps_ndt_pyramid_carve_cells": (i32, [vp, i32, vp, vp, vp]),
+        "sps_ndt_pyramid_align_batch_scratch": (i64, [i64, i32]),
+        "sps_ndt_pyramid_align_batch": (i32, [vp, vp, vp, i64, vp, i32, i32, vp, i32, i32, C.c_double, C.c_double, vp, vp, vp, vp,
+                                              vp, vp, vp, vp, vp, vp]),
         "sps_ndt_source_scratch": (i64, [i64]),
         "sps_ndt_source_build": (i32, [vp, vp, vp, i64, C.c_double, i32, C.c_double, vp, vp, vp, vp, vp]),
         "sps_ndt_align_d2d_scratch": (i64, [i64]),
@@ -204,6 +207,7 @@ EXPORTS = ["sps_last_error", "sps_version", "sps_ctx_create", "sps_ctx_destroy",
            "sps_ndt_pyramid_build", "sps_ndt_pyramid_cells", "sps_ndt_pyramid_align_scratch", "sps_ndt_pyramid_align",
            "sps_ndt_pyramid_build_dynamic", "sps_ndt_pyramid_update_scratch", "sps_ndt_pyramid_update",
            "sps_ndt_pyramid_carve_scratch", "sps_ndt_pyramid_carve", "sps_ndt_pyramid_info", "sps_ndt_pyramid_carve_cells",
+           "sps_ndt_pyramid_align_batch_scratch", "sps_ndt_pyramid_align_batch",
            "sps_ndt_source_scratch", "sps_ndt_source_build", "sps_ndt_align_d2d_scratch", "sps_ndt_align_d2d",
            "sps_ukf_state_bytes", "sps_ukf_init", "sps_ukf_predict", "sps_ukf_predict_dt", "sps_ukf_correct"]
 NDT_SRC_REC = 10           # SPS_NDT_SRC_REC: doubles of a source record
@@ -581,6 +585,17 @@ class Context:
         check(lib.sps_ndt_pyramid_align(self.handle, pts_ptr, n_dev_ptr, int(cap), self._mat(T_init), int(iters), caps,
                                         int(neighbours), int(min_corr), float(tol_t), float(tol_r), T_out_ptr, status_ptr,
                                         trace_ptr, normal_ptr, level_ptr, scratch_ptr, stream))
+
+    # ---- NDT localiser, pyramid, several hypotheses (include/sps_hip.h, same title) ----
+    def ndt_pyramid_align_batch(self, pts_ptr, n_dev_ptr: int, cap: int, T_init_ptr, n_hyp: int, iters: int, level_iters,
+                                neighbours: int, min_corr: int, tol_t: float, tol_r: float, T_out_ptr: int, status_ptr: int,
+                                trace_ptr, normal_ptr, level_ptr, final_ptr: int, best_ptr: int, T_best_ptr: int,
+                                scratch_ptr: int, stream: int):
+        caps = (C.c_int32 * len(level_iters))(*[int(v) for v in level_iters])
+        check(lib.sps_ndt_pyramid_align_batch(self.handle, pts_ptr, n_dev_ptr, int(cap), T_init_ptr, int(n_hyp), int(iters), caps,
+                                              int(neighbours), int(min_corr), float(tol_t), float(tol_r), T_out_ptr, status_ptr,
+                                              trace_ptr, normal_ptr, level_ptr, final_ptr, best_ptr, T_best_ptr, scratch_ptr,
+                                              stream))
 
     # ---- NDT localiser, distribution to distribution (include/sps_hip.h, same title) ----
     def ndt_source_build(self, pts_ptr, n_dev_ptr: int, cap: int, source_resolution: float, min_points: int, eig_ratio: float,

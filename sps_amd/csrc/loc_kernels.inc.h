@@ -240,11 +240,20 @@ __device__ inline void loc_sum_rows(const double *__restrict__ partial, int nb, 
 // status[2], the 6 x 6 Cholesky solve, Rodrigues, the pose update.  Returns -1 after a step (vn = |v|, th = |omega|, also in
 // the trace row), or the final code 2 (too few correspondences) / 3 (singular) with T = T_init and status[0] = the code.
 // What a step means for the call is the caller's: loc_solve_body below, k_ndt_pyr_solve in ndt_pyramid_kernels.inc.h.
-__device__ inline int loc_solve_step(const double *tot, int iter, int min_corr, const double *__restrict__ T_init,
-                                     double *__restrict__ T, int *__restrict__ status, double *__restrict__ trace,
-                                     double *__restrict__ normal, double &vn_out, double &th_out) {
+//
+// The arrays of the 6 x 6 solve live where the caller puts them (loc_solve_step_in): a kernel that may not use scratch memory
+// hands in workgroup memory (k_ndt_pyr_solve_batch, ndt_pyramid_batch_kernels.inc.h); loc_solve_step keeps them private.
+struct alignas(16) LocSolveWork {
+  double L[6][6], H[6][6];
+};
+
+__device__ inline int loc_solve_step_in(LocSolveWork &w, const double *tot, int iter, int min_corr,
+                                        const double *__restrict__ T_init, double *__restrict__ T, int *__restrict__ status,
+                                        double *__restrict__ trace, double *__restrict__ normal, double &vn_out,
+                                        double &th_out) {
   const int n_corr = (int)tot[28];
   const double sum_d2 = tot[27];
+  double(&L)[6][6] = w.L, (&H)[6][6] = w.H;
   double b[6];
   for (int i = 0; i < 6; ++i) b[i] = -tot[21 + i];
   if (normal) {
@@ -258,11 +267,10 @@ __device__ inline int loc_solve_step(const double *tot, int iter, int min_corr, 
   status[1] = iter + 1;
   status[2] = n_corr;
   int code = -1;
-  double L[6][6], y[6], x[6];
+  double y[6], x[6];
   if (n_corr < min_corr) {
     code = 2;
   } else {
-    double H[6][6];
     for (int i = 0, k = 0; i < 6; ++i)
       for (int j = i; j < 6; ++j, ++k) H[i][j] = H[j][i] = tot[k];
     for (int j = 0; j < 6 && code < 0; ++j) {
@@ -330,6 +338,13 @@ __device__ inline int loc_solve_step(const double *tot, int iter, int min_corr, 
   tr[2] = vn, tr[3] = th;
   vn_out = vn, th_out = th;
   return -1;
+}
+
+__device__ inline int loc_solve_step(const double *tot, int iter, int min_corr, const double *__restrict__ T_init,
+                                     double *__restrict__ T, int *__restrict__ status, double *__restrict__ trace,
+                                     double *__restrict__ normal, double &vn_out, double &th_out) {
+  LocSolveWork w;
+  return loc_solve_step_in(w, tot, iter, min_corr, T_init, T, status, trace, normal, vn_out, th_out);
 }
 
 // Launch B for one pose, by one workgroup of 256 (k_loc_solve; k_loc_solve_batch in ndt_batch_kernels.inc.h runs it once per

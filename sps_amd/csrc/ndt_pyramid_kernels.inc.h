@@ -4,7 +4,8 @@
 //
 //   k_ndt_pyr_init    T_out = T_init, status = (1, 0, 0, 0), the state words 0, level[s] = -1, trace and normal rows 0
 //   k_ndt_pyr_assoc   (launch A of a slot)  ndt_assoc_body against the map of the level the state names
-//   k_ndt_pyr_solve   (launch B of a slot)  loc_sum_rows + loc_solve_step, then the handoff rule
+//   k_ndt_pyr_solve   (launch B of a slot)  loc_sum_rows + loc_solve_step, then the handoff rule (ndt_pyr_handoff: its one
+//                     definition, shared with k_ndt_pyr_solve_batch of ndt_pyramid_batch_kernels.inc.h)
 //
 // The levels are the maps k_radius_cells_insert and k_ndt_cells build, one NdtPyrLevel (map + Gaussian fit) each in a device
 // array.  Which level a slot runs at is decided on the device: the state words live in the caller's scratch behind the
@@ -71,6 +72,31 @@ __global__ __launch_bounds__(256) void k_ndt_pyr_assoc(const double *__restrict_
   ndt_assoc_body(pts, n_dev, cap, d.m, d.gs, neighbours, T, partial, lds);
 }
 
+// The handoff rule, by the one thread that made a step at level l (k_ndt_pyr_solve below; k_ndt_pyr_solve_batch in
+// ndt_pyramid_batch_kernels.inc.h runs it once per hypothesis): that level's count of used slots goes up; a converged step
+// ends the call with status 0 on the last level and hands the pose to level l + 1 otherwise; a step that is not converged
+// does the same once the level has used its cap, except that the status stays 1.  state: the call's (the hypothesis') words.
+__device__ inline void ndt_pyr_handoff(int l, int n_levels, NdtPyrCaps caps, bool converged, int *__restrict__ status,
+                                       int *__restrict__ state) {
+  const int used = state[2 + l] + 1;
+  state[2 + l] = used;
+  const int cap_l = l == 0 ? caps.v[0] : (l == 1 ? caps.v[1] : (l == 2 ? caps.v[2] : caps.v[3]));
+  const bool last = l == n_levels - 1;
+  if (converged) {
+    if (last) {
+      status[0] = 0;
+      state[0] = 1;
+    } else {
+      state[1] = l + 1;
+    }
+  } else if (used >= cap_l) {
+    if (last)
+      state[0] = 1;
+    else
+      state[1] = l + 1;
+  }
+}
+
 // Launch B, one workgroup of 256.  After a step at level l that level's count of used slots goes up; a converged step
 // (|v| < tol_t and |omega| < tol_r) ends the call with status 0 on the last level and hands the pose to level l + 1
 // otherwise; a step that is not converged does the same once the level has used its cap, except that the status stays 1.
@@ -95,23 +121,7 @@ __global__ __launch_bounds__(256) void k_ndt_pyr_solve(const double *__restrict_
     state[0] = 1;
     return;
   }
-  const int used = state[2 + l] + 1;
-  state[2 + l] = used;
-  const int cap_l = l == 0 ? caps.v[0] : (l == 1 ? caps.v[1] : (l == 2 ? caps.v[2] : caps.v[3]));
-  const bool last = l == n_levels - 1;
-  if (vn < tol_t && th < tol_r) {
-    if (last) {
-      status[0] = 0;
-      state[0] = 1;
-    } else {
-      state[1] = l + 1;
-    }
-  } else if (used >= cap_l) {
-    if (last)
-      state[0] = 1;
-    else
-      state[1] = l + 1;
-  }
+  ndt_pyr_handoff(l, n_levels, caps, vn < tol_t && th < tol_r, status, state);
 }
 
 #pragma clang fp contract(fast)

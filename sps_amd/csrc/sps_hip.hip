@@ -156,6 +156,7 @@ int fail(int code, const char *fmt, ...) {
 #include "ndt_carve_kernels.inc.h"
 #include "ndt_pyramid_kernels.inc.h"
 #include "ndt_pyramid_update_kernels.inc.h"
+#include "ndt_pyramid_batch_kernels.inc.h"
 #include "ukf_kernels.inc.h"
 
 // ------------------------------------------------------------------------------------------
@@ -2272,6 +2273,7 @@ int sps_get_feature(sps_ctx *c, const char *name, float *out_dev, int64_t *rows,
 #include "ndt_carve_host.inc.h"
 #include "ndt_pyramid_host.inc.h"
 #include "ndt_pyramid_update_host.inc.h"
+#include "ndt_pyramid_batch_host.inc.h"
 #include "ukf_host.inc.h"
 
 }  // extern "C"

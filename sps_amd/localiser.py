@@ -38,6 +38,10 @@ through for ``miss_frames`` frames on end while none ends in it is cleared.
 pyramid"): one static map per resolution beside the single one, and ``submit`` / ``submit_filtered`` /
 ``__call__`` run one alignment that starts on the coarsest map and hands its pose to the next finer one on the device.
 
+``submit_batch``, ``submit_from_device`` and ``relocalise`` take ``coarse_to_fine=True`` on such a localiser (C ABI: "NDT
+localiser, pyramid, several hypotheses"): their hypotheses are then registered on the pyramid, each at a level
+of its own, from start poses that live on the device, and selected by the score on the finest level.
+
 ``NDTLocaliser(..., resolutions=(2.0, 1.0, 0.5), level_capacities=(c0, c1, c2))`` makes that pyramid an online one (C ABI:
 "NDT localiser, online pyramid"): every level is a dynamic map, and ``integrate`` / ``carve`` / ``submit(...,
 integrate=True, carve=True)`` update and carve all levels in one set of launches; their results are then tuples, one entry per
@@ -145,14 +149,16 @@ def _pose_layout(K, with_normal, pyramid=False, L=None, integrate=False, carve=F
     return o
 
 
-def _batch_layout(K, I, with_normal, integrate=False, carve=False):
+def _batch_layout(K, I, with_normal, integrate=False, carve=False, pyramid=False, L=None):
     """offsets (in doubles) of a batch's one float64 buffer: T_out[K][16] | status int32[K][4] | n_points int32 (+ pad) |
-    best int32[4] | T_best[16] | final[K][2] | trace[K][I][4] | normal[K][I][28] | info int32[4] of the update | info
-    int32[4] of the carve.  ``hands_on``, as in ``_pose_layout``: ``T_best`` and ``best[1]``, the selected hypothesis' status,
-    -1 where none was selected"""
+    best int32[4] | T_best[16] | final[K][2] | trace[K][I][4] | normal[K][I][28] | level int32[K][I] (+ pad) of a coarse-to-fine
+    batch (``pyramid``) | info int32[4] of the update | info int32[4] of the carve (an online pyramid of L levels: int32[L][4]
+    each).  ``hands_on``, as in ``_pose_layout``: ``T_best`` and ``best[1]``, the selected hypothesis' status, -1 where none
+    was selected"""
+    w = 2 if L is None else 2 * L                                    # doubles of one call's info words
     o = _offsets((("T_out", 16 * K), ("status", 2 * K), ("n_points", 1), ("best", 2), ("T_best", 16), ("final", 2 * K),
                   ("trace", 4 * K * I), ("normal", 28 * K * I if with_normal else 0)),
-                 (("update", 2 if integrate else 0), ("carve", 2 if carve else 0)))
+                 (("levels", (K * I + 1) // 2 if pyramid else 0), ("update", w if integrate else 0), ("carve", w if carve else 0)))
     o["hands_on"] = (o["T_best"] * 8, o["best"] * 8 + 4)
     return o
 
@@ -238,21 +244,24 @@ class BatchPoseResult:
     counts: np.ndarray         # [K] int, the scan points counted at that pose
     best: int                  # the hypothesis selected, or -1 where none has status 0 / 1 and enough points counted
     pose: np.ndarray           # 4x4: results[best].pose, or the first start pose when best is -1
-    map_update: object = None  # MapUpdateResult of the frame, with integrate=True
-    map_carve: object = None   # MapCarveResult of the frame, with carve=True
+    map_update: object = None  # MapUpdateResult of the frame, with integrate=True (an online pyramid: a tuple, one per level)
+    map_carve: object = None   # MapCarveResult of the frame, with carve=True (an online pyramid: a tuple, one per level)
 
 
 class PendingPoses(_Pending):
     """A batch of localisations whose work has been issued; everything lives on the device until result()."""
 
-    def __init__(self, n_hyp, iters, with_normal, host, event, keep, at=0, integrate=False, carve=False):
+    def __init__(self, n_hyp, iters, with_normal, host, event, keep, at=0, integrate=False, carve=False, pyramid=False,
+                 n_levels=None):
         super().__init__(host, event, keep)
         self._n_hyp, self._iters, self._with_normal = n_hyp, iters, with_normal
         self._at = at                                                # doubles in front of the batch's part of the buffer
         self._integrate, self._carve = integrate, carve              # the batch's buffer has their info words
+        self._pyramid, self._n_levels = pyramid, n_levels            # coarse to fine: level rows; online: info words per level
 
     def _layout(self):
-        return _batch_layout(self._n_hyp, self._iters, self._with_normal, self._integrate, self._carve)
+        return _batch_layout(self._n_hyp, self._iters, self._with_normal, self._integrate, self._carve, self._pyramid,
+                             self._n_levels)
 
     def result(self) -> BatchPoseResult:
         return self._parse(self._wait())
@@ -267,15 +276,18 @@ class PendingPoses(_Pending):
         final = h[o["final"]:o["trace"]].reshape(K, 2)
         trace = h[o["trace"]:o["normal"]].reshape(K, I, 4)
         normal = h[o["normal"]:o["size"]].reshape(K, I, 28) if self._with_normal else None
+        levels = h[o["levels"]:o["update"]].view(np.int32)[:K * I].reshape(K, I) if self._pyramid else None
         results = []
         for k in range(K):
             code, it, n_corr, _ = (int(x) for x in status[k])
             tr = trace[k, :it].copy()
             rmse = math.sqrt(tr[-1, 1] / n_corr) if it and n_corr > 0 else float("nan")
             results.append(PoseResult(T_out[k].copy(), code, it, n_corr, rmse, tr,
-                                      normal[k, :it].copy() if normal is not None else None, n_points))
-        upd = _map_update_of(h[o["update"]:o["carve"]].view(np.int32), n_points) if self._integrate else None
-        carved = _map_carve_of(h[o["carve"]:o["total"]].view(np.int32), n_points) if self._carve else None
+                                      normal[k, :it].copy() if normal is not None else None, n_points,
+                                      levels=levels[k, :it].astype(np.int64) if levels is not None else None))
+        L = self._n_levels
+        upd = _per_level(_map_update_of, h[o["update"]:o["carve"]].view(np.int32), n_points, L) if self._integrate else None
+        carved = _per_level(_map_carve_of, h[o["carve"]:o["total"]].view(np.int32), n_points, L) if self._carve else None
         return BatchPoseResult(results, final[:, 0].copy(), final[:, 1].astype(np.int64), int(best[0]),
                                h[o["T_best"]:o["final"]].reshape(4, 4).copy(), upd, carved)
 
@@ -598,13 +610,15 @@ class NDTLocaliser(ScanToMapLocaliser):
     ``iterations`` is the budget of slots (one slot = one iteration at some level) and ``level_iterations`` the most slots
     each level may use (None: ``iterations`` each).  A level hands its pose to the next when it converges or has used its
     slots; only the last level's convergence is status 0, and the result's ``levels`` tells the level of every slot.
-    Status 2 / 3 at any level are final and give the guess back.  ``submit_batch``, ``score_poses``, ``relocalise`` and
-    ``map_cells`` keep using the single map of edge ``resolution``; ``pyramid_cells(level)`` shows a level.
+    Status 2 / 3 at any level are final and give the guess back.  ``submit_batch``, ``submit_from_device`` and
+    ``relocalise`` register on the pyramid too when asked with ``coarse_to_fine=True``; without it they,
+    ``score_poses`` and ``map_cells`` keep using the single map of edge ``resolution``; ``pyramid_cells(level)`` shows a level.
 
     ``level_capacities`` (with ``resolutions``; one cell capacity per level, each at least the level's cells): the pyramid's
     levels are online maps, ``integrate`` / ``carve`` and ``submit(..., integrate=True, carve=True)`` work on all of them
     at once and report one result per level; ``pyramid_info(level)`` and ``carve_state(level)`` show a level.  The single
-    map stays static, so the batch and the search refuse ``integrate`` and ``carve``.  ``capacity`` is then at most 65536.
+    map stays static, so the batch and the search refuse ``integrate`` and ``carve`` unless they register
+    ``coarse_to_fine``: then both work on all levels at the selected pose.  ``capacity`` is then at most 65536.
 
     ``source="cells"`` registers distribution to distribution: the thinned scan is reduced to one Gaussian per cell of edge
     ``source_resolution`` (default: ``resolution``) of the sensor frame, valid from ``source_min_points`` points (default:
@@ -640,6 +654,7 @@ class NDTLocaliser(ScanToMapLocaliser):
         self._open(xyz, leaf, iterations, min_correspondences, tol_t, tol_r, device, capacity, _native.lib.sps_ndt_align_scratch)
         with torch.cuda.device(self.device):
             self._batch_scratch, self._batch_hyp = None, 0
+            self._pyr_batch_scratch, self._pyr_batch_hyp = None, 0
             self._score_scratch, self._score_poses = None, 0
             if self.source == "cells":                               # the scan's cells, their counts, (cells, valid cells)
                 self._src = torch.empty((self.capacity, _native.NDT_SRC_REC), dtype=torch.float64, device=self.device)
@@ -894,61 +909,95 @@ class NDTLocaliser(ScanToMapLocaliser):
 
     @torch.no_grad()
     def submit_batch(self, rows, count, T_inits, with_normal: bool = False, iterations: int = None, integrate: bool = False,
-                     max_cell_points: int = 0, carve: bool = False, carve_options: dict = None) -> PendingPoses:
+                     max_cell_points: int = 0, carve: bool = False, carve_options: dict = None,
+                     coarse_to_fine: bool = False) -> PendingPoses:
         """``submit`` from the K start poses ``T_inits`` [K, 4, 4] (1 <= K <= 64) at once: the scan is thinned once, every
         hypothesis is registered as ``submit`` would register it from its pose, and the hypothesis with the highest NDT
         score at its final pose is selected among those with status 0 / 1 and at least ``min_correspondences`` points
         counted there (equal scores: the lowest index).  Issued on the current stream; ``result()`` -> BatchPoseResult.
-        ``integrate`` and ``carve``: as for ``submit``, at the selected pose and only where a hypothesis was selected."""
-        rows, copts = self._checked_for_batch("submit_batch", rows, integrate, max_cell_points, carve, carve_options)
+        ``integrate`` and ``carve``: as for ``submit``, at the selected pose and only where a hypothesis was selected.
+
+        ``coarse_to_fine`` (a localiser with ``resolutions``; False: the single map at ``resolution``, as ever): every
+        hypothesis is registered on the pyramid, as ``submit`` registers there (C ABI: "NDT localiser, pyramid, several
+        hypotheses").  ``iterations`` is then the budget of slots and the caps are ``level_iterations`` or
+        that budget per level; ``results[k].levels`` tells the level of every slot of hypothesis k and ``iterations`` counts
+        its slots; the final scores are taken on the finest level, however far a hypothesis got.  On an online pyramid
+        ``integrate`` and ``carve`` then work on all levels at the selected pose, and their results are tuples, one entry
+        per level."""
+        rows, copts = self._checked_for_batch("submit_batch", rows, integrate, max_cell_points, carve, carve_options,
+                                              coarse_to_fine)
         T = _checked_poses(T_inits, "T_inits", MAX_HYPOTHESES, "K")
-        return self._issue_batch(rows, count, T, len(T), with_normal, iterations, integrate, max_cell_points, copts)
+        return self._issue_batch(rows, count, T, len(T), with_normal, iterations, integrate, max_cell_points, copts,
+                                 coarse_to_fine)
 
     @torch.no_grad()
     def submit_from_device(self, rows, count, T_init_dev, with_normal: bool = False, iterations: int = None,
                            integrate: bool = False, max_cell_points: int = 0, carve: bool = False,
-                           carve_options: dict = None) -> PendingPoses:
+                           carve_options: dict = None, coarse_to_fine: bool = False) -> PendingPoses:
         """``submit_batch`` with one hypothesis whose start pose is already on the device: ``T_init_dev`` holds 16 contiguous
         float64 entries (a row-major 4 x 4, e.g. ``PoseEstimator.pose_dev``) that work issued earlier on the current stream
         may still be writing.  The host never sees the pose; hypothesis 0 of the result is what ``submit`` gives from the
-        same pose, bit for bit.  A pose that is not finite ends as such a pose does in ``sps_ndt_align_batch``."""
-        rows, copts = self._checked_for_batch("submit_from_device", rows, integrate, max_cell_points, carve, carve_options)
+        same pose, bit for bit.  A pose that is not finite ends as such a pose does in ``sps_ndt_align_batch``.
+        ``coarse_to_fine``: as for ``submit_batch``; hypothesis 0 is then what ``submit`` gives on the pyramid."""
+        rows, copts = self._checked_for_batch("submit_from_device", rows, integrate, max_cell_points, carve, carve_options,
+                                              coarse_to_fine)
         T_dev = T_init_dev
         if not (torch.is_tensor(T_dev) and T_dev.is_cuda and T_dev.device == self.device and T_dev.dtype == torch.float64
                 and T_dev.numel() == 16 and T_dev.is_contiguous()):
             raise TypeError("T_init_dev must be 16 contiguous float64 entries on the localiser's device")
-        return self._issue_batch(rows, count, T_dev, 1, with_normal, iterations, integrate, max_cell_points, copts)
+        return self._issue_batch(rows, count, T_dev, 1, with_normal, iterations, integrate, max_cell_points, copts,
+                                 coarse_to_fine)
 
-    def _checked_for_batch(self, what, rows, integrate, max_cell_points, carve, carve_options):
-        """the checks of everything that registers on the single map, in their order -> (the checked rows, the carve's options)"""
+    def _checked_for_batch(self, what, rows, integrate, max_cell_points, carve, carve_options, coarse_to_fine=False):
+        """the checks of everything that registers from poses on the device, in their order -> (the checked rows, the carve's
+        options).  Without ``coarse_to_fine`` the work is on the single map; with it on the pyramid, which must exist and
+        whose levels ``integrate`` and ``carve`` then mean"""
         self._refuse_cells(what)
-        self._check_integrate(integrate, max_cell_points, single_map=True)
-        copts = self._check_carve(carve, carve_options, single_map=True)
+        if coarse_to_fine and self.resolutions is None:
+            raise ValueError("coarse_to_fine needs a localiser with a pyramid: NDTLocaliser(..., resolutions=...)")
+        self._check_integrate(integrate, max_cell_points, single_map=not coarse_to_fine)
+        copts = self._check_carve(carve, carve_options, single_map=not coarse_to_fine)
         return self._checked_rows(rows), copts
 
-    def _issue_batch(self, rows, count, poses, K, with_normal, iterations, integrate, max_cell_points, copts):
+    def _batch_shape(self, integrate, carve, coarse_to_fine):
+        """the last four arguments of ``_batch_layout`` and of ``PendingPoses``"""
+        online = coarse_to_fine and self.level_capacities is not None
+        return integrate, carve, bool(coarse_to_fine), len(self.level_capacities) if online else None
+
+    def _issue_batch(self, rows, count, poses, K, with_normal, iterations, integrate, max_cell_points, copts,
+                     coarse_to_fine=False):
         """the batch of the K start poses ``poses``: a host array [K, 4, 4], or 16 float64 entries on the device (K = 1)"""
         I = self.iterations if iterations is None else int(iterations)
-        o = _batch_layout(K, I, with_normal, integrate, copts is not None)
+        shape = self._batch_shape(integrate, copts is not None, coarse_to_fine)
+        o = _batch_layout(K, I, with_normal, *shape)
 
         def work(out, n_ptr, T_dev, s):
-            self._align_batch(n_ptr, T_dev.data_ptr(), K, I, with_normal, out.data_ptr(), o, s, integrate, max_cell_points, copts)
-        return PendingPoses(K, I, with_normal, *self._issue(rows, count, o["total"], o["n_points"] * 8, work, poses),
-                            integrate=integrate, carve=copts is not None)
+            self._align_batch(n_ptr, T_dev.data_ptr(), K, I, with_normal, out.data_ptr(), o, s, integrate, max_cell_points, copts,
+                              coarse_to_fine)
+        return PendingPoses(K, I, with_normal, *self._issue(rows, count, o["total"], o["n_points"] * 8, work, poses), 0, *shape)
 
     def submit_filtered_batch(self, pending, T_inits, **kw) -> PendingPoses:
         """``submit_batch`` of the kept rows of a pending SPSFilter / SPSCVMFilter frame, without the frame's result()."""
         return self.submit_batch(pending._filtered, pending.count_dev, T_inits, **kw)
 
-    def _align_batch(self, n_ptr, T_ptr, K, I, with_normal, base, o, s, integrate=False, max_cell_points=0, carve_opts=None):
-        """the K alignments of self._pts from the device poses at T_ptr into the batch's buffer at ``base`` (layout ``o``);
-        ``carve_opts``: then the carve at the selected pose, its info words last; ``integrate``: then the map update at the
-        selected pose, its info words behind the batch's part"""
-        self.ctx.ndt_align_batch(self._pts.data_ptr(), n_ptr, self.capacity, T_ptr, K, I, self.neighbours,
-                                 self.min_correspondences, self.outlier_ratio, self.tol_t, self.tol_r, base + o["T_out"] * 8,
-                                 base + o["status"] * 8, base + o["trace"] * 8 if I else None,
-                                 base + o["normal"] * 8 if with_normal and I else None, base + o["final"] * 8,
-                                 base + o["best"] * 8, base + o["T_best"] * 8, self._batch_scratch_for(K).data_ptr(), s)
+    def _align_batch(self, n_ptr, T_ptr, K, I, with_normal, base, o, s, integrate=False, max_cell_points=0, carve_opts=None,
+                     coarse_to_fine=False):
+        """the K alignments of self._pts from the device poses at T_ptr into the batch's buffer at ``base`` (layout ``o``), on
+        the single map or, ``coarse_to_fine``, on the pyramid; ``carve_opts``: then the carve at the selected pose, its info
+        words last; ``integrate``: then the map update at the selected pose, its info words behind the batch's part"""
+        trace_ptr, normal_ptr = base + o["trace"] * 8 if I else None, base + o["normal"] * 8 if with_normal and I else None
+        if coarse_to_fine:
+            caps = self.level_iterations or (max(I, 1),) * len(self.resolutions)
+            self.ctx.ndt_pyramid_align_batch(self._pts.data_ptr(), n_ptr, self.capacity, T_ptr, K, I, caps, self.neighbours,
+                                             self.min_correspondences, self.tol_t, self.tol_r, base + o["T_out"] * 8,
+                                             base + o["status"] * 8, trace_ptr, normal_ptr, base + o["levels"] * 8 if I else None,
+                                             base + o["final"] * 8, base + o["best"] * 8, base + o["T_best"] * 8,
+                                             self._pyr_batch_scratch_for(K).data_ptr(), s)
+        else:
+            self.ctx.ndt_align_batch(self._pts.data_ptr(), n_ptr, self.capacity, T_ptr, K, I, self.neighbours,
+                                     self.min_correspondences, self.outlier_ratio, self.tol_t, self.tol_r, base + o["T_out"] * 8,
+                                     base + o["status"] * 8, trace_ptr, normal_ptr, base + o["final"] * 8,
+                                     base + o["best"] * 8, base + o["T_best"] * 8, self._batch_scratch_for(K).data_ptr(), s)
         T_best, gate_ptr = (base + b for b in o["hands_on"])
         if carve_opts is not None:
             self._carve(n_ptr, None, T_best, gate_ptr, carve_opts, base + o["carve"] * 8, s)
@@ -961,6 +1010,13 @@ class NDTLocaliser(ScanToMapLocaliser):
                                               device=self.device)
             self._batch_hyp = K
         return self._batch_scratch
+
+    def _pyr_batch_scratch_for(self, K):
+        if K > self._pyr_batch_hyp:                                  # grows with the largest batch seen (stream-ordered reuse)
+            self._pyr_batch_scratch = torch.empty(_native.lib.sps_ndt_pyramid_align_batch_scratch(self.capacity, K),
+                                                  dtype=torch.uint8, device=self.device)
+            self._pyr_batch_hyp = K
+        return self._pyr_batch_scratch
 
     def _score(self, T_dev, P, n_points_ptr, score_ptr, s):
         """the scores of the P poses of T_dev for the thinned points in self._pts (their count at n_points_ptr)"""
@@ -989,20 +1045,23 @@ class NDTLocaliser(ScanToMapLocaliser):
     @torch.no_grad()
     def relocalise(self, rows, count, poses, keep: int = 8, with_normal: bool = False, iterations: int = None,
                    integrate: bool = False, max_cell_points: int = 0, carve: bool = False,
-                   carve_options: dict = None) -> PendingRelocalisation:
+                   carve_options: dict = None, coarse_to_fine: bool = False) -> PendingRelocalisation:
         """Thin, score the P poses ``poses`` [P, 4, 4] (e.g. ``T_center @ pose_grid(...)``), keep the best ``keep`` (1..64)
         by (score descending, index ascending) among those with at least ``min_correspondences`` points counted, register
         from these as ``submit_batch`` does and select among the end poses as it selects.  Everything is issued on the
         current stream with no synchronisation in between; ``result()`` -> RelocalisationResult.  ``integrate`` and
-        ``carve``: as for ``submit_batch``."""
-        rows, copts = self._checked_for_batch("relocalise", rows, integrate, max_cell_points, carve, carve_options)
+        ``carve``: as for ``submit_batch``.  ``coarse_to_fine``: the grid is scored and its best ``keep`` chosen on the single
+        map as ever; these are then registered as ``submit_batch(..., coarse_to_fine=True)`` registers them."""
+        rows, copts = self._checked_for_batch("relocalise", rows, integrate, max_cell_points, carve, carve_options,
+                                              coarse_to_fine)
         T = _checked_poses(poses)
         K = int(keep)
         if not 1 <= K <= MAX_HYPOTHESES:
             raise ValueError(f"keep must be in [1, {MAX_HYPOTHESES}]")
         P = len(T)
         I = self.iterations if iterations is None else int(iterations)
-        so, o = _search_layout(P, K), _batch_layout(K, I, with_normal, integrate, carve)
+        shape = self._batch_shape(integrate, carve, coarse_to_fine)
+        so, o = _search_layout(P, K), _batch_layout(K, I, with_normal, *shape)
 
         def work(out, n_ptr, T_dev, s):
             sbase = out.data_ptr()
@@ -1010,9 +1069,9 @@ class NDTLocaliser(ScanToMapLocaliser):
             self.ctx.ndt_top_poses(sbase + so["score"] * 8, T_dev.data_ptr(), P, self.min_correspondences, K,
                                    sbase + so["top"] * 8, sbase + so["T_top"] * 8, sbase + so["n_top"] * 8, s)
             self._align_batch(n_ptr, sbase + so["T_top"] * 8, K, I, with_normal, sbase + so["size"] * 8, o, s, integrate,
-                              max_cell_points, copts)
+                              max_cell_points, copts, coarse_to_fine)
         issued = self._issue(rows, count, so["size"] + o["total"], (so["size"] + o["n_points"]) * 8, work, T)
-        return PendingRelocalisation(P, PendingPoses(K, I, with_normal, *issued, so["size"], integrate, carve))
+        return PendingRelocalisation(P, PendingPoses(K, I, with_normal, *issued, so["size"], *shape))
 
     def relocalise_filtered(self, pending, poses, **kw) -> PendingRelocalisation:
         """``relocalise`` of the kept rows of a pending SPSFilter / SPSCVMFilter frame, without the frame's result()."""
@@ -1092,7 +1151,8 @@ class LocalisationLoop:
     and keeps the guess.
 
     ``update_map`` (a localiser with an online map: ``NDTLocaliser(..., cell_capacity=N)``, or with an online pyramid:
-    ``level_capacities``, whose frames report one result per level and take no hypotheses and no search): every frame's kept points, as
+    ``level_capacities``, whose frames report one result per level and take hypotheses and search with ``coarse_to_fine``
+    only): every frame's kept points, as
     thinned for the registration, are folded into the map at the frame's corrected pose, behind the registration on its
     stream.  The device gates the update on the registration's status, so a flagged frame leaves the map alone; the
     frame's ``pose_result.map_update`` (``batch.map_update``) tells what happened.  ``max_cell_points``: the forgetting
@@ -1112,15 +1172,20 @@ class LocalisationLoop:
     ``device_guess`` (None: where possible): the predicted pose starts the registration from the device
     (predict -> ``submit_from_device`` -> ``correct_from``, the guess read back with the frame's results: the one
     synchronisation per frame of the loop without an estimator).  That is possible where the filter takes no pose from the
-    loop (SPSCVMFilter, LTSFilter, ``takes_pose`` false) and the localiser is an NDTLocaliser without a pyramid, hypotheses
-    or search that registers points (``submit_from_device`` takes no source cells); the frame's ``batch`` is then the
-    one-hypothesis batch.  Everywhere else, and with ``device_guess=False``, the
+    loop (SPSCVMFilter, LTSFilter, ``takes_pose`` false) and the localiser is an NDTLocaliser without hypotheses or search
+    that registers points (``submit_from_device`` takes no source cells), and without a pyramid unless ``coarse_to_fine``
+    is set; the frame's ``batch`` is then the one-hypothesis batch.  Everywhere else, and with ``device_guess=False``, the
     predicted pose is fetched to the host first: one more small synchronisation per frame.  ``device_guess=True`` raises
-    where the device path is impossible."""
+    where the device path is impossible.
+
+    ``coarse_to_fine`` (a localiser with ``resolutions``; False: everything above, unchanged): the frames of ``hypotheses``
+    and ``search`` and the estimator's device path are registered on the pyramid (``submit_batch`` / ``relocalise`` /
+    ``submit_from_device`` with ``coarse_to_fine=True``).  An online pyramid with ``update_map`` /
+    ``carve_map`` may then take hypotheses and search, and with an estimator the device path is possible with a pyramid."""
 
     def __init__(self, filter, localiser, initial_pose, hypotheses=None, search=None, search_keep: int = 8,
                  update_map: bool = False, max_cell_points: int = 0, carve_map: bool = False, carve_options: dict = None,
-                 estimator=None, device_guess=None):
+                 estimator=None, device_guess=None, coarse_to_fine: bool = False):
         from .sps_filters import ConstantVelocityModel
         self.filter, self.localiser = filter, localiser
         # a localiser of the caller's own may have none of these: ScanToMapLocaliser's defaults then stand in
@@ -1129,11 +1194,17 @@ class LocalisationLoop:
         cells = source == "cells"
         if cells and (hypotheses is not None or search is not None):
             raise ValueError("hypotheses and search register points: they need an NDTLocaliser with source='points'")
+        self.coarse_to_fine = bool(coarse_to_fine)
+        if self.coarse_to_fine and resolutions is None:
+            raise ValueError("coarse_to_fine needs a localiser with a pyramid: NDTLocaliser(..., resolutions=...)")
+        # what the batch, the search and the device path get on top of the keyword arguments below
+        self._c2f = dict(coarse_to_fine=True) if self.coarse_to_fine else {}
         self.update_map, self.max_cell_points = bool(update_map), int(max_cell_points)
         online_pyramid = caps is not None
         if self.update_map and cell_capacity is None and not online_pyramid:
             raise ValueError("update_map needs a localiser with an online map: NDTLocaliser(..., cell_capacity=N)")
-        if online_pyramid and (update_map or carve_map) and (hypotheses is not None or search is not None):
+        if online_pyramid and (update_map or carve_map) and (hypotheses is not None or search is not None) \
+                and not self.coarse_to_fine:
             raise ValueError("an online pyramid is updated and carved by the plain registration only: no hypotheses, no search")
         # the keyword arguments every registration of the loop gets: none unless the map is updated
         self._kw = dict(integrate=True, max_cell_points=self.max_cell_points) if self.update_map else {}
@@ -1171,7 +1242,7 @@ class LocalisationLoop:
                 raise TypeError("estimator must be a PoseEstimator")
             takes_none = (hasattr(filter, "add_pose") or type(filter).__name__ == "LTSFilter"
                           or getattr(filter, "takes_pose", True) is False)
-            possible = (takes_none and hasattr(localiser, "submit_from_device") and resolutions is None
+            possible = (takes_none and hasattr(localiser, "submit_from_device") and (resolutions is None or self.coarse_to_fine)
                         and hypotheses is None and search is None and not cells)
             if device_guess and not possible:
                 raise ValueError("device_guess=True needs a filter that takes no pose from the loop and an NDTLocaliser without "
@@ -1236,14 +1307,14 @@ class LocalisationLoop:
         else:
             self._predict(imu, dt)
             if self.device_guess:                                    # predict -> filter -> submit_from_device(pose_dev) -> correct_from
-                return self._register(scan, None, "submit_from_device", (self.estimator.pose_dev,), {}, self._read_batch)
+                return self._register(scan, None, "submit_from_device", (self.estimator.pose_dev,), self._c2f, self._read_batch)
             self._est_guess = self.estimator.pose_dev.cpu().numpy().astype(np.float64)   # the one more synchronisation
         guess = self.guess()
         if self.search is not None and self._search_next:
-            out = self._register(scan, guess, "relocalise", (self.search_poses(guess),), dict(keep=self.search_keep),
+            out = self._register(scan, guess, "relocalise", (self.search_poses(guess),), dict(self._c2f, keep=self.search_keep),
                                  self._read_search)
         elif self.hypotheses is not None:
-            out = self._register(scan, guess, "submit_batch", (self.start_poses(guess),), {}, self._read_batch)
+            out = self._register(scan, guess, "submit_batch", (self.start_poses(guess),), self._c2f, self._read_batch)
         else:
             out = self._register(scan, guess, "submit", (guess,), {}, self._read_pose)
         self._search_next = out.flagged

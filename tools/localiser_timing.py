@@ -49,6 +49,12 @@ without an estimator, with one on the device path and with one on the host path,
 per frame the hipEvent time around submit(), the iterations, the scan's valid source cells and the error against the true
 pose, beside the point path on the same frames, the two alternating frame by frame in one run; then the loop with each.
 
+``--localiser ndt --resolutions R0,R1,... --coarse-to-fine`` times the batched coarse-to-fine registration,
+hipEvents around each call and the calls of one table alternating frame by frame: submit_from_device(coarse_to_fine=True)
+against submit on the pyramid (K = 1); submit_batch(coarse_to_fine=True) against the single-map submit_batch for K = 8 and
+64 at the budgets 30 (caps 10 each) and 90 (caps 30 each); then LocalisationLoop per frame (host wall clock) with the UKF
+on the pyramid, device path against host path, and the same loop on an online pyramid with update and carve.
+
 ``--one-frame`` runs a warm-up and ONE localiser frame: the target of a ``rocprofv3 --kernel-trace --stats`` run.
 """
 import argparse
@@ -144,6 +150,8 @@ def main():
                     "pyramid beside the single-map localiser, in the same session")
     ap.add_argument("--iterations", type=int, default=30, help="with --resolutions: the pyramid's budget of slots")
     ap.add_argument("--level-iterations", type=str, default=None, help="with --resolutions: N0,N1,... the cap of every level")
+    ap.add_argument("--coarse-to-fine", dest="c2f", action="store_true", help="with --resolutions: time the batched "
+                    "coarse-to-fine registration against the calls it extends")
     ap.add_argument("--estimator", action="store_true", help="with --localiser ndt: time the UKF pose estimator's calls and the "
                     "loop with it, on the device path and the host path")
     ap.add_argument("--source", choices=("points", "cells"), default="points", help="with --localiser ndt: cells times "
@@ -158,6 +166,8 @@ def main():
         ap.error("--source-resolution and --source-min-points need --source cells")
     if a.estimator and (a.localiser != "ndt" or a.hypotheses or a.search or a.update_map or a.carve or a.resolutions):
         ap.error("--estimator needs --localiser ndt and none of the other modes")
+    if a.c2f and (not a.resolutions or a.update_map or a.carve or a.estimator or a.one_frame):
+        ap.error("--coarse-to-fine needs --resolutions and none of --update-map, --carve, --estimator, --one-frame")
     if a.resolutions and (a.localiser != "ndt" or a.hypotheses or a.search):
         ap.error("--resolutions needs --localiser ndt and none of --hypotheses, --search")
     if a.carve and (a.localiser != "ndt" or a.hypotheses or a.search or (a.update_map and not a.resolutions)):
@@ -177,6 +187,8 @@ def main():
     T_init = LR.perturbation(0.15, 0.12, 0.05, 1.0)
     if a.estimator:
         return ndt_estimator_main(a, scans, dscans, mp, T_init)
+    if a.c2f:
+        return ndt_c2f_main(a, scans, dscans, mp, T_init)
     if a.localiser == "ndt" and a.resolutions and (a.update_map or a.carve):
         return ndt_online_pyramid_main(a, dscans, mp, T_init)
     if a.localiser == "ndt" and a.update_map:
@@ -856,6 +868,87 @@ def ndt_estimator_main(a, scans, dscans, mp, T_init):
         out[f"loop_{m}_flagged"] = int(flagged[m])
         print(f"LocalisationLoop(sps_cvm, ndt), estimator {m:6s} median {out[f'loop_{m}_ms']['median']:.3f} ms per frame "
               f"(min {min(t_loop[m]):.3f} max {max(t_loop[m]):.3f}; {flagged[m]} flagged)", flush=True)
+    print(json.dumps(out))
+
+
+def ndt_c2f_main(a, scans, dscans, mp, T_init):
+    """--coarse-to-fine: see the module docstring.  The sensor stands still at I, so the estimator runs with zero velocity
+    and a 0.1 s scan period, as in --estimator."""
+    from sps_amd.pose_estimator import PoseEstimator
+    res = tuple(float(v) for v in a.resolutions.split(","))
+    L = len(res)
+    map64 = mp[:, :3].astype(np.float64)
+    st = torch.cuda.current_stream()
+    I4 = np.eye(4)
+
+    def stats(v):
+        return {"median": round(float(np.median(v)), 4), "min": round(min(v), 4), "max": round(max(v), 4)}
+
+    def alternate(calls):
+        """hipEvent time around every call of ``calls`` (name -> function of the frame's scan that returns a pending object),
+        alternating frame by frame -> name -> (ms per frame, the last result)"""
+        t, last = {n: [] for n in calls}, {}
+        for k in range(a.warmup + a.frames):
+            s = dscans[k % len(dscans)]
+            for n, call in calls.items():
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record(st)
+                pend = call(s)
+                e1.record(st)
+                last[n] = pend.result()
+                e1.synchronize()
+                if k >= a.warmup:
+                    t[n].append(e0.elapsed_time(e1))
+        return t, last
+
+    out = {"frames": a.frames, "warmup": a.warmup, "n_map": len(mp), "resolutions": res}
+    for budget, cap in ((30, 10), (90, 30)):
+        pyr = NDTLocaliser(map64, resolutions=res, iterations=budget, level_iterations=(cap,) * L)
+        T_dev = torch.from_numpy(np.ascontiguousarray(T_init)).cuda()
+        t, last = alternate({"submit": lambda s: pyr.submit(s, len(s), T_init),
+                             "from_device": lambda s: pyr.submit_from_device(s, len(s), T_dev, coarse_to_fine=True)})
+        assert last["submit"].pose.tobytes() == last["from_device"].results[0].pose.tobytes()
+        out[f"k1_budget{budget}"] = {n: stats(v) for n, v in t.items()}
+        print(f"budget {budget} K = 1: submit on the pyramid median {np.median(t['submit']):.3f} ms, submit_from_device("
+              f"coarse_to_fine) {np.median(t['from_device']):.3f} ms ({last['submit'].iterations} slots)", flush=True)
+        for K in (8, 64):
+            starts = hypothesis_starts(T_init, K)
+            t, last = alternate({"single_map": lambda s: pyr.submit_batch(s, len(s), starts, iterations=30),
+                                 "coarse_to_fine": lambda s: pyr.submit_batch(s, len(s), starts, coarse_to_fine=True)})
+            rows = {n: dict(stats(v), best=r.best, slots_max=max(p.iterations for p in r.results),
+                            error_m=round(LR.pose_difference(r.pose, I4)[0], 5)) for (n, v), r in zip(t.items(), last.values())}
+            out[f"k{K}_budget{budget}"] = rows
+            print(f"budget {budget} K = {K}: single-map batch (30 iterations) median {rows['single_map']['median']:.3f} ms, error "
+                  f"{rows['single_map']['error_m']:.4f} m; coarse to fine median {rows['coarse_to_fine']['median']:.3f} ms, longest "
+                  f"hypothesis {rows['coarse_to_fine']['slots_max']} slots, error {rows['coarse_to_fine']['error_m']:.4f} m", flush=True)
+    # the loop per frame, host wall clock: the UKF on the pyramid on the device path and on the host path; then all queued on
+    # an online pyramid with update and carve
+    net = net_from_params(O.random_params(seed=0)).cuda().eval().freeze()
+    mpt = torch.from_numpy(mp)
+    pyr = NDTLocaliser(map64, resolutions=res, iterations=30, level_iterations=(10,) * L)
+    caps = tuple(max(2 * len(np.unique(np.floor(map64 / r).astype(np.int64), axis=0)), 4096) for r in res)
+    online = NDTLocaliser(map64, resolutions=res, iterations=30, level_iterations=(10,) * L, level_capacities=caps,
+                          capacity=1 << 16)
+
+    def make_loop(loc, device_guess, **kw):
+        return LocalisationLoop(SPSCVMFilter(net, mpt, voxel_size=VS, epsilon=EPS), loc, I4, estimator=PoseEstimator(I4, "cuda"),
+                                device_guess=device_guess, coarse_to_fine=True, **kw)
+    loops = {"pyramid_device": make_loop(pyr, True), "pyramid_host": make_loop(pyr, False),
+             "online_device": make_loop(online, True, update_map=True, carve_map=True),
+             "online_host": make_loop(online, False, update_map=True, carve_map=True)}
+    t_loop, flagged = {m: [] for m in loops}, {m: 0 for m in loops}
+    for k in range(a.warmup + a.frames):
+        for m, loop in loops.items():                                # alternating: all see the same machine state
+            t0 = time.perf_counter()
+            step = loop.step(scans[k % len(scans)], dt=0.1)
+            if k >= a.warmup:
+                t_loop[m].append((time.perf_counter() - t0) * 1e3)
+                flagged[m] += step.flagged
+    for m in loops:
+        out[f"loop_{m}_ms"] = stats(t_loop[m])
+        out[f"loop_{m}_flagged"] = int(flagged[m])
+        print(f"LocalisationLoop(sps_cvm, pyramid, ukf, coarse_to_fine) {m:15s} median {out[f'loop_{m}_ms']['median']:.3f} ms per "
+              f"frame (min {min(t_loop[m]):.3f} max {max(t_loop[m]):.3f}; {flagged[m]} flagged)", flush=True)
     print(json.dumps(out))
 
 
