@@ -1,5 +1,6 @@
 // aux_kernels.inc.h -- part of the single translation unit sps_hip.hip (included inside its anonymous namespace).
-// slice/metrics, variant-A / variant-B submaps, small utility kernels.
+// slice/metrics, variant-A / variant-B submaps, the ordered compaction (compact_count / compact_base / compact_rank) that
+// every count / write kernel pair of the library stands on, small utility kernels.
 
 // ------------------------------------------------------------------------------------------
 // metrics (models.py:84-105, util.py:285-299): per batch index accumulators over scan rows
@@ -225,13 +226,49 @@ __global__ void k_submap_filter(int *__restrict__ pslot, const int *first, const
   if ((threadIdx.x & 63) == 0 && bal) atomicAdd(n_scan_vox, __popcll(bal));
 }
 
+// ------------------------------------------------------------------------------------------
+// ordered compaction: rows kept "in input order, no atomics", a count launch and a write launch of SCAN_BLOCK threads,
+// one row per thread.  The one definition under k_keep_*, k_stable_*, k_crop_*, k_label_*, k_filter_write and
+// k_loc_ds_*; a kernel keeps its predicate, its row emitter and its count words.  The caller owns lds[SCAN_BLOCK / 64]
+// and wave_off[SCAN_BLOCK / 64], as for block_reduce_sum.
+// ------------------------------------------------------------------------------------------
+// count launch: block_sums[blockIdx.x] = rows this workgroup keeps
+__device__ inline void compact_count(int flag, int *lds, int *__restrict__ block_sums) {
+  const int tot = block_reduce_sum(flag, lds);
+  if (threadIdx.x == 0) block_sums[blockIdx.x] = tot;
+}
+
+// write launch, first call (before the flag's operands are loaded): rows kept by the workgroups before this one
+__device__ inline int compact_base(const int *__restrict__ block_sums, int *lds) {
+  int part = 0;
+  for (int i = threadIdx.x; i < (int)blockIdx.x; i += SCAN_BLOCK) part += block_sums[i];
+  return block_reduce_sum(part, lds);
+}
+
+// write launch, second call: the rank of this thread's row among all kept rows of the grid (meaningful where flag is
+// set); upto = rows kept up to and including this workgroup, so the last workgroup holds the grid's count
+__device__ inline int compact_rank(int base, int flag, int *wave_off, int &upto) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const unsigned long long bal = __ballot(flag);
+  const int in_wave = __popcll(bal & ((1ull << lane) - 1ull));
+  if (lane == 0) wave_off[wave] = __popcll(bal);
+  __syncthreads();
+  int off = 0, tot = 0;
+  for (int i = 0; i < SCAN_BLOCK / 64; ++i) {
+    const int c = wave_off[i];
+    if (i < wave) off += c;
+    tot += c;
+  }
+  upto = base + tot;
+  return base + off + in_wave;
+}
+__device__ inline bool compact_last_thread() { return blockIdx.x == gridDim.x - 1 && threadIdx.x == 0; }
+
 __global__ __launch_bounds__(SCAN_BLOCK) void k_keep_count(const int *__restrict__ keep, int n,
                                                             int *__restrict__ block_sums) {
   __shared__ int lds[SCAN_BLOCK / 64];
   const int p = blockIdx.x * SCAN_BLOCK + threadIdx.x;
-  const int flag = p < n ? keep[p] : 0;
-  const int tot = block_reduce_sum(flag, lds);
-  if (threadIdx.x == 0) block_sums[blockIdx.x] = tot;
+  compact_count(p < n ? keep[p] : 0, lds, block_sums);
 }
 
 // ROWS5 = false: out rows are [x, y, z] with stride ldo (util.prune's return value).
@@ -245,26 +282,15 @@ __global__ __launch_bounds__(SCAN_BLOCK) void k_keep_write(const int *__restrict
                                                             int *__restrict__ count_out) {
   __shared__ int lds[SCAN_BLOCK / 64];
   __shared__ int wave_off[SCAN_BLOCK / 64];
-  int part = 0;
-  for (int i = threadIdx.x; i < (int)blockIdx.x; i += SCAN_BLOCK) part += block_sums[i];
-  const int base = block_reduce_sum(part, lds);
+  const int base = compact_base(block_sums, lds);
   const int p = blockIdx.x * SCAN_BLOCK + threadIdx.x;
   const int flag = p < n ? keep[p] : 0;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const unsigned long long bal = __ballot(flag);
-  const int in_wave = __popcll(bal & ((1ull << lane) - 1ull));
-  if (lane == 0) wave_off[wave] = __popcll(bal);
-  __syncthreads();
-  int off = 0, tot = 0;
-  for (int i = 0; i < SCAN_BLOCK / 64; ++i) {
-    const int c = wave_off[i];
-    if (i < wave) off += c;
-    tot += c;
-  }
+  int kept;
+  const int k = compact_rank(base, flag, wave_off, kept);
   if (flag) {
     int b, x, y, z, t;
     key_unpack(srckey[p], b, x, y, z, t);
-    float *o = out_xyz + (size_t)(base + off + in_wave) * ldo;
+    float *o = out_xyz + (size_t)k * ldo;
     if (ROWS5) {
       o[0] = 0.f;  // batch index (util.py:170)
       o[4] = 0.f;  // MAP_TIMESTAMP (util.py:21)
@@ -275,9 +301,9 @@ __global__ __launch_bounds__(SCAN_BLOCK) void k_keep_write(const int *__restrict
     o[1] = (float)y * ds;
     o[2] = (float)z * ds;
   }
-  if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) {
-    count_out[0] = base + tot;
-    if (ROWS5) count_out[2] = n + base + tot;
+  if (compact_last_thread()) {
+    count_out[0] = kept;
+    if (ROWS5) count_out[2] = n + kept;
   }
 }
 
@@ -331,15 +357,12 @@ __global__ void k_transform_points(const TIN *__restrict__ in, int64_t ld, int n
 }
 
 // epsilon filter (sps_node.py:147-148: `scan[scores <= eps]`): order-preserving compaction of the rows whose
-// score is <= eps (NaN scores -- unrepresentable coordinates -- are dropped).  Two passes over SCAN_BLOCK-row chunks:
-// count, then ballot / prefix-sum placement; no atomics, so the output order is the input order.
+// score is <= eps (NaN scores -- unrepresentable coordinates -- are dropped), by the ordered compaction above.
 __global__ __launch_bounds__(SCAN_BLOCK) void k_stable_count(const float *__restrict__ scores, int n, float eps,
                                                               int *__restrict__ block_sums) {
   __shared__ int lds[SCAN_BLOCK / 64];
   const int p = blockIdx.x * SCAN_BLOCK + threadIdx.x;
-  const int flag = p < n && scores[p] <= eps;
-  const int tot = block_reduce_sum(flag, lds);
-  if (threadIdx.x == 0) block_sums[blockIdx.x] = tot;
+  compact_count(p < n && scores[p] <= eps, lds, block_sums);
 }
 
 __global__ __launch_bounds__(SCAN_BLOCK) void k_stable_write(const float *__restrict__ scores, int n, float eps,
@@ -348,28 +371,17 @@ __global__ __launch_bounds__(SCAN_BLOCK) void k_stable_write(const float *__rest
                                                               float *__restrict__ out, int *__restrict__ count_out) {
   __shared__ int lds[SCAN_BLOCK / 64];
   __shared__ int wave_off[SCAN_BLOCK / 64];
-  int part = 0;
-  for (int i = threadIdx.x; i < (int)blockIdx.x; i += SCAN_BLOCK) part += block_sums[i];
-  const int base = block_reduce_sum(part, lds);
+  const int base = compact_base(block_sums, lds);
   const int p = blockIdx.x * SCAN_BLOCK + threadIdx.x;
   const int flag = p < n && scores[p] <= eps;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const unsigned long long bal = __ballot(flag);
-  const int in_wave = __popcll(bal & ((1ull << lane) - 1ull));
-  if (lane == 0) wave_off[wave] = __popcll(bal);
-  __syncthreads();
-  int off = 0, tot = 0;
-  for (int i = 0; i < SCAN_BLOCK / 64; ++i) {
-    const int c = wave_off[i];
-    if (i < wave) off += c;
-    tot += c;
-  }
+  int kept;
+  const int k = compact_rank(base, flag, wave_off, kept);
   if (flag) {
     const float *r = rows + (size_t)p * ld;
-    float *o = out + (size_t)(base + off + in_wave) * cols;
+    float *o = out + (size_t)k * cols;
     for (int j = 0; j < cols; ++j) o[j] = r[j];
   }
-  if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) *count_out = base + tot;
+  if (compact_last_thread()) *count_out = kept;
 }
 
 // ------------------------------------------------------------------------------------------

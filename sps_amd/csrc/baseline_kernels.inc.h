@@ -6,8 +6,8 @@
 //   k_crop_count / k_crop_write   mapmos_node.py:63-68, 79-80  select_points_within_radius (np.where order)
 //   k_label_count / k_label_write mos4d_node.py:121-127, mapmos_node.py:98-103  logits > 0, filter label 0, confusion counts
 //
-// Both are two passes over SCAN_BLOCK-row chunks (count, then ballot / prefix placement, as k_stable_count /
-// k_stable_write): no atomics decide an output position, so the outputs keep the input order.
+// Both are pairs of the ordered compaction (compact_count / compact_base / compact_rank, aux_kernels.inc.h): no atomics
+// decide an output position, so the outputs keep the input order.
 
 // mapmos_node.py:63-68: sqrt(sum((p - c) ** 2, axis=1)) <= r in float64.  numpy adds the three squares left to right;
 // every operation is rounded on its own (no contraction into FMA), so the kept set is the reference's bit for bit,
@@ -25,9 +25,7 @@ __global__ __launch_bounds__(SCAN_BLOCK) void k_crop_count(const TIN *__restrict
                                                             double cz, double r, int *__restrict__ block_sums) {
   __shared__ int lds[SCAN_BLOCK / 64];
   const int p = blockIdx.x * SCAN_BLOCK + threadIdx.x;
-  const int flag = p < m && crop_keep(map, ld, p, cx, cy, cz, r);
-  const int tot = block_reduce_sum(flag, lds);
-  if (threadIdx.x == 0) block_sums[blockIdx.x] = tot;
+  compact_count(p < m && crop_keep(map, ld, p, cx, cy, cz, r), lds, block_sums);
 }
 
 // The kept map point of rank k (ascending map index) becomes row n_scan + k of the batch: (0, x, y, z, -1) as float32
@@ -41,23 +39,11 @@ __global__ __launch_bounds__(SCAN_BLOCK) void k_crop_write(const TIN *__restrict
                                                             int *__restrict__ counts, int *__restrict__ err) {
   __shared__ int lds[SCAN_BLOCK / 64];
   __shared__ int wave_off[SCAN_BLOCK / 64];
-  int part = 0;
-  for (int i = threadIdx.x; i < (int)blockIdx.x; i += SCAN_BLOCK) part += block_sums[i];
-  const int base = block_reduce_sum(part, lds);
+  const int base = compact_base(block_sums, lds);
   const int p = blockIdx.x * SCAN_BLOCK + threadIdx.x;
   const int flag = p < m && crop_keep(map, ld, p, cx, cy, cz, r);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const unsigned long long bal = __ballot(flag);
-  const int in_wave = __popcll(bal & ((1ull << lane) - 1ull));
-  if (lane == 0) wave_off[wave] = __popcll(bal);
-  __syncthreads();
-  int off = 0, tot = 0;
-  for (int i = 0; i < SCAN_BLOCK / 64; ++i) {
-    const int c = wave_off[i];
-    if (i < wave) off += c;
-    tot += c;
-  }
-  const int k = base + off + in_wave;
+  int kept;
+  const int k = compact_rank(base, flag, wave_off, kept);
   if (flag && k < cap) {
     const TIN *s = map + (size_t)p * ld;
     float *o = rows + (size_t)(n_scan + k) * ldo;
@@ -68,8 +54,7 @@ __global__ __launch_bounds__(SCAN_BLOCK) void k_crop_write(const TIN *__restrict
     o[4] = -1.f;
     if (feat_out) feat_out[n_scan + k] = feat_value;
   }
-  if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) {
-    const int kept = base + tot;
+  if (compact_last_thread()) {
     counts[0] = min(kept, cap);
     counts[1] = n_scan + min(kept, cap);
     if (kept > cap) atomicOr(err, 32);
@@ -91,8 +76,7 @@ __global__ __launch_bounds__(SCAN_BLOCK) void k_label_count(const float *__restr
     pred = logits[(size_t)p * ldl] > 0.f ? 1 : 0;
     labels[p] = pred ? 1.f : 0.f;
   }
-  const int tot = block_reduce_sum(p < n && !pred, lds);
-  if (threadIdx.x == 0) block_sums[blockIdx.x] = tot;
+  compact_count(p < n && !pred, lds, block_sums);
   if (gt) {
     const int g = p < n ? (gt[(size_t)p * ldg] < gt_eps ? 0 : 1) : -1;
     const int tp = block_reduce_sum(g == 1 && pred == 1, lds);
@@ -115,29 +99,18 @@ __global__ __launch_bounds__(SCAN_BLOCK) void k_label_write(const float *__restr
                                                              int64_t ld, float *__restrict__ out, int *__restrict__ count_out) {
   __shared__ int lds[SCAN_BLOCK / 64];
   __shared__ int wave_off[SCAN_BLOCK / 64];
-  int part = 0;
-  for (int i = threadIdx.x; i < (int)blockIdx.x; i += SCAN_BLOCK) part += block_sums[i];
-  const int base = block_reduce_sum(part, lds);
+  const int base = compact_base(block_sums, lds);
   const int p = blockIdx.x * SCAN_BLOCK + threadIdx.x;
   const int flag = p < n && !(logits[(size_t)p * ldl] > 0.f);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const unsigned long long bal = __ballot(flag);
-  const int in_wave = __popcll(bal & ((1ull << lane) - 1ull));
-  if (lane == 0) wave_off[wave] = __popcll(bal);
-  __syncthreads();
-  int off = 0, tot = 0;
-  for (int i = 0; i < SCAN_BLOCK / 64; ++i) {
-    const int c = wave_off[i];
-    if (i < wave) off += c;
-    tot += c;
-  }
+  int kept;
+  const int k = compact_rank(base, flag, wave_off, kept);
   if (flag) {
     const float *r = rows + (size_t)p * ld;
-    float *o = out + (size_t)(base + off + in_wave) * 4;
+    float *o = out + (size_t)k * 4;
     o[0] = r[0];
     o[1] = r[1];
     o[2] = r[2];
     o[3] = 0.f;
   }
-  if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) *count_out = base + tot;
+  if (compact_last_thread()) *count_out = kept;
 }

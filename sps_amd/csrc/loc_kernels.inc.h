@@ -65,12 +65,10 @@ __global__ __launch_bounds__(SCAN_BLOCK) void k_loc_ds_count(const float *__rest
   __shared__ int lds[SCAN_BLOCK / 64];
   const int n = min(n_max, max(*n_dev, 0));
   const int p = blockIdx.x * SCAN_BLOCK + threadIdx.x;
-  const int flag = loc_ds_survives(rows, ld, p, n, leaf, h);
-  const int tot = block_reduce_sum(flag, lds);
-  if (threadIdx.x == 0) block_sums[blockIdx.x] = tot;
+  compact_count(loc_ds_survives(rows, ld, p, n, leaf, h), lds, block_sums);
 }
 
-// the survivor of rank k (ascending row index) becomes out[k] = (double)(x, y, z); ranks >= cap are dropped and the
+// ordered compaction (aux_kernels.inc.h): the survivor of rank k (ascending row index) becomes out[k] = (double)(x, y, z); ranks >= cap are dropped and the
 // count saturates at cap
 __global__ __launch_bounds__(SCAN_BLOCK) void k_loc_ds_write(const float *__restrict__ rows, int64_t ld, int n_max,
                                                               const int *__restrict__ n_dev, double leaf, HashTable h,
@@ -78,30 +76,18 @@ __global__ __launch_bounds__(SCAN_BLOCK) void k_loc_ds_write(const float *__rest
                                                               int cap, int *__restrict__ count_out) {
   __shared__ int lds[SCAN_BLOCK / 64];
   __shared__ int wave_off[SCAN_BLOCK / 64];
-  int part = 0;
-  for (int i = threadIdx.x; i < (int)blockIdx.x; i += SCAN_BLOCK) part += block_sums[i];
-  const int base = block_reduce_sum(part, lds);
+  const int base = compact_base(block_sums, lds);
   const int n = min(n_max, max(*n_dev, 0));
   const int p = blockIdx.x * SCAN_BLOCK + threadIdx.x;
   const int flag = loc_ds_survives(rows, ld, p, n, leaf, h);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const unsigned long long bal = __ballot(flag);
-  const int in_wave = __popcll(bal & ((1ull << lane) - 1ull));
-  if (lane == 0) wave_off[wave] = __popcll(bal);
-  __syncthreads();
-  int off = 0, tot = 0;
-  for (int i = 0; i < SCAN_BLOCK / 64; ++i) {
-    const int c = wave_off[i];
-    if (i < wave) off += c;
-    tot += c;
-  }
-  const int k = base + off + in_wave;
+  int kept;
+  const int k = compact_rank(base, flag, wave_off, kept);
   if (flag && k < cap) {
     const float *r = rows + (size_t)p * ld;
     double *o = out + (size_t)k * 3;
     o[0] = (double)r[0], o[1] = (double)r[1], o[2] = (double)r[2];
   }
-  if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) *count_out = min(base + tot, cap);
+  if (compact_last_thread()) *count_out = min(kept, cap);
 }
 
 // ---- alignment -------------------------------------------------------------------------------------------------------

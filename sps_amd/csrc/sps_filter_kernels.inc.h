@@ -9,8 +9,9 @@
 //   k_filter_write   order-preserving compaction of the WHOLE received rows that are kept (:148 / cvm :171), the submap
 //                    debug cloud (vx, vy, vz, 1) (:157-161), and the partial rows combined in block order
 //
-// The shape is k_stable_count / k_stable_write (aux_kernels.inc.h).  No atomics anywhere: a position comes from the
-// per-workgroup counts, a sum from the partial rows, both combined in a fixed order -- two runs on the same input give
+// The kept rows go through the ordered compaction of aux_kernels.inc.h (k_filter_count fills block_sums from the ballot
+// it shares with its confusion counters; k_filter_write places with compact_base / compact_rank).  No atomics anywhere:
+// a position comes from the per-workgroup counts, a sum from the partial rows, both combined in a fixed order -- two runs on the same input give
 // the same bits (unlike the f64 atomicAdds of k_metrics).
 
 struct FilterFinishArgs {
@@ -35,11 +36,6 @@ struct FilterFinishArgs {
 };
 
 __device__ inline bool filter_keep(float s, float eps, int strict) { return strict ? s < eps : s <= eps; }  // NaN: dropped
-
-// rank of this lane among the set bits of a wave64 ballot
-__device__ inline int ballot_rank(unsigned long long bal) {
-  return (int)__builtin_amdgcn_mbcnt_hi((unsigned)(bal >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)bal, 0u));
-}
 
 constexpr int FILTER_WAVES = SCAN_BLOCK / 64;
 
@@ -119,28 +115,17 @@ __global__ __launch_bounds__(SCAN_BLOCK) void k_filter_write(const FilterFinishA
   __shared__ int wave_off[FILTER_WAVES];
   __shared__ double sl[FILTER_SLICES][8];
   const int p = blockIdx.x * SCAN_BLOCK + threadIdx.x;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   if (a.filtered) {
-    int part = 0;
-    for (int i = threadIdx.x; i < (int)blockIdx.x; i += SCAN_BLOCK) part += a.block_sums[i];
-    const int base = block_reduce_sum(part, lds);
+    const int base = compact_base(a.block_sums, lds);
     const bool keep = p < a.n && filter_keep(a.scores[p], a.eps, a.strict);
-    const unsigned long long bal = __ballot(keep);
-    const int in_wave = ballot_rank(bal);
-    if (lane == 0) wave_off[wave] = __popcll(bal);
-    __syncthreads();
-    int off = 0, tot = 0;
-    for (int i = 0; i < FILTER_WAVES; ++i) {
-      const int c = wave_off[i];
-      if (i < wave) off += c;
-      tot += c;
-    }
+    int kept;
+    const int k = compact_rank(base, keep, wave_off, kept);
     if (keep) {
       const float *r = a.raw + (size_t)p * a.ld;
-      float *o = a.filtered + (size_t)(base + off + in_wave) * a.cols;
+      float *o = a.filtered + (size_t)k * a.cols;
       for (int j = 0; j < a.cols; ++j) o[j] = r[j];
     }
-    if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) *a.count_out = base + tot;
+    if (compact_last_thread()) *a.count_out = kept;
   }
   if (a.submap) {
     const int n_sub = min(a.n, a.counts[0]);  // (the submap never has more rows than the scan; the clamp bounds the reads)
