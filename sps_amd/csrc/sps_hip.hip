@@ -206,12 +206,6 @@ struct SubmapScratch {  // variant-B submap: voxel-level hash with first-occurre
   int *pslot = nullptr;
 };
 
-struct Feat {
-  const char *name;
-  float *ptr;
-  int ld, cols, level;
-};
-
 }  // namespace
 
 // Device-resident weights of one network: immutable once uploaded, shared by every context of the device that
@@ -294,12 +288,8 @@ struct sps_ctx {
   const float *cur_vfeat = nullptr;  // non-null while a forward with per-point features is being issued
   bool cur_head = false;             // the forward being issued wants block8's output, not the fused `final`
   bool diag_have_state = false;
-  // feature buffers
-  float *cat8 = nullptr, *b8t = nullptr, *b8o = nullptr, *logits = nullptr;
-  float *x1 = nullptr, *b1t = nullptr, *cat7 = nullptr, *b7t = nullptr, *b7o = nullptr;
-  float *x2 = nullptr, *b2t = nullptr, *cat6 = nullptr, *b6t = nullptr, *b6o = nullptr;
-  float *x3 = nullptr, *b3t = nullptr, *cat5 = nullptr, *b5t = nullptr, *b5o = nullptr;
-  float *x4 = nullptr, *b4t = nullptr, *b4o = nullptr;
+  float *feat[N_FEAT] = {};  // feature buffers, by FeatId (shapes: FEAT)
+  float *logits = nullptr;
   // per-stage hipEvent profiling (sps_profile_*): off by default
   bool prof = false;
   std::vector<hipEvent_t> prof_ev;
@@ -492,32 +482,14 @@ int reserve(sps_ctx *c, int64_t n) {
   ALLOC(c->scan_agg, unsigned long long, agg_words);
   HIP_TRY(hipMemset(c->scan_agg, 0, sizeof(unsigned long long) * agg_words));
   ALLOC(c->keep, int, cap);
-  const int64_t *cl = c->capl;
-  ALLOC(c->cat8, float, 16 * cap);
-  ALLOC(c->b8t, float, 8 * cap);
-  ALLOC(c->b8o, float, 8 * cap);
-  ALLOC(c->logits, float, cap);
-  ALLOC(c->vacc, long long, cap);
-  ALLOC(c->vcnt, int, cap);
-  ALLOC(c->vfeat, float, cap);
-  ALLOC(c->x1, float, 8 * cl[1]);
-  ALLOC(c->b1t, float, 8 * cl[1]);
-  ALLOC(c->cat7, float, 24 * cl[1]);
-  ALLOC(c->b7t, float, 16 * cl[1]);
-  ALLOC(c->b7o, float, 16 * cl[1]);
-  ALLOC(c->x2, float, 8 * cl[2]);
-  ALLOC(c->b2t, float, 16 * cl[2]);
-  ALLOC(c->cat6, float, 48 * cl[2]);
-  ALLOC(c->b6t, float, 32 * cl[2]);
-  ALLOC(c->b6o, float, 32 * cl[2]);
-  ALLOC(c->x3, float, 16 * cl[3]);
-  ALLOC(c->b3t, float, 32 * cl[3]);
-  ALLOC(c->cat5, float, 96 * cl[3]);
-  ALLOC(c->b5t, float, 64 * cl[3]);
-  ALLOC(c->b5o, float, 64 * cl[3]);
-  ALLOC(c->x4, float, 32 * cl[4]);
-  ALLOC(c->b4t, float, 64 * cl[4]);
-  ALLOC(c->b4o, float, 64 * cl[4]);
+  for (int f = 0; f < N_FEAT; ++f) {
+    ALLOC(c->feat[f], float, FEAT[f].ld * c->capl[FEAT[f].level]);  // (capl[0] == cap)
+    if (f != F_B8O) continue;
+    ALLOC(c->logits, float, cap);  // the head's buffers keep their place behind the level-0 ones
+    ALLOC(c->vacc, long long, cap);
+    ALLOC(c->vcnt, int, cap);
+    ALLOC(c->vfeat, float, cap);
+  }
   c->cap = cap;
   c->hcap = hcap;
   c->last_n = 0;
@@ -577,24 +549,48 @@ struct Map {
   const uint32_t *tmask;
 };
 
-struct ConvCall {
-  const char *name;
-  const float *in;
-  int ldi;
-  float *out;
-  int ldo;
-  Map map;
-  int level_out;
-  const float *res;
-  int ldr;
-  int relu;
-  const float *in2 = nullptr;  // fused downsample input (block input x)
-  int ldi2 = 0;
-  bool fin = false;            // fuse the `final` 1x1 conv into the epilogue
-  const char *up = nullptr;    // transposed convolution fused into the epilogue (its output: up_out / up_ldo)
-  float *up_out = nullptr;
-  int up_ldo = 0;
+// the kernel map a convolution of `kind` walks at the level whose rows it iterates (T_LIN: identity, no table)
+inline Map level_map(const sps_ctx *c, ConvKind kind, int level_rows) {
+  const Level &L = c->lv[level_rows];
+  if (kind == T_K3) return {L.nbr3, L.tm3};
+  if (kind == T_DOWN || kind == T_UP) return {L.down, L.tmdown};
+  return {nullptr, nullptr};
+}
+
+inline float *feat_ptr(const sps_ctx *c, FeatView v) { return v.buf < 0 ? nullptr : c->feat[v.buf] + v.col0; }
+inline int feat_ld(FeatView v) { return v.buf < 0 ? 0 : FEAT[v.buf].ld; }
+
+// diagnostic hooks of the network's launches, read once (-DSPS_DIAG builds; the product build sees every one unset)
+struct ConvDiag {
+  float grid_scale = 1.f;             // SPS_GRID_SCALE: scales the k_conv row grid
+  int max_wg = 0;                     // SPS_CONV_MAX_WG: caps the workgroups of a k_conv launch
+  const char *trace_layer = nullptr;  // SPS_TRACE_LAYER: the layer -DSPS_WAVE_TRACE builds record
+  int conv0_mode = 0;                 // SPS_DIAG_CONV0 = 1: only the hosted order bodies run, 2: only the convolution
+  int lds_pad = 0;                    // SPS_CONV_LDS_PAD=<bytes>: occupancy cap of the coarse-level k_conv launches (dynamic LDS never touched)
+  int skip = 0;                       // SPS_DIAG_SKIP bit 0 = reuse the coordinate structures of the previous forward (valid for
+                                      // an identical input), bit 1 = skip the convolutions
+  int no_merge = 0;                   // SPS_NO_MERGE bit i launches the parts of merged kernel i separately (0 rows|ancestors,
+                                      // 1 link|adj, 2 nbr3|stride maps, 3 slice|cleanup)
+  int skip_class = 0;                 // SPS_DIAG_SKIP_CLASS bit 0 = skip the 3x3x3x3 layers of levels 2-4, 1 = those of levels 0-1,
+                                      // 2 = the strided convolutions, 3 = the transposed ones, 4 = conv0 -- what a kernel class
+                                      // costs the PIPELINED rate
 };
+const ConvDiag &conv_diag() {
+  static const ConvDiag d = [] {
+    ConvDiag v;
+    auto num = [](const char *name) { const char *e = diag_env(name); return e ? atoi(e) : 0; };
+    if (const char *e = diag_env("SPS_GRID_SCALE")) v.grid_scale = (float)atof(e);
+    v.max_wg = num("SPS_CONV_MAX_WG");
+    v.trace_layer = diag_env("SPS_TRACE_LAYER");
+    v.conv0_mode = num("SPS_DIAG_CONV0");
+    v.lds_pad = num("SPS_CONV_LDS_PAD");
+    v.skip = num("SPS_DIAG_SKIP");
+    v.no_merge = num("SPS_NO_MERGE");
+    v.skip_class = num("SPS_DIAG_SKIP_CLASS");
+    return v;
+  }();
+  return d;
+}
 
 // Transposed convolutions run in the epilogue of the layer that produces their input (minkunet.py:107-146: convtrXpYs2
 // follows blockX.conv2).  SPS_FUSE_UP: bit 0 = convtr4 into block4.conv2, 1 = convtr5 into block5.conv2, 2 = convtr6 into
@@ -723,215 +719,235 @@ int launch_k_conv(const ConvArgs &a, Geometry g, bool ds, dim3 grid, hipStream_t
   return SPS_OK;
 }
 
-int run_conv(sps_ctx *c, const ConvCall &cc, hipStream_t st) {
-  const NetSpec &s = *c->net;
-  const int ci = s.find_conv(cc.name);
-  if (ci < 0) return fail(SPS_ERR_INVALID, "unknown conv %s", cc.name);
-  const ConvSpec &cs = s.convs[ci];
+// launch grids from the arena capacity: the rows a level is expected to hold shrink ~2.5x per level; the floor keeps small
+// clouds parallel (the kernels grid-stride over the real, device-side row count)
+inline int64_t row_grid(int64_t cap, int level) { return std::min<int64_t>(std::max<int64_t>((cap / 64) >> level, 64), 4096); }
+// k_upconv: one workgroup per 16 parent rows of the coarse level
+inline int64_t upconv_grid(int64_t cap, int coarse) { return std::min<int64_t>(std::max<int64_t>((cap / 16) >> coarse, 64), 8192); }
+
+// the rows a launch walks: table stride, device row count and tile-mask capacity of `level_rows`
+inline void conv_rows(ConvArgs &a, const sps_ctx *c, int level_rows) {
+  a.ldn = c->capl[level_rows];
+  a.n_out = c->counts + level_rows;
+  a.tile_cap = (int)(c->capl[level_rows] / 16);
+}
+
+// What every kernel family reads, for inference (run_conv) and training (conv_plain): operands, shape, the rows walked.
+// The caller adds what differs between the two: abort_flag, in_bytes / wu_bytes, relu, S and the kernel map.
+ConvArgs conv_args(const sps_ctx *c, int level_rows, int K, int cin, int cout, const float *Wu, const float *scale,
+                   const float *shift, const float *in, int ldi, float *out, int ldo, const float *res, int ldr) {
   ConvArgs a{};
-  a.in = cc.in;
-  a.ldi = cc.ldi;
-  a.out = cc.out;
-  a.ldo = cc.ldo;
-  a.Wu = c->wu + cs.wu_off;
-  a.scale = c->ss + cs.ss_off;
-  a.shift = c->ss + cs.ss_off + cs.cout;
-  a.res = cc.res;
-  a.ldr = cc.ldr;
-  a.nbr = cc.map.nbr;
-  a.tmask = cc.map.tmask;
-  a.ldn = c->capl[cc.level_out];
-  a.n_out = c->counts + cc.level_out;
-  a.abort_flag = c->counts + 15;
-  a.K = cs.K;
-  a.cin = cs.cin;
-  a.cout = cs.cout;
-  a.NT = cs.nt();
-  a.upk = cs.upk();
-  a.inv_upk = cs.cin >= 4 ? 1.0f / (float)cs.upk() : 1.f;
-  a.relu = cc.relu;
+  a.in = in;
+  a.ldi = ldi;
+  a.out = out;
+  a.ldo = ldo;
+  a.Wu = Wu;
+  a.scale = scale;
+  a.shift = shift;
+  a.res = res;
+  a.ldr = ldr;
+  a.K = K;
+  a.cin = cin;
+  a.cout = cout;
+  a.NT = (cout + 15) / 16;
+  a.upk = cin / 4;
+  a.inv_upk = cin >= 4 ? 1.0f / (float)a.upk : 1.f;
   a.in_const = 0.5f;  // models.py:22
-  const Geometry g = conv_geometry(cc.level_out, cs.K, cs.cin, a.NT, (int64_t)c->cap, !c->pipelined);
-  a.S = g.S;
-  // expected tiles at this level (rows shrink ~2.5x per level); floor keeps small clouds parallel
-  int64_t gx = (c->cap / 64) >> cc.level_out;
-  if (gx < 64) gx = 64;
-  if (gx > 4096) gx = 4096;
-  {
-    static const float gscale = [] { const char *e = diag_env("SPS_GRID_SCALE"); return e ? (float)atof(e) : 1.f; }();  // DIAGNOSTICS
-    if (gscale != 1.f) gx = std::max<int64_t>(16, (int64_t)((float)gx * gscale));
-  }
-  static const int max_wg = [] { const char *e = diag_env("SPS_CONV_MAX_WG"); return e ? atoi(e) : 0; }();
-  if (max_wg > 0 && gx * (a.NT / g.ntw) * g.S > max_wg) gx = std::max<int64_t>(16, max_wg / ((a.NT / g.ntw) * g.S));
-  // a workgroup holds 4 / S tiles x S splits: S times as many workgroups for the same tiles
-  dim3 grid((unsigned)(a.NT / g.ntw), (unsigned)(gx * g.S), 1u);  // x = column group (fastest), y = tile group
-  a.in2 = cc.in2;
-  a.ldi2 = cc.ldi2;
-  a.upk2 = cs.ds_cin / 4;
-  a.in2_bytes = (uint32_t)((size_t)c->capl[cc.level_out] * (size_t)(cc.ldi2 > 0 ? cc.ldi2 : 1) * 4u);
-  if (cs.ds_cin > 0 && !cc.in2) return fail(SPS_ERR_INVALID, "%s needs the block input for its fused downsample", cc.name);
-  if (cc.fin) {
-    const ConvSpec &fs = s.convs[s.find_conv("final")];
-    a.fin_w = c->blob + fs.w_off;
-    a.fin_b = c->final_bias;
-    a.fin_out = c->logits;
-  }
-  // level of the input rows: the level itself (3^4, 1x1), the finer one (stride-2 conv), the coarser one (transposed)
-  const bool is_up = cs.K == 8 && std::strncmp(cc.name, "convtr", 6) == 0;
-  const int level_in = cs.K == 8 ? (is_up ? cc.level_out + 1 : cc.level_out - 1) : cc.level_out;
-  a.in_bytes = (uint32_t)((size_t)c->capl[level_in < 0 ? 0 : level_in] * (size_t)cc.ldi * 4u);
-  a.wu_bytes = (uint32_t)(cs.wu_numel() * 4);
-  a.nbr_bytes = (uint32_t)((size_t)cs.K * (size_t)c->capl[cc.level_out] * 4u);
-  a.tile_cap = (int)(c->capl[cc.level_out] / 16);
-  // 3x3x3x3 layers of the coarse levels: tiles in the level's balanced order
-  a.tile_order = (TILE_ORDER != 0 && cs.K == 81 && cc.level_out >= TILE_ORDER_FIRST_LEVEL) ? c->lv[cc.level_out].tile_order : nullptr;
-  // workgroups are dealt to the CUs in block-index order (column group fastest): positions p and p + 256 / column groups share a CU
-  a.order_ways = TILE_ORDER == 2 ? TILE_ORDER_WAYS / std::max(1, a.NT / g.ntw) : 0;
-  if (cc.up) {
-    // the transposed convolution that consumes this layer's output runs in its epilogue: all column groups of a tile in one
-    // workgroup (complete rows), the stride map's child table of THIS (the coarse) level, the fine level's buffer
-    const ConvSpec &us = s.convs[s.find_conv(cc.up)];
-    if (us.cin != cs.cout || cc.level_out < 1) return fail(SPS_ERR_INVALID, "%s cannot be fused into %s", cc.up, cc.name);
-    a.up_Wu = c->wu + us.wu_off;
-    a.up_scale = c->ss + us.ss_off;
-    a.up_shift = c->ss + us.ss_off + us.cout;
-    a.up_down = c->lv[cc.level_out].down;
-    a.up_tmask = c->lv[cc.level_out].tmdown;
-    a.up_ldn = c->capl[cc.level_out];
-    a.up_out = cc.up_out;
-    a.up_ldo = cc.up_ldo;
-    a.up_cout = us.cout;
-    a.up_rows = (int)c->capl[cc.level_out - 1];
-    a.up_wu_bytes = (uint32_t)(us.wu_numel() * 4);
-    grid.x = 1;
-    a.order_ways = TILE_ORDER == 2 ? TILE_ORDER_WAYS : 0;
-  }
-  {
-    static const char *trace_layer = diag_env("SPS_TRACE_LAYER");  // diagnostic builds (-DSPS_WAVE_TRACE) only
-    a.trace_on = trace_layer && std::strcmp(trace_layer, cc.name) == 0;
-  }
-  if (cs.cin == 1) {  // conv0p1s1: fused with its kernel map, no neighbour table
-    // its launch follows k_maps and precedes every 3x3x3x3 layer of the coarse levels: the last workgroups sort those
-    // levels' tiles by present-offset count (balanced tile order, map_kernels.inc.h) -- no launch of their own
-    TileOrderArgs to{};
-    const int g0 = grid_for(c->cap, 64, 4096);
-    int gto = 0;
-    if (TILE_ORDER != 0) {
-      for (int l = 0; l < NLV; ++l) {
-        const bool px = l < PX_LEVELS && ((px_levels() >> l) & 1) && c->lv[l].px_order;
-        // k_maps writes tile masks where a neighbour table is kept or no rulebook replaces it (`want_tm`, build_nbr3)
-        to.tm3[l] = (c->lv[l].nbr3 || !px) ? c->lv[l].tm3 : nullptr, to.order[l] = c->lv[l].tile_order;
-        to.rb_cnt[l] = px ? c->lv[l].rb_cnt : nullptr, to.px_sorted[l] = c->lv[l].px_sorted, to.px_order[l] = c->lv[l].px_order;
-      }
-      to.counts = c->counts;
-      gto = NLV - TILE_ORDER_FIRST_LEVEL + PX_LEVELS;
+  a.S = 1;
+  conv_rows(a, c, level_rows);
+  a.nbr_bytes = (uint32_t)((size_t)K * (size_t)c->capl[level_rows] * 4u);
+  return a;
+}
+
+// transposed conv: parent-stationary kernel over the COARSE level's rows (`a` already describes that level)
+int launch_upconv(const ConvArgs &a, int64_t cap, int coarse, hipStream_t st) {
+  const dim3 gr((unsigned)upconv_grid(cap, coarse));
+  if (a.NT == 1)
+    hipLaunchKernelGGL((k_upconv<1>), gr, dim3(256), 0, st, a);
+  else if (a.NT == 2)
+    hipLaunchKernelGGL((k_upconv<2>), gr, dim3(256), 0, st, a);
+  else if (a.NT == 4)
+    hipLaunchKernelGGL((k_upconv<4>), gr, dim3(256), 0, st, a);
+  else
+    return fail(SPS_ERR_INVALID, "k_upconv: unsupported column count %d", a.cout);
+  return SPS_OK;
+}
+
+// conv0p1s1: fused with its kernel map, no neighbour table
+int launch_conv0(sps_ctx *c, const ConvSpec &cs, const ConvArgs &a, hipStream_t st) {
+  // its launch follows k_maps and precedes every 3x3x3x3 layer of the coarse levels: the last workgroups sort those
+  // levels' tiles by present-offset count (balanced tile order, map_kernels.inc.h) -- no launch of their own
+  TileOrderArgs to{};
+  const int g0 = grid_for(c->cap, 64, 4096);
+  int gto = 0;
+  if (TILE_ORDER != 0) {
+    for (int l = 0; l < NLV; ++l) {
+      const bool px = l < PX_LEVELS && ((px_levels() >> l) & 1) && c->lv[l].px_order;
+      // k_maps writes tile masks where a neighbour table is kept or no rulebook replaces it (`want_tm`, build_nbr3)
+      to.tm3[l] = (c->lv[l].nbr3 || !px) ? c->lv[l].tm3 : nullptr, to.order[l] = c->lv[l].tile_order;
+      to.rb_cnt[l] = px ? c->lv[l].rb_cnt : nullptr, to.px_sorted[l] = c->lv[l].px_sorted, to.px_order[l] = c->lv[l].px_order;
     }
-    c->last_kernel = c->cur_vfeat ? "k_conv0_feat" : "k_conv0_fused";
-    {  // DIAGNOSTICS (-DSPS_DIAG): SPS_DIAG_CONV0 = 1: only the hosted order bodies run, 2: only the convolution
-      static const int c0mode = [] { const char *e = diag_env("SPS_DIAG_CONV0"); return e ? atoi(e) : 0; }();
-      if (c0mode == 1) {
-        hipLaunchKernelGGL(k_conv0_fused, dim3((unsigned)gto), dim3(256), 0, st, a.n_out, c->lv[0].view(), c->blob + cs.w_off, a.scale,
-                           a.shift, a.in_const, a.out, a.ldo, 1, to, 0);
-        return SPS_OK;
-      }
-      if (c0mode == 2) gto = 0;
-    }
-    if (c->cur_vfeat) {
-      hipLaunchKernelGGL(k_conv0_feat, dim3((unsigned)(g0 + gto)), dim3(256), 0, st, a.n_out,
-                         c->lv[0].view(), c->blob + cs.w_off, a.scale, a.shift, c->cur_vfeat, a.out, a.ldo, to, g0);
-      return SPS_OK;
-    }
-    hipLaunchKernelGGL(k_conv0_fused, dim3((unsigned)(g0 + gto)), dim3(256), 0, st, a.n_out,
-                       c->lv[0].view(), c->blob + cs.w_off, a.scale, a.shift, a.in_const, a.out, a.ldo, 1, to, g0);
+    to.counts = c->counts;
+    gto = NLV - TILE_ORDER_FIRST_LEVEL + PX_LEVELS;
+  }
+  c->last_kernel = c->cur_vfeat ? "k_conv0_feat" : "k_conv0_fused";
+  if (conv_diag().conv0_mode == 1) {
+    hipLaunchKernelGGL(k_conv0_fused, dim3((unsigned)gto), dim3(256), 0, st, a.n_out, c->lv[0].view(), c->blob + cs.w_off, a.scale,
+                       a.shift, a.in_const, a.out, a.ldo, 1, to, 0);
     return SPS_OK;
   }
-  if (cs.K == 8 && std::strncmp(cc.name, "convtr", 6) == 0) {
-    // transposed conv: parent-stationary kernel over the COARSE level's rows (k_upconv)
-    {
-      const int coarse = cc.level_out + 1;
-      a.nbr = c->lv[coarse].down;
-      a.tmask = c->lv[coarse].tmdown;
-      a.n_out = c->counts + coarse;
-      a.ldn = c->capl[coarse];
-      a.tile_cap = (int)(c->capl[coarse] / 16);
-      a.out_rows = (int)c->capl[cc.level_out];
-      int64_t gu = (c->cap / 16) >> coarse;  // one workgroup per 16 parent rows
-      if (gu < 64) gu = 64;
-      if (gu > 8192) gu = 8192;
-      const dim3 gr((unsigned)gu);
-      c->last_kernel = "k_upconv";
-      if (a.NT == 1)
-        hipLaunchKernelGGL((k_upconv<1>), gr, dim3(256), 0, st, a);
-      else if (a.NT == 2)
-        hipLaunchKernelGGL((k_upconv<2>), gr, dim3(256), 0, st, a);
-      else
-        hipLaunchKernelGGL((k_upconv<4>), gr, dim3(256), 0, st, a);
-      return SPS_OK;
-    }
+  if (conv_diag().conv0_mode == 2) gto = 0;
+  if (c->cur_vfeat) {
+    hipLaunchKernelGGL(k_conv0_feat, dim3((unsigned)(g0 + gto)), dim3(256), 0, st, a.n_out,
+                       c->lv[0].view(), c->blob + cs.w_off, a.scale, a.shift, c->cur_vfeat, a.out, a.ldo, to, g0);
+    return SPS_OK;
   }
+  hipLaunchKernelGGL(k_conv0_fused, dim3((unsigned)(g0 + gto)), dim3(256), 0, st, a.n_out,
+                     c->lv[0].view(), c->blob + cs.w_off, a.scale, a.shift, a.in_const, a.out, a.ldo, 1, to, g0);
+  return SPS_OK;
+}
+
+// one-column-tile layers over a 3x3x3x3 map run pair-exact over the level's rulebook (k_conv_px)
+inline bool runs_pair_exact(const sps_ctx *c, const ConvSpec &cs, int level, bool fin) {
+  return level < PX_LEVELS && ((px_levels() >> level) & 1) && c->lv[level].rb_e && cs.K == 81 && cs.nt() == 1 && (cs.cout == 8 || cs.cout == 16) &&
+         (cs.cin == 8 || cs.cin == 16 || cs.cin == 24) && (!fin || cs.cout == 8);
+}
+
+int launch_conv_px(sps_ctx *c, const ConvSpec &cs, ConvArgs &a, int level_out, bool fin, const char *up, hipStream_t st) {
+  const char *name = cs.name.c_str();
   const bool ds = cs.ds_cin > 0;
-  // one-column-tile layers over a 3x3x3x3 map: pair-exact kernel over the level's rulebook (k_conv_px)
-  if (cc.level_out < PX_LEVELS && ((px_levels() >> cc.level_out) & 1) && c->lv[cc.level_out].rb_e && cs.K == 81 && a.NT == 1 && (cs.cout == 8 || cs.cout == 16) &&
-      (cs.cin == 8 || cs.cin == 16 || cs.cin == 24) && (!cc.fin || cs.cout == 8)) {
-    int64_t gs = (c->cap / 64) >> cc.level_out;  // expected supertiles at this level
-    if (gs < 64) gs = 64;
-    if (gs > 4096) gs = 4096;
-    const dim3 gridp((unsigned)gs);
-    a.rb_e = c->lv[cc.level_out].rb_e;
-    a.rb_k = c->lv[cc.level_out].rb_k;
-    a.rb_cnt = c->lv[cc.level_out].rb_cnt;
-    a.px_order = TILE_ORDER != 0 ? c->lv[cc.level_out].px_order : nullptr;
-    a.rb_supertiles = (int)(c->capl[cc.level_out] / 64);
-    const int key = cs.cin * 100 + (cs.cout == 8 ? 10 : 0) + (cc.fin ? 2 : (ds ? 1 : 0));
-    c->last_kernel = "k_conv_px";
-    // the level-0 rulebook is padded per 8 pairs: only the C_out = 8 instantiations (HALF) can read it
-    static_assert(PX_HALF_LEVELS == 1, "SPS_PX_LAUNCH picks the HALF instantiations for level 0 alone");
-    if (px_half_level(cc.level_out) && cs.cout != 8)
-      return fail(SPS_ERR_INVALID, "%s: C_out = %d cannot read the 8-pair rulebook of level %d", cc.name, cs.cout, cc.level_out);
+  const dim3 gridp((unsigned)row_grid(c->cap, level_out));  // expected supertiles at this level
+  a.rb_e = c->lv[level_out].rb_e;
+  a.rb_k = c->lv[level_out].rb_k;
+  a.rb_cnt = c->lv[level_out].rb_cnt;
+  a.px_order = TILE_ORDER != 0 ? c->lv[level_out].px_order : nullptr;
+  a.rb_supertiles = (int)(c->capl[level_out] / 64);
+  const int key = cs.cin * 100 + (cs.cout == 8 ? 10 : 0) + (fin ? 2 : (ds ? 1 : 0));
+  c->last_kernel = "k_conv_px";
+  // the level-0 rulebook is padded per 8 pairs: only the C_out = 8 instantiations (HALF) can read it
+  static_assert(PX_HALF_LEVELS == 1, "SPS_PX_LAUNCH picks the HALF instantiations for level 0 alone");
+  if (px_half_level(level_out) && cs.cout != 8)
+    return fail(SPS_ERR_INVALID, "%s: C_out = %d cannot read the 8-pair rulebook of level %d", name, cs.cout, level_out);
 #define SPS_PX_LAUNCH(CIN_, C8_, DS_, FIN_)                                                                  \
   do {                                                                                                       \
-    if (cc.level_out == 0)                                                                                   \
+    if (level_out == 0)                                                                                      \
       launch_px<SPS_PX0, CIN_, C8_, DS_, FIN_, SPS_PX0_W, false, C8_>(gridp, st, a);                         \
     else                                                                                                     \
       launch_px<SPS_PX1, CIN_, C8_, DS_, FIN_, SPS_PX1_W>(gridp, st, a);                                     \
   } while (0)
-    switch (key) {
-      case 800: SPS_PX_LAUNCH(8, false, false, false); break;   // block2.conv1
-      case 810: SPS_PX_LAUNCH(8, true, false, false); break;    // block1.conv1 / conv2
-      case 811: SPS_PX_LAUNCH(8, true, true, false); break;     // block8.conv2 (heads: `final` not fused)
-      case 812: SPS_PX_LAUNCH(8, true, true, true); break;      // block8.conv2 + `final`
-      case 1601:                                                // block7.conv2 (+ convtr7p2s2 in its epilogue)
-        if (cc.up) {
-          if (cc.level_out != 1 || a.up_cout > 16) return fail(SPS_ERR_INVALID, "%s cannot be fused into %s", cc.up, cc.name);
-          launch_px<SPS_PX1, 16, false, true, false, SPS_PX1_W, true>(gridp, st, a);
-        } else {
-          SPS_PX_LAUNCH(16, false, true, false);
-        }
-        break;
-      case 1610: SPS_PX_LAUNCH(16, true, false, false); break;  // block8.conv1
-      case 2400: SPS_PX_LAUNCH(24, false, false, false); break; // block7.conv1
-      default: return fail(SPS_ERR_INVALID, "no k_conv_px instantiation for %s", cc.name);
-    }
-#undef SPS_PX_LAUNCH
-    return SPS_OK;
+  switch (key) {
+    case 800: SPS_PX_LAUNCH(8, false, false, false); break;   // block2.conv1
+    case 810: SPS_PX_LAUNCH(8, true, false, false); break;    // block1.conv1 / conv2
+    case 811: SPS_PX_LAUNCH(8, true, true, false); break;     // block8.conv2 (heads: `final` not fused)
+    case 812: SPS_PX_LAUNCH(8, true, true, true); break;      // block8.conv2 + `final`
+    case 1601:                                                // block7.conv2 (+ convtr7p2s2 in its epilogue)
+      if (up) {
+        if (level_out != 1 || a.up_cout > 16) return fail(SPS_ERR_INVALID, "%s cannot be fused into %s", up, name);
+        launch_px<SPS_PX1, 16, false, true, false, SPS_PX1_W, true>(gridp, st, a);
+      } else {
+        SPS_PX_LAUNCH(16, false, true, false);
+      }
+      break;
+    case 1610: SPS_PX_LAUNCH(16, true, false, false); break;  // block8.conv1
+    case 2400: SPS_PX_LAUNCH(24, false, false, false); break; // block7.conv1
+    default: return fail(SPS_ERR_INVALID, "no k_conv_px instantiation for %s", name);
   }
+#undef SPS_PX_LAUNCH
+  return SPS_OK;
+}
+
+// k_conv over a gather map (3x3x3x3 tables, `down` tables): the inference launch with its fused epilogues
+int launch_conv_rows(sps_ctx *c, const ConvSpec &cs, const ConvArgs &a, Geometry g, int level_out, bool fin, hipStream_t st) {
+  const bool ds = cs.ds_cin > 0;
+  const int cgs = a.NT / g.ntw;  // column groups of a tile
+  int64_t gx = row_grid(c->cap, level_out);
+  const ConvDiag &dg = conv_diag();
+  if (dg.grid_scale != 1.f) gx = std::max<int64_t>(16, (int64_t)((float)gx * dg.grid_scale));
+  if (dg.max_wg > 0 && gx * cgs * g.S > dg.max_wg) gx = std::max<int64_t>(16, dg.max_wg / (cgs * g.S));
+  // a workgroup holds 4 / S tiles x S splits: S times as many workgroups for the same tiles.  x = column group (fastest; a
+  // fused transposed convolution needs complete rows: all column groups in one workgroup), y = tile group
+  const dim3 grid((unsigned)(a.up_out ? 1 : cgs), (unsigned)(gx * g.S), 1u);
   if (cs.K == 81 && !a.nbr)
     return fail(SPS_ERR_INVALID, "%s has no pair-exact instantiation and the inference-only context keeps no neighbour table at level %d",
-                cc.name, cc.level_out);
-  if (cc.fin && !(g.ntw == 1 && ds && g.S == 1)) return fail(SPS_ERR_INVALID, "final fusion needs NT = 1, S = 1");
-  c->last_kernel = cs.K == 81 ? (cc.level_out >= 2 ? "k_conv<3x3x3x3, levels 2-4>" : "k_conv<3x3x3x3, levels 0-1>") : "k_conv<2x2x2x1 stride 2>";
-  if (cc.fin) {
+                cs.name.c_str(), level_out);
+  if (fin && !(g.ntw == 1 && ds && g.S == 1)) return fail(SPS_ERR_INVALID, "final fusion needs NT = 1, S = 1");
+  c->last_kernel = cs.K == 81 ? (level_out >= 2 ? "k_conv<3x3x3x3, levels 2-4>" : "k_conv<3x3x3x3, levels 0-1>") : "k_conv<2x2x2x1 stride 2>";
+  if (fin) {
     hipLaunchKernelGGL((k_conv<1, SPS_G1DS, SPS_W1, true, true, 1>), grid, dim3(256), 0, st, a);
     return SPS_OK;
   }
-  unsigned lds_pad = 0;
-#if defined(SPS_DIAG)
-  {  // occupancy cap of the coarse-level launches (dynamic LDS that is never touched): SPS_CONV_LDS_PAD=<bytes>
-    static const int pad = [] { const char *e = diag_env("SPS_CONV_LDS_PAD"); return e ? atoi(e) : 0; }();
-    if (cc.level_out >= 2 && cs.K == 81) lds_pad = (unsigned)pad;
-  }
-#endif
+  const unsigned lds_pad = (level_out >= 2 && cs.K == 81) ? (unsigned)dg.lds_pad : 0u;
   return launch_k_conv(a, g, ds, grid, st, lds_pad);
+}
+
+// One layer of the inference forward: row `r` of the wiring table, with `final` fused into its epilogue (fin) and / or the
+// transposed convolution of row `up` (the next one)
+int run_conv(sps_ctx *c, const LayerRow &r, bool fin, const LayerRow *up, hipStream_t st) {
+  const NetSpec &s = *c->net;
+  const ConvSpec &cs = s.convs[r.conv];
+  const int lo = r.level;
+  // the block input: the residual of a block without downsample, else the operand of the fused 1x1 downsample
+  const bool ds = cs.ds_cin > 0;
+  const float *blk = feat_ptr(c, r.blk);
+  const int ldb = feat_ld(r.blk);
+  const int ldi = r.kind == T_CONV0 ? 1 : feat_ld(r.in);
+  ConvArgs a = conv_args(c, lo, cs.K, cs.cin, cs.cout, c->wu + cs.wu_off, c->ss + cs.ss_off, c->ss + cs.ss_off + cs.cout,
+                         feat_ptr(c, r.in), ldi, feat_ptr(c, r.out), feat_ld(r.out), ds ? nullptr : blk, ds ? 0 : ldb);
+  const Map map = level_map(c, r.kind, r.kind == T_UP ? lo + 1 : lo);
+  a.nbr = map.nbr;
+  a.tmask = map.tmask;
+  a.abort_flag = c->counts + 15;
+  a.relu = r.relu;
+  const Geometry g = conv_geometry(lo, cs.K, cs.cin, a.NT, (int64_t)c->cap, !c->pipelined);
+  a.S = g.S;
+  a.in2 = ds ? blk : nullptr;
+  a.ldi2 = ds ? ldb : 0;
+  a.upk2 = cs.ds_cin / 4;
+  a.in2_bytes = (uint32_t)((size_t)c->capl[lo] * (size_t)(a.ldi2 > 0 ? a.ldi2 : 1) * 4u);
+  if (fin) {
+    a.fin_w = c->blob + s.convs[s.final_idx].w_off;
+    a.fin_b = c->final_bias;
+    a.fin_out = c->logits;
+  }
+  // level of the input rows: the level itself (3^4), the finer one (stride-2 conv), the coarser one (transposed)
+  const int level_in = r.kind == T_DOWN ? lo - 1 : r.kind == T_UP ? lo + 1 : lo;
+  a.in_bytes = (uint32_t)((size_t)c->capl[level_in] * (size_t)ldi * 4u);
+  a.wu_bytes = (uint32_t)(cs.wu_numel() * 4);
+  // 3x3x3x3 layers of the coarse levels: tiles in the level's balanced order
+  a.tile_order = (TILE_ORDER != 0 && cs.K == 81 && lo >= TILE_ORDER_FIRST_LEVEL) ? c->lv[lo].tile_order : nullptr;
+  // workgroups are dealt to the CUs in block-index order (column group fastest): positions p and p + 256 / column groups share a CU
+  a.order_ways = TILE_ORDER == 2 ? TILE_ORDER_WAYS / std::max(1, a.NT / g.ntw) : 0;
+  const char *up_name = nullptr;
+  if (up) {
+    // the transposed convolution that consumes this layer's output runs in its epilogue: all column groups of a tile in one
+    // workgroup (complete rows), the stride map's child table of THIS (the coarse) level, the fine level's buffer
+    const ConvSpec &us = s.convs[up->conv];
+    up_name = us.name.c_str();
+    if (us.cin != cs.cout || lo < 1) return fail(SPS_ERR_INVALID, "%s cannot be fused into %s", up_name, cs.name.c_str());
+    a.up_Wu = c->wu + us.wu_off;
+    a.up_scale = c->ss + us.ss_off;
+    a.up_shift = c->ss + us.ss_off + us.cout;
+    a.up_down = c->lv[lo].down;
+    a.up_tmask = c->lv[lo].tmdown;
+    a.up_ldn = c->capl[lo];
+    a.up_out = feat_ptr(c, up->out);
+    a.up_ldo = feat_ld(up->out);
+    a.up_cout = us.cout;
+    a.up_rows = (int)c->capl[lo - 1];
+    a.up_wu_bytes = (uint32_t)(us.wu_numel() * 4);
+    a.order_ways = TILE_ORDER == 2 ? TILE_ORDER_WAYS : 0;
+  }
+  const char *trace_layer = conv_diag().trace_layer;  // diagnostic builds (-DSPS_WAVE_TRACE) only
+  a.trace_on = trace_layer && std::strcmp(trace_layer, cs.name.c_str()) == 0;
+  if (r.kind == T_CONV0) return launch_conv0(c, cs, a, st);
+  if (r.kind == T_UP) {  // k_upconv walks the rows of the coarse level and scatters into this one
+    conv_rows(a, c, lo + 1);
+    a.out_rows = (int)c->capl[lo];
+    c->last_kernel = "k_upconv";
+    return launch_upconv(a, c->cap, lo + 1, st);
+  }
+  if (runs_pair_exact(c, cs, lo, fin)) return launch_conv_px(c, cs, a, lo, fin, up_name, st);
+  return launch_conv_rows(c, cs, a, g, lo, fin, st);
 }
 
 // Host-side permutation of one kernel [K][cin][cout] into the unit-major MFMA B-fragment order
@@ -972,14 +988,6 @@ void prof_mark(sps_ctx *c, const char *name, hipStream_t st) {
   c->last_kernel = "";
   (void)hipEventRecord(c->prof_ev[c->prof_n], st);
   ++c->prof_n;
-}
-
-std::vector<Feat> feature_taps(sps_ctx *c) {
-  return {
-      {"out_p1", c->cat8 + 8, 16, 8, 0},  {"block1", c->cat7 + 16, 24, 8, 1}, {"block2", c->cat6 + 32, 48, 16, 2},
-      {"block3", c->cat5 + 64, 96, 32, 3}, {"block4", c->b4o, 64, 64, 4},      {"block5", c->b5o, 64, 64, 3},
-      {"block6", c->b6o, 32, 32, 2},       {"block7", c->b7o, 16, 16, 1},      {"block8", c->b8o, 8, 8, 0},
-  };
 }
 
 template <typename TIN>
@@ -1038,6 +1046,7 @@ int sps_version(void) { return 202; }
 
 int sps_ctx_create(int device, sps_ctx **out) {
   if (!out) return fail(SPS_ERR_INVALID, "out is null");
+  if (!spec(1).wiring_error.empty()) return fail(SPS_ERR_INVALID, "internal: %s", spec(1).wiring_error.c_str());
   int ndev = 0;
   HIP_TRY(hipGetDeviceCount(&ndev));
   if (device < 0 || device >= ndev) return fail(SPS_ERR_INVALID, "device %d out of range (%d devices)", device, ndev);
@@ -1125,6 +1134,7 @@ int sps_weights_create(int device, const float *blob, int64_t numel, int out_cha
   if (!out) return fail(SPS_ERR_INVALID, "out is null");
   if (out_channels < 1 || out_channels > MAX_HEAD) return fail(SPS_ERR_INVALID, "out_channels must be in [1,%d]", MAX_HEAD);
   const NetSpec &s = spec(out_channels);
+  if (!s.wiring_error.empty()) return fail(SPS_ERR_INVALID, "internal: %s", s.wiring_error.c_str());
   if (!blob) return fail(SPS_ERR_INVALID, "null argument");
   if (numel != s.numel) return fail(SPS_ERR_INVALID, "blob has %lld floats, expected %lld", (long long)numel, (long long)s.numel);
   int ndev = 0;
@@ -1134,14 +1144,14 @@ int sps_weights_create(int device, const float *blob, int64_t numel, int out_cha
   std::vector<float> ss((size_t)s.ss_numel);
   for (const ConvSpec &cs : s.convs) {
     float *sc = ss.data() + cs.ss_off, *sh = sc + cs.cout;
-    if (cs.bn.empty()) {
+    if (cs.bn_idx < 0) {
       for (int j = 0; j < cs.cout; ++j) {
         sc[j] = 1.f;
         sh[j] = blob[s.bias_off + j];
       }
       continue;
     }
-    const BnSpec &b = s.bns[s.find_bn(cs.bn)];
+    const BnSpec &b = s.bns[cs.bn_idx];
     const float *w = blob + b.off, *bi = w + b.c, *mu = bi + b.c, *var = mu + b.c;
     for (int j = 0; j < cs.cout; ++j) {
       // eval BatchNorm1d, eps = 1e-5 (App. A.12): y = (x - mu) / sqrt(var + eps) * w + b
@@ -1160,9 +1170,7 @@ int sps_weights_create(int device, const float *blob, int64_t numel, int out_cha
     // conv2 of a block with a 1x1 downsample branch: out = relu(bn2(conv2(y)) + bn_ds(x @ Wds)).
     // Both BN scales go into the weights (columns of W2 by scale2, of Wds by scale_ds), the extra
     // units follow the K*upk regular ones, and the epilogue becomes acc + (shift2 + shift_ds).
-    std::string dsname = cs.name;
-    dsname.replace(dsname.find(".conv2"), 6, ".downsample.0");
-    const ConvSpec &ds = s.convs[s.find_conv(dsname)];
+    const ConvSpec &ds = s.convs[cs.ds_idx];
     float *sc2 = ss.data() + cs.ss_off, *sh2 = sc2 + cs.cout;
     const float *scd = ss.data() + ds.ss_off, *shd = scd + ds.cout;
     permute_weights(cs, blob + cs.w_off, wu.data() + cs.wu_off, sc2);
@@ -1251,16 +1259,38 @@ struct ForwardOpts {
 static int forward_impl(sps_ctx *c, const float *coords, int64_t ld, int64_t n, float vs, float *scores,
                         const ForwardOpts &fo, void *stream);
 
-int sps_forward(sps_ctx *c, const float *coords, int64_t ld, int64_t n, float vs, float *scores, void *stream) {
+// the SPS entry points want the one-channel network
+static int check_sps_head(const sps_ctx *c) {
   if (c && c->have_weights && c->net->out_channels != 1)
     return fail(SPS_ERR_INVALID, "the loaded weights have a %d-channel head: use sps_forward_head", c->net->out_channels);
+  return SPS_OK;
+}
+
+// argument checks of the two fused-metrics entry points (null_arg: a required pointer is missing); an empty batch has zero sums
+static int metrics_opts(const sps_ctx *c, bool null_arg, int64_t ld, int64_t n, float eps, int n_batches, double *out_dev,
+                        void *stream, ForwardOpts &fo) {
+  if (int rc = check_sps_head(c)) return rc;
+  if (null_arg) return fail(SPS_ERR_INVALID, "null argument");
+  if (n_batches < 1 || n_batches > 31) return fail(SPS_ERR_INVALID, "n_batches must be in [1,31]");
+  if (ld < 6) return fail(SPS_ERR_INVALID, "rows must carry (b,x,y,z,t,label): ld >= 6");
+  if (n == 0) {
+    HIP_TRY(hipSetDevice(c ? c->device : 0));
+    HIP_TRY(hipMemsetAsync(out_dev, 0, (size_t)n_batches * 8 * sizeof(double), (hipStream_t)stream));
+  }
+  fo.metrics_out = out_dev;
+  fo.eps = eps;
+  fo.n_batches = n_batches;
+  return SPS_OK;
+}
+
+int sps_forward(sps_ctx *c, const float *coords, int64_t ld, int64_t n, float vs, float *scores, void *stream) {
+  if (int rc = check_sps_head(c)) return rc;
   return forward_impl(c, coords, ld, n, vs, scores, ForwardOpts{}, stream);
 }
 
 int sps_forward_n(sps_ctx *c, const float *coords, int64_t ld, int64_t n_max, const int32_t *n_dev, float vs, float *scores,
                   void *stream) {
-  if (c && c->have_weights && c->net->out_channels != 1)
-    return fail(SPS_ERR_INVALID, "the loaded weights have a %d-channel head: use sps_forward_head", c->net->out_channels);
+  if (int rc = check_sps_head(c)) return rc;
   if (!n_dev) return fail(SPS_ERR_INVALID, "n_dev is null");
   ForwardOpts fo;
   fo.n_dev = n_dev;
@@ -1283,37 +1313,15 @@ int sps_forward_head(sps_ctx *c, const float *coords, int64_t ld, int64_t n, flo
 
 int sps_forward_metrics(sps_ctx *c, const float *batch, int64_t ld, int64_t n, float vs, float eps, int n_batches,
                         float *scores, double *out_dev, void *stream) {
-  if (c && c->have_weights && c->net->out_channels != 1)
-    return fail(SPS_ERR_INVALID, "the loaded weights have a %d-channel head: use sps_forward_head", c->net->out_channels);
-  if (!out_dev) return fail(SPS_ERR_INVALID, "null argument");
-  if (n_batches < 1 || n_batches > 31) return fail(SPS_ERR_INVALID, "n_batches must be in [1,31]");
-  if (ld < 6) return fail(SPS_ERR_INVALID, "rows must carry (b,x,y,z,t,label): ld >= 6");
-  if (n == 0) {
-    HIP_TRY(hipSetDevice(c ? c->device : 0));
-    HIP_TRY(hipMemsetAsync(out_dev, 0, (size_t)n_batches * 8 * sizeof(double), (hipStream_t)stream));
-  }
   ForwardOpts fo;
-  fo.metrics_out = out_dev;
-  fo.eps = eps;
-  fo.n_batches = n_batches;
+  if (int rc = metrics_opts(c, !out_dev, ld, n, eps, n_batches, out_dev, stream, fo)) return rc;
   return forward_impl(c, batch, ld, n, vs, scores, fo, stream);
 }
 
 int sps_forward_metrics_n(sps_ctx *c, const float *batch, int64_t ld, int64_t n_max, const int32_t *n_dev, float vs, float eps,
                           int n_batches, float *scores, double *out_dev, void *stream) {
-  if (c && c->have_weights && c->net->out_channels != 1)
-    return fail(SPS_ERR_INVALID, "the loaded weights have a %d-channel head: use sps_forward_head", c->net->out_channels);
-  if (!out_dev || !n_dev) return fail(SPS_ERR_INVALID, "null argument");
-  if (n_batches < 1 || n_batches > 31) return fail(SPS_ERR_INVALID, "n_batches must be in [1,31]");
-  if (ld < 6) return fail(SPS_ERR_INVALID, "rows must carry (b,x,y,z,t,label): ld >= 6");
-  if (n_max == 0) {
-    HIP_TRY(hipSetDevice(c ? c->device : 0));
-    HIP_TRY(hipMemsetAsync(out_dev, 0, (size_t)n_batches * 8 * sizeof(double), (hipStream_t)stream));
-  }
   ForwardOpts fo;
-  fo.metrics_out = out_dev;
-  fo.eps = eps;
-  fo.n_batches = n_batches;
+  if (int rc = metrics_opts(c, !out_dev || !n_dev, ld, n_max, eps, n_batches, out_dev, stream, fo)) return rc;
   fo.n_dev = n_dev;
   return forward_impl(c, batch, ld, n_max, vs, scores, fo, stream);
 }
@@ -1334,12 +1342,8 @@ static int forward_impl(sps_ctx *c, const float *coords, int64_t ld, int64_t n, 
     int rc = reserve(c, n);
     if (rc != SPS_OK) return rc;
   }
-  // DIAGNOSTICS ONLY: SPS_DIAG_SKIP bit 0 = reuse the coordinate structures of the
-  // previous forward (valid for an identical input), bit 1 = skip the convolutions.  Never set in product use.
-  static const int diag_skip = [] { const char *e = diag_env("SPS_DIAG_SKIP"); return e ? atoi(e) : 0; }();
-  // DIAGNOSTICS: SPS_NO_MERGE bit i launches the parts of merged kernel i separately (0 rows|ancestors,
-  // 1 link|adj, 2 nbr3|stride maps, 3 slice|cleanup)
-  static const int no_merge = [] { const char *e = diag_env("SPS_NO_MERGE"); return e ? atoi(e) : 0; }();
+  // DIAGNOSTICS ONLY (ConvDiag): never set in product use
+  const int diag_skip = conv_diag().skip, no_merge = conv_diag().no_merge, skip_class = conv_diag().skip_class;
   const bool skip_front = (diag_skip & 1) && c->last_n == n && c->diag_have_state;
   const bool skip_convs = (diag_skip & 2) != 0;
   c->last_n = n;
@@ -1448,76 +1452,34 @@ static int forward_impl(sps_ctx *c, const float *coords, int64_t ld, int64_t n, 
     return SPS_OK;  // the caller runs its own network and the hash clean-up
   }
   // ---- network (minkunet.py:161-219)
-  Level *lv = c->lv;
   c->cur_vfeat = fo.feats ? c->vfeat : nullptr;
-  const bool fuse_final = !fo.head;
-  const ConvCall calls[] = {
-      {"conv0p1s1", nullptr, 1, c->cat8 + 8, 16, Map{c->nbr5, c->tm5}, 0, nullptr, 0, 1},
-      {"conv1p1s2", c->cat8 + 8, 16, c->x1, 8, Map{lv[1].down, lv[1].tmdown}, 1, nullptr, 0, 1},
-      {"block1.0.conv1", c->x1, 8, c->b1t, 8, Map{lv[1].nbr3, lv[1].tm3}, 1, nullptr, 0, 1},
-      {"block1.0.conv2", c->b1t, 8, c->cat7 + 16, 24, Map{lv[1].nbr3, lv[1].tm3}, 1, c->x1, 8, 1},
-      {"conv2p2s2", c->cat7 + 16, 24, c->x2, 8, Map{lv[2].down, lv[2].tmdown}, 2, nullptr, 0, 1},
-      {"block2.0.conv1", c->x2, 8, c->b2t, 16, Map{lv[2].nbr3, lv[2].tm3}, 2, nullptr, 0, 1},
-      {"block2.0.conv2", c->b2t, 16, c->cat6 + 32, 48, Map{lv[2].nbr3, lv[2].tm3}, 2, nullptr, 0, 1, c->x2, 8},
-      {"conv3p4s2", c->cat6 + 32, 48, c->x3, 16, Map{lv[3].down, lv[3].tmdown}, 3, nullptr, 0, 1},
-      {"block3.0.conv1", c->x3, 16, c->b3t, 32, Map{lv[3].nbr3, lv[3].tm3}, 3, nullptr, 0, 1},
-      {"block3.0.conv2", c->b3t, 32, c->cat5 + 64, 96, Map{lv[3].nbr3, lv[3].tm3}, 3, nullptr, 0, 1, c->x3, 16},
-      {"conv4p8s2", c->cat5 + 64, 96, c->x4, 32, Map{lv[4].down, lv[4].tmdown}, 4, nullptr, 0, 1},
-      {"block4.0.conv1", c->x4, 32, c->b4t, 64, Map{lv[4].nbr3, lv[4].tm3}, 4, nullptr, 0, 1},
-      {"block4.0.conv2", c->b4t, 64, c->b4o, 64, Map{lv[4].nbr3, lv[4].tm3}, 4, nullptr, 0, 1, c->x4, 32, false,
-       (FUSE_UP & 1) ? "convtr4p16s2" : nullptr, c->cat5, 96},
-      {"convtr4p16s2", c->b4o, 64, c->cat5, 96, Map{lv[4].down, lv[4].tmdown}, 3, nullptr, 0, 1},
-      {"block5.0.conv1", c->cat5, 96, c->b5t, 64, Map{lv[3].nbr3, lv[3].tm3}, 3, nullptr, 0, 1},
-      {"block5.0.conv2", c->b5t, 64, c->b5o, 64, Map{lv[3].nbr3, lv[3].tm3}, 3, nullptr, 0, 1, c->cat5, 96, false,
-       (FUSE_UP & 2) ? "convtr5p8s2" : nullptr, c->cat6, 48},
-      {"convtr5p8s2", c->b5o, 64, c->cat6, 48, Map{lv[3].down, lv[3].tmdown}, 2, nullptr, 0, 1},
-      {"block6.0.conv1", c->cat6, 48, c->b6t, 32, Map{lv[2].nbr3, lv[2].tm3}, 2, nullptr, 0, 1},
-      {"block6.0.conv2", c->b6t, 32, c->b6o, 32, Map{lv[2].nbr3, lv[2].tm3}, 2, nullptr, 0, 1, c->cat6, 48, false,
-       (FUSE_UP & 4) ? "convtr6p4s2" : nullptr, c->cat7, 24},
-      {"convtr6p4s2", c->b6o, 32, c->cat7, 24, Map{lv[2].down, lv[2].tmdown}, 1, nullptr, 0, 1},
-      {"block7.0.conv1", c->cat7, 24, c->b7t, 16, Map{lv[1].nbr3, lv[1].tm3}, 1, nullptr, 0, 1},
-      {"block7.0.conv2", c->b7t, 16, c->b7o, 16, Map{lv[1].nbr3, lv[1].tm3}, 1, nullptr, 0, 1, c->cat7, 24, false,
-       (FUSE_UP & 8) ? "convtr7p2s2" : nullptr, c->cat8, 16},
-      {"convtr7p2s2", c->b7o, 16, c->cat8, 16, Map{lv[1].down, lv[1].tmdown}, 0, nullptr, 0, 1},
-      {"block8.0.conv1", c->cat8, 16, c->b8t, 8, Map{lv[0].nbr3, lv[0].tm3}, 0, nullptr, 0, 1},
-      {"block8.0.conv2", c->b8t, 8, c->b8o, 8, Map{lv[0].nbr3, lv[0].tm3}, 0, nullptr, 0, 1, c->cat8, 16, fuse_final},
-  };
-  const char *fused_up = nullptr;  // the transposed convolution the previous launch ran in its epilogue
-  static const char *const fused_stage[][2] = {{"block4.0.conv2", "block4.0.conv2+convtr4p16s2"},
-                                               {"block5.0.conv2", "block5.0.conv2+convtr5p8s2"},
-                                               {"block6.0.conv2", "block6.0.conv2+convtr6p4s2"},
-                                               {"block7.0.conv2", "block7.0.conv2+convtr7p2s2"}};
-  // DIAGNOSTICS (-DSPS_DIAG builds): SPS_DIAG_SKIP_CLASS bit 0 = skip the 3x3x3x3 layers of levels 2-4, 1 = those of levels
-  // 0-1, 2 = the strided convolutions, 3 = the transposed ones, 4 = conv0 -- what a kernel class costs the PIPELINED rate
-  static const int skip_class = [] { const char *e = diag_env("SPS_DIAG_SKIP_CLASS"); return e ? atoi(e) : 0; }();
-  for (const ConvCall &cc : calls) {
-    if (skip_convs) break;
+  const NetSpec &s = *c->net;
+  for (size_t i = 0; i < s.layers.size() && !skip_convs; ++i) {
+    const LayerRow &r = s.layers[i];
     if (skip_class) {
-      const bool tr = std::strncmp(cc.name, "convtr", 6) == 0, c0 = std::strcmp(cc.name, "conv0p1s1") == 0;
-      const bool blk = std::strncmp(cc.name, "block", 5) == 0, strided = !tr && !c0 && !blk;
-      const int cls = blk ? (cc.level_out >= 2 ? 1 : 2) : strided ? 4 : tr ? 8 : 16;
+      const int cls = r.kind == T_K3 ? (r.level >= 2 ? 1 : 2) : r.kind == T_DOWN ? 4 : r.kind == T_UP ? 8 : 16;
       if (skip_class & cls) continue;
     }
-    if (fused_up && std::strcmp(cc.name, fused_up) == 0) {  // already done
-      fused_up = nullptr;
-      continue;
-    }
-    int rc = run_conv(c, cc, st);
+    // the transposed convolution behind conv2 of blocks 4-7 (the next row) runs in that launch's epilogue where FUSE_UP says so
+    const LayerRow *up = nullptr;
+    if (r.blk.buf >= 0 && i + 1 < s.layers.size() && s.layers[i + 1].kind == T_UP && ((FUSE_UP >> (3 - s.layers[i + 1].level)) & 1))
+      up = &s.layers[i + 1];
+    const bool fin = !fo.head && i + 1 == s.layers.size();  // the SPS scores: `final` in the epilogue of the last layer
+    int rc = run_conv(c, r, fin, up, st);
     if (rc != SPS_OK) return rc;
-    const char *stage = cc.name;
-    if (cc.up) {
-      fused_up = cc.up;
-      for (const auto &fs : fused_stage)
-        if (std::strcmp(cc.name, fs[0]) == 0) stage = fs[1];
+    const std::string &name = s.convs[r.conv].name;
+    if (up) {
+      if (c->prof) prof_mark(c, (name + "+" + s.convs[up->conv].name).c_str(), st);
+      ++i;  // already done
+    } else {
+      prof_mark(c, name.c_str(), st);
     }
-    prof_mark(c, stage, st);
   }
   c->cur_vfeat = nullptr;
   const int gs = (int)((n + 255) / 256), gbc = grid_for(cap >> 2, 256, 256);
   if (fo.head) {
-    const NetSpec &s = *c->net;
-    const ConvSpec &fs = s.convs[s.find_conv("final")];
-    hipLaunchKernelGGL(k_slice_head, dim3((unsigned)gs), dim3(256), 0, st, c->b8o, 8, L0.inv, (int)n,
+    const ConvSpec &fs = s.convs[s.final_idx];
+    hipLaunchKernelGGL(k_slice_head, dim3((unsigned)gs), dim3(256), 0, st, c->feat[F_B8O], FEAT[F_B8O].ld, L0.inv, (int)n,
                        c->blob + fs.w_off, c->blob + s.bias_off, s.out_channels, fo.act, scores, fo.ldo, c->counts + 15,
                        fo.n_dev);
     c->last_kernel = "k_slice_head";
@@ -2247,14 +2209,14 @@ int sps_get_feature(sps_ctx *c, const char *name, float *out_dev, int64_t *rows,
   int64_t cnt[SPS_NUM_LEVELS];
   int rc = sps_level_counts(c, cnt);
   if (rc != SPS_OK) return rc;
-  for (const Feat &f : feature_taps(c)) {
+  for (const FeatTap &f : FEATURE_TAPS) {
     if (std::strcmp(f.name, name) != 0) continue;
-    *rows = cnt[f.level];
-    *cols = f.cols;
+    *rows = cnt[FEAT[f.v.buf].level];
+    *cols = f.v.cols;
     if (out_dev && *rows > 0) {
-      const int64_t tot = *rows * f.cols;
-      hipLaunchKernelGGL(k_copy_strided, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, 0, f.ptr, f.ld, (int)*rows,
-                         f.cols, out_dev);
+      const int64_t tot = *rows * f.v.cols;
+      hipLaunchKernelGGL(k_copy_strided, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, 0, feat_ptr(c, f.v), feat_ld(f.v), (int)*rows,
+                         f.v.cols, out_dev);
       HIP_TRY(hipDeviceSynchronize());
     }
     return SPS_OK;

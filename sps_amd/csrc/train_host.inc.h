@@ -9,6 +9,9 @@
 //                       sps_weights_tensor_info).  Data gradients reuse the forward's gather kernels over the same
 //                       kernel maps with mirrored / transposed weights; weight gradients are MFMA reductions over the
 //                       map's pairs (k_wgrad); BN / ReLU / residual backward in k_bn_bwd_*.
+// The op list of a step (train_ops) is the wiring table of netspec.inc.h resolved against the training views -- the same
+// rows the inference forward walks; conv_plain fills its ConvArgs through conv_args and launches through launch_upconv /
+// launch_k_conv, the launchers of the inference path (sps_hip.hip).
 // The loss (nn.MSELoss on the scan rows, models.py:62-70) and the optimiser (Adam + StepLR, models.py:154-160) stay in
 // torch: they are a handful of elementwise kernels on tensors torch already owns.
 
@@ -20,11 +23,9 @@ struct TView {      // a feature tensor view: `cols` columns starting at column 
   int ld = 0, cols = 0, level = 0;
 };
 
-enum TKind { T_CONV0 = 0, T_K3 = 1, T_DOWN = 2, T_UP = 3, T_LIN = 4 };
-
 struct TOp {
-  const char *name;  // conv name in the spec (its BN follows)
-  TKind kind;
+  int conv;          // index into NetSpec::convs (its BN: bn_idx)
+  ConvKind kind;
   TView in, out;     // out = destination of relu?(bn(z) [+ res])
   int relu;
   TView res;         // residual operand (p == nullptr: none)
@@ -48,7 +49,7 @@ struct sps_train {
   std::vector<float *> z;                  // per conv: raw output [cap, cout]
   float *gpool = nullptr;                  // gradients of the feature buffers (one allocation, zeroed per backward)
   size_t gpool_bytes = 0;
-  float *r_p[9] = {}, *r_g[9] = {};        // BN'd 1x1 downsample branch (the residual operand) of block i (2..8)
+  std::vector<float *> r_p, r_g;           // per downsample conv: its BN'd output (the residual operand of the block's conv2)
   std::vector<float *> dzl;                // per conv: gradient wrt its raw output [cap, cout] (kept until the weight gradients run, at the end)
   std::vector<WgradJobs> wjobs;            // weight-gradient jobs of the running backward, by block shape (wgrad_shape_index)
   float *slab = nullptr;                   // workgroup partials of the weight gradients, every layer its own region
@@ -62,7 +63,7 @@ struct sps_train {
   PermDesc *perm = nullptr;                // operand table of k_permute_weights (one launch per step)
   int n_perm = 0, perm_blocks = 0;
   long long *vacc = nullptr;
-  // gradient views of the context's feature buffers, in the order of feat_list()
+  // gradient views of the context's feature buffers, by FeatId
   std::vector<TView> views;
   int64_t n_last = 0;
   bool have_forward = false;
@@ -89,19 +90,8 @@ constexpr int C0_WG = 1024;  // workgroups (x 4 waves, one row at a time each) o
     ptr = reinterpret_cast<type *>(p_);                                                             \
   } while (0)
 
-// the context's feature buffers (name, pointer, row stride, level) -- gradients get the same shapes
-struct FeatDesc {
-  float *p;
-  int ld, level;
-};
-std::vector<FeatDesc> feat_list(sps_ctx *c) {
-  return {{c->cat8, 16, 0}, {c->b8t, 8, 0}, {c->b8o, 8, 0}, {c->x1, 8, 1},  {c->b1t, 8, 1},  {c->cat7, 24, 1}, {c->b7t, 16, 1},
-          {c->b7o, 16, 1},  {c->x2, 8, 2},  {c->b2t, 16, 2}, {c->cat6, 48, 2}, {c->b6t, 32, 2}, {c->b6o, 32, 2}, {c->x3, 16, 3},
-          {c->b3t, 32, 3},  {c->cat5, 96, 3}, {c->b5t, 64, 3}, {c->b5o, 64, 3}, {c->x4, 32, 4}, {c->b4t, 64, 4}, {c->b4o, 64, 4}};
-}
-
 std::vector<TOp> train_ops(sps_ctx *c);
-inline bool is_downsample(const TOp &op) { return std::strstr(op.name, "downsample") != nullptr; }
+inline bool is_downsample(const TOp &op) { return op.kind == T_LIN; }
 
 int train_reserve(sps_ctx *c) {
   if (!c->train) c->train = new sps_train();
@@ -122,7 +112,7 @@ int train_reserve(sps_ctx *c) {
     const ConvSpec &cs = s.convs[i];
     t->wu_off[i] = nwu;
     t->wut_off[i] = nwut;
-    if (cs.cin == 1 || cs.name == "final") continue;
+    if (cs.cin == 1 || (int)i == s.final_idx) continue;
     nwu += (int64_t)cs.K * (cs.cin / 4) * ((cs.cout + 15) / 16) * 64;
     nwut += (int64_t)cs.K * (cs.cout / 4) * ((cs.cin + 15) / 16) * 64;
   }
@@ -130,38 +120,33 @@ int train_reserve(sps_ctx *c) {
   TALLOC(t->wut, float, nwut);
   t->z.assign(s.convs.size(), nullptr);
   for (size_t i = 0; i < s.convs.size(); ++i) {
-    if (s.convs[i].name == "final") continue;
+    if ((int)i == s.final_idx) continue;
     TALLOC(t->z[i], float, (size_t)cap * s.convs[i].cout);
   }
-  // gradients of the feature buffers + of the residual operands, one pool
-  const auto feats = feat_list(c);
-  size_t gfloats = 0;
-  for (const FeatDesc &f : feats) gfloats += (size_t)cap * f.ld;
-  const int rcols[9] = {0, 0, 16, 32, 64, 64, 32, 16, 8};  // C_out of block i's downsample branch (block1 has none)
-  size_t rfloats = 0;
-  for (int b = 2; b <= 8; ++b) rfloats += (size_t)cap * rcols[b];
+  // gradients of the feature buffers (same shapes) + of the residual operands, one pool
+  size_t gfloats = 0, rfloats = 0;
+  for (const FeatShape &f : FEAT) gfloats += (size_t)cap * f.ld;
+  for (const ConvSpec &cs : s.convs)
+    if (cs.ds_idx >= 0) rfloats += (size_t)cap * cs.cout;
   TALLOC(t->gpool, float, gfloats + rfloats);
   t->gpool_bytes = (gfloats + rfloats) * sizeof(float);
   t->views.clear();
   float *gp = t->gpool;
-  for (const FeatDesc &f : feats) {
-    TView v;
-    v.p = f.p;
-    v.g = gp;
-    v.ld = f.ld;
-    v.cols = f.ld;
-    v.level = f.level;
-    t->views.push_back(v);
-    gp += (size_t)cap * f.ld;
+  for (int f = 0; f < N_FEAT; ++f) {
+    t->views.push_back(TView{c->feat[f], gp, FEAT[f].ld, FEAT[f].ld, FEAT[f].level});
+    gp += (size_t)cap * FEAT[f].ld;
   }
-  for (int b = 2; b <= 8; ++b) {
-    t->r_g[b] = gp;
-    gp += (size_t)cap * rcols[b];
-    TALLOC(t->r_p[b], float, (size_t)cap * rcols[b]);
+  t->r_p.assign(s.convs.size(), nullptr);
+  t->r_g.assign(s.convs.size(), nullptr);
+  for (const ConvSpec &cs : s.convs) {  // (in block order)
+    if (cs.ds_idx < 0) continue;
+    t->r_g[cs.ds_idx] = gp;
+    gp += (size_t)cap * cs.cout;
+    TALLOC(t->r_p[cs.ds_idx], float, (size_t)cap * cs.cout);
   }
   t->dzl.assign(s.convs.size(), nullptr);
   for (size_t i = 0; i < s.convs.size(); ++i) {
-    if (s.convs[i].name == "final") continue;
+    if ((int)i == s.final_idx) continue;
     TALLOC(t->dzl[i], float, (size_t)cap * s.convs[i].cout);
   }
   // weight gradients: a wave owns aw x bw tiles of 16 x 16 of dW[k] and one chunk of the level's row tiles; the rows are cut
@@ -180,7 +165,7 @@ int train_reserve(sps_ctx *c) {
     int64_t off = 0;
     for (const TOp &op : train_ops(c)) {
       if (op.kind == T_CONV0) continue;
-      const int i = s.find_conv(op.name);
+      const int i = op.conv;
       const ConvSpec &cs = s.convs[i];
       const int level = op.kind == T_UP ? op.out.level + 1 : op.out.level;  // the level whose rows the map lists
       WgPlan &w = t->wg[i];
@@ -218,7 +203,7 @@ int train_reserve(sps_ctx *c) {
     int blk = 0;
     for (size_t i = 0; i < s.convs.size(); ++i) {
       const ConvSpec &cs = s.convs[i];
-      if (cs.cin == 1 || cs.name == "final") continue;
+      if (cs.cin == 1 || (int)i == s.final_idx) continue;
       // forward operand, then the data-gradient operand: symmetric 3^4 maps mirror the offset; stride / transposed / 1x1 maps keep it
       const int modes[2] = {0, cs.K == 81 ? 1 : 2};
       for (int mode : modes) {
@@ -250,11 +235,6 @@ int train_reserve(sps_ctx *c) {
 
 inline bool vec4_ok(const float *p, int ld) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0 && (ld & 3) == 0; }
 
-TView view_of(sps_train *t, const float *p) {
-  for (const TView &v : t->views)
-    if (v.p == p) return v;
-  return TView{};
-}
 TView cols_of(TView v, int col0, int cols) {  // sub-view: columns [col0, col0 + cols)
   v.p += col0;
   v.g += col0;
@@ -262,54 +242,23 @@ TView cols_of(TView v, int col0, int cols) {  // sub-view: columns [col0, col0 +
   return v;
 }
 
-// the network as a list of conv + BN (+ residual) (+ ReLU) ops in forward order (minkunet.py:161-219, resnet BasicBlock)
+// the network as a list of conv + BN (+ residual) (+ ReLU) ops in forward order: the rows of the wiring table (netspec.inc.h)
+// resolved against the training views, plus, before conv2 of a block with a downsample, the T_LIN op that writes the BN'd
+// 1x1 branch of the block input into its own buffer -- conv2's residual operand (resnet BasicBlock)
 std::vector<TOp> train_ops(sps_ctx *c) {
   sps_train *t = c->train;
-  auto V = [&](const float *p) { return view_of(t, p); };
-  auto R = [&](int block, int level, int cols) {
-    TView v;
-    v.p = t->r_p[block];
-    v.g = t->r_g[block];
-    v.ld = cols;
-    v.cols = cols;
-    v.level = level;
-    return v;
-  };
-  const TView none{};
-  const TView cat8 = V(c->cat8), cat7 = V(c->cat7), cat6 = V(c->cat6), cat5 = V(c->cat5);
+  const NetSpec &s = *t->net;
+  auto V = [&](FeatView v) { return v.buf < 0 ? TView{} : cols_of(t->views[v.buf], v.col0, v.cols); };
   std::vector<TOp> ops;
-  ops.push_back({"conv0p1s1", T_CONV0, none, cols_of(cat8, 8, 8), 1, none});
-  ops.push_back({"conv1p1s2", T_DOWN, cols_of(cat8, 8, 8), V(c->x1), 1, none});
-  ops.push_back({"block1.0.conv1", T_K3, V(c->x1), V(c->b1t), 1, none});
-  ops.push_back({"block1.0.conv2", T_K3, V(c->b1t), cols_of(cat7, 16, 8), 1, V(c->x1)});
-  ops.push_back({"conv2p2s2", T_DOWN, cols_of(cat7, 16, 8), V(c->x2), 1, none});
-  ops.push_back({"block2.0.conv1", T_K3, V(c->x2), V(c->b2t), 1, none});
-  ops.push_back({"block2.0.downsample.0", T_LIN, V(c->x2), R(2, 2, 16), 0, none});
-  ops.push_back({"block2.0.conv2", T_K3, V(c->b2t), cols_of(cat6, 32, 16), 1, R(2, 2, 16)});
-  ops.push_back({"conv3p4s2", T_DOWN, cols_of(cat6, 32, 16), V(c->x3), 1, none});
-  ops.push_back({"block3.0.conv1", T_K3, V(c->x3), V(c->b3t), 1, none});
-  ops.push_back({"block3.0.downsample.0", T_LIN, V(c->x3), R(3, 3, 32), 0, none});
-  ops.push_back({"block3.0.conv2", T_K3, V(c->b3t), cols_of(cat5, 64, 32), 1, R(3, 3, 32)});
-  ops.push_back({"conv4p8s2", T_DOWN, cols_of(cat5, 64, 32), V(c->x4), 1, none});
-  ops.push_back({"block4.0.conv1", T_K3, V(c->x4), V(c->b4t), 1, none});
-  ops.push_back({"block4.0.downsample.0", T_LIN, V(c->x4), R(4, 4, 64), 0, none});
-  ops.push_back({"block4.0.conv2", T_K3, V(c->b4t), V(c->b4o), 1, R(4, 4, 64)});
-  ops.push_back({"convtr4p16s2", T_UP, V(c->b4o), cols_of(cat5, 0, 64), 1, none});
-  ops.push_back({"block5.0.conv1", T_K3, cat5, V(c->b5t), 1, none});
-  ops.push_back({"block5.0.downsample.0", T_LIN, cat5, R(5, 3, 64), 0, none});
-  ops.push_back({"block5.0.conv2", T_K3, V(c->b5t), V(c->b5o), 1, R(5, 3, 64)});
-  ops.push_back({"convtr5p8s2", T_UP, V(c->b5o), cols_of(cat6, 0, 32), 1, none});
-  ops.push_back({"block6.0.conv1", T_K3, cat6, V(c->b6t), 1, none});
-  ops.push_back({"block6.0.downsample.0", T_LIN, cat6, R(6, 2, 32), 0, none});
-  ops.push_back({"block6.0.conv2", T_K3, V(c->b6t), V(c->b6o), 1, R(6, 2, 32)});
-  ops.push_back({"convtr6p4s2", T_UP, V(c->b6o), cols_of(cat7, 0, 16), 1, none});
-  ops.push_back({"block7.0.conv1", T_K3, cat7, V(c->b7t), 1, none});
-  ops.push_back({"block7.0.downsample.0", T_LIN, cat7, R(7, 1, 16), 0, none});
-  ops.push_back({"block7.0.conv2", T_K3, V(c->b7t), V(c->b7o), 1, R(7, 1, 16)});
-  ops.push_back({"convtr7p2s2", T_UP, V(c->b7o), cols_of(cat8, 0, 8), 1, none});
-  ops.push_back({"block8.0.conv1", T_K3, cat8, V(c->b8t), 1, none});
-  ops.push_back({"block8.0.downsample.0", T_LIN, cat8, R(8, 0, 8), 0, none});
-  ops.push_back({"block8.0.conv2", T_K3, V(c->b8t), V(c->b8o), 1, R(8, 0, 8)});
+  for (const LayerRow &r : s.layers) {
+    const ConvSpec &cs = s.convs[r.conv];
+    TView res = V(r.blk);
+    if (cs.ds_idx >= 0) {
+      res = TView{t->r_p[cs.ds_idx], t->r_g[cs.ds_idx], cs.cout, cs.cout, r.level};
+      ops.push_back({cs.ds_idx, T_LIN, V(r.blk), res, 0, TView{}});
+    }
+    ops.push_back({r.conv, r.kind, V(r.in), V(r.out), r.relu, res});
+  }
   return ops;
 }
 
@@ -317,67 +266,22 @@ std::vector<TOp> train_ops(sps_ctx *c) {
 // k_conv (gather maps: 3^4 tables, `down` tables, identity) or k_upconv (parent-stationary over a `down` table).
 //   gather : T_K3 (nbr3 of level_rows), T_DOWN (down table of level_rows: rows = coarse), T_LIN (identity), or
 //            T_UP (k_upconv: rows iterate the COARSE level level_rows, children written at the fine level)
-int conv_plain(sps_ctx *c, hipStream_t st, TKind gather, int level_rows, int K, int cin, int cout, const float *Wu,
+int conv_plain(sps_ctx *c, hipStream_t st, ConvKind gather, int level_rows, int K, int cin, int cout, const float *Wu,
                const float *in, int ldi, float *out, int ldo, bool accumulate) {
   sps_train *t = c->train;
-  ConvArgs a{};
-  a.in = in;
-  a.ldi = ldi;
-  a.out = out;
-  a.ldo = ldo;
-  a.Wu = Wu;
-  a.scale = t->ones;
-  a.shift = t->zeros;
-  a.res = accumulate ? out : nullptr;
-  a.ldr = ldo;
-  a.ldn = c->capl[level_rows];
-  a.abort_flag = nullptr;
-  a.out_rows = 0;
-  a.K = K;
-  a.cin = cin;
-  a.cout = cout;
-  a.NT = (cout + 15) / 16;
-  a.upk = cin / 4;
-  a.inv_upk = 1.0f / (float)a.upk;
-  a.relu = 0;
-  a.in_const = 0.5f;
-  a.S = 1;
+  ConvArgs a = conv_args(c, level_rows, K, cin, cout, Wu, t->ones, t->zeros, in, ldi, out, ldo, accumulate ? out : nullptr, ldo);
   a.in_bytes = (uint32_t)((size_t)c->cap * (size_t)ldi * 4u);  // training runs on dense arenas: every level holds cap rows
   a.wu_bytes = (uint32_t)((size_t)K * a.upk * a.NT * 64 * 4);
-  a.nbr_bytes = (uint32_t)((size_t)K * (size_t)c->capl[level_rows] * 4u);
-  a.tile_cap = (int)(c->capl[level_rows] / 16);
-  a.n_out = c->counts + level_rows;
-  Level &L = c->lv[level_rows];
-  if (gather == T_UP) {
-    a.nbr = L.down;
-    a.tmask = L.tmdown;
-    int64_t gu = (c->cap / 16) >> level_rows;
-    gu = std::min<int64_t>(std::max<int64_t>(gu, 64), 8192);
-    if (a.NT == 1)
-      hipLaunchKernelGGL((k_upconv<1>), dim3((unsigned)gu), dim3(256), 0, st, a);
-    else if (a.NT == 2)
-      hipLaunchKernelGGL((k_upconv<2>), dim3((unsigned)gu), dim3(256), 0, st, a);
-    else if (a.NT == 4)
-      hipLaunchKernelGGL((k_upconv<4>), dim3((unsigned)gu), dim3(256), 0, st, a);
-    else
-      return fail(SPS_ERR_INVALID, "k_upconv: unsupported column count %d", cout);
-    return SPS_OK;
-  }
-  if (gather == T_K3) {
-    a.nbr = L.nbr3;
-    a.tmask = L.tm3;
-  } else if (gather == T_DOWN) {
-    a.nbr = L.down;
-    a.tmask = L.tmdown;
-  }  // T_LIN: identity (nbr = tmask = null)
-  int64_t gx = (c->cap / 64) >> level_rows;
-  gx = std::min<int64_t>(std::max<int64_t>(gx, 64), 4096);
+  const Map map = level_map(c, gather, level_rows);  // T_LIN: identity (nbr = tmask = null)
+  a.nbr = map.nbr;
+  a.tmask = map.tmask;
+  if (gather == T_UP) return launch_upconv(a, c->cap, level_rows, st);
   // the inference geometry of the level (column tiles per wave x splits); NT = 3 / 6 (gradients wrt 48 / 96 channels)
   // only divide by one column tile per wave
   Geometry g = conv_geometry(level_rows, K, cin, a.NT);
   if (a.NT % g.ntw != 0) g.ntw = 1;
   a.S = g.S;
-  const dim3 grid((unsigned)(a.NT / g.ntw), (unsigned)(gx * g.S), 1u);
+  const dim3 grid((unsigned)(a.NT / g.ntw), (unsigned)(row_grid(c->cap, level_rows) * g.S), 1u);
   return launch_k_conv(a, g, false, grid, st);
 }
 
@@ -387,7 +291,7 @@ inline int wgrad_shape_index(int aw, int bw) {  // <1,1> <1,2> <1,4> <2,1> <2,2>
 }
 
 // The weight gradient of a layer joins the job table of its block shape; wgrad_run launches the tables at the end of the backward.
-int wgrad_defer(sps_ctx *c, TKind kind, int conv_index, int level_rows, int K, int cin, int cout, const float *x, int ldx,
+int wgrad_defer(sps_ctx *c, ConvKind kind, int conv_index, int level_rows, int K, int cin, int cout, const float *x, int ldx,
                 const float *dz, int ldz, float *dW) {
   sps_train *t = c->train;
   const WgPlan &pl = t->wg[conv_index];
@@ -406,15 +310,10 @@ int wgrad_defer(sps_ctx *c, TKind kind, int conv_index, int level_rows, int K, i
   w.dz_bytes = (uint32_t)((size_t)c->cap * (size_t)ldz * 4u);
   w.ldn = c->capl[level_rows];
   w.n_rows = c->counts + level_rows;
-  Level &L = c->lv[level_rows];
   w.gather_b = kind == T_UP ? 1 : 0;
-  if (kind == T_K3) {
-    w.nbr = L.nbr3;
-    w.tmask = L.tm3;
-  } else if (kind == T_DOWN || kind == T_UP) {
-    w.nbr = L.down;
-    w.tmask = L.tmdown;
-  }
+  const Map map = level_map(c, kind, level_rows);
+  w.nbr = map.nbr;
+  w.tmask = map.tmask;
   if ((cin & 7) || (cout & 7) || (ldx & 3) || (ldz & 3) || (reinterpret_cast<uintptr_t>(x) & 15) || (reinterpret_cast<uintptr_t>(dz) & 15))
     return fail(SPS_ERR_INVALID, "wgrad: operands must be 16-byte aligned with channel counts in multiples of 8");
   w.out = pl.nwg > 1 ? t->slab + pl.slab_off : dW;
@@ -520,9 +419,9 @@ int sps_train_forward(sps_ctx *c, const float *params_dev, int64_t numel, const 
     int64_t apply_items = 0;
     for (size_t j = 0; j < npair; ++j) {
       const TOp &op = ops[oi + j];
-      const int ci = s.find_conv(op.name);
+      const int ci = op.conv;
       const ConvSpec &cs = s.convs[ci];
-      const int bi = s.find_bn(cs.bn);
+      const int bi = cs.bn_idx;
       const BnSpec &bn = s.bns[bi];
       const int lo = op.out.level;
       float *z = t->z[ci];
@@ -537,7 +436,7 @@ int sps_train_forward(sps_ctx *c, const float *params_dev, int64_t numel, const 
       }
       if (rc != SPS_OK) return rc;
       if (!vec4_ok(z, cs.cout) || !vec4_ok(op.out.p, op.out.ld) || (op.res.p && !vec4_ok(op.res.p, op.res.ld)))
-        return fail(SPS_ERR_INVALID, "training BatchNorm operands must be 16-byte aligned (%s)", op.name);
+        return fail(SPS_ERR_INVALID, "training BatchNorm operands must be 16-byte aligned (%s)", cs.name.c_str());
       BnFwd &b = jobs.j[j];
       b.Z = z;
       b.ldz = cs.cout;
@@ -561,8 +460,8 @@ int sps_train_forward(sps_ctx *c, const float *params_dev, int64_t numel, const 
     oi += npair;
   }
   // final 1x1 conv + bias, slice, sigmoid (models.py:28-29)
-  const ConvSpec &fs = s.convs[s.find_conv("final")];
-  hipLaunchKernelGGL(k_slice_head, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, c->b8o, 8, c->lv[0].inv, (int)n,
+  const ConvSpec &fs = s.convs[s.final_idx];
+  hipLaunchKernelGGL(k_slice_head, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, c->feat[F_B8O], FEAT[F_B8O].ld, c->lv[0].inv, (int)n,
                      t->blob + fs.w_off, t->blob + s.bias_off, 1, 1, scores, (int64_t)1, (const int *)nullptr,
                      (const int *)nullptr);
   if (batch_stats_dev)
@@ -625,8 +524,8 @@ static int train_backward_impl(sps_ctx *c, const float *dscores, const float *sc
       ++nz;
     };
     for (const TView &v : t->views) add(v.g, v.ld, v.level);
-    static const int rlevel[9] = {0, 0, 2, 3, 4, 3, 2, 1, 0}, rcols[9] = {0, 0, 16, 32, 64, 64, 32, 16, 8};
-    for (int b = 2; b <= 8; ++b) add(t->r_g[b], rcols[b], rlevel[b]);
+    for (const LayerRow &r : s.layers)
+      if (s.convs[r.conv].ds_idx >= 0) add(t->r_g[s.convs[r.conv].ds_idx], s.convs[r.conv].cout, r.level);
     add(t->grad, (numel + 3) & ~(int64_t)3, -1);  // (allocations are padded to 16 bytes)
     add(reinterpret_cast<float *>(t->vacc), 2 * c->cap, -1);
     if (nz > ZERO_MAX) return fail(SPS_ERR_INVALID, "backward: %d buffers to clear, table holds %d", nz, ZERO_MAX);
@@ -634,8 +533,8 @@ static int train_backward_impl(sps_ctx *c, const float *dscores, const float *sc
   }
   t->wjobs.assign(WGRAD_SHAPES, WgradJobs{});
   // head: sigmoid + slice + final
-  const ConvSpec &fs = s.convs[s.find_conv("final")];
-  const TView b8o = view_of(t, c->b8o);
+  const ConvSpec &fs = s.convs[s.final_idx];
+  const TView b8o = t->views[F_B8O];
   hipLaunchKernelGGL(k_dlogit_accum, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, dscores, scores, c->lv[0].inv, (int)n, t->vacc);
   hipLaunchKernelGGL(k_final_bwd, dim3(BN_WG), dim3(256), 0, st, t->vacc, c->counts + 0, b8o.p, b8o.ld, t->blob + fs.w_off, b8o.g,
                      b8o.ld, t->fin_part);
@@ -649,13 +548,13 @@ static int train_backward_impl(sps_ctx *c, const float *dscores, const float *sc
     int64_t apply_items = 0;
     for (int j = 0; j < npair; ++j) {
       const TOp &op = ops[oi - j];
-      const int ci = s.find_conv(op.name);
+      const int ci = op.conv;
       const ConvSpec &cs = s.convs[ci];
-      const int bi = s.find_bn(cs.bn);
+      const int bi = cs.bn_idx;
       const BnSpec &bn = s.bns[bi];
       const int lo = op.out.level;
       if (!vec4_ok(op.out.g, op.out.ld) || (op.res.g && !vec4_ok(op.res.g, op.res.ld)))
-        return fail(SPS_ERR_INVALID, "training BatchNorm gradients must be 16-byte aligned (%s)", op.name);
+        return fail(SPS_ERR_INVALID, "training BatchNorm gradients must be 16-byte aligned (%s)", cs.name.c_str());
       // BN (+ ReLU, + residual) backward: dY -> dZ, dgamma, dbeta, and dA added to the residual operand's gradient
       BnBwd &b = jobs.j[j];
       b.dY = op.out.g;
@@ -682,7 +581,7 @@ static int train_backward_impl(sps_ctx *c, const float *dscores, const float *sc
     hipLaunchKernelGGL(k_bn_bwd_apply, dim3((unsigned)grid_for(apply_items, 256, 1024), (unsigned)npair), dim3(256), 0, st, jobs);
     for (int j = 0; j < npair; ++j) {
       const TOp &op = ops[oi - j];
-      const int ci = s.find_conv(op.name);
+      const int ci = op.conv;
       const ConvSpec &cs = s.convs[ci];
       const int lo = op.out.level;
       const float *dz = t->dzl[ci];
