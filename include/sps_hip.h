@@ -606,6 +606,8 @@ int sps_ndt_top_poses(sps_ctx *ctx, const double *score_dev, const double *T_dev
 /* ---- NDT localiser, online map ----------------------------------------------------------------------------------------
  * A map that grows: the stable points a filter keeps are folded into the cells at the frame's corrected pose, on the
  * frame's stream, so that a localiser can start from an empty map and a scene that changed is learnt.  
+ * The context's single map is a pyramid of one level: the calls of this section and of the carving section below are
+ * those of the "online pyramid" section with n_levels = 1 on a slot of its own, and share their implementation.
  *
  * sps_ndt_map_build_dynamic: sps_ndt_map_build's arguments and checks, plus cell_capacity >= max(n_cells, 1).  Records,
  *   counts and keys are allocated for cell_capacity cells and the hash for next_pow2(2 * max(512, cell_capacity)) slots (it
@@ -635,8 +637,8 @@ int sps_ndt_top_poses(sps_ctx *ctx, const double *score_dev, const double *T_dev
  *   info_dev int32[4] = (cells assigned after the update, cells founded, cells dropped for capacity in this update,
  *   points integrated).  Seven launches and two memsets of the scratch whatever the data; cap <=
  *   SPS_NDT_UPDATE_MAX_POINTS.  scratch_dev: sps_ndt_map_update_scratch(cap) bytes (-1 for cap out of range), 256-byte
- *   aligned.  The result depends on the points, their order and the pose only.  Never allocates, never synchronises, never
- *   raises the sticky error.
+ *   aligned; it is sps_ndt_pyramid_update_scratch(cap, 1).  The result depends on the points, their order and the pose
+ *   only.  Never allocates, never synchronises, never raises the sticky error.
  * sps_ndt_map_info: debug -- out_host = (cells assigned, cell_capacity, cells dropped since the build, 0).  Synchronises. */
 #define SPS_NDT_UPDATE_MAX_POINTS 65536
 int sps_ndt_map_build_dynamic(sps_ctx *ctx, const uint64_t *cell_keys_dev, const int32_t *cell_start_dev,
@@ -657,7 +659,8 @@ int sps_ndt_map_info(sps_ctx *ctx, int64_t *out_host);
  * Per-cell state: a map built by sps_ndt_map_build_dynamic also holds three int32[cell_capacity] arrays, zero after the
  *   build: pass and hit, the counts of the last carve whose gate was open, and miss, the consecutive carves in which the
  *   cell was seen through.  sps_ndt_map_build drops them with the rest of the dynamic state.
- * sps_ndt_map_carve: pts_dev, n_dev, cap, T_host, T_dev and gate_dev are sps_ndt_map_update's and are checked as there
+ * sps_ndt_map_carve: the carve of a pyramid of one level (sps_ndt_pyramid_carve with the scalar end_margin as its one
+ *   entry).  pts_dev, n_dev, cap, T_host, T_dev and gate_dev are sps_ndt_map_update's and are checked as there
  *   (cap <= SPS_NDT_UPDATE_MAX_POINTS; a map built by sps_ndt_map_build is refused with INVALID).  end_margin >= 0 and
  *   finite, through_sigma > 0 and finite, min_pass >= 1, miss_frames >= 1, 1 <= max_steps <= 4096, else INVALID.
  *   Gate: unless *gate_dev holds 0 or 1 (NULL: open) no byte of the map and none of the three arrays changes and
@@ -746,6 +749,7 @@ int sps_ndt_pyramid_align(sps_ctx *ctx, const double *pts_dev, const int32_t *n_
 /* ---- NDT localiser, online pyramid ------------------------------------------------------------------------------------
  * The pyramid above with the online map's two operations: every level is a dynamic map (moments, capacity, carve counters),
  * and one call updates, one call carves, all levels in the same launches, the level being a grid dimension.  
+ * These are the launches of sps_ndt_map_update and sps_ndt_map_carve, whose single map is a pyramid of one level.
  * Additive: sps_version() is unchanged; the context's single map and every call above keep their behaviour and their bits.
  *
  * sps_ndt_pyramid_build_dynamic: sps_ndt_pyramid_build with cell_capacity (host int64[n_levels]).  Level l is the map that

@@ -473,7 +473,7 @@ class Context:
                                     float(resolution), int(min_points), float(eig_ratio), stream))
 
     def ndt_map_cells(self, key_ptr, count_ptr, mean_ptr, icov_ptr, valid_ptr):
-        check(lib.sps_ndt_map_cells(self.handle, key_ptr, count_ptr, mean_ptr, icov_ptr, valid_ptr))
+        self._ndt_level_call("cells", None, key_ptr, count_ptr, mean_ptr, icov_ptr, valid_ptr)
 
     def ndt_align(self, pts_ptr, n_dev_ptr: int, cap: int, T_init, iters: int, neighbours: int, min_corr: int,
                   outlier_ratio: float, tol_t: float, tol_r: float, T_out_ptr: int, status_ptr: int, trace_ptr, normal_ptr,
@@ -507,28 +507,52 @@ class Context:
         check(lib.sps_ndt_map_build_dynamic(self.handle, keys_ptr, start_ptr, pts_ptr, xyz_ptr, int(n_cells), int(n_map),
                                             float(resolution), int(min_points), float(eig_ratio), int(cell_capacity), stream))
 
-    def ndt_map_update(self, pts_ptr, n_dev_ptr: int, cap: int, T_host, T_dev_ptr, gate_ptr, max_cell_points: int,
-                       info_ptr: int, scratch_ptr: int, stream: int):
-        check(lib.sps_ndt_map_update(self.handle, pts_ptr, n_dev_ptr, int(cap), self._mat(T_host) if T_host is not None else None,
-                                     T_dev_ptr, gate_ptr, int(max_cell_points), info_ptr, scratch_ptr, stream))
+    def ndt_map_update(self, *args):
+        """the arguments of ``_ndt_update`` after ``pyramid``; info_ptr: int32[4]"""
+        self._ndt_update(False, *args)
 
     def ndt_map_info(self):
         """(cells assigned, cell capacity, cells dropped for capacity since the build); synchronises"""
-        out = (C.c_int64 * 4)()
-        check(lib.sps_ndt_map_info(self.handle, out))
-        return int(out[0]), int(out[1]), int(out[2])
+        return self._ndt_info(None)
 
     # ---- free-space carving (include/sps_hip.h, "NDT localiser, online map: free-space carving") ----
-    def ndt_map_carve(self, pts_ptr, n_dev_ptr: int, cap: int, T_host, T_dev_ptr, gate_ptr, end_margin: float,
-                      through_sigma: float, min_pass: int, miss_frames: int, max_steps: int, info_ptr: int, scratch_ptr,
-                      stream: int):
-        check(lib.sps_ndt_map_carve(self.handle, pts_ptr, n_dev_ptr, int(cap), self._mat(T_host) if T_host is not None else None,
-                                    T_dev_ptr, gate_ptr, float(end_margin), float(through_sigma), int(min_pass), int(miss_frames),
-                                    int(max_steps), info_ptr, scratch_ptr, stream))
+    def ndt_map_carve(self, *args):
+        """the arguments of ``_ndt_carve`` after ``pyramid``; end_margin: a float; info_ptr: int32[4]"""
+        self._ndt_carve(False, *args)
 
     def ndt_map_carve_cells(self, pass_ptr, hit_ptr, miss_ptr):
         """pass, hit and miss of every cell of the capacity into int32 device arrays (any may be None); synchronises"""
-        check(lib.sps_ndt_map_carve_cells(self.handle, pass_ptr, hit_ptr, miss_ptr))
+        self._ndt_level_call("carve_cells", None, pass_ptr, hit_ptr, miss_ptr)
+
+    # The online map is a pyramid of one level (include/sps_hip.h), so its ABI functions and the online pyramid's differ by
+    # their names and a level argument: one helper per pair.  ``pyramid`` False / ``level`` None: the single map.
+    def _ndt_update(self, pyramid: bool, pts_ptr, n_dev_ptr: int, cap: int, T_host, T_dev_ptr, gate_ptr, max_cell_points: int,
+                    info_ptr: int, scratch_ptr: int, stream: int):
+        """info_ptr: int32[4], of a pyramid int32[n_levels][4]"""
+        fn = lib.sps_ndt_pyramid_update if pyramid else lib.sps_ndt_map_update
+        check(fn(self.handle, pts_ptr, n_dev_ptr, int(cap), self._mat(T_host) if T_host is not None else None, T_dev_ptr, gate_ptr,
+                 int(max_cell_points), info_ptr, scratch_ptr, stream))
+
+    def _ndt_carve(self, pyramid: bool, pts_ptr, n_dev_ptr: int, cap: int, T_host, T_dev_ptr, gate_ptr, end_margin,
+                   through_sigma: float, min_pass: int, miss_frames: int, max_steps: int, info_ptr: int, scratch_ptr, stream: int):
+        """end_margin: a float, of a pyramid one float per level; info_ptr: as for ``_ndt_update``"""
+        fn = lib.sps_ndt_pyramid_carve if pyramid else lib.sps_ndt_map_carve
+        em = (C.c_double * len(end_margin))(*[float(v) for v in end_margin]) if pyramid else float(end_margin)
+        check(fn(self.handle, pts_ptr, n_dev_ptr, int(cap), self._mat(T_host) if T_host is not None else None, T_dev_ptr, gate_ptr,
+                 em, float(through_sigma), int(min_pass), int(miss_frames), int(max_steps), info_ptr, scratch_ptr, stream))
+
+    def _ndt_level_call(self, name: str, level, *args):
+        """sps_ndt_map_<name>(ctx, args) or, with a level, sps_ndt_pyramid_<name>(ctx, level, args); name: info, cells or
+        carve_cells"""
+        if level is None:
+            check(getattr(lib, f"sps_ndt_map_{name}")(self.handle, *args))
+        else:
+            check(getattr(lib, f"sps_ndt_pyramid_{name}")(self.handle, int(level), *args))
+
+    def _ndt_info(self, level):
+        out = (C.c_int64 * 4)()
+        self._ndt_level_call("info", level, out)
+        return int(out[0]), int(out[1]), int(out[2])
 
     # ---- NDT localiser, multi-resolution pyramid (include/sps_hip.h, "NDT localiser, multi-resolution pyramid") ----
     def ndt_pyramid_build(self, levels, xyz_ptr, n_map: int, min_points: int, eig_ratio: float, outlier_ratio: float,
@@ -550,33 +574,24 @@ class Context:
                                                 int(min_points), float(eig_ratio), float(outlier_ratio), caps, stream))
 
     # ---- NDT localiser, online pyramid (include/sps_hip.h, "NDT localiser, online pyramid") ----
-    def ndt_pyramid_update(self, pts_ptr, n_dev_ptr: int, cap: int, T_host, T_dev_ptr, gate_ptr, max_cell_points: int,
-                           info_ptr: int, scratch_ptr: int, stream: int):
-        """info_ptr: int32[n_levels][4]"""
-        check(lib.sps_ndt_pyramid_update(self.handle, pts_ptr, n_dev_ptr, int(cap), self._mat(T_host) if T_host is not None else None,
-                                         T_dev_ptr, gate_ptr, int(max_cell_points), info_ptr, scratch_ptr, stream))
+    def ndt_pyramid_update(self, *args):
+        """the arguments of ``_ndt_update`` after ``pyramid``; info_ptr: int32[n_levels][4]"""
+        self._ndt_update(True, *args)
 
-    def ndt_pyramid_carve(self, pts_ptr, n_dev_ptr: int, cap: int, T_host, T_dev_ptr, gate_ptr, end_margins,
-                          through_sigma: float, min_pass: int, miss_frames: int, max_steps: int, info_ptr: int, scratch_ptr,
-                          stream: int):
-        """end_margins: one float per level; info_ptr: int32[n_levels][4]"""
-        em = (C.c_double * len(end_margins))(*[float(v) for v in end_margins])
-        check(lib.sps_ndt_pyramid_carve(self.handle, pts_ptr, n_dev_ptr, int(cap), self._mat(T_host) if T_host is not None else None,
-                                        T_dev_ptr, gate_ptr, em, float(through_sigma), int(min_pass), int(miss_frames),
-                                        int(max_steps), info_ptr, scratch_ptr, stream))
+    def ndt_pyramid_carve(self, *args):
+        """the arguments of ``_ndt_carve`` after ``pyramid``; end_margin: one float per level; info_ptr: int32[n_levels][4]"""
+        self._ndt_carve(True, *args)
 
     def ndt_pyramid_info(self, level: int):
         """(cells assigned, cell capacity, cells dropped for capacity since the build) of a level; synchronises"""
-        out = (C.c_int64 * 4)()
-        check(lib.sps_ndt_pyramid_info(self.handle, int(level), out))
-        return int(out[0]), int(out[1]), int(out[2])
+        return self._ndt_info(level)
 
     def ndt_pyramid_carve_cells(self, level: int, pass_ptr, hit_ptr, miss_ptr):
         """pass, hit and miss of every cell of a level's capacity into int32 device arrays (any may be None); synchronises"""
-        check(lib.sps_ndt_pyramid_carve_cells(self.handle, int(level), pass_ptr, hit_ptr, miss_ptr))
+        self._ndt_level_call("carve_cells", level, pass_ptr, hit_ptr, miss_ptr)
 
     def ndt_pyramid_cells(self, level: int, key_ptr, count_ptr, mean_ptr, icov_ptr, valid_ptr):
-        check(lib.sps_ndt_pyramid_cells(self.handle, int(level), key_ptr, count_ptr, mean_ptr, icov_ptr, valid_ptr))
+        self._ndt_level_call("cells", level, key_ptr, count_ptr, mean_ptr, icov_ptr, valid_ptr)
 
     def ndt_pyramid_align(self, pts_ptr, n_dev_ptr: int, cap: int, T_init, iters: int, level_iters, neighbours: int,
                           min_corr: int, tol_t: float, tol_r: float, T_out_ptr: int, status_ptr: int, trace_ptr, normal_ptr,

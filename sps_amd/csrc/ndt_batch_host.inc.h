@@ -31,13 +31,13 @@ int sps_ndt_align_batch(sps_ctx *c, const double *pts_dev, const int32_t *n_dev,
   if (iters > 0 && normal_dev) HIP_TRY(hipMemsetAsync(normal_dev, 0, (size_t)n_hyp * iters * 28 * sizeof(double), st));
   hipLaunchKernelGGL(k_loc_init_batch, dim3(n_hyp), dim3(64), 0, st, T_init_dev, n_hyp, T_out_dev, status_dev, done);
   for (int it = 0; it < iters; ++it) {
-    hipLaunchKernelGGL(k_ndt_assoc_batch, dim3(nb, n_hyp), dim3(256), 0, st, pts_dev, n_dev, (int)cap, c->ndt, gs, neighbours,
+    hipLaunchKernelGGL(k_ndt_assoc_batch, dim3(nb, n_hyp), dim3(256), 0, st, pts_dev, n_dev, (int)cap, c->ndt_map.lv[0].m, gs, neighbours,
                        n_hyp, (const double *)T_out_dev, (const int *)done, 0, partial);
     hipLaunchKernelGGL(k_loc_solve_batch, dim3(n_hyp), dim3(256), 0, st, (const double *)partial, nb, n_dev, (int)cap, it, iters,
                        min_corr, tol_t, tol_r, n_hyp, T_init_dev, T_out_dev, status_dev, done, trace_dev, normal_dev);
   }
   // every hypothesis once more at its final pose: the scores k_ndt_select chooses by
-  hipLaunchKernelGGL(k_ndt_assoc_batch, dim3(nb, n_hyp), dim3(256), 0, st, pts_dev, n_dev, (int)cap, c->ndt, gs, neighbours, n_hyp,
+  hipLaunchKernelGGL(k_ndt_assoc_batch, dim3(nb, n_hyp), dim3(256), 0, st, pts_dev, n_dev, (int)cap, c->ndt_map.lv[0].m, gs, neighbours, n_hyp,
                      (const double *)T_out_dev, (const int *)done, 1, partial);
   hipLaunchKernelGGL(k_ndt_select, dim3(1), dim3(256 * NDT_SELECT_GROUPS), 0, st, (const double *)partial, nb, n_dev, (int)cap,
                      n_hyp, min_corr, (const int *)status_dev, (const double *)T_out_dev, T_init_dev, final_dev, best_dev,

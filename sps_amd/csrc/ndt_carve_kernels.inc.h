@@ -1,5 +1,6 @@
 // ndt_carve_kernels.inc.h -- part of sps_hip.hip (included inside its anonymous namespace, after ndt_update_kernels.inc.h):
-// free-space carving of the online NDT map (host side: ndt_carve_host.inc.h; ABI: the "NDT localiser, online map: free-space
+// the bodies of the free-space carving of the online NDT map (their __global__ kernels, for the single map and the pyramid
+// alike: ndt_online_kernels.inc.h; host side: ndt_online_host.inc.h; ABI: the "NDT localiser, online map: free-space
 // carving" section of include/sps_hip.h).
 //
 //   k_ndt_carve_begin    (carve, 1)     the gate; pass = hit = 0 for every cell of the capacity, info = 0
@@ -25,8 +26,8 @@ __device__ inline void ndt_carve_count(int flag, int *word) {
   if (b && (threadIdx.x & 63) == 0) atomicAdd(word, __popcll(b));
 }
 
-// The bodies of the three kernels: one definition for the single map here and for the levels of the online pyramid
-// (ndt_pyramid_update_kernels.inc.h).  Every body indexes by blockIdx.x only; blockIdx.y is the caller's.
+// The bodies of the three kernels (ndt_online_kernels.inc.h).  Every body indexes by blockIdx.x only; blockIdx.y is the
+// caller's.
 
 // 1: one thread per cell of the capacity
 __device__ inline void ndt_carve_begin_body(const int *__restrict__ gate, const NdtDyn &d, int *__restrict__ info) {
@@ -35,9 +36,6 @@ __device__ inline void ndt_carve_begin_body(const int *__restrict__ gate, const 
   if (!ndt_upd_gate_open(gate) || c >= d.capacity) return;
   d.pass[c] = 0;
   d.hit[c] = 0;
-}
-__global__ __launch_bounds__(256) void k_ndt_carve_begin(const int *__restrict__ gate, NdtDyn d, int *__restrict__ info) {
-  ndt_carve_begin_body(gate, d, info);
 }
 
 // Does the ray o + s d come within the gate of the cell's Gaussian for some s in [s_in, s_out]?  The point of the line
@@ -138,12 +136,6 @@ __device__ inline void ndt_carve_rays_body(const double *__restrict__ pts, const
   ndt_carve_count(cast, &info[0]);
   ndt_carve_count(cut, &info[3]);
 }
-__global__ __launch_bounds__(256) void k_ndt_carve_rays(const double *__restrict__ pts, const int *__restrict__ n_dev, int cap,
-                                                         LocPose Th, const double *__restrict__ T_dev,
-                                                         const int *__restrict__ gate, NdtMap m, NdtDyn dy, NdtCarveParams p,
-                                                         int *__restrict__ info) {
-  ndt_carve_rays_body(pts, n_dev, cap, Th, T_dev, gate, m, dy, p, info);
-}
 
 // 3: one thread per cell of the capacity; the cells below the assigned count decide
 __device__ inline void ndt_carve_decide_body(const int *__restrict__ gate, const NdtDyn &d, const NdtCarveParams &p,
@@ -170,10 +162,6 @@ __device__ inline void ndt_carve_decide_body(const int *__restrict__ gate, const
   }
   ndt_carve_count(seen, &info[1]);
   ndt_carve_count(cleared, &info[2]);
-}
-__global__ __launch_bounds__(256) void k_ndt_carve_decide(const int *__restrict__ gate, NdtDyn d, NdtCarveParams p,
-                                                           int *__restrict__ info) {
-  ndt_carve_decide_body(gate, d, p, info);
 }
 
 #pragma clang fp contract(fast)

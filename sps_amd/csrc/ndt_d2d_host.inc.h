@@ -1,4 +1,4 @@
-// ndt_d2d_host.inc.h -- part of sps_hip.hip (included inside its extern "C" block, after ndt_update_host.inc.h): the entry
+// ndt_d2d_host.inc.h -- part of sps_hip.hip (included inside its extern "C" block, after ndt_online_host.inc.h): the entry
 // points of distribution-to-distribution NDT (ABI: the "NDT localiser, distribution to distribution" section of
 // include/sps_hip.h; kernels: ndt_d2d_kernels.inc.h).  Neither call allocates or synchronises: the scratch is the caller's.
 
@@ -114,7 +114,7 @@ int sps_ndt_align_d2d(sps_ctx *c, const double *src_dev, const int32_t *n_src_de
   if (iters > 0 && normal_dev) HIP_TRY(hipMemsetAsync(normal_dev, 0, (size_t)iters * 28 * sizeof(double), st));
   hipLaunchKernelGGL(k_loc_init, dim3(1), dim3(64), 0, st, T0, T_out_dev, status_dev, done);
   for (int it = 0; it < iters; ++it) {
-    hipLaunchKernelGGL(k_ndt_d2d_assoc, dim3(nb), dim3(256), 0, st, src_dev, n_src_dev, (int)cap_src, c->ndt, gs, neighbours,
+    hipLaunchKernelGGL(k_ndt_d2d_assoc, dim3(nb), dim3(256), 0, st, src_dev, n_src_dev, (int)cap_src, c->ndt_map.lv[0].m, gs, neighbours,
                        (const double *)T_out_dev, (const int *)done, partial);
     hipLaunchKernelGGL(k_loc_solve, dim3(1), dim3(256), 0, st, (const double *)partial, n_src_dev, (int)cap_src, it, min_corr,
                        tol_t, tol_r, T0, T_out_dev, status_dev, done, trace_dev, normal_dev);

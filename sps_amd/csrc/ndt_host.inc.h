@@ -1,8 +1,9 @@
 // ndt_host.inc.h -- part of sps_hip.hip (included inside its extern "C" block): the entry points of the NDT localiser
 // (ABI: the "NDT localiser" section of include/sps_hip.h; kernels: ndt_kernels.inc.h).  sps_ndt_map_build allocates and
-// synchronises, like sps_radius_grid_upload; sps_ndt_align does neither: its scratch is the caller's.  Two helpers here
-// serve the later NDT files too: ndt_map_build_impl (the static and the dynamic build; ndt_map_make under it also builds the
-// levels of a pyramid) and ndt_check_scan_args (the checks that the alignment, the batch and the pose score share).
+// synchronises, like sps_radius_grid_upload; sps_ndt_align does neither: its scratch is the caller's.  The single map of a
+// context is a pyramid of one level (sps_ctx::ndt_map), so three helpers here serve the single map and the pyramid alike
+// and the later NDT files too: ndt_build_impl (every build: static or dynamic, one level or several), ndt_cells_impl (both
+// cell getters) and ndt_check_scan_args (the checks that the alignment, the batch and the pose score share).
 
 namespace {
 // the Gaussian fit of the mixture (Magnusson 2009, eq. 6.8; PCL's gauss_d1_ / gauss_d2_), in float64 on the host; false
@@ -33,12 +34,13 @@ inline int ndt_check_scan_limits(int neighbours, int64_t cap, bool aligns, int i
 }
 inline int ndt_check_scan_args(const sps_ctx *c, int neighbours, int64_t cap, double outlier_ratio, NdtGauss &gs, bool aligns,
                                int iters = 0, double tol_t = 0.0, double tol_r = 0.0) {
-  if (!c->ndt.h.keys) return fail(SPS_ERR_INVALID, "sps_ndt_map_build has not been called");
+  if (c->ndt_map.n_levels < 1) return fail(SPS_ERR_INVALID, "sps_ndt_map_build has not been called");
   if (int e = ndt_check_scan_limits(neighbours, cap, aligns, iters, tol_t, tol_r)) return e;
-  return ndt_gauss_fit(c->ndt.resolution, outlier_ratio, gs) ? SPS_OK : SPS_ERR_INVALID;
+  return ndt_gauss_fit(c->ndt_map.lv[0].m.resolution, outlier_ratio, gs) ? SPS_OK : SPS_ERR_INVALID;
 }
 
 inline int64_t ndt_hash_slots(int64_t cells) { return next_pow2(2 * (cells < 512 ? 512 : cells)); }
+inline size_t ndt_upd_align(size_t v) { return (v + 255) & ~(size_t)255; }   // of the arrays cut from a caller's scratch
 
 // what every map build asks of its arguments (cell_capacity is read for a dynamic map only)
 inline int ndt_map_check_args(const sps_ctx *c, const uint64_t *cell_keys_dev, const int32_t *cell_start_dev,
@@ -118,31 +120,76 @@ int ndt_map_make(std::vector<void *> &allocs, const uint64_t *cell_keys_dev, con
   return SPS_OK;
 }
 
-// The map of the context, static (room for the n_cells of the build; cell_capacity is not read) or dynamic (room for
-// cell_capacity cells, their moments S and the update's per-cell state beside the records).  Either replaces whatever map
-// the context had.  Allocates and synchronises.
-int ndt_map_build_impl(sps_ctx *c, const uint64_t *cell_keys_dev, const int32_t *cell_start_dev, const int32_t *cell_pts_dev,
-                       const double *map_xyz_dev, int64_t n_cells, int64_t n_map, double resolution, int min_points,
-                       double eig_ratio, bool dynamic, int64_t cell_capacity, void *stream) {
-  if (int e = ndt_map_check_args(c, cell_keys_dev, cell_start_dev, cell_pts_dev, map_xyz_dev, n_cells, n_map, resolution,
-                                 min_points, eig_ratio, dynamic, cell_capacity))
-    return e;
+// One of the two pyramids of the context (`slot`: the single map, n_levels == 1, or the pyramid), static (cell_capacity ==
+// nullptr: level l has room for the n_cells[l] of the build) or dynamic (room for cell_capacity[l] cells, their moments S,
+// the update's per-cell state and the carve's counters beside the records).  outlier_ratio: of the levels' Gaussian fits;
+// nullptr for the single map, whose alignments take the ratio per call, so its gs stays zero and nothing reads it.  Replaces
+// whatever that slot held and leaves the other slot alone.  Allocates and synchronises.
+int ndt_build_impl(sps_ctx *c, NdtPyramid sps_ctx::*slot, int n_levels, const uint64_t *const *cell_keys_dev,
+                   const int32_t *const *cell_start_dev, const int32_t *const *cell_pts_dev, const int64_t *n_cells,
+                   const double *resolution, const double *map_xyz_dev, int64_t n_map, int min_points, double eig_ratio,
+                   const double *outlier_ratio, const int64_t *cell_capacity, void *stream) {
+  const bool dynamic = cell_capacity != nullptr;
+  if (!c || !cell_keys_dev || !cell_start_dev || !cell_pts_dev || !n_cells || !resolution) return fail(SPS_ERR_INVALID, "bad arguments");
+  if (n_levels < 1 || n_levels > NDT_PYR_MAX) return fail(SPS_ERR_INVALID, "n_levels must be in [1, %d]", NDT_PYR_MAX);
+  NdtGauss gs[NDT_PYR_MAX]{};
+  for (int l = 0; l < n_levels; ++l) {
+    if (int e = ndt_map_check_args(c, cell_keys_dev[l], cell_start_dev[l], cell_pts_dev[l], map_xyz_dev, n_cells[l], n_map,
+                                   resolution[l], min_points, eig_ratio, dynamic, dynamic ? cell_capacity[l] : 0))
+      return e;
+    if (l > 0 && !(resolution[l] < resolution[l - 1])) return fail(SPS_ERR_INVALID, "resolutions must be strictly decreasing");
+    if (outlier_ratio && !ndt_gauss_fit(resolution[l], *outlier_ratio, gs[l])) return SPS_ERR_INVALID;
+  }
   HIP_TRY(hipSetDevice(c->device));
   hipStream_t st = (hipStream_t)stream;
   HIP_TRY(hipDeviceSynchronize());
-  for (void *p : c->ndt_allocs) (void)hipFree(p);
-  c->ndt_allocs.clear();
-  c->ndt = NdtMap{};
-  c->ndt_dyn = NdtDyn{};
-  NdtMap m{};
-  NdtDyn d{};
-  int32_t state0[4];
-  if (int e = ndt_map_make(c->ndt_allocs, cell_keys_dev, cell_start_dev, cell_pts_dev, map_xyz_dev, n_cells, n_map, resolution,
-                           min_points, eig_ratio, dynamic, cell_capacity, st, state0, m, d))
-    return e;
-  HIP_TRY(hipStreamSynchronize(st));   // state0 is on this frame
-  c->ndt = m;
-  if (dynamic) c->ndt_dyn = d;
+  NdtPyramid &py = c->*slot;
+  for (void *p : py.allocs) (void)hipFree(p);
+  py = NdtPyramid{};
+  NdtPyrLevel lv[NDT_PYR_MAX]{};
+  NdtDyn dy[NDT_PYR_MAX]{};
+  int32_t state0[NDT_PYR_MAX][4];   // read by copies in flight until the synchronisation below; a static map copies none
+  for (int l = 0; l < n_levels; ++l) {
+    if (int e = ndt_map_make(py.allocs, cell_keys_dev[l], cell_start_dev[l], cell_pts_dev[l], map_xyz_dev, n_cells[l], n_map,
+                             resolution[l], min_points, eig_ratio, dynamic, dynamic ? cell_capacity[l] : 0, st, state0[l],
+                             lv[l].m, dy[l]))
+      return e;
+    lv[l].gs = gs[l];
+  }
+  NdtPyrLevel *dev = nullptr;
+  if (hipMalloc((void **)&dev, sizeof(lv)) != hipSuccess) return fail(SPS_ERR_NOMEM, "hipMalloc for the NDT pyramid failed");
+  py.allocs.push_back(dev);
+  HIP_TRY(hipMemcpyAsync(dev, lv, sizeof(lv), hipMemcpyHostToDevice, st));
+  NdtDyn *dyn_dev = nullptr;
+  if (dynamic) {
+    if (hipMalloc((void **)&dyn_dev, sizeof(dy)) != hipSuccess) return fail(SPS_ERR_NOMEM, "hipMalloc for the NDT pyramid failed");
+    py.allocs.push_back(dyn_dev);
+    HIP_TRY(hipMemcpyAsync(dyn_dev, dy, sizeof(dy), hipMemcpyHostToDevice, st));
+  }
+  HIP_TRY(hipStreamSynchronize(st));   // lv, dy and state0 are on this frame
+  for (int l = 0; l < n_levels; ++l) py.lv[l] = lv[l], py.dyn[l] = dy[l];
+  py.dev = dev;
+  py.dynamic = dynamic;
+  py.dyn_dev = dyn_dev;
+  py.n_levels = n_levels;
+  return SPS_OK;
+}
+
+// the records of level `level` of a pyramid; not_built: the error text of a slot that holds none
+int ndt_cells_impl(sps_ctx *c, NdtPyramid sps_ctx::*slot, const char *not_built, int level, uint64_t *key_out_dev,
+                   int32_t *count_out_dev, double *mean_out_dev, double *icov_out_dev, int32_t *valid_out_dev) {
+  if (!c) return fail(SPS_ERR_INVALID, "ctx is null");
+  const NdtPyramid &py = c->*slot;
+  if (py.n_levels < 1) return fail(SPS_ERR_INVALID, "%s", not_built);
+  if (level < 0 || level >= py.n_levels) return fail(SPS_ERR_INVALID, "level must be in [0, %d)", py.n_levels);
+  HIP_TRY(hipSetDevice(c->device));
+  HIP_TRY(hipDeviceSynchronize());
+  const NdtMap &m = py.lv[level].m;
+  if (m.n_cells > 0)
+    hipLaunchKernelGGL(k_ndt_cells_get, dim3((unsigned)((m.n_cells + 255) / 256)), dim3(256), 0, 0, m,
+                       (unsigned long long *)key_out_dev, count_out_dev, mean_out_dev, icov_out_dev, valid_out_dev);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipDeviceSynchronize());
   return SPS_OK;
 }
 }  // namespace
@@ -152,22 +199,14 @@ int64_t sps_ndt_align_scratch(int64_t cap) { return sps_loc_align_scratch(cap); 
 int sps_ndt_map_build(sps_ctx *c, const uint64_t *cell_keys_dev, const int32_t *cell_start_dev, const int32_t *cell_pts_dev,
                       const double *map_xyz_dev, int64_t n_cells, int64_t n_map, double resolution, int min_points,
                       double eig_ratio, void *stream) {
-  return ndt_map_build_impl(c, cell_keys_dev, cell_start_dev, cell_pts_dev, map_xyz_dev, n_cells, n_map, resolution, min_points,
-                            eig_ratio, false, 0, stream);
+  return ndt_build_impl(c, &sps_ctx::ndt_map, 1, &cell_keys_dev, &cell_start_dev, &cell_pts_dev, &n_cells, &resolution,
+                        map_xyz_dev, n_map, min_points, eig_ratio, nullptr, nullptr, stream);
 }
 
 int sps_ndt_map_cells(sps_ctx *c, uint64_t *key_out_dev, int32_t *count_out_dev, double *mean_out_dev, double *icov_out_dev,
                       int32_t *valid_out_dev) {
-  if (!c) return fail(SPS_ERR_INVALID, "ctx is null");
-  if (!c->ndt.h.keys) return fail(SPS_ERR_INVALID, "sps_ndt_map_build has not been called");
-  HIP_TRY(hipSetDevice(c->device));
-  HIP_TRY(hipDeviceSynchronize());
-  if (c->ndt.n_cells > 0)
-    hipLaunchKernelGGL(k_ndt_cells_get, dim3((unsigned)((c->ndt.n_cells + 255) / 256)), dim3(256), 0, 0, c->ndt,
-                       (unsigned long long *)key_out_dev, count_out_dev, mean_out_dev, icov_out_dev, valid_out_dev);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipDeviceSynchronize());
-  return SPS_OK;
+  return ndt_cells_impl(c, &sps_ctx::ndt_map, "sps_ndt_map_build has not been called", 0, key_out_dev, count_out_dev,
+                        mean_out_dev, icov_out_dev, valid_out_dev);
 }
 
 int sps_ndt_align(sps_ctx *c, const double *pts_dev, const int32_t *n_dev, int64_t cap, const double *T_init_host, int iters,
@@ -189,7 +228,7 @@ int sps_ndt_align(sps_ctx *c, const double *pts_dev, const int32_t *n_dev, int64
   if (iters > 0 && normal_dev) HIP_TRY(hipMemsetAsync(normal_dev, 0, (size_t)iters * 28 * sizeof(double), st));
   hipLaunchKernelGGL(k_loc_init, dim3(1), dim3(64), 0, st, T0, T_out_dev, status_dev, done);
   for (int it = 0; it < iters; ++it) {
-    hipLaunchKernelGGL(k_ndt_assoc, dim3(nb), dim3(256), 0, st, pts_dev, n_dev, (int)cap, c->ndt, gs, neighbours,
+    hipLaunchKernelGGL(k_ndt_assoc, dim3(nb), dim3(256), 0, st, pts_dev, n_dev, (int)cap, c->ndt_map.lv[0].m, gs, neighbours,
                        (const double *)T_out_dev, (const int *)done, partial);
     hipLaunchKernelGGL(k_loc_solve, dim3(1), dim3(256), 0, st, (const double *)partial, n_dev, (int)cap, it, min_corr, tol_t,
                        tol_r, T0, T_out_dev, status_dev, done, trace_dev, normal_dev);

@@ -1,5 +1,5 @@
 // ndt_pyramid_batch_host.inc.h -- part of sps_hip.hip (included inside its extern "C" block, after
-// ndt_pyramid_update_host.inc.h): the coarse-to-fine NDT alignment from several start poses at once (ABI: the "NDT
+// ndt_pyramid_host.inc.h): the coarse-to-fine NDT alignment from several start poses at once (ABI: the "NDT
 // localiser, pyramid, several hypotheses" section of include/sps_hip.h; kernels: ndt_pyramid_batch_kernels.inc.h, and
 // k_ndt_assoc_batch / k_ndt_select of ndt_batch_kernels.inc.h for the final pass and the selection).  Like
 // sps_ndt_pyramid_align the call neither allocates nor synchronises.

@@ -1,5 +1,5 @@
 // ndt_pyramid_kernels.inc.h -- part of sps_hip.hip (included inside its anonymous namespace, after ndt_update_kernels.inc.h):
-// the NDT localiser registering coarse to fine over a pyramid of cell maps, static or (ndt_pyramid_update_kernels.inc.h)
+// the NDT localiser registering coarse to fine over a pyramid of cell maps, static or (ndt_online_kernels.inc.h)
 // dynamic (host side: ndt_pyramid_host.inc.h; ABI: the "NDT localiser, multi-resolution pyramid" section of include/sps_hip.h).
 //
 //   k_ndt_pyr_init    T_out = T_init, status = (1, 0, 0, 0), the state words 0, level[s] = -1, trace and normal rows 0
@@ -29,13 +29,15 @@ struct NdtPyrCaps {
   int v[NDT_PYR_MAX];      // level_iters: the most slots a level may use
 };
 
-// the pyramid of a context (sps_ndt_pyramid_build, sps_ndt_pyramid_build_dynamic): the levels on the host, for the getters,
-// and their device copy; a dynamic pyramid also has every level's NdtDyn, in a device array beside the levels'
+// A pyramid of a context: the levels on the host, for the getters and the by-value kernels, and their device copy; a
+// dynamic pyramid also has every level's NdtDyn, in a device array beside the levels'.  A context has two (sps_ctx): the
+// single map of sps_ndt_map_build[_dynamic], one level whose gs is not set, and that of sps_ndt_pyramid_build[_dynamic].
 struct NdtPyramid {
   int n_levels = 0;        // 0: none built
+  std::vector<void *> allocs;         // the device memory of the levels and of the two arrays below, owned
   NdtPyrLevel lv[NDT_PYR_MAX]{};
   const NdtPyrLevel *dev = nullptr;   // [NDT_PYR_MAX]
-  bool dynamic = false;    // built by sps_ndt_pyramid_build_dynamic
+  bool dynamic = false;    // built by a *_build_dynamic
   NdtDyn dyn[NDT_PYR_MAX]{};
   const NdtDyn *dyn_dev = nullptr;    // [NDT_PYR_MAX], dynamic only
 };

@@ -34,7 +34,7 @@ int sps_ndt_score_poses(sps_ctx *c, const double *pts_dev, const int32_t *n_dev,
   for (int64_t p0 = 0; p0 < n_pose; p0 += chunk) {      // chunks follow one another on the stream and share the scratch
     const int np = (int)std::min(chunk, n_pose - p0);
     hipLaunchKernelGGL(k_ndt_score, dim3(nb, (np + NDT_SCORE_TILE - 1) / NDT_SCORE_TILE), dim3(256), 0, st, pts_dev, n_dev,
-                       (int)cap, c->ndt, gs, neighbours, T_dev + p0 * 16, np, partial);
+                       (int)cap, c->ndt_map.lv[0].m, gs, neighbours, T_dev + p0 * 16, np, partial);
     hipLaunchKernelGGL(k_ndt_score_reduce, dim3((np + NDT_REDUCE_POSES - 1) / NDT_REDUCE_POSES), dim3(256), 0, st,
                        (const double *)partial, nb, n_dev, (int)cap, np, score_dev + p0 * 2);
   }

@@ -1,6 +1,7 @@
 // ndt_update_kernels.inc.h -- part of sps_hip.hip (included inside its anonymous namespace, after ndt_search_kernels.inc.h):
-// the online NDT map (host side: ndt_update_host.inc.h; ABI: the "NDT localiser, online map" section of include/sps_hip.h;
-// DESIGN.md 8f).
+// the bodies of the online NDT map's update (their __global__ kernels, for the single map and the pyramid alike:
+// ndt_online_kernels.inc.h; host side: ndt_online_host.inc.h; ABI: the "NDT localiser, online map" section of
+// include/sps_hip.h).  The d2d source build (ndt_d2d_kernels.inc.h) calls some of them too.
 //
 //   (dynamic build: k_ndt_cells of ndt_kernels.inc.h with its S_out set, S = sum (p - mean)(p - mean)^T beside the record)
 //   k_ndt_upd_lookup    (update, 1)      q = R p + t (loc_transform), the cell of q (ndt_cell_key) in the map's hash; misses
@@ -79,9 +80,8 @@ __device__ inline int ndt_upd_scan(int v, int *lds, int &total) {
   return off + inc - v;
 }
 
-// The bodies of the seven kernels: one definition for the single map here and for the levels of the online pyramid
-// (ndt_pyramid_update_kernels.inc.h), which passes a level's map, state, scratch slice and info words.  Every body indexes
-// by blockIdx.x / gridDim.x only; blockIdx.y is the caller's.
+// The bodies of the seven kernels.  A kernel of ndt_online_kernels.inc.h passes a level's map, state, scratch slice and info
+// words.  Every body indexes by blockIdx.x / gridDim.x only; blockIdx.y is the caller's.
 
 // 1: one thread per point.  store_q: q goes to s.q (it does not depend on the map: of several levels that share s.q one stores)
 __device__ inline void ndt_upd_lookup_body(const double *__restrict__ pts, const int *__restrict__ n_dev, int cap,
@@ -114,11 +114,6 @@ __device__ inline void ndt_upd_lookup_body(const double *__restrict__ pts, const
   s.cell_of[i] = cell;
   s.slot_of[i] = slot;
 }
-__global__ __launch_bounds__(256) void k_ndt_upd_lookup(const double *__restrict__ pts, const int *__restrict__ n_dev, int cap,
-                                                         LocPose Th, const double *__restrict__ T_dev,
-                                                         const int *__restrict__ gate, NdtMap m, NdtUpdScratch s) {
-  ndt_upd_lookup_body(pts, n_dev, cap, Th, T_dev, gate, m, s, true);
-}
 
 // 2: one workgroup.  A founder is the lowest point index of a missed key; founder r (ascending index) gets the cell id
 // assigned + r while that is below the capacity.  Writes info[0..2], the cell counter and the dropped total.
@@ -148,12 +143,6 @@ __device__ inline void ndt_upd_found_body(const int *__restrict__ n_dev, int cap
     info[0] = n0 + founded, info[1] = founded, info[2] = base - founded;
   }
 }
-__global__ __launch_bounds__(NDT_UPD_BLOCK) void k_ndt_upd_found(const int *__restrict__ n_dev, int cap,
-                                                                  const int *__restrict__ gate, NdtDyn d, NdtUpdScratch s,
-                                                                  int *__restrict__ info) {
-  __shared__ int lds[NDT_UPD_BLOCK / 64];
-  ndt_upd_found_body(n_dev, cap, gate, d, s, info, lds);
-}
 
 // 3: one thread per point
 __device__ inline void ndt_upd_resolve_body(const int *__restrict__ n_dev, int cap, const int *__restrict__ gate,
@@ -179,10 +168,6 @@ __device__ inline void ndt_upd_resolve_body(const int *__restrict__ n_dev, int c
     atomicAdd(&d.bcnt[cell], 1);
     atomicMin(&d.lead[cell], i);
   }
-}
-__global__ __launch_bounds__(256) void k_ndt_upd_resolve(const int *__restrict__ n_dev, int cap, const int *__restrict__ gate,
-                                                          NdtMap m, NdtDyn d, NdtUpdScratch s) {
-  ndt_upd_resolve_body(n_dev, cap, gate, m, d, s);
 }
 
 // 4: one workgroup.  The touched cells in ascending order of their lowest point, the offsets of their lists, info[3].
@@ -214,12 +199,6 @@ __device__ inline void ndt_upd_offsets_body(const int *__restrict__ n_dev, int c
     info[3] = base;
   }
 }
-__global__ __launch_bounds__(NDT_UPD_BLOCK) void k_ndt_upd_offsets(const int *__restrict__ n_dev, int cap,
-                                                                    const int *__restrict__ gate, NdtDyn d, NdtUpdScratch s,
-                                                                    int *__restrict__ info) {
-  __shared__ int lds[NDT_UPD_BLOCK / 64];
-  ndt_upd_offsets_body(n_dev, cap, gate, d, s, info, lds);
-}
 
 // 5: one thread per point
 __device__ inline void ndt_upd_fill_body(const int *__restrict__ n_dev, int cap, const int *__restrict__ gate, const NdtDyn &d,
@@ -232,10 +211,6 @@ __device__ inline void ndt_upd_fill_body(const int *__restrict__ n_dev, int cap,
   if (cell < 0) return;
   const int pos = d.cstart[cell] + atomicAdd(&d.bcnt[cell], 1);
   if (pos >= 0 && pos < cap) s.list[pos] = i;
-}
-__global__ __launch_bounds__(256) void k_ndt_upd_fill(const int *__restrict__ n_dev, int cap, const int *__restrict__ gate,
-                                                       NdtDyn d, NdtUpdScratch s) {
-  ndt_upd_fill_body(n_dev, cap, gate, d, s);
 }
 
 // lane l's point of a chunk of m <= 64 entries of the ordered list that starts at entry `at` (zeros for l >= m)
@@ -322,11 +297,6 @@ __device__ inline void ndt_upd_stats_body(const int *__restrict__ n_dev, int cap
     __syncthreads();   // the bitmap is cleared for the next cell only after every lane has read it
   }
 }
-__global__ __launch_bounds__(64) void k_ndt_upd_stats(const int *__restrict__ n_dev, int cap, const int *__restrict__ gate,
-                                                       NdtDyn d, NdtUpdScratch s) {
-  __shared__ unsigned bits[NDT_UPD_MAX_POINTS / 32];
-  ndt_upd_stats_body(n_dev, cap, gate, d, s, bits);
-}
 
 // 7: one thread per touched cell: forgetting, merge, the record; the cell's update counters go back to their rest values.
 __device__ inline void ndt_upd_merge_body(const int *__restrict__ n_dev, int cap, const int *__restrict__ gate,
@@ -369,10 +339,6 @@ __device__ inline void ndt_upd_merge_body(const int *__restrict__ n_dev, int cap
   for (int i = 0; i < 6; ++i) Sg[i] = S[i];
   ndt_record_from_moments(n2, mu, S, d.min_points, d.eig_ratio, rec);
   d.count[cell] = n2;
-}
-__global__ __launch_bounds__(256) void k_ndt_upd_merge(const int *__restrict__ n_dev, int cap, const int *__restrict__ gate,
-                                                        int max_cell_points, NdtDyn d, NdtUpdScratch s) {
-  ndt_upd_merge_body(n_dev, cap, gate, max_cell_points, d, s);
 }
 
 #pragma clang fp contract(fast)

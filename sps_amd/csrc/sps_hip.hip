@@ -155,7 +155,7 @@ int fail(int code, const char *fmt, ...) {
 #include "ndt_d2d_kernels.inc.h"
 #include "ndt_carve_kernels.inc.h"
 #include "ndt_pyramid_kernels.inc.h"
-#include "ndt_pyramid_update_kernels.inc.h"
+#include "ndt_online_kernels.inc.h"
 #include "ndt_pyramid_batch_kernels.inc.h"
 #include "ukf_kernels.inc.h"
 
@@ -300,13 +300,10 @@ struct sps_ctx {
   // variant-A radius grid (device copies owned by the ctx)
   RadiusGrid rg{};
   std::vector<void *> rg_allocs;
-  // NDT localiser map (sps_ndt_map_build): cell hash + one 80-byte record per cell, owned by the ctx
-  NdtMap ndt{};
-  std::vector<void *> ndt_allocs;
-  NdtDyn ndt_dyn{};                      // capacity > 0: the map is dynamic (sps_ndt_map_build_dynamic)
+  // NDT localiser map (sps_ndt_map_build, sps_ndt_map_build_dynamic): a pyramid of one level, lv[0].m is the map
+  NdtPyramid ndt_map{};
   // NDT pyramid (sps_ndt_pyramid_build, sps_ndt_pyramid_build_dynamic): maps of its own beside the one above, coarse to fine
   NdtPyramid ndt_pyr{};
-  std::vector<void *> ndt_pyr_allocs;
   // variant-A item scratch (sps_radius_item): per (scan point, neighbour cell) hit counts and their prefix sums
   int *item_counts = nullptr, *item_offsets = nullptr, *item_bsum = nullptr, *item_base = nullptr;
   int64_t item_cap = 0;
@@ -1076,8 +1073,8 @@ int sps_ctx_destroy(sps_ctx *c) {
   c->weights.reset();
   if (c->map_keys_alloc) (void)hipFree(c->map_keys_alloc);
   for (void *p : c->rg_allocs) (void)hipFree(p);
-  for (void *p : c->ndt_allocs) (void)hipFree(p);
-  for (void *p : c->ndt_pyr_allocs) (void)hipFree(p);
+  for (void *p : c->ndt_map.allocs) (void)hipFree(p);
+  for (void *p : c->ndt_pyr.allocs) (void)hipFree(p);
   for (void *p : {(void *)c->item_counts, (void *)c->item_offsets, (void *)c->item_bsum, (void *)c->item_base}) (void)hipFree(p);
   delete c;
   return SPS_OK;
@@ -2230,11 +2227,9 @@ int sps_get_feature(sps_ctx *c, const char *name, float *out_dev, int64_t *rows,
 #include "ndt_host.inc.h"
 #include "ndt_batch_host.inc.h"
 #include "ndt_search_host.inc.h"
-#include "ndt_update_host.inc.h"
+#include "ndt_online_host.inc.h"
 #include "ndt_d2d_host.inc.h"
-#include "ndt_carve_host.inc.h"
 #include "ndt_pyramid_host.inc.h"
-#include "ndt_pyramid_update_host.inc.h"
 #include "ndt_pyramid_batch_host.inc.h"
 #include "ukf_host.inc.h"
 

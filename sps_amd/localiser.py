@@ -696,8 +696,8 @@ class NDTLocaliser(ScanToMapLocaliser):
             self.level_cells = tuple(lv[3] for lv in levels)
             self.ctx.ndt_pyramid_build(levels, xyz.data_ptr() if self.n_map else None, self.n_map, self.min_points_per_cell,
                                        self.eig_ratio, self.outlier_ratio, self.stream.cuda_stream, self.level_capacities)
-            if self.level_capacities is not None:
-                self._pyr_update_scratch = torch.empty(
+            if self.level_capacities is not None:                # excludes cell_capacity: a localiser has one online map
+                self._update_scratch = torch.empty(
                     _native.lib.sps_ndt_pyramid_update_scratch(self.capacity, len(self.resolutions)), dtype=torch.uint8,
                     device=self.device)
             self._pyr_scratch = torch.empty(_native.lib.sps_ndt_pyramid_align_scratch(self.capacity), dtype=torch.uint8,
@@ -812,21 +812,15 @@ class NDTLocaliser(ScanToMapLocaliser):
             cnt = self._src_count[:C].cpu().numpy()
         return dict(mean=rec[:, 0:3].copy(), cov=rec[:, 3:9].copy(), count=cnt, valid=rec[:, 9] != 0.0)
 
+    # the online map or, with level_capacities, every level of the online pyramid (then info_ptr: int32[L][4])
     def _update(self, n_ptr, T_host, T_dev_ptr, gate_ptr, max_cell_points, info_ptr, s):
-        if self.level_capacities is not None:                        # every level, info_ptr: int32[L][4]
-            self.ctx.ndt_pyramid_update(self._pts.data_ptr(), n_ptr, self.capacity, T_host, T_dev_ptr, gate_ptr, max_cell_points,
-                                        info_ptr, self._pyr_update_scratch.data_ptr(), s)
-            return
-        self.ctx.ndt_map_update(self._pts.data_ptr(), n_ptr, self.capacity, T_host, T_dev_ptr, gate_ptr, max_cell_points,
-                                info_ptr, self._update_scratch.data_ptr(), s)
+        self.ctx._ndt_update(self.level_capacities is not None, self._pts.data_ptr(), n_ptr, self.capacity, T_host, T_dev_ptr,
+                             gate_ptr, max_cell_points, info_ptr, self._update_scratch.data_ptr(), s)
 
     def _carve(self, n_ptr, T_host, T_dev_ptr, gate_ptr, o, info_ptr, s):
-        if self.level_capacities is not None:                        # every level, info_ptr: int32[L][4]
-            self.ctx.ndt_pyramid_carve(self._pts.data_ptr(), n_ptr, self.capacity, T_host, T_dev_ptr, gate_ptr, o["end_margin"],
-                                       o["through_sigma"], o["min_pass"], o["miss_frames"], o["max_steps"], info_ptr, None, s)
-            return
-        self.ctx.ndt_map_carve(self._pts.data_ptr(), n_ptr, self.capacity, T_host, T_dev_ptr, gate_ptr, o["end_margin"],
-                               o["through_sigma"], o["min_pass"], o["miss_frames"], o["max_steps"], info_ptr, None, s)
+        self.ctx._ndt_carve(self.level_capacities is not None, self._pts.data_ptr(), n_ptr, self.capacity, T_host, T_dev_ptr,
+                            gate_ptr, o["end_margin"], o["through_sigma"], o["min_pass"], o["miss_frames"], o["max_steps"],
+                            info_ptr, None, s)
 
     @torch.no_grad()
     def carve(self, rows, count, T, end_margin=None, through_sigma: float = 1.0, min_pass: int = 2, miss_frames: int = 3,
@@ -865,17 +859,13 @@ class NDTLocaliser(ScanToMapLocaliser):
         ``pyramid_cells(level)``.  Synchronises."""
         if level is not None:
             level = self._checked_online_level(level)
-            return self._read_carve_cells(self.level_capacities[level], self.ctx.ndt_pyramid_carve_cells, self.ctx.ndt_pyramid_info,
-                                          level)
-        self._check_carve(True, single_map=True)
-        return self._read_carve_cells(self.cell_capacity, self.ctx.ndt_map_carve_cells, self.ctx.ndt_map_info)
-
-    def _read_carve_cells(self, C, read, info, *level):
-        """``read([level,] pass, hit, miss)`` of an online map of capacity C, of which ``info([level])[0]`` cells are assigned"""
+        else:
+            self._check_carve(True, single_map=True)
+        C = self.cell_capacity if level is None else self.level_capacities[level]
         with torch.cuda.device(self.device):
             out = torch.zeros((3, C), dtype=torch.int32, device=self.device)
-            read(*level, out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr())
-        n = info(*level)[0]
+            self.ctx._ndt_level_call("carve_cells", level, out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr())
+        n = self.ctx._ndt_info(level)[0]
         h = out.cpu().numpy()
         return h[0, :n].copy(), h[1, :n].copy(), h[2, :n].copy()
 
@@ -893,7 +883,7 @@ class NDTLocaliser(ScanToMapLocaliser):
     def map_info(self):
         """Debug: (cells assigned, cell capacity, cells dropped for capacity since the build) of the online map; synchronises."""
         self._check_integrate(True, single_map=True)
-        return self.ctx.ndt_map_info()
+        return self.ctx._ndt_info(None)
 
     def _checked_online_level(self, level):
         if self.level_capacities is None:
@@ -905,7 +895,7 @@ class NDTLocaliser(ScanToMapLocaliser):
     def pyramid_info(self, level: int):
         """Debug: ``map_info()`` of level ``level`` of an online pyramid (0: the coarsest); synchronises."""
         level = self._checked_online_level(level)
-        return self.ctx.ndt_pyramid_info(level)
+        return self.ctx._ndt_info(level)
 
     @torch.no_grad()
     def submit_batch(self, rows, count, T_inits, with_normal: bool = False, iterations: int = None, integrate: bool = False,
@@ -1082,21 +1072,22 @@ class NDTLocaliser(ScanToMapLocaliser):
         valid bool [C]) of the device map, in ascending key order, as numpy arrays.  An online map gives its assigned
         cells in the order of their ids: the cells of the build in ascending key order, then the founded cells in the order
         they were founded."""
-        if self.cell_capacity is None:
-            return self._read_cells(self.n_cells, self.ctx.ndt_map_cells)
-        return self._read_cells(self.cell_capacity, self.ctx.ndt_map_cells, self.ctx.ndt_map_info)
+        return self._read_cells(None, self.n_cells, self.cell_capacity)
 
-    def _read_cells(self, C, read, info=None, *level):
-        """``read([level,] key, count, mean, icov, valid)`` of a map of up to C cells -> what ``map_cells`` gives; ``info``: of
-        an online map, whose ``info([level])[0]`` cells are assigned"""
+    def _read_cells(self, level, n_cells, capacity):
+        """what ``map_cells`` gives, of the single map (``level`` None) or of a level of the pyramid: a static map
+        (``capacity`` None) has ``n_cells`` cells, an online one room for ``capacity``, of which its info tells how many are
+        assigned"""
+        C = n_cells if capacity is None else capacity
         with torch.cuda.device(self.device):
             key = torch.zeros(C, dtype=torch.int64, device=self.device)
             cnt = torch.zeros(C, dtype=torch.int32, device=self.device)
             mean = torch.zeros((C, 3), dtype=torch.float64, device=self.device)
             icov = torch.zeros((C, 6), dtype=torch.float64, device=self.device)
             valid = torch.zeros(C, dtype=torch.int32, device=self.device)
-            read(*level, key.data_ptr(), cnt.data_ptr(), mean.data_ptr(), icov.data_ptr(), valid.data_ptr())
-        n = C if info is None else info(*level)[0]
+            self.ctx._ndt_level_call("cells", level, key.data_ptr(), cnt.data_ptr(), mean.data_ptr(), icov.data_ptr(),
+                                     valid.data_ptr())
+        n = C if capacity is None else self.ctx._ndt_info(level)[0]
         return (key.cpu().numpy().view(np.uint64)[:n], cnt.cpu().numpy()[:n], mean.cpu().numpy()[:n], icov.cpu().numpy()[:n],
                 valid.cpu().numpy().astype(bool)[:n])
 
@@ -1107,9 +1098,8 @@ class NDTLocaliser(ScanToMapLocaliser):
             raise ValueError("pyramid_cells needs a localiser with resolutions")
         if not 0 <= int(level) < len(self.resolutions):
             raise ValueError(f"level must be in [0, {len(self.resolutions)})")
-        if self.level_capacities is None:
-            return self._read_cells(self.level_cells[int(level)], self.ctx.ndt_pyramid_cells, None, int(level))
-        return self._read_cells(self.level_capacities[int(level)], self.ctx.ndt_pyramid_cells, self.ctx.ndt_pyramid_info, int(level))
+        caps = self.level_capacities
+        return self._read_cells(int(level), self.level_cells[int(level)], None if caps is None else caps[int(level)])
 
 
 @dataclass

@@ -655,3 +655,114 @@ def test_the_closed_loop_follows_the_restatement_on_a_changed_scene(scans):
     assert all(got[0].pose_result.map_update[l].founded > 50 for l in range(3))      # the loop learned the cut half
     assert_levels_are(like, levels)
     like.ctx.check_errors(stream())
+
+
+# ---- the single map is a pyramid of one level: the two slots of a context -------------------------------------------------
+def test_the_single_map_scratch_is_the_scratch_of_a_pyramid_of_one_level():
+    from sps_amd import _native
+    lib = _native.lib
+    for cap in (0, 1, 255, 256, 257, 65536):                                   # SPS_NDT_UPDATE_MAX_POINTS
+        assert lib.sps_ndt_map_update_scratch(cap) == lib.sps_ndt_pyramid_update_scratch(cap, 1) > 0, cap
+        assert lib.sps_ndt_map_carve_scratch(cap) == lib.sps_ndt_pyramid_carve_scratch(cap, 1) == 0, cap
+
+
+class TwoSlots:
+    """One context with the single dynamic map and a one-level dynamic pyramid of the same resolution and capacity: the 8
+    cells of 1 m of [0, 2)^3 and room for 10, so that points which reach the 4 cells at 2 <= x < 3 found 2 and drop 2."""
+    RES, CAP = 1.0, 10
+
+    def __init__(self):
+        from sps_amd.datasets.blt_dataset import radius_grid_cells
+        from sps_amd.localiser import NDTLocaliser
+        rng = np.random.default_rng(11)
+        self.mp = 0.05 + 1.9 * rng.random((300, 3))
+        self.pts = 0.05 + np.array([2.9, 1.9, 1.9]) * rng.random((257, 3))
+        self.loc = NDTLocaliser(self.mp, resolution=self.RES, leaf=LEAF, cell_capacity=self.CAP)
+        self.ctx, self.resolution, self.resolutions = self.loc.ctx, self.RES, (self.RES,)    # what the raw_* helpers read
+        self.xyz = dev(self.mp)
+        keys, start, idx = radius_grid_cells(self.xyz, self.RES)
+        self.keep = (keys.contiguous(), start, idx)
+        assert len(keys) == 8
+        self.build_pyramid()
+
+    def map_args(self):
+        k, s, p = self.keep
+        return (k.data_ptr(), s.data_ptr(), p.data_ptr(), self.xyz.data_ptr(), len(k), len(self.mp), self.RES,
+                self.loc.min_points_per_cell, self.loc.eig_ratio)
+
+    def build_pyramid(self):
+        k, s, p = self.keep
+        self.ctx.ndt_pyramid_build([(k.data_ptr(), s.data_ptr(), p.data_ptr(), len(k), self.RES)], self.xyz.data_ptr(), len(self.mp),
+                                   self.loc.min_points_per_cell, self.loc.eig_ratio, self.loc.outlier_ratio, stream(), [self.CAP])
+
+    def snapshot(self, level):
+        """every byte the getters of a slot return: the single map (level None) or that level of the pyramid"""
+        lv = () if level is None else (level,)
+        cells, info, carve_cells = ((self.ctx.ndt_map_cells, self.ctx.ndt_map_info, self.ctx.ndt_map_carve_cells) if level is None else
+                                    (self.ctx.ndt_pyramid_cells, self.ctx.ndt_pyramid_info, self.ctx.ndt_pyramid_carve_cells))
+        C = self.CAP
+        out = [torch.full((C,), -3, dtype=torch.int64, device="cuda"), torch.full((C,), -3, dtype=torch.int32, device="cuda"),
+               torch.full((C, 3), -3.0, dtype=torch.float64, device="cuda"), torch.full((C, 6), -3.0, dtype=torch.float64, device="cuda"),
+               torch.full((C,), -3, dtype=torch.int32, device="cuda")]
+        counters = torch.full((3, C), -3, dtype=torch.int32, device="cuda")
+        cells(*lv, *[t.data_ptr() for t in out])
+        carve_cells(*lv, counters[0].data_ptr(), counters[1].data_ptr(), counters[2].data_ptr())
+        return tuple(t.cpu().numpy().tobytes() for t in out + [counters]) + (info(*lv),)
+
+    def run(self, pyramid, n, gate=None):
+        """an update and a carve of the first n points on one slot -> their info words (of the pyramid: level 0's)"""
+        from tests.test_hip_ndt_carve import raw_carve as single_carve
+        from tests.test_hip_ndt_update import raw_update as single_update
+        opts = dict(through_sigma=2.0, min_pass=1, miss_frames=2)
+        if not pyramid:
+            return (single_update(self, self.pts[:n], n, n, np.eye(4), gate=gate),
+                    single_carve(self, self.pts[:n], n, n, np.eye(4), gate=gate, **opts))
+        g = None if gate is None else torch.tensor([gate], dtype=torch.int32, device="cuda")
+        gp = None if g is None else g.data_ptr()
+        return (raw_update(self, self.pts[:n], n, n, np.eye(4), gate_ptr=gp)[0], raw_carve(self, self.pts[:n], n, n, np.eye(4), gate_ptr=gp, **opts)[0])
+
+
+def test_the_two_slots_of_one_context_do_not_alias():
+    """The single map and the pyramid of a context go through one implementation and must not share state: calls on the
+    single map leave every byte of the pyramid's getters as built, the same calls on the pyramid then give the same bytes and
+    info words, and behind a closed gate neither slot changes."""
+    two = TwoSlots()
+    fresh = two.snapshot(0)
+    assert two.snapshot(None) == fresh and fresh[-1] == (8, 10, 0)
+    sizes = (0, 1, 33, 257)                                                    # 257: past the 256-thread block edge
+    single = []
+    for n in sizes:
+        single.append(two.run(False, n))
+        assert two.snapshot(0) == fresh, n                                     # the pyramid is as built
+    after = two.snapshot(None)
+    assert after != fresh and after[-1][0] == 10 and after[-1][2] > 0          # the capacity filled and cells were dropped
+    assert [c[0] for _, c in single] == list(sizes)                            # every point cast a ray,
+    assert all(0 < u[3] <= n for (u, _), n in zip(single[1:], sizes[1:])) and single[3][0][2] > 0   # some lay in dropped cells
+    for n, want in zip(sizes, single):
+        assert two.run(True, n) == want, n
+        assert two.snapshot(None) == after, n                                  # and the single map is where its own calls left it
+    assert two.snapshot(0) == after
+    for pyramid in (False, True):                                              # a closed gate: no byte of either slot changes
+        u, c = two.run(pyramid, 257, gate=2)
+        assert u == [10, 0, 0, 0] and c == [0, 0, 0, 0]
+        assert two.snapshot(None) == after and two.snapshot(0) == after
+    two.ctx.check_errors(stream())
+
+
+def test_rebuilding_the_single_map_leaves_the_pyramid_alone():
+    from sps_amd import _native
+    two = TwoSlots()
+    fresh = two.snapshot(None)
+    two.run(True, 257)
+    pyr = two.snapshot(0)
+    assert pyr != fresh and two.snapshot(None) == fresh
+    two.ctx.ndt_map_build(*two.map_args(), stream())                           # static: the single map's online getters refuse
+    with pytest.raises(_native.SpsError):
+        two.ctx.ndt_map_info()
+    assert_same_cells(raw_cells(two.loc, 8), NR.cells(two.mp, two.RES))
+    assert two.snapshot(0) == pyr
+    two.ctx.ndt_map_build_dynamic(*two.map_args(), two.CAP, stream())
+    assert two.snapshot(None) == fresh and two.snapshot(0) == pyr
+    two.build_pyramid()                                                        # and the other way round
+    assert two.snapshot(0) == fresh and two.snapshot(None) == fresh
+    two.ctx.check_errors(stream())
