@@ -942,6 +942,64 @@ int sps_ukf_predict_dt(double *state_dev, double dt, const double *process_diag_
 int sps_ukf_correct(double *state_dev, const double *T_meas_dev, const int32_t *gate_dev, const double *meas_diag_host,
                     double *info_dev, void *stream);
 
+/* ---- NDT localiser, global search -------------------------------------------------------------------------------------
+ * Where on the map is the robot, with no start pose: a branch and bound over (x, y, yaw) on a pyramid of 2-D occupancy
+ * grids cut from a height slice of the map (the BBS engine of hdl_global_localization; Cartographer's fast correlative scan
+ * matcher is the same method).  It ends in K start poses on the device, which sps_ndt_align_batch takes as they are.
+ *   Additive: sps_version() is unchanged and no call above is touched.
+ *
+ * Grid: G0[H][W] bytes, 0 or 1, made by the caller; cell (i, j) covers [r (i0 + i), r (i0 + i + 1)) x [r (j0 + j), ...) of
+ *   the map frame.  G_l(x, y) = max G0[y + dj][x + di] over 0 <= di, dj < 2^l, l = 0 .. levels, reads outside G0 giving 0;
+ *   it is defined, and may be 1, from x, y = -(2^l - 1) on.
+ * sps_bbs_map_build: copies G0 (g0_dev, a device array) and pools levels 1 .. levels on the device; the pyramid lives in
+ *   the context, a second build replaces the first.  0 <= levels < SPS_BBS_MAX_LEVELS; W, H >= 1 and W + 2^levels - 1,
+ *   H + 2^levels - 1 <= 16384, else INVALID.  Allocates and synchronises.
+ * sps_bbs_map_level: debug -- level `level` as stored, (H + pad) rows of (W + pad) bytes with pad = 2^levels - 1 and
+ *   G_level(x, y) at [y + pad][x + pad].  Synchronises.
+ * sps_bbs_search: pts_dev, n_dev and cap are the thinned points of sps_loc_downsample (sensor frame), cap <= 65536.
+ *   Scan: q = ((r0*x + r1*y) + r2*z) + t of T_up_host (4 x 4, finite: roll, pitch and height, which a planar search cannot
+ *     find); a point is kept iff scan_z_lo <= q_z <= scan_z_hi (NaN fails).
+ *   Yaws: yaw_cs_dev is double[n_yaw][2] = (cos, sin)(2 pi a / n_yaw), made by the caller; the device calls no sin or cos.
+ *     u = c*q_x - s*q_y, v = s*q_x + c*q_y, dx = floor(u / resolution), dy = floor(v / resolution) (true divisions); a point
+ *     whose u / resolution or v / resolution is not finite or exceeds 2^20 in magnitude contributes nothing at that yaw.
+ *   Score of node (a, j, i) at level l: the sum over the kept points of G_l(i + dx, j + dy), an int32: an upper bound on
+ *     every leaf below the node, at l = 0 the leaf's score.
+ *   Search: the candidates of level `levels` are all (a, j, i) with j, i multiples of 2^levels inside the grid, ascending;
+ *     more than 4 * frontier of them is INVALID.  Per level, downwards: every candidate is scored; those with score <
+ *     min_score (>= 0) are dropped; if more than `frontier` remain, the `frontier` first by (score descending, position in
+ *     the candidate list ascending) are kept; dropped_bound (from -1) becomes the maximum of itself and the highest score
+ *     dropped, n_dropped grows by the number dropped; above level 0 the kept nodes, in candidate order, emit their children
+ *     (i + di h, j + dj h), h = 2^(l-1), (dj, di) = (0,0), (0,1), (1,0), (1,1), those with i >= W or j >= H skipped.
+ *   Result: the leaves kept at level 0 by (score descending, id ascending), id = (a * H + j) * W + i (n_yaw * H * W must fit
+ *     int32, else INVALID).  top_index_dev[k], top_score_dev[k]: id and score of the first k <= SPS_NDT_MAX_HYP; T_top_dev
+ *     [k][16]: their poses Trans(r (i0 + i), r (j0 + j), 0) Rz(yaw a) T_up -- entry (0, c) = c*U0c - s*U1c, entry (1, c) =
+ *     s*U0c + c*U1c, the translation r * (i0 + i) resp. r * (j0 + j) added to column 3, rows 2 and 3 those of T_up, every
+ *     operation rounded on its own.  Slots past the last leaf: index -1, score 0 and the pose of slot 0 (T_up where there
+ *     is none).  n_top_dev: the slots filled.
+ *   info_dev int32[SPS_BBS_INFO_WORDS] = (certified, dropped_bound, n_dropped, points in the slice, then per level l =
+ *     0 .. 7 (candidates, kept)); certified = the leading results with score > dropped_bound: that prefix is the prefix of
+ *     the exhaustive ranking of all leaves with score >= min_score.
+ *   trace_dev (debug, may be NULL): int32[levels + 1][5 * frontier], per level its candidate slots [4 * frontier] (four
+ *     per kept parent, -1 for a child outside the grid; level `levels`: the candidates themselves), then its kept nodes
+ *     [frontier], as ids; only the entries in use are written.
+ *   Launches: 2 + 4 * (levels + 1) and two memsets, whatever the data; grids are sized by capacity.  Scores are integer
+ *   counts: the results do not depend on the order of points or threads.  The only atomics are integer adds.
+ *   scratch_dev: sps_bbs_search_scratch(cap, n_yaw, frontier) bytes (-1 for cap > 65536, n_yaw outside [1,
+ *   SPS_BBS_MAX_YAWS] or frontier outside [1, SPS_BBS_MAX_FRONTIER]).  Never allocates, never synchronises, never raises
+ *   the sticky error. */
+#define SPS_BBS_MAX_LEVELS 8
+#define SPS_BBS_MAX_YAWS 4096
+#define SPS_BBS_MAX_FRONTIER 65536
+#define SPS_BBS_INFO_WORDS 20
+int sps_bbs_map_build(sps_ctx *ctx, const uint8_t *g0_dev, int64_t W, int64_t H, int levels, void *stream);
+int sps_bbs_map_level(sps_ctx *ctx, int level, uint8_t *out_dev);
+int64_t sps_bbs_search_scratch(int64_t cap, int64_t n_yaw, int64_t frontier);
+int sps_bbs_search(sps_ctx *ctx, const double *pts_dev, const int32_t *n_dev, int64_t cap, const double *T_up_host,
+                   double resolution, int64_t i0, int64_t j0, double scan_z_lo, double scan_z_hi, const double *yaw_cs_dev,
+                   int64_t n_yaw, int64_t frontier, int min_score, int k, int32_t *top_index_dev, int32_t *top_score_dev,
+                   double *T_top_dev, int32_t *n_top_dev, int32_t *info_dev, int32_t *trace_dev, void *scratch_dev,
+                   void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -27,7 +27,11 @@ per level; with ``--source cells`` it registers distribution to distribution (on
 the map's; ``--source-resolution``, ``--source-min-points``), ``n_corr`` then counts source cells and the ``loc:`` line
 ends with ``| N sources``, the scan's valid cells.  Frames then run one at a time; behind each frame's lines comes
 ``loc: status iterations n_corr rmse | err_t err_r`` (metres, degrees, against the replayed pose map_tr @ pose) and at
-the end the absolute pose error evo_ape prints by default.  ``--traj-out FILE`` writes the estimated trajectory
+the end the absolute pose error evo_ape prints by default.  ``--global-start`` (with ``--localiser ndt``) takes the loop's
+initial pose from ``NDTLocaliser.localise_global`` on the first raw scan instead of from the sequence (``--global-resolution``,
+``--global-map-z``, ``--global-scan-z``, ``--global-yaw-steps``, ``--global-levels``, ``--global-frontier``; the defaults are
+the slice chosen for sps_amd.synthetic: profiles/localiser_global/README.md) and prints the selected leaf, the certificate
+and the error against the sequence's first pose in ``global:`` lines.  ``--traj-out FILE`` writes the estimated trajectory
 (stamp + the top three rows of the pose per line).
 """
 from __future__ import annotations
@@ -141,39 +145,45 @@ def hypothesis_grid(counts, steps, option="--hypotheses", step_option="--hypothe
 
 def closed_loop(name, f, pc_map, replay, finish, traj_out, which="icp", hypotheses=None, search=None, update_map=False,
                 cell_capacity=None, max_cell_points=0, resolutions=None, level_iterations=None, carve_map=False,
-                carve_options=None, level_capacities=None, estimator=None, source=None, coarse_to_fine=False):
+                carve_options=None, level_capacities=None, estimator=None, source=None, coarse_to_fine=False,
+                global_start=None):
     """--localise: one LocalisationLoop step per frame, scored against the replayed poses.  ``estimator``: None, or the
     options of --estimator ukf (initial_velocity, scan_period, imu: None / a rate in Hz / an array of rows t ax .. gz).
     ``source``: None, or the keywords of NDTLocaliser(source="cells", ...) of --source cells.  ``coarse_to_fine``: hypotheses,
-    search and the estimator's device path register on the pyramid of --resolutions."""
+    search and the estimator's device path register on the pyramid of --resolutions.  ``global_start``: None, or the
+    options of --global-start (grid: the localiser's global_grid; yaw_steps, frontier, scan_z: of localise_global): the
+    loop's initial pose is then found on the map from the first raw scan, and the sequence's first pose only scores it."""
     from sps_amd.localiser import LocalisationLoop, NDTLocaliser, ScanToMapLocaliser
     from sps_amd.trajectory import ape_translation, rotation_angle, write_trajectory
     skw = source or {}
+    gkw = dict(global_grid=global_start["grid"]) if global_start is not None else {}
     if resolutions is not None and (update_map or carve_map):    # an online pyramid: per level, room for twice its cells
         caps = level_iterations or (30,) * len(resolutions)
         if level_capacities is None:
             xyz = np.ascontiguousarray(pc_map[:, :3], dtype=np.float64)
             level_capacities = tuple(max(2 * len(np.unique(np.floor(xyz / r).astype(np.int64), axis=0)), 4096) for r in resolutions)
         localiser = NDTLocaliser(pc_map[:, :3], resolutions=resolutions, iterations=sum(caps), level_iterations=caps,
-                                 level_capacities=level_capacities)
+                                 level_capacities=level_capacities, **gkw)
     elif update_map or carve_map:                                # an online map: room for twice the map's cells by default
         n_cells = NDTLocaliser(pc_map[:, :3]).n_cells
-        localiser = NDTLocaliser(pc_map[:, :3], cell_capacity=cell_capacity or max(2 * n_cells, 4096), **skw)
+        localiser = NDTLocaliser(pc_map[:, :3], cell_capacity=cell_capacity or max(2 * n_cells, 4096), **skw, **gkw)
     elif resolutions is not None:                                # coarse to fine; hypotheses and search keep the single map
                                                                  # unless --coarse-to-fine sends them to the pyramid too
         caps = level_iterations or (30,) * len(resolutions)       # the budget is their sum: it cuts no level short
-        localiser = NDTLocaliser(pc_map[:, :3], resolutions=resolutions, iterations=sum(caps), level_iterations=caps)
+        localiser = NDTLocaliser(pc_map[:, :3], resolutions=resolutions, iterations=sum(caps), level_iterations=caps, **gkw)
     else:
-        localiser = NDTLocaliser(pc_map[:, :3], **skw) if which == "ndt" else ScanToMapLocaliser(pc_map[:, :3])
+        localiser = NDTLocaliser(pc_map[:, :3], **skw, **gkw) if which == "ndt" else ScanToMapLocaliser(pc_map[:, :3])
     loop, stamps, ref, estimates = None, [], [], []
     for stamp, scan, pose, map_tr in replay:
         T = map_tr @ pose
         if loop is None:
-            est = None
+            est, T0 = None, T
+            if global_start is not None:
+                T0 = global_pose(localiser, scan, stamp, T, global_start, rotation_angle)
             if estimator is not None:
                 from sps_amd.pose_estimator import PoseEstimator
-                est = PoseEstimator(T, localiser.device, initial_velocity=estimator["initial_velocity"])
-            loop = LocalisationLoop(f, localiser, T, hypotheses=hypotheses, search=search, update_map=update_map,
+                est = PoseEstimator(T0, localiser.device, initial_velocity=estimator["initial_velocity"])
+            loop = LocalisationLoop(f, localiser, T0, hypotheses=hypotheses, search=search, update_map=update_map,
                                     max_cell_points=max_cell_points, carve_map=carve_map, carve_options=carve_options,
                                     estimator=est, coarse_to_fine=coarse_to_fine)
             if est is not None:
@@ -218,6 +228,32 @@ def closed_loop(name, f, pc_map, replay, finish, traj_out, which="icp", hypothes
             print(f"APE translation (m) of the estimator over {len(stamps)} frames: " + " ".join(f"{k}: {v:.4f}" for k, v in ape.items()))
     if traj_out:
         write_trajectory(traj_out, stamps, loop.poses if loop is not None else [])
+
+
+def global_pose(localiser, scan, stamp, T, opts, rotation_angle):
+    """--global-start: the initial pose of the loop from the first raw scan alone (NDTLocaliser.localise_global): the
+    selected leaf, the certificate and the error against the sequence's first pose ``T`` are printed"""
+    rows = torch.from_numpy(np.ascontiguousarray(np.asarray(scan)[:, :3], dtype=np.float32)).to(localiser.device)
+    g = localiser.localise_global(rows, len(rows), opts["yaw_steps"], frontier=opts["frontier"], scan_z=opts["scan_z"]).result()
+    s, grid = g.search, localiser._global
+    print(f"[{stamp}] global: {s.n_slice:d} of {s.n_points:d} points in the slice | grid {grid['W']:d} x {grid['H']:d} | "
+          f"candidates " + " ".join(str(int(v)) for v in s.candidates[::-1]) + " | kept " + " ".join(str(int(v)) for v in s.kept[::-1]))
+    print(f"[{stamp}] global: certified {s.certified:d} of {s.n_found:d} | dropped {s.n_dropped:d}, bound {s.dropped_bound:d} | "
+          f"scores " + " ".join(str(int(v)) for v in s.score[:s.n_found]))
+    if not s.n_found:
+        print(f"[{stamp}] global: no leaf found: the sequence's first pose starts the loop")
+        return T
+    k = g.batch.best if g.ok else 0
+    a, j, i = s.leaf(k, grid["W"], grid["H"])
+    T0 = g.pose if g.ok else s.poses[0]
+    err_t = float(np.linalg.norm(T0[:3, 3] - T[:3, 3]))
+    err_r = float(np.degrees(rotation_angle(T0, T)))
+    leaf_t = float(np.linalg.norm(s.poses[k][:2, 3] - T[:2, 3]))
+    print(f"[{stamp}] global: leaf {int(s.index[k]):d} (result {k:d}: yaw step {a:d} of {opts['yaw_steps']:d}, cell {i:d} {j:d}, "
+          f"score {int(s.score[k]):d}, {leaf_t:.4f} m from the sequence's first pose)"
+          + ("" if g.ok else " | no alignment was selected: the best leaf starts the loop"))
+    print(f"[{stamp}] global: start pose | {err_t:.4f} {err_r:.4f}")
+    return T0
 
 
 def frame_motion(estimator, k):
@@ -289,6 +325,18 @@ def frame_motion(estimator, k):
               help="with --source cells: edge of the scan's cells in m (default: the map's resolution)")
 @click.option("--source-min-points", "source_min_points", type=int, default=None,
               help="with --source cells: points a cell of the scan needs to be used (default: the map's)")
+@click.option("--global-start", "global_start", is_flag=True,
+              help="with --localiser ndt: the loop's initial pose comes from a global search of the first raw scan on an "
+                   "occupancy grid of the map (branch and bound over x, y, yaw), not from the sequence")
+@click.option("--global-resolution", "global_resolution", type=float, default=0.5, help="with --global-start: cell edge in m")
+@click.option("--global-map-z", "global_map_z", type=str, default="-1,3",
+              help="with --global-start: LO,HI, the height slice of the map that makes the grid (map frame, m)")
+@click.option("--global-scan-z", "global_scan_z", type=str, default="-1,3",
+              help="with --global-start: LO,HI, the height slice of the scan that is matched (sensor frame, m)")
+@click.option("--global-yaw-steps", "global_yaw_steps", type=int, default=72, help="with --global-start: headings tried")
+@click.option("--global-levels", "global_levels", type=int, default=3, help="with --global-start: pooled levels of the grid")
+@click.option("--global-frontier", "global_frontier", type=int, default=16384,
+              help="with --global-start: nodes kept per level of the search")
 @click.option("--estimator", "estimator", type=click.Choice(("ukf",)), default=None,
               help="with --localise: the guess of every frame is the prediction of the device UKF pose estimator, which the "
                    "registered pose corrects; a second APE line is the estimator's")
@@ -302,7 +350,23 @@ def frame_motion(estimator, k):
 def main(name, weights, sequence, config, epsilon, out_dir, n_synth, localise, which, traj_out, hyp_counts, hyp_steps,
          search_counts, search_steps, update_map, cell_capacity, max_cell_points, carve_map, carve_miss_frames, carve_sigma,
          resolutions, level_iterations, coarse_to_fine, level_capacities, source, source_resolution, source_min_points,
-         estimator, initial_velocity, scan_period, imu_rate, imu_file):
+         estimator, initial_velocity, scan_period, imu_rate, imu_file, global_start, global_resolution, global_map_z,
+         global_scan_z, global_yaw_steps, global_levels, global_frontier):
+    if global_start and (which != "ndt" or not localise):
+        raise click.UsageError("--global-start needs --localise --localiser ndt")
+    if global_start and source == "cells":
+        raise click.UsageError("--global-start takes no --source cells: the search matches points")
+    if global_start:
+        try:
+            slices = [tuple(float(v) for v in z.split(",")) for z in (global_map_z, global_scan_z)]
+        except ValueError:
+            slices = [()]
+        if any(len(z) != 2 for z in slices):
+            raise click.UsageError("--global-map-z and --global-scan-z take LO,HI")
+        global_start = dict(grid=dict(resolution=global_resolution, map_z=slices[0], levels=global_levels), scan_z=slices[1],
+                            yaw_steps=global_yaw_steps, frontier=global_frontier)
+    else:
+        global_start = None
     if coarse_to_fine and (resolutions is None or (hyp_counts is None and search_counts is None and estimator is None)):
         raise click.UsageError("--coarse-to-fine needs --resolutions and one of --hypotheses, --search, --estimator ukf")
     if source is not None and (which != "ndt" or not localise):
@@ -414,7 +478,7 @@ def main(name, weights, sequence, config, epsilon, out_dir, n_synth, localise, w
     if localise:
         closed_loop(name, f, pc_map, replay, finish, traj_out, which or "icp", hypotheses, search, update_map, cell_capacity,
                     max_cell_points, resolutions, level_iterations, carve_map, carve_options or None, level_capacities,
-                    estimator, source, coarse_to_fine)
+                    estimator, source, coarse_to_fine, global_start)
     elif traj_out:
         raise click.UsageError("--traj-out needs --localise")
     in_flight, prev_pose = None, None

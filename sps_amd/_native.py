@@ -140,6 +140,11 @@ def _load() -> C.CDLL:
         "sps_ndt_score_scratch": (i64, [i64, i64]),
         "sps_ndt_score_poses": (i32, [vp, vp, vp, i64, vp, i64, i32, C.c_double, vp, vp, vp]),
         "sps_ndt_top_poses": (i32, [vp, vp, vp, i64, i32, i32, vp, vp, vp, vp]),
+        "sps_bbs_map_build": (i32, [vp, vp, i64, i64, i32, vp]),
+        "sps_bbs_map_level": (i32, [vp, i32, vp]),
+        "sps_bbs_search_scratch": (i64, [i64, i64, i64]),
+        "sps_bbs_search": (i32, [vp, vp, vp, i64, vp, C.c_double, i64, i64, C.c_double, C.c_double, vp, i64, i64, i32, i32, vp, vp,
+                                 vp, vp, vp, vp, vp, vp]),
         "sps_ndt_map_build_dynamic": (i32, [vp, vp, vp, vp, vp, i64, i64, C.c_double, i32, C.c_double, i64, vp]),
         "sps_ndt_map_update_scratch": (i64, [i64]),
         "sps_ndt_map_update": (i32, [vp, vp, vp, i64, vp, vp, vp, i32, vp, vp, vp]),
@@ -202,6 +207,7 @@ EXPORTS = ["sps_last_error", "sps_version", "sps_ctx_create", "sps_ctx_destroy",
            "sps_ndt_align_scratch", "sps_ndt_map_build", "sps_ndt_map_cells", "sps_ndt_align",
            "sps_ndt_align_batch_scratch", "sps_ndt_align_batch",
            "sps_ndt_score_scratch", "sps_ndt_score_poses", "sps_ndt_top_poses",
+           "sps_bbs_map_build", "sps_bbs_map_level", "sps_bbs_search_scratch", "sps_bbs_search",
            "sps_ndt_map_build_dynamic", "sps_ndt_map_update_scratch", "sps_ndt_map_update", "sps_ndt_map_info",
            "sps_ndt_map_carve_scratch", "sps_ndt_map_carve", "sps_ndt_map_carve_cells",
            "sps_ndt_pyramid_build", "sps_ndt_pyramid_cells", "sps_ndt_pyramid_align_scratch", "sps_ndt_pyramid_align",
@@ -211,6 +217,12 @@ EXPORTS = ["sps_last_error", "sps_version", "sps_ctx_create", "sps_ctx_destroy",
            "sps_ndt_source_scratch", "sps_ndt_source_build", "sps_ndt_align_d2d_scratch", "sps_ndt_align_d2d",
            "sps_ukf_state_bytes", "sps_ukf_init", "sps_ukf_predict", "sps_ukf_predict_dt", "sps_ukf_correct"]
 NDT_SRC_REC = 10           # SPS_NDT_SRC_REC: doubles of a source record
+BBS_MAX_LEVELS = 8         # SPS_BBS_MAX_LEVELS
+BBS_MAX_YAWS = 4096        # SPS_BBS_MAX_YAWS
+BBS_MAX_FRONTIER = 65536   # SPS_BBS_MAX_FRONTIER
+BBS_INFO_WORDS = 20        # SPS_BBS_INFO_WORDS
+BBS_MAX_STORE = 16384      # W + 2^levels - 1 and H + 2^levels - 1 of sps_bbs_map_build stay within this
+BBS_MAX_POINTS = 65536     # cap of sps_bbs_search
 UKF_MAX_IMU = 256          # SPS_UKF_MAX_IMU
 CROP_BLOCK = 1024          # SPS_CROP_BLOCK: map rows per int of sps_radius_crop's scratch
 
@@ -500,6 +512,21 @@ class Context:
                       n_top_ptr: int, stream: int):
         check(lib.sps_ndt_top_poses(self.handle, score_ptr, T_ptr, int(n_pose), int(min_corr), int(k), top_index_ptr, T_top_ptr,
                                     n_top_ptr, stream))
+
+    # ---- NDT localiser, global search (include/sps_hip.h, "NDT localiser, global search") ----
+    def bbs_map_build(self, g0_ptr: int, W: int, H: int, levels: int, stream: int):
+        check(lib.sps_bbs_map_build(self.handle, g0_ptr, int(W), int(H), int(levels), stream))
+
+    def bbs_map_level(self, level: int, out_ptr: int):
+        """level ``level`` as stored, (H + pad) x (W + pad) bytes, into a device array; synchronises"""
+        check(lib.sps_bbs_map_level(self.handle, int(level), out_ptr))
+
+    def bbs_search(self, pts_ptr, n_dev_ptr: int, cap: int, T_up, resolution: float, i0: int, j0: int, scan_z_lo: float,
+                   scan_z_hi: float, yaw_cs_ptr: int, n_yaw: int, frontier: int, min_score: int, k: int, top_index_ptr: int,
+                   top_score_ptr: int, T_top_ptr: int, n_top_ptr: int, info_ptr: int, trace_ptr, scratch_ptr: int, stream: int):
+        check(lib.sps_bbs_search(self.handle, pts_ptr, n_dev_ptr, int(cap), self._mat(T_up), float(resolution), int(i0), int(j0),
+                                 float(scan_z_lo), float(scan_z_hi), yaw_cs_ptr, int(n_yaw), int(frontier), int(min_score), int(k),
+                                 top_index_ptr, top_score_ptr, T_top_ptr, n_top_ptr, info_ptr, trace_ptr, scratch_ptr, stream))
 
     # ---- NDT localiser, online map (include/sps_hip.h, "NDT localiser, online map") ----
     def ndt_map_build_dynamic(self, keys_ptr, start_ptr, pts_ptr, xyz_ptr, n_cells: int, n_map: int, resolution: float,

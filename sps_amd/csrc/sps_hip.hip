@@ -151,6 +151,7 @@ int fail(int code, const char *fmt, ...) {
 #include "ndt_kernels.inc.h"
 #include "ndt_batch_kernels.inc.h"
 #include "ndt_search_kernels.inc.h"
+#include "bbs_kernels.inc.h"
 #include "ndt_update_kernels.inc.h"
 #include "ndt_d2d_kernels.inc.h"
 #include "ndt_carve_kernels.inc.h"
@@ -304,6 +305,9 @@ struct sps_ctx {
   NdtPyramid ndt_map{};
   // NDT pyramid (sps_ndt_pyramid_build, sps_ndt_pyramid_build_dynamic): maps of its own beside the one above, coarse to fine
   NdtPyramid ndt_pyr{};
+  // occupancy pyramid of the global search (sps_bbs_map_build)
+  BbsGrid bbs{};
+  void *bbs_alloc = nullptr;
   // variant-A item scratch (sps_radius_item): per (scan point, neighbour cell) hit counts and their prefix sums
   int *item_counts = nullptr, *item_offsets = nullptr, *item_bsum = nullptr, *item_base = nullptr;
   int64_t item_cap = 0;
@@ -1075,6 +1079,7 @@ int sps_ctx_destroy(sps_ctx *c) {
   for (void *p : c->rg_allocs) (void)hipFree(p);
   for (void *p : c->ndt_map.allocs) (void)hipFree(p);
   for (void *p : c->ndt_pyr.allocs) (void)hipFree(p);
+  if (c->bbs_alloc) (void)hipFree(c->bbs_alloc);
   for (void *p : {(void *)c->item_counts, (void *)c->item_offsets, (void *)c->item_bsum, (void *)c->item_base}) (void)hipFree(p);
   delete c;
   return SPS_OK;
@@ -2227,6 +2232,7 @@ int sps_get_feature(sps_ctx *c, const char *name, float *out_dev, int64_t *rows,
 #include "ndt_host.inc.h"
 #include "ndt_batch_host.inc.h"
 #include "ndt_search_host.inc.h"
+#include "bbs_host.inc.h"
 #include "ndt_online_host.inc.h"
 #include "ndt_d2d_host.inc.h"
 #include "ndt_pyramid_host.inc.h"

@@ -47,6 +47,12 @@ of its own, from start poses that live on the device, and selected by the score 
 integrate=True, carve=True)`` update and carve all levels in one set of launches; their results are then tuples, one entry per
 level, coarsest first.  The single map at ``resolution`` stays static.
 
+``NDTLocaliser(..., global_grid=dict(resolution=0.5, map_z=(lo, hi), levels=3))`` can find a pose with no start pose (C ABI:
+"NDT localiser, global search"): a height slice of the map becomes a pyramid of 2-D occupancy grids, and
+``global_search`` scores every cell and heading by the scan points that fall on occupied cells, level by level within a
+frontier, and says how many of its best leaves are provably the exhaustive search's; ``localise_global`` hands those leaves
+to the batched registration on the device.
+
 ``LocalisationLoop`` closes the loop for any of the seven filters of scripts/filter_sequence.py, around either localiser.
 """
 from __future__ import annotations
@@ -384,6 +390,100 @@ class PendingRelocalisation(_Pending):
                                     batch.map_carve)
 
 
+GLOBAL_GRID_DEFAULTS = dict(resolution=0.5, map_z=(-math.inf, math.inf), levels=3)
+
+
+@dataclass
+class GlobalSearchResult:
+    index: np.ndarray          # [keep] int, leaf ids (a * H + j) * W + i by (score descending, id ascending); -1: slot not filled
+    score: np.ndarray          # [keep] int, the slice points of the scan that fall on occupied cells at that leaf
+    poses: np.ndarray          # [keep, 4, 4]: Trans(r (i0 + i), r (j0 + j), 0) Rz(2 pi a / yaw_steps) T_up of every leaf
+    n_found: int               # slots filled
+    certified: int             # the leading results that are the exhaustive ranking's: score > dropped_bound
+    dropped_bound: int         # the highest bound of anything the search dropped (-1: nothing was dropped)
+    n_dropped: int             # nodes dropped, for min_score or for the frontier
+    candidates: np.ndarray     # [levels + 1] int, nodes scored at level l
+    kept: np.ndarray           # [levels + 1] int, nodes kept at level l
+    n_slice: int               # thinned points inside the scan slice
+    n_points: int              # points after thinning
+    candidate_lists: list = None   # with trace=True: per level the ids of the candidates, in their order
+    kept_lists: list = None        # with trace=True: per level the ids of the kept nodes, in their order
+
+    def leaf(self, k: int, W: int, H: int):
+        """(a, j, i) of result k"""
+        i, aj = int(self.index[k]) % W, int(self.index[k]) // W
+        return aj // H, aj % H, i
+
+
+def _global_layout(K, trace_words=0):
+    """offsets (in doubles) of the global search's part of a buffer: top int32[K] (+ pad) | score int32[K] (+ pad) | n_top
+    int32 (+ pad) | info int32[20] | T_top[K][16] | trace int32[trace_words] (+ pad)"""
+    return _offsets((("top", (K + 1) // 2), ("score", (K + 1) // 2), ("n_top", 1), ("info", _native.BBS_INFO_WORDS // 2),
+                     ("T_top", 16 * K), ("trace", (trace_words + 1) // 2)), (("n_points", 1),))
+
+
+def _global_result_of(h, K, L, F, trace, n_points) -> GlobalSearchResult:
+    o = _global_layout(K, (L + 1) * 5 * F if trace else 0)
+    info = h[o["info"]:o["T_top"]].view(np.int32).astype(np.int64)
+    per_level = info[4:4 + 2 * (L + 1)].reshape(L + 1, 2)
+    cl = kl = None
+    if trace:
+        tr = h[o["trace"]:o["size"]].view(np.int32)[:(L + 1) * 5 * F].reshape(L + 1, 5 * F).astype(np.int64)
+        cl = [tr[l, :4 * F][tr[l, :4 * F] >= 0] for l in range(L + 1)]
+        kl = [tr[l, 4 * F:][tr[l, 4 * F:] >= 0] for l in range(L + 1)]
+    return GlobalSearchResult(h[o["top"]:o["score"]].view(np.int32)[:K].astype(np.int64),
+                              h[o["score"]:o["n_top"]].view(np.int32)[:K].astype(np.int64),
+                              h[o["T_top"]:o["trace"]].reshape(K, 4, 4).copy(), int(h[o["n_top"]:o["info"]].view(np.int32)[0]),
+                              int(info[0]), int(info[1]), int(info[2]), per_level[:, 0].copy(), per_level[:, 1].copy(),
+                              int(info[3]), int(n_points), cl, kl)
+
+
+class PendingGlobalSearch(_Pending):
+    """A global search whose work has been issued; ``result()`` -> GlobalSearchResult."""
+
+    def __init__(self, K, L, F, trace, host, event, keep):
+        super().__init__(host, event, keep)
+        self._shape = (K, L, F, trace)
+
+    def result(self) -> GlobalSearchResult:
+        K, L, F, trace = self._shape
+        h = self._wait()
+        o = _global_layout(K, (L + 1) * 5 * F if trace else 0)
+        return _global_result_of(h, K, L, F, trace, h[o["n_points"]:o["total"]].view(np.int32)[0])
+
+
+@dataclass
+class GlobalLocalisationResult:
+    search: GlobalSearchResult # the leaves the registration started from
+    batch: BatchPoseResult     # the ``keep`` alignments, hypothesis k started from search.poses[k]
+    index: int                 # the leaf id of the selected alignment's start pose, or -1 where none was selected
+    pose: np.ndarray           # 4x4: batch.pose
+    map_update: object = None  # MapUpdateResult of the frame, with integrate=True (batch.map_update)
+    map_carve: object = None   # MapCarveResult of the frame, with carve=True (batch.map_carve)
+
+    @property
+    def ok(self) -> bool:
+        return self.index >= 0
+
+
+class PendingGlobalLocalisation(_Pending):
+    """A global search and the alignments of its leaves, issued; everything lives on the device until result()."""
+
+    def __init__(self, L, F, batch_pending):
+        super().__init__(batch_pending._host, batch_pending._event, batch_pending._keep)
+        self._L, self._F, self._batch = L, F, batch_pending
+
+    def _pose_on_device(self):
+        return self._batch._pose_on_device()
+
+    def result(self) -> GlobalLocalisationResult:
+        h = self._wait()
+        batch = self._batch._parse(h)
+        search = _global_result_of(h, self._batch._n_hyp, self._L, self._F, False, batch.results[0].n_points)
+        index = int(search.index[batch.best]) if batch.best >= 0 else -1
+        return GlobalLocalisationResult(search, batch, index, batch.pose, batch.map_update, batch.map_carve)
+
+
 class ScanToMapLocaliser:
     """``ScanToMapLocaliser(map_points)(rows, count, T_init)`` -> PoseResult.  The map's uniform grid (cell size =
     ``max_distance``) lives in a native context of the localiser's own, so the grid of the offline item path
@@ -626,13 +726,19 @@ class NDTLocaliser(ScanToMapLocaliser):
     ``min_correspondences`` bounds them, and the result's ``n_sources`` tells how many valid ones the scan gave.
     ``submit`` / ``submit_filtered`` / ``__call__``, ``integrate`` and ``carve`` work as before (the map still takes the
     thinned points); ``resolutions``, ``submit_batch``, ``submit_from_device``, ``score_poses`` and ``relocalise`` are
-    refused.  ``capacity`` is then at most 65536.  ``source="points"`` (the default) is the point-to-distribution path."""
+    refused.  ``capacity`` is then at most 65536.  ``source="points"`` (the default) is the point-to-distribution path.
+
+    ``global_grid`` (None: nothing is built; a dict with any of ``resolution`` (0.5), ``map_z`` = (lo, hi) (everything) and
+    ``levels`` (3, at most 7)): the map points of that height slice become an occupancy grid of that edge with ``levels``
+    pooled levels on the device, and ``global_search`` / ``localise_global`` find the pose with no start pose.
+    ``capacity`` is then at most 65536, and ``source="cells"`` is refused."""
 
     def __init__(self, map_points, resolution: float = 1.0, neighbours: int = 7, leaf: float = 0.2, iterations: int = 30,
                  min_correspondences: int = 50, min_points_per_cell: int = 6, outlier_ratio: float = 0.55,
                  eig_ratio: float = 0.01, tol_t: float = 1e-4, tol_r: float = 1e-5, device="cuda", capacity: int = 1 << 16,
                  cell_capacity: int = None, resolutions=None, level_iterations=None, level_capacities=None,
-                 source: str = "points", source_resolution: float = None, source_min_points: int = None):
+                 source: str = "points", source_resolution: float = None, source_min_points: int = None,
+                 global_grid: dict = None):
         self.source, self.source_resolution, self.source_min_points = self._checked_source(
             source, source_resolution, source_min_points, resolution, min_points_per_cell, resolutions, capacity)
         if level_capacities is not None and cell_capacity is not None:
@@ -651,8 +757,14 @@ class NDTLocaliser(ScanToMapLocaliser):
         self.resolution, self.neighbours = float(resolution), int(neighbours)
         self.min_points_per_cell, self.outlier_ratio, self.eig_ratio = int(min_points_per_cell), float(outlier_ratio), float(eig_ratio)
         self.cell_capacity = None if cell_capacity is None else int(cell_capacity)
+        self._global = self._checked_global_grid(global_grid, xyz, capacity, self.source)
         self._open(xyz, leaf, iterations, min_correspondences, tol_t, tol_r, device, capacity, _native.lib.sps_ndt_align_scratch)
         with torch.cuda.device(self.device):
+            if self._global is not None:                             # the occupancy pyramid: G0 from the host, pooled there
+                g0 = torch.from_numpy(self._global["G0"]).to(self.device)
+                self.ctx.bbs_map_build(g0.data_ptr(), self._global["W"], self._global["H"], self._global["levels"],
+                                       self.stream.cuda_stream)
+                self._bbs_scratch, self._bbs_shape = None, None
             self._batch_scratch, self._batch_hyp = None, 0
             self._pyr_batch_scratch, self._pyr_batch_hyp = None, 0
             self._score_scratch, self._score_poses = None, 0
@@ -721,6 +833,151 @@ class NDTLocaliser(ScanToMapLocaliser):
         if not (math.isfinite(res) and res > 0 and mp >= 0):
             raise ValueError("source_resolution must be finite and > 0 and source_min_points >= 0")
         return source, res, mp
+
+    _global = None                                                   # no global_grid: nothing is built
+
+    @staticmethod
+    def _checked_global_grid(global_grid, xyz, capacity, source="points"):
+        """None, or the occupancy grid of the global search, before any device work: dict(resolution, map_z, levels, G0 uint8
+        [H, W], i0, j0, W, H).  A map point with map_z[0] <= z <= map_z[1] falls into cell (floor(x / r) - i0, floor(y / r) -
+        j0), float64 divisions as the NDT cells are grouped; (i0, j0) is the lowest cell hit ((0, 0) and a 1 x 1 grid of 0
+        where the slice holds no point)"""
+        if global_grid is None:
+            return None
+        unknown = set(global_grid) - set(GLOBAL_GRID_DEFAULTS)
+        if unknown:
+            raise ValueError(f"unknown global_grid entries {sorted(unknown)}")
+        if source == "cells":
+            raise ValueError("global_grid searches with points: it needs an NDTLocaliser with source='points'")
+        g = dict(GLOBAL_GRID_DEFAULTS, **global_grid)
+        r, L = float(g["resolution"]), int(g["levels"])
+        lo, hi = (float(v) for v in g["map_z"])
+        if not (math.isfinite(r) and r > 0) or math.isnan(lo) or math.isnan(hi):
+            raise ValueError("global_grid: resolution must be finite and > 0 and map_z must not be NaN")
+        if not 0 <= L < _native.BBS_MAX_LEVELS:
+            raise ValueError(f"global_grid: levels must be in [0, {_native.BBS_MAX_LEVELS - 1}]")
+        if capacity > _native.BBS_MAX_POINTS:
+            raise ValueError(f"with global_grid, capacity must be <= {_native.BBS_MAX_POINTS}")
+        sel = xyz[(xyz[:, 2] >= lo) & (xyz[:, 2] <= hi)]
+        with np.errstate(invalid="ignore"):
+            c = np.floor(sel[:, :2] / np.float64(r))
+        c = c[np.isfinite(c).all(axis=1)]
+        if len(c) and np.abs(c).max() >= (1 << 20):
+            raise ValueError("global_grid: the map extent exceeds the grid")
+        c = c.astype(np.int64)
+        i0, j0 = (int(c[:, 0].min()), int(c[:, 1].min())) if len(c) else (0, 0)
+        W, H = (int(c[:, 0].max()) - i0 + 1, int(c[:, 1].max()) - j0 + 1) if len(c) else (1, 1)
+        if max(W, H) + (1 << L) - 1 > _native.BBS_MAX_STORE:
+            raise ValueError(f"global_grid: {W} x {H} cells with {L} levels exceed {_native.BBS_MAX_STORE} cells per axis")
+        G0 = np.zeros((H, W), dtype=np.uint8)
+        G0[c[:, 1] - j0, c[:, 0] - i0] = 1
+        return dict(resolution=r, map_z=(lo, hi), levels=L, G0=G0, i0=i0, j0=j0, W=W, H=H)
+
+    def _checked_global(self, what, keep, yaw_steps, frontier, min_score, scan_z, T_up):
+        """the checks of the global search, before any device work -> (K, A, F, min_score, (lo, hi), T_up, yaw table [A, 2])"""
+        self._refuse_cells(what)
+        g = self._global
+        if g is None:
+            raise ValueError(f"{what} needs a localiser with an occupancy grid: NDTLocaliser(..., global_grid=dict(...))")
+        K, A, F, ms = int(keep), int(yaw_steps), int(frontier), int(min_score)
+        if not 1 <= K <= MAX_HYPOTHESES:
+            raise ValueError(f"keep must be in [1, {MAX_HYPOTHESES}]")
+        if not (1 <= A <= _native.BBS_MAX_YAWS and 1 <= F <= _native.BBS_MAX_FRONTIER and ms >= 0):
+            raise ValueError(f"yaw_steps must be in [1, {_native.BBS_MAX_YAWS}], frontier in [1, {_native.BBS_MAX_FRONTIER}] "
+                             "and min_score >= 0")
+        if A * g["H"] * g["W"] >= 1 << 31:
+            raise ValueError("yaw_steps * H * W overflows the int32 leaf id")
+        step = 1 << g["levels"]
+        n_root = A * (-(-g["H"] // step)) * (-(-g["W"] // step))
+        if n_root > 4 * F:
+            raise ValueError(f"{n_root} candidates at level {g['levels']} exceed 4 * frontier = {4 * F}: more levels or a "
+                             "larger frontier")
+        lo, hi = (-math.inf, math.inf) if scan_z is None else (float(v) for v in scan_z)
+        if math.isnan(lo) or math.isnan(hi):
+            raise ValueError("scan_z must not be NaN")
+        U = np.eye(4) if T_up is None else _pose(T_up)
+        if U is None or not np.isfinite(U).all():
+            raise ValueError("T_up must be a finite 4x4 matrix")
+        ang = 2.0 * np.pi * np.arange(A, dtype=np.float64) / np.float64(A)
+        return K, A, F, ms, (lo, hi), U, np.ascontiguousarray(np.stack([np.cos(ang), np.sin(ang)], axis=1))
+
+    def _bbs_scratch_for(self, A, F):
+        if self._bbs_shape is None or A > self._bbs_shape[0] or F > self._bbs_shape[1]:    # grows (stream-ordered reuse)
+            A0, F0 = self._bbs_shape or (0, 0)
+            self._bbs_shape = (max(A, A0), max(F, F0))
+            self._bbs_scratch = torch.empty(_native.lib.sps_bbs_search_scratch(self.capacity, *self._bbs_shape),
+                                            dtype=torch.uint8, device=self.device)
+        return self._bbs_scratch
+
+    def _global_search(self, n_ptr, cs_dev, K, A, F, ms, z, U, base, o, trace, s):
+        """the search of self._pts into the search's part of a buffer at ``base`` (layout ``o``), on stream s"""
+        g = self._global
+        self.ctx.bbs_search(self._pts.data_ptr(), n_ptr, self.capacity, U, g["resolution"], g["i0"], g["j0"], z[0], z[1],
+                            cs_dev.data_ptr(), A, F, ms, K, base + o["top"] * 8, base + o["score"] * 8, base + o["T_top"] * 8,
+                            base + o["n_top"] * 8, base + o["info"] * 8, base + o["trace"] * 8 if trace else None,
+                            self._bbs_scratch_for(A, F).data_ptr(), s)
+
+    @torch.no_grad()
+    def global_search(self, rows, count, yaw_steps, keep: int = 8, frontier: int = 16384, min_score: int = 1, scan_z=None,
+                      T_up=None, trace: bool = False) -> PendingGlobalSearch:
+        """Where on the map is the scan, with no start pose (C ABI: "NDT localiser, global search"): the rows
+        are thinned as ``submit`` thins them, moved by ``T_up`` (4x4, default the identity: roll, pitch and height), cut to
+        ``scan_z`` = (lo, hi) of that frame (None: everything) and matched against the occupancy grid of ``global_grid`` at
+        every cell and each of ``yaw_steps`` headings by branch and bound; a leaf's score is the number of slice points on
+        occupied cells.  ``frontier`` bounds the nodes kept per level, ``min_score`` the score of anything kept.
+        ``result()`` -> GlobalSearchResult with the best ``keep`` (1..64) leaves; its ``certified`` tells how many of them
+        are provably the exhaustive search's.  ``trace`` (debug): the result also lists every level's candidates and kept
+        nodes.  Issued on the current stream with no synchronisation."""
+        K, A, F, ms, z, U, cs = self._checked_global("global_search", keep, yaw_steps, frontier, min_score, scan_z, T_up)
+        rows = self._checked_rows(rows)
+        L = self._global["levels"]
+        o = _global_layout(K, (L + 1) * 5 * F if trace else 0)
+
+        def work(out, n_ptr, cs_dev, s):
+            if trace:
+                out[o["trace"]:o["size"]].view(torch.int32).fill_(-1)
+            self._global_search(n_ptr, cs_dev, K, A, F, ms, z, U, out.data_ptr(), o, trace, s)
+        return PendingGlobalSearch(K, L, F, trace, *self._issue(rows, count, o["total"], o["n_points"] * 8, work, cs))
+
+    @torch.no_grad()
+    def localise_global(self, rows, count, yaw_steps, keep: int = 8, frontier: int = 16384, min_score: int = 1, scan_z=None,
+                        T_up=None, with_normal: bool = False, iterations: int = None, integrate: bool = False,
+                        max_cell_points: int = 0, carve: bool = False, carve_options: dict = None,
+                        coarse_to_fine: bool = False) -> PendingGlobalLocalisation:
+        """``global_search``, then the registration of its ``keep`` leaves as ``submit_batch`` registers start poses and the
+        choice among the end poses as it chooses: the leaves' poses stay on the device, as the candidates of ``relocalise``
+        do.  ``result()`` -> GlobalLocalisationResult.  ``with_normal`` ... ``coarse_to_fine``: as for ``submit_batch``."""
+        K, A, F, ms, z, U, cs = self._checked_global("localise_global", keep, yaw_steps, frontier, min_score, scan_z, T_up)
+        rows, copts = self._checked_for_batch("localise_global", rows, integrate, max_cell_points, carve, carve_options,
+                                              coarse_to_fine)
+        I = self.iterations if iterations is None else int(iterations)
+        shape = self._batch_shape(integrate, carve, coarse_to_fine)
+        so, o = _global_layout(K), _batch_layout(K, I, with_normal, *shape)
+
+        def work(out, n_ptr, cs_dev, s):
+            sbase = out.data_ptr()
+            self._global_search(n_ptr, cs_dev, K, A, F, ms, z, U, sbase, so, False, s)
+            self._align_batch(n_ptr, sbase + so["T_top"] * 8, K, I, with_normal, sbase + so["size"] * 8, o, s, integrate,
+                              max_cell_points, copts, coarse_to_fine)
+        issued = self._issue(rows, count, so["size"] + o["total"], (so["size"] + o["n_points"]) * 8, work, cs)
+        return PendingGlobalLocalisation(self._global["levels"], F,
+                                         PendingPoses(K, I, with_normal, *issued, so["size"], *shape))
+
+    def localise_global_filtered(self, pending, yaw_steps, **kw) -> PendingGlobalLocalisation:
+        """``localise_global`` of the kept rows of a pending SPSFilter / SPSCVMFilter frame, without the frame's result()."""
+        return self.localise_global(pending._filtered, pending.count_dev, yaw_steps, **kw)
+
+    def global_level(self, level: int) -> np.ndarray:
+        """Debug: level ``level`` of the occupancy pyramid as the device stores it, uint8 [H + pad, W + pad] with pad =
+        2^levels - 1 and G_level(x, y) at [y + pad, x + pad].  Synchronises."""
+        g = self._global
+        if g is None:
+            raise ValueError("global_level needs a localiser with an occupancy grid: NDTLocaliser(..., global_grid=dict(...))")
+        pad = (1 << g["levels"]) - 1
+        with torch.cuda.device(self.device):
+            out = torch.zeros((g["H"] + pad, g["W"] + pad), dtype=torch.uint8, device=self.device)
+            self.ctx.bbs_map_level(level, out.data_ptr())
+        return out.cpu().numpy()
 
     def _refuse_cells(self, what):
         if self.source == "cells":

@@ -11,7 +11,7 @@ synthetic.build_map() map, max_distance 1 m, leaf 0.2 m):
 
     python tools/localiser_timing.py [--frames 200] [--warmup 20] [--cpu-frames 1] [--one-frame] [--cpu-only]
                                      [--localiser {icp,ndt}] [--hypotheses K] [--search P] [--update-map] [--carve]
-                                     [--source {points,cells}] [--source-resolution R] [--source-min-points N]
+                                     [--source {points,cells}] [--source-resolution R] [--source-min-points N] [--global]
 
 ``--localiser ndt`` times sps_amd.localiser.NDTLocaliser (1 m cells, 7 neighbours) on the same frames and from the same
 start, prints the ICP's per-frame figures of the same session beside it and the build time of both maps; the
@@ -54,6 +54,13 @@ hipEvents around each call and the calls of one table alternating frame by frame
 against submit on the pyramid (K = 1); submit_batch(coarse_to_fine=True) against the single-map submit_batch for K = 8 and
 64 at the budgets 30 (caps 10 each) and 90 (caps 30 each); then LocalisationLoop per frame (host wall clock) with the UKF
 on the pyramid, device path against host path, and the same loop on an online pyramid with update and carve.
+
+``--localiser ndt --global`` times the global search on the synthetic map with the slice of
+scripts/filter_sequence.py --global-start (0.5 m cells, map and scan slice -1 .. 3 m, 72 yaws, 3 levels, frontier 16384):
+hipEvents around global_search and around localise_global (keep 8), the two alternating frame by frame, the scan moved to
+a pose the search has to find; then, on --cpu-frames frames, the only comparable means without it: score_poses over the
+poses of all leaves in chunks of 65536 (the pose upload included), and whether its best leaf is the search's.  With
+--one-frame: a warm-up and ONE global_search.
 
 ``--one-frame`` runs a warm-up and ONE localiser frame: the target of a ``rocprofv3 --kernel-trace --stats`` run.
 """
@@ -158,7 +165,12 @@ def main():
                     "distribution-to-distribution registration beside the point path")
     ap.add_argument("--source-resolution", type=float, default=None, help="with --source cells: edge of the scan's cells")
     ap.add_argument("--source-min-points", type=int, default=None, help="with --source cells: points a cell of the scan needs")
+    ap.add_argument("--global", dest="global_search", action="store_true", help="with --localiser ndt: time global_search and "
+                    "localise_global against score_poses over all leaf poses")
     a = ap.parse_args()
+    if a.global_search and (a.localiser != "ndt" or a.hypotheses or a.search or a.update_map or a.carve or a.resolutions
+                            or a.estimator or a.source == "cells"):
+        ap.error("--global needs --localiser ndt and none of the other modes")
     if a.source == "cells" and (a.localiser != "ndt" or a.hypotheses or a.search or a.update_map or a.carve or a.resolutions
                                 or a.estimator):
         ap.error("--source cells needs --localiser ndt and none of the other modes")
@@ -185,6 +197,8 @@ def main():
     dscans = [torch.from_numpy(s).cuda() for s in scans]
     mp = synthetic.build_map()
     T_init = LR.perturbation(0.15, 0.12, 0.05, 1.0)
+    if a.global_search:
+        return ndt_global_main(a, scans, mp)
     if a.estimator:
         return ndt_estimator_main(a, scans, dscans, mp, T_init)
     if a.c2f:
@@ -273,6 +287,95 @@ def main():
     out["loop_flagged_frames"] = int(flagged)
     print(f"SPSFilter alone {out['sps_filter_ms']:.3f} ms, LocalisationLoop(sps_cvm) {out['loop_sps_cvm_ms']:.3f} ms per frame "
           f"({flagged} flagged)")
+    print(json.dumps(out))
+
+
+GLOBAL = dict(grid=dict(resolution=0.5, map_z=(-1.0, 3.0), levels=3), scan_z=(-1.0, 3.0), yaw_steps=72, frontier=16384, keep=8)
+
+
+def ndt_global_main(a, scans, mp):
+    """--global: see the module docstring.  The scans are taken at the identity; they are moved into the sensor frame of
+    T_true, so the search has a pose to find that is not the origin of the grid"""
+    th = np.radians(40.0)
+    T_true = np.eye(4)
+    T_true[:2, :2] = [[np.cos(th), -np.sin(th)], [np.sin(th), np.cos(th)]]
+    T_true[:2, 3] = [2.3, 0.4]
+    Ti = np.linalg.inv(T_true)
+    moved = [np.c_[s[:, :3].astype(np.float64) @ Ti[:3, :3].T + Ti[:3, 3], s[:, 3]].astype(np.float32) for s in scans]
+    dscans = [torch.from_numpy(s).cuda() for s in moved]
+    loc, t_build = build_ms(lambda: NDTLocaliser(mp[:, :3], global_grid=GLOBAL["grid"]))
+    g, A, kw = loc._global, GLOBAL["yaw_steps"], dict(keep=GLOBAL["keep"], frontier=GLOBAL["frontier"], scan_z=GLOBAL["scan_z"])
+    st = torch.cuda.current_stream()
+
+    def timed(call):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(st)
+        pend = call()
+        e1.record(st)
+        r = pend.result() if hasattr(pend, "result") else pend
+        e1.synchronize()
+        return e0.elapsed_time(e1), r
+
+    for k in range(a.warmup):
+        s = dscans[k % len(dscans)]
+        loc.global_search(s, len(s), A, **kw).result()
+        loc.localise_global(s, len(s), A, **kw).result()
+    torch.cuda.synchronize()
+    if a.one_frame:
+        s = dscans[a.warmup % len(dscans)]
+        r = loc.global_search(s, len(s), A, **kw).result()
+        print(json.dumps({"one_frame": True, "n_found": r.n_found, "certified": r.certified, "n_slice": r.n_slice}))
+        return
+    ms_s, ms_l, cert, err_leaf, err_pose, ok, cands = [], [], [], [], [], 0, []
+    for k in range(a.frames):
+        s = dscans[(a.warmup + k) % len(dscans)]
+        t, r = timed(lambda: loc.global_search(s, len(s), A, **kw))
+        ms_s.append(t)
+        cert.append(r.certified)
+        cands.append(int(r.candidates.sum()))
+        err_leaf.append(float(np.linalg.norm(r.poses[0][:2, 3] - T_true[:2, 3])))
+        t, r2 = timed(lambda: loc.localise_global(s, len(s), A, **kw))
+        ms_l.append(t)
+        ok += r2.ok
+        err_pose.append(LR.pose_difference(r2.pose, T_true)[0])
+    med = lambda v: round(float(np.median(v)), 4)
+    out = {"n_scan": int(np.mean([len(s) for s in scans])), "n_map": len(mp), "frames": a.frames, "warmup": a.warmup,
+           "grid": [g["W"], g["H"]], "leaves": A * g["W"] * g["H"], "settings": {k: v for k, v in GLOBAL.items() if k != "grid"},
+           "grid_settings": GLOBAL["grid"], "build_ms": round(t_build, 2),
+           "global_search_ms": {"median": med(ms_s), "min": round(min(ms_s), 4), "max": round(max(ms_s), 4)},
+           "localise_global_ms": {"median": med(ms_l), "min": round(min(ms_l), 4), "max": round(max(ms_l), 4)},
+           "certified_min": int(min(cert)), "nodes_scored_median": med(cands), "best_leaf_error_m_max": round(max(err_leaf), 4),
+           "localise_global_selected": int(ok), "localise_global_error_m_max": round(max(err_pose), 5),
+           "points_after_thinning": r.n_points, "points_in_slice": r.n_slice}
+    print(f"global_search  median {out['global_search_ms']['median']:.3f} ms (min {min(ms_s):.3f} max {max(ms_s):.3f}); "
+          f"localise_global median {out['localise_global_ms']['median']:.3f} ms (min {min(ms_l):.3f} max {max(ms_l):.3f}); "
+          f"grid {g['W']} x {g['H']} x {A} yaws = {out['leaves']} leaves, {r.n_slice} of {r.n_points} points in the slice", flush=True)
+    # the parent's only comparable means: the NDT score of every leaf pose, 65536 poses per call
+    if a.cpu_frames:
+        cs = np.stack([np.cos(2 * np.pi * np.arange(A) / A), np.sin(2 * np.pi * np.arange(A) / A)], axis=1)
+        P = np.tile(np.eye(4), (out["leaves"], 1, 1)).reshape(A, g["H"], g["W"], 4, 4)
+        P[..., 0, 0] = P[..., 1, 1] = cs[:, 0, None, None]
+        P[..., 1, 0] = cs[:, 1, None, None]
+        P[..., 0, 1] = -cs[:, 1, None, None]
+        P[..., 0, 3] = g["resolution"] * (g["i0"] + np.arange(g["W"]))[None, None, :]
+        P[..., 1, 3] = g["resolution"] * (g["j0"] + np.arange(g["H"]))[None, :, None]
+        P = np.ascontiguousarray(P.reshape(-1, 4, 4))
+        chunks = [P[c:c + 65536] for c in range(0, len(P), 65536)]
+        loc.score_poses(dscans[0], len(dscans[0]), chunks[-1]).result()       # warm-up of the shape
+        ms_b, same = [], 0
+        for k in range(a.cpu_frames):
+            s = dscans[(a.warmup + k) % len(dscans)]
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            parts = [loc.score_poses(s, len(s), c) for c in chunks]
+            sc = np.concatenate([p.result()[0] for p in parts])
+            ms_b.append((time.perf_counter() - t0) * 1e3)
+            r = loc.global_search(s, len(s), A, **kw).result()
+            same += int(np.argmax(sc)) == int(r.index[0])
+        out["score_poses_all_leaves_ms"] = {"median": med(ms_b), "calls": len(chunks), "frames": a.cpu_frames,
+                                            "best_is_the_searchs_best": same}
+        print(f"score_poses over all {len(P)} leaf poses in {len(chunks)} calls: median {med(ms_b):.1f} ms per scan (host clock, "
+              f"uploads included); its best leaf is the search's on {same} of {a.cpu_frames} frames", flush=True)
     print(json.dumps(out))
 
 
