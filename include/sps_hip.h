@@ -1000,6 +1000,42 @@ int sps_bbs_search(sps_ctx *ctx, const double *pts_dev, const int32_t *n_dev, in
                    double *T_top_dev, int32_t *n_top_dev, int32_t *info_dev, int32_t *trace_dev, void *scratch_dev,
                    void *stream);
 
+/* ---- localiser, scan-matching status ------------------------------------------------------------------------------------
+ * How well does a scan fit the map at a pose: the share of its points with a map point nearby, and their mean squared
+ * distance.  A registration that converges to the wrong place ends with status 0 or 1 like a good one; this measure tells
+ * them apart, on the device, and its verdict word can stand where the registration's status gates what follows it
+ * (sps_ndt_map_update, sps_ndt_map_carve, sps_ukf_correct: all open on (unsigned)word <= 1).    Additive:
+ * sps_version() is unchanged and no call above is touched.
+ *
+ * sps_loc_match_status: pts_dev, n_dev and cap are the thinned points of sps_loc_downsample (sensor frame); T_dev is a
+ *   row-major 4 x 4 on the device (the T_out of an alignment, the T_best of a batch, a pose estimator's pose ...), of which
+ *   the first 12 entries are read.  The map is the context's radius grid (sps_radius_grid_upload): INVALID when none was
+ *   uploaded, and when max_distance is not finite and > 0 or exceeds the grid's cell size (the 27-cell search is exact
+ *   only up to one cell).  NaN thresholds, min_valid < 0 and cap > SPS_MAX_POINTS are INVALID too.
+ *   n = min(cap, max(*n_dev, 0)).  Point i < n is valid iff its three coordinates are finite and either max_range < 0 or
+ *     (px*px + py*py) + pz*pz <= max_range*max_range (the sensor frame; the host squares both radii in float64).
+ *   q = R p + t as in sps_loc_align; the nearest map point over the 27 cells around q exactly as sps_loc_align takes it:
+ *     d2 = (ex*ex + ey*ey) + ez*ez, ties to the lowest map index; q not finite or outside the key range: no neighbour.
+ *   A valid point is an inlier iff it has a neighbour with d2 <= max_distance^2.
+ *   Each workgroup of 32 points adds its inliers' d2 in point order; a second launch with one workgroup adds the rows of
+ *     the ceil(n / 32) workgroups that hold points as launch B of sps_loc_align adds its partial rows (8 runs of
+ *     consecutive rows, each in order, then the runs in order).  Counts are integers.  No float atomics; nothing depends
+ *     on the order in which threads arrive, so two calls give the same bits.
+ *   out_dev: double[4] = (inlier_fraction, matching_error, sum_d2, 0), then int32[4] = (verdict, n_valid, n_inliers, n).
+ *     inlier_fraction = n_inliers / max(n_valid, 1); matching_error = sum_d2 / n_inliers, +inf without inliers (true
+ *     divisions).  verdict: g = gate_in_dev ? *gate_in_dev : 0; (unsigned)g > 1: g (the registration already failed; -1
+ *     stays -1); else g where n_valid >= min_valid && inlier_fraction >= min_inlier_fraction && matching_error <=
+ *     max_error; else SPS_LOC_LOST.
+ *   d2_dev (may be NULL) double[cap]: the inlier's d2; +inf for a valid point that is not an inlier; -1 for a point that is
+ *     not valid; rows >= n are not written.
+ *   Two launches, whatever the data.  scratch_dev: sps_loc_match_status_scratch(cap) bytes (-1 for cap outside [0,
+ *   SPS_MAX_POINTS]).  Never allocates, never synchronises, never raises the sticky error. */
+#define SPS_LOC_LOST 4
+int64_t sps_loc_match_status_scratch(int64_t cap);
+int sps_loc_match_status(sps_ctx *ctx, const double *pts_dev, const int32_t *n_dev, int64_t cap, const double *T_dev,
+                         const int32_t *gate_in_dev, double max_distance, double max_range, double min_inlier_fraction,
+                         double max_error, int min_valid, double *out_dev, double *d2_dev, void *scratch_dev, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

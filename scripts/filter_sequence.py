@@ -31,11 +31,15 @@ the end the absolute pose error evo_ape prints by default.  ``--global-start`` (
 initial pose from ``NDTLocaliser.localise_global`` on the first raw scan instead of from the sequence (``--global-resolution``,
 ``--global-map-z``, ``--global-scan-z``, ``--global-yaw-steps``, ``--global-levels``, ``--global-frontier``; the defaults are
 the slice chosen for sps_amd.synthetic: profiles/localiser_global/README.md) and prints the selected leaf, the certificate
-and the error against the sequence's first pose in ``global:`` lines.  ``--traj-out FILE`` writes the estimated trajectory
+and the error against the sequence's first pose in ``global:`` lines.  ``--match-status [DIST[,RANGE]]`` (with ``--min-inlier-fraction F``) follows every
+registration by the scan-matching status at its pose and prints it in ``match:`` lines, ``--recover-global N`` registers the frame
+after N flagged ones by the global search, and ``--inject-jump FRAME,DX,DY,YAW`` kidnaps the sensor to try both.
+``--traj-out FILE`` writes the estimated trajectory
 (stamp + the top three rows of the pose per line).
 """
 from __future__ import annotations
 
+import math
 import os
 import sys
 import tempfile
@@ -146,36 +150,50 @@ def hypothesis_grid(counts, steps, option="--hypotheses", step_option="--hypothe
 def closed_loop(name, f, pc_map, replay, finish, traj_out, which="icp", hypotheses=None, search=None, update_map=False,
                 cell_capacity=None, max_cell_points=0, resolutions=None, level_iterations=None, carve_map=False,
                 carve_options=None, level_capacities=None, estimator=None, source=None, coarse_to_fine=False,
-                global_start=None):
+                global_start=None, match_status=None, recover=None, inject=None):
     """--localise: one LocalisationLoop step per frame, scored against the replayed poses.  ``estimator``: None, or the
     options of --estimator ukf (initial_velocity, scan_period, imu: None / a rate in Hz / an array of rows t ax .. gz).
     ``source``: None, or the keywords of NDTLocaliser(source="cells", ...) of --source cells.  ``coarse_to_fine``: hypotheses,
     search and the estimator's device path register on the pyramid of --resolutions.  ``global_start``: None, or the
     options of --global-start (grid: the localiser's global_grid; yaw_steps, frontier, scan_z: of localise_global): the
-    loop's initial pose is then found on the map from the first raw scan, and the sequence's first pose only scores it."""
+    loop's initial pose is then found on the map from the first raw scan, and the sequence's first pose only scores it.
+    ``match_status``: None, or the localiser's match_status of --match-status: every frame's inlier fraction and matching
+    error are printed, and the lost and recovered frames counted at the end.  ``recover``: None, or the options of
+    --recover-global (grid, and the loop's ``recover``).  ``inject``: None, or (frame, P) of --inject-jump: from that frame on
+    the sensor stands at ``T @ P`` instead of T, so its scans are the replayed ones moved by the inverse of P, and the
+    frames are scored against ``T @ P``."""
     from sps_amd.localiser import LocalisationLoop, NDTLocaliser, ScanToMapLocaliser
     from sps_amd.trajectory import ape_translation, rotation_angle, write_trajectory
     skw = source or {}
-    gkw = dict(global_grid=global_start["grid"]) if global_start is not None else {}
+    grid = global_start["grid"] if global_start is not None else recover["grid"] if recover is not None else None
+    gkw = dict(global_grid=grid) if grid is not None else {}
+    mkw = dict(match_status=match_status) if match_status is not None else {}
+    lkw = dict(recover=recover["loop"]) if recover is not None else {}
+    n_lost = n_recovered = 0
     if resolutions is not None and (update_map or carve_map):    # an online pyramid: per level, room for twice its cells
         caps = level_iterations or (30,) * len(resolutions)
         if level_capacities is None:
             xyz = np.ascontiguousarray(pc_map[:, :3], dtype=np.float64)
             level_capacities = tuple(max(2 * len(np.unique(np.floor(xyz / r).astype(np.int64), axis=0)), 4096) for r in resolutions)
         localiser = NDTLocaliser(pc_map[:, :3], resolutions=resolutions, iterations=sum(caps), level_iterations=caps,
-                                 level_capacities=level_capacities, **gkw)
+                                 level_capacities=level_capacities, **gkw, **mkw)
     elif update_map or carve_map:                                # an online map: room for twice the map's cells by default
         n_cells = NDTLocaliser(pc_map[:, :3]).n_cells
-        localiser = NDTLocaliser(pc_map[:, :3], cell_capacity=cell_capacity or max(2 * n_cells, 4096), **skw, **gkw)
+        localiser = NDTLocaliser(pc_map[:, :3], cell_capacity=cell_capacity or max(2 * n_cells, 4096), **skw, **gkw, **mkw)
     elif resolutions is not None:                                # coarse to fine; hypotheses and search keep the single map
                                                                  # unless --coarse-to-fine sends them to the pyramid too
         caps = level_iterations or (30,) * len(resolutions)       # the budget is their sum: it cuts no level short
-        localiser = NDTLocaliser(pc_map[:, :3], resolutions=resolutions, iterations=sum(caps), level_iterations=caps, **gkw)
+        localiser = NDTLocaliser(pc_map[:, :3], resolutions=resolutions, iterations=sum(caps), level_iterations=caps, **gkw, **mkw)
     else:
-        localiser = NDTLocaliser(pc_map[:, :3], **skw, **gkw) if which == "ndt" else ScanToMapLocaliser(pc_map[:, :3])
+        localiser = NDTLocaliser(pc_map[:, :3], **skw, **gkw, **mkw) if which == "ndt" else ScanToMapLocaliser(pc_map[:, :3], **mkw)
     loop, stamps, ref, estimates = None, [], [], []
     for stamp, scan, pose, map_tr in replay:
         T = map_tr @ pose
+        if inject is not None and len(stamps) >= inject[0]:
+            Pi = np.linalg.inv(inject[1])
+            scan = np.array(scan, copy=True)
+            scan[:, :3] = (scan[:, :3].astype(np.float64) @ Pi[:3, :3].T + Pi[:3, 3]).astype(scan.dtype)
+            T = T @ inject[1]
         if loop is None:
             est, T0 = None, T
             if global_start is not None:
@@ -185,7 +203,7 @@ def closed_loop(name, f, pc_map, replay, finish, traj_out, which="icp", hypothes
                 est = PoseEstimator(T0, localiser.device, initial_velocity=estimator["initial_velocity"])
             loop = LocalisationLoop(f, localiser, T0, hypotheses=hypotheses, search=search, update_map=update_map,
                                     max_cell_points=max_cell_points, carve_map=carve_map, carve_options=carve_options,
-                                    estimator=est, coarse_to_fine=coarse_to_fine)
+                                    estimator=est, coarse_to_fine=coarse_to_fine, **lkw)
             if est is not None:
                 print("estimator: ukf  start of the registration: " + ("device pose" if loop.device_guess else "host pose"))
         if estimator is None:
@@ -199,6 +217,11 @@ def closed_loop(name, f, pc_map, replay, finish, traj_out, which="icp", hypothes
         err_r = float(np.degrees(rotation_angle(step.pose, T)))
         print(f"[{stamp}] loc: {p.status:d} {p.iterations:d} {p.n_corr:d} {p.rmse:.4f} | {err_t:.4f} {err_r:.4f}"
               + (f" | {p.n_sources:d} sources" if source else "") + (" (flagged: the guess is kept)" if step.flagged else ""))
+        if step.match is not None:
+            m = step.match
+            n_lost, n_recovered = n_lost + bool(m.lost), n_recovered + bool(step.recovered)
+            print(f"[{stamp}] match: {m.inlier_fraction:.4f} {m.matching_error:.5f} | {m.n_inliers:d} of {m.n_valid:d} points"
+                  + (" (lost)" if m.lost else "") + (" (recovered by the global search)" if step.recovered else ""))
         if p.levels is not None:
             print(f"[{stamp}] levels: slots per level " + " ".join(str(int((p.levels == l).sum())) for l in range(len(resolutions))))
         u = step.batch.map_update if step.batch is not None else p.map_update
@@ -226,6 +249,8 @@ def closed_loop(name, f, pc_map, replay, finish, traj_out, which="icp", hypothes
         if estimates:
             ape = ape_translation(estimates, ref)
             print(f"APE translation (m) of the estimator over {len(stamps)} frames: " + " ".join(f"{k}: {v:.4f}" for k, v in ape.items()))
+    if match_status is not None and stamps:
+        print(f"scan matching over {len(stamps)} frames: lost {n_lost:d} recovered {n_recovered:d}")
     if traj_out:
         write_trajectory(traj_out, stamps, loop.poses if loop is not None else [])
 
@@ -337,6 +362,20 @@ def frame_motion(estimator, k):
 @click.option("--global-levels", "global_levels", type=int, default=3, help="with --global-start: pooled levels of the grid")
 @click.option("--global-frontier", "global_frontier", type=int, default=16384,
               help="with --global-start: nodes kept per level of the search")
+@click.option("--match-status", "match_status", type=str, default=None, is_flag=False, flag_value="0.5",
+              help="with --localise: DIST[,RANGE] (default 0.5): every registration is followed by the scan-matching status at "
+                   "its pose -- the share of the thinned points within RANGE m of the sensor (default: all) that have a map "
+                   "point within DIST m, and their mean squared distance -- printed per frame")
+@click.option("--min-inlier-fraction", "min_inlier_fraction", type=float, default=0.0,
+              help="with --match-status: a frame whose inlier fraction is below this is lost: flagged, the guess kept, the "
+                   "online map and the estimator left alone")
+@click.option("--recover-global", "recover_global", type=int, default=None,
+              help="with --localiser ndt: after N flagged frames in a row the next frame is registered by the global search "
+                   "(the --global-* options) instead of from the guess")
+@click.option("--inject-jump", "inject_jump", type=str, default=None,
+              help="with --localise: FRAME,DX,DY,YAW -- from that frame on the sensor is moved by (DX, DY) m and turned by YAW "
+                   "degrees in its own frame against the replayed pose, unknown to the loop: a kidnap to test --match-status "
+                   "and --recover-global with")
 @click.option("--estimator", "estimator", type=click.Choice(("ukf",)), default=None,
               help="with --localise: the guess of every frame is the prediction of the device UKF pose estimator, which the "
                    "registered pose corrects; a second APE line is the estimator's")
@@ -351,20 +390,49 @@ def main(name, weights, sequence, config, epsilon, out_dir, n_synth, localise, w
          search_counts, search_steps, update_map, cell_capacity, max_cell_points, carve_map, carve_miss_frames, carve_sigma,
          resolutions, level_iterations, coarse_to_fine, level_capacities, source, source_resolution, source_min_points,
          estimator, initial_velocity, scan_period, imu_rate, imu_file, global_start, global_resolution, global_map_z,
-         global_scan_z, global_yaw_steps, global_levels, global_frontier):
+         global_scan_z, global_yaw_steps, global_levels, global_frontier, match_status, min_inlier_fraction, recover_global,
+         inject_jump):
     if global_start and (which != "ndt" or not localise):
         raise click.UsageError("--global-start needs --localise --localiser ndt")
     if global_start and source == "cells":
         raise click.UsageError("--global-start takes no --source cells: the search matches points")
-    if global_start:
+    if match_status is not None:
+        if not localise:
+            raise click.UsageError("--match-status needs --localise")
+        try:
+            v = [float(x) for x in match_status.split(",")]
+        except ValueError:
+            v = []
+        if not 1 <= len(v) <= 2:
+            raise click.UsageError("--match-status takes DIST[,RANGE]")
+        match_status = dict(max_distance=v[0], min_inlier_fraction=min_inlier_fraction, **(dict(max_range=v[1]) if len(v) == 2 else {}))
+    elif min_inlier_fraction:
+        raise click.UsageError("--min-inlier-fraction needs --match-status")
+    if recover_global is not None and (which != "ndt" or not localise or source == "cells" or recover_global < 1):
+        raise click.UsageError("--recover-global needs N >= 1 and --localise --localiser ndt without --source cells")
+    want_recover = recover_global is not None
+    inject = None
+    if inject_jump is not None:
+        if not localise:
+            raise click.UsageError("--inject-jump needs --localise")
+        try:
+            k, dx, dy, yaw = (float(x) for x in inject_jump.split(","))
+        except ValueError:
+            raise click.UsageError("--inject-jump takes FRAME,DX,DY,YAW")
+        c, sn = math.cos(math.radians(yaw)), math.sin(math.radians(yaw))
+        inject = (int(k), np.array([[c, -sn, 0.0, dx], [sn, c, 0.0, dy], [0.0, 0.0, 1.0, 0.0], [0.0, 0.0, 0.0, 1.0]]))
+    if global_start or want_recover:
         try:
             slices = [tuple(float(v) for v in z.split(",")) for z in (global_map_z, global_scan_z)]
         except ValueError:
             slices = [()]
         if any(len(z) != 2 for z in slices):
             raise click.UsageError("--global-map-z and --global-scan-z take LO,HI")
-        global_start = dict(grid=dict(resolution=global_resolution, map_z=slices[0], levels=global_levels), scan_z=slices[1],
-                            yaw_steps=global_yaw_steps, frontier=global_frontier)
+        global_opts = dict(grid=dict(resolution=global_resolution, map_z=slices[0], levels=global_levels), scan_z=slices[1],
+                           yaw_steps=global_yaw_steps, frontier=global_frontier)
+        global_start = global_opts if global_start else None
+        recover_global = dict(grid=global_opts["grid"], loop=dict(after=recover_global, yaw_steps=global_yaw_steps,
+                                                                  frontier=global_frontier, scan_z=slices[1])) if want_recover else None
     else:
         global_start = None
     if coarse_to_fine and (resolutions is None or (hyp_counts is None and search_counts is None and estimator is None)):
@@ -427,6 +495,9 @@ def main(name, weights, sequence, config, epsilon, out_dir, n_synth, localise, w
         if (hyp_counts is not None or search_counts is not None) and not coarse_to_fine:
             raise click.UsageError("--resolutions with --update-map or --carve-map takes no --hypotheses and no --search: they "
                                    "register on the single map, which stays static")
+        if recover_global is not None and not coarse_to_fine:
+            raise click.UsageError("--resolutions with --update-map or --carve-map takes no --recover-global without "
+                                   "--coarse-to-fine: the global search registers on the single map, which stays static")
     if update_map and which != "ndt":
         raise click.UsageError("--update-map needs --localise --localiser ndt")
     if max_cell_points and not update_map:
@@ -478,7 +549,7 @@ def main(name, weights, sequence, config, epsilon, out_dir, n_synth, localise, w
     if localise:
         closed_loop(name, f, pc_map, replay, finish, traj_out, which or "icp", hypotheses, search, update_map, cell_capacity,
                     max_cell_points, resolutions, level_iterations, carve_map, carve_options or None, level_capacities,
-                    estimator, source, coarse_to_fine, global_start)
+                    estimator, source, coarse_to_fine, global_start, match_status, recover_global, inject)
     elif traj_out:
         raise click.UsageError("--traj-out needs --localise")
     in_flight, prev_pose = None, None

@@ -129,6 +129,9 @@ def _load() -> C.CDLL:
         "sps_loc_align_scratch": (i64, [i64]),
         "sps_loc_downsample": (i32, [vp, vp, i64, i64, vp, C.c_double, vp, i64, vp, vp, vp]),
         "sps_loc_align": (i32, [vp, vp, vp, i64, vp, i32, i32, C.c_double, C.c_double, vp, vp, vp, vp, vp, vp]),
+        "sps_loc_match_status_scratch": (i64, [i64]),
+        "sps_loc_match_status": (i32, [vp, vp, vp, i64, vp, vp, C.c_double, C.c_double, C.c_double, C.c_double, i32, vp, vp, vp,
+                                       vp]),
         "sps_ndt_align_scratch": (i64, [i64]),
         "sps_ndt_map_build": (i32, [vp, vp, vp, vp, vp, i64, i64, C.c_double, i32, C.c_double, vp]),
         "sps_ndt_map_cells": (i32, [vp, vp, vp, vp, vp, vp]),
@@ -204,6 +207,7 @@ EXPORTS = ["sps_last_error", "sps_version", "sps_ctx_create", "sps_ctx_destroy",
            "sps_lts_destroy", "sps_lts_project", "sps_lts_forward", "sps_lts_check", "sps_lts_tap",
            "sps_forward_head_n", "sps_transform_rows", "sps_transform_points_n", "sps_radius_crop", "sps_label_filter",
            "sps_loc_downsample_scratch", "sps_loc_align_scratch", "sps_loc_downsample", "sps_loc_align",
+           "sps_loc_match_status_scratch", "sps_loc_match_status",
            "sps_ndt_align_scratch", "sps_ndt_map_build", "sps_ndt_map_cells", "sps_ndt_align",
            "sps_ndt_align_batch_scratch", "sps_ndt_align_batch",
            "sps_ndt_score_scratch", "sps_ndt_score_poses", "sps_ndt_top_poses",
@@ -477,6 +481,14 @@ class Context:
                   T_out_ptr: int, status_ptr: int, trace_ptr, normal_ptr, scratch_ptr: int, stream: int):
         check(lib.sps_loc_align(self.handle, pts_ptr, n_dev_ptr, int(cap), self._mat(T_init), int(iters), int(min_corr),
                                 float(tol_t), float(tol_r), T_out_ptr, status_ptr, trace_ptr, normal_ptr, scratch_ptr, stream))
+
+    # ---- localiser, scan-matching status (include/sps_hip.h, "localiser, scan-matching status") ----
+    def loc_match_status(self, pts_ptr, n_dev_ptr: int, cap: int, T_dev_ptr: int, gate_in_ptr, max_distance: float,
+                         max_range: float, min_inlier_fraction: float, max_error: float, min_valid: int, out_ptr: int, d2_ptr,
+                         scratch_ptr: int, stream: int):
+        check(lib.sps_loc_match_status(self.handle, pts_ptr, n_dev_ptr, int(cap), T_dev_ptr, gate_in_ptr, float(max_distance),
+                                       float(max_range), float(min_inlier_fraction), float(max_error), int(min_valid), out_ptr,
+                                       d2_ptr, scratch_ptr, stream))
 
     # ---- NDT localiser (include/sps_hip.h, "NDT localiser") ----
     def ndt_map_build(self, keys_ptr, start_ptr, pts_ptr, xyz_ptr, n_cells: int, n_map: int, resolution: float,

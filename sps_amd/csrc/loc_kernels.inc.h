@@ -121,10 +121,55 @@ __device__ inline double loc_dot3(const double a[3], const double b[3]) {
   return loc_add(loc_add(loc_mul(a[0], b[0]), loc_mul(a[1], b[1])), loc_mul(a[2], b[2]));
 }
 
-// Launch A.  One wave per scan point: q = R p + t; lanes 0..26 look up the 27 cells around q, then all 64 lanes stride
-// over the cells' map points with the exact test d2 = (ex*ex + ey*ey) + ez*ez <= r2; the wave's minimum is taken over
-// (d2, map index), so ties go to the lowest map index.  Lane l < 29 then forms term l of the point, the workgroup adds
-// its LOC_PTS points in point order, and thread l writes entry l of the workgroup's partial row.
+// The nearest map point of q within d2 <= r2, by a group of W consecutive lanes of a wave (all W lanes call, with the same q
+// and r2; lane = the lane's index in its group; W = 64: the whole wave): the lanes look up the 27 cells around q, one or, for
+// W < 27, two each, then all W lanes stride over the cells' map points with the exact test d2 = (ex*ex + ey*ey) + ez*ez
+// <= r2; the group's minimum is taken over (d2, map index), so ties go to the lowest map index and the result does not
+// depend on W.  Every lane gets best = that d2 and best_j = that index; best_j = 0x7FFFFFFF where there is none (q not finite
+// or beyond the key range included).  The one definition behind k_loc_assoc and k_loc_match (loc_match_kernels.inc.h).
+template <int W>
+__device__ inline void loc_nearest(const RadiusGrid &g, const double q[3], double r2, int lane, double &best, int &best_j) {
+  static_assert(W == 64 || W == 32 || W == 16, "27 cells in at most two rounds of W lanes");
+  constexpr int NC = (27 + W - 1) / W;
+  long long cx, cy, cz;
+  int c_lo[NC], c_hi[NC];
+  const bool in_range = radius_cell(q[0], g.cell_size, cx) && radius_cell(q[1], g.cell_size, cy) && radius_cell(q[2], g.cell_size, cz);
+#pragma unroll
+  for (int u = 0; u < NC; ++u) {
+    const int cell = lane + u * W;
+    c_lo[u] = c_hi[u] = 0;
+    if (cell < 27 && in_range) {
+      const int s = hash_find_slot(g.h, radius_key(cx + (cell % 3 - 1), cy + ((cell / 3) % 3 - 1), cz + (cell / 9 - 1)));
+      if (s >= 0) {
+        const int c = g.h.rank[s];
+        c_lo[u] = g.cell_start[c], c_hi[u] = g.cell_start[c + 1];
+      }
+    }
+  }
+  best = INFINITY;
+  best_j = 0x7FFFFFFF;
+  for (int c = 0; c < 27; ++c) {
+    const int u = NC == 1 ? 0 : c / W;
+    const int lo = __shfl(NC == 1 ? c_lo[0] : (u ? c_lo[NC - 1] : c_lo[0]), c % W, W);
+    const int hi = __shfl(NC == 1 ? c_hi[0] : (u ? c_hi[NC - 1] : c_hi[0]), c % W, W);
+    for (int t = lo + lane; t < hi; t += W) {
+      const int j = g.cell_pts[t];
+      const double ex = q[0] - g.xyz[(size_t)j * 3], ey = q[1] - g.xyz[(size_t)j * 3 + 1], ez = q[2] - g.xyz[(size_t)j * 3 + 2];
+      const double d2 = loc_add(loc_add(loc_mul(ex, ex), loc_mul(ey, ey)), loc_mul(ez, ez));
+      if (d2 <= r2 && (d2 < best || (d2 == best && j < best_j))) best = d2, best_j = j;
+    }
+  }
+#pragma unroll
+  for (int o = W / 2; o > 0; o >>= 1) {
+    const double od = __shfl_xor(best, o, W);
+    const int oj = __shfl_xor(best_j, o, W);
+    if (od < best || (od == best && oj < best_j)) best = od, best_j = oj;
+  }
+}
+
+// Launch A.  One wave per scan point: q = R p + t, then loc_nearest within the grid's radius.  Lane l < 29 then forms
+// term l of the point, the workgroup adds its LOC_PTS points in point order, and thread l writes entry l of the
+// workgroup's partial row.
 __global__ __launch_bounds__(256) void k_loc_assoc(const double *__restrict__ pts, const int *__restrict__ n_dev, int cap,
                                                     RadiusGrid g, const double *__restrict__ T, const int *__restrict__ done,
                                                     double *__restrict__ partial) {
@@ -144,32 +189,9 @@ __global__ __launch_bounds__(256) void k_loc_assoc(const double *__restrict__ pt
       const double px = pts[(size_t)i * 3], py = pts[(size_t)i * 3 + 1], pz = pts[(size_t)i * 3 + 2];
       double q[3];
       loc_transform(R, px, py, pz, q);
-      long long cx, cy, cz;
-      int c_lo = 0, c_hi = 0;
-      if (lane < 27 && radius_cell(q[0], g.cell_size, cx) && radius_cell(q[1], g.cell_size, cy) && radius_cell(q[2], g.cell_size, cz)) {
-        const int s = hash_find_slot(g.h, radius_key(cx + (lane % 3 - 1), cy + ((lane / 3) % 3 - 1), cz + (lane / 9 - 1)));
-        if (s >= 0) {
-          const int c = g.h.rank[s];
-          c_lo = g.cell_start[c], c_hi = g.cell_start[c + 1];
-        }
-      }
-      double best = INFINITY;
-      int best_j = 0x7FFFFFFF;
-      for (int c = 0; c < 27; ++c) {
-        const int lo = __shfl(c_lo, c, 64), hi = __shfl(c_hi, c, 64);
-        for (int t = lo + lane; t < hi; t += 64) {
-          const int j = g.cell_pts[t];
-          const double ex = q[0] - g.xyz[(size_t)j * 3], ey = q[1] - g.xyz[(size_t)j * 3 + 1], ez = q[2] - g.xyz[(size_t)j * 3 + 2];
-          const double d2 = loc_add(loc_add(loc_mul(ex, ex), loc_mul(ey, ey)), loc_mul(ez, ez));
-          if (d2 <= g.r2 && (d2 < best || (d2 == best && j < best_j))) best = d2, best_j = j;
-        }
-      }
-#pragma unroll
-      for (int o = 32; o > 0; o >>= 1) {
-        const double od = __shfl_xor(best, o, 64);
-        const int oj = __shfl_xor(best_j, o, 64);
-        if (od < best || (od == best && oj < best_j)) best = od, best_j = oj;
-      }
+      double best;
+      int best_j;
+      loc_nearest<64>(g, q, g.r2, lane, best, best_j);
       if (best_j != 0x7FFFFFFF && lane < LOC_TERMS) {
         const int j = best_j;
         const double e[3] = {q[0] - g.xyz[(size_t)j * 3], q[1] - g.xyz[(size_t)j * 3 + 1], q[2] - g.xyz[(size_t)j * 3 + 2]};

@@ -148,6 +148,7 @@ int fail(int code, const char *fmt, ...) {
 #include "baseline_kernels.inc.h"
 #include "sps_filter_kernels.inc.h"
 #include "loc_kernels.inc.h"
+#include "loc_match_kernels.inc.h"
 #include "ndt_kernels.inc.h"
 #include "ndt_batch_kernels.inc.h"
 #include "ndt_search_kernels.inc.h"
@@ -2229,6 +2230,7 @@ int sps_get_feature(sps_ctx *c, const char *name, float *out_dev, int64_t *rows,
 #include "lts_host.inc.h"
 #include "baseline_host.inc.h"
 #include "loc_host.inc.h"
+#include "loc_match_host.inc.h"
 #include "ndt_host.inc.h"
 #include "ndt_batch_host.inc.h"
 #include "ndt_search_host.inc.h"

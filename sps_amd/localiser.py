@@ -53,6 +53,11 @@ level, coarsest first.  The single map at ``resolution`` stays static.
 frontier, and says how many of its best leaves are provably the exhaustive search's; ``localise_global`` hands those leaves
 to the batched registration on the device.
 
+Either localiser takes ``match_status=dict(...)`` (C ABI: "localiser, scan-matching status"): the share of the
+scan's points with a map point nearby at the pose handed on, and their mean squared distance, follow every registration on
+the device, and their verdict closes the gates of the map update, the carve and the estimator on a registration that
+converged to the wrong place; ``LocalisationLoop(..., recover=...)`` answers such frames through the global search.
+
 ``LocalisationLoop`` closes the loop for any of the seven filters of scripts/filter_sequence.py, around either localiser.
 """
 from __future__ import annotations
@@ -67,8 +72,55 @@ from . import _native
 from .baseline_filters import _device_of, _pose
 
 CONVERGED, EXHAUSTED, FEW_CORRESPONDENCES, SINGULAR = 0, 1, 2, 3
+LOST = 4                       # SPS_LOC_LOST: a verdict of the scan-matching status, never a registration's status
 STATUS_NAMES = {CONVERGED: "converged", EXHAUSTED: "iterations exhausted", FEW_CORRESPONDENCES: "too few correspondences",
-                SINGULAR: "singular system"}
+                SINGULAR: "singular system", LOST: "lost: the scan does not match the map at the pose"}
+
+MATCH_DEFAULTS = dict(max_distance=0.5, max_range=None, min_inlier_fraction=0.0, max_error=math.inf, min_valid=1)
+MATCH_WORDS = 6                # doubles of a status: (inlier_fraction, matching_error, sum_d2, 0) | int32 (verdict, n_valid, n_inliers, n)
+
+
+@dataclass
+class MatchStatus:
+    inlier_fraction: float     # n_inliers / max(n_valid, 1)
+    matching_error: float      # the inliers' mean squared distance to their nearest map point (inf without inliers)
+    n_valid: int               # thinned points that are finite and within max_range
+    n_inliers: int             # of those, the points with a map point within max_distance
+    verdict: int               # the registration's gate word where it had failed (2, 3, -1); else that word, or LOST
+    lost: bool                 # verdict == LOST
+
+
+def _match_of(words) -> MatchStatus:
+    """the MatchStatus of the MATCH_WORDS float64 words the device wrote"""
+    verdict, n_valid, n_in, _ = (int(x) for x in words[4:6].view(np.int32))
+    return MatchStatus(float(words[0]), float(words[1]), n_valid, n_in, verdict, verdict == LOST)
+
+
+def _checked_match(match_status):
+    """None, or the options of the scan-matching status with the defaults filled in, before any device work"""
+    if match_status is None:
+        return None
+    unknown = set(match_status) - set(MATCH_DEFAULTS)
+    if unknown:
+        raise ValueError(f"unknown match_status entries {sorted(unknown)}")
+    m = dict(MATCH_DEFAULTS, **match_status)
+    try:
+        m["max_distance"], m["min_inlier_fraction"], m["max_error"] = (float(m[k]) for k in ("max_distance", "min_inlier_fraction",
+                                                                                            "max_error"))
+        m["max_range"] = None if m["max_range"] is None else float(m["max_range"])
+        if m["min_valid"] != int(m["min_valid"]):
+            raise ValueError
+        m["min_valid"] = int(m["min_valid"])
+    except (TypeError, ValueError):
+        raise ValueError("match_status: max_distance, max_range, min_inlier_fraction and max_error must be numbers and "
+                         "min_valid an integer") from None
+    if not (math.isfinite(m["max_distance"]) and m["max_distance"] > 0):
+        raise ValueError("match_status: max_distance must be finite and > 0")
+    if m["max_range"] is not None and not m["max_range"] >= 0:
+        raise ValueError("match_status: max_range must be None or >= 0")
+    if not 0.0 <= m["min_inlier_fraction"] <= 1.0 or not m["max_error"] >= 0 or m["min_valid"] < 0:
+        raise ValueError("match_status: min_inlier_fraction must be in [0, 1], max_error >= 0 and min_valid >= 0")
+    return m
 
 
 @dataclass
@@ -85,6 +137,9 @@ class PoseResult:
     levels: np.ndarray = None  # [iterations] int, the pyramid level every slot ran at (None without a pyramid)
     map_carve: object = None   # MapCarveResult of the frame, with carve=True (an online pyramid: a tuple, one per level)
     n_sources: int = 0         # valid source cells of the scan (NDTLocaliser(source="cells") only; n_corr then counts sources)
+    # MatchStatus at ``pose``, of a localiser with match_status (None without): set by ``result()``, not a field, so the
+    # fields and their positional order stay what they were
+    match = None
 
     @property
     def ok(self) -> bool:
@@ -143,29 +198,32 @@ def _offsets(parts, tail=()):
     return o
 
 
-def _pose_layout(K, with_normal, pyramid=False, L=None, integrate=False, carve=False):
+def _pose_layout(K, with_normal, pyramid=False, L=None, integrate=False, carve=False, match=False):
     """offsets (in doubles) of a frame's one float64 buffer: T_out[16] | status int32[4] | n_points int32 (+ n_sources int32
     in the pad) | trace[K][4] | normal[K][28] | level int32[K] (+ pad) with a pyramid | info int32[4] of the update | info
-    int32[4] of the carve, last (an online pyramid of L levels: int32[L][4] each).  ``hands_on``: the offsets in bytes of
-    the pose the frame hands on and of the int32 that gates what follows it on the device: ``T_out`` and the status"""
+    int32[4] of the carve (an online pyramid of L levels: int32[L][4] each) | the MATCH_WORDS words of the scan-matching
+    status, last, with ``match``.  ``hands_on``: the offsets in bytes of the pose the frame hands on and of the int32 that
+    gates what follows it on the device: ``T_out`` and the status or, with ``match``, the status' verdict"""
     w = 2 if L is None else 2 * L                                    # doubles of one call's info words
     o = _offsets((("T_out", 16), ("status", 2), ("n_points", 1), ("trace", 4 * K), ("normal", 28 * K if with_normal else 0)),
-                 (("levels", (K + 1) // 2 if pyramid else 0), ("update", w if integrate else 0), ("carve", w if carve else 0)))
-    o["hands_on"] = (o["T_out"] * 8, o["status"] * 8)
+                 (("levels", (K + 1) // 2 if pyramid else 0), ("update", w if integrate else 0), ("carve", w if carve else 0),
+                  ("match", MATCH_WORDS if match else 0)))
+    o["hands_on"] = (o["T_out"] * 8, (o["match"] + 4) * 8 if match else o["status"] * 8)
     return o
 
 
-def _batch_layout(K, I, with_normal, integrate=False, carve=False, pyramid=False, L=None):
+def _batch_layout(K, I, with_normal, integrate=False, carve=False, pyramid=False, L=None, match=False):
     """offsets (in doubles) of a batch's one float64 buffer: T_out[K][16] | status int32[K][4] | n_points int32 (+ pad) |
     best int32[4] | T_best[16] | final[K][2] | trace[K][I][4] | normal[K][I][28] | level int32[K][I] (+ pad) of a coarse-to-fine
     batch (``pyramid``) | info int32[4] of the update | info int32[4] of the carve (an online pyramid of L levels: int32[L][4]
-    each).  ``hands_on``, as in ``_pose_layout``: ``T_best`` and ``best[1]``, the selected hypothesis' status, -1 where none
-    was selected"""
+    each) | the MATCH_WORDS words of the scan-matching status with ``match``.  ``hands_on``, as in ``_pose_layout``:
+    ``T_best`` and ``best[1]``, the selected hypothesis' status, -1 where none was selected, or, with ``match``, the verdict"""
     w = 2 if L is None else 2 * L                                    # doubles of one call's info words
     o = _offsets((("T_out", 16 * K), ("status", 2 * K), ("n_points", 1), ("best", 2), ("T_best", 16), ("final", 2 * K),
                   ("trace", 4 * K * I), ("normal", 28 * K * I if with_normal else 0)),
-                 (("levels", (K * I + 1) // 2 if pyramid else 0), ("update", w if integrate else 0), ("carve", w if carve else 0)))
-    o["hands_on"] = (o["T_best"] * 8, o["best"] * 8 + 4)
+                 (("levels", (K * I + 1) // 2 if pyramid else 0), ("update", w if integrate else 0), ("carve", w if carve else 0),
+                  ("match", MATCH_WORDS if match else 0)))
+    o["hands_on"] = (o["T_best"] * 8, (o["match"] + 4) * 8 if match else o["best"] * 8 + 4)
     return o
 
 
@@ -219,14 +277,17 @@ class PendingPose(_Pending):
     """A localisation whose work has been issued; everything lives on the device until result()."""
     _at = 0
 
-    def __init__(self, iters, with_normal, host, event, keep, pyramid=False, n_levels=None, integrate=False, carve=False):
+    def __init__(self, iters, with_normal, host, event, keep, pyramid=False, n_levels=None, integrate=False, carve=False,
+                 match=False):
         super().__init__(host, event, keep)
         self._iters, self._with_normal, self._pyramid = iters, with_normal, pyramid
         self._n_levels = n_levels                                    # an online pyramid: info words per level, tuples out
         self._integrate, self._carve = integrate, carve              # the frame's buffer has their info words
+        self._match = match                                          # and those of the scan-matching status
 
     def _layout(self):
-        return _pose_layout(self._iters, self._with_normal, self._pyramid, self._n_levels, self._integrate, self._carve)
+        return _pose_layout(self._iters, self._with_normal, self._pyramid, self._n_levels, self._integrate, self._carve,
+                            self._match)
 
     def result(self) -> PoseResult:
         h, o = self._wait(), self._layout()
@@ -238,9 +299,12 @@ class PendingPose(_Pending):
         rmse = math.sqrt(trace[-1, 1] / n_corr) if it and n_corr > 0 else float("nan")
         levels = h[o["levels"]:o["update"]].view(np.int32)[:it].astype(np.int64) if self._pyramid else None
         upd = _per_level(_map_update_of, h[o["update"]:o["carve"]].view(np.int32), n_points, L) if self._integrate else None
-        carved = _per_level(_map_carve_of, h[o["carve"]:o["total"]].view(np.int32), n_points, L) if self._carve else None
-        return PoseResult(h[o["T_out"]:o["status"]].reshape(4, 4).copy(), code, it, n_corr, rmse, trace, normal, n_points, upd,
-                          levels, carved, n_sources)
+        carved = _per_level(_map_carve_of, h[o["carve"]:o["match"]].view(np.int32), n_points, L) if self._carve else None
+        res = PoseResult(h[o["T_out"]:o["status"]].reshape(4, 4).copy(), code, it, n_corr, rmse, trace, normal, n_points, upd,
+                         levels, carved, n_sources)
+        if self._match:
+            res.match = _match_of(h[o["match"]:o["total"]])
+        return res
 
 
 @dataclass
@@ -252,14 +316,16 @@ class BatchPoseResult:
     pose: np.ndarray           # 4x4: results[best].pose, or the first start pose when best is -1
     map_update: object = None  # MapUpdateResult of the frame, with integrate=True (an online pyramid: a tuple, one per level)
     map_carve: object = None   # MapCarveResult of the frame, with carve=True (an online pyramid: a tuple, one per level)
+    match: object = None       # MatchStatus at ``pose``, of a localiser with match_status (None without)
 
 
 class PendingPoses(_Pending):
     """A batch of localisations whose work has been issued; everything lives on the device until result()."""
 
     def __init__(self, n_hyp, iters, with_normal, host, event, keep, at=0, integrate=False, carve=False, pyramid=False,
-                 n_levels=None):
+                 n_levels=None, match=False):
         super().__init__(host, event, keep)
+        self._match = match                                          # the batch's buffer has the scan-matching status
         self._n_hyp, self._iters, self._with_normal = n_hyp, iters, with_normal
         self._at = at                                                # doubles in front of the batch's part of the buffer
         self._integrate, self._carve = integrate, carve              # the batch's buffer has their info words
@@ -267,7 +333,7 @@ class PendingPoses(_Pending):
 
     def _layout(self):
         return _batch_layout(self._n_hyp, self._iters, self._with_normal, self._integrate, self._carve, self._pyramid,
-                             self._n_levels)
+                             self._n_levels, self._match)
 
     def result(self) -> BatchPoseResult:
         return self._parse(self._wait())
@@ -293,9 +359,10 @@ class PendingPoses(_Pending):
                                       levels=levels[k, :it].astype(np.int64) if levels is not None else None))
         L = self._n_levels
         upd = _per_level(_map_update_of, h[o["update"]:o["carve"]].view(np.int32), n_points, L) if self._integrate else None
-        carved = _per_level(_map_carve_of, h[o["carve"]:o["total"]].view(np.int32), n_points, L) if self._carve else None
+        carved = _per_level(_map_carve_of, h[o["carve"]:o["match"]].view(np.int32), n_points, L) if self._carve else None
+        match = _match_of(h[o["match"]:o["total"]]) if self._match else None
         return BatchPoseResult(results, final[:, 0].copy(), final[:, 1].astype(np.int64), int(best[0]),
-                               h[o["T_best"]:o["final"]].reshape(4, 4).copy(), upd, carved)
+                               h[o["T_best"]:o["final"]].reshape(4, 4).copy(), upd, carved, match)
 
 
 def pose_grid(along, across, yaw_deg) -> np.ndarray:
@@ -484,22 +551,51 @@ class PendingGlobalLocalisation(_Pending):
         return GlobalLocalisationResult(search, batch, index, batch.pose, batch.map_update, batch.map_carve)
 
 
+class PendingMatch(_Pending):
+    """A scan-matching status whose work has been issued; ``result()`` -> MatchStatus, with ``distances`` (MatchStatus, d2)."""
+
+    def __init__(self, distances, host, event, keep):
+        super().__init__(host, event, keep)
+        self._distances = distances
+
+    def result(self):
+        h = self._wait()
+        m = _match_of(h[:MATCH_WORDS])
+        if not self._distances:
+            return m
+        n = int(h[MATCH_WORDS:MATCH_WORDS + 1].view(np.int32)[0])
+        return m, h[MATCH_WORDS + 1:MATCH_WORDS + 1 + n].copy()
+
+
 class ScanToMapLocaliser:
     """``ScanToMapLocaliser(map_points)(rows, count, T_init)`` -> PoseResult.  The map's uniform grid (cell size =
     ``max_distance``) lives in a native context of the localiser's own, so the grid of the offline item path
     (datasets.blt_dataset.DeviceRadiusSubmap, r = voxel size) is untouched.  ``capacity`` bounds the points that enter
-    the alignment: survivors of the thinning beyond it are dropped."""
+    the alignment: survivors of the thinning beyond it are dropped.
+
+    ``match_status`` (None: nothing is built and nothing changes; a dict with any of ``max_distance`` (0.5), ``max_range``
+    (None), ``min_inlier_fraction`` (0.0), ``max_error`` (inf), ``min_valid`` (1); C ABI: "localiser, scan-matching status";
+    DESIGN.md 8n): every registration is followed on its stream by the scan-matching status at the pose it hands on -- of the
+    thinned points that are finite and within ``max_range`` of the sensor (valid), the share with a map point within
+    ``max_distance`` (inliers), and the inliers' mean squared distance -- and the result's ``match`` carries it.  A
+    registration with status 0 or 1 whose status misses a threshold is *lost* (verdict ``LOST``), and that verdict, not the
+    registration's status, then gates ``integrate``, ``carve`` and ``PoseEstimator.correct_from`` on the device.  The map
+    is the localiser's own grid, so ``max_distance`` may not exceed the localiser's."""
 
     # what only an NDTLocaliser can have: no pyramid, no online map, the scan's points registered as they are
     resolutions = level_iterations = level_capacities = cell_capacity = None
     source = "points"
+    _match_opts = None                                               # no match_status: nothing is built, nothing changes
 
     def __init__(self, map_points, max_distance: float = 1.0, leaf: float = 0.2, iterations: int = 30,
                  min_correspondences: int = 50, tol_t: float = 1e-4, tol_r: float = 1e-5, device="cuda",
-                 capacity: int = 1 << 16):
+                 capacity: int = 1 << 16, match_status: dict = None):
         if not (math.isfinite(max_distance) and max_distance > 0 and math.isfinite(leaf) and leaf > 0):
             raise ValueError("max_distance and leaf must be finite and > 0")
         self.max_distance = float(max_distance)
+        self._match_opts = _checked_match(match_status)
+        if self._match_opts is not None and self._match_opts["max_distance"] > self.max_distance:
+            raise ValueError("match_status: max_distance must not exceed the localiser's max_distance (its grid's cell)")
         self._open(self._map_xyz(map_points), leaf, iterations, min_correspondences, tol_t, tol_r, device, capacity,
                    _native.lib.sps_loc_align_scratch)
 
@@ -535,9 +631,45 @@ class ScanToMapLocaliser:
             self.stream = torch.cuda.current_stream()
             self.ctx = _native.Context(self.device.index)
             self._build_map(xyz)
+            if self._match_opts is not None:
+                self._build_match(xyz)
+                self._match_scratch = torch.empty(_native.lib.sps_loc_match_status_scratch(self.capacity), dtype=torch.uint8,
+                                                  device=self.device)
             self._pts = torch.empty((self.capacity, 3), dtype=torch.float64, device=self.device)
             self._align_scratch = torch.empty(align_scratch_bytes(self.capacity), dtype=torch.uint8, device=self.device)
             self._ds_scratch, self._ds_rows = None, -1
+
+    def _build_match(self, xyz):
+        """the map of the scan-matching status: the ICP's own grid, uploaded by ``_build_map``"""
+
+    def _status(self, n_ptr, T_ptr, gate_in_ptr, out_ptr, s, d2_ptr=None):
+        """the scan-matching status of self._pts (their count at n_ptr) at the device pose at T_ptr into the MATCH_WORDS words
+        at out_ptr, on stream s; ``gate_in_ptr``: the registration's status word, or None"""
+        m = self._match_opts
+        self.ctx.loc_match_status(self._pts.data_ptr(), n_ptr, self.capacity, T_ptr, gate_in_ptr, m["max_distance"],
+                                  -1.0 if m["max_range"] is None else m["max_range"], m["min_inlier_fraction"], m["max_error"],
+                                  m["min_valid"], out_ptr, d2_ptr, self._match_scratch.data_ptr(), s)
+
+    @torch.no_grad()
+    def match_status_at(self, rows, count, T, distances: bool = False) -> "PendingMatch":
+        """The scan-matching status of the rows at any host pose ``T`` (4x4, sensor -> map), ungated: the rows are thinned as
+        ``submit`` thins them and compared with the map as every registration of a localiser with ``match_status`` is
+        (DESIGN.md 8n).  Issued on the current stream; ``result()`` -> MatchStatus, or with ``distances`` (debug)
+        (MatchStatus, float64 [n_points]): per thinned point the squared distance to its nearest map point where it is an
+        inlier, inf where it is valid but no inlier, -1 where it is not valid."""
+        if self._match_opts is None:
+            raise ValueError("match_status_at needs a localiser with match_status")
+        rows = self._checked_rows(rows)
+        Th = _pose(T)
+        if Th is None or not np.isfinite(Th).all():
+            raise ValueError("T must be a finite 4x4 matrix")
+        o = _offsets((("match", MATCH_WORDS), ("n_points", 1), ("d2", self.capacity if distances else 0)))
+
+        def work(out, n_ptr, T_dev, s):
+            base = out.data_ptr()
+            self._status(n_ptr, T_dev.data_ptr(), None, base + o["match"] * 8, s, base + o["d2"] * 8 if distances else None)
+        return PendingMatch(distances, *self._issue(rows, count, o["total"], o["n_points"] * 8, work,
+                                                    np.ascontiguousarray(Th, dtype=np.float64)[None].copy()))
 
     def _downsample_scratch(self, n_max):
         if n_max > self._ds_rows:                                    # grows with the largest scan seen (stream-ordered reuse)
@@ -599,18 +731,23 @@ class ScanToMapLocaliser:
             raise ValueError("T_init must be a finite 4x4 matrix")
         K = self.iterations if iterations is None else int(iterations)
         pyramid = self.resolutions is not None
-        shape = (K, with_normal, pyramid, None if self.level_capacities is None else len(self.level_capacities), integrate, carve)
+        match = self._match_opts is not None
+        shape = (K, with_normal, pyramid, None if self.level_capacities is None else len(self.level_capacities), integrate, carve,
+                 match)
         o = _pose_layout(*shape)
 
         def work(out, n_ptr, _, s):
             base = out.data_ptr()
             T_ptr, gate_ptr = (base + b for b in o["hands_on"])
+            status_ptr = base + o["status"] * 8
             kw = dict(level_ptr=base + o["levels"] * 8 if K else None) if pyramid else {}
-            self._align(n_ptr, T, K, T_ptr, gate_ptr, base + o["trace"] * 8 if K else None,
+            self._align(n_ptr, T, K, T_ptr, status_ptr, base + o["trace"] * 8 if K else None,
                         base + o["normal"] * 8 if with_normal and K else None, s, **kw)
             if self.source == "cells":                               # the valid source cells into the pad behind n_points
                 at = 2 * o["n_points"] + 1
                 out.view(torch.int32)[at:at + 1].copy_(self._n_src[1:2])
+            if match:                                                # its verdict is the gate of what follows
+                self._status(n_ptr, T_ptr, status_ptr, base + o["match"] * 8, s)
             if carve:
                 self._carve(n_ptr, None, T_ptr, gate_ptr, copts, base + o["carve"] * 8, s)
             if integrate:
@@ -731,14 +868,22 @@ class NDTLocaliser(ScanToMapLocaliser):
     ``global_grid`` (None: nothing is built; a dict with any of ``resolution`` (0.5), ``map_z`` = (lo, hi) (everything) and
     ``levels`` (3, at most 7)): the map points of that height slice become an occupancy grid of that edge with ``levels``
     pooled levels on the device, and ``global_search`` / ``localise_global`` find the pose with no start pose.
-    ``capacity`` is then at most 65536, and ``source="cells"`` is refused."""
+    ``capacity`` is then at most 65536, and ``source="cells"`` is refused.
+
+    ``match_status``: as for ScanToMapLocaliser, behind ``submit``, ``submit_batch``, ``submit_from_device``, ``relocalise``
+    and ``localise_global`` (the pose is ``T_best`` for all but the first), on the single map, the pyramid and
+    ``source="cells"``.  A radius grid of cell ``max_distance`` over the points given at construction is uploaded into the
+    localiser's context for it.  The status is taken against those points, not against an online map's Gaussians: with
+    ``update_map`` / ``integrate`` and ``min_inlier_fraction > 0`` the map grows only while that share of the scan still
+    matches the prior map."""
 
     def __init__(self, map_points, resolution: float = 1.0, neighbours: int = 7, leaf: float = 0.2, iterations: int = 30,
                  min_correspondences: int = 50, min_points_per_cell: int = 6, outlier_ratio: float = 0.55,
                  eig_ratio: float = 0.01, tol_t: float = 1e-4, tol_r: float = 1e-5, device="cuda", capacity: int = 1 << 16,
                  cell_capacity: int = None, resolutions=None, level_iterations=None, level_capacities=None,
                  source: str = "points", source_resolution: float = None, source_min_points: int = None,
-                 global_grid: dict = None):
+                 global_grid: dict = None, match_status: dict = None):
+        self._match_opts = _checked_match(match_status)
         self.source, self.source_resolution, self.source_min_points = self._checked_source(
             source, source_resolution, source_min_points, resolution, min_points_per_cell, resolutions, capacity)
         if level_capacities is not None and cell_capacity is not None:
@@ -814,6 +959,18 @@ class NDTLocaliser(ScanToMapLocaliser):
                     device=self.device)
             self._pyr_scratch = torch.empty(_native.lib.sps_ndt_pyramid_align_scratch(self.capacity), dtype=torch.uint8,
                                             device=self.device)
+
+    def _build_match(self, xyz):
+        """the map of the scan-matching status: a radius grid of cell ``max_distance`` over the construction's points, in the
+        localiser's context, which has no other"""
+        from .datasets.blt_dataset import radius_grid_cells
+        d = self._match_opts["max_distance"]
+        if self.n_map:
+            keys, start, pts = radius_grid_cells(xyz, d)
+            self.ctx.radius_grid_upload(keys.contiguous().data_ptr(), start.data_ptr(), pts.data_ptr(), xyz.data_ptr(), len(keys),
+                                        self.n_map, d, d, self.stream.cuda_stream)
+        else:
+            self.ctx.radius_grid_upload(None, None, None, None, 0, 0, d, d, self.stream.cuda_stream)
 
     @staticmethod
     def _checked_source(source, source_resolution, source_min_points, resolution, min_points_per_cell, resolutions, capacity):
@@ -1207,9 +1364,9 @@ class NDTLocaliser(ScanToMapLocaliser):
         return self._checked_rows(rows), copts
 
     def _batch_shape(self, integrate, carve, coarse_to_fine):
-        """the last four arguments of ``_batch_layout`` and of ``PendingPoses``"""
+        """the last five arguments of ``_batch_layout`` and of ``PendingPoses``"""
         online = coarse_to_fine and self.level_capacities is not None
-        return integrate, carve, bool(coarse_to_fine), len(self.level_capacities) if online else None
+        return integrate, carve, bool(coarse_to_fine), len(self.level_capacities) if online else None, self._match_opts is not None
 
     def _issue_batch(self, rows, count, poses, K, with_normal, iterations, integrate, max_cell_points, copts,
                      coarse_to_fine=False):
@@ -1246,6 +1403,8 @@ class NDTLocaliser(ScanToMapLocaliser):
                                      base + o["status"] * 8, trace_ptr, normal_ptr, base + o["final"] * 8,
                                      base + o["best"] * 8, base + o["T_best"] * 8, self._batch_scratch_for(K).data_ptr(), s)
         T_best, gate_ptr = (base + b for b in o["hands_on"])
+        if self._match_opts is not None:                             # its verdict is the gate of what follows
+            self._status(n_ptr, T_best, base + o["best"] * 8 + 4, base + o["match"] * 8, s)
         if carve_opts is not None:
             self._carve(n_ptr, None, T_best, gate_ptr, carve_opts, base + o["carve"] * 8, s)
         if integrate:
@@ -1365,10 +1524,13 @@ class LoopStep:
     pose_result: PoseResult
     guess: np.ndarray          # the pose the frame started from
     pose: np.ndarray           # the corrected pose handed on (the guess when flagged)
-    flagged: bool              # the localiser reported status 2 or 3 (with hypotheses: none of them was selected)
+    flagged: bool              # the localiser reported status 2 or 3 (with hypotheses: none of them was selected), or lost
     batch: BatchPoseResult = None   # with hypotheses: every hypothesis of the frame (pose_result is the selected one's)
     search: RelocalisationResult = None   # a frame registered by the pose search (batch is then its candidates' batch)
     estimate: np.ndarray = None     # with an estimator: its pose after the frame's correction (None without one)
+    match: MatchStatus = None       # the scan-matching status at the registered pose (a localiser with match_status)
+    recovered: bool = False         # a ``recover`` frame whose global search found a pose that is not lost
+    global_result: GlobalLocalisationResult = None   # a ``recover`` frame: what ``localise_global`` gave
 
 
 class LocalisationLoop:
@@ -1428,11 +1590,42 @@ class LocalisationLoop:
     ``coarse_to_fine`` (a localiser with ``resolutions``; False: everything above, unchanged): the frames of ``hypotheses``
     and ``search`` and the estimator's device path are registered on the pyramid (``submit_batch`` / ``relocalise`` /
     ``submit_from_device`` with ``coarse_to_fine=True``).  An online pyramid with ``update_map`` /
-    ``carve_map`` may then take hypotheses and search, and with an estimator the device path is possible with a pyramid."""
+    ``carve_map`` may then take hypotheses and search, and with an estimator the device path is possible with a pyramid.
+
+    A localiser with ``match_status``: a frame whose registration ends with status 0 or 1 but whose scan does
+    not match the map at the registered pose (``match.lost``) is flagged as status 2 / 3 is: it keeps the guess, the map and
+    the estimator stay untouched (the device gate, which is the status' verdict, already saw to that) and ``search`` frames
+    follow as they do after any flagged frame.  ``LoopStep.match`` carries the status.
+
+    ``recover`` (an NDTLocaliser with ``global_grid``; None: no recovery): ``dict(after=N, yaw_steps=A, keep=8,
+    frontier=16384, min_score=1, scan_z=None, T_up=None)``, the last six the arguments of ``localise_global``.  After N >= 1
+    flagged frames in a row the next frame is registered by ``localise_global`` instead of from the guess.  Where a pose is
+    selected and not lost it is handed on, the loop's constant-velocity model is emptied (its motions would span the jump),
+    an estimator is re-initialised at that pose (``PoseEstimator.reset``) and ``LoopStep.recovered`` is set; otherwise the
+    frame is flagged and the count goes on, so the frame after it searches again.  ``LoopStep.global_result`` is what
+    ``localise_global`` gave on such a frame (None on every other).  ``recover`` with ``device_guess=True`` is refused: a
+    recovery frame reads the pose on the host anyway.  So is ``recover`` on an online pyramid with ``update_map`` or
+    ``carve_map`` unless ``coarse_to_fine`` is set, as hypotheses and search are, and an estimator without ``reset``."""
+
+    _RECOVER_DEFAULTS = dict(after=None, yaw_steps=None, keep=8, frontier=16384, min_score=1, scan_z=None, T_up=None)
 
     def __init__(self, filter, localiser, initial_pose, hypotheses=None, search=None, search_keep: int = 8,
                  update_map: bool = False, max_cell_points: int = 0, carve_map: bool = False, carve_options: dict = None,
-                 estimator=None, device_guess=None, coarse_to_fine: bool = False):
+                 estimator=None, device_guess=None, coarse_to_fine: bool = False, recover: dict = None):
+        self.recover, self._flagged_run = None, 0
+        if recover is not None:
+            unknown = set(recover) - set(self._RECOVER_DEFAULTS)
+            if unknown:
+                raise ValueError(f"unknown recover entries {sorted(unknown)}")
+            r = dict(self._RECOVER_DEFAULTS, **recover)
+            if r["after"] is None or r["yaw_steps"] is None or int(r["after"]) < 1 or int(r["yaw_steps"]) < 1:
+                raise ValueError("recover needs after >= 1 and yaw_steps >= 1")
+            if getattr(localiser, "_global", None) is None or not hasattr(localiser, "localise_global"):
+                raise ValueError("recover needs a localiser with an occupancy grid: NDTLocaliser(..., global_grid=dict(...))")
+            if device_guess:
+                raise ValueError("recover and device_guess=True exclude each other: a recovery frame reads the pose on the host")
+            r["after"], r["yaw_steps"] = int(r["after"]), int(r["yaw_steps"])
+            self.recover = r
         from .sps_filters import ConstantVelocityModel
         self.filter, self.localiser = filter, localiser
         # a localiser of the caller's own may have none of these: ScanToMapLocaliser's defaults then stand in
@@ -1450,9 +1643,10 @@ class LocalisationLoop:
         online_pyramid = caps is not None
         if self.update_map and cell_capacity is None and not online_pyramid:
             raise ValueError("update_map needs a localiser with an online map: NDTLocaliser(..., cell_capacity=N)")
-        if online_pyramid and (update_map or carve_map) and (hypotheses is not None or search is not None) \
-                and not self.coarse_to_fine:
-            raise ValueError("an online pyramid is updated and carved by the plain registration only: no hypotheses, no search")
+        if online_pyramid and (update_map or carve_map) and (hypotheses is not None or search is not None
+                                                             or self.recover is not None) and not self.coarse_to_fine:
+            raise ValueError("an online pyramid is updated and carved by the plain registration only: no hypotheses, no search, "
+                             "no recover (unless coarse_to_fine)")
         # the keyword arguments every registration of the loop gets: none unless the map is updated
         self._kw = dict(integrate=True, max_cell_points=self.max_cell_points) if self.update_map else {}
         self.carve_map = bool(carve_map)
@@ -1487,6 +1681,8 @@ class LocalisationLoop:
         else:
             if not all(hasattr(estimator, a) for a in ("predict", "predict_imu", "pose_dev", "correct_from", "snapshot")):
                 raise TypeError("estimator must be a PoseEstimator")
+            if self.recover is not None and not hasattr(estimator, "reset"):
+                raise TypeError("recover needs an estimator with reset (PoseEstimator): a recovered pose re-initialises it")
             takes_none = (hasattr(filter, "add_pose") or type(filter).__name__ == "LTSFilter"
                           or getattr(filter, "takes_pose", True) is False)
             possible = (takes_none and hasattr(localiser, "submit_from_device") and (resolutions is None or self.coarse_to_fine)
@@ -1494,7 +1690,7 @@ class LocalisationLoop:
             if device_guess and not possible:
                 raise ValueError("device_guess=True needs a filter that takes no pose from the loop and an NDTLocaliser without "
                                  "a pyramid, hypotheses or search")
-            self.device_guess = possible if device_guess is None else bool(device_guess)
+            self.device_guess = (possible and self.recover is None) if device_guess is None else bool(device_guess)
         self._est_guess, self._est_wait, self._frames = None, None, 0
         self.initial_pose = np.array(_pose(initial_pose), dtype=np.float64)
         self.model = ConstantVelocityModel()
@@ -1528,10 +1724,12 @@ class LocalisationLoop:
         """[P, 4, 4]: ``guess @ search[k]``"""
         return np.stack([guess @ d for d in self.search])
 
-    def _queue_correction(self, pose_pend):
-        """with an estimator: its correction behind the registration just issued, then a copy of its state for the host"""
+    def _queue_correction(self, pose_pend, correct=True):
+        """with an estimator: its correction behind the registration just issued, then a copy of its state for the host.  A
+        recovery frame queues no correction (``correct`` false): its pose re-initialises the estimator, or is not handed on"""
         if self.estimator is not None:
-            self.estimator.correct_from(pose_pend)
+            if correct:
+                self.estimator.correct_from(pose_pend)
             self._est_wait = self.estimator.snapshot()
 
     def _predict(self, imu, dt):
@@ -1557,7 +1755,11 @@ class LocalisationLoop:
                 return self._register(scan, None, "submit_from_device", (self.estimator.pose_dev,), self._c2f, self._read_batch)
             self._est_guess = self.estimator.pose_dev.cpu().numpy().astype(np.float64)   # the one more synchronisation
         guess = self.guess()
-        if self.search is not None and self._search_next:
+        if self.recover is not None and self._flagged_run >= self.recover["after"]:
+            r = self.recover
+            kw = dict(self._c2f, **{k: r[k] for k in ("keep", "frontier", "min_score", "scan_z", "T_up")})
+            out = self._register(scan, guess, "localise_global", (r["yaw_steps"],), kw, self._read_global, recovering=True)
+        elif self.search is not None and self._search_next:
             out = self._register(scan, guess, "relocalise", (self.search_poses(guess),), dict(self._c2f, keep=self.search_keep),
                                  self._read_search)
         elif self.hypotheses is not None:
@@ -1567,23 +1769,37 @@ class LocalisationLoop:
         self._search_next = out.flagged
         return out
 
-    # how a registration's result reads: -> (flagged, the pose it hands on, PoseResult, BatchPoseResult, RelocalisationResult)
+    # how a registration's result reads: -> (flagged, the pose it hands on, PoseResult, BatchPoseResult, RelocalisationResult,
+    # MatchStatus or None); a result of the caller's own localiser may have no ``match``
     @staticmethod
-    def _read_pose(pres):
-        return pres.status in (FEW_CORRESPONDENCES, SINGULAR), pres.pose, pres, None, None
+    def _lost(match):
+        return match is not None and bool(match.lost)
 
-    @staticmethod
-    def _read_batch(bres):
-        return bres.best < 0, bres.pose, bres.results[max(bres.best, 0)], bres, None
+    @classmethod
+    def _read_pose(cls, pres):
+        m = getattr(pres, "match", None)
+        return pres.status in (FEW_CORRESPONDENCES, SINGULAR) or cls._lost(m), pres.pose, pres, None, None, m
 
-    @staticmethod
-    def _read_search(sres):
-        return sres.index < 0, sres.pose, sres.batch.results[max(sres.batch.best, 0)], sres.batch, sres
+    @classmethod
+    def _read_batch(cls, bres):
+        m = getattr(bres, "match", None)
+        return bres.best < 0 or cls._lost(m), bres.pose, bres.results[max(bres.best, 0)], bres, None, m
+
+    @classmethod
+    def _read_search(cls, sres):
+        m = getattr(sres.batch, "match", None)
+        return sres.index < 0 or cls._lost(m), sres.pose, sres.batch.results[max(sres.batch.best, 0)], sres.batch, sres, m
+
+    @classmethod
+    def _read_global(cls, gres):
+        m = getattr(gres.batch, "match", None)
+        return gres.index < 0 or cls._lost(m), gres.pose, gres.batch.results[max(gres.batch.best, 0)], gres.batch, None, m
 
     # the localiser's entry points that take a filter's pending frame in place of (rows, count)
-    _FILTERED = dict(submit="submit_filtered", submit_batch="submit_filtered_batch", relocalise="relocalise_filtered")
+    _FILTERED = dict(submit="submit_filtered", submit_batch="submit_filtered_batch", relocalise="relocalise_filtered",
+                     localise_global="localise_global_filtered")
 
-    def _register(self, scan, guess, method, args, kw, read) -> LoopStep:
+    def _register(self, scan, guess, method, args, kw, read, recovering=False) -> LoopStep:
         """One frame through the filter and ``localiser.<method>(rows, count, *args, **kw)``; ``read`` (above) reads its
         result.  Where the filter's pending frame exposes its device rows, the registration and the estimator's correction
         are queued before the filter's ``result()``, so nothing synchronises between filter and localiser; otherwise they
@@ -1596,21 +1812,30 @@ class LocalisationLoop:
                 pose_pend = getattr(self.localiser, self._FILTERED[method])(pend, *args, **kw)
             else:
                 pose_pend = getattr(self.localiser, method)(pend._filtered, pend.count_dev, *args, **kw)
-            self._queue_correction(pose_pend)
+            self._queue_correction(pose_pend, not recovering)
             fres = pend.result()
         else:
             fres = pend.result()
             kept = fres.filtered
             pose_pend = getattr(self.localiser, method)(kept, len(kept), *args, **kw)
-            self._queue_correction(pose_pend)
-        flagged, pose, pres, bres, sres = read(pose_pend.result())
+            self._queue_correction(pose_pend, not recovering)
+        res = pose_pend.result()
+        flagged, pose, pres, bres, sres, match = read(res)
         estimate = None
         if self.estimator is not None:
             wait, self._est_wait = self._est_wait, None
             state, predicted = wait()
             estimate, guess = state.pose, predicted if guess is None else guess
+        recovered = recovering and not flagged
+        if recovered:                                                # the model's motions span the jump
+            self.model.poses = []
+            if self.estimator is not None:
+                self.estimator.reset(pose)
+                estimate = np.array(pose, dtype=np.float64)
+        self._flagged_run = self._flagged_run + 1 if flagged else 0
         self._hand_on(guess if flagged else pose)
-        return LoopStep(fres, pres, guess, self.poses[-1], flagged, bres, sres, estimate)
+        return LoopStep(fres, pres, guess, self.poses[-1], flagged, bres, sres, estimate, match, recovered,
+                        res if recovering else None)
 
     def _hand_on(self, pose):
         """the frame's corrected pose to the loop's model, to the filter's ``add_pose`` where it has one, and to ``poses``"""

@@ -89,12 +89,27 @@ class PoseEstimator:
             base = self._buf.data_ptr()
             self._state_ptr, self._pred_ptr = base, base + words * 8
             self._pinfo_ptr, self._cinfo_ptr = base + (words + 16) * 8, base + (words + 18) * 8
-            _native.check(_native.lib.sps_ukf_init(self._state_ptr, _native.Context._mat(T), (C.c_double * 3)(*v.tolist()), p0,
-                                                   torch.cuda.current_stream().cuda_stream))
-            # the predicted pose before any prediction is the initial one (n_imu = 0 only writes the pose)
-            _native.check(_native.lib.sps_ukf_predict(self._state_ptr, None, 0, self._Q, self._pred_ptr, self._pinfo_ptr,
-                                                      torch.cuda.current_stream().cuda_stream))
+        self._p0 = p0
+        self._init(T, v)
         self._keep = None
+
+    def _init(self, T, v):
+        with torch.cuda.device(self.device):
+            st = torch.cuda.current_stream().cuda_stream
+            _native.check(_native.lib.sps_ukf_init(self._state_ptr, _native.Context._mat(T), (C.c_double * 3)(*v.tolist()), self._p0,
+                                                   st))
+            # the predicted pose before any prediction is the initial one (n_imu = 0 only writes the pose)
+            _native.check(_native.lib.sps_ukf_predict(self._state_ptr, None, 0, self._Q, self._pred_ptr, self._pinfo_ptr, st))
+
+    def reset(self, pose, velocity=(0.0, 0.0, 0.0)) -> None:
+        """Start again at ``pose`` (4x4) with ``velocity``, the construction's ``initial_cov`` and zeroed biases and counters,
+        behind the work issued so far on the current stream: what a new estimator built with the same noise would hold.  For a
+        pose that a global search found, to which no motion leads from the state before."""
+        T = _pose(pose)
+        v = np.asarray(velocity, dtype=np.float64)
+        if T is None or not np.isfinite(T).all() or v.shape != (3,) or not np.isfinite(v).all():
+            raise ValueError("pose must be a finite 4x4 matrix and velocity three finite numbers")
+        self._init(T, v)
 
     @property
     def state_dev(self) -> torch.Tensor:

@@ -62,6 +62,10 @@ a pose the search has to find; then, on --cpu-frames frames, the only comparable
 poses of all leaves in chunks of 65536 (the pose upload included), and whether its best leaf is the search's.  With
 --one-frame: a warm-up and ONE global_search.
 
+``--match-status`` (either localiser): hipEvents around ``submit`` of a localiser without and one with ``match_status``
+(max_distance 0.5; the ICP's grid has 1 m cells, the NDT localiser's own 0.5 m), the two alternating frame by frame, and around
+the status' two launches alone at the pose and on the thinned points the last frame left.
+
 ``--one-frame`` runs a warm-up and ONE localiser frame: the target of a ``rocprofv3 --kernel-trace --stats`` run.
 """
 import argparse
@@ -104,6 +108,53 @@ def timed_frames(loc, dscans, T_init, warmup, frames):
             npts.append(r.n_points)
             errs.append(LR.pose_difference(r.pose, np.eye(4))[0])
     return ms, iters, npts, errs
+
+
+def match_status_main(a, dscans, mp, T_init):
+    """submit without and with match_status, alternating frame by frame; then the status' two launches alone"""
+    from sps_amd.localiser import MATCH_WORDS
+    make = (lambda **kw: NDTLocaliser(mp[:, :3], **kw)) if a.localiser == "ndt" else (lambda **kw: ScanToMapLocaliser(mp[:, :3], **kw))
+    locs = {"without": make(), "with": make(match_status=dict(min_inlier_fraction=0.5))}
+    st = torch.cuda.current_stream()
+    ms = {k: [] for k in locs}
+    frac, lost = [], 0
+    for k in range(a.warmup + a.frames):
+        s = dscans[k % len(dscans)]
+        for name in (("without", "with") if k % 2 == 0 else ("with", "without")):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(st)
+            pend = locs[name].submit(s, len(s), T_init)
+            e1.record(st)
+            r = pend.result()
+            e1.synchronize()
+            if k >= a.warmup:
+                ms[name].append(e0.elapsed_time(e1))
+                if name == "with":
+                    frac.append(r.match.inlier_fraction)
+                    lost += bool(r.match.lost)
+    loc = locs["with"]
+    out_words = torch.zeros(MATCH_WORDS + 1, dtype=torch.float64, device="cuda")
+    out_words[MATCH_WORDS:].view(torch.int32)[0] = r.n_points
+    T_dev = torch.from_numpy(np.ascontiguousarray(r.pose)).cuda()
+    alone = []
+    for k in range(a.warmup + a.frames):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(st)
+        loc._status(out_words.data_ptr() + MATCH_WORDS * 8, T_dev.data_ptr(), None, out_words.data_ptr(), st.cuda_stream)
+        e1.record(st)
+        e1.synchronize()
+        if k >= a.warmup:
+            alone.append(e0.elapsed_time(e1))
+    med = lambda v: round(float(np.median(v)), 4)
+    out = {"localiser": a.localiser, "frames": a.frames, "warmup": a.warmup, "points_after_thinning": int(r.n_points),
+           "submit_ms": {k: {"median": med(v), "min": round(min(v), 4), "max": round(max(v), 4)} for k, v in ms.items()},
+           "submit_difference_ms": round(med(ms["with"]) - med(ms["without"]), 4),
+           "status_alone_ms": {"median": med(alone), "min": round(min(alone), 4), "max": round(max(alone), 4)},
+           "inlier_fraction_min": round(min(frac), 4), "lost": lost}
+    print(f"submit without match_status median {out['submit_ms']['without']['median']:.3f} ms, with {out['submit_ms']['with']['median']:.3f} ms; "
+          f"the status' two launches alone median {out['status_alone_ms']['median']:.4f} ms on {out['points_after_thinning']} points",
+          flush=True)
+    print(json.dumps(out))
 
 
 def build_ms(make):
@@ -165,6 +216,8 @@ def main():
                     "distribution-to-distribution registration beside the point path")
     ap.add_argument("--source-resolution", type=float, default=None, help="with --source cells: edge of the scan's cells")
     ap.add_argument("--source-min-points", type=int, default=None, help="with --source cells: points a cell of the scan needs")
+    ap.add_argument("--match-status", dest="match_status", action="store_true", help="time submit without and with the "
+                    "scan-matching status, alternating, and the status' two launches alone")
     ap.add_argument("--global", dest="global_search", action="store_true", help="with --localiser ndt: time global_search and "
                     "localise_global against score_poses over all leaf poses")
     a = ap.parse_args()
@@ -197,6 +250,8 @@ def main():
     dscans = [torch.from_numpy(s).cuda() for s in scans]
     mp = synthetic.build_map()
     T_init = LR.perturbation(0.15, 0.12, 0.05, 1.0)
+    if a.match_status:
+        return match_status_main(a, dscans, mp, T_init)
     if a.global_search:
         return ndt_global_main(a, scans, mp)
     if a.estimator:
