@@ -311,8 +311,17 @@ int sps_train_backward(sps_ctx *ctx, const float *dscores_dev, const float *scor
  * after an intervening inference forward.
  * Train-mode BatchNorm needs more than one active row per level (nn.BatchNorm1d raises "Expected more than 1 value per
  * channel when training", reference resnet.py:100-107): a training forward whose coarsest level has a single voxel sets a
- * sticky flag and the next synchronising call (sps_check) returns SPS_ERR_INVALID. */
+ * sticky flag and the next synchronising call (sps_check) returns SPS_ERR_INVALID.
+ * The loss gradient: the backward adds dscores[p] * s_p * (1 - s_p) per voxel in 32.32 fixed point (sums independent of the
+ * arrival order), so every term of a row that has a voxel must be finite with |term| <= 32768 (out-of-range rows, whose
+ * score is NaN, contribute nothing and their dscores are not read); terms below 2^-33 round to zero.  A NaN, an infinity
+ * or a larger term (a diverged loss) sets a sticky flag of its own: the next synchronising call returns SPS_ERR_INVALID with
+ * a message that names the loss gradient, and the gradients of that step are unspecified (autograd would return NaN). */
 int sps_train_generation(sps_ctx *ctx, int64_t *generation);
+/* Introspection (tests): the launch plan of the weight gradient of convolution `conv_name` (state_dict name without
+ * ".kernel"; not conv0p1s1 or final) at the context's current capacity, valid after a training forward: *gshift = 4 or 6
+ * (rows read 16 or 64 at a time), *nwg = workgroups per (offset, channel block) (> 1: partial sums reduced at the end). */
+int sps_train_wgrad_plan(sps_ctx *ctx, const char *conv_name, int32_t *gshift, int32_t *nwg);
 int sps_train_backward_at(sps_ctx *ctx, int64_t generation, const float *dscores_dev, const float *scores_dev,
                           float *grad_dev, int64_t numel, void *stream);
 

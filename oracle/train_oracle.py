@@ -58,10 +58,17 @@ def _lin(W, cin, cv):
     return W.reshape(cin, -1)
 
 
-def train_step(params: dict, batch: np.ndarray, voxel_size: float, dtype=torch.float64, cv=None):
+def _head(logits, inv):
+    """slice to the points, sigmoid (models.py:28-29)"""
+    return torch.sigmoid(logits[torch.from_numpy(inv), 0])
+
+
+def train_step(params: dict, batch: np.ndarray, voxel_size: float, dtype=torch.float64, cv=None, dscores=None):
     """One common_step: returns (loss float, scores [N] numpy, grads dict name -> numpy, batch stats dict
     bn name -> (mean, biased var, rows)).  ``batch`` rows are (b,x,y,z,t,label).  ``cv``: ME-convention options
-    (oracle/sps_oracle.py); gradients come back in the layout the parameters were given in."""
+    (oracle/sps_oracle.py); gradients come back in the layout the parameters were given in.
+    ``dscores`` (float [N]): an arbitrary cotangent instead of the MSE -- the step ends in scores.backward(dscores) and
+    the returned loss is (scores * dscores).sum()."""
     p = {k: torch.tensor(np.asarray(v), dtype=dtype, requires_grad=("running" not in k)) for k, v in params.items()}
     q = O.quantize(batch[:, :5], voxel_size)
     vox, inv = O.unique_first(q)
@@ -89,10 +96,15 @@ def train_step(params: dict, batch: np.ndarray, voxel_size: float, dtype=torch.f
         cur = torch.cat([cur, skips[ts]], dim=1)
         cur = _block(p, f"block{5 + i}.0", cur, cm, ts, stats)
     logits = cur @ _lin(p["final.kernel"], cur.shape[1], cv) + p["final.bias"]
-    scores = torch.sigmoid(logits[torch.from_numpy(inv), 0])
+    scores = _head(logits, inv)
     scan = torch.from_numpy(np.flatnonzero(batch[:, 4] == 1))
     gt = torch.tensor(batch[:, 5], dtype=dtype)
-    loss = F.mse_loss(scores[scan], gt[scan])               # nn.MSELoss (models.py:52, :68)
-    loss.backward()
+    if dscores is None:
+        loss = F.mse_loss(scores[scan], gt[scan])           # nn.MSELoss (models.py:52, :68)
+        loss.backward()
+    else:
+        g = torch.tensor(np.asarray(dscores), dtype=dtype)
+        loss = (scores.detach() * g).sum()
+        scores.backward(g)
     grads = {k: v.grad.numpy().copy() for k, v in p.items() if v.requires_grad and v.grad is not None}
     return float(loss.detach()), scores.detach().numpy(), grads, {k: (m.numpy(), v.numpy(), n) for k, (m, v, n) in stats.items()}

@@ -90,6 +90,7 @@ def _load() -> C.CDLL:
         "sps_train_forward": (i32, [vp, vp, i64, vp, i64, i64, f32, vp, vp, vp]),
         "sps_train_backward": (i32, [vp, vp, vp, vp, i64, vp]),
         "sps_train_generation": (i32, [vp, C.POINTER(i64)]),
+        "sps_train_wgrad_plan": (i32, [vp, C.c_char_p, C.POINTER(i32), C.POINTER(i32)]),
         "sps_train_backward_at": (i32, [vp, i64, vp, vp, vp, i64, vp]),
         "sps_scan_mse": (i32, [vp, vp, i64, vp, i64, i64, vp, vp, vp]),
         "sps_scan_mse_backward": (i32, [vp, vp, i64, vp, i64, i64, vp, vp, vp, vp]),
@@ -200,7 +201,7 @@ EXPORTS = ["sps_last_error", "sps_version", "sps_ctx_create", "sps_ctx_destroy",
            "sps_forward_head", "sps_check", "sps_metrics", "sps_metrics_dev",
            "sps_profile_enable", "sps_profile_count", "sps_profile_read", "sps_profile_kernel", "sps_map_upload", "sps_map_upload_voxels",
            "sps_submap_voxel", "sps_submap_voxel_ijk", "sps_transform_points", "sps_filter_prepare", "sps_forward_n",
-           "sps_compact_stable", "sps_filter_finish", "sps_train_forward", "sps_train_backward", "sps_train_generation", "sps_train_backward_at", "sps_scan_mse", "sps_scan_mse_backward", "sps_radius_grid_upload", "sps_radius_count",
+           "sps_compact_stable", "sps_filter_finish", "sps_train_forward", "sps_train_backward", "sps_train_generation", "sps_train_wgrad_plan", "sps_train_backward_at", "sps_scan_mse", "sps_scan_mse_backward", "sps_radius_grid_upload", "sps_radius_count",
            "sps_radius_fill", "sps_radius_grid_attach", "sps_radius_item", "sps_forward_metrics_n", "sps_level_counts", "sps_get_voxels",
            "sps_get_inverse", "sps_get_parent", "sps_get_map_pairs", "sps_get_tile_masks", "sps_get_nbr", "sps_get_kernel_map", "sps_get_rulebook_chunks", "sps_get_logits", "sps_get_feature",
            "sps_lts_num_tensors", "sps_lts_tensor_info", "sps_lts_numel", "sps_lts_lidar_info", "sps_lts_create",
@@ -681,6 +682,12 @@ class Context:
         g = C.c_int64()
         check(lib.sps_train_generation(self.handle, C.byref(g)))
         return g.value
+
+    def train_wgrad_plan(self, conv_name: str):
+        """(gshift, nwg) of the weight-gradient launch of a convolution at this context's capacity (after a training forward)"""
+        g, n = C.c_int32(), C.c_int32()
+        check(lib.sps_train_wgrad_plan(self.handle, conv_name.encode(), C.byref(g), C.byref(n)))
+        return g.value, n.value
 
     def level_counts(self):
         out = (C.c_int64 * NUM_LEVELS)()

@@ -1555,7 +1555,7 @@ __global__ void k_err_clear(int *err, int bits) { atomicAnd(err, ~bits); }
 // two users of one context (a training step and a device item loader) each get to see their own error.
 static int report_device_errors(sps_ctx *c, int e, hipStream_t st) {
   if (!e) return SPS_OK;
-  const int bit = (e & 2) ? 2 : (e & 16) ? 16 : (e & 8) ? 8 : (e & 1) ? 1 : (e & 4) ? 4 : (e & 32) ? 32 : e;
+  const int bit = (e & 2) ? 2 : (e & 16) ? 16 : (e & 8) ? 8 : (e & 1) ? 1 : (e & ERR_BIT_LOSS_GRAD) ? ERR_BIT_LOSS_GRAD : (e & 4) ? 4 : (e & 32) ? 32 : e;
   hipLaunchKernelGGL(k_err_clear, dim3(1), dim3(1), 0, st, c->err, bit);
   if (bit == 2) {
     // a level outgrew its compact arrays: that forward was aborted (NaN scores).  Dense sizes from now on -- the next
@@ -1570,6 +1570,9 @@ static int report_device_errors(sps_ctx *c, int e, hipStream_t st) {
   if (bit == 8)
     return fail(SPS_ERR_INVALID, "train-mode BatchNorm: a level of the training forward had a single active row (Expected more "
                                  "than 1 value per channel when training)");
+  if (bit == ERR_BIT_LOSS_GRAD)
+    return fail(SPS_ERR_INVALID, "training backward: the loss gradient (dscores) has a term that is not finite or exceeds the "
+                                 "fixed-point range (|dscores * s * (1 - s)| <= 32768): the gradients of that step are unspecified");
   if (bit == 1)
     return fail(SPS_ERR_RANGE,
                 "a coordinate is outside the voxel-key range (|x,y,z| < 131072 voxels, t in [-16,15], b in [0,30])");

@@ -155,6 +155,8 @@ int train_reserve(sps_ctx *c) {
   // count a level typically has (a prior: the real count is only known on the device; it does not affect results beyond
   // the summation order, which stays fixed for a given capacity)
   {
+    // (tests/train_edge_inputs.py::plan restates this block to choose capacities; the GPU edge tests read the result back
+    // through sps_train_wgrad_plan and fail if the two part)
     static const double level_prior[SPS_NUM_LEVELS] = {1.0, 0.5, 0.2, 0.06, 0.02};
     int64_t wave_target = 16384;  // waves a weight-gradient launch aims for (8 k: +15 us, 32 k: -5 us on the level-0 layers, +8 % on the coarse ones)
 #if defined(SPS_DIAG)
@@ -487,6 +489,21 @@ int sps_train_generation(sps_ctx *c, int64_t *generation) {
   return SPS_OK;
 }
 
+int sps_train_wgrad_plan(sps_ctx *c, const char *conv_name, int32_t *gshift, int32_t *nwg) {
+  if (!c || !conv_name || !gshift || !nwg) return fail(SPS_ERR_INVALID, "null argument");
+  const sps_train *t = c->train;
+  if (!t || !t->net || t->cap <= 0) return fail(SPS_ERR_INVALID, "sps_train_forward has not been called on this context");
+  const NetSpec &s = *t->net;
+  for (size_t i = 0; i < s.convs.size(); ++i) {
+    if (s.convs[i].name != conv_name) continue;
+    if (s.convs[i].cin == 1 || (int)i == s.final_idx) break;  // conv0 and final have kernels of their own
+    *gshift = t->wg[i].gshift;
+    *nwg = t->wg[i].nwg;
+    return SPS_OK;
+  }
+  return fail(SPS_ERR_INVALID, "no k_wgrad job for a convolution named '%s'", conv_name);
+}
+
 static int train_backward_impl(sps_ctx *c, const float *dscores, const float *scores, float *grad_dev, int64_t numel, void *stream);
 
 int sps_train_backward_at(sps_ctx *c, int64_t generation, const float *dscores, const float *scores, float *grad_dev, int64_t numel,
@@ -535,7 +552,8 @@ static int train_backward_impl(sps_ctx *c, const float *dscores, const float *sc
   // head: sigmoid + slice + final
   const ConvSpec &fs = s.convs[s.final_idx];
   const TView b8o = t->views[F_B8O];
-  hipLaunchKernelGGL(k_dlogit_accum, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, dscores, scores, c->lv[0].inv, (int)n, t->vacc);
+  hipLaunchKernelGGL(k_dlogit_accum, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, dscores, scores, c->lv[0].inv, (int)n, t->vacc,
+                     c->err);
   hipLaunchKernelGGL(k_final_bwd, dim3(BN_WG), dim3(256), 0, st, t->vacc, c->counts + 0, b8o.p, b8o.ld, t->blob + fs.w_off, b8o.g,
                      b8o.ld, t->fin_part);
   hipLaunchKernelGGL(k_final_bwd_reduce, dim3(1), dim3(64), 0, st, t->fin_part, t->grad + fs.w_off, t->grad + s.bias_off);

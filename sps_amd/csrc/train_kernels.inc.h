@@ -157,7 +157,7 @@ __global__ __launch_bounds__(BN_TPB) void k_bn_stats(BnFwd2 a) {
 }
 // pass 2, one float4 per thread step
 __global__ __launch_bounds__(256) void k_bn_apply(BnFwd2 a) {
-  __shared__ float sc[BN_MAXC], sh[BN_MAXC];
+  __shared__ float sc[BN_MAXC], sh[BN_MAXC], mu[BN_MAXC];
   __shared__ double red[2][256];
   const BnFwd &b = a.j[blockIdx.y];
   const int C = b.C, ldz = b.ldz, ldy = b.ldy, ldr = b.ldr, relu = b.relu;
@@ -172,8 +172,11 @@ __global__ __launch_bounds__(256) void k_bn_apply(BnFwd2 a) {
     double var = n > 0 ? s1 / n - m * m : 0.0;
     if (var < 0) var = 0;
     const float mean = (float)m, invstd = (float)(1.0 / sqrt(var + 1e-5));
+    // y = (z - mean) * sc + beta, centred first: folded into z * sc + (beta - mean * sc) the two products cancel, and their
+    // rounding, |mean| / std times that of y, is what a level with a handful of nearly equal rows then shows in the scores
     sc[c] = invstd * b.gamma[c];
-    sh[c] = b.beta[c] - mean * invstd * b.gamma[c];
+    sh[c] = b.beta[c];
+    mu[c] = mean;
     if (blockIdx.x == 0) {
       b.fin[c] = mean;
       b.fin[BN_MAXC + c] = invstd;
@@ -188,7 +191,8 @@ __global__ __launch_bounds__(256) void k_bn_apply(BnFwd2 a) {
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) {
     const int r = i >> lcv, c = (i & (CV - 1)) << 2;
     const float4 z = *reinterpret_cast<const float4 *>(Z + (size_t)r * ldz + c);
-    float y[4] = {z.x * sc[c] + sh[c], z.y * sc[c + 1] + sh[c + 1], z.z * sc[c + 2] + sh[c + 2], z.w * sc[c + 3] + sh[c + 3]};
+    float y[4] = {(z.x - mu[c]) * sc[c] + sh[c], (z.y - mu[c + 1]) * sc[c + 1] + sh[c + 1], (z.z - mu[c + 2]) * sc[c + 2] + sh[c + 2],
+                  (z.w - mu[c + 3]) * sc[c + 3] + sh[c + 3]};
     if (res) {
       const float4 q = *reinterpret_cast<const float4 *>(res + (size_t)r * ldr + c);
       y[0] += q.x, y[1] += q.y, y[2] += q.z, y[3] += q.w;
@@ -672,15 +676,20 @@ __global__ __launch_bounds__(256) void k_conv0_wgrad_reduce(const float *__restr
 // head of the backward: scores = sigmoid(logits[inv]) (models.py:28-29), logits = b8o . w + b (minkunet.py:152-158)
 // ------------------------------------------------------------------------------------------
 // dlogit[v] = sum over the points p of voxel v of dscores[p] * s_p (1 - s_p): 32.32 fixed-point integer atomics, so
-// the sum does not depend on the arrival order (|term| < 2^15; resolution 2^-32).
+// the sum does not depend on the arrival order (|term| <= 2^15; resolution 2^-32).  A term the accumulator cannot hold
+// -- NaN, +-inf, |term| > 2^15: the loss has diverged -- sets error bit 6 (reported by the next synchronising call); the
+// clamped value still goes in, the gradients of such a step are unspecified.
+constexpr int ERR_BIT_LOSS_GRAD = 64;
 __global__ void k_dlogit_accum(const float *__restrict__ dscores, const float *__restrict__ scores, const int *__restrict__ inv,
-                               int n, long long *__restrict__ vacc) {
+                               int n, long long *__restrict__ vacc, int *__restrict__ err) {
   const int p = blockIdx.x * blockDim.x + threadIdx.x;
   if (p >= n) return;
   const int v = inv[p];
   if (v < 0) return;
   const float s = scores[p];
-  const double t = fmin(fmax((double)dscores[p] * (double)s * (double)(1.f - s), -32768.0), 32768.0);
+  const double raw = (double)dscores[p] * (double)s * (double)(1.f - s);
+  const double t = fmin(fmax(raw, -32768.0), 32768.0);
+  if (!(t == raw)) atomicOr(err, ERR_BIT_LOSS_GRAD);  // (NaN compares unequal to everything, the clamp moves +-inf and |raw| > 2^15)
   if (t != 0.0) atomicAdd(reinterpret_cast<unsigned long long *>(vacc) + v, (unsigned long long)__double2ll_rn(t * FEAT_FIX));
 }
 
@@ -694,13 +703,14 @@ __global__ __launch_bounds__(256) void k_final_bwd(const long long *__restrict__
   const int r0 = blockIdx.x * per, r1 = min(n, r0 + per);
   double s[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
   for (int v = r0 + (int)threadIdx.x; v < r1; v += blockDim.x) {
-    const float dl = (float)((double)vacc[v] / FEAT_FIX);
+    const double dle = (double)vacc[v] / FEAT_FIX;  // exact in f64: a multiple of 2^-32
+    const float dl = (float)dle;
 #pragma unroll
     for (int c = 0; c < 8; ++c) {
       dF[(size_t)v * ldd + c] = dl * w[c];
       s[c] += (double)dl * (double)F[(size_t)v * ldf + c];
     }
-    s[8] += (double)dl;
+    s[8] += dle;  // the bias gradient sums the accumulators themselves (exact in f64 while |sum| < 2^21): rounded to f32 once, at the end
   }
 #pragma unroll
   for (int j = 0; j < 9; ++j) red[j][threadIdx.x] = s[j];
