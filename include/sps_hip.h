@@ -900,6 +900,58 @@ int sps_ndt_align_d2d(sps_ctx *ctx, const double *src_dev, const int32_t *n_src_
                       double tol_r, double *T_out_dev, int32_t *status_dev, double *trace_dev, double *normal_dev,
                       void *scratch_dev, void *stream);
 
+/* ---- NDT localiser, distribution to distribution, several poses ---------------------------------------------------------
+ * What "several hypotheses" and "pose search" above give the point registration, for source cells: sps_ndt_align_d2d from
+ * n_hyp start poses that live on the device, with best-score selection, and the D2D score of a grid of poses.  (DESIGN.md
+ * 8o.)  Additive: sps_version() is unchanged.  The rules of sps_ndt_align_d2d hold; src_dev, n_src_dev and cap_src are its
+ * arguments, and the first min(cap_src, n_src_dev[0]) records are read and the valid ones used.  Static and online maps are
+ * both accepted.  No call allocates, synchronises or raises the sticky error.
+ *
+ * sps_ndt_align_d2d_batch: hypothesis k starts from the row-major 4x4 T_init_dev[k] (double[n_hyp][16] on the device, which
+ *   work issued earlier on the stream may still be writing; the caller leaves it unchanged until the stream has passed the
+ *   call) and is, operation for operation and sum for sum, sps_ndt_align_d2d from that pose: T_out_dev[k], status_dev[k],
+ *   trace_dev[k] and normal_dev[k] have the bits of the single call, T_out_dev[k] is T_init_dev[k] bit for bit on status 2
+ *   and 3, and a hypothesis whose status is final sits out the remaining iterations while the others go on.  The source
+ *   records and the map are shared.  iters = 0 is legal.
+ *   Launches: 1 (initialise) + 2 * iters (A with grid (ceil(cap_src / 32), n_hyp), B with grid n_hyp) + 2, whatever the
+ *   data, and the up to two memsets of the single call (trace_dev, normal_dev; none with iters = 0):
+ *     A once more, for every hypothesis at its final pose whatever its status: final_dev[k] = (D2D score at the final pose,
+ *        sources counted), the partial rows (one per 32 sources) added in launch B's block order;
+ *     select (sps_ndt_align_batch's): the hypothesis with the highest final score among those with status 0 or 1 and at
+ *        least min_corr sources counted at the final pose; equal scores go to the lowest k, NaN never wins.  best_dev = (k,
+ *        status of k, sources counted at its final pose, n_hyp) and T_best_dev = T_out_dev[k]; where no hypothesis
+ *        qualifies best_dev = (-1, -1, 0, n_hyp) and T_best_dev = T_init_dev[0].
+ *   T_best_dev and best_dev + 1 serve as T_dev and gate_dev of sps_ndt_map_update, sps_ndt_map_carve, sps_loc_match_status
+ *   and sps_ukf_correct.  Arguments are checked as for sps_ndt_align_d2d, and 1 <= n_hyp <= SPS_NDT_MAX_HYP.  trace_dev
+ *   double[n_hyp][iters][4], normal_dev (may be NULL) double[n_hyp][iters][28].  scratch_dev:
+ *   sps_ndt_align_d2d_batch_scratch(cap_src, n_hyp) bytes (-1 for arguments out of range): the partial rows of every
+ *   hypothesis, then one done flag each.
+ *
+ * sps_ndt_score_poses_d2d: score_dev[p] = (D2D score, sources counted) of the row-major 4x4 pose T_dev[p].  Per valid
+ *   source and pose this is launch A of sps_ndt_align_d2d restricted to its last two sums: q = R mu + t and Cw = R C R^T as
+ *   there, the cells of q in lookup order, per valid map record Sm, M, B, x, y, s, e and w as there with the same guards,
+ *   score += (-d1) e, and a source with at least one contributing cell counts once.  Orders: cells in lookup order within a
+ *   source, sources in index order within a workgroup of 32, workgroups as launch B adds them.  score_dev[p] therefore has
+ *   the bits of final_dev[k] of sps_ndt_align_d2d_batch(iters = 0) started at T_dev[p].  A pose with a NaN entry, or one
+ *   that puts every source off the map, scores (0, 0).  An empty map, n_src_dev[0] = 0 and records that are all invalid are
+ *   legal: every pose scores (0, 0).  1 <= n_pose <= SPS_NDT_MAX_POSES; neighbours, outlier_ratio and cap_src are checked
+ *   as for sps_ndt_align_d2d.  Launches: 2 per chunk of poses (the scorer with grid (ceil(cap_src / 32), ceil(poses of
+ *   the chunk / 32)), then the reduction of sps_ndt_score_poses).  scratch_dev: sps_ndt_score_d2d_scratch(cap_src, n_pose)
+ *   bytes (-1 for arguments out of range) = 16 * ceil(cap_src / 32) bytes per pose of a chunk, chunked under the bound of
+ *   sps_ndt_score_scratch: at or below 64 MiB, or the 32 poses of one tile where those need more.  sps_ndt_top_poses
+ *   serves unchanged on score_dev, min_corr then meaning sources.  T_dev stays unchanged until the stream has passed the
+ *   call. */
+int64_t sps_ndt_align_d2d_batch_scratch(int64_t cap_src, int n_hyp);
+int sps_ndt_align_d2d_batch(sps_ctx *ctx, const double *src_dev, const int32_t *n_src_dev, int64_t cap_src,
+                            const double *T_init_dev, int n_hyp, int iters, int neighbours, int min_corr, double outlier_ratio,
+                            double tol_t, double tol_r, double *T_out_dev, int32_t *status_dev, double *trace_dev,
+                            double *normal_dev, double *final_dev, int32_t *best_dev, double *T_best_dev, void *scratch_dev,
+                            void *stream);
+int64_t sps_ndt_score_d2d_scratch(int64_t cap_src, int64_t n_pose);
+int sps_ndt_score_poses_d2d(sps_ctx *ctx, const double *src_dev, const int32_t *n_src_dev, int64_t cap_src, const double *T_dev,
+                            int64_t n_pose, int neighbours, double outlier_ratio, double *score_dev, void *scratch_dev,
+                            void *stream);
+
 /* ---- pose estimator (unscented Kalman filter with IMU prediction) -----------------------------------------------------
  * hdl_localization's pose system as published, restated: tests/ukf_reference.py is the specification, not that package
  * (DESIGN.md 8j lists the differences).  Additive: sps_version() is unchanged.  No entry takes a context, allocates,

@@ -25,7 +25,8 @@ line then tells the iterations per level); with ``--update-map`` / ``--carve-map
 (``--level-capacities``), every level is updated and carved in the same launches and the ``map`` / ``carve`` lines come once
 per level; with ``--source cells`` it registers distribution to distribution (one Gaussian per cell of the scan against
 the map's; ``--source-resolution``, ``--source-min-points``), ``n_corr`` then counts source cells and the ``loc:`` line
-ends with ``| N sources``, the scan's valid cells.  Frames then run one at a time; behind each frame's lines comes
+ends with ``| N sources``, the scan's valid cells; ``--d2d`` lets ``--hypotheses``, ``--search`` and the device path of
+``--estimator ukf`` register the scan's cells too.  Frames then run one at a time; behind each frame's lines comes
 ``loc: status iterations n_corr rmse | err_t err_r`` (metres, degrees, against the replayed pose map_tr @ pose) and at
 the end the absolute pose error evo_ape prints by default.  ``--global-start`` (with ``--localiser ndt``) takes the loop's
 initial pose from ``NDTLocaliser.localise_global`` on the first raw scan instead of from the sequence (``--global-resolution``,
@@ -150,11 +151,12 @@ def hypothesis_grid(counts, steps, option="--hypotheses", step_option="--hypothe
 def closed_loop(name, f, pc_map, replay, finish, traj_out, which="icp", hypotheses=None, search=None, update_map=False,
                 cell_capacity=None, max_cell_points=0, resolutions=None, level_iterations=None, carve_map=False,
                 carve_options=None, level_capacities=None, estimator=None, source=None, coarse_to_fine=False,
-                global_start=None, match_status=None, recover=None, inject=None):
+                global_start=None, match_status=None, recover=None, inject=None, d2d=False):
     """--localise: one LocalisationLoop step per frame, scored against the replayed poses.  ``estimator``: None, or the
     options of --estimator ukf (initial_velocity, scan_period, imu: None / a rate in Hz / an array of rows t ax .. gz).
     ``source``: None, or the keywords of NDTLocaliser(source="cells", ...) of --source cells.  ``coarse_to_fine``: hypotheses,
-    search and the estimator's device path register on the pyramid of --resolutions.  ``global_start``: None, or the
+    search and the estimator's device path register on the pyramid of --resolutions.  ``d2d``: with ``source``, they
+    register the scan's cells (--d2d).  ``global_start``: None, or the
     options of --global-start (grid: the localiser's global_grid; yaw_steps, frontier, scan_z: of localise_global): the
     loop's initial pose is then found on the map from the first raw scan, and the sequence's first pose only scores it.
     ``match_status``: None, or the localiser's match_status of --match-status: every frame's inlier fraction and matching
@@ -203,7 +205,7 @@ def closed_loop(name, f, pc_map, replay, finish, traj_out, which="icp", hypothes
                 est = PoseEstimator(T0, localiser.device, initial_velocity=estimator["initial_velocity"])
             loop = LocalisationLoop(f, localiser, T0, hypotheses=hypotheses, search=search, update_map=update_map,
                                     max_cell_points=max_cell_points, carve_map=carve_map, carve_options=carve_options,
-                                    estimator=est, coarse_to_fine=coarse_to_fine, **lkw)
+                                    estimator=est, coarse_to_fine=coarse_to_fine, **(dict(d2d=True) if d2d else {}), **lkw)
             if est is not None:
                 print("estimator: ukf  start of the registration: " + ("device pose" if loop.device_guess else "host pose"))
         if estimator is None:
@@ -346,6 +348,10 @@ def frame_motion(estimator, k):
 @click.option("--source", "source", type=click.Choice(("points", "cells")), default=None,
               help="with --localiser ndt: register the scan's points (default) or, distribution to distribution, one Gaussian "
                    "per cell of the scan; the loc: line then ends with the scan's valid source cells")
+@click.option("--d2d", "d2d", is_flag=True,
+              help="with --source cells and one of --hypotheses, --search, --estimator ukf: these register the scan's cells "
+                   "too, distribution to distribution, from start poses on the device (without it --source cells takes "
+                   "neither --hypotheses nor --search, and the estimator's guess is fetched to the host)")
 @click.option("--source-resolution", "source_resolution", type=float, default=None,
               help="with --source cells: edge of the scan's cells in m (default: the map's resolution)")
 @click.option("--source-min-points", "source_min_points", type=int, default=None,
@@ -388,7 +394,7 @@ def frame_motion(estimator, k):
               help="with --estimator: a text file of rows `t ax ay az gx gy gz`, scan k being at k * scan-period")
 def main(name, weights, sequence, config, epsilon, out_dir, n_synth, localise, which, traj_out, hyp_counts, hyp_steps,
          search_counts, search_steps, update_map, cell_capacity, max_cell_points, carve_map, carve_miss_frames, carve_sigma,
-         resolutions, level_iterations, coarse_to_fine, level_capacities, source, source_resolution, source_min_points,
+         resolutions, level_iterations, coarse_to_fine, level_capacities, source, d2d, source_resolution, source_min_points,
          estimator, initial_velocity, scan_period, imu_rate, imu_file, global_start, global_resolution, global_map_z,
          global_scan_z, global_yaw_steps, global_levels, global_frontier, match_status, min_inlier_fraction, recover_global,
          inject_jump):
@@ -441,8 +447,11 @@ def main(name, weights, sequence, config, epsilon, out_dir, n_synth, localise, w
         raise click.UsageError("--source needs --localise --localiser ndt")
     if (source_resolution is not None or source_min_points is not None) and source != "cells":
         raise click.UsageError("--source-resolution and --source-min-points need --source cells")
-    if source == "cells" and (resolutions is not None or hyp_counts is not None or search_counts is not None):
-        raise click.UsageError("--source cells takes no --resolutions, --hypotheses or --search: they register points")
+    if d2d and (source != "cells" or (hyp_counts is None and search_counts is None and estimator is None)):
+        raise click.UsageError("--d2d needs --source cells and one of --hypotheses, --search, --estimator ukf")
+    if source == "cells" and (resolutions is not None or ((hyp_counts is not None or search_counts is not None) and not d2d)):
+        raise click.UsageError("--source cells takes no --resolutions, --hypotheses or --search: they register points"
+                               " (--d2d lets --hypotheses and --search register the scan's cells)")
     source = dict(source="cells", source_resolution=source_resolution, source_min_points=source_min_points) \
         if source == "cells" else None
     if estimator is None and (initial_velocity != "0,0,0" or imu_rate is not None or imu_file is not None):
@@ -549,7 +558,7 @@ def main(name, weights, sequence, config, epsilon, out_dir, n_synth, localise, w
     if localise:
         closed_loop(name, f, pc_map, replay, finish, traj_out, which or "icp", hypotheses, search, update_map, cell_capacity,
                     max_cell_points, resolutions, level_iterations, carve_map, carve_options or None, level_capacities,
-                    estimator, source, coarse_to_fine, global_start, match_status, recover_global, inject)
+                    estimator, source, coarse_to_fine, global_start, match_status, recover_global, inject, d2d)
     elif traj_out:
         raise click.UsageError("--traj-out needs --localise")
     in_flight, prev_pose = None, None

@@ -176,6 +176,11 @@ def _load() -> C.CDLL:
         "sps_ndt_align_d2d_scratch": (i64, [i64]),
         "sps_ndt_align_d2d": (i32, [vp, vp, vp, i64, vp, i32, i32, i32, C.c_double, C.c_double, C.c_double, vp, vp, vp, vp, vp,
                                     vp]),
+        "sps_ndt_align_d2d_batch_scratch": (i64, [i64, i32]),
+        "sps_ndt_align_d2d_batch": (i32, [vp, vp, vp, i64, vp, i32, i32, i32, i32, C.c_double, C.c_double, C.c_double, vp, vp, vp,
+                                          vp, vp, vp, vp, vp, vp]),
+        "sps_ndt_score_d2d_scratch": (i64, [i64, i64]),
+        "sps_ndt_score_poses_d2d": (i32, [vp, vp, vp, i64, vp, i64, i32, C.c_double, vp, vp, vp]),
         "sps_ukf_state_bytes": (i64, []),
         "sps_ukf_init": (i32, [vp, vp, vp, vp, vp]),
         "sps_ukf_predict": (i32, [vp, vp, i32, vp, vp, vp, vp]),
@@ -220,6 +225,7 @@ EXPORTS = ["sps_last_error", "sps_version", "sps_ctx_create", "sps_ctx_destroy",
            "sps_ndt_pyramid_carve_scratch", "sps_ndt_pyramid_carve", "sps_ndt_pyramid_info", "sps_ndt_pyramid_carve_cells",
            "sps_ndt_pyramid_align_batch_scratch", "sps_ndt_pyramid_align_batch",
            "sps_ndt_source_scratch", "sps_ndt_source_build", "sps_ndt_align_d2d_scratch", "sps_ndt_align_d2d",
+           "sps_ndt_align_d2d_batch_scratch", "sps_ndt_align_d2d_batch", "sps_ndt_score_d2d_scratch", "sps_ndt_score_poses_d2d",
            "sps_ukf_state_bytes", "sps_ukf_init", "sps_ukf_predict", "sps_ukf_predict_dt", "sps_ukf_correct"]
 NDT_SRC_REC = 10           # SPS_NDT_SRC_REC: doubles of a source record
 BBS_MAX_LEVELS = 8         # SPS_BBS_MAX_LEVELS
@@ -664,6 +670,21 @@ class Context:
         check(lib.sps_ndt_align_d2d(self.handle, src_ptr, n_src_ptr, int(cap_src), self._mat(T_init), int(iters),
                                     int(neighbours), int(min_corr), float(outlier_ratio), float(tol_t), float(tol_r), T_out_ptr,
                                     status_ptr, trace_ptr, normal_ptr, scratch_ptr, stream))
+
+    # ---- NDT localiser, distribution to distribution, several poses (include/sps_hip.h, same title) ----
+    def ndt_align_d2d_batch(self, src_ptr, n_src_ptr: int, cap_src: int, T_init_ptr, n_hyp: int, iters: int, neighbours: int,
+                            min_corr: int, outlier_ratio: float, tol_t: float, tol_r: float, T_out_ptr: int, status_ptr: int,
+                            trace_ptr, normal_ptr, final_ptr: int, best_ptr: int, T_best_ptr: int, scratch_ptr: int,
+                            stream: int):
+        check(lib.sps_ndt_align_d2d_batch(self.handle, src_ptr, n_src_ptr, int(cap_src), T_init_ptr, int(n_hyp), int(iters),
+                                          int(neighbours), int(min_corr), float(outlier_ratio), float(tol_t), float(tol_r),
+                                          T_out_ptr, status_ptr, trace_ptr, normal_ptr, final_ptr, best_ptr, T_best_ptr,
+                                          scratch_ptr, stream))
+
+    def ndt_score_poses_d2d(self, src_ptr, n_src_ptr: int, cap_src: int, T_ptr, n_pose: int, neighbours: int,
+                            outlier_ratio: float, score_ptr: int, scratch_ptr: int, stream: int):
+        check(lib.sps_ndt_score_poses_d2d(self.handle, src_ptr, n_src_ptr, int(cap_src), T_ptr, int(n_pose), int(neighbours),
+                                          float(outlier_ratio), score_ptr, scratch_ptr, stream))
 
     def train_forward(self, params_ptr: int, numel: int, coords_ptr: int, ld: int, n: int, voxel_size: float,
                       scores_ptr: int, batch_stats_ptr, stream: int):

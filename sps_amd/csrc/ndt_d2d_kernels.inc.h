@@ -10,6 +10,7 @@
 //   k_ndt_src_records      (source build, 7)  one thread per cell: ndt_floored_eigen, covariance, flag -> one 80-byte record
 //   k_ndt_d2d_assoc        (launch A of an iteration)  q = R mu + t, Cw = R C R^T, the records of q's cell and its face
 //                          neighbours, per cell B = inv3(inv3(icov) + Cw) and the normal-equation terms with B
+//                          (its body is ndt_d2d_assoc_body, which ndt_d2d_batch_kernels.inc.h runs once per hypothesis)
 //
 // Launch B is k_loc_solve unchanged.  The rules of ndt_kernels.inc.h hold: float64, contraction off, loc_mul / loc_add /
 // __ddiv_rn, no float atomics, no sum that depends on the order in which threads arrive.  The one atomic of this file is an
@@ -155,11 +156,11 @@ __device__ inline bool ndt_d2d_hit(const double q[3], const double Cw[6], const 
 //            where the cell contributes (ndt_d2d_hit), leaves a = -d1 w, B, y = B x and the score in LDS;
 //   phases 2 and 3: ndt_assoc_reduce, with B where k_ndt_assoc has the cell's inverse covariance.
 // A source that is not valid, or lies beyond the cells built, contributes nothing and is not counted.
-__global__ __launch_bounds__(256) void k_ndt_d2d_assoc(const double *__restrict__ src, const int *__restrict__ n_src, int cap,
-                                                        NdtMap m, NdtGauss gs, int neighbours, const double *__restrict__ T,
-                                                        const int *__restrict__ done, double *__restrict__ partial) {
-  __shared__ NdtAssocLds lds;
-  if (*done) return;
+// The body is shared with k_ndt_d2d_assoc_batch (ndt_d2d_batch_kernels.inc.h), which runs it once per hypothesis: T is the
+// pose, partial the rows of that pose, blockIdx.x the workgroup's place among them.
+__device__ inline void ndt_d2d_assoc_body(const double *__restrict__ src, const int *__restrict__ n_src, int cap, const NdtMap &m,
+                                          const NdtGauss &gs, int neighbours, const double *__restrict__ T,
+                                          double *__restrict__ partial, NdtAssocLds &lds) {
   const int n = min(cap, max(*n_src, 0));
   const int base = blockIdx.x * LOC_PTS;
   if (base >= n) return;
@@ -190,6 +191,14 @@ __global__ __launch_bounds__(256) void k_ndt_d2d_assoc(const double *__restrict_
   }
   lds.hit_ok[k][sub] = ok;
   ndt_assoc_reduce(lds, k, sub, q, neighbours, partial);
+}
+
+__global__ __launch_bounds__(256) void k_ndt_d2d_assoc(const double *__restrict__ src, const int *__restrict__ n_src, int cap,
+                                                        NdtMap m, NdtGauss gs, int neighbours, const double *__restrict__ T,
+                                                        const int *__restrict__ done, double *__restrict__ partial) {
+  __shared__ NdtAssocLds lds;
+  if (*done) return;
+  ndt_d2d_assoc_body(src, n_src, cap, m, gs, neighbours, T, partial, lds);
 }
 
 #pragma clang fp contract(fast)

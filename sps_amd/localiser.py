@@ -213,7 +213,8 @@ def _pose_layout(K, with_normal, pyramid=False, L=None, integrate=False, carve=F
 
 
 def _batch_layout(K, I, with_normal, integrate=False, carve=False, pyramid=False, L=None, match=False):
-    """offsets (in doubles) of a batch's one float64 buffer: T_out[K][16] | status int32[K][4] | n_points int32 (+ pad) |
+    """offsets (in doubles) of a batch's one float64 buffer: T_out[K][16] | status int32[K][4] | n_points int32 (+ n_sources
+    int32 of a d2d batch in the pad) |
     best int32[4] | T_best[16] | final[K][2] | trace[K][I][4] | normal[K][I][28] | level int32[K][I] (+ pad) of a coarse-to-fine
     batch (``pyramid``) | info int32[4] of the update | info int32[4] of the carve (an online pyramid of L levels: int32[L][4]
     each) | the MATCH_WORDS words of the scan-matching status with ``match``.  ``hands_on``, as in ``_pose_layout``:
@@ -343,7 +344,7 @@ class PendingPoses(_Pending):
         K, I = self._n_hyp, self._iters
         T_out = h[o["T_out"]:o["status"]].reshape(K, 4, 4)
         status = h[o["status"]:o["n_points"]].view(np.int32).reshape(K, 4)
-        n_points = int(h[o["n_points"]:o["best"]].view(np.int32)[0])
+        n_points, n_sources = (int(x) for x in h[o["n_points"]:o["best"]].view(np.int32))   # sources: a d2d batch only
         best = h[o["best"]:o["T_best"]].view(np.int32)
         final = h[o["final"]:o["trace"]].reshape(K, 2)
         trace = h[o["trace"]:o["normal"]].reshape(K, I, 4)
@@ -356,7 +357,8 @@ class PendingPoses(_Pending):
             rmse = math.sqrt(tr[-1, 1] / n_corr) if it and n_corr > 0 else float("nan")
             results.append(PoseResult(T_out[k].copy(), code, it, n_corr, rmse, tr,
                                       normal[k, :it].copy() if normal is not None else None, n_points,
-                                      levels=levels[k, :it].astype(np.int64) if levels is not None else None))
+                                      levels=levels[k, :it].astype(np.int64) if levels is not None else None,
+                                      n_sources=n_sources))
         L = self._n_levels
         upd = _per_level(_map_update_of, h[o["update"]:o["carve"]].view(np.int32), n_points, L) if self._integrate else None
         carved = _per_level(_map_carve_of, h[o["carve"]:o["match"]].view(np.int32), n_points, L) if self._carve else None
@@ -862,8 +864,10 @@ class NDTLocaliser(ScanToMapLocaliser):
     ``min_points_per_cell``), and these are registered against the map's Gaussians.  ``n_corr`` then counts source cells,
     ``min_correspondences`` bounds them, and the result's ``n_sources`` tells how many valid ones the scan gave.
     ``submit`` / ``submit_filtered`` / ``__call__``, ``integrate`` and ``carve`` work as before (the map still takes the
-    thinned points); ``resolutions``, ``submit_batch``, ``submit_from_device``, ``score_poses`` and ``relocalise`` are
-    refused.  ``capacity`` is then at most 65536.  ``source="points"`` (the default) is the point-to-distribution path.
+    thinned points); ``resolutions`` and the global search are refused, and ``submit_batch``, ``submit_from_device``,
+    ``score_poses`` and ``relocalise`` are refused unless they are called with ``d2d=True``, which registers and scores the
+    scan's cells from poses on the device.  ``capacity`` is then at most 65536.  ``source="points"`` (the
+    default) is the point-to-distribution path.
 
     ``global_grid`` (None: nothing is built; a dict with any of ``resolution`` (0.5), ``map_z`` = (lo, hi) (everything) and
     ``levels`` (3, at most 7)): the map points of that height slice become an occupancy grid of that edge with ``levels``
@@ -921,6 +925,8 @@ class NDTLocaliser(ScanToMapLocaliser):
                                                 device=self.device)
                 self._d2d_scratch = torch.empty(_native.lib.sps_ndt_align_d2d_scratch(self.capacity), dtype=torch.uint8,
                                                 device=self.device)
+                self._d2d_batch_scratch, self._d2d_batch_hyp = None, 0   # those of the d2d=True calls, grown on demand
+                self._d2d_score_scratch, self._d2d_score_poses = None, 0
 
     def _build_map(self, xyz):
         """the single map at ``resolution``, static or online, and the pyramid's levels beside it"""
@@ -1136,9 +1142,21 @@ class NDTLocaliser(ScanToMapLocaliser):
             self.ctx.bbs_map_level(level, out.data_ptr())
         return out.cpu().numpy()
 
-    def _refuse_cells(self, what):
+    def _refuse_cells(self, what, hint=""):
         if self.source == "cells":
-            raise ValueError(f"{what} registers points: it needs an NDTLocaliser with source='points'")
+            raise ValueError(f"{what} registers points: it needs an NDTLocaliser with source='points'{hint}")
+
+    def _checked_d2d(self, what, d2d, coarse_to_fine=False):
+        """the checks of the ``d2d`` keyword of the calls that take several poses, before any device work: without it a
+        cells localiser refuses them as ever, with it the localiser must register cells, and on the single map"""
+        if not d2d:
+            self._refuse_cells(what, " (or d2d=True, which registers the scan's cells)")
+            return False
+        if self.source != "cells":
+            raise ValueError(f"{what}: d2d=True needs an NDTLocaliser with source='cells'")
+        if coarse_to_fine:
+            raise ValueError(f"{what}: d2d=True and coarse_to_fine exclude each other: the pyramid registers points")
+        return True
 
     @staticmethod
     def _checked_pyramid(resolutions, level_iterations, cell_capacity):
@@ -1314,7 +1332,7 @@ class NDTLocaliser(ScanToMapLocaliser):
     @torch.no_grad()
     def submit_batch(self, rows, count, T_inits, with_normal: bool = False, iterations: int = None, integrate: bool = False,
                      max_cell_points: int = 0, carve: bool = False, carve_options: dict = None,
-                     coarse_to_fine: bool = False) -> PendingPoses:
+                     coarse_to_fine: bool = False, d2d: bool = False) -> PendingPoses:
         """``submit`` from the K start poses ``T_inits`` [K, 4, 4] (1 <= K <= 64) at once: the scan is thinned once, every
         hypothesis is registered as ``submit`` would register it from its pose, and the hypothesis with the highest NDT
         score at its final pose is selected among those with status 0 / 1 and at least ``min_correspondences`` points
@@ -1327,36 +1345,46 @@ class NDTLocaliser(ScanToMapLocaliser):
         that budget per level; ``results[k].levels`` tells the level of every slot of hypothesis k and ``iterations`` counts
         its slots; the final scores are taken on the finest level, however far a hypothesis got.  On an online pyramid
         ``integrate`` and ``carve`` then work on all levels at the selected pose, and their results are tuples, one entry
-        per level."""
+        per level.
+
+        ``d2d`` (a localiser with ``source="cells"``, which refuses the call without it; not with ``coarse_to_fine``): the
+        scan is thinned and its source cells are built once, as ``submit`` builds them, and every hypothesis is registered
+        distribution to distribution, as ``submit`` registers there (C ABI: "NDT localiser, distribution to distribution,
+        several poses").  ``n_corr``, ``counts`` and ``min_correspondences`` then mean source cells and every
+        hypothesis' result carries ``n_sources``; ``integrate`` and ``carve`` still work on the thinned points."""
+        if d2d:                                                      # poses first: they need no device
+            self._checked_d2d("submit_batch", d2d, coarse_to_fine)
+            _checked_poses(T_inits, "T_inits", MAX_HYPOTHESES, "K")
         rows, copts = self._checked_for_batch("submit_batch", rows, integrate, max_cell_points, carve, carve_options,
-                                              coarse_to_fine)
+                                              coarse_to_fine, d2d)
         T = _checked_poses(T_inits, "T_inits", MAX_HYPOTHESES, "K")
         return self._issue_batch(rows, count, T, len(T), with_normal, iterations, integrate, max_cell_points, copts,
-                                 coarse_to_fine)
+                                 coarse_to_fine, d2d)
 
     @torch.no_grad()
     def submit_from_device(self, rows, count, T_init_dev, with_normal: bool = False, iterations: int = None,
                            integrate: bool = False, max_cell_points: int = 0, carve: bool = False,
-                           carve_options: dict = None, coarse_to_fine: bool = False) -> PendingPoses:
+                           carve_options: dict = None, coarse_to_fine: bool = False, d2d: bool = False) -> PendingPoses:
         """``submit_batch`` with one hypothesis whose start pose is already on the device: ``T_init_dev`` holds 16 contiguous
         float64 entries (a row-major 4 x 4, e.g. ``PoseEstimator.pose_dev``) that work issued earlier on the current stream
         may still be writing.  The host never sees the pose; hypothesis 0 of the result is what ``submit`` gives from the
         same pose, bit for bit.  A pose that is not finite ends as such a pose does in ``sps_ndt_align_batch``.
-        ``coarse_to_fine``: as for ``submit_batch``; hypothesis 0 is then what ``submit`` gives on the pyramid."""
+        ``coarse_to_fine``: as for ``submit_batch``; hypothesis 0 is then what ``submit`` gives on the pyramid.
+        ``d2d``: as for ``submit_batch``; hypothesis 0 is then what ``submit`` gives on a ``source="cells"`` localiser."""
         rows, copts = self._checked_for_batch("submit_from_device", rows, integrate, max_cell_points, carve, carve_options,
-                                              coarse_to_fine)
+                                              coarse_to_fine, d2d)
         T_dev = T_init_dev
         if not (torch.is_tensor(T_dev) and T_dev.is_cuda and T_dev.device == self.device and T_dev.dtype == torch.float64
                 and T_dev.numel() == 16 and T_dev.is_contiguous()):
             raise TypeError("T_init_dev must be 16 contiguous float64 entries on the localiser's device")
         return self._issue_batch(rows, count, T_dev, 1, with_normal, iterations, integrate, max_cell_points, copts,
-                                 coarse_to_fine)
+                                 coarse_to_fine, d2d)
 
-    def _checked_for_batch(self, what, rows, integrate, max_cell_points, carve, carve_options, coarse_to_fine=False):
+    def _checked_for_batch(self, what, rows, integrate, max_cell_points, carve, carve_options, coarse_to_fine=False, d2d=False):
         """the checks of everything that registers from poses on the device, in their order -> (the checked rows, the carve's
         options).  Without ``coarse_to_fine`` the work is on the single map; with it on the pyramid, which must exist and
-        whose levels ``integrate`` and ``carve`` then mean"""
-        self._refuse_cells(what)
+        whose levels ``integrate`` and ``carve`` then mean; ``d2d``: the scan's cells are registered (``_checked_d2d``)"""
+        self._checked_d2d(what, d2d, coarse_to_fine)
         if coarse_to_fine and self.resolutions is None:
             raise ValueError("coarse_to_fine needs a localiser with a pyramid: NDTLocaliser(..., resolutions=...)")
         self._check_integrate(integrate, max_cell_points, single_map=not coarse_to_fine)
@@ -1369,15 +1397,18 @@ class NDTLocaliser(ScanToMapLocaliser):
         return integrate, carve, bool(coarse_to_fine), len(self.level_capacities) if online else None, self._match_opts is not None
 
     def _issue_batch(self, rows, count, poses, K, with_normal, iterations, integrate, max_cell_points, copts,
-                     coarse_to_fine=False):
-        """the batch of the K start poses ``poses``: a host array [K, 4, 4], or 16 float64 entries on the device (K = 1)"""
+                     coarse_to_fine=False, d2d=False):
+        """the batch of the K start poses ``poses``: a host array [K, 4, 4], or 16 float64 entries on the device (K = 1);
+        ``d2d``: of the scan's source cells, which are built first"""
         I = self.iterations if iterations is None else int(iterations)
         shape = self._batch_shape(integrate, copts is not None, coarse_to_fine)
         o = _batch_layout(K, I, with_normal, *shape)
 
         def work(out, n_ptr, T_dev, s):
+            if d2d:
+                self._sources_for_batch(out, n_ptr, o["n_points"], s)
             self._align_batch(n_ptr, T_dev.data_ptr(), K, I, with_normal, out.data_ptr(), o, s, integrate, max_cell_points, copts,
-                              coarse_to_fine)
+                              coarse_to_fine, d2d)
         return PendingPoses(K, I, with_normal, *self._issue(rows, count, o["total"], o["n_points"] * 8, work, poses), 0, *shape)
 
     def submit_filtered_batch(self, pending, T_inits, **kw) -> PendingPoses:
@@ -1385,10 +1416,11 @@ class NDTLocaliser(ScanToMapLocaliser):
         return self.submit_batch(pending._filtered, pending.count_dev, T_inits, **kw)
 
     def _align_batch(self, n_ptr, T_ptr, K, I, with_normal, base, o, s, integrate=False, max_cell_points=0, carve_opts=None,
-                     coarse_to_fine=False):
+                     coarse_to_fine=False, d2d=False):
         """the K alignments of self._pts from the device poses at T_ptr into the batch's buffer at ``base`` (layout ``o``), on
         the single map or, ``coarse_to_fine``, on the pyramid; ``carve_opts``: then the carve at the selected pose, its info
-        words last; ``integrate``: then the map update at the selected pose, its info words behind the batch's part"""
+        words last; ``integrate``: then the map update at the selected pose, its info words behind the batch's part;
+        ``d2d``: the K alignments are those of the source cells in self._src, which the caller has built"""
         trace_ptr, normal_ptr = base + o["trace"] * 8 if I else None, base + o["normal"] * 8 if with_normal and I else None
         if coarse_to_fine:
             caps = self.level_iterations or (max(I, 1),) * len(self.resolutions)
@@ -1397,6 +1429,12 @@ class NDTLocaliser(ScanToMapLocaliser):
                                              base + o["status"] * 8, trace_ptr, normal_ptr, base + o["levels"] * 8 if I else None,
                                              base + o["final"] * 8, base + o["best"] * 8, base + o["T_best"] * 8,
                                              self._pyr_batch_scratch_for(K).data_ptr(), s)
+        elif d2d:
+            self.ctx.ndt_align_d2d_batch(self._src.data_ptr(), self._n_src.data_ptr(), self.capacity, T_ptr, K, I, self.neighbours,
+                                         self.min_correspondences, self.outlier_ratio, self.tol_t, self.tol_r,
+                                         base + o["T_out"] * 8, base + o["status"] * 8, trace_ptr, normal_ptr,
+                                         base + o["final"] * 8, base + o["best"] * 8, base + o["T_best"] * 8,
+                                         self._d2d_batch_scratch_for(K).data_ptr(), s)
         else:
             self.ctx.ndt_align_batch(self._pts.data_ptr(), n_ptr, self.capacity, T_ptr, K, I, self.neighbours,
                                      self.min_correspondences, self.outlier_ratio, self.tol_t, self.tol_r, base + o["T_out"] * 8,
@@ -1417,6 +1455,20 @@ class NDTLocaliser(ScanToMapLocaliser):
             self._batch_hyp = K
         return self._batch_scratch
 
+    def _d2d_batch_scratch_for(self, K):
+        if K > self._d2d_batch_hyp:                                  # grows with the largest batch seen (stream-ordered reuse)
+            self._d2d_batch_scratch = torch.empty(_native.lib.sps_ndt_align_d2d_batch_scratch(self.capacity, K),
+                                                  dtype=torch.uint8, device=self.device)
+            self._d2d_batch_hyp = K
+        return self._d2d_batch_scratch
+
+    def _sources_for_batch(self, out, n_ptr, n_points_at, s):
+        """``_build_sources`` for a d2d=True call, and the count of valid source cells into the pad behind the n_points
+        word (double ``n_points_at`` of ``out``)"""
+        self._build_sources(n_ptr, s)
+        at = 2 * n_points_at + 1
+        out.view(torch.int32)[at:at + 1].copy_(self._n_src[1:2])
+
     def _pyr_batch_scratch_for(self, K):
         if K > self._pyr_batch_hyp:                                  # grows with the largest batch seen (stream-ordered reuse)
             self._pyr_batch_scratch = torch.empty(_native.lib.sps_ndt_pyramid_align_batch_scratch(self.capacity, K),
@@ -1424,8 +1476,17 @@ class NDTLocaliser(ScanToMapLocaliser):
             self._pyr_batch_hyp = K
         return self._pyr_batch_scratch
 
-    def _score(self, T_dev, P, n_points_ptr, score_ptr, s):
-        """the scores of the P poses of T_dev for the thinned points in self._pts (their count at n_points_ptr)"""
+    def _score(self, T_dev, P, n_points_ptr, score_ptr, s, d2d=False):
+        """the scores of the P poses of T_dev for the thinned points in self._pts (their count at n_points_ptr) or, ``d2d``,
+        for the source cells in self._src, which the caller has built"""
+        if d2d:
+            if P > self._d2d_score_poses:                            # grows with the largest grid seen (stream-ordered reuse)
+                self._d2d_score_scratch = torch.empty(_native.lib.sps_ndt_score_d2d_scratch(self.capacity, P), dtype=torch.uint8,
+                                                      device=self.device)
+                self._d2d_score_poses = P
+            self.ctx.ndt_score_poses_d2d(self._src.data_ptr(), self._n_src.data_ptr(), self.capacity, T_dev.data_ptr(), P,
+                                         self.neighbours, self.outlier_ratio, score_ptr, self._d2d_score_scratch.data_ptr(), s)
+            return
         if P > self._score_poses:                                    # grows with the largest grid seen (stream-ordered reuse)
             self._score_scratch = torch.empty(_native.lib.sps_ndt_score_scratch(self.capacity, P), dtype=torch.uint8,
                                               device=self.device)
@@ -1434,36 +1495,49 @@ class NDTLocaliser(ScanToMapLocaliser):
                                  self.outlier_ratio, score_ptr, self._score_scratch.data_ptr(), s)
 
     @torch.no_grad()
-    def score_poses(self, rows, count, poses) -> PendingScores:
+    def score_poses(self, rows, count, poses, d2d: bool = False) -> PendingScores:
         """The NDT score and the points counted at each of the P poses ``poses`` [P, 4, 4] (1 <= P <= 65536), with no
         alignment: the scan is thinned once as ``submit`` thins it, and pose p scores what ``submit_batch`` reports as the
-        final score of a hypothesis that starts there with ``iterations=0``, bit for bit.  Issued on the current stream."""
-        self._refuse_cells("score_poses")
+        final score of a hypothesis that starts there with ``iterations=0``, bit for bit.  Issued on the current stream.
+        ``d2d``: as for ``submit_batch``: the D2D score and the source cells counted, bit for bit what
+        ``submit_batch(..., iterations=0, d2d=True)`` reports."""
+        if self._checked_d2d("score_poses", d2d):                    # poses first: they need no device
+            _checked_poses(poses)
         rows = self._checked_rows(rows)
         T = _checked_poses(poses)
         P = len(T)
         o = _score_layout(P)
 
         def work(out, n_ptr, T_dev, s):
-            self._score(T_dev, P, n_ptr, out.data_ptr() + o["score"] * 8, s)
+            if d2d:
+                self._sources_for_batch(out, n_ptr, o["n_points"], s)
+            self._score(T_dev, P, n_ptr, out.data_ptr() + o["score"] * 8, s, d2d)
         return PendingScores(P, *self._issue(rows, count, o["total"], o["n_points"] * 8, work, T))
 
     @torch.no_grad()
     def relocalise(self, rows, count, poses, keep: int = 8, with_normal: bool = False, iterations: int = None,
                    integrate: bool = False, max_cell_points: int = 0, carve: bool = False,
-                   carve_options: dict = None, coarse_to_fine: bool = False) -> PendingRelocalisation:
+                   carve_options: dict = None, coarse_to_fine: bool = False, d2d: bool = False) -> PendingRelocalisation:
         """Thin, score the P poses ``poses`` [P, 4, 4] (e.g. ``T_center @ pose_grid(...)``), keep the best ``keep`` (1..64)
         by (score descending, index ascending) among those with at least ``min_correspondences`` points counted, register
         from these as ``submit_batch`` does and select among the end poses as it selects.  Everything is issued on the
         current stream with no synchronisation in between; ``result()`` -> RelocalisationResult.  ``integrate`` and
         ``carve``: as for ``submit_batch``.  ``coarse_to_fine``: the grid is scored and its best ``keep`` chosen on the single
-        map as ever; these are then registered as ``submit_batch(..., coarse_to_fine=True)`` registers them."""
+        map as ever; these are then registered as ``submit_batch(..., coarse_to_fine=True)`` registers them.
+        ``d2d``: as for ``submit_batch``: the source cells are built once, the grid is scored as
+        ``score_poses(..., d2d=True)`` scores it and its best ``keep`` are registered as ``submit_batch(..., d2d=True)``
+        registers them."""
+        def grid():
+            T, K = _checked_poses(poses), int(keep)
+            if not 1 <= K <= MAX_HYPOTHESES:
+                raise ValueError(f"keep must be in [1, {MAX_HYPOTHESES}]")
+            return T, K
+        if d2d:                                                      # the grid first: it needs no device
+            self._checked_d2d("relocalise", d2d, coarse_to_fine)
+            grid()
         rows, copts = self._checked_for_batch("relocalise", rows, integrate, max_cell_points, carve, carve_options,
-                                              coarse_to_fine)
-        T = _checked_poses(poses)
-        K = int(keep)
-        if not 1 <= K <= MAX_HYPOTHESES:
-            raise ValueError(f"keep must be in [1, {MAX_HYPOTHESES}]")
+                                              coarse_to_fine, d2d)
+        T, K = grid()
         P = len(T)
         I = self.iterations if iterations is None else int(iterations)
         shape = self._batch_shape(integrate, carve, coarse_to_fine)
@@ -1471,11 +1545,13 @@ class NDTLocaliser(ScanToMapLocaliser):
 
         def work(out, n_ptr, T_dev, s):
             sbase = out.data_ptr()
-            self._score(T_dev, P, n_ptr, sbase + so["score"] * 8, s)
+            if d2d:
+                self._sources_for_batch(out, n_ptr, so["size"] + o["n_points"], s)
+            self._score(T_dev, P, n_ptr, sbase + so["score"] * 8, s, d2d)
             self.ctx.ndt_top_poses(sbase + so["score"] * 8, T_dev.data_ptr(), P, self.min_correspondences, K,
                                    sbase + so["top"] * 8, sbase + so["T_top"] * 8, sbase + so["n_top"] * 8, s)
             self._align_batch(n_ptr, sbase + so["T_top"] * 8, K, I, with_normal, sbase + so["size"] * 8, o, s, integrate,
-                              max_cell_points, copts, coarse_to_fine)
+                              max_cell_points, copts, coarse_to_fine, d2d)
         issued = self._issue(rows, count, so["size"] + o["total"], (so["size"] + o["n_points"]) * 8, work, T)
         return PendingRelocalisation(P, PendingPoses(K, I, with_normal, *issued, so["size"], *shape))
 
@@ -1582,8 +1658,8 @@ class LocalisationLoop:
     (predict -> ``submit_from_device`` -> ``correct_from``, the guess read back with the frame's results: the one
     synchronisation per frame of the loop without an estimator).  That is possible where the filter takes no pose from the
     loop (SPSCVMFilter, LTSFilter, ``takes_pose`` false) and the localiser is an NDTLocaliser without hypotheses or search
-    that registers points (``submit_from_device`` takes no source cells), and without a pyramid unless ``coarse_to_fine``
-    is set; the frame's ``batch`` is then the one-hypothesis batch.  Everywhere else, and with ``device_guess=False``, the
+    that registers points (``submit_from_device`` takes source cells with ``d2d`` only), and without a pyramid unless
+    ``coarse_to_fine`` is set; the frame's ``batch`` is then the one-hypothesis batch.  Everywhere else, and with ``device_guess=False``, the
     predicted pose is fetched to the host first: one more small synchronisation per frame.  ``device_guess=True`` raises
     where the device path is impossible.
 
@@ -1591,6 +1667,11 @@ class LocalisationLoop:
     and ``search`` and the estimator's device path are registered on the pyramid (``submit_batch`` / ``relocalise`` /
     ``submit_from_device`` with ``coarse_to_fine=True``).  An online pyramid with ``update_map`` /
     ``carve_map`` may then take hypotheses and search, and with an estimator the device path is possible with a pyramid.
+
+    ``d2d`` (a localiser with ``source="cells"``; False: everything above, unchanged, a cells localiser taking neither
+    hypotheses nor search nor the device path): the frames of ``hypotheses`` and ``search`` and the estimator's device path
+    are registered distribution to distribution (``submit_batch`` / ``relocalise`` / ``submit_from_device`` with
+    ``d2d=True``).  Not with ``coarse_to_fine``.
 
     A localiser with ``match_status``: a frame whose registration ends with status 0 or 1 but whose scan does
     not match the map at the registered pose (``match.lost``) is flagged as status 2 / 3 is: it keeps the guess, the map and
@@ -1611,7 +1692,7 @@ class LocalisationLoop:
 
     def __init__(self, filter, localiser, initial_pose, hypotheses=None, search=None, search_keep: int = 8,
                  update_map: bool = False, max_cell_points: int = 0, carve_map: bool = False, carve_options: dict = None,
-                 estimator=None, device_guess=None, coarse_to_fine: bool = False, recover: dict = None):
+                 estimator=None, device_guess=None, coarse_to_fine: bool = False, recover: dict = None, d2d: bool = False):
         self.recover, self._flagged_run = None, 0
         if recover is not None:
             unknown = set(recover) - set(self._RECOVER_DEFAULTS)
@@ -1632,13 +1713,19 @@ class LocalisationLoop:
         source, caps, cell_capacity, resolutions = (getattr(localiser, a, getattr(ScanToMapLocaliser, a)) for a in
                                                     ("source", "level_capacities", "cell_capacity", "resolutions"))
         cells = source == "cells"
-        if cells and (hypotheses is not None or search is not None):
-            raise ValueError("hypotheses and search register points: they need an NDTLocaliser with source='points'")
+        self.d2d = bool(d2d)
+        if self.d2d and not cells:
+            raise ValueError("d2d=True needs an NDTLocaliser with source='cells'")
+        if self.d2d and coarse_to_fine:
+            raise ValueError("d2d=True and coarse_to_fine exclude each other: the pyramid registers points")
+        if cells and not self.d2d and (hypotheses is not None or search is not None):
+            raise ValueError("hypotheses and search register points: they need an NDTLocaliser with source='points' "
+                             "(or d2d=True, which registers the scan's cells)")
         self.coarse_to_fine = bool(coarse_to_fine)
         if self.coarse_to_fine and resolutions is None:
             raise ValueError("coarse_to_fine needs a localiser with a pyramid: NDTLocaliser(..., resolutions=...)")
         # what the batch, the search and the device path get on top of the keyword arguments below
-        self._c2f = dict(coarse_to_fine=True) if self.coarse_to_fine else {}
+        self._c2f = dict(coarse_to_fine=True) if self.coarse_to_fine else dict(d2d=True) if self.d2d else {}
         self.update_map, self.max_cell_points = bool(update_map), int(max_cell_points)
         online_pyramid = caps is not None
         if self.update_map and cell_capacity is None and not online_pyramid:
@@ -1686,7 +1773,7 @@ class LocalisationLoop:
             takes_none = (hasattr(filter, "add_pose") or type(filter).__name__ == "LTSFilter"
                           or getattr(filter, "takes_pose", True) is False)
             possible = (takes_none and hasattr(localiser, "submit_from_device") and (resolutions is None or self.coarse_to_fine)
-                        and hypotheses is None and search is None and not cells)
+                        and hypotheses is None and search is None and (not cells or self.d2d))
             if device_guess and not possible:
                 raise ValueError("device_guess=True needs a filter that takes no pose from the loop and an NDTLocaliser without "
                                  "a pyramid, hypotheses or search")

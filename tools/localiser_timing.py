@@ -12,6 +12,7 @@ synthetic.build_map() map, max_distance 1 m, leaf 0.2 m):
     python tools/localiser_timing.py [--frames 200] [--warmup 20] [--cpu-frames 1] [--one-frame] [--cpu-only]
                                      [--localiser {icp,ndt}] [--hypotheses K] [--search P] [--update-map] [--carve]
                                      [--source {points,cells}] [--source-resolution R] [--source-min-points N] [--global]
+                                     [--d2d]
 
 ``--localiser ndt`` times sps_amd.localiser.NDTLocaliser (1 m cells, 7 neighbours) on the same frames and from the same
 start, prints the ICP's per-frame figures of the same session beside it and the build time of both maps; the
@@ -48,6 +49,13 @@ without an estimator, with one on the device path and with one on the host path,
 ``--localiser ndt --source cells`` times distribution-to-distribution registration (NDTLocaliser(..., source="cells")):
 per frame the hipEvent time around submit(), the iterations, the scan's valid source cells and the error against the true
 pose, beside the point path on the same frames, the two alternating frame by frame in one run; then the loop with each.
+
+``--localiser ndt --source cells --d2d`` with any of ``--search P``, ``--hypotheses K``, ``--estimator`` times the
+distribution-to-distribution calls that take several poses beside the point path's on the same frames, the two
+alternating frame by frame, hipEvents around each call: score_poses of P poses and relocalise(keep=8) over them; submit_batch
+from K start poses; and LocalisationLoop(SPSCVMFilter, ., ukf) per frame (host wall clock) on cells with ``d2d`` (device
+path), on cells without (the guess fetched) and on points (device path).  With --one-frame and --search: a warm-up and ONE
+score_poses on each path, the target of a kernel trace.
 
 ``--localiser ndt --resolutions R0,R1,... --coarse-to-fine`` times the batched coarse-to-fine registration,
 hipEvents around each call and the calls of one table alternating frame by frame: submit_from_device(coarse_to_fine=True)
@@ -216,6 +224,8 @@ def main():
                     "distribution-to-distribution registration beside the point path")
     ap.add_argument("--source-resolution", type=float, default=None, help="with --source cells: edge of the scan's cells")
     ap.add_argument("--source-min-points", type=int, default=None, help="with --source cells: points a cell of the scan needs")
+    ap.add_argument("--d2d", action="store_true", help="with --source cells and any of --search, --hypotheses, --estimator: time "
+                    "the d2d=True calls beside the point path's")
     ap.add_argument("--match-status", dest="match_status", action="store_true", help="time submit without and with the "
                     "scan-matching status, alternating, and the status' two launches alone")
     ap.add_argument("--global", dest="global_search", action="store_true", help="with --localiser ndt: time global_search and "
@@ -224,12 +234,15 @@ def main():
     if a.global_search and (a.localiser != "ndt" or a.hypotheses or a.search or a.update_map or a.carve or a.resolutions
                             or a.estimator or a.source == "cells"):
         ap.error("--global needs --localiser ndt and none of the other modes")
-    if a.source == "cells" and (a.localiser != "ndt" or a.hypotheses or a.search or a.update_map or a.carve or a.resolutions
-                                or a.estimator):
-        ap.error("--source cells needs --localiser ndt and none of the other modes")
+    if a.d2d and (a.source != "cells" or a.localiser != "ndt" or not (a.hypotheses or a.search or a.estimator) or a.update_map
+                  or a.carve or a.resolutions or a.global_search or a.match_status):
+        ap.error("--d2d needs --localiser ndt --source cells, any of --search, --hypotheses, --estimator, and no other mode")
+    if a.source == "cells" and not a.d2d and (a.localiser != "ndt" or a.hypotheses or a.search or a.update_map or a.carve
+                                              or a.resolutions or a.estimator):
+        ap.error("--source cells needs --localiser ndt and none of the other modes (--d2d: with --search, --hypotheses, --estimator)")
     if (a.source_resolution is not None or a.source_min_points is not None) and a.source != "cells":
         ap.error("--source-resolution and --source-min-points need --source cells")
-    if a.estimator and (a.localiser != "ndt" or a.hypotheses or a.search or a.update_map or a.carve or a.resolutions):
+    if a.estimator and not a.d2d and (a.localiser != "ndt" or a.hypotheses or a.search or a.update_map or a.carve or a.resolutions):
         ap.error("--estimator needs --localiser ndt and none of the other modes")
     if a.c2f and (not a.resolutions or a.update_map or a.carve or a.estimator or a.one_frame):
         ap.error("--coarse-to-fine needs --resolutions and none of --update-map, --carve, --estimator, --one-frame")
@@ -254,6 +267,8 @@ def main():
         return match_status_main(a, dscans, mp, T_init)
     if a.global_search:
         return ndt_global_main(a, scans, mp)
+    if a.d2d:
+        return ndt_d2d_batch_main(a, scans, dscans, mp, T_init)
     if a.estimator:
         return ndt_estimator_main(a, scans, dscans, mp, T_init)
     if a.c2f:
@@ -547,6 +562,97 @@ def ndt_d2d_main(a, scans, dscans, mp, T_init):
         out[name]["loop_sps_cvm_ms"] = round(float(np.median(t_loop)) * 1e3, 4)
         out[name]["loop_flagged_frames"] = int(flagged)
         print(f"LocalisationLoop(sps_cvm, ndt {name}) {out[name]['loop_sps_cvm_ms']:.3f} ms per frame ({flagged} flagged)", flush=True)
+    print(json.dumps(out))
+
+
+def ndt_d2d_batch_main(a, scans, dscans, mp, T_init):
+    """--source cells --d2d: the calls that take several poses, distribution to distribution against the point path, the two
+    alternating frame by frame in one run, hipEvents around each call (the windows include the host staging of the poses, as
+    in ndt_search_main).  --search P: score_poses and relocalise(keep=8); --hypotheses K: submit_batch; --estimator: the loop
+    with the UKF per frame (host wall clock), cells on the device path (d2d), cells on the host path, points on the device
+    path."""
+    from sps_amd.pose_estimator import PoseEstimator
+    map64 = mp[:, :3].astype(np.float64)
+    kw = dict(source="cells", source_resolution=a.source_resolution, source_min_points=a.source_min_points)
+    locs = {"points": (NDTLocaliser(map64), {}), "cells": (NDTLocaliser(map64, **kw), dict(d2d=True))}
+    st = torch.cuda.current_stream()
+    stats = lambda v: {"median": round(float(np.median(v)), 4), "min": round(min(v), 4), "max": round(max(v), 4)}
+    out = {"frames": a.frames, "warmup": a.warmup, "n_cells": locs["points"][0].n_cells}
+
+    def timed(call):
+        """-> (ms, result) of one call, hipEvents around its issue"""
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(st)
+        pend = call()
+        e1.record(st)
+        r = pend.result()
+        e1.synchronize()
+        return e0.elapsed_time(e1), r
+
+    def alternate(what, make):
+        """make(loc, extra, scan) -> a pending call; both localisers per frame, the order swapped every frame"""
+        ms, last = {n: [] for n in locs}, {}
+        for k in range(a.warmup + a.frames):
+            s = dscans[k % len(dscans)]
+            for n in (tuple(locs) if k % 2 == 0 else tuple(locs)[::-1]):
+                t, last[n] = timed(lambda: make(*locs[n], s))
+                if k >= a.warmup:
+                    ms[n].append(t)
+        out[what] = {n: stats(v) for n, v in ms.items()}
+        out[what]["ratio_points_over_cells"] = round(out[what]["points"]["median"] / out[what]["cells"]["median"], 3)
+        print(f"{what}: points median {out[what]['points']['median']:.3f} ms (min {min(ms['points']):.3f} max {max(ms['points']):.3f}), "
+              f"cells d2d median {out[what]['cells']['median']:.3f} ms (min {min(ms['cells']):.3f} max {max(ms['cells']):.3f}), "
+              f"ratio {out[what]['ratio_points_over_cells']:.2f}", flush=True)
+        return last
+
+    if a.search:
+        poses = search_poses(T_init, a.search)
+        if a.one_frame:
+            for n, (loc, extra) in locs.items():
+                for k in range(max(a.warmup, 1)):
+                    loc.submit(dscans[k % len(dscans)], len(dscans[k % len(dscans)]), T_init).result()
+                torch.cuda.synchronize()
+                sc, cnt = loc.score_poses(dscans[0], len(dscans[0]), poses, **extra).result()
+                print(json.dumps({"one_frame": True, "path": n, "search": a.search, "best": int(np.argmax(sc)), "count_max": int(cnt.max())}))
+            return
+        last = alternate(f"score_poses_P{a.search}", lambda loc, extra, s: loc.score_poses(s, len(s), poses, **extra))
+        out["score_best_index"] = {n: int(np.argmax(r[0])) for n, r in last.items()}
+        out["score_count_max"] = {n: int(r[1].max()) for n, r in last.items()}
+        last = alternate(f"relocalise_P{a.search}_keep8", lambda loc, extra, s: loc.relocalise(s, len(s), poses, keep=8, **extra))
+        out["relocalise"] = {n: {"index": r.index, "status": r.batch.results[max(r.batch.best, 0)].status,
+                                 "error_m": round(LR.pose_difference(r.pose, np.eye(4))[0], 5)} for n, r in last.items()}
+    if a.hypotheses:
+        starts = hypothesis_starts(T_init, a.hypotheses)
+        last = alternate(f"submit_batch_K{a.hypotheses}", lambda loc, extra, s: loc.submit_batch(s, len(s), starts, **extra))
+        out["batch"] = {n: {"best": r.best, "iterations_max": max(x.iterations for x in r.results),
+                            "iterations_sum": sum(x.iterations for x in r.results), "n_points": r.results[0].n_points,
+                            "n_sources": r.results[0].n_sources,
+                            "error_m": round(LR.pose_difference(r.pose, np.eye(4))[0], 5)} for n, r in last.items()}
+    if a.estimator:
+        net = net_from_params(O.random_params(seed=0)).cuda().eval().freeze()
+        mpt = torch.from_numpy(mp)
+        I4 = np.eye(4)
+
+        def make_loop(n, **lkw):
+            return LocalisationLoop(SPSCVMFilter(net, mpt, voxel_size=VS, epsilon=EPS), locs[n][0], I4,
+                                    estimator=PoseEstimator(I4, "cuda"), **lkw)
+        loops = {"cells_d2d_device": make_loop("cells", d2d=True), "cells_host": make_loop("cells"),
+                 "points_device": make_loop("points")}
+        assert [l.device_guess for l in loops.values()] == [True, False, True]
+        t_loop, flagged = {m: [] for m in loops}, {m: 0 for m in loops}
+        for k in range(a.warmup + a.frames):
+            order = tuple(loops) if k % 2 == 0 else tuple(loops)[::-1]
+            for m in order:                                          # alternating: all see the same machine state
+                t0 = time.perf_counter()
+                step = loops[m].step(scans[k % len(scans)], dt=0.1)
+                if k >= a.warmup:
+                    t_loop[m].append((time.perf_counter() - t0) * 1e3)
+                    flagged[m] += step.flagged
+        for m in loops:
+            out[f"loop_{m}_ms"] = stats(t_loop[m])
+            out[f"loop_{m}_flagged"] = int(flagged[m])
+            print(f"LocalisationLoop(sps_cvm, ndt, ukf) {m:17s} median {out[f'loop_{m}_ms']['median']:.3f} ms per frame (min "
+                  f"{min(t_loop[m]):.3f} max {max(t_loop[m]):.3f}; {flagged[m]} flagged)", flush=True)
     print(json.dumps(out))
 
 
