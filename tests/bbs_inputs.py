@@ -1,6 +1,6 @@
 """The inputs that tests/test_bbs_cpu.py and tests/test_hip_bbs.py share: small hand-built maps and scans for the global
-search, chosen so that every path of the kernels is taken (module docstring of tests/test_hip_bbs.py), and the restatement
-of each case, computed once."""
+search that go through the wrapper (the module docstring of tests/test_hip_bbs.py lists what they cover), and the
+restatement of each case, computed once.  The cases that need the raw ABI are in tests/bbs_edge_inputs.py."""
 import functools
 import math
 
@@ -90,6 +90,14 @@ _case("empty_slice", SCAN7, 0, 7, scan_z=(100.0, 200.0), T_up=T_TILT)
 _case("zero_map", SCAN7, 255, 7, map_z=(50.0, 60.0))
 _case("one_cell", SCAN7, 255, 7, map_xyz=np.array([[0.2, 0.2, 1.0], [0.3, 0.1, 1.5]]))
 _case("level0_only", SCAN7, 255, 7, levels=0)
+# three chunks of k_bbs_score through the wrapper: 2544 thinned slice points (the CPU test checks the count)
+_case("three_chunks", scan_of(MAP, true_pose(3), 2600, 40), 2544, 3)
+# the frontier cuts lists of 3344 and more slots, which four to six workgroups of k_bbs_count / k_bbs_write compact: one
+# level below the leaves, 16 yaws, scans of 3, 5 and 9 points, so that hundreds of nodes tie at every score.  The CPU test
+# says where each cut falls.  984 = the roots of the 3-point scan that score 2 or 3: the frontier is filled exactly.
+for _n, _seed, _fs in ((3, 30, (900, 901, 984, 1500)), (5, 30, (900, 1500)), (9, 33, (900, 1500))):
+    for _f in _fs:
+        _case(f"cut_n{_n}_f{_f}", scan_of(MAP, true_pose(), _n, _seed), _n, 16, levels=1, keep=64, frontier=_f)
 
 
 def thinned(rows):

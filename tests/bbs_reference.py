@@ -106,7 +106,10 @@ def score_nodes(Gl, l, nodes, offs):
 
 def search(G0, L, r, i0, j0, pts, A, keep=8, frontier=16384, min_score=1, scan_z=(-np.inf, np.inf), T_up=None):
     """-> dict(index, score, poses, n_found, certified, dropped_bound, n_dropped, candidates, kept, n_slice,
-    candidate_lists, kept_lists), the lists as leaf / node ids per level"""
+    candidate_lists, kept_lists, slot_lists, slot_scores), the lists as leaf / node ids per level.  slot_lists[l] is the
+    candidate list of level l as the device lays it out -- at level L the root order, below it four slots per kept parent
+    in the parents' order, -1 where the child is outside the grid -- and slot_scores[l] the score of every slot, -1 for a
+    void"""
     H, W = G0.shape
     T_up = np.eye(4) if T_up is None else np.asarray(T_up, dtype=np.float64)
     if not 1 <= keep <= 64:
@@ -122,6 +125,8 @@ def search(G0, L, r, i0, j0, pts, A, keep=8, frontier=16384, min_score=1, scan_z
     ids = lambda nd: (nd[:, 0] * H + nd[:, 1]) * W + nd[:, 2]
     bound, n_dropped = -1, 0
     n_cand, n_kept, cand_lists, kept_lists = np.zeros(L + 1, np.int64), np.zeros(L + 1, np.int64), [None] * (L + 1), [None] * (L + 1)
+    slot_lists, slot_scores = [None] * (L + 1), [None] * (L + 1)
+    filled = np.ones(len(nodes), bool)                                       # the slots of the level that hold a node
     for l in range(L, -1, -1):
         sc = score_nodes(pooled(G0, l), l, nodes, offs)
         alive = np.nonzero(sc >= min_score)[0]
@@ -134,15 +139,18 @@ def search(G0, L, r, i0, j0, pts, A, keep=8, frontier=16384, min_score=1, scan_z
             bound = max(bound, int(sc[gone].max()))
         n_dropped += int(gone.sum())
         n_cand[l], n_kept[l], cand_lists[l], kept_lists[l] = len(nodes), len(alive), ids(nodes), ids(nodes[alive])
+        slot_lists[l], slot_scores[l] = np.full(len(filled), -1, np.int64), np.full(len(filled), -1, np.int64)
+        slot_lists[l][filled], slot_scores[l][filled] = ids(nodes), sc
         kept_nodes, kept_scores = nodes[alive], sc[alive]
         if l > 0:
             h = 1 << (l - 1)
-            kids = []
+            kids, inside = [], []
             for a, j, i in kept_nodes.tolist():
                 for dj, di in ((0, 0), (0, 1), (1, 0), (1, 1)):
-                    if i + di * h < W and j + dj * h < H:
+                    inside.append(i + di * h < W and j + dj * h < H)
+                    if inside[-1]:
                         kids.append((a, j + dj * h, i + di * h))
-            nodes = np.array(kids, np.int64).reshape(-1, 3)
+            nodes, filled = np.array(kids, np.int64).reshape(-1, 3), np.array(inside, bool)
     leaf_ids = ids(kept_nodes)
     order = sorted(range(len(leaf_ids)), key=lambda c: (-int(kept_scores[c]), int(leaf_ids[c])))[:keep]
     index, score = np.full(keep, -1, np.int64), np.zeros(keep, np.int64)
@@ -157,7 +165,7 @@ def search(G0, L, r, i0, j0, pts, A, keep=8, frontier=16384, min_score=1, scan_z
         certified += 1
     return dict(index=index, score=score, poses=poses, n_found=len(order), certified=certified, dropped_bound=bound,
                 n_dropped=n_dropped, candidates=n_cand, kept=n_kept, n_slice=n_slice, candidate_lists=cand_lists,
-                kept_lists=kept_lists)
+                kept_lists=kept_lists, slot_lists=slot_lists, slot_scores=slot_scores)
 
 
 # ---- exhaustive scorer ---------------------------------------------------------------------------------------------------

@@ -2,13 +2,20 @@
 localiser, global search" section of include/sps_hip.h) against the numpy restatement in tests/bbs_reference.py.  Every
 quantity is an integer or a pose whose operations the restatement fixes, so every comparison is exact.
 
-The cases (tests/bbs_inputs.py) are the smallest that can still go wrong: a grid of 37 x 21 cells with three pooled
-levels (no multiple of 8 on either axis, so children fall outside the grid and pooled cells reach into the negative pad),
-a grid of one cell and an all-zero one; 1, 7 and 16 yaws; 0, 1, 255, 256 and 257 points in the scan slice (the score
-kernel's workgroup stages 1024 offsets at a time and gives every wave a quarter; the offsets kernel has 256 threads);
-points exactly on cell edges, off the grid on all four sides, rows that are not finite; a slice that excludes every point;
-a frontier below the survivors of the first level with equal scores on both sides of the cut; a frontier so small that the
-certificate fails; more results asked for than leaves found; a min_score that prunes everything."""
+The cases (tests/bbs_inputs.py) go through the wrapper: a grid of 37 x 21 cells with three pooled levels (no multiple of
+8 on either axis, so children fall outside the grid and pooled cells reach into the negative pad), a grid of one cell and
+an all-zero one; 1, 3, 7 and 16 yaws; 0, 1, 255, 256 and 257 points in the scan slice (the edges of the 256 threads of the
+offsets kernel; all within one chunk of the 1024 offsets that the score kernel stages at a time) and 2544 points (three
+chunks, the last one partial); points exactly on cell edges, off the grid on all four sides, rows that are not finite; a
+slice that excludes every point; a frontier below the survivors of the first level with equal scores on both sides of the
+cut, within one workgroup of the compaction (160 and 240 slots) and, in the cut_* cases, across four to six workgroups
+(3344 to 6000 slots of a grid with one pooled level, frontiers 900, 901, 984 and 1500: ties kept in several workgroups and
+dropped in the quota's own and in later ones, void slots in front of the cut, a frontier that the scores above the cut
+fill exactly) with 64 results picked from 1500 leaves that tie at two or three scores; a frontier so small that the
+certificate fails; more results asked for than leaves found; a min_score that prunes everything.  tests/test_bbs_cpu.py
+asserts from the restatement alone that each case sits where it is said to.  Capacities other than 4096, exact row counts
+on the chunk edges, the threshold kernel's segment lengths, offsets near the 16-bit limit and counts or frontiers on
+their limits need the raw ABI: tests/test_hip_bbs_edges.py."""
 import numpy as np
 import pytest
 import torch
