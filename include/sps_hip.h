@@ -952,6 +952,44 @@ int sps_ndt_score_poses_d2d(sps_ctx *ctx, const double *src_dev, const int32_t *
                             int64_t n_pose, int neighbours, double outlier_ratio, double *score_dev, void *scratch_dev,
                             void *stream);
 
+/* ---- NDT localiser, distribution to distribution, pyramid ----------------------------------------------------------------
+ * sps_ndt_align_d2d registered coarse to fine: the scan's cells are built at one resolution per level and registered against
+ * the context's pyramid of map cells, the pose handed from level to level on the device as sps_ndt_pyramid_align hands it.
+ *   Additive: sps_version() is unchanged, and no call above changes.  The rules of sps_ndt_align_d2d hold;
+ * neither call allocates, synchronises or raises the sticky error.
+ *
+ * sps_ndt_pyramid_source_build: sps_ndt_source_build at n_levels (1 .. SPS_NDT_PYR_MAX_LEVELS) resolutions at once.
+ *   source_resolution and min_points are host arrays of n_levels entries, in no way tied to the map's levels (equal entries
+ *   are legal).  src_dev double[n_levels][cap][SPS_NDT_SRC_REC], src_count_dev int32[n_levels][cap] (may be NULL) and
+ *   n_src_dev int32[n_levels][2]: level l is, bit for bit, what sps_ndt_source_build writes for (source_resolution[l],
+ *   min_points[l]): records, counts, (cells, valid cells), and the rows beyond the cells are not written.  It does not read
+ *   the context's maps.  Arguments are checked as sps_ndt_source_build checks them, every level's.  Launches: seven and four
+ *   memsets whatever n_levels and the data (the level is a grid dimension).  scratch_dev:
+ *   sps_ndt_pyramid_source_scratch(cap, n_levels) bytes (-1 for arguments out of range), 256-byte aligned.
+ *
+ * sps_ndt_pyramid_align_d2d: sps_ndt_pyramid_align with launch A replaced by sps_ndt_align_d2d's, against the pyramid of
+ *   sps_ndt_pyramid_build[_dynamic] (refused without one).  src_dev and n_src_dev are sps_ndt_pyramid_source_build's (or
+ *   hand-made) with cap = cap_src and n_levels = the pyramid's: a slot at level l reads the first min(cap_src, n_src_dev[l][0])
+ *   records of src_dev[l] against the map of level l, with that level's (-d1, d2).  Slots, level_iters, status_dev (its third
+ *   word counts sources), trace_dev, normal_dev, level_dev, the budget and "status 2 / 3 are final at any level and T_out_dev
+ *   is then T_init_host bit for bit" are sps_ndt_pyramid_align's.  The handoff has one more rule: the call starts at level 0,
+ *   and the level that follows l is the next l' > l whose valid sources, min(cap_src, n_src_dev[l'][1]), are at least
+ *   min_corr; where there is none, l is the last level: its convergence is status 0 and its cap ends the call with status 1.
+ *   (A level with fewer valid sources could only end the call with status 2 and throw the pose away.)  So one level gives
+ *   the bits of sps_ndt_align_d2d, and several levels those of as many sps_ndt_align_d2d calls with iters = level_iters[l]
+ *   over the levels entered, each started from the end pose of the one before (while every one of them ends with status 0
+ *   or 1).  Launches: 1 + 2 * iters, no memset.  scratch_dev: sps_ndt_pyramid_align_d2d_scratch(cap_src) bytes (-1 for
+ *   cap_src out of range). */
+int64_t sps_ndt_pyramid_source_scratch(int64_t cap, int n_levels);
+int sps_ndt_pyramid_source_build(sps_ctx *ctx, const double *pts_dev, const int32_t *n_dev, int64_t cap, int n_levels,
+                                 const double *source_resolution, const int32_t *min_points, double eig_ratio, double *src_dev,
+                                 int32_t *src_count_dev, int32_t *n_src_dev, void *scratch_dev, void *stream);
+int64_t sps_ndt_pyramid_align_d2d_scratch(int64_t cap_src);
+int sps_ndt_pyramid_align_d2d(sps_ctx *ctx, const double *src_dev, const int32_t *n_src_dev, int64_t cap_src,
+                              const double *T_init_host, int iters, const int32_t *level_iters, int neighbours, int min_corr,
+                              double tol_t, double tol_r, double *T_out_dev, int32_t *status_dev, double *trace_dev,
+                              double *normal_dev, int32_t *level_dev, void *scratch_dev, void *stream);
+
 /* ---- pose estimator (unscented Kalman filter with IMU prediction) -----------------------------------------------------
  * hdl_localization's pose system as published, restated: tests/ukf_reference.py is the specification, not that package
  * (DESIGN.md 8j lists the differences).  Additive: sps_version() is unchanged.  No entry takes a context, allocates,

@@ -26,7 +26,9 @@ line then tells the iterations per level); with ``--update-map`` / ``--carve-map
 per level; with ``--source cells`` it registers distribution to distribution (one Gaussian per cell of the scan against
 the map's; ``--source-resolution``, ``--source-min-points``), ``n_corr`` then counts source cells and the ``loc:`` line
 ends with ``| N sources``, the scan's valid cells; ``--d2d`` lets ``--hypotheses``, ``--search`` and the device path of
-``--estimator ukf`` register the scan's cells too.  Frames then run one at a time; behind each frame's lines comes
+``--estimator ukf`` register the scan's cells too; ``--source cells --resolutions 2,1,0.5 --source-resolutions 2,1,0.5``
+registers the scan's cells coarse to fine, built once per level at that level's edge (``--source-min-points`` then also
+takes one value per level; the ``| N sources`` are those of the level the frame ended on).  Frames then run one at a time; behind each frame's lines comes
 ``loc: status iterations n_corr rmse | err_t err_r`` (metres, degrees, against the replayed pose map_tr @ pose) and at
 the end the absolute pose error evo_ape prints by default.  ``--global-start`` (with ``--localiser ndt``) takes the loop's
 initial pose from ``NDTLocaliser.localise_global`` on the first raw scan instead of from the sequence (``--global-resolution``,
@@ -178,14 +180,15 @@ def closed_loop(name, f, pc_map, replay, finish, traj_out, which="icp", hypothes
             xyz = np.ascontiguousarray(pc_map[:, :3], dtype=np.float64)
             level_capacities = tuple(max(2 * len(np.unique(np.floor(xyz / r).astype(np.int64), axis=0)), 4096) for r in resolutions)
         localiser = NDTLocaliser(pc_map[:, :3], resolutions=resolutions, iterations=sum(caps), level_iterations=caps,
-                                 level_capacities=level_capacities, **gkw, **mkw)
+                                 level_capacities=level_capacities, **skw, **gkw, **mkw)
     elif update_map or carve_map:                                # an online map: room for twice the map's cells by default
         n_cells = NDTLocaliser(pc_map[:, :3]).n_cells
         localiser = NDTLocaliser(pc_map[:, :3], cell_capacity=cell_capacity or max(2 * n_cells, 4096), **skw, **gkw, **mkw)
     elif resolutions is not None:                                # coarse to fine; hypotheses and search keep the single map
                                                                  # unless --coarse-to-fine sends them to the pyramid too
         caps = level_iterations or (30,) * len(resolutions)       # the budget is their sum: it cuts no level short
-        localiser = NDTLocaliser(pc_map[:, :3], resolutions=resolutions, iterations=sum(caps), level_iterations=caps, **gkw, **mkw)
+        localiser = NDTLocaliser(pc_map[:, :3], resolutions=resolutions, iterations=sum(caps), level_iterations=caps, **skw, **gkw,
+                                 **mkw)
     else:
         localiser = NDTLocaliser(pc_map[:, :3], **skw, **gkw, **mkw) if which == "ndt" else ScanToMapLocaliser(pc_map[:, :3], **mkw)
     loop, stamps, ref, estimates = None, [], [], []
@@ -354,8 +357,13 @@ def frame_motion(estimator, k):
                    "neither --hypotheses nor --search, and the estimator's guess is fetched to the host)")
 @click.option("--source-resolution", "source_resolution", type=float, default=None,
               help="with --source cells: edge of the scan's cells in m (default: the map's resolution)")
-@click.option("--source-min-points", "source_min_points", type=int, default=None,
-              help="with --source cells: points a cell of the scan needs to be used (default: the map's)")
+@click.option("--source-min-points", "source_min_points", type=str, default=None,
+              help="with --source cells: points a cell of the scan needs to be used (default: the map's); with "
+                   "--source-resolutions also N0,N1,..., one per level")
+@click.option("--source-resolutions", "source_resolutions", type=str, default=None,
+              help="with --source cells --resolutions R0,R1,...: S0,S1,... the edge of the scan's cells at every level; the "
+                   "scan's cells are then registered coarse to fine against the pyramid (without it --source cells takes "
+                   "no --resolutions)")
 @click.option("--global-start", "global_start", is_flag=True,
               help="with --localiser ndt: the loop's initial pose comes from a global search of the first raw scan on an "
                    "occupancy grid of the map (branch and bound over x, y, yaw), not from the sequence")
@@ -394,7 +402,7 @@ def frame_motion(estimator, k):
               help="with --estimator: a text file of rows `t ax ay az gx gy gz`, scan k being at k * scan-period")
 def main(name, weights, sequence, config, epsilon, out_dir, n_synth, localise, which, traj_out, hyp_counts, hyp_steps,
          search_counts, search_steps, update_map, cell_capacity, max_cell_points, carve_map, carve_miss_frames, carve_sigma,
-         resolutions, level_iterations, coarse_to_fine, level_capacities, source, d2d, source_resolution, source_min_points,
+         resolutions, level_iterations, coarse_to_fine, level_capacities, source, d2d, source_resolution, source_min_points, source_resolutions,
          estimator, initial_velocity, scan_period, imu_rate, imu_file, global_start, global_resolution, global_map_z,
          global_scan_z, global_yaw_steps, global_levels, global_frontier, match_status, min_inlier_fraction, recover_global,
          inject_jump):
@@ -449,11 +457,29 @@ def main(name, weights, sequence, config, epsilon, out_dir, n_synth, localise, w
         raise click.UsageError("--source-resolution and --source-min-points need --source cells")
     if d2d and (source != "cells" or (hyp_counts is None and search_counts is None and estimator is None)):
         raise click.UsageError("--d2d needs --source cells and one of --hypotheses, --search, --estimator ukf")
-    if source == "cells" and (resolutions is not None or ((hyp_counts is not None or search_counts is not None) and not d2d)):
+    if source_resolutions is not None and (source != "cells" or resolutions is None or source_resolution is not None):
+        raise click.UsageError("--source-resolutions needs --source cells and --resolutions, and no --source-resolution")
+    if source == "cells" and ((resolutions is not None and source_resolutions is None)
+                              or ((hyp_counts is not None or search_counts is not None) and not d2d)):
         raise click.UsageError("--source cells takes no --resolutions, --hypotheses or --search: they register points"
-                               " (--d2d lets --hypotheses and --search register the scan's cells)")
-    source = dict(source="cells", source_resolution=source_resolution, source_min_points=source_min_points) \
-        if source == "cells" else None
+                               " (--d2d lets --hypotheses and --search register the scan's cells; --source-resolutions "
+                               "registers them on the pyramid of --resolutions)")
+    try:
+        if source_min_points is not None:
+            mps = tuple(int(v) for v in source_min_points.split(","))
+            source_min_points = mps[0] if len(mps) == 1 else mps
+        if source_resolutions is not None:
+            source_resolutions = tuple(float(v) for v in source_resolutions.split(","))
+    except ValueError:
+        raise click.UsageError("--source-min-points takes integers and --source-resolutions numbers, separated by commas")
+    if isinstance(source_min_points, tuple) and source_resolutions is None:
+        raise click.UsageError("a --source-min-points list needs --source-resolutions")
+    if source == "cells":
+        source = dict(source="cells", source_resolution=source_resolution, source_min_points=source_min_points)
+        if source_resolutions is not None:
+            source["source_resolutions"] = source_resolutions
+    else:
+        source = None
     if estimator is None and (initial_velocity != "0,0,0" or imu_rate is not None or imu_file is not None):
         raise click.UsageError("--initial-velocity, --imu-rate and --imu need --estimator")
     if estimator is not None:

@@ -179,6 +179,11 @@ def _load() -> C.CDLL:
         "sps_ndt_align_d2d_batch_scratch": (i64, [i64, i32]),
         "sps_ndt_align_d2d_batch": (i32, [vp, vp, vp, i64, vp, i32, i32, i32, i32, C.c_double, C.c_double, C.c_double, vp, vp, vp,
                                           vp, vp, vp, vp, vp, vp]),
+        "sps_ndt_pyramid_source_scratch": (i64, [i64, i32]),
+        "sps_ndt_pyramid_source_build": (i32, [vp, vp, vp, i64, i32, vp, vp, C.c_double, vp, vp, vp, vp, vp]),
+        "sps_ndt_pyramid_align_d2d_scratch": (i64, [i64]),
+        "sps_ndt_pyramid_align_d2d": (i32, [vp, vp, vp, i64, vp, i32, vp, i32, i32, C.c_double, C.c_double, vp, vp, vp, vp, vp, vp,
+                                            vp]),
         "sps_ndt_score_d2d_scratch": (i64, [i64, i64]),
         "sps_ndt_score_poses_d2d": (i32, [vp, vp, vp, i64, vp, i64, i32, C.c_double, vp, vp, vp]),
         "sps_ukf_state_bytes": (i64, []),
@@ -226,6 +231,8 @@ EXPORTS = ["sps_last_error", "sps_version", "sps_ctx_create", "sps_ctx_destroy",
            "sps_ndt_pyramid_align_batch_scratch", "sps_ndt_pyramid_align_batch",
            "sps_ndt_source_scratch", "sps_ndt_source_build", "sps_ndt_align_d2d_scratch", "sps_ndt_align_d2d",
            "sps_ndt_align_d2d_batch_scratch", "sps_ndt_align_d2d_batch", "sps_ndt_score_d2d_scratch", "sps_ndt_score_poses_d2d",
+           "sps_ndt_pyramid_source_scratch", "sps_ndt_pyramid_source_build", "sps_ndt_pyramid_align_d2d_scratch",
+           "sps_ndt_pyramid_align_d2d",
            "sps_ukf_state_bytes", "sps_ukf_init", "sps_ukf_predict", "sps_ukf_predict_dt", "sps_ukf_correct"]
 NDT_SRC_REC = 10           # SPS_NDT_SRC_REC: doubles of a source record
 BBS_MAX_LEVELS = 8         # SPS_BBS_MAX_LEVELS
@@ -685,6 +692,26 @@ class Context:
                             outlier_ratio: float, score_ptr: int, scratch_ptr: int, stream: int):
         check(lib.sps_ndt_score_poses_d2d(self.handle, src_ptr, n_src_ptr, int(cap_src), T_ptr, int(n_pose), int(neighbours),
                                           float(outlier_ratio), score_ptr, scratch_ptr, stream))
+
+    # ---- NDT localiser, distribution to distribution, pyramid (include/sps_hip.h, same title) ----
+    def ndt_pyramid_source_build(self, pts_ptr, n_dev_ptr: int, cap: int, source_resolutions, min_points, eig_ratio: float,
+                                 src_ptr, src_count_ptr, n_src_ptr: int, scratch_ptr: int, stream: int):
+        """source_resolutions, min_points: one entry per level; src [L][cap][NDT_SRC_REC], src_count [L][cap], n_src [L][2]"""
+        L = len(source_resolutions)
+        if len(min_points) != L:
+            raise ValueError("min_points needs one entry per level")
+        res = (C.c_double * L)(*[float(v) for v in source_resolutions])
+        mp = (C.c_int32 * L)(*[int(v) for v in min_points])
+        check(lib.sps_ndt_pyramid_source_build(self.handle, pts_ptr, n_dev_ptr, int(cap), L, res, mp, float(eig_ratio), src_ptr,
+                                               src_count_ptr, n_src_ptr, scratch_ptr, stream))
+
+    def ndt_pyramid_align_d2d(self, src_ptr, n_src_ptr: int, cap_src: int, T_init, iters: int, level_iters, neighbours: int,
+                              min_corr: int, tol_t: float, tol_r: float, T_out_ptr: int, status_ptr: int, trace_ptr, normal_ptr,
+                              level_ptr, scratch_ptr: int, stream: int):
+        caps = (C.c_int32 * len(level_iters))(*[int(v) for v in level_iters])
+        check(lib.sps_ndt_pyramid_align_d2d(self.handle, src_ptr, n_src_ptr, int(cap_src), self._mat(T_init), int(iters), caps,
+                                            int(neighbours), int(min_corr), float(tol_t), float(tol_r), T_out_ptr, status_ptr,
+                                            trace_ptr, normal_ptr, level_ptr, scratch_ptr, stream))
 
     def train_forward(self, params_ptr: int, numel: int, coords_ptr: int, ld: int, n: int, voxel_size: float,
                       scores_ptr: int, batch_stats_ptr, stream: int):

@@ -8,30 +8,35 @@ namespace {
 //   0xFF  the update's hash keys, the map's hash keys, the map's hash ranks
 //   0x7F  the update's hash `first`, the cells' `lead`
 //   0     the cells' `bcnt`, the map's state words
+// For the pyramid of sources (ndt_d2d_pyramid_host.inc.h) it is array-major: every array holds the n_levels levels back to
+// back, so the three memsets still serve.  s, m and d are then level 0's views and w what turns them into level l's
+// (ndt_pyr_upd_slice, ndt_pyr_src_map, ndt_pyr_src_dyn); info: int[n_levels][4].  One level is the single build's layout.
 struct NdtSrcLayout {
   NdtUpdScratch s;
   NdtMap m;
   NdtDyn d;
+  NdtPyrUpdStride w;
   int *info;
   char *ff, *sf, *zero;
   size_t ff_bytes, sf_bytes, zero_bytes;
 };
-inline size_t ndt_src_layout(int64_t cap, double resolution, char *base, NdtSrcLayout *L) {
-  const size_t n = (size_t)(cap < 1 ? 1 : cap), hs = (size_t)ndt_hash_slots(cap);
+inline size_t ndt_src_layout(int64_t cap, int n_levels, double resolution, char *base, NdtSrcLayout *L) {
+  const size_t n = (size_t)(cap < 1 ? 1 : cap), hs = (size_t)ndt_hash_slots(cap), l = (size_t)n_levels;
   size_t at = 0;
   auto take = [&](size_t bytes) {
     char *p = base ? base + at : nullptr;
     at += ndt_upd_align(bytes);
     return p;
   };
-  char *shkeys = take(hs * 8), *mhkeys = take(hs * 8), *mhrank = take(hs * 4);
+  char *shkeys = take(l * hs * 8), *mhkeys = take(l * hs * 8), *mhrank = take(l * hs * 4);
   const size_t ff_end = at;
-  char *shfirst = take(hs * 4), *lead = take(n * 4);
+  char *shfirst = take(l * hs * 4), *lead = take(l * n * 4);
   const size_t sf_end = at;
-  char *bcnt = take(n * 4), *state = take(16);
+  char *bcnt = take(l * n * 4), *state = take(l * 16);
   const size_t zero_end = at;
-  char *q = take(n * 3 * 8), *bstat = take(n * 10 * 8), *cell_of = take(n * 4), *slot_of = take(n * 4), *list = take(n * 4),
-       *tcell = take(n * 4), *shrank = take(hs * 4), *nt = take(4), *cstart = take(n * 4), *keys = take(n * 8), *info = take(16);
+  char *q = take(n * 3 * 8), *bstat = take(l * n * 10 * 8), *cell_of = take(l * n * 4), *slot_of = take(l * n * 4),
+       *list = take(l * n * 4), *tcell = take(l * n * 4), *shrank = take(l * hs * 4), *nt = take(l * 4), *cstart = take(l * n * 4),
+       *keys = take(l * n * 8), *info = take(l * 16);
   if (L) {
     NdtUpdScratch &s = L->s;
     s.q = (double *)q, s.bstat = (double *)bstat, s.cell_of = (int *)cell_of, s.slot_of = (int *)slot_of;
@@ -39,11 +44,13 @@ inline size_t ndt_src_layout(int64_t cap, double resolution, char *base, NdtSrcL
     s.h.keys = (uint64_t *)shkeys, s.h.first = (int *)shfirst, s.h.rank = (int *)shrank, s.h.mask = (uint32_t)(hs - 1);
     L->m = NdtMap{};
     L->m.h.keys = (uint64_t *)mhkeys, L->m.h.first = nullptr, L->m.h.rank = (int *)mhrank, L->m.h.mask = (uint32_t)(hs - 1);
-    L->m.n_cells = (int)n, L->m.resolution = resolution;   // rec, count and keys are not read by the bodies used
+    L->m.n_cells = (int)n, L->m.resolution = resolution;   // rec, count and keys are not read by the bodies used; the
+                                                           // pyramid sets a level's resolution on the device
     L->d = NdtDyn{};
     L->d.capacity = (int)n;                                // room for every point's own cell: nothing is ever dropped
     L->d.keys = (uint64_t *)keys, L->d.bcnt = (int *)bcnt, L->d.lead = (int *)lead, L->d.cstart = (int *)cstart;
     L->d.state = (int *)state;
+    L->w.n = (int)n, L->w.hs = (int)hs;
     L->info = (int *)info;
     L->ff = shkeys, L->ff_bytes = ff_end;
     L->sf = shfirst, L->sf_bytes = sf_end - ff_end;
@@ -55,7 +62,7 @@ inline size_t ndt_src_layout(int64_t cap, double resolution, char *base, NdtSrcL
 
 int64_t sps_ndt_source_scratch(int64_t cap) {
   if (cap < 0 || cap > SPS_NDT_UPDATE_MAX_POINTS) return -1;
-  return (int64_t)ndt_src_layout(cap, 1.0, nullptr, nullptr);
+  return (int64_t)ndt_src_layout(cap, 1, 1.0, nullptr, nullptr);
 }
 
 int sps_ndt_source_build(sps_ctx *c, const double *pts_dev, const int32_t *n_dev, int64_t cap, double source_resolution,
@@ -71,7 +78,7 @@ int sps_ndt_source_build(sps_ctx *c, const double *pts_dev, const int32_t *n_dev
   HIP_TRY(hipSetDevice(c->device));
   hipStream_t st = (hipStream_t)stream;
   NdtSrcLayout L{};
-  ndt_src_layout(cap, source_resolution, (char *)scratch_dev, &L);
+  ndt_src_layout(cap, 1, source_resolution, (char *)scratch_dev, &L);
   LocPose I{};
   I.m[0] = I.m[5] = I.m[10] = I.m[15] = 1.0;
   const int nbp = (int)((cap + 255) / 256 > 0 ? (cap + 255) / 256 : 1);

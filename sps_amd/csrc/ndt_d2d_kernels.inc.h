@@ -8,6 +8,7 @@
 //                          founded, cell id = rank of its lowest point, and k_ndt_upd_stats leaves n, mean and S per cell
 //                          in bstat, cells in that order, points in ascending index
 //   k_ndt_src_records      (source build, 7)  one thread per cell: ndt_floored_eigen, covariance, flag -> one 80-byte record
+//                          (its body is ndt_src_records_body, which ndt_d2d_pyramid_kernels.inc.h runs once per level)
 //   k_ndt_d2d_assoc        (launch A of an iteration)  q = R mu + t, Cw = R C R^T, the records of q's cell and its face
 //                          neighbours, per cell B = inv3(inv3(icov) + Cw) and the normal-equation terms with B
 //                          (its body is ndt_d2d_assoc_body, which ndt_d2d_batch_kernels.inc.h runs once per hypothesis)
@@ -52,10 +53,11 @@ __global__ __launch_bounds__(64) void k_ndt_src_stats(const int *__restrict__ n_
 
 // 7: one thread per cell t (bstat row t: n, mean, S).  The covariance is reassembled from the floored eigenvalues, entry
 // (i, j) = ((v_i0 v_j0) l0 + (v_i1 v_j1) l1) + (v_i2 v_j2) l2.  n_src[0] = cells (thread 0), n_src[1] counts the valid ones
-// (zero on entry: the host's memset).
-__global__ __launch_bounds__(256) void k_ndt_src_records(const int *__restrict__ n_dev, int cap, int min_points, double eig_ratio,
-                                                          NdtUpdScratch s, double *__restrict__ src, int *__restrict__ src_count,
-                                                          int *__restrict__ n_src) {
+// (zero on entry: the host's memset).  The body indexes by blockIdx.x only: k_ndt_pyr_src_records
+// (ndt_d2d_pyramid_kernels.inc.h) runs it once per level of a pyramid of sources.
+__device__ inline void ndt_src_records_body(const int *__restrict__ n_dev, int cap, int min_points, double eig_ratio,
+                                            const NdtUpdScratch &s, double *__restrict__ src, int *__restrict__ src_count,
+                                            int *__restrict__ n_src) {
   const int nt = min(max(*s.n_touched, 0), min(cap, max(*n_dev, 0)));
   const int t = blockIdx.x * 256 + threadIdx.x;
   if (t == 0) n_src[0] = nt;
@@ -86,6 +88,12 @@ __global__ __launch_bounds__(256) void k_ndt_src_records(const int *__restrict__
   o[9] = valid ? 1.0 : 0.0;
   if (src_count) src_count[t] = n;
   if (valid) atomicAdd(&n_src[1], 1);
+}
+
+__global__ __launch_bounds__(256) void k_ndt_src_records(const int *__restrict__ n_dev, int cap, int min_points, double eig_ratio,
+                                                          NdtUpdScratch s, double *__restrict__ src, int *__restrict__ src_count,
+                                                          int *__restrict__ n_src) {
+  ndt_src_records_body(n_dev, cap, min_points, eig_ratio, s, src, src_count, n_src);
 }
 
 // ---- alignment -------------------------------------------------------------------------------------------------------

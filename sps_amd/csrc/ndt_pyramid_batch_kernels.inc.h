@@ -87,7 +87,7 @@ __global__ __launch_bounds__(256) void k_ndt_pyr_solve_batch(const double *__res
     state[0] = 1;
     return;
   }
-  ndt_pyr_handoff(l, n_levels, caps, vn < tol_t && th < tol_r, status, state);
+  ndt_pyr_handoff(l, ndt_pyr_next(l, n_levels), caps, vn < tol_t && th < tol_r, status, state);
 }
 
 #pragma clang fp contract(fast)

@@ -74,29 +74,52 @@ __global__ __launch_bounds__(256) void k_ndt_pyr_assoc(const double *__restrict_
   ndt_assoc_body(pts, n_dev, cap, d.m, d.gs, neighbours, T, partial, lds);
 }
 
-// The handoff rule, by the one thread that made a step at level l (k_ndt_pyr_solve below; k_ndt_pyr_solve_batch in
+// The handoff rule, by the one thread that made a step at level l (ndt_pyr_solve_body below; k_ndt_pyr_solve_batch in
 // ndt_pyramid_batch_kernels.inc.h runs it once per hypothesis): that level's count of used slots goes up; a converged step
-// ends the call with status 0 on the last level and hands the pose to level l + 1 otherwise; a step that is not converged
-// does the same once the level has used its cap, except that the status stays 1.  state: the call's (the hypothesis') words.
-__device__ inline void ndt_pyr_handoff(int l, int n_levels, NdtPyrCaps caps, bool converged, int *__restrict__ status,
+// ends the call with status 0 on the last level and hands the pose to level `next` otherwise; a step that is not converged
+// does the same once the level has used its cap, except that the status stays 1.  next: the level that follows l, < 0
+// where l is the last (ndt_pyr_next: l + 1 of n_levels; the d2d pyramid of ndt_d2d_pyramid_kernels.inc.h skips levels).
+// state: the call's (the hypothesis') words.
+__device__ inline int ndt_pyr_next(int l, int n_levels) { return l == n_levels - 1 ? -1 : l + 1; }
+
+__device__ inline void ndt_pyr_handoff(int l, int next, NdtPyrCaps caps, bool converged, int *__restrict__ status,
                                        int *__restrict__ state) {
   const int used = state[2 + l] + 1;
   state[2 + l] = used;
   const int cap_l = l == 0 ? caps.v[0] : (l == 1 ? caps.v[1] : (l == 2 ? caps.v[2] : caps.v[3]));
-  const bool last = l == n_levels - 1;
+  const bool last = next < 0;
   if (converged) {
     if (last) {
       status[0] = 0;
       state[0] = 1;
     } else {
-      state[1] = l + 1;
+      state[1] = next;
     }
   } else if (used >= cap_l) {
     if (last)
       state[0] = 1;
     else
-      state[1] = l + 1;
+      state[1] = next;
   }
+}
+
+// The step of launch B, by a workgroup of 256 whose call is live: the n rows' partial sums (loc_sum_rows), then thread 0
+// alone: loc_solve_step at level l and the handoff to `next`.  k_ndt_pyr_solve below and k_ndt_d2d_pyr_solve
+// (ndt_d2d_pyramid_kernels.inc.h) differ in where n, l and next come from.
+__device__ inline void ndt_pyr_solve_body(const double *__restrict__ partial, int n, int slot, int l, int next, NdtPyrCaps caps,
+                                          int min_corr, double tol_t, double tol_r, const LocPose &T_init, double *__restrict__ T,
+                                          int *__restrict__ status, int *__restrict__ state, double *__restrict__ trace,
+                                          double *__restrict__ normal, int *__restrict__ level, double (*seg)[32], double *tot) {
+  loc_sum_rows(partial, (n + LOC_PTS - 1) / LOC_PTS, threadIdx.x, seg, tot);
+  if (threadIdx.x != 0) return;
+  level[slot] = l;
+  status[3] = l;
+  double vn, th;
+  if (loc_solve_step(tot, slot, min_corr, T_init.m, T, status, trace, normal, vn, th) >= 0) {
+    state[0] = 1;
+    return;
+  }
+  ndt_pyr_handoff(l, next, caps, vn < tol_t && th < tol_r, status, state);
 }
 
 // Launch B, one workgroup of 256.  After a step at level l that level's count of used slots goes up; a converged step
@@ -113,17 +136,9 @@ __global__ __launch_bounds__(256) void k_ndt_pyr_solve(const double *__restrict_
   __shared__ double tot[32];
   if (state[0]) return;
   const int n = min(cap, max(*n_dev, 0));
-  loc_sum_rows(partial, (n + LOC_PTS - 1) / LOC_PTS, threadIdx.x, seg, tot);
-  if (threadIdx.x != 0) return;
   const int l = min(max(state[1], 0), n_levels - 1);
-  level[slot] = l;
-  status[3] = l;
-  double vn, th;
-  if (loc_solve_step(tot, slot, min_corr, T_init.m, T, status, trace, normal, vn, th) >= 0) {
-    state[0] = 1;
-    return;
-  }
-  ndt_pyr_handoff(l, n_levels, caps, vn < tol_t && th < tol_r, status, state);
+  ndt_pyr_solve_body(partial, n, slot, l, ndt_pyr_next(l, n_levels), caps, min_corr, tol_t, tol_r, T_init, T, status, state, trace,
+                     normal, level, seg, tot);
 }
 
 #pragma clang fp contract(fast)

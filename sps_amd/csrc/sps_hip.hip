@@ -159,6 +159,7 @@ int fail(int code, const char *fmt, ...) {
 #include "ndt_carve_kernels.inc.h"
 #include "ndt_pyramid_kernels.inc.h"
 #include "ndt_online_kernels.inc.h"
+#include "ndt_d2d_pyramid_kernels.inc.h"
 #include "ndt_pyramid_batch_kernels.inc.h"
 #include "ukf_kernels.inc.h"
 
@@ -2243,6 +2244,7 @@ int sps_get_feature(sps_ctx *c, const char *name, float *out_dev, int64_t *rows,
 #include "ndt_d2d_host.inc.h"
 #include "ndt_d2d_batch_host.inc.h"
 #include "ndt_pyramid_host.inc.h"
+#include "ndt_d2d_pyramid_host.inc.h"
 #include "ndt_pyramid_batch_host.inc.h"
 #include "ukf_host.inc.h"
 

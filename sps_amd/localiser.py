@@ -198,16 +198,17 @@ def _offsets(parts, tail=()):
     return o
 
 
-def _pose_layout(K, with_normal, pyramid=False, L=None, integrate=False, carve=False, match=False):
+def _pose_layout(K, with_normal, pyramid=False, L=None, integrate=False, carve=False, match=False, sources=0):
     """offsets (in doubles) of a frame's one float64 buffer: T_out[16] | status int32[4] | n_points int32 (+ n_sources int32
-    in the pad) | trace[K][4] | normal[K][28] | level int32[K] (+ pad) with a pyramid | info int32[4] of the update | info
+    in the pad) | trace[K][4] | normal[K][28] | valid sources int32[sources] (+ pad), one per level of a pyramid of source
+    cells | level int32[K] (+ pad) with a pyramid | info int32[4] of the update | info
     int32[4] of the carve (an online pyramid of L levels: int32[L][4] each) | the MATCH_WORDS words of the scan-matching
     status, last, with ``match``.  ``hands_on``: the offsets in bytes of the pose the frame hands on and of the int32 that
     gates what follows it on the device: ``T_out`` and the status or, with ``match``, the status' verdict"""
     w = 2 if L is None else 2 * L                                    # doubles of one call's info words
     o = _offsets((("T_out", 16), ("status", 2), ("n_points", 1), ("trace", 4 * K), ("normal", 28 * K if with_normal else 0)),
-                 (("levels", (K + 1) // 2 if pyramid else 0), ("update", w if integrate else 0), ("carve", w if carve else 0),
-                  ("match", MATCH_WORDS if match else 0)))
+                 (("sources", (sources + 1) // 2), ("levels", (K + 1) // 2 if pyramid else 0), ("update", w if integrate else 0),
+                  ("carve", w if carve else 0), ("match", MATCH_WORDS if match else 0)))
     o["hands_on"] = (o["T_out"] * 8, (o["match"] + 4) * 8 if match else o["status"] * 8)
     return o
 
@@ -279,8 +280,9 @@ class PendingPose(_Pending):
     _at = 0
 
     def __init__(self, iters, with_normal, host, event, keep, pyramid=False, n_levels=None, integrate=False, carve=False,
-                 match=False):
+                 match=False, sources=0):
         super().__init__(host, event, keep)
+        self._sources = sources                                      # levels of a pyramid of source cells (0: none)
         self._iters, self._with_normal, self._pyramid = iters, with_normal, pyramid
         self._n_levels = n_levels                                    # an online pyramid: info words per level, tuples out
         self._integrate, self._carve = integrate, carve              # the frame's buffer has their info words
@@ -288,13 +290,15 @@ class PendingPose(_Pending):
 
     def _layout(self):
         return _pose_layout(self._iters, self._with_normal, self._pyramid, self._n_levels, self._integrate, self._carve,
-                            self._match)
+                            self._match, self._sources)
 
     def result(self) -> PoseResult:
         h, o = self._wait(), self._layout()
         K, L = self._iters, self._n_levels
-        code, it, n_corr, _ = (int(x) for x in h[o["status"]:o["n_points"]].view(np.int32))
+        code, it, n_corr, last_level = (int(x) for x in h[o["status"]:o["n_points"]].view(np.int32))
         n_points, n_sources = (int(x) for x in h[o["n_points"]:o["trace"]].view(np.int32))
+        if self._sources:                                            # the level of the last live slot tells whose count
+            n_sources = int(h[o["sources"]:o["levels"]].view(np.int32)[min(max(last_level, 0), self._sources - 1)])
         trace = h[o["trace"]:o["normal"]].reshape(K, 4)[:it].copy()
         normal = h[o["normal"]:o["size"]].reshape(K, 28)[:it].copy() if self._with_normal else None
         rmse = math.sqrt(trace[-1, 1] / n_corr) if it and n_corr > 0 else float("nan")
@@ -585,7 +589,7 @@ class ScanToMapLocaliser:
     is the localiser's own grid, so ``max_distance`` may not exceed the localiser's."""
 
     # what only an NDTLocaliser can have: no pyramid, no online map, the scan's points registered as they are
-    resolutions = level_iterations = level_capacities = cell_capacity = None
+    resolutions = level_iterations = level_capacities = cell_capacity = source_resolutions = None
     source = "points"
     _match_opts = None                                               # no match_status: nothing is built, nothing changes
 
@@ -734,8 +738,9 @@ class ScanToMapLocaliser:
         K = self.iterations if iterations is None else int(iterations)
         pyramid = self.resolutions is not None
         match = self._match_opts is not None
+        n_src_levels = 0 if self.source_resolutions is None else len(self.source_resolutions)
         shape = (K, with_normal, pyramid, None if self.level_capacities is None else len(self.level_capacities), integrate, carve,
-                 match)
+                 match, n_src_levels)
         o = _pose_layout(*shape)
 
         def work(out, n_ptr, _, s):
@@ -745,7 +750,10 @@ class ScanToMapLocaliser:
             kw = dict(level_ptr=base + o["levels"] * 8 if K else None) if pyramid else {}
             self._align(n_ptr, T, K, T_ptr, status_ptr, base + o["trace"] * 8 if K else None,
                         base + o["normal"] * 8 if with_normal and K else None, s, **kw)
-            if self.source == "cells":                               # the valid source cells into the pad behind n_points
+            if n_src_levels:                                         # every level's valid source cells: the host picks
+                at = 2 * o["sources"]
+                out.view(torch.int32)[at:at + n_src_levels].copy_(self._n_src_lv[:, 1])
+            elif self.source == "cells":                             # the valid source cells into the pad behind n_points
                 at = 2 * o["n_points"] + 1
                 out.view(torch.int32)[at:at + 1].copy_(self._n_src[1:2])
             if match:                                                # its verdict is the gate of what follows
@@ -869,6 +877,18 @@ class NDTLocaliser(ScanToMapLocaliser):
     scan's cells from poses on the device.  ``capacity`` is then at most 65536.  ``source="points"`` (the
     default) is the point-to-distribution path.
 
+    ``source_resolutions`` (with ``source="cells"`` and ``resolutions``, one finite edge > 0 per level, in no way tied to the
+    map's; not with ``source_resolution``) lifts the refusal of ``resolutions``: ``submit`` / ``submit_filtered`` /
+    ``__call__`` thin the scan once, build its cells at every level's edge in one set of launches and register them coarse
+    to fine against the pyramid in one call.  ``source_min_points`` is then an int for all levels or one
+    per level.  The handoff is the pyramid's with one more rule: a level whose valid sources are fewer than
+    ``min_correspondences`` is skipped, and the last level that qualifies ends the call as the last level does (level 0 is
+    always entered).  ``levels`` is as for points, ``n_sources`` is the valid-cell count of the level of the last live slot,
+    and ``source_cells(rows, count, level)`` shows a level.  ``level_capacities`` is allowed: the map still takes the thinned
+    points.  The calls with ``d2d=True`` keep working on the single map, with sources at ``resolution`` (valid from
+    ``source_min_points`` where that is one int, else from ``min_points_per_cell``); ``d2d=True`` with
+    ``coarse_to_fine=True`` and the global search stay refused.
+
     ``global_grid`` (None: nothing is built; a dict with any of ``resolution`` (0.5), ``map_z`` = (lo, hi) (everything) and
     ``levels`` (3, at most 7)): the map points of that height slice become an occupancy grid of that edge with ``levels``
     pooled levels on the device, and ``global_search`` / ``localise_global`` find the pose with no start pose.
@@ -885,11 +905,14 @@ class NDTLocaliser(ScanToMapLocaliser):
                  min_correspondences: int = 50, min_points_per_cell: int = 6, outlier_ratio: float = 0.55,
                  eig_ratio: float = 0.01, tol_t: float = 1e-4, tol_r: float = 1e-5, device="cuda", capacity: int = 1 << 16,
                  cell_capacity: int = None, resolutions=None, level_iterations=None, level_capacities=None,
-                 source: str = "points", source_resolution: float = None, source_min_points: int = None,
-                 global_grid: dict = None, match_status: dict = None):
+                 source: str = "points", source_resolution: float = None, source_min_points=None,
+                 global_grid: dict = None, match_status: dict = None, source_resolutions=None):
         self._match_opts = _checked_match(match_status)
+        self.source_resolutions, self.source_level_min_points, source_min_points = self._checked_source_pyramid(
+            source, source_resolution, source_resolutions, source_min_points, min_points_per_cell, resolutions)
         self.source, self.source_resolution, self.source_min_points = self._checked_source(
-            source, source_resolution, source_min_points, resolution, min_points_per_cell, resolutions, capacity)
+            source, source_resolution, source_min_points, resolution, min_points_per_cell,
+            None if self.source_resolutions is not None else resolutions, capacity)
         if level_capacities is not None and cell_capacity is not None:
             raise ValueError("level_capacities and cell_capacity exclude each other: the single map beside an online pyramid is static")
         self.resolutions, self.level_iterations = self._checked_pyramid(resolutions, level_iterations, cell_capacity)
@@ -927,6 +950,15 @@ class NDTLocaliser(ScanToMapLocaliser):
                                                 device=self.device)
                 self._d2d_batch_scratch, self._d2d_batch_hyp = None, 0   # those of the d2d=True calls, grown on demand
                 self._d2d_score_scratch, self._d2d_score_poses = None, 0
+            if self.source_resolutions is not None:                  # the same per level of the pyramid of source cells
+                L = len(self.source_resolutions)
+                self._src_lv = torch.empty((L, self.capacity, _native.NDT_SRC_REC), dtype=torch.float64, device=self.device)
+                self._src_count_lv = torch.empty((L, self.capacity), dtype=torch.int32, device=self.device)
+                self._n_src_lv = torch.zeros((L, 2), dtype=torch.int32, device=self.device)
+                self._src_lv_scratch = torch.empty(_native.lib.sps_ndt_pyramid_source_scratch(self.capacity, L),
+                                                   dtype=torch.uint8, device=self.device)
+                self._d2d_pyr_scratch = torch.empty(_native.lib.sps_ndt_pyramid_align_d2d_scratch(self.capacity),
+                                                    dtype=torch.uint8, device=self.device)
 
     def _build_map(self, xyz):
         """the single map at ``resolution``, static or online, and the pyramid's levels beside it"""
@@ -977,6 +1009,34 @@ class NDTLocaliser(ScanToMapLocaliser):
                                         self.n_map, d, d, self.stream.cuda_stream)
         else:
             self.ctx.radius_grid_upload(None, None, None, None, 0, 0, d, d, self.stream.cuda_stream)
+
+    @staticmethod
+    def _checked_source_pyramid(source, source_resolution, source_resolutions, source_min_points, min_points_per_cell,
+                                resolutions):
+        """(source_resolutions, the levels' source_min_points, the single map's source_min_points) before any device work:
+        the first two are tuples, one entry per level, or None without ``source_resolutions``; the third is what
+        ``_checked_source`` takes: ``source_min_points`` where that is not a sequence, else None (its default)"""
+        seq = source_min_points is not None and np.ndim(source_min_points) != 0
+        if source_resolutions is None:
+            if seq:
+                raise ValueError("a source_min_points sequence needs source_resolutions")
+            return None, None, source_min_points
+        if source != "cells" or resolutions is None:
+            raise ValueError("source_resolutions needs source='cells' and resolutions: one source resolution per level")
+        if source_resolution is not None:
+            raise ValueError("source_resolutions and source_resolution exclude each other")
+        try:
+            n_levels = len(tuple(resolutions))
+            res = tuple(float(r) for r in source_resolutions)
+            mps = tuple(int(v) for v in source_min_points) if seq else \
+                (int(min_points_per_cell if source_min_points is None else source_min_points),) * len(res)
+        except TypeError:
+            raise ValueError("source_resolutions must be a sequence of numbers") from None
+        if len(res) != n_levels or not all(math.isfinite(r) and r > 0 for r in res):
+            raise ValueError("source_resolutions needs one finite entry > 0 per level of resolutions")
+        if len(mps) != n_levels or min(mps) < 0:
+            raise ValueError("a source_min_points sequence needs one entry >= 0 per level of resolutions")
+        return res, mps, None if seq else source_min_points
 
     @staticmethod
     def _checked_source(source, source_resolution, source_min_points, resolution, min_points_per_cell, resolutions, capacity):
@@ -1155,7 +1215,8 @@ class NDTLocaliser(ScanToMapLocaliser):
         if self.source != "cells":
             raise ValueError(f"{what}: d2d=True needs an NDTLocaliser with source='cells'")
         if coarse_to_fine:
-            raise ValueError(f"{what}: d2d=True and coarse_to_fine exclude each other: the pyramid registers points")
+            raise ValueError(f"{what}: d2d=True and coarse_to_fine exclude each other: the pyramid registers points here "
+                             "(source cells go coarse to fine through submit, with source_resolutions)")
         return True
 
     @staticmethod
@@ -1202,6 +1263,13 @@ class NDTLocaliser(ScanToMapLocaliser):
         return caps
 
     def _align(self, n_ptr, T, K, T_out_ptr, status_ptr, trace_ptr, normal_ptr, s, level_ptr=None):
+        if self.source_resolutions is not None:                      # the scan's cells at every level against the pyramid
+            caps = self.level_iterations or (max(K, 1),) * len(self.resolutions)
+            self._build_level_sources(n_ptr, s)
+            self.ctx.ndt_pyramid_align_d2d(self._src_lv.data_ptr(), self._n_src_lv.data_ptr(), self.capacity, T, K, caps,
+                                           self.neighbours, self.min_correspondences, self.tol_t, self.tol_r, T_out_ptr,
+                                           status_ptr, trace_ptr, normal_ptr, level_ptr, self._d2d_pyr_scratch.data_ptr(), s)
+            return
         if self.resolutions is not None:
             caps = self.level_iterations or (max(K, 1),) * len(self.resolutions)
             self.ctx.ndt_pyramid_align(self._pts.data_ptr(), n_ptr, self.capacity, T, K, caps, self.neighbours,
@@ -1224,13 +1292,23 @@ class NDTLocaliser(ScanToMapLocaliser):
                                   self.eig_ratio, self._src.data_ptr(), self._src_count.data_ptr(), self._n_src.data_ptr(),
                                   self._src_scratch.data_ptr(), s)
 
+    def _build_level_sources(self, n_ptr, s):
+        """the same at every level of ``source_resolutions`` into self._src_lv, in one set of launches"""
+        self.ctx.ndt_pyramid_source_build(self._pts.data_ptr(), n_ptr, self.capacity, self.source_resolutions,
+                                          self.source_level_min_points, self.eig_ratio, self._src_lv.data_ptr(),
+                                          self._src_count_lv.data_ptr(), self._n_src_lv.data_ptr(),
+                                          self._src_lv_scratch.data_ptr(), s)
+
     @torch.no_grad()
-    def source_cells(self, rows, count):
+    def source_cells(self, rows, count, level: int = 0):
         """Debug (``source="cells"``): the thinning plus the source build of ``submit`` -> dict(mean [C, 3], cov [C, 6] as
         (xx, xy, xz, yy, yz, zz), count int32 [C], valid bool [C]) in the order of the cells' lowest points, as numpy arrays.
-        Synchronises."""
+        With ``source_resolutions``: the cells of level ``level`` of the pyramid of source cells.  Synchronises."""
         if self.source != "cells":
             raise ValueError("source_cells needs an NDTLocaliser with source='cells'")
+        levels = self.source_resolutions
+        if not 0 <= int(level) < (1 if levels is None else len(levels)):
+            raise ValueError(f"level must be in [0, {1 if levels is None else len(levels)})")
         rows = self._checked_rows(rows)
         n_max = rows.shape[0]
         with torch.cuda.device(self.device):
@@ -1238,10 +1316,15 @@ class NDTLocaliser(ScanToMapLocaliser):
             n_dev = self._count_on_device(count, n_max)
             n_pts = torch.zeros(2, dtype=torch.int32, device=self.device)
             self._thin(rows, n_dev, n_max, n_pts.data_ptr(), st.cuda_stream)
-            self._build_sources(n_pts.data_ptr(), st.cuda_stream)
-            C = int(self._n_src.cpu()[0])                            # synchronises
-            rec = self._src[:C].cpu().numpy()
-            cnt = self._src_count[:C].cpu().numpy()
+            if levels is None:
+                self._build_sources(n_pts.data_ptr(), st.cuda_stream)
+                n_src, src, src_count = self._n_src, self._src, self._src_count
+            else:
+                self._build_level_sources(n_pts.data_ptr(), st.cuda_stream)
+                n_src, src, src_count = (a[int(level)] for a in (self._n_src_lv, self._src_lv, self._src_count_lv))
+            C = int(n_src.cpu()[0])                                  # synchronises
+            rec = src[:C].cpu().numpy()
+            cnt = src_count[:C].cpu().numpy()
         return dict(mean=rec[:, 0:3].copy(), cov=rec[:, 3:9].copy(), count=cnt, valid=rec[:, 9] != 0.0)
 
     # the online map or, with level_capacities, every level of the online pyramid (then info_ptr: int32[L][4])

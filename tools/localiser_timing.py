@@ -12,7 +12,7 @@ synthetic.build_map() map, max_distance 1 m, leaf 0.2 m):
     python tools/localiser_timing.py [--frames 200] [--warmup 20] [--cpu-frames 1] [--one-frame] [--cpu-only]
                                      [--localiser {icp,ndt}] [--hypotheses K] [--search P] [--update-map] [--carve]
                                      [--source {points,cells}] [--source-resolution R] [--source-min-points N] [--global]
-                                     [--d2d]
+                                     [--d2d] [--source-resolutions S0,S1,...] [--start-behind M]
 
 ``--localiser ndt`` times sps_amd.localiser.NDTLocaliser (1 m cells, 7 neighbours) on the same frames and from the same
 start, prints the ICP's per-frame figures of the same session beside it and the build time of both maps; the
@@ -49,6 +49,11 @@ without an estimator, with one on the device path and with one on the host path,
 ``--localiser ndt --source cells`` times distribution-to-distribution registration (NDTLocaliser(..., source="cells")):
 per frame the hipEvent time around submit(), the iterations, the scan's valid source cells and the error against the true
 pose, beside the point path on the same frames, the two alternating frame by frame in one run; then the loop with each.
+
+``--localiser ndt --source cells --resolutions 2,1,0.5 --source-resolutions 2,1,0.5`` times the coarse-to-fine registration
+of the scan's cells (NDTLocaliser(..., source_resolutions=...)) beside the single cells localiser and the
+point pyramid, frame by frame alternating in one run, with the live slots per level, and the source build of all levels
+in one call against one single build per level; ``--start-behind 0.5`` starts that far behind the usual start pose.
 
 ``--localiser ndt --source cells --d2d`` with any of ``--search P``, ``--hypotheses K``, ``--estimator`` times the
 distribution-to-distribution calls that take several poses beside the point path's on the same frames, the two
@@ -223,7 +228,13 @@ def main():
     ap.add_argument("--source", choices=("points", "cells"), default="points", help="with --localiser ndt: cells times "
                     "distribution-to-distribution registration beside the point path")
     ap.add_argument("--source-resolution", type=float, default=None, help="with --source cells: edge of the scan's cells")
-    ap.add_argument("--source-min-points", type=int, default=None, help="with --source cells: points a cell of the scan needs")
+    ap.add_argument("--source-min-points", type=str, default=None, help="with --source cells: points a cell of the scan needs; "
+                    "with --source-resolutions also N0,N1,..., one per level")
+    ap.add_argument("--source-resolutions", type=str, default=None, help="with --source cells --resolutions R0,R1,...: S0,S1,... "
+                    "time the coarse-to-fine registration of the scan's cells beside the single cells localiser and the point "
+                    "pyramid")
+    ap.add_argument("--start-behind", type=float, default=0.0, help="with --source-resolutions: start this many metres behind "
+                    "the usual start pose, along x")
     ap.add_argument("--d2d", action="store_true", help="with --source cells and any of --search, --hypotheses, --estimator: time "
                     "the d2d=True calls beside the point path's")
     ap.add_argument("--match-status", dest="match_status", action="store_true", help="time submit without and with the "
@@ -237,8 +248,22 @@ def main():
     if a.d2d and (a.source != "cells" or a.localiser != "ndt" or not (a.hypotheses or a.search or a.estimator) or a.update_map
                   or a.carve or a.resolutions or a.global_search or a.match_status):
         ap.error("--d2d needs --localiser ndt --source cells, any of --search, --hypotheses, --estimator, and no other mode")
+    try:
+        if a.source_min_points is not None:
+            mps = tuple(int(v) for v in a.source_min_points.split(","))
+            a.source_min_points = mps[0] if len(mps) == 1 else mps
+        if a.source_resolutions is not None:
+            a.source_resolutions = tuple(float(v) for v in a.source_resolutions.split(","))
+    except ValueError:
+        ap.error("--source-min-points takes integers and --source-resolutions numbers, separated by commas")
+    if a.source_resolutions is not None and (a.localiser != "ndt" or a.source != "cells" or not a.resolutions or a.d2d or a.c2f
+                                             or a.hypotheses or a.search or a.update_map or a.carve or a.estimator
+                                             or a.source_resolution is not None):
+        ap.error("--source-resolutions needs --localiser ndt --source cells --resolutions and none of the other modes")
+    if isinstance(a.source_min_points, tuple) and a.source_resolutions is None:
+        ap.error("a --source-min-points list needs --source-resolutions")
     if a.source == "cells" and not a.d2d and (a.localiser != "ndt" or a.hypotheses or a.search or a.update_map or a.carve
-                                              or a.resolutions or a.estimator):
+                                              or (a.resolutions and a.source_resolutions is None) or a.estimator):
         ap.error("--source cells needs --localiser ndt and none of the other modes (--d2d: with --search, --hypotheses, --estimator)")
     if (a.source_resolution is not None or a.source_min_points is not None) and a.source != "cells":
         ap.error("--source-resolution and --source-min-points need --source cells")
@@ -273,6 +298,8 @@ def main():
         return ndt_estimator_main(a, scans, dscans, mp, T_init)
     if a.c2f:
         return ndt_c2f_main(a, scans, dscans, mp, T_init)
+    if a.source_resolutions is not None:
+        return ndt_d2d_pyramid_main(a, scans, dscans, mp, T_init)
     if a.localiser == "ndt" and a.resolutions and (a.update_map or a.carve):
         return ndt_online_pyramid_main(a, dscans, mp, T_init)
     if a.localiser == "ndt" and a.update_map:
@@ -562,6 +589,94 @@ def ndt_d2d_main(a, scans, dscans, mp, T_init):
         out[name]["loop_sps_cvm_ms"] = round(float(np.median(t_loop)) * 1e3, 4)
         out[name]["loop_flagged_frames"] = int(flagged)
         print(f"LocalisationLoop(sps_cvm, ndt {name}) {out[name]['loop_sps_cvm_ms']:.3f} ms per frame ({flagged} flagged)", flush=True)
+    print(json.dumps(out))
+
+
+def ndt_d2d_pyramid_main(a, scans, dscans, mp, T_init):
+    """--source cells --resolutions --source-resolutions: the coarse-to-fine registration of the scan's cells
+    beside the single cells localiser and the point pyramid on the same frames, alternating frame by frame within one run.
+    Per frame: hipEvent time around submit(), slots, live slots per level, valid source cells, the error against the true
+    pose.  Then the source build of all levels in one call against one single build per level, alternating too."""
+    map64 = mp[:, :3].astype(np.float64)
+    res, sres = tuple(float(v) for v in a.resolutions.split(",")), a.source_resolutions
+    caps = tuple(int(v) for v in a.level_iterations.split(",")) if a.level_iterations else None
+    pkw = dict(resolutions=res, iterations=a.iterations, level_iterations=caps)
+    skw = dict(source="cells", source_min_points=a.source_min_points)
+    locs = {"cells_pyramid": NDTLocaliser(map64, source_resolutions=sres, **skw, **pkw),
+            "cells": NDTLocaliser(map64, source="cells", source_min_points=a.source_min_points
+                                  if not isinstance(a.source_min_points, tuple) else None),
+            "points_pyramid": NDTLocaliser(map64, **pkw)}
+    T0 = LR.perturbation(-a.start_behind, 0.0, 0.0, 0.0) @ T_init
+    if a.one_frame:
+        loc = locs["cells_pyramid"]
+        for k in range(a.warmup):
+            loc.submit(dscans[k % len(dscans)], len(dscans[k % len(dscans)]), T0).result()
+        torch.cuda.synchronize()
+        s = dscans[a.warmup % len(dscans)]
+        r = loc.submit(s, len(s), T0).result()
+        print(json.dumps({"one_frame": True, "localiser": "ndt", "source": "cells", "resolutions": res, "status": r.status,
+                          "iterations": r.iterations, "n_points": r.n_points, "n_sources": r.n_sources, "n_corr": r.n_corr}))
+        return
+    st = torch.cuda.current_stream()
+    L = len(res)
+    rec = {name: [] for name in locs}
+    for k in range(a.warmup + a.frames):
+        s = dscans[k % len(dscans)]
+        for name, loc in locs.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(st)
+            pend = loc.submit(s, len(s), T0)
+            e1.record(st)
+            r = pend.result()
+            e1.synchronize()
+            if k >= a.warmup:
+                per = [int((r.levels == l).sum()) for l in range(L)] if r.levels is not None else [r.iterations]
+                rec[name].append((e0.elapsed_time(e1), r.iterations, r.n_points, r.n_sources, r.n_corr, r.status,
+                                  LR.pose_difference(r.pose, np.eye(4))[0], per))
+    budget = locs["cells_pyramid"].iterations
+    out = {"n_scan": int(np.mean([len(s) for s in scans])), "n_map": len(mp), "frames": a.frames, "warmup": a.warmup,
+           "resolutions": res, "source_resolutions": sres, "source_min_points": locs["cells_pyramid"].source_level_min_points,
+           "budget": budget, "level_iterations": caps, "start_behind_m": a.start_behind}
+    for name, rows in rec.items():
+        ms, iters, npts, nsrc, ncorr, status, errs, per = (list(c) for c in zip(*rows))
+        med, it = float(np.median(ms)), float(np.median(iters))
+        out[name] = {"ms": {"median": round(med, 4), "min": round(min(ms), 4), "max": round(max(ms), 4)},
+                     "slots": {"median": it, "min": min(iters), "max": max(iters)},
+                     "live_slots_per_level": [float(v) for v in np.median(np.array(per), axis=0)],
+                     "idle_slots": float(np.median([(budget if name != "cells" else locs[name].iterations) - i for i in iters])),
+                     "points_after_thinning": int(np.mean(npts)), "n_sources": int(np.median(nsrc)),
+                     "n_corr": int(np.median(ncorr)), "status_not_converged": int(sum(v != 0 for v in status)),
+                     "max_error_m": round(max(errs), 5), "median_error_m": round(float(np.median(errs)), 5)}
+        print(f"{name}  median {med:.3f} ms (min {min(ms):.3f} max {max(ms):.3f}) per frame, slots median {it:.0f} "
+              f"(per level {out[name]['live_slots_per_level']}), {out[name]['n_sources']} sources, error median "
+              f"{out[name]['median_error_m']:.4f} m max {out[name]['max_error_m']:.4f} m", flush=True)
+    # the source build alone: all levels in one call against one single build per level
+    pyr = locs["cells_pyramid"]
+    singles = [NDTLocaliser(map64, source="cells", source_resolution=r, source_min_points=m)
+               for r, m in zip(pyr.source_resolutions, pyr.source_level_min_points)]
+    s = dscans[0]
+    n_pts = torch.zeros(2, dtype=torch.int32, device=pyr.device)
+    pyr._thin(s[:, :3].to(torch.float32).contiguous(), torch.full((1,), len(s), dtype=torch.int32, device=pyr.device), len(s),
+              n_pts.data_ptr(), st.cuda_stream)
+    for one in singles:
+        one._pts.copy_(pyr._pts)
+    t = {"one_call": [], "single_builds": []}
+    for k in range(a.warmup + a.frames):
+        for name in t:
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(st)
+            if name == "one_call":
+                pyr._build_level_sources(n_pts.data_ptr(), st.cuda_stream)
+            else:
+                for one in singles:
+                    one._build_sources(n_pts.data_ptr(), st.cuda_stream)
+            e1.record(st)
+            e1.synchronize()
+            if k >= a.warmup:
+                t[name].append(e0.elapsed_time(e1))
+    out["source_build_ms"] = {name: round(float(np.median(v)), 4) for name, v in t.items()}
+    print(f"source build: {L} levels in one call {out['source_build_ms']['one_call']:.4f} ms, {L} single builds "
+          f"{out['source_build_ms']['single_builds']:.4f} ms", flush=True)
     print(json.dumps(out))
 
 
