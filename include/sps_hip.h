@@ -355,6 +355,10 @@ int sps_profile_kernel(sps_ctx *ctx, int idx, char *name, int name_cap);
 int sps_level_counts(sps_ctx *ctx, int64_t counts_host[SPS_NUM_LEVELS]);
 /* Integer coordinates [V,5] (b,x,y,z,t) of level `level` (0 = tensor stride 1). */
 int sps_get_voxels(sps_ctx *ctx, int level, int32_t *coords_dev);
+/* Debug view of the block hash of level `level` after the last forward: the number of slots of the level's table, the
+ * number of 4x4x4 blocks, and (bslot_host non-null, room for `cap` entries) the slot each block held, by block rank
+ * (first-occurrence order; the voxel rows of sps_get_voxels are block-contiguous in that order).  Read-only. */
+int sps_get_block_slots(sps_ctx *ctx, int level, int64_t *n_slots, int64_t *n_blocks, int32_t *bslot_host, int64_t cap);
 /* inverse map point -> ts1 voxel row, int64 [n] (-1 for out-of-range rows). */
 int sps_get_inverse(sps_ctx *ctx, int64_t *inv_dev);
 /* parent row (level+1) of each voxel of `level` (0..3), int32 [V_level]. */

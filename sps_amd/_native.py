@@ -102,6 +102,7 @@ def _load() -> C.CDLL:
         "sps_forward_metrics_n": (i32, [vp, vp, i64, i64, vp, f32, f32, i32, vp, vp, vp]),
         "sps_level_counts": (i32, [vp, C.POINTER(i64)]),
         "sps_get_voxels": (i32, [vp, i32, vp]),
+        "sps_get_block_slots": (i32, [vp, i32, C.POINTER(i64), C.POINTER(i64), vp, i64]),
         "sps_get_inverse": (i32, [vp, vp]),
         "sps_get_parent": (i32, [vp, i32, vp]),
         "sps_get_map_pairs": (i32, [vp, i32, C.POINTER(i64)]),
@@ -213,7 +214,7 @@ EXPORTS = ["sps_last_error", "sps_version", "sps_ctx_create", "sps_ctx_destroy",
            "sps_submap_voxel", "sps_submap_voxel_ijk", "sps_transform_points", "sps_filter_prepare", "sps_forward_n",
            "sps_compact_stable", "sps_filter_finish", "sps_train_forward", "sps_train_backward", "sps_train_generation", "sps_train_wgrad_plan", "sps_train_backward_at", "sps_scan_mse", "sps_scan_mse_backward", "sps_radius_grid_upload", "sps_radius_count",
            "sps_radius_fill", "sps_radius_grid_attach", "sps_radius_item", "sps_forward_metrics_n", "sps_level_counts", "sps_get_voxels",
-           "sps_get_inverse", "sps_get_parent", "sps_get_map_pairs", "sps_get_tile_masks", "sps_get_nbr", "sps_get_kernel_map", "sps_get_rulebook_chunks", "sps_get_logits", "sps_get_feature",
+           "sps_get_block_slots", "sps_get_inverse", "sps_get_parent", "sps_get_map_pairs", "sps_get_tile_masks", "sps_get_nbr", "sps_get_kernel_map", "sps_get_rulebook_chunks", "sps_get_logits", "sps_get_feature",
            "sps_lts_num_tensors", "sps_lts_tensor_info", "sps_lts_numel", "sps_lts_lidar_info", "sps_lts_create",
            "sps_lts_destroy", "sps_lts_project", "sps_lts_forward", "sps_lts_check", "sps_lts_tap",
            "sps_forward_head_n", "sps_transform_rows", "sps_transform_points_n", "sps_radius_crop", "sps_label_filter",
@@ -741,6 +742,17 @@ class Context:
         out = (C.c_int64 * NUM_LEVELS)()
         check(lib.sps_level_counts(self.handle, out))
         return list(out)
+
+    def block_slots(self, level: int):
+        """(slots of the level's block hash, int32 numpy [blocks]: the slot each block of the last forward held, by block
+        rank) -- a debug view for the tests of the hash walk (include/sps_hip.h: sps_get_block_slots)"""
+        import numpy as np
+        ns, nb = C.c_int64(), C.c_int64()
+        check(lib.sps_get_block_slots(self.handle, level, C.byref(ns), C.byref(nb), None, 0))
+        out = np.zeros(nb.value, np.int32)
+        if nb.value:
+            check(lib.sps_get_block_slots(self.handle, level, C.byref(ns), C.byref(nb), out.ctypes.data, len(out)))
+        return ns.value, out
 
     def kernel_map(self, which: int, source: int = 0):
         """Dense int32 [K, V_out] table of a kernel map of the last forward (include/sps_hip.h: sps_get_kernel_map), on the

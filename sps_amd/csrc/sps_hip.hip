@@ -2028,6 +2028,20 @@ int sps_get_voxels(sps_ctx *c, int level, int32_t *coords_dev) {
   return SPS_OK;
 }
 
+int sps_get_block_slots(sps_ctx *c, int level, int64_t *n_slots, int64_t *n_blocks, int32_t *bslot_host, int64_t cap) {
+  if (!c || !n_slots || !n_blocks || level < 0 || level >= SPS_NUM_LEVELS || cap < 0) return fail(SPS_ERR_INVALID, "bad arguments");
+  HIP_TRY(hipSetDevice(c->device));
+  HIP_TRY(hipDeviceSynchronize());  // the forward may still be running on a non-blocking stream
+  int nb = 0;
+  if (c->cap > 0 && c->last_n > 0) HIP_TRY(hipMemcpy(&nb, c->counts + 8 + level, sizeof nb, hipMemcpyDeviceToHost));
+  *n_slots = c->cap > 0 ? c->hcapl[level] : 0;
+  *n_blocks = nb;
+  if (!bslot_host) return SPS_OK;
+  if (nb > cap) return fail(SPS_ERR_INVALID, "level %d has %d blocks, the buffer holds %lld", level, nb, (long long)cap);
+  if (nb > 0) HIP_TRY(hipMemcpy(bslot_host, c->lv[level].bslot, (size_t)nb * sizeof(int), hipMemcpyDeviceToHost));
+  return SPS_OK;
+}
+
 int sps_get_inverse(sps_ctx *c, int64_t *inv_dev) {
   if (!c || !inv_dev) return fail(SPS_ERR_INVALID, "null argument");
   HIP_TRY(hipSetDevice(c->device));

@@ -124,6 +124,13 @@ def _big():
     return synthetic.small_scene(seed=3, n_scan=3000)
 
 
+def _key_limit(name, every, seed):
+    # a scene of tests/key_limit_inputs.py (which imports this module: hence here): `corners` has rows at both ends of every
+    # coordinate field of the voxel key, `chain40x8` blocks that collide in the block hash at levels 0 to 3
+    from tests import key_limit_inputs
+    return with_duplicates(key_limit_inputs.case(name).copy(), every, seed)
+
+
 # name -> (builder, rows at levels 0..4)
 CASES = {
     "min": (_min, (17, 3, 2, 2, 2)),
@@ -136,6 +143,8 @@ CASES = {
     "brick": (_brick, (324, 45, 16, 16, 2)),
     "dupes": (_dupes, (60, 16, 9, 5, 5)),
     "off_range": (_off_range, (81, 13, 3, 3, 3)),
+    "corners": (lambda: _key_limit("corners", 9, seed=71), (270, 80, 10, 10, 10)),
+    "chain40x8": (lambda: _key_limit("chain40x8", 7, seed=72), (160, 160, 160, 160, 160)),
 }
 TILE_EDGES = ("tile16", "tile17", "tile64", "tile65", "tile257")
 
