@@ -514,26 +514,32 @@ class Context:
     def ndt_map_cells(self, key_ptr, count_ptr, mean_ptr, icov_ptr, valid_ptr):
         self._ndt_level_call("cells", None, key_ptr, count_ptr, mean_ptr, icov_ptr, valid_ptr)
 
+    # What is registered, the thinned points or the scan's own cells ("NDT localiser, distribution to distribution"), changes
+    # the name of the ABI function and what the first three arguments hold: ``d2d`` True: the source records, n_src and
+    # cap_src in the place of pts, n_dev and cap.  The ``_d2d`` methods further down are these with ``d2d=True``.
     def ndt_align(self, pts_ptr, n_dev_ptr: int, cap: int, T_init, iters: int, neighbours: int, min_corr: int,
                   outlier_ratio: float, tol_t: float, tol_r: float, T_out_ptr: int, status_ptr: int, trace_ptr, normal_ptr,
-                  scratch_ptr: int, stream: int):
-        check(lib.sps_ndt_align(self.handle, pts_ptr, n_dev_ptr, int(cap), self._mat(T_init), int(iters), int(neighbours),
-                                int(min_corr), float(outlier_ratio), float(tol_t), float(tol_r), T_out_ptr, status_ptr,
-                                trace_ptr, normal_ptr, scratch_ptr, stream))
+                  scratch_ptr: int, stream: int, d2d: bool = False):
+        fn = lib.sps_ndt_align_d2d if d2d else lib.sps_ndt_align
+        check(fn(self.handle, pts_ptr, n_dev_ptr, int(cap), self._mat(T_init), int(iters), int(neighbours), int(min_corr),
+                 float(outlier_ratio), float(tol_t), float(tol_r), T_out_ptr, status_ptr, trace_ptr, normal_ptr, scratch_ptr,
+                 stream))
 
     def ndt_align_batch(self, pts_ptr, n_dev_ptr: int, cap: int, T_init_ptr, n_hyp: int, iters: int, neighbours: int,
                         min_corr: int, outlier_ratio: float, tol_t: float, tol_r: float, T_out_ptr: int, status_ptr: int,
-                        trace_ptr, normal_ptr, final_ptr: int, best_ptr: int, T_best_ptr: int, scratch_ptr: int, stream: int):
-        check(lib.sps_ndt_align_batch(self.handle, pts_ptr, n_dev_ptr, int(cap), T_init_ptr, int(n_hyp), int(iters),
-                                      int(neighbours), int(min_corr), float(outlier_ratio), float(tol_t), float(tol_r),
-                                      T_out_ptr, status_ptr, trace_ptr, normal_ptr, final_ptr, best_ptr, T_best_ptr,
-                                      scratch_ptr, stream))
+                        trace_ptr, normal_ptr, final_ptr: int, best_ptr: int, T_best_ptr: int, scratch_ptr: int, stream: int,
+                        d2d: bool = False):
+        fn = lib.sps_ndt_align_d2d_batch if d2d else lib.sps_ndt_align_batch
+        check(fn(self.handle, pts_ptr, n_dev_ptr, int(cap), T_init_ptr, int(n_hyp), int(iters), int(neighbours), int(min_corr),
+                 float(outlier_ratio), float(tol_t), float(tol_r), T_out_ptr, status_ptr, trace_ptr, normal_ptr, final_ptr,
+                 best_ptr, T_best_ptr, scratch_ptr, stream))
 
     # ---- NDT localiser, pose search (include/sps_hip.h, "NDT localiser, pose search") ----
     def ndt_score_poses(self, pts_ptr, n_dev_ptr: int, cap: int, T_ptr, n_pose: int, neighbours: int, outlier_ratio: float,
-                        score_ptr: int, scratch_ptr: int, stream: int):
-        check(lib.sps_ndt_score_poses(self.handle, pts_ptr, n_dev_ptr, int(cap), T_ptr, int(n_pose), int(neighbours),
-                                      float(outlier_ratio), score_ptr, scratch_ptr, stream))
+                        score_ptr: int, scratch_ptr: int, stream: int, d2d: bool = False):
+        fn = lib.sps_ndt_score_poses_d2d if d2d else lib.sps_ndt_score_poses
+        check(fn(self.handle, pts_ptr, n_dev_ptr, int(cap), T_ptr, int(n_pose), int(neighbours), float(outlier_ratio),
+                 score_ptr, scratch_ptr, stream))
 
     def ndt_top_poses(self, score_ptr: int, T_ptr, n_pose: int, min_corr: int, k: int, top_index_ptr: int, T_top_ptr: int,
                       n_top_ptr: int, stream: int):
@@ -649,11 +655,13 @@ class Context:
 
     def ndt_pyramid_align(self, pts_ptr, n_dev_ptr: int, cap: int, T_init, iters: int, level_iters, neighbours: int,
                           min_corr: int, tol_t: float, tol_r: float, T_out_ptr: int, status_ptr: int, trace_ptr, normal_ptr,
-                          level_ptr, scratch_ptr: int, stream: int):
+                          level_ptr, scratch_ptr: int, stream: int, d2d: bool = False):
+        """d2d: src [L][cap][NDT_SRC_REC] and n_src [L][2] for pts and n_dev, as ``ndt_pyramid_source_build`` leaves them"""
+        fn = lib.sps_ndt_pyramid_align_d2d if d2d else lib.sps_ndt_pyramid_align
         caps = (C.c_int32 * len(level_iters))(*[int(v) for v in level_iters])
-        check(lib.sps_ndt_pyramid_align(self.handle, pts_ptr, n_dev_ptr, int(cap), self._mat(T_init), int(iters), caps,
-                                        int(neighbours), int(min_corr), float(tol_t), float(tol_r), T_out_ptr, status_ptr,
-                                        trace_ptr, normal_ptr, level_ptr, scratch_ptr, stream))
+        check(fn(self.handle, pts_ptr, n_dev_ptr, int(cap), self._mat(T_init), int(iters), caps, int(neighbours),
+                 int(min_corr), float(tol_t), float(tol_r), T_out_ptr, status_ptr, trace_ptr, normal_ptr, level_ptr,
+                 scratch_ptr, stream))
 
     # ---- NDT localiser, pyramid, several hypotheses (include/sps_hip.h, same title) ----
     def ndt_pyramid_align_batch(self, pts_ptr, n_dev_ptr: int, cap: int, T_init_ptr, n_hyp: int, iters: int, level_iters,
@@ -672,27 +680,16 @@ class Context:
         check(lib.sps_ndt_source_build(self.handle, pts_ptr, n_dev_ptr, int(cap), float(source_resolution), int(min_points),
                                        float(eig_ratio), src_ptr, src_count_ptr, n_src_ptr, scratch_ptr, stream))
 
-    def ndt_align_d2d(self, src_ptr, n_src_ptr: int, cap_src: int, T_init, iters: int, neighbours: int, min_corr: int,
-                      outlier_ratio: float, tol_t: float, tol_r: float, T_out_ptr: int, status_ptr: int, trace_ptr, normal_ptr,
-                      scratch_ptr: int, stream: int):
-        check(lib.sps_ndt_align_d2d(self.handle, src_ptr, n_src_ptr, int(cap_src), self._mat(T_init), int(iters),
-                                    int(neighbours), int(min_corr), float(outlier_ratio), float(tol_t), float(tol_r), T_out_ptr,
-                                    status_ptr, trace_ptr, normal_ptr, scratch_ptr, stream))
+    def ndt_align_d2d(self, *args):
+        """``ndt_align`` with the source records, n_src and cap_src"""
+        self.ndt_align(*args, d2d=True)
 
     # ---- NDT localiser, distribution to distribution, several poses (include/sps_hip.h, same title) ----
-    def ndt_align_d2d_batch(self, src_ptr, n_src_ptr: int, cap_src: int, T_init_ptr, n_hyp: int, iters: int, neighbours: int,
-                            min_corr: int, outlier_ratio: float, tol_t: float, tol_r: float, T_out_ptr: int, status_ptr: int,
-                            trace_ptr, normal_ptr, final_ptr: int, best_ptr: int, T_best_ptr: int, scratch_ptr: int,
-                            stream: int):
-        check(lib.sps_ndt_align_d2d_batch(self.handle, src_ptr, n_src_ptr, int(cap_src), T_init_ptr, int(n_hyp), int(iters),
-                                          int(neighbours), int(min_corr), float(outlier_ratio), float(tol_t), float(tol_r),
-                                          T_out_ptr, status_ptr, trace_ptr, normal_ptr, final_ptr, best_ptr, T_best_ptr,
-                                          scratch_ptr, stream))
+    def ndt_align_d2d_batch(self, *args):
+        self.ndt_align_batch(*args, d2d=True)
 
-    def ndt_score_poses_d2d(self, src_ptr, n_src_ptr: int, cap_src: int, T_ptr, n_pose: int, neighbours: int,
-                            outlier_ratio: float, score_ptr: int, scratch_ptr: int, stream: int):
-        check(lib.sps_ndt_score_poses_d2d(self.handle, src_ptr, n_src_ptr, int(cap_src), T_ptr, int(n_pose), int(neighbours),
-                                          float(outlier_ratio), score_ptr, scratch_ptr, stream))
+    def ndt_score_poses_d2d(self, *args):
+        self.ndt_score_poses(*args, d2d=True)
 
     # ---- NDT localiser, distribution to distribution, pyramid (include/sps_hip.h, same title) ----
     def ndt_pyramid_source_build(self, pts_ptr, n_dev_ptr: int, cap: int, source_resolutions, min_points, eig_ratio: float,
@@ -706,13 +703,8 @@ class Context:
         check(lib.sps_ndt_pyramid_source_build(self.handle, pts_ptr, n_dev_ptr, int(cap), L, res, mp, float(eig_ratio), src_ptr,
                                                src_count_ptr, n_src_ptr, scratch_ptr, stream))
 
-    def ndt_pyramid_align_d2d(self, src_ptr, n_src_ptr: int, cap_src: int, T_init, iters: int, level_iters, neighbours: int,
-                              min_corr: int, tol_t: float, tol_r: float, T_out_ptr: int, status_ptr: int, trace_ptr, normal_ptr,
-                              level_ptr, scratch_ptr: int, stream: int):
-        caps = (C.c_int32 * len(level_iters))(*[int(v) for v in level_iters])
-        check(lib.sps_ndt_pyramid_align_d2d(self.handle, src_ptr, n_src_ptr, int(cap_src), self._mat(T_init), int(iters), caps,
-                                            int(neighbours), int(min_corr), float(tol_t), float(tol_r), T_out_ptr, status_ptr,
-                                            trace_ptr, normal_ptr, level_ptr, scratch_ptr, stream))
+    def ndt_pyramid_align_d2d(self, *args):
+        self.ndt_pyramid_align(*args, d2d=True)
 
     def train_forward(self, params_ptr: int, numel: int, coords_ptr: int, ld: int, n: int, voxel_size: float,
                       scores_ptr: int, batch_stats_ptr, stream: int):

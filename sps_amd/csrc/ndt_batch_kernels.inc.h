@@ -3,14 +3,16 @@
 // "NDT localiser, several hypotheses" section of include/sps_hip.h).
 //
 //   k_loc_init_batch    T_out[k] = T_init[k], status[k] = (1, 0, 0, 0), done[k] = 0
-//   k_ndt_assoc_batch   (launch A)  grid (blocks, K): ndt_assoc_body of hypothesis blockIdx.y
+//   k_ndt_assoc_batch   (launch A)  grid (blocks, K): ndt_assoc_body of hypothesis blockIdx.y (a template over the scan, as
+//                       k_ndt_assoc)
 //   k_loc_solve_batch   (launch B)  grid K: loc_solve_body of hypothesis blockIdx.x
 //   k_ndt_select        the score and the count of every hypothesis at its final pose, and the best of them
 //
-// The scan points and the map are read by all hypotheses; a hypothesis owns its pose, its done flag, its partial rows
-// (partial[k][block][LOC_TERMS]), its status, trace and normal rows.  Per hypothesis every operation and the order of
-// every sum are those of k_ndt_assoc / k_loc_solve, whose bodies these kernels call, so hypothesis k of a batch has the
-// bits of a single alignment from T_init[k].  Stores are plain vector stores; nothing here is atomic.
+// The scan (points or, NdtCells, source cells) and the map are read by all hypotheses; a hypothesis owns its pose, its
+// done flag, its partial rows (partial[k][block][LOC_TERMS]), its status, trace and normal rows.  Per hypothesis every
+// operation and the order of every sum are those of k_ndt_assoc / k_loc_solve, whose bodies these kernels call, so
+// hypothesis k of a batch has the bits of a single alignment from T_init[k].  Stores are plain vector stores; nothing here
+// is atomic.
 
 #pragma clang fp contract(off)
 
@@ -27,7 +29,8 @@ __global__ __launch_bounds__(64) void k_loc_init_batch(const double *__restrict_
 
 // Launch A.  nb = the partial rows of one hypothesis (gridDim.x); all = 1: the pass after the last iteration, which
 // evaluates every hypothesis at its final pose whatever its done flag says.
-__global__ __launch_bounds__(256) void k_ndt_assoc_batch(const double *__restrict__ pts, const int *__restrict__ n_dev, int cap,
+template <class Scan>
+__global__ __launch_bounds__(256) void k_ndt_assoc_batch(const double *__restrict__ elems, const int *__restrict__ n_dev, int cap,
                                                           NdtMap m, NdtGauss gs, int neighbours, int n_hyp,
                                                           const double *__restrict__ T, const int *__restrict__ done, int all,
                                                           double *__restrict__ partial) {
@@ -35,8 +38,9 @@ __global__ __launch_bounds__(256) void k_ndt_assoc_batch(const double *__restric
   const int k = blockIdx.y;
   if (k >= n_hyp) return;
   if (!all && done[k]) return;
-  ndt_assoc_body(pts, n_dev, cap, m, gs, neighbours, T + (size_t)k * 16, partial + (size_t)k * gridDim.x * LOC_TERMS, lds);
+  ndt_assoc_body<Scan>(elems, n_dev, cap, m, gs, neighbours, T + (size_t)k * 16, partial + (size_t)k * gridDim.x * LOC_TERMS, lds);
 }
+using NdtAssocBatchKernel = decltype(&k_ndt_assoc_batch<NdtPoints>);
 
 // Launch B, one workgroup of 256 per hypothesis.  nb = the partial rows of one hypothesis.
 __global__ __launch_bounds__(256) void k_loc_solve_batch(const double *__restrict__ partial, int nb, const int *__restrict__ n_dev,

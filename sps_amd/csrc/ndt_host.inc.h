@@ -3,7 +3,11 @@
 // synchronises, like sps_radius_grid_upload; sps_ndt_align does neither: its scratch is the caller's.  The single map of a
 // context is a pyramid of one level (sps_ctx::ndt_map), so three helpers here serve the single map and the pyramid alike
 // and the later NDT files too: ndt_build_impl (every build: static or dynamic, one level or several), ndt_cells_impl (both
-// cell getters) and ndt_check_scan_args (the checks that the alignment, the batch and the pose score share).
+// cell getters) and ndt_check_scan_args (the checks that the alignment, the batch and the pose score share).  What is
+// registered, the thinned points or the scan's own cells, is a type (NdtPoints, NdtCells) that launch A's body is a template
+// over: ndt_align_batch_impl, ndt_score_poses_impl and ndt_pyramid_align_impl of the later files take the scan's kernel
+// instantiation as an argument, and the entry points of ndt_d2d_host.inc.h hand them NdtCells'.  The single alignment's two
+// entry points keep a host body each (sps_ndt_align here, sps_ndt_align_d2d there; see k_ndt_assoc).
 
 namespace {
 // the Gaussian fit of the mixture (Magnusson 2009, eq. 6.8; PCL's gauss_d1_ / gauss_d2_), in float64 on the host; false

@@ -5,7 +5,8 @@
 //   k_ndt_cells   (map build)                 per map cell: n, mean, sample covariance, Jacobi eigen-decomposition, floored
 //                                             eigenvalues, inverse covariance -> one 80-byte record (and S for an online map)
 //   k_ndt_assoc   (launch A of an iteration)  q = R p + t, the records of q's cell and its face neighbours, the
-//                                             normal-equation terms of every contributing cell
+//                                             normal-equation terms of every contributing cell (its body a template
+//                                             over the scan: NdtPoints here, NdtCells of ndt_d2d_kernels.inc.h)
 //
 // This file also holds the one definition of what the batch, search and update kernels share with these two:
 //   ndt_list_moments, ndt_record_from_moments   a cell's moments from its point list; its record from (n, mean, S)
@@ -13,7 +14,7 @@
 //                                               cells of ndt_d2d_kernels.inc.h)
 //   ndt_cell_key, ndt_cell_of                   the cell of a point (radius_cell of aux_kernels.inc.h) and its id in the map
 //   ndt_cell_hit                                one cell's contribution to one point
-//   ndt_assoc_reduce                            phases 2 and 3 of launch A, from the hits in LDS (also k_ndt_d2d_assoc's)
+//   ndt_assoc_body, ndt_assoc_reduce            launch A: phase 1 over the scan's policy type, phases 2 and 3 from the hits in LDS
 // with loc_transform of loc_kernels.inc.h in front.  That the entry points agree bit for bit follows from that.
 //
 // Launch B is k_loc_solve unchanged: the partial rows have its layout (21 of H, 6 of g, the score, the count; one row per
@@ -225,13 +226,14 @@ __device__ inline bool ndt_cell_hit(const double q[3], const double *__restrict_
   return w >= 0.0 && w <= 1.0;   // NaN fails both: the guard of ndt_omp
 }
 
-// Launch A.  NDT_LANES lanes per scan point, LOC_PTS points per workgroup.
-//   phase 1: lane c < neighbours looks up cell c of the point (ndt_cell_of) and, where the cell contributes
-//            (ndt_cell_hit), leaves a, icov, y = icov x and the score in LDS;
-//   phase 2: lane l forms terms l, l + 8, l + 16, l + 24 of the point, adding the contributing cells in lookup order;
-//   phase 3: thread l < LOC_TERMS adds the workgroup's points in point order and writes entry l of the partial row.
-// The body is shared with k_ndt_assoc_batch (ndt_batch_kernels.inc.h), which runs it once per hypothesis: T is the pose,
-// partial the rows of that pose, blockIdx.x the workgroup's place among them.
+// Launch A.  NDT_LANES lanes per element of the scan (a point, a source cell), LOC_PTS elements per workgroup.
+//   phase 1: lane c < neighbours looks up cell c of the element's place (ndt_cell_of) and, where the cell contributes
+//            (Scan::hit), leaves a, the inverse covariance, y and the score in LDS;
+//   phase 2: lane l forms terms l, l + 8, l + 16, l + 24 of the element, adding the contributing cells in lookup order;
+//   phase 3: thread l < LOC_TERMS adds the workgroup's elements in index order and writes entry l of the partial row.
+// The body (ndt_assoc_body below) is shared with k_ndt_assoc_batch (ndt_batch_kernels.inc.h), which runs it once per
+// hypothesis, and with the pyramid's launches: T is the pose, partial the rows of that pose, blockIdx.x the workgroup's
+// place among them.
 struct NdtAssocLds {
   double hit[LOC_PTS][7][NDT_HIT];
   int hit_ok[LOC_PTS][NDT_LANES];
@@ -239,9 +241,8 @@ struct NdtAssocLds {
 };
 
 // Phases 2 and 3 of launch A, from the hits that phase 1 left in LDS (every thread of the workgroup must call, for the
-// barriers): k is the thread's element of the workgroup, sub its lane, q the element's place in the map frame.  Shared by
-// the point-to-distribution kernels and k_ndt_d2d_assoc (ndt_d2d_kernels.inc.h), whose hit holds the combined inverse
-// covariance where a point's hit holds the cell's.
+// barriers): k is the thread's element of the workgroup, sub its lane, q the element's place in the map frame.  A source
+// cell's hit holds the combined inverse covariance where a point's hit holds the cell's.
 __device__ inline void ndt_assoc_reduce(NdtAssocLds &lds, int k, int sub, const double q[3], int neighbours,
                                         double *__restrict__ partial) {
   double(*hit)[7][NDT_HIT] = lds.hit;
@@ -284,11 +285,35 @@ __device__ inline void ndt_assoc_reduce(NdtAssocLds &lds, int k, int sub, const 
   }
 }
 
-__device__ inline void ndt_assoc_body(const double *__restrict__ pts, const int *__restrict__ n_dev, int cap, const NdtMap &m,
+// ---- the scan as a type ----------------------------------------------------------------------------------------------
+// What launch A registers is a policy type: how a lane gets its element and its hit, and, for a pyramid, where a level's
+// elements and their count lie and which level follows.  NdtPoints: the thinned points, the same array at every level.
+// NdtCells (ndt_d2d_kernels.inc.h): the scan's own cells, a slice per level.
+//   ELEM                       doubles of one element
+//   valid(el)                  false: the element contributes nothing at any pose and is not counted (apart from hit: the
+//                              scorer asks once per element, not once per pose)
+//   hit(...)                   of a valid element: q = its place at the pose T, and lane `sub`'s contribution: false where
+//                              the cell of q adds nothing; true hands back e, w, y and the inverse covariance B
+//   level_elems, level_count   the elements of level l of a pyramid, and where their count is
+//   next                       the level after l, < 0 where l is the last
+struct NdtPoints {
+  static constexpr int ELEM = 3;
+  __device__ static bool valid(const double *) { return true; }
+  __device__ static bool hit(const NdtMap &m, const NdtGauss &gs, const double *T, const double *p, int sub, int neighbours,
+                             double q[3], double &e, double &w, double y[3], double B[6]) {
+    loc_transform(T, p[0], p[1], p[2], q);
+    const int cell = sub < neighbours ? ndt_cell_of(m, q, sub) : -1;
+    return cell >= 0 && ndt_cell_hit(q, m.rec + (size_t)cell * NDT_REC, gs, e, w, y, B);
+  }
+  __device__ static const double *level_elems(const double *pts, int, int) { return pts; }
+  __device__ static const int *level_count(const int *n_dev, int) { return n_dev; }
+  __device__ static int next(const int *, int, int l, int n_levels, int) { return l == n_levels - 1 ? -1 : l + 1; }
+};
+
+template <class Scan>
+__device__ inline void ndt_assoc_body(const double *__restrict__ elems, const int *__restrict__ n_dev, int cap, const NdtMap &m,
                                       const NdtGauss &gs, int neighbours, const double *__restrict__ T,
                                       double *__restrict__ partial, NdtAssocLds &lds) {
-  double(*hit)[7][NDT_HIT] = lds.hit;
-  int(*hit_ok)[NDT_LANES] = lds.hit_ok;
   const int n = min(cap, max(*n_dev, 0));
   const int base = blockIdx.x * LOC_PTS;
   if (base >= n) return;
@@ -297,29 +322,35 @@ __device__ inline void ndt_assoc_body(const double *__restrict__ pts, const int 
   double q[3] = {0.0, 0.0, 0.0};
   int ok = 0;
   if (i < n) {
-    loc_transform(T, pts[(size_t)i * 3], pts[(size_t)i * 3 + 1], pts[(size_t)i * 3 + 2], q);
-    const int cell = sub < neighbours ? ndt_cell_of(m, q, sub) : -1;
-    double e, w, y[3], icov[6];
-    if (cell >= 0 && ndt_cell_hit(q, m.rec + (size_t)cell * NDT_REC, gs, e, w, y, icov)) {
-      double *o = hit[k][sub];
-      o[0] = loc_mul(gs.nd1, w);
+    double el[Scan::ELEM];
 #pragma unroll
-      for (int j = 0; j < 6; ++j) o[1 + j] = icov[j];
-      o[7] = y[0], o[8] = y[1], o[9] = y[2];
-      o[10] = loc_mul(gs.nd1, e);
-      ok = 1;
+    for (int j = 0; j < Scan::ELEM; ++j) el[j] = elems[(size_t)i * Scan::ELEM + j];
+    if (Scan::valid(el)) {
+      double e, w, y[3], B[6];
+      if (Scan::hit(m, gs, T, el, sub, neighbours, q, e, w, y, B)) {
+        double *o = lds.hit[k][sub];
+        o[0] = loc_mul(gs.nd1, w);
+#pragma unroll
+        for (int j = 0; j < 6; ++j) o[1 + j] = B[j];
+        o[7] = y[0], o[8] = y[1], o[9] = y[2];
+        o[10] = loc_mul(gs.nd1, e);
+        ok = 1;
+      }
     }
   }
-  hit_ok[k][sub] = ok;
+  lds.hit_ok[k][sub] = ok;
   ndt_assoc_reduce(lds, k, sub, q, neighbours, partial);
 }
 
+// The single alignment's launch A stays a kernel of its own per scan (k_ndt_d2d_assoc: ndt_d2d_kernels.inc.h), launched by
+// name from its entry point: the plain submit, 61 launches in 1.0 ms, read 0.2 - 0.4 % slower in two sessions through the
+// shared host implementation (profiles/ndt_one_scan).
 __global__ __launch_bounds__(256) void k_ndt_assoc(const double *__restrict__ pts, const int *__restrict__ n_dev, int cap,
                                                     NdtMap m, NdtGauss gs, int neighbours, const double *__restrict__ T,
                                                     const int *__restrict__ done, double *__restrict__ partial) {
   __shared__ NdtAssocLds lds;
   if (*done) return;
-  ndt_assoc_body(pts, n_dev, cap, m, gs, neighbours, T, partial, lds);
+  ndt_assoc_body<NdtPoints>(pts, n_dev, cap, m, gs, neighbours, T, partial, lds);
 }
 
 #pragma clang fp contract(fast)

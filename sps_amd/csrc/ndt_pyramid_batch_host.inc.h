@@ -24,10 +24,7 @@ int sps_ndt_pyramid_align_batch(sps_ctx *c, const double *pts_dev, const int32_t
   if (L < 1) return fail(SPS_ERR_INVALID, "sps_ndt_pyramid_build has not been called");
   if (int e = ndt_check_scan_limits(neighbours, cap, true, iters, tol_t, tol_r)) return e;
   NdtPyrCaps caps{};
-  for (int l = 0; l < NDT_PYR_MAX; ++l) {
-    caps.v[l] = l < L ? level_iters[l] : 1;
-    if (caps.v[l] < 1) return fail(SPS_ERR_INVALID, "level_iters must be >= 1");
-  }
+  if (int e = ndt_pyr_caps(L, level_iters, caps)) return e;
   HIP_TRY(hipSetDevice(c->device));
   hipStream_t st = (hipStream_t)stream;
   const int nb = (int)loc_align_blocks(cap);
@@ -46,8 +43,8 @@ int sps_ndt_pyramid_align_batch(sps_ctx *c, const double *pts_dev, const int32_t
   // every hypothesis once more at its final pose, against the finest level whatever level it stopped at: the scores
   // k_ndt_select chooses by (the done flags are not read with all = 1: the state words stand in for them)
   const NdtPyrLevel &fine = c->ndt_pyr.lv[L - 1];
-  hipLaunchKernelGGL(k_ndt_assoc_batch, dim3(nb, n_hyp), dim3(256), 0, st, pts_dev, n_dev, (int)cap, fine.m, fine.gs, neighbours,
-                     n_hyp, (const double *)T_out_dev, (const int *)state, 1, partial);
+  hipLaunchKernelGGL(k_ndt_assoc_batch<NdtPoints>, dim3(nb, n_hyp), dim3(256), 0, st, pts_dev, n_dev, (int)cap, fine.m, fine.gs,
+                     neighbours, n_hyp, (const double *)T_out_dev, (const int *)state, 1, partial);
   hipLaunchKernelGGL(k_ndt_select, dim3(1), dim3(256 * NDT_SELECT_GROUPS), 0, st, (const double *)partial, nb, n_dev, (int)cap,
                      n_hyp, min_corr, (const int *)status_dev, (const double *)T_out_dev, T_init_dev, final_dev, best_dev,
                      T_best_dev);

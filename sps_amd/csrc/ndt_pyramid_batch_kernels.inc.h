@@ -55,7 +55,8 @@ __global__ __launch_bounds__(256) void k_ndt_pyr_assoc_batch(const double *__res
   if (st[0]) return;
   const int l = __builtin_amdgcn_readfirstlane(min(max(st[1], 0), n_levels - 1));
   const NdtPyrLevel d = levels[l];
-  ndt_assoc_body(pts, n_dev, cap, d.m, d.gs, neighbours, T + (size_t)k * 16, partial + (size_t)k * gridDim.x * LOC_TERMS, lds);
+  ndt_assoc_body<NdtPoints>(pts, n_dev, cap, d.m, d.gs, neighbours, T + (size_t)k * 16,
+                            partial + (size_t)k * gridDim.x * LOC_TERMS, lds);
 }
 
 // Launch B, one workgroup of 256 per hypothesis.  nb = the partial rows of one hypothesis.  T_init is read from the device
@@ -87,7 +88,7 @@ __global__ __launch_bounds__(256) void k_ndt_pyr_solve_batch(const double *__res
     state[0] = 1;
     return;
   }
-  ndt_pyr_handoff(l, ndt_pyr_next(l, n_levels), caps, vn < tol_t && th < tol_r, status, state);
+  ndt_pyr_handoff(l, NdtPoints::next(n_dev, cap, l, n_levels, min_corr), caps, vn < tol_t && th < tol_r, status, state);
 }
 
 #pragma clang fp contract(fast)

@@ -3,9 +3,12 @@
 // dynamic (host side: ndt_pyramid_host.inc.h; ABI: the "NDT localiser, multi-resolution pyramid" section of include/sps_hip.h).
 //
 //   k_ndt_pyr_init    T_out = T_init, status = (1, 0, 0, 0), the state words 0, level[s] = -1, trace and normal rows 0
-//   k_ndt_pyr_assoc   (launch A of a slot)  ndt_assoc_body against the map of the level the state names
+//   k_ndt_pyr_assoc   (launch A of a slot)  ndt_assoc_body on the scan's elements of the level the state names, against
+//                     that level's map
 //   k_ndt_pyr_solve   (launch B of a slot)  loc_sum_rows + loc_solve_step, then the handoff rule (ndt_pyr_handoff: its one
 //                     definition, shared with k_ndt_pyr_solve_batch of ndt_pyramid_batch_kernels.inc.h)
+// Both are templates over the scan (NdtPoints of ndt_kernels.inc.h: the same points at every level, level l + 1 follows l;
+// NdtCells of ndt_d2d_kernels.inc.h: a slice of source cells per level, levels with too few valid cells are skipped).
 //
 // The levels are the maps k_radius_cells_insert and k_ndt_cells build, one NdtPyrLevel (map + Gaussian fit) each in a device
 // array.  Which level a slot runs at is decided on the device: the state words live in the caller's scratch behind the
@@ -63,7 +66,8 @@ __global__ __launch_bounds__(256) void k_ndt_pyr_init(LocPose T, int iters, doub
 // Launch A.  Grid and workgroup of k_ndt_assoc.  The level is the same for every thread of the grid: it goes through a
 // scalar register, and the level's descriptor is read from the device array (a by-value array indexed by it would live in
 // scratch).
-__global__ __launch_bounds__(256) void k_ndt_pyr_assoc(const double *__restrict__ pts, const int *__restrict__ n_dev, int cap,
+template <class Scan>
+__global__ __launch_bounds__(256) void k_ndt_pyr_assoc(const double *__restrict__ elems, const int *__restrict__ n_dev, int cap,
                                                         const NdtPyrLevel *__restrict__ levels, int n_levels, int neighbours,
                                                         const double *__restrict__ T, const int *__restrict__ state,
                                                         double *__restrict__ partial) {
@@ -71,17 +75,17 @@ __global__ __launch_bounds__(256) void k_ndt_pyr_assoc(const double *__restrict_
   if (state[0]) return;
   const int l = __builtin_amdgcn_readfirstlane(min(max(state[1], 0), n_levels - 1));
   const NdtPyrLevel d = levels[l];
-  ndt_assoc_body(pts, n_dev, cap, d.m, d.gs, neighbours, T, partial, lds);
+  ndt_assoc_body<Scan>(Scan::level_elems(elems, cap, l), Scan::level_count(n_dev, l), cap, d.m, d.gs, neighbours, T, partial,
+                       lds);
 }
+using NdtPyrAssocKernel = decltype(&k_ndt_pyr_assoc<NdtPoints>);
 
 // The handoff rule, by the one thread that made a step at level l (ndt_pyr_solve_body below; k_ndt_pyr_solve_batch in
 // ndt_pyramid_batch_kernels.inc.h runs it once per hypothesis): that level's count of used slots goes up; a converged step
 // ends the call with status 0 on the last level and hands the pose to level `next` otherwise; a step that is not converged
 // does the same once the level has used its cap, except that the status stays 1.  next: the level that follows l, < 0
-// where l is the last (ndt_pyr_next: l + 1 of n_levels; the d2d pyramid of ndt_d2d_pyramid_kernels.inc.h skips levels).
-// state: the call's (the hypothesis') words.
-__device__ inline int ndt_pyr_next(int l, int n_levels) { return l == n_levels - 1 ? -1 : l + 1; }
-
+// where l is the last (the scan's `next`: l + 1 for points, while source cells skip levels).  state: the call's (the
+// hypothesis') words.
 __device__ inline void ndt_pyr_handoff(int l, int next, NdtPyrCaps caps, bool converged, int *__restrict__ status,
                                        int *__restrict__ state) {
   const int used = state[2 + l] + 1;
@@ -104,8 +108,7 @@ __device__ inline void ndt_pyr_handoff(int l, int next, NdtPyrCaps caps, bool co
 }
 
 // The step of launch B, by a workgroup of 256 whose call is live: the n rows' partial sums (loc_sum_rows), then thread 0
-// alone: loc_solve_step at level l and the handoff to `next`.  k_ndt_pyr_solve below and k_ndt_d2d_pyr_solve
-// (ndt_d2d_pyramid_kernels.inc.h) differ in where n, l and next come from.
+// alone: loc_solve_step at level l and the handoff to `next`.
 __device__ inline void ndt_pyr_solve_body(const double *__restrict__ partial, int n, int slot, int l, int next, NdtPyrCaps caps,
                                           int min_corr, double tol_t, double tol_r, const LocPose &T_init, double *__restrict__ T,
                                           int *__restrict__ status, int *__restrict__ state, double *__restrict__ trace,
@@ -125,7 +128,9 @@ __device__ inline void ndt_pyr_solve_body(const double *__restrict__ partial, in
 // Launch B, one workgroup of 256.  After a step at level l that level's count of used slots goes up; a converged step
 // (|v| < tol_t and |omega| < tol_r) ends the call with status 0 on the last level and hands the pose to level l + 1
 // otherwise; a step that is not converged does the same once the level has used its cap, except that the status stays 1.
-// Status 2 and 3 are final at any level.  status = (code, slots used, count of the last live slot, its level).
+// Status 2 and 3 are final at any level.  status = (code, slots used, count of the last live slot, its level).  The rows are
+// those of the level's elements (Scan::level_count), the level that follows is the scan's (Scan::next).
+template <class Scan>
 __global__ __launch_bounds__(256) void k_ndt_pyr_solve(const double *__restrict__ partial, const int *__restrict__ n_dev, int cap,
                                                         int slot, int n_levels, NdtPyrCaps caps, int min_corr, double tol_t,
                                                         double tol_r, LocPose T_init, double *__restrict__ T,
@@ -135,10 +140,11 @@ __global__ __launch_bounds__(256) void k_ndt_pyr_solve(const double *__restrict_
   __shared__ double seg[LOC_SEG][32];
   __shared__ double tot[32];
   if (state[0]) return;
-  const int n = min(cap, max(*n_dev, 0));
   const int l = min(max(state[1], 0), n_levels - 1);
-  ndt_pyr_solve_body(partial, n, slot, l, ndt_pyr_next(l, n_levels), caps, min_corr, tol_t, tol_r, T_init, T, status, state, trace,
-                     normal, level, seg, tot);
+  const int n = min(cap, max(*Scan::level_count(n_dev, l), 0));
+  ndt_pyr_solve_body(partial, n, slot, l, Scan::next(n_dev, cap, l, n_levels, min_corr), caps, min_corr, tol_t, tol_r, T_init, T,
+                     status, state, trace, normal, level, seg, tot);
 }
+using NdtPyrSolveKernel = decltype(&k_ndt_pyr_solve<NdtPoints>);
 
 #pragma clang fp contract(fast)

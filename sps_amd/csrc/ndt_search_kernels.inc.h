@@ -2,15 +2,15 @@
 // ndt_batch_kernels.inc.h): the NDT score of many poses and the choice of the best of them (host side:
 // ndt_search_host.inc.h; ABI: the "NDT localiser, pose search" section of include/sps_hip.h).
 //
-//   k_ndt_score          grid (point blocks, pose tiles): partial[pose][block] = (score, points counted) of the block's
-//                        LOC_PTS points at every pose of the tile
+//   k_ndt_score          grid (element blocks, pose tiles): partial[pose][block] = (score, elements counted) of the
+//                        block's LOC_PTS elements of the scan at every pose of the tile; a template over the scan (NdtPoints
+//                        of ndt_kernels.inc.h, NdtCells of ndt_d2d_kernels.inc.h), as k_ndt_assoc
 //   k_ndt_score_reduce   score[pose] = the blocks of the pose added in loc_sum_rows' order
 //   k_ndt_top            one workgroup: the K best poses by (score descending, index ascending)
 //
-// Per point and pose k_ndt_score calls what phase 1 of ndt_assoc_body calls (loc_transform, ndt_cell_of, ndt_cell_hit:
-// ndt_kernels.inc.h), and of the 29 terms only the score (27) and the count (28) are formed; the sums run in the orders of
-// k_ndt_assoc and loc_sum_rows, so score[pose] has the bits of final_dev[k] of sps_ndt_align_batch(iters = 0) started at
-// that pose.
+// Per element and pose k_ndt_score calls what phase 1 of ndt_assoc_body calls (Scan::hit), and of the 29 terms only the
+// score (27) and the count (28) are formed; the sums run in the orders of ndt_assoc_reduce and loc_sum_rows, so score[pose]
+// has the bits of final_dev[k] of sps_ndt_align_batch(iters = 0), or of sps_ndt_align_d2d_batch, started at that pose.
 // Everything is float64, every operation is rounded on its own, stores are plain vector stores, nothing is atomic.
 
 #pragma clang fp contract(off)
@@ -20,11 +20,14 @@ constexpr int NDT_REDUCE_POSES = 16;    // poses of one workgroup of k_ndt_score
 constexpr int NDT_TOP_THREADS = 1024;
 static_assert(NDT_REDUCE_POSES * LOC_SEG * 2 == 256, "k_ndt_score_reduce: one workgroup of 256");
 
-// NDT_LANES lanes per scan point, LOC_PTS points per workgroup, as in k_ndt_assoc.  The workgroup reads its points
-// once and walks the poses of its tile: lane c < neighbours looks up cell c of the rotated point, the point's lane 0
-// adds the contributing cells in lookup order; then thread j adds the LOC_PTS points of pose j in point order.
+// NDT_LANES lanes per element of the scan (a point, a source cell), LOC_PTS elements per workgroup, as in k_ndt_assoc.  The
+// workgroup reads its elements once and walks the poses of its tile: lane c < neighbours looks up cell c of the element's
+// place at the pose (Scan::hit), the element's lane 0 adds the contributing cells in lookup order; then thread j adds the
+// LOC_PTS elements of pose j in index order.  An element that is not valid (Scan::valid: a source cell's flag) adds 0
+// and is not counted, which is what its row of zero terms adds in ndt_assoc_body.
 // nb = gridDim.x = the partial rows of one pose.  The +1 pads keep the last step free of LDS bank conflicts.
-__global__ __launch_bounds__(256) void k_ndt_score(const double *__restrict__ pts, const int *__restrict__ n_dev, int cap,
+template <class Scan>
+__global__ __launch_bounds__(256) void k_ndt_score(const double *__restrict__ elems, const int *__restrict__ n_dev, int cap,
                                                     NdtMap m, NdtGauss gs, int neighbours, const double *__restrict__ T,
                                                     int n_pose, double *__restrict__ partial) {
   __shared__ double pose[NDT_SCORE_TILE][12];
@@ -32,30 +35,33 @@ __global__ __launch_bounds__(256) void k_ndt_score(const double *__restrict__ pt
   __shared__ int hit[NDT_SCORE_TILE][LOC_PTS + 1];
   const int n = min(cap, max(*n_dev, 0));
   const int base = blockIdx.x * LOC_PTS;
-  if (base >= n) return;                     // as k_ndt_assoc: rows past the last point are never written, never read
+  if (base >= n) return;                     // as k_ndt_assoc: rows past the last element are never written, never read
   const int p0 = blockIdx.y * NDT_SCORE_TILE;
   const int tile = min(NDT_SCORE_TILE, n_pose - p0);
   if (tile <= 0) return;
   for (int t = threadIdx.x; t < tile * 12; t += 256) pose[t / 12][t % 12] = T[(size_t)(p0 + t / 12) * 16 + t % 12];
   const int k = threadIdx.x / NDT_LANES, sub = threadIdx.x % NDT_LANES;
   const int i = base + k;
-  const bool live = i < n && sub < neighbours;
-  double px = 0.0, py = 0.0, pz = 0.0;
-  if (i < n) px = pts[(size_t)i * 3], py = pts[(size_t)i * 3 + 1], pz = pts[(size_t)i * 3 + 2];
+  double el[Scan::ELEM];
+#pragma unroll
+  for (int j = 0; j < Scan::ELEM; ++j) el[j] = 0.0;
+  if (i < n) {
+#pragma unroll
+    for (int j = 0; j < Scan::ELEM; ++j) el[j] = elems[(size_t)i * Scan::ELEM + j];
+  }
+  const bool live = i < n && Scan::valid(el);
   __syncthreads();
   for (int j = 0; j < tile; ++j) {
     double v = 0.0;
     int ok = 0;
     if (live) {
-      double q[3], e, w, y[3], icov[6];
-      loc_transform(pose[j], px, py, pz, q);
-      const int cell = ndt_cell_of(m, q, sub);
-      if (cell >= 0 && ndt_cell_hit(q, m.rec + (size_t)cell * NDT_REC, gs, e, w, y, icov)) {
+      double q[3], e, w, y[3], B[6];
+      if (Scan::hit(m, gs, pose[j], el, sub, neighbours, q, e, w, y, B)) {
         v = loc_mul(gs.nd1, e);
         ok = 1;
       }
     }
-    // the point's cells in lookup order (every lane of the wave takes part in the shuffles)
+    // the element's cells in lookup order (every lane of the wave takes part in the shuffles)
     double term = 0.0;
     int any = 0;
 #pragma unroll
@@ -75,6 +81,7 @@ __global__ __launch_bounds__(256) void k_ndt_score(const double *__restrict__ pt
     o[0] = s, o[1] = cnt;
   }
 }
+using NdtScoreKernel = decltype(&k_ndt_score<NdtPoints>);
 
 // Thread (pose, sg, col) adds the rows of run sg of the pose's blocks in order, thread (pose, 0, col) the LOC_SEG runs
 // in order: loc_sum_rows restated for two columns, NDT_REDUCE_POSES poses per workgroup.  nb = the partial rows of one

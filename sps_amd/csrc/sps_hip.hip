@@ -154,12 +154,10 @@ int fail(int code, const char *fmt, ...) {
 #include "ndt_search_kernels.inc.h"
 #include "bbs_kernels.inc.h"
 #include "ndt_update_kernels.inc.h"
-#include "ndt_d2d_kernels.inc.h"
-#include "ndt_d2d_batch_kernels.inc.h"
 #include "ndt_carve_kernels.inc.h"
 #include "ndt_pyramid_kernels.inc.h"
 #include "ndt_online_kernels.inc.h"
-#include "ndt_d2d_pyramid_kernels.inc.h"
+#include "ndt_d2d_kernels.inc.h"
 #include "ndt_pyramid_batch_kernels.inc.h"
 #include "ukf_kernels.inc.h"
 
@@ -2255,10 +2253,8 @@ int sps_get_feature(sps_ctx *c, const char *name, float *out_dev, int64_t *rows,
 #include "ndt_search_host.inc.h"
 #include "bbs_host.inc.h"
 #include "ndt_online_host.inc.h"
-#include "ndt_d2d_host.inc.h"
-#include "ndt_d2d_batch_host.inc.h"
 #include "ndt_pyramid_host.inc.h"
-#include "ndt_d2d_pyramid_host.inc.h"
+#include "ndt_d2d_host.inc.h"
 #include "ndt_pyramid_batch_host.inc.h"
 #include "ukf_host.inc.h"
 

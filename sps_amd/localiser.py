@@ -937,9 +937,7 @@ class NDTLocaliser(ScanToMapLocaliser):
                 self.ctx.bbs_map_build(g0.data_ptr(), self._global["W"], self._global["H"], self._global["levels"],
                                        self.stream.cuda_stream)
                 self._bbs_scratch, self._bbs_shape = None, None
-            self._batch_scratch, self._batch_hyp = None, 0
-            self._pyr_batch_scratch, self._pyr_batch_hyp = None, 0
-            self._score_scratch, self._score_poses = None, 0
+            self._grown = {}                                         # the scratch of the calls with K or P poses: _scratch_for
             if self.source == "cells":                               # the scan's cells, their counts, (cells, valid cells)
                 self._src = torch.empty((self.capacity, _native.NDT_SRC_REC), dtype=torch.float64, device=self.device)
                 self._src_count = torch.empty(self.capacity, dtype=torch.int32, device=self.device)
@@ -948,8 +946,6 @@ class NDTLocaliser(ScanToMapLocaliser):
                                                 device=self.device)
                 self._d2d_scratch = torch.empty(_native.lib.sps_ndt_align_d2d_scratch(self.capacity), dtype=torch.uint8,
                                                 device=self.device)
-                self._d2d_batch_scratch, self._d2d_batch_hyp = None, 0   # those of the d2d=True calls, grown on demand
-                self._d2d_score_scratch, self._d2d_score_poses = None, 0
             if self.source_resolutions is not None:                  # the same per level of the pyramid of source cells
                 L = len(self.source_resolutions)
                 self._src_lv = torch.empty((L, self.capacity, _native.NDT_SRC_REC), dtype=torch.float64, device=self.device)
@@ -1262,29 +1258,39 @@ class NDTLocaliser(ScanToMapLocaliser):
                 raise ValueError(f"level_capacities[{l}] = {c} is below the {n} cells of the map at {r} m")
         return caps
 
+    def _scan(self, n_ptr, cells, levels=False):
+        """What a call registers, chosen once: the thinned points in self._pts (their count at n_ptr) or, ``cells``, the
+        source cells that the caller has built (``levels``: those of every level of ``source_resolutions``) -> (array,
+        count pointer); ``d2d=cells`` picks the entry point of ``_native.Context``"""
+        if not cells:
+            return self._pts.data_ptr(), n_ptr
+        src, n_src = (self._src_lv, self._n_src_lv) if levels else (self._src, self._n_src)
+        return src.data_ptr(), n_src.data_ptr()
+
+    def _scratch_for(self, scratch_fn, size):
+        """the scratch that ``scratch_fn`` of the library sizes for ``size`` hypotheses or poses: one buffer per function
+        (by its name: ctypes function pointers do not hash), which grows with the largest size seen (stream-ordered reuse)"""
+        buf, seen = self._grown.get(scratch_fn.__name__, (None, 0))
+        if size > seen:
+            buf = torch.empty(scratch_fn(self.capacity, size), dtype=torch.uint8, device=self.device)
+            self._grown[scratch_fn.__name__] = (buf, size)
+        return buf
+
     def _align(self, n_ptr, T, K, T_out_ptr, status_ptr, trace_ptr, normal_ptr, s, level_ptr=None):
-        if self.source_resolutions is not None:                      # the scan's cells at every level against the pyramid
+        cells, pyramid = self.source == "cells", self.resolutions is not None
+        if cells:                                                    # at every level where the pyramid registers them
+            (self._build_level_sources if pyramid else self._build_sources)(n_ptr, s)
+        elems, count = self._scan(n_ptr, cells, pyramid)
+        if pyramid:
             caps = self.level_iterations or (max(K, 1),) * len(self.resolutions)
-            self._build_level_sources(n_ptr, s)
-            self.ctx.ndt_pyramid_align_d2d(self._src_lv.data_ptr(), self._n_src_lv.data_ptr(), self.capacity, T, K, caps,
-                                           self.neighbours, self.min_correspondences, self.tol_t, self.tol_r, T_out_ptr,
-                                           status_ptr, trace_ptr, normal_ptr, level_ptr, self._d2d_pyr_scratch.data_ptr(), s)
+            scratch = self._d2d_pyr_scratch if cells else self._pyr_scratch
+            self.ctx.ndt_pyramid_align(elems, count, self.capacity, T, K, caps, self.neighbours, self.min_correspondences,
+                                       self.tol_t, self.tol_r, T_out_ptr, status_ptr, trace_ptr, normal_ptr, level_ptr,
+                                       scratch.data_ptr(), s, d2d=cells)
             return
-        if self.resolutions is not None:
-            caps = self.level_iterations or (max(K, 1),) * len(self.resolutions)
-            self.ctx.ndt_pyramid_align(self._pts.data_ptr(), n_ptr, self.capacity, T, K, caps, self.neighbours,
-                                       self.min_correspondences, self.tol_t, self.tol_r, T_out_ptr, status_ptr, trace_ptr,
-                                       normal_ptr, level_ptr, self._pyr_scratch.data_ptr(), s)
-            return
-        if self.source == "cells":
-            self._build_sources(n_ptr, s)
-            self.ctx.ndt_align_d2d(self._src.data_ptr(), self._n_src.data_ptr(), self.capacity, T, K, self.neighbours,
-                                   self.min_correspondences, self.outlier_ratio, self.tol_t, self.tol_r, T_out_ptr, status_ptr,
-                                   trace_ptr, normal_ptr, self._d2d_scratch.data_ptr(), s)
-            return
-        self.ctx.ndt_align(self._pts.data_ptr(), n_ptr, self.capacity, T, K, self.neighbours, self.min_correspondences,
-                           self.outlier_ratio, self.tol_t, self.tol_r, T_out_ptr, status_ptr, trace_ptr, normal_ptr,
-                           self._align_scratch.data_ptr(), s)
+        scratch = self._d2d_scratch if cells else self._align_scratch
+        self.ctx.ndt_align(elems, count, self.capacity, T, K, self.neighbours, self.min_correspondences, self.outlier_ratio,
+                           self.tol_t, self.tol_r, T_out_ptr, status_ptr, trace_ptr, normal_ptr, scratch.data_ptr(), s, d2d=cells)
 
     def _build_sources(self, n_ptr, s):
         """the cells of the thinned points in self._pts (their count at n_ptr) into self._src, on stream s"""
@@ -1511,18 +1517,15 @@ class NDTLocaliser(ScanToMapLocaliser):
                                              self.min_correspondences, self.tol_t, self.tol_r, base + o["T_out"] * 8,
                                              base + o["status"] * 8, trace_ptr, normal_ptr, base + o["levels"] * 8 if I else None,
                                              base + o["final"] * 8, base + o["best"] * 8, base + o["T_best"] * 8,
-                                             self._pyr_batch_scratch_for(K).data_ptr(), s)
-        elif d2d:
-            self.ctx.ndt_align_d2d_batch(self._src.data_ptr(), self._n_src.data_ptr(), self.capacity, T_ptr, K, I, self.neighbours,
-                                         self.min_correspondences, self.outlier_ratio, self.tol_t, self.tol_r,
-                                         base + o["T_out"] * 8, base + o["status"] * 8, trace_ptr, normal_ptr,
-                                         base + o["final"] * 8, base + o["best"] * 8, base + o["T_best"] * 8,
-                                         self._d2d_batch_scratch_for(K).data_ptr(), s)
+                                             self._scratch_for(_native.lib.sps_ndt_pyramid_align_batch_scratch, K).data_ptr(), s)
         else:
-            self.ctx.ndt_align_batch(self._pts.data_ptr(), n_ptr, self.capacity, T_ptr, K, I, self.neighbours,
-                                     self.min_correspondences, self.outlier_ratio, self.tol_t, self.tol_r, base + o["T_out"] * 8,
-                                     base + o["status"] * 8, trace_ptr, normal_ptr, base + o["final"] * 8,
-                                     base + o["best"] * 8, base + o["T_best"] * 8, self._batch_scratch_for(K).data_ptr(), s)
+            elems, count = self._scan(n_ptr, d2d)
+            lib = _native.lib
+            scratch = self._scratch_for(lib.sps_ndt_align_d2d_batch_scratch if d2d else lib.sps_ndt_align_batch_scratch, K)
+            self.ctx.ndt_align_batch(elems, count, self.capacity, T_ptr, K, I, self.neighbours, self.min_correspondences,
+                                     self.outlier_ratio, self.tol_t, self.tol_r, base + o["T_out"] * 8, base + o["status"] * 8,
+                                     trace_ptr, normal_ptr, base + o["final"] * 8, base + o["best"] * 8,
+                                     base + o["T_best"] * 8, scratch.data_ptr(), s, d2d=d2d)
         T_best, gate_ptr = (base + b for b in o["hands_on"])
         if self._match_opts is not None:                             # its verdict is the gate of what follows
             self._status(n_ptr, T_best, base + o["best"] * 8 + 4, base + o["match"] * 8, s)
@@ -1531,20 +1534,6 @@ class NDTLocaliser(ScanToMapLocaliser):
         if integrate:
             self._update(n_ptr, None, T_best, gate_ptr, max_cell_points, base + o["update"] * 8, s)
 
-    def _batch_scratch_for(self, K):
-        if K > self._batch_hyp:                                      # grows with the largest batch seen (stream-ordered reuse)
-            self._batch_scratch = torch.empty(_native.lib.sps_ndt_align_batch_scratch(self.capacity, K), dtype=torch.uint8,
-                                              device=self.device)
-            self._batch_hyp = K
-        return self._batch_scratch
-
-    def _d2d_batch_scratch_for(self, K):
-        if K > self._d2d_batch_hyp:                                  # grows with the largest batch seen (stream-ordered reuse)
-            self._d2d_batch_scratch = torch.empty(_native.lib.sps_ndt_align_d2d_batch_scratch(self.capacity, K),
-                                                  dtype=torch.uint8, device=self.device)
-            self._d2d_batch_hyp = K
-        return self._d2d_batch_scratch
-
     def _sources_for_batch(self, out, n_ptr, n_points_at, s):
         """``_build_sources`` for a d2d=True call, and the count of valid source cells into the pad behind the n_points
         word (double ``n_points_at`` of ``out``)"""
@@ -1552,30 +1541,13 @@ class NDTLocaliser(ScanToMapLocaliser):
         at = 2 * n_points_at + 1
         out.view(torch.int32)[at:at + 1].copy_(self._n_src[1:2])
 
-    def _pyr_batch_scratch_for(self, K):
-        if K > self._pyr_batch_hyp:                                  # grows with the largest batch seen (stream-ordered reuse)
-            self._pyr_batch_scratch = torch.empty(_native.lib.sps_ndt_pyramid_align_batch_scratch(self.capacity, K),
-                                                  dtype=torch.uint8, device=self.device)
-            self._pyr_batch_hyp = K
-        return self._pyr_batch_scratch
-
     def _score(self, T_dev, P, n_points_ptr, score_ptr, s, d2d=False):
         """the scores of the P poses of T_dev for the thinned points in self._pts (their count at n_points_ptr) or, ``d2d``,
         for the source cells in self._src, which the caller has built"""
-        if d2d:
-            if P > self._d2d_score_poses:                            # grows with the largest grid seen (stream-ordered reuse)
-                self._d2d_score_scratch = torch.empty(_native.lib.sps_ndt_score_d2d_scratch(self.capacity, P), dtype=torch.uint8,
-                                                      device=self.device)
-                self._d2d_score_poses = P
-            self.ctx.ndt_score_poses_d2d(self._src.data_ptr(), self._n_src.data_ptr(), self.capacity, T_dev.data_ptr(), P,
-                                         self.neighbours, self.outlier_ratio, score_ptr, self._d2d_score_scratch.data_ptr(), s)
-            return
-        if P > self._score_poses:                                    # grows with the largest grid seen (stream-ordered reuse)
-            self._score_scratch = torch.empty(_native.lib.sps_ndt_score_scratch(self.capacity, P), dtype=torch.uint8,
-                                              device=self.device)
-            self._score_poses = P
-        self.ctx.ndt_score_poses(self._pts.data_ptr(), n_points_ptr, self.capacity, T_dev.data_ptr(), P, self.neighbours,
-                                 self.outlier_ratio, score_ptr, self._score_scratch.data_ptr(), s)
+        elems, count = self._scan(n_points_ptr, d2d)
+        scratch = self._scratch_for(_native.lib.sps_ndt_score_d2d_scratch if d2d else _native.lib.sps_ndt_score_scratch, P)
+        self.ctx.ndt_score_poses(elems, count, self.capacity, T_dev.data_ptr(), P, self.neighbours, self.outlier_ratio,
+                                 score_ptr, scratch.data_ptr(), s, d2d=d2d)
 
     @torch.no_grad()
     def score_poses(self, rows, count, poses, d2d: bool = False) -> PendingScores:

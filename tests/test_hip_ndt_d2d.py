@@ -63,7 +63,7 @@ def dev(a):
     return torch.from_numpy(np.ascontiguousarray(a)).cuda()
 
 
-def raw_build(loc, pts, n=None, cap=None, res=RES, min_points=6, eig_ratio=EIG_RATIO):
+def raw_build(loc, pts, n=None, cap=None, res=RES, min_points=6, eig_ratio=EIG_RATIO, scratch=None):
     """sps_ndt_source_build itself on float64 points: (records [cap, 10], counts [cap], n_src), the rows pre-filled"""
     from sps_amd import _native
     pts = np.asarray(pts, dtype=np.float64).reshape(-1, 3)
@@ -75,7 +75,8 @@ def raw_build(loc, pts, n=None, cap=None, res=RES, min_points=6, eig_ratio=EIG_R
     src = torch.full((max(cap, 1), 10), SENTINEL, dtype=torch.float64, device="cuda")
     cnt = torch.full((max(cap, 1),), -7, dtype=torch.int32, device="cuda")
     n_src = torch.full((2,), -7, dtype=torch.int32, device="cuda")
-    scratch = torch.empty(_native.lib.sps_ndt_source_scratch(cap), dtype=torch.uint8, device="cuda")
+    if scratch is None:
+        scratch = torch.empty(_native.lib.sps_ndt_source_scratch(cap), dtype=torch.uint8, device="cuda")
     loc.ctx.ndt_source_build(p.data_ptr(), n_dev.data_ptr(), cap, res, min_points, eig_ratio, src.data_ptr(), cnt.data_ptr(),
                              n_src.data_ptr(), scratch.data_ptr(), stream())
     out = src.cpu().numpy(), cnt.cpu().numpy(), tuple(int(v) for v in n_src.cpu().numpy())

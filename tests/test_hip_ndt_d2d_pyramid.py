@@ -187,6 +187,39 @@ def test_two_source_builds_on_one_scratch_give_the_same_bytes(pyr, scene):
     assert [tuple(v) for v in a[2]] == [s["n_src"] for s in scene["src"][3]]
 
 
+def lattice(n):
+    """n points of which three in four sit six to a 0.5 m cell, on corners 0.2 m apart inside it, and every fourth alone in a
+    2 m cell of its own: cells of several points and of one at every resolution of RESOLUTIONS"""
+    i = np.arange(n)
+    g, c = i // 8, i % 8
+    dense = np.stack([0.5 * g + 0.1 + 0.2 * (c & 1), 0.1 + 0.2 * ((c >> 1) & 1), 0.1 + 0.2 * ((c >> 2) & 1)], axis=1)
+    lone = np.stack([-3.0 - 2.0 * i, np.full(n, 0.3), np.full(n, 0.3)], axis=1)
+    return np.where((i % 4 == 3)[:, None], lone, dense).reshape(-1, 3)
+
+
+@pytest.mark.parametrize("n", [0, 1, 33, 257])
+def test_the_single_build_and_the_pyramid_of_sources_share_a_scratch(pyr, n):
+    """The single source build and the pyramid of sources cut their arrays from one layout function: on one scratch, sized
+    for three levels and filled with 0xA5, a single build, a three-level build and the single build again.  The strides of the two layouts differ and no byte
+    left by one may reach the other: the single build's bytes are the same before and after, and every level is the single
+    build at that level's resolution and min_points on a scratch of its own.  cap 257: one and two workgroups of 256 points,
+    one and two of the 32-element rows."""
+    from sps_amd import _native
+    cap, pts, (res, mps) = 257, lattice(n), LEVELS[3]
+    scratch = torch.full((_native.lib.sps_ndt_pyramid_source_scratch(cap, 3),), 0xA5, dtype=torch.uint8, device="cuda")
+    before = raw_build(pyr, pts, cap=cap, res=1.0, min_points=3, scratch=scratch)
+    rec, cnt, n_src = raw_build_levels(pyr, pts, res, mps, cap=cap, scratch=scratch)
+    after = raw_build(pyr, pts, cap=cap, res=1.0, min_points=3, scratch=scratch)
+    assert before[0].tobytes() == after[0].tobytes() and before[1].tobytes() == after[1].tobytes() and before[2] == after[2]
+    for l, (r, m) in enumerate(zip(res, mps)):
+        one = raw_build(pyr, pts, cap=cap, res=r, min_points=m)
+        assert rec[l].tobytes() == one[0].tobytes() and cnt[l].tobytes() == one[1].tobytes(), l
+        assert tuple(int(v) for v in n_src[l]) == one[2], l
+    if n >= 33:                                                         # cells of several points and cells of one, some valid
+        c = before[1][:before[2][0]]
+        assert (c == 1).any() and (c > 1).any() and 0 < before[2][1] < before[2][0]
+
+
 def test_source_cells_shows_every_level(pyr, singles, scene):
     scan = dev(scene["scan"])
     for l, one in enumerate(singles[3]):

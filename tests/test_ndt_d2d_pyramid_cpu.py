@@ -228,6 +228,15 @@ def test_the_binding_knows_the_d2d_pyramid_entry_points():
     assert _native.lib.sps_ndt_pyramid_align_d2d_scratch(-1) == -1
 
 
+def test_the_single_source_scratch_is_the_pyramid_s_for_one_level():
+    """one level of the pyramid of sources is the single build's layout, so the two size the same scratch"""
+    from sps_amd import _native
+    for cap in (0, 1, 255, 256, 257, 65536):
+        assert _native.lib.sps_ndt_source_scratch(cap) == _native.lib.sps_ndt_pyramid_source_scratch(cap, 1) > 0
+    for cap in (-1, 65537):
+        assert _native.lib.sps_ndt_source_scratch(cap) == _native.lib.sps_ndt_pyramid_source_scratch(cap, 1) == -1
+
+
 def test_the_drivers_list_the_source_pyramid_options():
     for script in (("scripts", "filter_sequence.py"), ("tools", "localiser_timing.py")):
         r = subprocess.run([sys.executable, os.path.join(ROOT, *script), "--help"], capture_output=True, text=True, cwd=ROOT)

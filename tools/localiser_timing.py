@@ -48,7 +48,8 @@ without an estimator, with one on the device path and with one on the host path,
 
 ``--localiser ndt --source cells`` times distribution-to-distribution registration (NDTLocaliser(..., source="cells")):
 per frame the hipEvent time around submit(), the iterations, the scan's valid source cells and the error against the true
-pose, beside the point path on the same frames, the two alternating frame by frame in one run; then the loop with each.
+pose, beside the point path on the same frames, the two alternating frame by frame in one run; then the source build alone
+and the loop with each.
 
 ``--localiser ndt --source cells --resolutions 2,1,0.5 --source-resolutions 2,1,0.5`` times the coarse-to-fine registration
 of the scan's cells (NDTLocaliser(..., source_resolutions=...)) beside the single cells localiser and the
@@ -532,7 +533,8 @@ def ndt_main(a, scans, dscans, mp, T_init):
 def ndt_d2d_main(a, scans, dscans, mp, T_init):
     """--source cells: the distribution-to-distribution localiser and the point one on the same frames, alternating frame
     by frame within one run.  Per frame: hipEvent time around submit(), iterations, valid source cells, the error against
-    the true pose.  Then LocalisationLoop(SPSCVMFilter, .) with each (host wall clock)."""
+    the true pose.  Then the hipEvent time around the source build alone, and LocalisationLoop(SPSCVMFilter, .) with each
+    localiser (host wall clock)."""
     map64 = mp[:, :3].astype(np.float64)
     kw = dict(source="cells", source_resolution=a.source_resolution, source_min_points=a.source_min_points)
     locs = {"points": NDTLocaliser(map64), "cells": NDTLocaliser(map64, **kw)}
@@ -575,6 +577,22 @@ def ndt_d2d_main(a, scans, dscans, mp, T_init):
         print(f"{name}  median {med:.3f} ms (min {min(ms):.3f} max {max(ms):.3f}) per frame, iterations median {it:.0f}, "
               f"{out[name]['ms_per_iteration']:.4f} ms per iteration, {out[name]['n_sources']} sources, error median "
               f"{out[name]['median_error_m']:.4f} m max {out[name]['max_error_m']:.4f} m", flush=True)
+    # the source build alone: the four memsets and seven launches of one scan's cells, on the thinned points of frame 0
+    loc, s = locs["cells"], dscans[0]
+    n_pts = torch.zeros(2, dtype=torch.int32, device=loc.device)
+    loc._thin(s[:, :3].to(torch.float32).contiguous(), torch.full((1,), len(s), dtype=torch.int32, device=loc.device), len(s),
+              n_pts.data_ptr(), st.cuda_stream)
+    t_src = []
+    for k in range(a.warmup + a.frames):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(st)
+        loc._build_sources(n_pts.data_ptr(), st.cuda_stream)
+        e1.record(st)
+        e1.synchronize()
+        if k >= a.warmup:
+            t_src.append(e0.elapsed_time(e1))
+    out["source_build_ms"] = {"median": round(float(np.median(t_src)), 4), "min": round(min(t_src), 4), "max": round(max(t_src), 4)}
+    print(f"source build alone: median {out['source_build_ms']['median']:.4f} ms (min {min(t_src):.4f} max {max(t_src):.4f})", flush=True)
     net = net_from_params(O.random_params(seed=0)).cuda().eval().freeze()
     mpt = torch.from_numpy(mp)
     for name, loc in locs.items():

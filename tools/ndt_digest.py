@@ -61,6 +61,11 @@ class KeptFrame:
         return self
 
 
+def source_arrays(cells):
+    """the arrays of NDTLocaliser.source_cells in a fixed order"""
+    return [cells[k] for k in ("mean", "cov", "count", "valid")]
+
+
 def loops(ndt, T_init):
     """the stacked poses of 8 steps in four set-ups, with the rows on the device and fetched"""
     scans = [torch.from_numpy(synthetic.lidar_scan(seed=40 + k, **SIZE)).cuda() for k in range(8)]
@@ -129,10 +134,29 @@ def main():
         digest(name, pend._host.numpy())
     for l in range(3):
         digest(f"online pyramid level {l}", *online.pyramid_cells(l), *online.carve_state(l))
-    pend = NDTLocaliser(map64, leaf=LEAF, source="cells").submit(scan, n, T_init, with_normal=True)
+    cells = NDTLocaliser(map64, leaf=LEAF, source="cells")
+    pend = cells.submit(scan, n, T_init, with_normal=True)
     r = pend.result()
     digest("cells submit with_normal", pend._host.numpy())
     print(f"# source cells: {r.n_sources} valid, status {r.status} after {r.iterations}", flush=True)
+    pend = cells.submit_batch(scan, n, hypothesis_starts(T_init, 5), d2d=True)
+    pend.result()
+    digest("cells submit_batch K=5", pend._host.numpy())
+    pend = cells.score_poses(scan, n, search_poses(T_init, 75), d2d=True)
+    pend.result()
+    digest("cells score_poses P=75", pend._host.numpy())
+    pend = cells.relocalise(scan, n, search_poses(T_init, 75), keep=4, d2d=True)
+    pend.result()
+    digest("cells relocalise keep=4", pend._batch._host.numpy())
+    digest("source_cells", *source_arrays(cells.source_cells(scan, n)))
+    cpyr = NDTLocaliser(map64, leaf=LEAF, resolutions=(2.0, 1.0, 0.5), source="cells", source_resolutions=(2.0, 1.0, 0.5),
+                        source_min_points=6, iterations=90, level_iterations=(30, 30, 30))
+    pend = cpyr.submit(scan, n, T_init, with_normal=True)
+    r = pend.result()
+    digest("cells pyramid submit", pend._host.numpy())
+    print(f"# cells pyramid: status {r.status} after {r.iterations}", flush=True)
+    for l in range(3):
+        digest(f"source_cells level {l}", *source_arrays(cpyr.source_cells(scan, n, level=l)))
     pend = static.submit_from_device(scan, n, torch.from_numpy(np.ascontiguousarray(T_init)).cuda())
     pend.result()
     digest("submit_from_device", pend._host.numpy())
