@@ -622,9 +622,11 @@ struct PxOperands {  // gathered rows + weight fragments of a group of G chunks
 };
 // UP: the transposed convolution that follows the layer (C_out = 16 -> <= 16 channels, block7.conv2 -> convtr7p2s2) runs in
 // the epilogue on the supertile's 64 finished rows, which stay in the first accumulator (see the epilogue).
-template <int NW, int CIN, bool C8, bool DS, bool FIN, int MINW, bool UP = false, bool HALF = false>
+// DEPTH: chunks whose operand loads a wave has in flight while it multiplies one (1..3; DEPTH + 1 register sets rotate).
+template <int NW, int CIN, bool C8, bool DS, bool FIN, int MINW, bool UP = false, bool HALF = false, int DEPTH = 1>
 __global__ __launch_bounds__(NW * 64, MINW) void k_conv_px(ConvArgs a) {
   static_assert(!HALF || C8, "two offsets per chunk: the 8 output channels of each fill half of the MFMA rows");
+  static_assert(DEPTH >= 1 && DEPTH <= 3, "a chunk issued ahead lies in this block or the next: at most three ahead");
   static_assert(!UP || (!C8 && !FIN && NW == 4), "fused transposed convolution: 16-channel rows, four waves");
   constexpr int AST = (C8 && !HALF) ? 12 : 20;  // floats per accumulator row: 16-byte aligned, strides 48 / 80 B spread the banks
   // + dummy slots (PAD entries; C_out <= 8: also the lane groups 2, 3 that hold the zero-padded channels 8..15).  C8: one
@@ -718,6 +720,42 @@ __global__ __launch_bounds__(NW * 64, MINW) void k_conv_px(ConvArgs a) {
         __builtin_amdgcn_make_buffer_rsrc((void *)(a.rb_e + (size_t)st * (PX_CH_MAX * 16)), 0, PX_CH_MAX * 64, 0x00020000);
     const __amdgpu_buffer_rsrc_t rsK =
         __builtin_amdgcn_make_buffer_rsrc((void *)(a.rb_k + (size_t)st * PX_KSTRIDE), 0, PX_KSTRIDE, 0x00020000);
+    // ---- chunks in BLOCKS of four consecutive chunks; block b goes to wave b % NW.  One 4-byte load per lane fetches the
+    // rulebook words of a whole block (lane group j = chunk j of the block) and one byte load per chunk its offset; the words
+    // of chunk j reach all lane groups through ds_bpermute.  Software pipeline: the words of the next block and the operand
+    // loads of the next chunk are in flight while the MFMAs and the accumulator update of the current chunk run.
+    // Everything past the end of the list is an out-of-range load (zeros) / a PAD slot.
+    const int nblk = (nch + 3) >> 2;
+    const int nbw = nblk > wave ? (nblk - wave + NW - 1) / NW : 0;  // blocks of this wave
+    // fetch() only issues the two loads of block t, arrived() turns what they returned into the block's words when the block
+    // moves up, a block's time later.  Chunks past the end of the list become padding there (decided once per block, not per
+    // chunk): an out-of-range load returns zero and the padding values are OR-ed in.  (Written as `on ? loaded : PAD` right
+    // behind the loads, the loads sank into an exec-masked block with a wait of its own, the words were due at the loop's
+    // latch, and the vmcnt(0) there drained the operand loads in flight once per block.)
+    auto fetch = [&](uint32_t &ev, uint32_t &kv, int t) {
+      const int c = 4 * (wave + NW * t) + q;  // this lane group's chunk
+      const int seg = c < n0 ? 0 : (c < n01 ? 1 : 2);
+      const int lc = c - (c < n0 ? 0 : (c < n01 ? n0 : n01));  // chunk inside its segment
+      const bool on = t < nbw && c < nch;
+      ev = __builtin_amdgcn_raw_buffer_load_b32(rsE, on ? (uint32_t)((seg * PX_SEG_CH + lc) * 16 + n) * 4u : OOR, 0, 0);
+      if constexpr (HALF) {
+        // every lane fetches the offset byte of ITS half (n < 8: first, n >= 8: second) of its lane group's chunk: the byte
+        // offset of the weights then travels with the rulebook word, through the same ds_bpermute pattern (issue())
+        kv = (uint32_t)__builtin_amdgcn_raw_buffer_load_b8(rsK, on ? (uint32_t)(seg * PX_KSEG + 2 * lc + (n >> 3)) : OOR, 0, 0);
+        return;
+      }
+      const int ck = 4 * (wave + NW * t) + lane;  // lanes 0..3: the block's four offset bytes
+      const int segk = ck < n0 ? 0 : (ck < n01 ? 1 : 2);
+      const int lck = ck - (ck < n0 ? 0 : (ck < n01 ? n0 : n01));
+      const bool onk = lane < 4 && t < nbw && ck < nch;
+      kv = (uint32_t)__builtin_amdgcn_raw_buffer_load_b8(rsK, onk ? (uint32_t)(segk * PX_KSEG + lck) : OOR, 0, 0);
+    };
+    auto arrived = [&](uint32_t &ev, uint32_t &kv, uint32_t evl, uint32_t kvl, int t) {
+      const bool on = t < nbw && 4 * (wave + NW * t) + q < nch;
+      const bool onk = HALF ? on : (lane < 4 && t < nbw && 4 * (wave + NW * t) + lane < nch);
+      ev = evl | (on ? 0u : PX_PAD);
+      kv = kvl * kwbytes | (onk ? 0u : 0x80000000u);  // byte offset of the chunk's weights (out of range for a chunk that is not there)
+    };
     // ---- zero this wave's accumulator (rows 0..63 + dummy)
     for (int i = lane; i < ACCN / 4; i += 64) reinterpret_cast<floatx4 *>(acc)[i] = floatx4{0.f, 0.f, 0.f, 0.f};
     __builtin_amdgcn_wave_barrier();
@@ -744,36 +782,7 @@ __global__ __launch_bounds__(NW * 64, MINW) void k_conv_px(ConvArgs a) {
     PX_STAMP(2);
     PX_STAMP(3);
 
-    // ---- chunks in BLOCKS of four consecutive chunks; block b goes to wave b % NW.  One 4-byte load per lane fetches the
-    // rulebook words of a whole block (lane group j = chunk j of the block) and one byte load per chunk its offset; the words
-    // of chunk j reach all lane groups through ds_bpermute.  Software pipeline: the words of the next block and the operand
-    // loads of the next chunk are in flight while the MFMAs and the accumulator update of the current chunk run.
-    // Everything past the end of the list is an out-of-range load (zeros) / a PAD slot.
-    const int nblk = (nch + 3) >> 2;
-    const int nbw = nblk > wave ? (nblk - wave + NW - 1) / NW : 0;  // blocks of this wave
-    auto fetch = [&](uint32_t &ev, uint32_t &kv, int t) {
-      const int c = 4 * (wave + NW * t) + q;  // this lane group's chunk
-      const int seg = c < n0 ? 0 : (c < n01 ? 1 : 2);
-      const int lc = c - (c < n0 ? 0 : (c < n01 ? n0 : n01));  // chunk inside its segment
-      const bool on = t < nbw && c < nch;
-      ev = __builtin_amdgcn_raw_buffer_load_b32(rsE, on ? (uint32_t)((seg * PX_SEG_CH + lc) * 16 + n) * 4u : OOR, 0, 0);
-      ev = on ? ev : PX_PAD;  // chunks past the end of the list: padding (decided once per block, not per chunk)
-      if constexpr (HALF) {
-        // every lane fetches the offset byte of ITS half (n < 8: first, n >= 8: second) of its lane group's chunk: the byte
-        // offset of the weights then travels with the rulebook word, through the same ds_bpermute pattern (issue())
-        kv = (uint32_t)__builtin_amdgcn_raw_buffer_load_b8(rsK, on ? (uint32_t)(seg * PX_KSEG + 2 * lc + (n >> 3)) : OOR, 0, 0);
-        kv = on ? kv * kwbytes : 0x80000000u;
-        return;
-      }
-      const int ck = 4 * (wave + NW * t) + lane;  // lanes 0..3: the block's four offset bytes
-      const int segk = ck < n0 ? 0 : (ck < n01 ? 1 : 2);
-      const int lck = ck - (ck < n0 ? 0 : (ck < n01 ? n0 : n01));
-      const bool onk = lane < 4 && t < nbw && ck < nch;
-      kv = (uint32_t)__builtin_amdgcn_raw_buffer_load_b8(rsK, onk ? (uint32_t)(segk * PX_KSEG + lck) : OOR, 0, 0);
-      kv = onk ? kv * kwbytes : 0x80000000u;  // byte offset of the chunk's weights (out of range for a chunk that is not there)
-    };
-    auto issue = [&](PxOperands<1> &r, uint32_t ev, uint32_t kv, int t, int j) {
-      (void)t;
+    auto issue = [&](PxOperands<1> &r, uint32_t ev, uint32_t kv, int j) {
       // no test for padding or for "is there a chunk": a PAD entry's row 2^23 is out of range by construction (zeros), its
       // accumulator row 64 is the dummy, and fetch() turned chunks past the end into PAD entries / out-of-range weights
       r.e[0] = (uint32_t)__shfl((int)ev, 16 * j + n, 64);
@@ -827,22 +836,56 @@ __global__ __launch_bounds__(NW * 64, MINW) void k_conv_px(ConvArgs a) {
       *ap = cur + d;
     };
     if (nbw > 0) {
+      // DEPTH chunks ahead: the wave's chunks, numbered along its list, rotate through NS = DEPTH + 1 operand sets -- chunk i
+      // lives in set i % NS, and while it is multiplied chunk i + DEPTH goes out into the set that chunk i - 1 left.  The
+      // sets are four NAMED structs picked at compile time (an indexed array would live in scratch), so the loop body is
+      // unrolled until the set of a block's first chunk repeats: one block for NS = 2, 4, three blocks for NS = 3 -- with an
+      // exit after every block, so that a wave runs exactly its nbw blocks whatever nbw % 3 is (exits are no merge points:
+      // the waits inside the body stay counted).  Chunk order and accumulation order are those of DEPTH = 1.
+      constexpr int NS = DEPTH + 1, NBU = NS == 3 ? 3 : 1;
       uint32_t ev0, kv0, ev1, kv1;
-      PxOperands<1> r0, r1;
+      PxOperands<1> rs0, rs1, rs2, rs3;
+      auto set = [&](auto I) -> PxOperands<1> & {
+        constexpr int i = decltype(I)::value;
+        if constexpr (i == 0) return rs0;
+        else if constexpr (i == 1) return rs1;
+        else if constexpr (i == 2) return rs2;
+        else return rs3;
+      };
+      // chunk pj of the unrolled body (chunk j = pj % 4 of block t): issue chunk pj + DEPTH, multiply chunk pj.  (ev0, kv0)
+      // hold the words of block t until its last chunk has been issued (step j = 3 - DEPTH); the step after that begins by
+      // moving block t + 1 up from (ev1, kv1), as loaded four steps earlier, and fetching block t + 2 -- at every DEPTH
+      auto step = [&](auto PJ, int t) {
+        constexpr int pj = decltype(PJ)::value, j = pj & 3;
+        if constexpr (j == 4 - DEPTH) {
+          arrived(ev0, kv0, ev1, kv1, t + 1);
+          fetch(ev1, kv1, t + 2);
+        }
+        issue(set(std::integral_constant<int, (pj + DEPTH) % NS>{}), ev0, kv0, (j + DEPTH) & 3);
+        compute(set(std::integral_constant<int, pj % NS>{}));
+      };
+      auto block = [&](auto P, int t) {
+        constexpr int p4 = 4 * decltype(P)::value;
+        step(std::integral_constant<int, p4>{}, t);
+        step(std::integral_constant<int, p4 + 1>{}, t);
+        step(std::integral_constant<int, p4 + 2>{}, t);
+        step(std::integral_constant<int, p4 + 3>{}, t);
+      };
       fetch(ev0, kv0, 0);
       fetch(ev1, kv1, 1);
-      issue(r0, ev0, kv0, 0, 0);
-      for (int t = 0; t < nbw; ++t) {  // block t in (ev0, kv0), block t + 1 in (ev1, kv1); chunk (t, 0) already issued into r0
-        issue(r1, ev0, kv0, t, 1);
-        compute(r0);
-        issue(r0, ev0, kv0, t, 2);
-        compute(r1);
-        issue(r1, ev0, kv0, t, 3);
-        compute(r0);
-        issue(r0, ev1, kv1, t + 1, 0);
-        compute(r1);
-        ev0 = ev1, kv0 = kv1;
-        fetch(ev1, kv1, t + 2);
+      arrived(ev0, kv0, ev0, kv0, 0);
+      issue(rs0, ev0, kv0, 0);
+      if constexpr (DEPTH >= 2) issue(rs1, ev0, kv0, 1);
+      if constexpr (DEPTH >= 3) issue(rs2, ev0, kv0, 2);
+      for (int t = 0;;) {  // chunks (t, 0) .. (t, DEPTH - 1) are in flight
+        block(std::integral_constant<int, 0>{}, t);
+        if (++t >= nbw) break;
+        if constexpr (NBU == 3) {
+          block(std::integral_constant<int, 1>{}, t);
+          if (++t >= nbw) break;
+          block(std::integral_constant<int, 2>{}, t);
+          if (++t >= nbw) break;
+        }
       }
     }
     PX_STAMP(4);
@@ -907,6 +950,7 @@ __global__ __launch_bounds__(NW * 64, MINW) void k_conv_px(ConvArgs a) {
       const __amdgpu_buffer_rsrc_t rsU = __builtin_amdgcn_make_buffer_rsrc((void *)a.up_Wu, 0, (int)a.up_wu_bytes, 0x00020000);
       const float usc = n < a.up_cout ? a.up_scale[n] : 0.f, ush = n < a.up_cout ? a.up_shift[n] : 0.f;
       const __amdgpu_buffer_rsrc_t rsUm = __builtin_amdgcn_make_buffer_rsrc((void *)a.up_tmask, 0, (int)0xFFFFFFFEu, 0x00020000);
+      const __amdgpu_buffer_rsrc_t rsD = __builtin_amdgcn_make_buffer_rsrc((void *)a.up_down, 0, (int)0xFFFFFFFEu, 0x00020000);
       uint32_t om[4];
       // ONE load: lane group q fetches the mask of tile q, the four words are then read from lanes 0 / 16 / 32 / 48 (four
       // conditional loads were four dependent round trips; four wave-uniform loads are too: the compiler moves each through
@@ -919,13 +963,20 @@ __global__ __launch_bounds__(NW * 64, MINW) void k_conv_px(ConvArgs a) {
         const int k = 2 * wave + kk;
         if (!(((om[0] | om[1] | om[2] | om[3]) >> k) & 1u)) continue;  // wave-uniform
         const u32x4 vb = __builtin_amdgcn_raw_buffer_load_b128(rsU, (uint32_t)(k * 4 + q) * 256u + (uint32_t)n * 16u, 0, 0);
+        // the child rows of the octant's four tiles go out with the weights, one round trip for the five loads (a load per
+        // tile inside the loop below is a round trip per tile); a tile without a child at this octant asks out of range.
+        // Byte offsets: 8 octants x <= 2^23 rows x 4 bytes
+        u32x4 cvt[4];
+#pragma unroll
+        for (int t = 0; t < 4; ++t)
+          cvt[t] = __builtin_amdgcn_raw_buffer_load_b128(
+              rsD, ((om[t] >> k) & 1u) ? ((uint32_t)k * (uint32_t)a.up_ldn + (uint32_t)(row0 + 16 * t + q * 4)) * 4u : 0xFFFFFFFFu, 0, 0);
 #pragma unroll
         for (int t = 0; t < 4; ++t) {
           if (!((om[t] >> k) & 1u)) continue;  // no row of this tile has a child at octant k (wave-uniform)
           int child[4];
           {
-            const int4 cv4 = *reinterpret_cast<const int4 *>(a.up_down + (size_t)k * a.up_ldn + row0 + 16 * t + q * 4);  // (one load: see k_upconv)
-            const int cv[4] = {cv4.x, cv4.y, cv4.z, cv4.w};
+            const int cv[4] = {(int)cvt[t].x, (int)cvt[t].y, (int)cvt[t].z, (int)cvt[t].w};
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
               const int ro = row0 + 16 * t + q * 4 + i;

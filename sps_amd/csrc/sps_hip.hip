@@ -137,6 +137,32 @@ int fail(int code, const char *fmt, ...) {
 #ifndef SPS_PX_DEFAULT
 #define SPS_PX_DEFAULT 3
 #endif
+// chunks whose operand loads a wave keeps in flight (k_conv_px<..., DEPTH>), per launch of the forward; every other
+// instantiation runs at depth 1
+#ifndef SPS_PXD_B1
+#define SPS_PXD_B1 3    // block1.conv1 / conv2 (level 1, C_in = 8)
+#endif
+#ifndef SPS_PXD_B7C1
+#define SPS_PXD_B7C1 2  // block7.conv1 (level 1, C_in = 24)
+#endif
+#ifndef SPS_PXD_B7C2
+#define SPS_PXD_B7C2 2  // block7.conv2 + convtr7p2s2 (level 1, C_in = 16)
+#endif
+#ifndef SPS_PXW_B1
+#define SPS_PXW_B1 SPS_PX1_W    // min waves / SIMD of the three level-1 launches
+#endif
+#ifndef SPS_PXW_B7C1
+#define SPS_PXW_B7C1 4
+#endif
+#ifndef SPS_PXW_B7C2
+#define SPS_PXW_B7C2 4
+#endif
+#ifndef SPS_PXD_B8C1
+#define SPS_PXD_B8C1 1  // block8.conv1 (level 0, C_in = 16)
+#endif
+#ifndef SPS_PXD_B8C2
+#define SPS_PXD_B8C2 1  // block8.conv2 (+ `final`) (level 0, C_in = 8)
+#endif
 #include "keys_hash.inc.h"
 #include "grid_kernels.inc.h"
 #include "map_kernels.inc.h"
@@ -661,9 +687,9 @@ Geometry conv_geometry(int level, int K, int cin, int nt, int64_t cap = 0, bool 
   return g;
 }
 
-template <int NW, int CIN, bool C8, bool DS, bool FIN, int MINW, bool UP = false, bool HALF = false>
+template <int NW, int CIN, bool C8, bool DS, bool FIN, int MINW, bool UP = false, bool HALF = false, int DEPTH = 1>
 void launch_px(dim3 grid, hipStream_t st, const ConvArgs &a) {
-  hipLaunchKernelGGL((k_conv_px<NW, CIN, C8, DS, FIN, MINW, UP, HALF>), grid, dim3(NW * 64), 0, st, a);
+  hipLaunchKernelGGL((k_conv_px<NW, CIN, C8, DS, FIN, MINW, UP, HALF, DEPTH>), grid, dim3(NW * 64), 0, st, a);
 }
 
 // k_conv instantiation for a launch geometry (column tiles per wave x splits) -- shared by inference and training
@@ -830,28 +856,28 @@ int launch_conv_px(sps_ctx *c, const ConvSpec &cs, ConvArgs &a, int level_out, b
   static_assert(PX_HALF_LEVELS == 1, "SPS_PX_LAUNCH picks the HALF instantiations for level 0 alone");
   if (px_half_level(level_out) && cs.cout != 8)
     return fail(SPS_ERR_INVALID, "%s: C_out = %d cannot read the 8-pair rulebook of level %d", name, cs.cout, level_out);
-#define SPS_PX_LAUNCH(CIN_, C8_, DS_, FIN_)                                                                  \
+#define SPS_PX_LAUNCH(CIN_, C8_, DS_, FIN_, D0_, D1_, W1_)                                                   \
   do {                                                                                                       \
     if (level_out == 0)                                                                                      \
-      launch_px<SPS_PX0, CIN_, C8_, DS_, FIN_, SPS_PX0_W, false, C8_>(gridp, st, a);                         \
+      launch_px<SPS_PX0, CIN_, C8_, DS_, FIN_, SPS_PX0_W, false, C8_, D0_>(gridp, st, a);                    \
     else                                                                                                     \
-      launch_px<SPS_PX1, CIN_, C8_, DS_, FIN_, SPS_PX1_W>(gridp, st, a);                                     \
+      launch_px<SPS_PX1, CIN_, C8_, DS_, FIN_, W1_, false, false, D1_>(gridp, st, a);                        \
   } while (0)
   switch (key) {
-    case 800: SPS_PX_LAUNCH(8, false, false, false); break;   // block2.conv1
-    case 810: SPS_PX_LAUNCH(8, true, false, false); break;    // block1.conv1 / conv2
-    case 811: SPS_PX_LAUNCH(8, true, true, false); break;     // block8.conv2 (heads: `final` not fused)
-    case 812: SPS_PX_LAUNCH(8, true, true, true); break;      // block8.conv2 + `final`
+    case 800: SPS_PX_LAUNCH(8, false, false, false, 1, 1, SPS_PX1_W); break;   // block2.conv1
+    case 810: SPS_PX_LAUNCH(8, true, false, false, 1, SPS_PXD_B1, SPS_PXW_B1); break;   // block1.conv1 / conv2
+    case 811: SPS_PX_LAUNCH(8, true, true, false, SPS_PXD_B8C2, 1, SPS_PX1_W); break;   // block8.conv2 (heads: `final` not fused)
+    case 812: SPS_PX_LAUNCH(8, true, true, true, SPS_PXD_B8C2, 1, SPS_PX1_W); break;   // block8.conv2 + `final`
     case 1601:                                                // block7.conv2 (+ convtr7p2s2 in its epilogue)
       if (up) {
         if (level_out != 1 || a.up_cout > 16) return fail(SPS_ERR_INVALID, "%s cannot be fused into %s", up, name);
-        launch_px<SPS_PX1, 16, false, true, false, SPS_PX1_W, true>(gridp, st, a);
+        launch_px<SPS_PX1, 16, false, true, false, SPS_PXW_B7C2, true, false, SPS_PXD_B7C2>(gridp, st, a);
       } else {
-        SPS_PX_LAUNCH(16, false, true, false);
+        SPS_PX_LAUNCH(16, false, true, false, 1, 1, SPS_PX1_W);
       }
       break;
-    case 1610: SPS_PX_LAUNCH(16, true, false, false); break;  // block8.conv1
-    case 2400: SPS_PX_LAUNCH(24, false, false, false); break; // block7.conv1
+    case 1610: SPS_PX_LAUNCH(16, true, false, false, SPS_PXD_B8C1, 1, SPS_PX1_W); break;  // block8.conv1
+    case 2400: SPS_PX_LAUNCH(24, false, false, false, 1, SPS_PXD_B7C1, SPS_PXW_B7C1); break; // block7.conv1
     default: return fail(SPS_ERR_INVALID, "no k_conv_px instantiation for %s", name);
   }
 #undef SPS_PX_LAUNCH
