@@ -823,8 +823,8 @@ int sps_ndt_pyramid_carve_cells(sps_ctx *ctx, int level, int32_t *pass_out_dev, 
  *   T_best_dev included, has the bits of sps_ndt_align_batch on a single map of that resolution.
  *   Launches: 1 (initialise: poses, statuses, state words and the per-slot rows) + 2 * iters (A with grid
  *   (ceil(cap / 32), n_hyp), B with grid n_hyp) + 2, whatever the data, no memset:
- *     A once more, sps_ndt_align_batch's, for every hypothesis at its final pose whatever its status, against the map and
- *        the Gaussian fit of the finest level (so the scores compare however far a hypothesis got): final_dev[k] = (score,
+ *     A once more, sps_ndt_align_batch's body, for every hypothesis at its final pose whatever its status, against the map
+ *        and the Gaussian fit of the finest level (so the scores compare however far a hypothesis got): final_dev[k] = (score,
  *        points counted), the partial rows added in launch B's block order;
  *     select, sps_ndt_align_batch's: the highest final score among the hypotheses with status 0 or 1 (one that used up
  *        `iters` on a coarse level is eligible) and at least min_corr points counted at the final pose; equal scores go to
@@ -993,6 +993,43 @@ int sps_ndt_pyramid_align_d2d(sps_ctx *ctx, const double *src_dev, const int32_t
                               const double *T_init_host, int iters, const int32_t *level_iters, int neighbours, int min_corr,
                               double tol_t, double tol_r, double *T_out_dev, int32_t *status_dev, double *trace_dev,
                               double *normal_dev, int32_t *level_dev, void *scratch_dev, void *stream);
+
+/* ---- NDT localiser, distribution to distribution, pyramid, several hypotheses ---------------------------------------------
+ * sps_ndt_pyramid_align_d2d from n_hyp start poses that live on the device, in the same launches, and
+ * sps_ndt_align_batch's choice among the end poses.    Additive: sps_version() is unchanged, and no call
+ * above changes its bits or its behaviour.  The rules of sps_ndt_align_d2d hold; the call does not allocate, does not
+ * synchronise and never raises the sticky error.
+ *
+ * sps_ndt_pyramid_align_d2d_batch: src_dev double[n_levels][cap_src][SPS_NDT_SRC_REC] and n_src_dev int32[n_levels][2]
+ *   (cells, valid cells) are sps_ndt_pyramid_source_build's (or hand-made), the levels back to back.  Every other argument
+ *   and output means what it means in sps_ndt_pyramid_align_batch.  Hypothesis k is, operation for operation and sum for
+ *   sum, sps_ndt_pyramid_align_d2d from T_init_dev[k]: T_out_dev[k], status_dev[k], its trace, normal and level rows and
+ *   the slots used per level have the bits of the single call.  Hypotheses stand at different levels in the same slot: launch
+ *   A of hypothesis k reads the map, the source records and the count of the level its state words name, launch B sums the
+ *   rows of that level's count and hands off by sps_ndt_pyramid_align_d2d's skip rule.  The sources are in the sensor
+ *   frame, so every hypothesis walks the same chain of levels.
+ *   Launches: 1 + 2 * iters + 2, whatever the data, no memset:
+ *     the final pass: the scoring level l* is the last level of that chain, the largest l >= 1 with
+ *        min(cap_src, n_src_dev[l][1]) >= min_corr, or 0 where there is none.  It is found on the device; the host never
+ *        reads it during the call.  Every hypothesis, whatever its status and the level it stopped at, is evaluated at
+ *        T_out_dev[k] with level l*'s sources against level l*'s map: final_dev[k] = (D2D score, sources counted), the bits of
+ *        sps_ndt_score_poses_d2d at T_out_dev[k] on a single map and single sources built at level l*'s two resolutions and
+ *        min_points.  A finest level that was skipped is not used for scoring.
+ *     select, sps_ndt_align_batch's, on the rows of level l*'s count: the highest score among status 0 or 1 with at least
+ *        min_corr sources counted; ties go to the lowest k; NaN never wins.  best_dev = (k, status of k, sources counted at
+ *        its final pose, n_hyp), T_best_dev = T_out_dev[k]; nobody qualifies: (-1, -1, 0, n_hyp) and T_init_dev[0].
+ *   Level 0 with fewer than min_corr sources counted is status 2 for every hypothesis after one slot.  iters = 0 is legal
+ *   and gives the scores of the start poses.  Arguments are checked as for sps_ndt_pyramid_align_batch and
+ *   sps_ndt_pyramid_align_d2d: 1 <= n_hyp <= SPS_NDT_MAX_HYP, a built pyramid, level_iters each >= 1, the limits on cap_src.
+ *   scratch_dev: sps_ndt_pyramid_align_d2d_batch_scratch(cap_src, n_hyp) bytes (-1 for arguments out of range): the layout
+ *   of sps_ndt_pyramid_align_batch_scratch with the source capacity.  The final pass leaves (count of level l*, l*) in the
+ *   two spare state words of hypothesis 0. */
+int64_t sps_ndt_pyramid_align_d2d_batch_scratch(int64_t cap_src, int n_hyp);
+int sps_ndt_pyramid_align_d2d_batch(sps_ctx *ctx, const double *src_dev, const int32_t *n_src_dev, int64_t cap_src,
+                                    const double *T_init_dev, int n_hyp, int iters, const int32_t *level_iters, int neighbours,
+                                    int min_corr, double tol_t, double tol_r, double *T_out_dev, int32_t *status_dev,
+                                    double *trace_dev, double *normal_dev, int32_t *level_dev, double *final_dev,
+                                    int32_t *best_dev, double *T_best_dev, void *scratch_dev, void *stream);
 
 /* ---- pose estimator (unscented Kalman filter with IMU prediction) -----------------------------------------------------
  * hdl_localization's pose system as published, restated: tests/ukf_reference.py is the specification, not that package

@@ -26,7 +26,8 @@ line then tells the iterations per level); with ``--update-map`` / ``--carve-map
 per level; with ``--source cells`` it registers distribution to distribution (one Gaussian per cell of the scan against
 the map's; ``--source-resolution``, ``--source-min-points``), ``n_corr`` then counts source cells and the ``loc:`` line
 ends with ``| N sources``, the scan's valid cells; ``--d2d`` lets ``--hypotheses``, ``--search`` and the device path of
-``--estimator ukf`` register the scan's cells too; ``--source cells --resolutions 2,1,0.5 --source-resolutions 2,1,0.5``
+``--estimator ukf`` register the scan's cells too (``--d2d-pyramid``: coarse to fine on the pyramid of
+``--source-resolutions``); ``--source cells --resolutions 2,1,0.5 --source-resolutions 2,1,0.5``
 registers the scan's cells coarse to fine, built once per level at that level's edge (``--source-min-points`` then also
 takes one value per level; the ``| N sources`` are those of the level the frame ended on).  Frames then run one at a time; behind each frame's lines comes
 ``loc: status iterations n_corr rmse | err_t err_r`` (metres, degrees, against the replayed pose map_tr @ pose) and at
@@ -153,12 +154,13 @@ def hypothesis_grid(counts, steps, option="--hypotheses", step_option="--hypothe
 def closed_loop(name, f, pc_map, replay, finish, traj_out, which="icp", hypotheses=None, search=None, update_map=False,
                 cell_capacity=None, max_cell_points=0, resolutions=None, level_iterations=None, carve_map=False,
                 carve_options=None, level_capacities=None, estimator=None, source=None, coarse_to_fine=False,
-                global_start=None, match_status=None, recover=None, inject=None, d2d=False):
+                global_start=None, match_status=None, recover=None, inject=None, d2d=False, d2d_pyramid=False):
     """--localise: one LocalisationLoop step per frame, scored against the replayed poses.  ``estimator``: None, or the
     options of --estimator ukf (initial_velocity, scan_period, imu: None / a rate in Hz / an array of rows t ax .. gz).
     ``source``: None, or the keywords of NDTLocaliser(source="cells", ...) of --source cells.  ``coarse_to_fine``: hypotheses,
     search and the estimator's device path register on the pyramid of --resolutions.  ``d2d``: with ``source``, they
-    register the scan's cells (--d2d).  ``global_start``: None, or the
+    register the scan's cells (--d2d); ``d2d_pyramid``: with ``source`` and its ``source_resolutions``, they register the
+    scan's cells coarse to fine on the pyramid (--d2d-pyramid).  ``global_start``: None, or the
     options of --global-start (grid: the localiser's global_grid; yaw_steps, frontier, scan_z: of localise_global): the
     loop's initial pose is then found on the map from the first raw scan, and the sequence's first pose only scores it.
     ``match_status``: None, or the localiser's match_status of --match-status: every frame's inlier fraction and matching
@@ -208,7 +210,8 @@ def closed_loop(name, f, pc_map, replay, finish, traj_out, which="icp", hypothes
                 est = PoseEstimator(T0, localiser.device, initial_velocity=estimator["initial_velocity"])
             loop = LocalisationLoop(f, localiser, T0, hypotheses=hypotheses, search=search, update_map=update_map,
                                     max_cell_points=max_cell_points, carve_map=carve_map, carve_options=carve_options,
-                                    estimator=est, coarse_to_fine=coarse_to_fine, **(dict(d2d=True) if d2d else {}), **lkw)
+                                    estimator=est, coarse_to_fine=coarse_to_fine, **(dict(d2d=True) if d2d else {}),
+                                    **(dict(d2d_pyramid=True) if d2d_pyramid else {}), **lkw)
             if est is not None:
                 print("estimator: ukf  start of the registration: " + ("device pose" if loop.device_guess else "host pose"))
         if estimator is None:
@@ -355,6 +358,9 @@ def frame_motion(estimator, k):
               help="with --source cells and one of --hypotheses, --search, --estimator ukf: these register the scan's cells "
                    "too, distribution to distribution, from start poses on the device (without it --source cells takes "
                    "neither --hypotheses nor --search, and the estimator's guess is fetched to the host)")
+@click.option("--d2d-pyramid", "d2d_pyramid", is_flag=True,
+              help="with --source cells --resolutions --source-resolutions and one of --hypotheses, --search, --estimator ukf: "
+                   "these register the scan's cells coarse to fine on the pyramid too, from start poses on the device")
 @click.option("--source-resolution", "source_resolution", type=float, default=None,
               help="with --source cells: edge of the scan's cells in m (default: the map's resolution)")
 @click.option("--source-min-points", "source_min_points", type=str, default=None,
@@ -405,7 +411,7 @@ def main(name, weights, sequence, config, epsilon, out_dir, n_synth, localise, w
          resolutions, level_iterations, coarse_to_fine, level_capacities, source, d2d, source_resolution, source_min_points, source_resolutions,
          estimator, initial_velocity, scan_period, imu_rate, imu_file, global_start, global_resolution, global_map_z,
          global_scan_z, global_yaw_steps, global_levels, global_frontier, match_status, min_inlier_fraction, recover_global,
-         inject_jump):
+         inject_jump, d2d_pyramid):
     if global_start and (which != "ndt" or not localise):
         raise click.UsageError("--global-start needs --localise --localiser ndt")
     if global_start and source == "cells":
@@ -459,8 +465,12 @@ def main(name, weights, sequence, config, epsilon, out_dir, n_synth, localise, w
         raise click.UsageError("--d2d needs --source cells and one of --hypotheses, --search, --estimator ukf")
     if source_resolutions is not None and (source != "cells" or resolutions is None or source_resolution is not None):
         raise click.UsageError("--source-resolutions needs --source cells and --resolutions, and no --source-resolution")
+    if d2d_pyramid and (source != "cells" or resolutions is None or source_resolutions is None or d2d or coarse_to_fine
+                        or (hyp_counts is None and search_counts is None and estimator is None)):
+        raise click.UsageError("--d2d-pyramid needs --source cells, --resolutions, --source-resolutions and one of --hypotheses, "
+                               "--search, --estimator ukf, and neither --d2d nor --coarse-to-fine")
     if source == "cells" and ((resolutions is not None and source_resolutions is None)
-                              or ((hyp_counts is not None or search_counts is not None) and not d2d)):
+                              or ((hyp_counts is not None or search_counts is not None) and not (d2d or d2d_pyramid))):
         raise click.UsageError("--source cells takes no --resolutions, --hypotheses or --search: they register points"
                                " (--d2d lets --hypotheses and --search register the scan's cells; --source-resolutions "
                                "registers them on the pyramid of --resolutions)")
@@ -527,7 +537,7 @@ def main(name, weights, sequence, config, epsilon, out_dir, n_synth, localise, w
     if resolutions is not None and (update_map or carve_map):
         if cell_capacity is not None:
             raise click.UsageError("--cell-capacity is the single map's: with --resolutions give --level-capacities")
-        if (hyp_counts is not None or search_counts is not None) and not coarse_to_fine:
+        if (hyp_counts is not None or search_counts is not None) and not (coarse_to_fine or d2d_pyramid):
             raise click.UsageError("--resolutions with --update-map or --carve-map takes no --hypotheses and no --search: they "
                                    "register on the single map, which stays static")
         if recover_global is not None and not coarse_to_fine:
@@ -584,7 +594,7 @@ def main(name, weights, sequence, config, epsilon, out_dir, n_synth, localise, w
     if localise:
         closed_loop(name, f, pc_map, replay, finish, traj_out, which or "icp", hypotheses, search, update_map, cell_capacity,
                     max_cell_points, resolutions, level_iterations, carve_map, carve_options or None, level_capacities,
-                    estimator, source, coarse_to_fine, global_start, match_status, recover_global, inject, d2d)
+                    estimator, source, coarse_to_fine, global_start, match_status, recover_global, inject, d2d, d2d_pyramid)
     elif traj_out:
         raise click.UsageError("--traj-out needs --localise")
     in_flight, prev_pose = None, None

@@ -185,6 +185,9 @@ def _load() -> C.CDLL:
         "sps_ndt_pyramid_align_d2d_scratch": (i64, [i64]),
         "sps_ndt_pyramid_align_d2d": (i32, [vp, vp, vp, i64, vp, i32, vp, i32, i32, C.c_double, C.c_double, vp, vp, vp, vp, vp, vp,
                                             vp]),
+        "sps_ndt_pyramid_align_d2d_batch_scratch": (i64, [i64, i32]),
+        "sps_ndt_pyramid_align_d2d_batch": (i32, [vp, vp, vp, i64, vp, i32, i32, vp, i32, i32, C.c_double, C.c_double, vp, vp, vp,
+                                                  vp, vp, vp, vp, vp, vp, vp]),
         "sps_ndt_score_d2d_scratch": (i64, [i64, i64]),
         "sps_ndt_score_poses_d2d": (i32, [vp, vp, vp, i64, vp, i64, i32, C.c_double, vp, vp, vp]),
         "sps_ukf_state_bytes": (i64, []),
@@ -233,7 +236,7 @@ EXPORTS = ["sps_last_error", "sps_version", "sps_ctx_create", "sps_ctx_destroy",
            "sps_ndt_source_scratch", "sps_ndt_source_build", "sps_ndt_align_d2d_scratch", "sps_ndt_align_d2d",
            "sps_ndt_align_d2d_batch_scratch", "sps_ndt_align_d2d_batch", "sps_ndt_score_d2d_scratch", "sps_ndt_score_poses_d2d",
            "sps_ndt_pyramid_source_scratch", "sps_ndt_pyramid_source_build", "sps_ndt_pyramid_align_d2d_scratch",
-           "sps_ndt_pyramid_align_d2d",
+           "sps_ndt_pyramid_align_d2d", "sps_ndt_pyramid_align_d2d_batch_scratch", "sps_ndt_pyramid_align_d2d_batch",
            "sps_ukf_state_bytes", "sps_ukf_init", "sps_ukf_predict", "sps_ukf_predict_dt", "sps_ukf_correct"]
 NDT_SRC_REC = 10           # SPS_NDT_SRC_REC: doubles of a source record
 BBS_MAX_LEVELS = 8         # SPS_BBS_MAX_LEVELS
@@ -667,12 +670,13 @@ class Context:
     def ndt_pyramid_align_batch(self, pts_ptr, n_dev_ptr: int, cap: int, T_init_ptr, n_hyp: int, iters: int, level_iters,
                                 neighbours: int, min_corr: int, tol_t: float, tol_r: float, T_out_ptr: int, status_ptr: int,
                                 trace_ptr, normal_ptr, level_ptr, final_ptr: int, best_ptr: int, T_best_ptr: int,
-                                scratch_ptr: int, stream: int):
+                                scratch_ptr: int, stream: int, d2d: bool = False):
+        """d2d: src [L][cap][NDT_SRC_REC] and n_src [L][2] for pts and n_dev, as ``ndt_pyramid_source_build`` leaves them"""
+        fn = lib.sps_ndt_pyramid_align_d2d_batch if d2d else lib.sps_ndt_pyramid_align_batch
         caps = (C.c_int32 * len(level_iters))(*[int(v) for v in level_iters])
-        check(lib.sps_ndt_pyramid_align_batch(self.handle, pts_ptr, n_dev_ptr, int(cap), T_init_ptr, int(n_hyp), int(iters), caps,
-                                              int(neighbours), int(min_corr), float(tol_t), float(tol_r), T_out_ptr, status_ptr,
-                                              trace_ptr, normal_ptr, level_ptr, final_ptr, best_ptr, T_best_ptr, scratch_ptr,
-                                              stream))
+        check(fn(self.handle, pts_ptr, n_dev_ptr, int(cap), T_init_ptr, int(n_hyp), int(iters), caps,
+                 int(neighbours), int(min_corr), float(tol_t), float(tol_r), T_out_ptr, status_ptr, trace_ptr, normal_ptr,
+                 level_ptr, final_ptr, best_ptr, T_best_ptr, scratch_ptr, stream))
 
     # ---- NDT localiser, distribution to distribution (include/sps_hip.h, same title) ----
     def ndt_source_build(self, pts_ptr, n_dev_ptr: int, cap: int, source_resolution: float, min_points: int, eig_ratio: float,
@@ -705,6 +709,11 @@ class Context:
 
     def ndt_pyramid_align_d2d(self, *args):
         self.ndt_pyramid_align(*args, d2d=True)
+
+    # ---- NDT localiser, distribution to distribution, pyramid, several hypotheses (include/sps_hip.h, same title) ----
+    def ndt_pyramid_align_d2d_batch(self, *args):
+        """``ndt_pyramid_align_batch`` with the levels' source records, n_src and cap_src"""
+        self.ndt_pyramid_align_batch(*args, d2d=True)
 
     def train_forward(self, params_ptr: int, numel: int, coords_ptr: int, ld: int, n: int, voxel_size: float,
                       scores_ptr: int, batch_stats_ptr, stream: int):

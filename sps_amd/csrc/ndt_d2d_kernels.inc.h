@@ -274,6 +274,13 @@ struct NdtCells {
       if (min(cap, max(n_src[2 * k + 1], 0)) >= min_corr) return k;
     return -1;
   }
+  // where the chain of `next` from level 0 ends: the last level that is not skipped, 0 where every other one is
+  __device__ static int last(const int *n_src, int cap, int n_levels, int min_corr) {
+    int l = 0;
+    for (int k = 1; k < n_levels; ++k)
+      if (min(cap, max(n_src[2 * k + 1], 0)) >= min_corr) l = k;
+    return l;
+  }
 };
 
 // launch A of sps_ndt_align_d2d: k_ndt_assoc (ndt_kernels.inc.h) for the scan's cells

@@ -296,6 +296,7 @@ __device__ inline void ndt_assoc_reduce(NdtAssocLds &lds, int k, int sub, const 
 //                              the cell of q adds nothing; true hands back e, w, y and the inverse covariance B
 //   level_elems, level_count   the elements of level l of a pyramid, and where their count is
 //   next                       the level after l, < 0 where l is the last
+//   last                       the level at which the chain of `next` from level 0 ends
 struct NdtPoints {
   static constexpr int ELEM = 3;
   __device__ static bool valid(const double *) { return true; }
@@ -308,6 +309,7 @@ struct NdtPoints {
   __device__ static const double *level_elems(const double *pts, int, int) { return pts; }
   __device__ static const int *level_count(const int *n_dev, int) { return n_dev; }
   __device__ static int next(const int *, int, int l, int n_levels, int) { return l == n_levels - 1 ? -1 : l + 1; }
+  __device__ static int last(const int *, int, int n_levels, int) { return n_levels - 1; }
 };
 
 template <class Scan>

@@ -40,7 +40,10 @@ pyramid"): one static map per resolution beside the single one, an
 
 ``submit_batch``, ``submit_from_device`` and ``relocalise`` take ``coarse_to_fine=True`` on such a localiser (C ABI: "NDT
 localiser, pyramid, several hypotheses"): their hypotheses are then registered on the pyramid, each at a level
-of its own, from start poses that live on the device, and selected by the score on the finest level.
+of its own, from start poses that live on the device, and selected by the score on the finest level.  With
+``d2d_pyramid=True`` on a localiser with ``source="cells"`` and ``source_resolutions`` they register the scan's cells on the
+pyramid instead (C ABI: "NDT localiser, distribution to distribution, pyramid, several hypotheses"), selected by
+the score on the last level the scan's cells do not skip.
 
 ``NDTLocaliser(..., resolutions=(2.0, 1.0, 0.5), level_capacities=(c0, c1, c2))`` makes that pyramid an online one (C ABI:
 "NDT localiser, online pyramid"): every level is a dynamic map, and ``integrate`` / ``carve`` / ``submit(...,
@@ -213,20 +216,41 @@ def _pose_layout(K, with_normal, pyramid=False, L=None, integrate=False, carve=F
     return o
 
 
-def _batch_layout(K, I, with_normal, integrate=False, carve=False, pyramid=False, L=None, match=False):
+def _batch_layout(K, I, with_normal, integrate=False, carve=False, pyramid=False, L=None, match=False, sources=0):
     """offsets (in doubles) of a batch's one float64 buffer: T_out[K][16] | status int32[K][4] | n_points int32 (+ n_sources
     int32 of a d2d batch in the pad) |
-    best int32[4] | T_best[16] | final[K][2] | trace[K][I][4] | normal[K][I][28] | level int32[K][I] (+ pad) of a coarse-to-fine
+    best int32[4] | T_best[16] | final[K][2] | trace[K][I][4] | normal[K][I][28] | valid sources int32[sources] (+ pad), one
+    per level, of a batch on a pyramid of source cells (``sources``: 0, or ``(levels, capacity, min_correspondences)``,
+    from which the host tells the scoring level) | level int32[K][I] (+ pad) of a coarse-to-fine
     batch (``pyramid``) | info int32[4] of the update | info int32[4] of the carve (an online pyramid of L levels: int32[L][4]
     each) | the MATCH_WORDS words of the scan-matching status with ``match``.  ``hands_on``, as in ``_pose_layout``:
     ``T_best`` and ``best[1]``, the selected hypothesis' status, -1 where none was selected, or, with ``match``, the verdict"""
     w = 2 if L is None else 2 * L                                    # doubles of one call's info words
     o = _offsets((("T_out", 16 * K), ("status", 2 * K), ("n_points", 1), ("best", 2), ("T_best", 16), ("final", 2 * K),
                   ("trace", 4 * K * I), ("normal", 28 * K * I if with_normal else 0)),
-                 (("levels", (K * I + 1) // 2 if pyramid else 0), ("update", w if integrate else 0), ("carve", w if carve else 0),
-                  ("match", MATCH_WORDS if match else 0)))
+                 (("sources", (_source_levels(sources) + 1) // 2), ("levels", (K * I + 1) // 2 if pyramid else 0),
+                  ("update", w if integrate else 0), ("carve", w if carve else 0), ("match", MATCH_WORDS if match else 0)))
     o["hands_on"] = (o["T_best"] * 8, (o["match"] + 4) * 8 if match else o["best"] * 8 + 4)
     return o
+
+
+def _source_levels(sources) -> int:
+    """the levels of a pyramid of source cells from the ``sources`` of ``_batch_layout``: 0 (no such pyramid), or the first
+    of ``(levels, capacity, min_correspondences)``"""
+    if not sources:
+        return 0
+    levels, _, _ = sources                                           # nothing but the triple: ``_parse`` needs all of it
+    return int(levels)
+
+
+def _scoring_level(valid, capacity, min_corr) -> int:
+    """the level a batch on a pyramid of source cells takes its final scores on, from the levels' valid source cells: the
+    last level that is not skipped, the largest l >= 1 with min(capacity, valid[l]) >= min_corr, or 0"""
+    best = 0
+    for l in range(1, len(valid)):
+        if min(int(capacity), max(int(valid[l]), 0)) >= int(min_corr):
+            best = l
+    return best
 
 
 def _map_op_layout(L=None):
@@ -322,14 +346,17 @@ class BatchPoseResult:
     map_update: object = None  # MapUpdateResult of the frame, with integrate=True (an online pyramid: a tuple, one per level)
     map_carve: object = None   # MapCarveResult of the frame, with carve=True (an online pyramid: a tuple, one per level)
     match: object = None       # MatchStatus at ``pose``, of a localiser with match_status (None without)
+    n_sources: int = None      # d2d_pyramid: the valid source cells of the level the final scores were taken on
+    score_level: int = None    # d2d_pyramid: that level
 
 
 class PendingPoses(_Pending):
     """A batch of localisations whose work has been issued; everything lives on the device until result()."""
 
     def __init__(self, n_hyp, iters, with_normal, host, event, keep, at=0, integrate=False, carve=False, pyramid=False,
-                 n_levels=None, match=False):
+                 n_levels=None, match=False, sources=0):
         super().__init__(host, event, keep)
+        self._sources = sources                                      # a pyramid of source cells: (levels, capacity, min_corr)
         self._match = match                                          # the batch's buffer has the scan-matching status
         self._n_hyp, self._iters, self._with_normal = n_hyp, iters, with_normal
         self._at = at                                                # doubles in front of the batch's part of the buffer
@@ -338,7 +365,7 @@ class PendingPoses(_Pending):
 
     def _layout(self):
         return _batch_layout(self._n_hyp, self._iters, self._with_normal, self._integrate, self._carve, self._pyramid,
-                             self._n_levels, self._match)
+                             self._n_levels, self._match, self._sources)
 
     def result(self) -> BatchPoseResult:
         return self._parse(self._wait())
@@ -354,9 +381,12 @@ class PendingPoses(_Pending):
         trace = h[o["trace"]:o["normal"]].reshape(K, I, 4)
         normal = h[o["normal"]:o["size"]].reshape(K, I, 28) if self._with_normal else None
         levels = h[o["levels"]:o["update"]].view(np.int32)[:K * I].reshape(K, I) if self._pyramid else None
+        valid = h[o["sources"]:o["levels"]].view(np.int32)[:_source_levels(self._sources)] if self._sources else None
         results = []
         for k in range(K):
-            code, it, n_corr, _ = (int(x) for x in status[k])
+            code, it, n_corr, last_level = (int(x) for x in status[k])
+            if valid is not None:                                    # as ``submit``: the level of the last live slot tells
+                n_sources = int(valid[min(max(last_level, 0), len(valid) - 1)])
             tr = trace[k, :it].copy()
             rmse = math.sqrt(tr[-1, 1] / n_corr) if it and n_corr > 0 else float("nan")
             results.append(PoseResult(T_out[k].copy(), code, it, n_corr, rmse, tr,
@@ -367,8 +397,12 @@ class PendingPoses(_Pending):
         upd = _per_level(_map_update_of, h[o["update"]:o["carve"]].view(np.int32), n_points, L) if self._integrate else None
         carved = _per_level(_map_carve_of, h[o["carve"]:o["match"]].view(np.int32), n_points, L) if self._carve else None
         match = _match_of(h[o["match"]:o["total"]]) if self._match else None
-        return BatchPoseResult(results, final[:, 0].copy(), final[:, 1].astype(np.int64), int(best[0]),
-                               h[o["T_best"]:o["final"]].reshape(4, 4).copy(), upd, carved, match)
+        out = BatchPoseResult(results, final[:, 0].copy(), final[:, 1].astype(np.int64), int(best[0]),
+                              h[o["T_best"]:o["final"]].reshape(4, 4).copy(), upd, carved, match)
+        if valid is not None:
+            out.score_level = _scoring_level(valid, *self._sources[1:])
+            out.n_sources = int(valid[out.score_level])
+        return out
 
 
 def pose_grid(along, across, yaw_deg) -> np.ndarray:
@@ -886,8 +920,9 @@ class NDTLocaliser(ScanToMapLocaliser):
     always entered).  ``levels`` is as for points, ``n_sources`` is the valid-cell count of the level of the last live slot,
     and ``source_cells(rows, count, level)`` shows a level.  ``level_capacities`` is allowed: the map still takes the thinned
     points.  The calls with ``d2d=True`` keep working on the single map, with sources at ``resolution`` (valid from
-    ``source_min_points`` where that is one int, else from ``min_points_per_cell``); ``d2d=True`` with
-    ``coarse_to_fine=True`` and the global search stay refused.
+    ``source_min_points`` where that is one int, else from ``min_points_per_cell``).  ``submit_batch``,
+    ``submit_from_device`` and ``relocalise`` register the scan's cells on the pyramid too when asked with
+    ``d2d_pyramid=True``; ``d2d=True`` with ``coarse_to_fine=True`` and the global search stay refused.
 
     ``global_grid`` (None: nothing is built; a dict with any of ``resolution`` (0.5), ``map_z`` = (lo, hi) (everything) and
     ``levels`` (3, at most 7)): the map points of that height slice become an occupancy grid of that edge with ``levels``
@@ -1212,7 +1247,20 @@ class NDTLocaliser(ScanToMapLocaliser):
             raise ValueError(f"{what}: d2d=True needs an NDTLocaliser with source='cells'")
         if coarse_to_fine:
             raise ValueError(f"{what}: d2d=True and coarse_to_fine exclude each other: the pyramid registers points here "
-                             "(source cells go coarse to fine through submit, with source_resolutions)")
+                             "(source cells go coarse to fine through submit, with source_resolutions, and from several "
+                             "poses with d2d_pyramid=True)")
+        return True
+
+    def _checked_d2d_pyramid(self, what, d2d_pyramid, d2d=False, coarse_to_fine=False):
+        """the checks of the ``d2d_pyramid`` keyword, before any device work -> whether it is set: it needs the pyramid of
+        source cells and stands alone"""
+        if not d2d_pyramid:
+            return False
+        if d2d or coarse_to_fine:
+            raise ValueError(f"{what}: d2d_pyramid=True excludes d2d and coarse_to_fine: it registers the scan's cells coarse "
+                             "to fine by itself")
+        if self.source != "cells" or self.source_resolutions is None:
+            raise ValueError(f"{what}: d2d_pyramid=True needs an NDTLocaliser with source='cells' and source_resolutions")
         return True
 
     @staticmethod
@@ -1421,7 +1469,7 @@ class NDTLocaliser(ScanToMapLocaliser):
     @torch.no_grad()
     def submit_batch(self, rows, count, T_inits, with_normal: bool = False, iterations: int = None, integrate: bool = False,
                      max_cell_points: int = 0, carve: bool = False, carve_options: dict = None,
-                     coarse_to_fine: bool = False, d2d: bool = False) -> PendingPoses:
+                     coarse_to_fine: bool = False, d2d: bool = False, d2d_pyramid: bool = False) -> PendingPoses:
         """``submit`` from the K start poses ``T_inits`` [K, 4, 4] (1 <= K <= 64) at once: the scan is thinned once, every
         hypothesis is registered as ``submit`` would register it from its pose, and the hypothesis with the highest NDT
         score at its final pose is selected among those with status 0 / 1 and at least ``min_correspondences`` points
@@ -1440,61 +1488,90 @@ class NDTLocaliser(ScanToMapLocaliser):
         scan is thinned and its source cells are built once, as ``submit`` builds them, and every hypothesis is registered
         distribution to distribution, as ``submit`` registers there (C ABI: "NDT localiser, distribution to distribution,
         several poses").  ``n_corr``, ``counts`` and ``min_correspondences`` then mean source cells and every
-        hypothesis' result carries ``n_sources``; ``integrate`` and ``carve`` still work on the thinned points."""
+        hypothesis' result carries ``n_sources``; ``integrate`` and ``carve`` still work on the thinned points.
+
+        ``d2d_pyramid`` (a localiser with ``source="cells"`` and ``source_resolutions``; not with ``d2d`` or
+        ``coarse_to_fine``): the scan is thinned once, its source cells are built at every level and every hypothesis is
+        registered coarse to fine distribution to distribution, as ``submit`` registers there (C ABI: "NDT localiser,
+        distribution to distribution, pyramid, several hypotheses").  The final scores are taken on the last
+        level that the scan's cells do not skip, ``score_level`` of the result, whose valid source cells are its
+        ``n_sources``; ``results[k].n_sources`` is, as for ``submit``, the count of the level of hypothesis k's last live
+        slot.  ``iterations``, the caps, ``levels``, ``integrate`` and ``carve`` are those of ``coarse_to_fine``."""
+        pyr = self._checked_d2d_pyramid("submit_batch", d2d_pyramid, d2d, coarse_to_fine)
         if d2d:                                                      # poses first: they need no device
             self._checked_d2d("submit_batch", d2d, coarse_to_fine)
+        if d2d or pyr:
             _checked_poses(T_inits, "T_inits", MAX_HYPOTHESES, "K")
         rows, copts = self._checked_for_batch("submit_batch", rows, integrate, max_cell_points, carve, carve_options,
-                                              coarse_to_fine, d2d)
+                                              coarse_to_fine, d2d, pyr)
         T = _checked_poses(T_inits, "T_inits", MAX_HYPOTHESES, "K")
         return self._issue_batch(rows, count, T, len(T), with_normal, iterations, integrate, max_cell_points, copts,
-                                 coarse_to_fine, d2d)
+                                 coarse_to_fine or pyr, d2d or pyr)
 
     @torch.no_grad()
     def submit_from_device(self, rows, count, T_init_dev, with_normal: bool = False, iterations: int = None,
                            integrate: bool = False, max_cell_points: int = 0, carve: bool = False,
-                           carve_options: dict = None, coarse_to_fine: bool = False, d2d: bool = False) -> PendingPoses:
+                           carve_options: dict = None, coarse_to_fine: bool = False, d2d: bool = False,
+                           d2d_pyramid: bool = False) -> PendingPoses:
         """``submit_batch`` with one hypothesis whose start pose is already on the device: ``T_init_dev`` holds 16 contiguous
         float64 entries (a row-major 4 x 4, e.g. ``PoseEstimator.pose_dev``) that work issued earlier on the current stream
         may still be writing.  The host never sees the pose; hypothesis 0 of the result is what ``submit`` gives from the
         same pose, bit for bit.  A pose that is not finite ends as such a pose does in ``sps_ndt_align_batch``.
         ``coarse_to_fine``: as for ``submit_batch``; hypothesis 0 is then what ``submit`` gives on the pyramid.
-        ``d2d``: as for ``submit_batch``; hypothesis 0 is then what ``submit`` gives on a ``source="cells"`` localiser."""
+        ``d2d``: as for ``submit_batch``; hypothesis 0 is then what ``submit`` gives on a ``source="cells"`` localiser.
+        ``d2d_pyramid``: as for ``submit_batch``; hypothesis 0 is then what ``submit`` gives on a localiser with
+        ``source_resolutions``."""
+        pyr = self._checked_d2d_pyramid("submit_from_device", d2d_pyramid, d2d, coarse_to_fine)
         rows, copts = self._checked_for_batch("submit_from_device", rows, integrate, max_cell_points, carve, carve_options,
-                                              coarse_to_fine, d2d)
+                                              coarse_to_fine, d2d, pyr)
         T_dev = T_init_dev
         if not (torch.is_tensor(T_dev) and T_dev.is_cuda and T_dev.device == self.device and T_dev.dtype == torch.float64
                 and T_dev.numel() == 16 and T_dev.is_contiguous()):
             raise TypeError("T_init_dev must be 16 contiguous float64 entries on the localiser's device")
         return self._issue_batch(rows, count, T_dev, 1, with_normal, iterations, integrate, max_cell_points, copts,
-                                 coarse_to_fine, d2d)
+                                 coarse_to_fine or pyr, d2d or pyr)
 
-    def _checked_for_batch(self, what, rows, integrate, max_cell_points, carve, carve_options, coarse_to_fine=False, d2d=False):
+    def _checked_for_batch(self, what, rows, integrate, max_cell_points, carve, carve_options, coarse_to_fine=False, d2d=False,
+                           d2d_pyramid=False):
         """the checks of everything that registers from poses on the device, in their order -> (the checked rows, the carve's
         options).  Without ``coarse_to_fine`` the work is on the single map; with it on the pyramid, which must exist and
-        whose levels ``integrate`` and ``carve`` then mean; ``d2d``: the scan's cells are registered (``_checked_d2d``)"""
-        self._checked_d2d(what, d2d, coarse_to_fine)
+        whose levels ``integrate`` and ``carve`` then mean; ``d2d``: the scan's cells are registered (``_checked_d2d``);
+        ``d2d_pyramid``: the scan's cells on the pyramid (``_checked_d2d_pyramid``), whose levels the map work then means"""
+        if self._checked_d2d_pyramid(what, d2d_pyramid, d2d, coarse_to_fine):
+            coarse_to_fine = True
+        else:
+            self._checked_d2d(what, d2d, coarse_to_fine)
         if coarse_to_fine and self.resolutions is None:
             raise ValueError("coarse_to_fine needs a localiser with a pyramid: NDTLocaliser(..., resolutions=...)")
         self._check_integrate(integrate, max_cell_points, single_map=not coarse_to_fine)
         copts = self._check_carve(carve, carve_options, single_map=not coarse_to_fine)
         return self._checked_rows(rows), copts
 
-    def _batch_shape(self, integrate, carve, coarse_to_fine):
-        """the last five arguments of ``_batch_layout`` and of ``PendingPoses``"""
+    def _batch_shape(self, integrate, carve, coarse_to_fine, d2d=False):
+        """the last arguments of ``_batch_layout`` and of ``PendingPoses``; ``coarse_to_fine`` with ``d2d``: the scan's cells
+        on the pyramid (``d2d_pyramid``), whose levels' valid source cells ride in the buffer"""
         online = coarse_to_fine and self.level_capacities is not None
-        return integrate, carve, bool(coarse_to_fine), len(self.level_capacities) if online else None, self._match_opts is not None
+        shape = (integrate, carve, bool(coarse_to_fine), len(self.level_capacities) if online else None,
+                 self._match_opts is not None)
+        # The scoring level is found twice: on the device by the call (NdtCells::last, from cap_src and min_corr) and on the
+        # host by ``_scoring_level`` from the two values below.  They must be the cap_src and the min_corr that
+        # ``_align_batch`` hands to ``ndt_pyramid_align_batch``: self.capacity and self.min_correspondences.
+        if coarse_to_fine and d2d:
+            shape += ((len(self.source_resolutions), self.capacity, self.min_correspondences),)
+        return shape
 
     def _issue_batch(self, rows, count, poses, K, with_normal, iterations, integrate, max_cell_points, copts,
                      coarse_to_fine=False, d2d=False):
         """the batch of the K start poses ``poses``: a host array [K, 4, 4], or 16 float64 entries on the device (K = 1);
-        ``d2d``: of the scan's source cells, which are built first"""
+        ``d2d``: of the scan's source cells, which are built first (with ``coarse_to_fine``: at every level)"""
         I = self.iterations if iterations is None else int(iterations)
-        shape = self._batch_shape(integrate, copts is not None, coarse_to_fine)
+        shape = self._batch_shape(integrate, copts is not None, coarse_to_fine, d2d)
         o = _batch_layout(K, I, with_normal, *shape)
 
         def work(out, n_ptr, T_dev, s):
-            if d2d:
+            if d2d and coarse_to_fine:
+                self._level_sources_for_batch(out, n_ptr, o["sources"], s)
+            elif d2d:
                 self._sources_for_batch(out, n_ptr, o["n_points"], s)
             self._align_batch(n_ptr, T_dev.data_ptr(), K, I, with_normal, out.data_ptr(), o, s, integrate, max_cell_points, copts,
                               coarse_to_fine, d2d)
@@ -1509,15 +1586,20 @@ class NDTLocaliser(ScanToMapLocaliser):
         """the K alignments of self._pts from the device poses at T_ptr into the batch's buffer at ``base`` (layout ``o``), on
         the single map or, ``coarse_to_fine``, on the pyramid; ``carve_opts``: then the carve at the selected pose, its info
         words last; ``integrate``: then the map update at the selected pose, its info words behind the batch's part;
-        ``d2d``: the K alignments are those of the source cells in self._src, which the caller has built"""
+        ``d2d``: the K alignments are those of the source cells in self._src (with ``coarse_to_fine``: of every level's in
+        self._src_lv), which the caller has built"""
         trace_ptr, normal_ptr = base + o["trace"] * 8 if I else None, base + o["normal"] * 8 if with_normal and I else None
         if coarse_to_fine:
             caps = self.level_iterations or (max(I, 1),) * len(self.resolutions)
-            self.ctx.ndt_pyramid_align_batch(self._pts.data_ptr(), n_ptr, self.capacity, T_ptr, K, I, caps, self.neighbours,
+            elems, count = self._scan(n_ptr, d2d, True)
+            lib = _native.lib
+            scratch = self._scratch_for(lib.sps_ndt_pyramid_align_d2d_batch_scratch if d2d
+                                        else lib.sps_ndt_pyramid_align_batch_scratch, K)
+            self.ctx.ndt_pyramid_align_batch(elems, count, self.capacity, T_ptr, K, I, caps, self.neighbours,
                                              self.min_correspondences, self.tol_t, self.tol_r, base + o["T_out"] * 8,
                                              base + o["status"] * 8, trace_ptr, normal_ptr, base + o["levels"] * 8 if I else None,
                                              base + o["final"] * 8, base + o["best"] * 8, base + o["T_best"] * 8,
-                                             self._scratch_for(_native.lib.sps_ndt_pyramid_align_batch_scratch, K).data_ptr(), s)
+                                             scratch.data_ptr(), s, d2d=d2d)
         else:
             elems, count = self._scan(n_ptr, d2d)
             lib = _native.lib
@@ -1540,6 +1622,13 @@ class NDTLocaliser(ScanToMapLocaliser):
         self._build_sources(n_ptr, s)
         at = 2 * n_points_at + 1
         out.view(torch.int32)[at:at + 1].copy_(self._n_src[1:2])
+
+    def _level_sources_for_batch(self, out, n_ptr, sources_at, s):
+        """``_build_level_sources`` for a d2d_pyramid=True call, and every level's count of valid source cells into the
+        ``sources`` part of the batch's buffer (double ``sources_at`` of ``out``)"""
+        self._build_level_sources(n_ptr, s)
+        at, L = 2 * sources_at, len(self.source_resolutions)
+        out.view(torch.int32)[at:at + L].copy_(self._n_src_lv[:, 1])
 
     def _score(self, T_dev, P, n_points_ptr, score_ptr, s, d2d=False):
         """the scores of the P poses of T_dev for the thinned points in self._pts (their count at n_points_ptr) or, ``d2d``,
@@ -1572,7 +1661,8 @@ class NDTLocaliser(ScanToMapLocaliser):
     @torch.no_grad()
     def relocalise(self, rows, count, poses, keep: int = 8, with_normal: bool = False, iterations: int = None,
                    integrate: bool = False, max_cell_points: int = 0, carve: bool = False,
-                   carve_options: dict = None, coarse_to_fine: bool = False, d2d: bool = False) -> PendingRelocalisation:
+                   carve_options: dict = None, coarse_to_fine: bool = False, d2d: bool = False,
+                   d2d_pyramid: bool = False) -> PendingRelocalisation:
         """Thin, score the P poses ``poses`` [P, 4, 4] (e.g. ``T_center @ pose_grid(...)``), keep the best ``keep`` (1..64)
         by (score descending, index ascending) among those with at least ``min_correspondences`` points counted, register
         from these as ``submit_batch`` does and select among the end poses as it selects.  Everything is issued on the
@@ -1581,27 +1671,35 @@ class NDTLocaliser(ScanToMapLocaliser):
         map as ever; these are then registered as ``submit_batch(..., coarse_to_fine=True)`` registers them.
         ``d2d``: as for ``submit_batch``: the source cells are built once, the grid is scored as
         ``score_poses(..., d2d=True)`` scores it and its best ``keep`` are registered as ``submit_batch(..., d2d=True)``
-        registers them."""
+        registers them.
+        ``d2d_pyramid``: the grid is scored and its best ``keep`` chosen as ``score_poses(..., d2d=True)`` does it, with the
+        single sources on the single map; these are then registered as ``submit_batch(..., d2d_pyramid=True)`` registers
+        them."""
         def grid():
             T, K = _checked_poses(poses), int(keep)
             if not 1 <= K <= MAX_HYPOTHESES:
                 raise ValueError(f"keep must be in [1, {MAX_HYPOTHESES}]")
             return T, K
+        pyr = self._checked_d2d_pyramid("relocalise", d2d_pyramid, d2d, coarse_to_fine)
         if d2d:                                                      # the grid first: it needs no device
             self._checked_d2d("relocalise", d2d, coarse_to_fine)
+        if d2d or pyr:
             grid()
         rows, copts = self._checked_for_batch("relocalise", rows, integrate, max_cell_points, carve, carve_options,
-                                              coarse_to_fine, d2d)
+                                              coarse_to_fine, d2d, pyr)
+        coarse_to_fine, d2d = coarse_to_fine or pyr, d2d or pyr
         T, K = grid()
         P = len(T)
         I = self.iterations if iterations is None else int(iterations)
-        shape = self._batch_shape(integrate, carve, coarse_to_fine)
+        shape = self._batch_shape(integrate, carve, coarse_to_fine, d2d)
         so, o = _search_layout(P, K), _batch_layout(K, I, with_normal, *shape)
 
         def work(out, n_ptr, T_dev, s):
             sbase = out.data_ptr()
-            if d2d:
+            if d2d:                                                  # the single sources: the grid is scored with them
                 self._sources_for_batch(out, n_ptr, so["size"] + o["n_points"], s)
+            if pyr:
+                self._level_sources_for_batch(out, n_ptr, so["size"] + o["sources"], s)
             self._score(T_dev, P, n_ptr, sbase + so["score"] * 8, s, d2d)
             self.ctx.ndt_top_poses(sbase + so["score"] * 8, T_dev.data_ptr(), P, self.min_correspondences, K,
                                    sbase + so["top"] * 8, sbase + so["T_top"] * 8, sbase + so["n_top"] * 8, s)
@@ -1728,6 +1826,13 @@ class LocalisationLoop:
     are registered distribution to distribution (``submit_batch`` / ``relocalise`` / ``submit_from_device`` with
     ``d2d=True``).  Not with ``coarse_to_fine``.
 
+    ``d2d_pyramid`` (a localiser with ``source="cells"`` and ``source_resolutions``; False: everything above, unchanged;
+    not with ``d2d`` or ``coarse_to_fine``): the frames of ``hypotheses`` and ``search`` and the estimator's device path are
+    registered distribution to distribution on the pyramid, as the plain ``submit`` of such a localiser registers
+    (``submit_batch`` / ``relocalise`` / ``submit_from_device`` with ``d2d_pyramid=True``).  An online pyramid
+    with ``update_map`` / ``carve_map`` may then take hypotheses and search, as with ``coarse_to_fine``.  ``recover`` stays
+    refused as ever: a localiser with ``source="cells"`` has no ``global_grid``.
+
     A localiser with ``match_status``: a frame whose registration ends with status 0 or 1 but whose scan does
     not match the map at the registered pose (``match.lost``) is flagged as status 2 / 3 is: it keeps the guess, the map and
     the estimator stay untouched (the device gate, which is the status' verdict, already saw to that) and ``search`` frames
@@ -1747,7 +1852,8 @@ class LocalisationLoop:
 
     def __init__(self, filter, localiser, initial_pose, hypotheses=None, search=None, search_keep: int = 8,
                  update_map: bool = False, max_cell_points: int = 0, carve_map: bool = False, carve_options: dict = None,
-                 estimator=None, device_guess=None, coarse_to_fine: bool = False, recover: dict = None, d2d: bool = False):
+                 estimator=None, device_guess=None, coarse_to_fine: bool = False, recover: dict = None, d2d: bool = False,
+                 d2d_pyramid: bool = False):
         self.recover, self._flagged_run = None, 0
         if recover is not None:
             unknown = set(recover) - set(self._RECOVER_DEFAULTS)
@@ -1773,20 +1879,28 @@ class LocalisationLoop:
             raise ValueError("d2d=True needs an NDTLocaliser with source='cells'")
         if self.d2d and coarse_to_fine:
             raise ValueError("d2d=True and coarse_to_fine exclude each other: the pyramid registers points")
-        if cells and not self.d2d and (hypotheses is not None or search is not None):
+        self.d2d_pyramid = bool(d2d_pyramid)
+        if self.d2d_pyramid and (self.d2d or coarse_to_fine):
+            raise ValueError("d2d_pyramid=True excludes d2d and coarse_to_fine: it registers the scan's cells coarse to fine "
+                             "by itself")
+        if self.d2d_pyramid and (not cells or getattr(localiser, "source_resolutions", None) is None):
+            raise ValueError("d2d_pyramid=True needs an NDTLocaliser with source='cells' and source_resolutions")
+        if cells and not (self.d2d or self.d2d_pyramid) and (hypotheses is not None or search is not None):
             raise ValueError("hypotheses and search register points: they need an NDTLocaliser with source='points' "
                              "(or d2d=True, which registers the scan's cells)")
         self.coarse_to_fine = bool(coarse_to_fine)
         if self.coarse_to_fine and resolutions is None:
             raise ValueError("coarse_to_fine needs a localiser with a pyramid: NDTLocaliser(..., resolutions=...)")
         # what the batch, the search and the device path get on top of the keyword arguments below
-        self._c2f = dict(coarse_to_fine=True) if self.coarse_to_fine else dict(d2d=True) if self.d2d else {}
+        self._c2f = (dict(coarse_to_fine=True) if self.coarse_to_fine else dict(d2d=True) if self.d2d
+                     else dict(d2d_pyramid=True) if self.d2d_pyramid else {})
+        on_pyramid = self.coarse_to_fine or self.d2d_pyramid         # the batch, the search and the device path work there
         self.update_map, self.max_cell_points = bool(update_map), int(max_cell_points)
         online_pyramid = caps is not None
         if self.update_map and cell_capacity is None and not online_pyramid:
             raise ValueError("update_map needs a localiser with an online map: NDTLocaliser(..., cell_capacity=N)")
         if online_pyramid and (update_map or carve_map) and (hypotheses is not None or search is not None
-                                                             or self.recover is not None) and not self.coarse_to_fine:
+                                                             or self.recover is not None) and not on_pyramid:
             raise ValueError("an online pyramid is updated and carved by the plain registration only: no hypotheses, no search, "
                              "no recover (unless coarse_to_fine)")
         # the keyword arguments every registration of the loop gets: none unless the map is updated
@@ -1827,8 +1941,8 @@ class LocalisationLoop:
                 raise TypeError("recover needs an estimator with reset (PoseEstimator): a recovered pose re-initialises it")
             takes_none = (hasattr(filter, "add_pose") or type(filter).__name__ == "LTSFilter"
                           or getattr(filter, "takes_pose", True) is False)
-            possible = (takes_none and hasattr(localiser, "submit_from_device") and (resolutions is None or self.coarse_to_fine)
-                        and hypotheses is None and search is None and (not cells or self.d2d))
+            possible = (takes_none and hasattr(localiser, "submit_from_device") and (resolutions is None or on_pyramid)
+                        and hypotheses is None and search is None and (not cells or self.d2d or self.d2d_pyramid))
             if device_guess and not possible:
                 raise ValueError("device_guess=True needs a filter that takes no pose from the loop and an NDTLocaliser without "
                                  "a pyramid, hypotheses or search")

@@ -12,7 +12,7 @@ synthetic.build_map() map, max_distance 1 m, leaf 0.2 m):
     python tools/localiser_timing.py [--frames 200] [--warmup 20] [--cpu-frames 1] [--one-frame] [--cpu-only]
                                      [--localiser {icp,ndt}] [--hypotheses K] [--search P] [--update-map] [--carve]
                                      [--source {points,cells}] [--source-resolution R] [--source-min-points N] [--global]
-                                     [--d2d] [--source-resolutions S0,S1,...] [--start-behind M]
+                                     [--d2d] [--source-resolutions S0,S1,...] [--start-behind M] [--d2d-pyramid]
 
 ``--localiser ndt`` times sps_amd.localiser.NDTLocaliser (1 m cells, 7 neighbours) on the same frames and from the same
 start, prints the ICP's per-frame figures of the same session beside it and the build time of both maps; the
@@ -62,6 +62,13 @@ alternating frame by frame, hipEvents around each call: score_poses of P poses a
 from K start poses; and LocalisationLoop(SPSCVMFilter, ., ukf) per frame (host wall clock) on cells with ``d2d`` (device
 path), on cells without (the guess fetched) and on points (device path).  With --one-frame and --search: a warm-up and ONE
 score_poses on each path, the target of a kernel trace.
+
+``--localiser ndt --source cells --resolutions R0,R1,... --source-resolutions S0,S1,... --d2d-pyramid`` times the batched
+coarse-to-fine registration of the scan's cells, hipEvents around each call, the sides of one table alternating
+frame by frame with the order swapped every frame: submit_batch(d2d_pyramid=True) for K = 8 and 64 against K back-to-back
+submit calls on the same localiser and against the point pyramid's submit_batch(coarse_to_fine=True); with ``--search P``
+relocalise(d2d_pyramid=True) over P poses against the point pyramid's; then LocalisationLoop(SPSCVMFilter, ., ukf) per frame
+(host wall clock) with ``d2d_pyramid`` on the device path against the host path of the same localiser.
 
 ``--localiser ndt --resolutions R0,R1,... --coarse-to-fine`` times the batched coarse-to-fine registration,
 hipEvents around each call and the calls of one table alternating frame by frame: submit_from_device(coarse_to_fine=True)
@@ -238,6 +245,8 @@ def main():
                     "the usual start pose, along x")
     ap.add_argument("--d2d", action="store_true", help="with --source cells and any of --search, --hypotheses, --estimator: time "
                     "the d2d=True calls beside the point path's")
+    ap.add_argument("--d2d-pyramid", dest="d2d_pyramid", action="store_true", help="with --source cells --resolutions "
+                    "--source-resolutions: time the d2d_pyramid=True calls beside K submits and the point pyramid's batch")
     ap.add_argument("--match-status", dest="match_status", action="store_true", help="time submit without and with the "
                     "scan-matching status, alternating, and the status' two launches alone")
     ap.add_argument("--global", dest="global_search", action="store_true", help="with --localiser ndt: time global_search and "
@@ -257,13 +266,19 @@ def main():
             a.source_resolutions = tuple(float(v) for v in a.source_resolutions.split(","))
     except ValueError:
         ap.error("--source-min-points takes integers and --source-resolutions numbers, separated by commas")
+    if a.d2d_pyramid and (a.localiser != "ndt" or a.source != "cells" or not a.resolutions or a.source_resolutions is None
+                          or a.d2d or a.c2f or a.hypotheses or a.update_map or a.carve or a.estimator or a.one_frame
+                          or a.source_resolution is not None):
+        ap.error("--d2d-pyramid needs --localiser ndt --source cells --resolutions --source-resolutions and, of the other modes, "
+                 "at most --search")
     if a.source_resolutions is not None and (a.localiser != "ndt" or a.source != "cells" or not a.resolutions or a.d2d or a.c2f
-                                             or a.hypotheses or a.search or a.update_map or a.carve or a.estimator
-                                             or a.source_resolution is not None):
+                                             or a.hypotheses or (a.search and not a.d2d_pyramid) or a.update_map or a.carve
+                                             or a.estimator or a.source_resolution is not None):
         ap.error("--source-resolutions needs --localiser ndt --source cells --resolutions and none of the other modes")
     if isinstance(a.source_min_points, tuple) and a.source_resolutions is None:
         ap.error("a --source-min-points list needs --source-resolutions")
-    if a.source == "cells" and not a.d2d and (a.localiser != "ndt" or a.hypotheses or a.search or a.update_map or a.carve
+    if a.source == "cells" and not a.d2d and (a.localiser != "ndt" or a.hypotheses or (a.search and not a.d2d_pyramid)
+                                              or a.update_map or a.carve
                                               or (a.resolutions and a.source_resolutions is None) or a.estimator):
         ap.error("--source cells needs --localiser ndt and none of the other modes (--d2d: with --search, --hypotheses, --estimator)")
     if (a.source_resolution is not None or a.source_min_points is not None) and a.source != "cells":
@@ -272,7 +287,7 @@ def main():
         ap.error("--estimator needs --localiser ndt and none of the other modes")
     if a.c2f and (not a.resolutions or a.update_map or a.carve or a.estimator or a.one_frame):
         ap.error("--coarse-to-fine needs --resolutions and none of --update-map, --carve, --estimator, --one-frame")
-    if a.resolutions and (a.localiser != "ndt" or a.hypotheses or a.search):
+    if a.resolutions and (a.localiser != "ndt" or a.hypotheses or (a.search and not a.d2d_pyramid)):
         ap.error("--resolutions needs --localiser ndt and none of --hypotheses, --search")
     if a.carve and (a.localiser != "ndt" or a.hypotheses or a.search or (a.update_map and not a.resolutions)):
         ap.error("--carve needs --localiser ndt and none of --hypotheses, --search, --update-map (but with --resolutions)")
@@ -299,6 +314,8 @@ def main():
         return ndt_estimator_main(a, scans, dscans, mp, T_init)
     if a.c2f:
         return ndt_c2f_main(a, scans, dscans, mp, T_init)
+    if a.d2d_pyramid:
+        return ndt_d2d_pyramid_batch_main(a, scans, dscans, mp, T_init)
     if a.source_resolutions is not None:
         return ndt_d2d_pyramid_main(a, scans, dscans, mp, T_init)
     if a.localiser == "ndt" and a.resolutions and (a.update_map or a.carve):
@@ -695,6 +712,94 @@ def ndt_d2d_pyramid_main(a, scans, dscans, mp, T_init):
     out["source_build_ms"] = {name: round(float(np.median(v)), 4) for name, v in t.items()}
     print(f"source build: {L} levels in one call {out['source_build_ms']['one_call']:.4f} ms, {L} single builds "
           f"{out['source_build_ms']['single_builds']:.4f} ms", flush=True)
+    print(json.dumps(out))
+
+
+def ndt_d2d_pyramid_batch_main(a, scans, dscans, mp, T_init):
+    """--d2d-pyramid: see the module docstring.  The sensor stands still at I, so the estimator runs with zero velocity and a
+    0.1 s scan period, as in --estimator.  The windows include the host staging of the poses, as in ndt_search_main."""
+    from sps_amd.pose_estimator import PoseEstimator
+    map64 = mp[:, :3].astype(np.float64)
+    res, sres = tuple(float(v) for v in a.resolutions.split(",")), a.source_resolutions
+    caps = tuple(int(v) for v in a.level_iterations.split(",")) if a.level_iterations else None
+    pkw = dict(resolutions=res, iterations=a.iterations, level_iterations=caps)
+    cells = NDTLocaliser(map64, source="cells", source_resolutions=sres, source_min_points=a.source_min_points, **pkw)
+    points = NDTLocaliser(map64, **pkw)
+    st = torch.cuda.current_stream()
+    I4 = np.eye(4)
+    stats = lambda v: {"median": round(float(np.median(v)), 4), "min": round(min(v), 4), "max": round(max(v), 4)}
+    out = {"frames": a.frames, "warmup": a.warmup, "n_map": len(mp), "resolutions": res, "source_resolutions": sres,
+           "source_min_points": cells.source_level_min_points, "budget": a.iterations, "level_iterations": caps}
+
+    def alternate(calls):
+        """hipEvent time around every call of ``calls`` (name -> function of the frame's scan that returns the last pending
+        object it issued), the order swapped every frame -> name -> (ms per frame, the last result)"""
+        t, last = {n: [] for n in calls}, {}
+        for k in range(a.warmup + a.frames):
+            s = dscans[k % len(dscans)]
+            for n in (tuple(calls) if k % 2 == 0 else tuple(calls)[::-1]):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record(st)
+                pend = calls[n](s)
+                e1.record(st)
+                last[n] = pend.result()
+                e1.synchronize()
+                if k >= a.warmup:
+                    t[n].append(e0.elapsed_time(e1))
+        return t, last
+
+    for K in (8, 64):
+        starts = hypothesis_starts(T_init, K)
+
+        def sequential(s):
+            for T in starts:
+                pend = cells.submit(s, len(s), T)
+            return pend
+        t, last = alternate({"d2d_pyramid_batch": lambda s: cells.submit_batch(s, len(s), starts, d2d_pyramid=True),
+                             "sequential_submits": sequential,
+                             "point_pyramid_batch": lambda s: points.submit_batch(s, len(s), starts, coarse_to_fine=True)})
+        rows = {n: stats(v) for n, v in t.items()}
+        for n in ("d2d_pyramid_batch", "point_pyramid_batch"):
+            r = last[n]
+            rows[n].update(best=r.best, slots_max=max(p.iterations for p in r.results),
+                           error_m=round(LR.pose_difference(r.pose, I4)[0], 5))
+        rows["d2d_pyramid_batch"].update(score_level=last["d2d_pyramid_batch"].score_level,
+                                         n_sources=last["d2d_pyramid_batch"].n_sources)
+        out[f"k{K}"] = rows
+        print(f"K = {K}: submit_batch(d2d_pyramid) median {rows['d2d_pyramid_batch']['median']:.3f} ms (scores on level "
+              f"{rows['d2d_pyramid_batch']['score_level']}, {rows['d2d_pyramid_batch']['n_sources']} sources, error "
+              f"{rows['d2d_pyramid_batch']['error_m']:.4f} m); {K} submits median {rows['sequential_submits']['median']:.3f} ms; "
+              f"point pyramid's batch median {rows['point_pyramid_batch']['median']:.3f} ms (error "
+              f"{rows['point_pyramid_batch']['error_m']:.4f} m)", flush=True)
+    if a.search:
+        poses = search_poses(T_init, a.search)
+        t, last = alternate({"d2d_pyramid": lambda s: cells.relocalise(s, len(s), poses, keep=8, d2d_pyramid=True),
+                             "point_pyramid": lambda s: points.relocalise(s, len(s), poses, keep=8, coarse_to_fine=True)})
+        out[f"relocalise_P{a.search}_keep8"] = {n: dict(stats(v), index=last[n].index,
+                                                        error_m=round(LR.pose_difference(last[n].pose, I4)[0], 5))
+                                                for n, v in t.items()}
+        print(f"relocalise over {a.search} poses, keep 8: d2d_pyramid median {np.median(t['d2d_pyramid']):.3f} ms, point pyramid "
+              f"median {np.median(t['point_pyramid']):.3f} ms", flush=True)
+    net = net_from_params(O.random_params(seed=0)).cuda().eval().freeze()
+    mpt = torch.from_numpy(mp)
+
+    def make_loop(device_guess):
+        return LocalisationLoop(SPSCVMFilter(net, mpt, voxel_size=VS, epsilon=EPS), cells, I4, estimator=PoseEstimator(I4, "cuda"),
+                                device_guess=device_guess, d2d_pyramid=True)
+    loops = {"d2d_pyramid_device": make_loop(True), "d2d_pyramid_host": make_loop(False)}
+    t_loop, flagged = {m: [] for m in loops}, {m: 0 for m in loops}
+    for k in range(a.warmup + a.frames):
+        for m in (tuple(loops) if k % 2 == 0 else tuple(loops)[::-1]):
+            t0 = time.perf_counter()
+            step = loops[m].step(scans[k % len(scans)], dt=0.1)
+            if k >= a.warmup:
+                t_loop[m].append((time.perf_counter() - t0) * 1e3)
+                flagged[m] += step.flagged
+    for m in loops:
+        out[f"loop_{m}_ms"] = stats(t_loop[m])
+        out[f"loop_{m}_flagged"] = int(flagged[m])
+        print(f"LocalisationLoop(sps_cvm, cells pyramid, ukf, d2d_pyramid) {m:18s} median {out[f'loop_{m}_ms']['median']:.3f} ms "
+              f"per frame (min {min(t_loop[m]):.3f} max {max(t_loop[m]):.3f}; {flagged[m]} flagged)", flush=True)
     print(json.dumps(out))
 
 
