@@ -389,6 +389,22 @@ int sps_get_kernel_map(sps_ctx *ctx, int which, int source, int32_t *out_dev, in
  * [n_supertiles][3] on the host: what the pair-exact convolutions execute (one chunk = 16 pair slots).  chunks_host may be
  * NULL (only *n_supertiles is set). */
 int sps_get_rulebook_chunks(sps_ctx *ctx, int which, int32_t *chunks_host, int64_t *n_supertiles);
+/* What the last forward launched for the layer `conv_name` of the wiring table (a state_dict name without ".kernel":
+ * "conv0p1s1", "block3.0.conv1", "convtr6p4s2", ...): the record of the decisions taken at launch time, not a second
+ * evaluation of the geometry rule.  Host only, no synchronisation.
+ *   out[0] kernel family (SPS_LAUNCH_*; SPS_LAUNCH_NONE: the layer had no launch of its own -- a transposed convolution that
+ *          ran in the epilogue of the layer before it, or a forward that stopped earlier)
+ *   out[1] column tiles per wave (ntw)          out[2] splits of a tile's unit list (S)
+ *   out[3] 1 = the scalar-counter unit loop (U4) out[4] 1 = the next layer's transposed convolution ran in this launch
+ *   out[5] positions per tier of the balanced tile order (order_ways; 0 = tiles in row order)
+ *   out[6] arena capacity in rows the geometry was decided from
+ *   out[7] 1 = the context was marked pipelined (sps_ctx_set_pipelined) */
+#define SPS_LAUNCH_NONE 0
+#define SPS_LAUNCH_CONV 1    /* k_conv */
+#define SPS_LAUNCH_CONV_PX 2 /* k_conv_px */
+#define SPS_LAUNCH_UPCONV 3  /* k_upconv */
+#define SPS_LAUNCH_CONV0 4   /* k_conv0_fused / k_conv0_feat */
+int sps_get_conv_launch(sps_ctx *ctx, const char *conv_name, int32_t out[8]);
 /* Per-voxel logits of the last forward, float32 [V_0]. */
 int sps_get_logits(sps_ctx *ctx, float *logits_dev);
 /* Named intermediate feature maps: "out_p1","block1".."block8"; copies [V,C] row-major

@@ -110,6 +110,7 @@ def _load() -> C.CDLL:
         "sps_get_nbr": (i32, [vp, i32, vp]),
         "sps_get_kernel_map": (i32, [vp, i32, i32, vp, C.POINTER(i64)]),
         "sps_get_rulebook_chunks": (i32, [vp, i32, vp, C.POINTER(i64)]),
+        "sps_get_conv_launch": (i32, [vp, C.c_char_p, C.POINTER(i32)]),
         "sps_get_logits": (i32, [vp, vp]),
         "sps_get_feature": (i32, [vp, C.c_char_p, vp, C.POINTER(i64), C.POINTER(i64)]),
         "sps_lts_num_tensors": (i32, []),
@@ -217,7 +218,7 @@ EXPORTS = ["sps_last_error", "sps_version", "sps_ctx_create", "sps_ctx_destroy",
            "sps_submap_voxel", "sps_submap_voxel_ijk", "sps_transform_points", "sps_filter_prepare", "sps_forward_n",
            "sps_compact_stable", "sps_filter_finish", "sps_train_forward", "sps_train_backward", "sps_train_generation", "sps_train_wgrad_plan", "sps_train_backward_at", "sps_scan_mse", "sps_scan_mse_backward", "sps_radius_grid_upload", "sps_radius_count",
            "sps_radius_fill", "sps_radius_grid_attach", "sps_radius_item", "sps_forward_metrics_n", "sps_level_counts", "sps_get_voxels",
-           "sps_get_block_slots", "sps_get_inverse", "sps_get_parent", "sps_get_map_pairs", "sps_get_tile_masks", "sps_get_nbr", "sps_get_kernel_map", "sps_get_rulebook_chunks", "sps_get_logits", "sps_get_feature",
+           "sps_get_block_slots", "sps_get_inverse", "sps_get_parent", "sps_get_map_pairs", "sps_get_tile_masks", "sps_get_nbr", "sps_get_kernel_map", "sps_get_rulebook_chunks", "sps_get_conv_launch", "sps_get_logits", "sps_get_feature",
            "sps_lts_num_tensors", "sps_lts_tensor_info", "sps_lts_numel", "sps_lts_lidar_info", "sps_lts_create",
            "sps_lts_destroy", "sps_lts_project", "sps_lts_forward", "sps_lts_check", "sps_lts_tap",
            "sps_forward_head_n", "sps_transform_rows", "sps_transform_points_n", "sps_radius_crop", "sps_label_filter",
@@ -776,6 +777,15 @@ class Context:
         if n.value:
             check(lib.sps_get_rulebook_chunks(self.handle, which, out.ctypes.data, C.byref(n)))
         return out
+
+    LAUNCH_FAMILIES = ("none", "k_conv", "k_conv_px", "k_upconv", "conv0")
+
+    def conv_launch(self, conv_name: str) -> dict:
+        """What the last forward launched for a layer of the wiring table (include/sps_hip.h: sps_get_conv_launch)."""
+        out = (C.c_int32 * 8)()
+        check(lib.sps_get_conv_launch(self.handle, conv_name.encode(), out))
+        return {"family": self.LAUNCH_FAMILIES[out[0]], "ntw": out[1], "S": out[2], "U4": bool(out[3]), "fused_up": bool(out[4]),
+                "order_ways": out[5], "cap": out[6], "pipelined": bool(out[7])}
 
     def map_pairs(self, which: int):
         out = (C.c_int64 * 125)()

@@ -324,6 +324,9 @@ struct sps_ctx {
   std::vector<std::string> prof_names;
   std::vector<std::string> prof_kernels;  // kernel(s) the stage launched (sps_profile_kernel)
   const char *last_kernel = "";          // set next to every launch of forward_impl / run_conv
+  // what run_conv launched for every row of the wiring table in the last forward (sps_get_conv_launch); a row that was
+  // not launched (a transposed convolution that ran in its producer's epilogue) stays all zero
+  std::vector<std::array<int32_t, 8>> launches;
   size_t prof_n = 0;
   // variant-A radius grid (device copies owned by the ctx)
   RadiusGrid rg{};
@@ -692,9 +695,19 @@ void launch_px(dim3 grid, hipStream_t st, const ConvArgs &a) {
   hipLaunchKernelGGL((k_conv_px<NW, CIN, C8, DS, FIN, MINW, UP, HALF, DEPTH>), grid, dim3(NW * 64), 0, st, a);
 }
 
+// the template arguments of the k_conv instantiation a launch took (the record behind sps_get_conv_launch)
+struct KConvInst {
+  int ntw = 0, S = 0;
+  bool u4 = false;
+};
+
 // k_conv instantiation for a launch geometry (column tiles per wave x splits) -- shared by inference and training
-int launch_k_conv(const ConvArgs &a, Geometry g, bool ds, dim3 grid, hipStream_t st, unsigned lds_pad = 0) {
-  if (a.up_out) {  // fused transposed convolution: the three wide decoder-side producers (block4 / 5 / 6 .conv2)
+int launch_k_conv(const ConvArgs &a, Geometry g, bool ds, dim3 grid, hipStream_t st, unsigned lds_pad = 0, KConvInst *inst = nullptr) {
+  KConvInst none;
+  KConvInst &in = inst ? *inst : none;
+  // fused transposed convolution: instantiations exist for the three wide decoder-side producers (block4 / 5 / 6 .conv2);
+  // with the default SPS_FUSE_UP = 12 only block6.0.conv2 arrives here (convtr4p16s2 / convtr5p8s2 run as k_upconv)
+  if (a.up_out) {
     const int cgs = a.NT / g.ntw;                       // column groups of a tile, all in one workgroup
     const int unt = (a.up_cout + 15) / 16;
     if (!(g.ntw == 2 && g.S == 4 && ds)) return fail(SPS_ERR_INVALID, "fused transposed convolution: geometry ntw = %d, S = %d", g.ntw, g.S);
@@ -706,10 +719,12 @@ int launch_k_conv(const ConvArgs &a, Geometry g, bool ds, dim3 grid, hipStream_t
       hipLaunchKernelGGL((k_conv<2, SPS_G2, 4, true, false, 4, 2, 4, true>), grid, dim3(512), lds_pad, st, a);
     else
       return fail(SPS_ERR_INVALID, "fused transposed convolution: no instantiation for %d column groups, %d output tiles", cgs, unt);
+    in = {2, 4, true};
     return SPS_OK;
   }
 #define SPS_LAUNCH(NTW_, G_, W_, S_)                                                              \
   do {                                                                                            \
+    in = {NTW_, S_, false};                                                                       \
     if (ds)                                                                                       \
       hipLaunchKernelGGL((k_conv<NTW_, G_, W_, true, false, S_>), grid, dim3(S_ == 8 ? 512 : 256), lds_pad, st, a);     \
     else                                                                                          \
@@ -718,6 +733,7 @@ int launch_k_conv(const ConvArgs &a, Geometry g, bool ds, dim3 grid, hipStream_t
   // C_in a multiple of 16 (the wide layers of the coarse levels, four splits): the scalar-counter unit loop
 #define SPS_LAUNCH_U4(NTW_, G_, W_)                                                                               \
   do {                                                                                                            \
+    in = {NTW_, 4, true};                                                                                         \
     if (ds)                                                                                                       \
       hipLaunchKernelGGL((k_conv<NTW_, G_, W_, true, false, 4, 1, 0, true>), grid, dim3(256), lds_pad, st, a);    \
     else                                                                                                          \
@@ -885,7 +901,7 @@ int launch_conv_px(sps_ctx *c, const ConvSpec &cs, ConvArgs &a, int level_out, b
 }
 
 // k_conv over a gather map (3x3x3x3 tables, `down` tables): the inference launch with its fused epilogues
-int launch_conv_rows(sps_ctx *c, const ConvSpec &cs, const ConvArgs &a, Geometry g, int level_out, bool fin, hipStream_t st) {
+int launch_conv_rows(sps_ctx *c, const ConvSpec &cs, const ConvArgs &a, Geometry g, int level_out, bool fin, hipStream_t st, KConvInst *inst) {
   const bool ds = cs.ds_cin > 0;
   const int cgs = a.NT / g.ntw;  // column groups of a tile
   int64_t gx = row_grid(c->cap, level_out);
@@ -902,10 +918,11 @@ int launch_conv_rows(sps_ctx *c, const ConvSpec &cs, const ConvArgs &a, Geometry
   c->last_kernel = cs.K == 81 ? (level_out >= 2 ? "k_conv<3x3x3x3, levels 2-4>" : "k_conv<3x3x3x3, levels 0-1>") : "k_conv<2x2x2x1 stride 2>";
   if (fin) {
     hipLaunchKernelGGL((k_conv<1, SPS_G1DS, SPS_W1, true, true, 1>), grid, dim3(256), 0, st, a);
+    if (inst) *inst = {1, 1, false};
     return SPS_OK;
   }
   const unsigned lds_pad = (level_out >= 2 && cs.K == 81) ? (unsigned)dg.lds_pad : 0u;
-  return launch_k_conv(a, g, ds, grid, st, lds_pad);
+  return launch_k_conv(a, g, ds, grid, st, lds_pad, inst);
 }
 
 // One layer of the inference forward: row `r` of the wiring table, with `final` fused into its epilogue (fin) and / or the
@@ -967,15 +984,36 @@ int run_conv(sps_ctx *c, const LayerRow &r, bool fin, const LayerRow *up, hipStr
   }
   const char *trace_layer = conv_diag().trace_layer;  // diagnostic builds (-DSPS_WAVE_TRACE) only
   a.trace_on = trace_layer && std::strcmp(trace_layer, cs.name.c_str()) == 0;
-  if (r.kind == T_CONV0) return launch_conv0(c, cs, a, st);
+  // the record sps_get_conv_launch reads: written where each decision is taken, [0] last (0 = the launch failed)
+  std::array<int32_t, 8> none{};
+  const size_t row = (size_t)(&r - s.layers.data());
+  std::array<int32_t, 8> &rec = row < c->launches.size() ? c->launches[row] : none;
+  rec = {0, 0, 0, 0, up ? 1 : 0, 0, (int32_t)c->cap, c->pipelined ? 1 : 0};
+  if (r.kind == T_CONV0) {
+    const int rc = launch_conv0(c, cs, a, st);
+    if (rc == SPS_OK) rec[0] = SPS_LAUNCH_CONV0;
+    return rc;
+  }
   if (r.kind == T_UP) {  // k_upconv walks the rows of the coarse level and scatters into this one
     conv_rows(a, c, lo + 1);
     a.out_rows = (int)c->capl[lo];
     c->last_kernel = "k_upconv";
-    return launch_upconv(a, c->cap, lo + 1, st);
+    const int rc = launch_upconv(a, c->cap, lo + 1, st);
+    if (rc == SPS_OK) rec[0] = SPS_LAUNCH_UPCONV;
+    return rc;
   }
-  if (runs_pair_exact(c, cs, lo, fin)) return launch_conv_px(c, cs, a, lo, fin, up_name, st);
-  return launch_conv_rows(c, cs, a, g, lo, fin, st);
+  if (runs_pair_exact(c, cs, lo, fin)) {
+    const int rc = launch_conv_px(c, cs, a, lo, fin, up_name, st);
+    if (rc == SPS_OK) rec[0] = SPS_LAUNCH_CONV_PX, rec[1] = a.NT, rec[2] = 1;
+    return rc;
+  }
+  KConvInst inst;
+  const int rc = launch_conv_rows(c, cs, a, g, lo, fin, st, &inst);
+  if (rc == SPS_OK) {
+    rec[0] = SPS_LAUNCH_CONV, rec[1] = inst.ntw, rec[2] = inst.S, rec[3] = inst.u4 ? 1 : 0;
+    rec[5] = a.tile_order ? a.order_ways : 0;
+  }
+  return rc;
 }
 
 // Host-side permutation of one kernel [K][cin][cout] into the unit-major MFMA B-fragment order
@@ -1483,6 +1521,7 @@ static int forward_impl(sps_ctx *c, const float *coords, int64_t ld, int64_t n, 
   // ---- network (minkunet.py:161-219)
   c->cur_vfeat = fo.feats ? c->vfeat : nullptr;
   const NetSpec &s = *c->net;
+  c->launches.assign(s.layers.size(), {});
   for (size_t i = 0; i < s.layers.size() && !skip_convs; ++i) {
     const LayerRow &r = s.layers[i];
     if (skip_class) {
@@ -2205,6 +2244,17 @@ int sps_get_kernel_map(sps_ctx *c, int which, int source, int32_t *out_dev, int6
                      c->counts + level, tm, out_dev);
   HIP_TRY(hipDeviceSynchronize());
   return SPS_OK;
+}
+
+int sps_get_conv_launch(sps_ctx *c, const char *conv_name, int32_t out[8]) {
+  if (!c || !conv_name || !out) return fail(SPS_ERR_INVALID, "null argument");
+  if (!c->net || c->launches.size() != c->net->layers.size()) return fail(SPS_ERR_INVALID, "no forward has run on this context");
+  for (size_t i = 0; i < c->net->layers.size(); ++i) {
+    if (c->net->convs[c->net->layers[i].conv].name != conv_name) continue;
+    for (int j = 0; j < 8; ++j) out[j] = c->launches[i][j];
+    return SPS_OK;
+  }
+  return fail(SPS_ERR_INVALID, "no layer of the wiring table is called '%s'", conv_name);
 }
 
 int sps_get_logits(sps_ctx *c, float *logits_dev) {

@@ -28,9 +28,13 @@ def net(params):
     return net_from_params(params).cuda().eval().freeze()
 
 
-def ctx():
+def ctx(c=None):
+    """The context the forwards of the current stream run on; `c`: a context of the caller's own (a fresh one on a stream
+    of its own, which must be the current stream) -- it is handed back after that has been checked."""
     from sps_amd.models.models import get_context
-    return get_context(0)
+    cur = get_context(0)
+    assert c is None or c is cur, "the context belongs to another stream than the current one"
+    return cur
 
 
 def run(net, batch_np):
@@ -47,17 +51,18 @@ def get_voxels_of(c, level, count):
     return out.cpu().numpy()
 
 
-def get_voxels(level, count):
-    return get_voxels_of(ctx(), level, count)
+def get_voxels(level, count, c=None):
+    return get_voxels_of(ctx(c), level, count)
 
 
-def get_feature(name):
+def get_feature(name, c=None):
     import ctypes as C
     from sps_amd import _native
-    r, c = C.c_int64(), C.c_int64()
-    _native.check(_native.lib.sps_get_feature(ctx().handle, name.encode(), None, C.byref(r), C.byref(c)))
-    out = torch.empty((r.value, c.value), dtype=torch.float32, device="cuda")
-    _native.check(_native.lib.sps_get_feature(ctx().handle, name.encode(), out.data_ptr(), C.byref(r), C.byref(c)))
+    h = ctx(c).handle
+    r, k = C.c_int64(), C.c_int64()
+    _native.check(_native.lib.sps_get_feature(h, name.encode(), None, C.byref(r), C.byref(k)))
+    out = torch.empty((r.value, k.value), dtype=torch.float32, device="cuda")
+    _native.check(_native.lib.sps_get_feature(h, name.encode(), out.data_ptr(), C.byref(r), C.byref(k)))
     return out.cpu().numpy()
 
 
@@ -96,11 +101,11 @@ def assert_same_pairs(got, want, perm_out, perm_in, what):
     np.testing.assert_array_equal(mapped, want[:, perm_out], err_msg=what)
 
 
-def check_kernel_maps(cm, perm, counts):
+def check_kernel_maps(cm, perm, counts, c=None):
     """Row a10 as pair SETS: the 3x3x3x3 map of every level from the neighbour table AND (levels that run pair-exact) decoded
     from the rulebook the convolutions read, the 5x5x5x1 map, and the four stride-2 maps (= the transposed convolutions' maps
     with in / out swapped) against cm.k3 / k5 / kdown of the oracle."""
-    c = ctx()
+    c = ctx(c)
     n_pairs = 0
     for l in range(5):
         want = oracle_table(cm.k3(1 << l), counts[l])
@@ -118,38 +123,43 @@ def check_kernel_maps(cm, perm, counts):
     return n_pairs
 
 
-def check_full(net, params, batch, tol=2e-4, both_classes=False):
+# level of the rows of every tap of sps_get_feature
+TAP_LEVEL = {"out_p1": 0, "block1": 1, "block2": 2, "block3": 3, "block4": 4, "block5": 3, "block6": 2, "block7": 1, "block8": 0}
+
+
+def check_full(net, params, batch, tol=2e-4, both_classes=False, c=None, oracle=None):
+    """`c`: the context of the current stream, where it is not the default one; `oracle`: (ref, info) of
+    O.sps_forward(params, batch[:, :5], VS, keep=True), where the caller shares it among several runs."""
+    c = ctx(c)
     dev, scores = run(net, batch)
-    ref, info = O.sps_forward(params, batch[:, :5], VS, keep=True)
-    counts = ctx().level_counts()
+    ref, info = oracle if oracle is not None else O.sps_forward(params, batch[:, :5], VS, keep=True)
+    counts = c.level_counts()
     cm = info["cm"]
     # --- integer structure: exact (as sets; rows matched by coordinate)
     perm = []
     for l in range(5):
         ts = 1 << l
         assert counts[l] == len(cm.coords[ts]), f"level {l}"
-        perm.append(match_rows(get_voxels(l, counts[l]), cm.coords[ts]))
+        perm.append(match_rows(get_voxels_of(c, l, counts[l]), cm.coords[ts]))
     from sps_amd import _native
     inv = torch.empty(len(batch), dtype=torch.int64, device="cuda")
-    _native.check(_native.lib.sps_get_inverse(ctx().handle, inv.data_ptr()))
+    _native.check(_native.lib.sps_get_inverse(c.handle, inv.data_ptr()))
     np.testing.assert_array_equal(perm[0][inv.cpu().numpy()], info["inverse"])
     for l in range(4):
         par = torch.empty(counts[l], dtype=torch.int32, device="cuda")
-        _native.check(_native.lib.sps_get_parent(ctx().handle, l, par.data_ptr()))
+        _native.check(_native.lib.sps_get_parent(c.handle, l, par.data_ptr()))
         np.testing.assert_array_equal(perm[l + 1][par.cpu().numpy()], cm.parent[1 << l][perm[l]])
     for l in range(5):
         want = [len(i) for i, _ in cm.k3(1 << l)]
-        assert ctx().map_pairs(l) == want, f"3^4 map level {l}"
-    assert ctx().map_pairs(5) == [len(i) for i, _ in cm.k5()]
-    check_kernel_maps(cm, perm, counts)                           # ... and as pair sets, offset by offset
+        assert c.map_pairs(l) == want, f"3^4 map level {l}"
+    assert c.map_pairs(5) == [len(i) for i, _ in cm.k5()]
+    check_kernel_maps(cm, perm, counts, c)                        # ... and as pair sets, offset by offset
     # --- features
-    tap_level = {"out_p1": 0, "block1": 1, "block2": 2, "block3": 3, "block4": 4, "block5": 3, "block6": 2,
-                 "block7": 1, "block8": 0}
     for name, want in info["inter"].items():
-        got = get_feature(name)
-        np.testing.assert_allclose(got, want[perm[tap_level[name]]], rtol=tol, atol=tol, err_msg=name)
+        got = get_feature(name, c)
+        np.testing.assert_allclose(got, want[perm[TAP_LEVEL[name]]], rtol=tol, atol=tol, err_msg=name)
     logits = torch.empty(counts[0], dtype=torch.float32, device="cuda")
-    _native.check(_native.lib.sps_get_logits(ctx().handle, logits.data_ptr()))
+    _native.check(_native.lib.sps_get_logits(c.handle, logits.data_ptr()))
     np.testing.assert_allclose(logits.cpu().numpy(), info["logits"][perm[0]], rtol=0, atol=1e-3)
     s = scores.cpu().numpy()
     np.testing.assert_allclose(s, ref, rtol=0, atol=1e-4)
@@ -170,16 +180,32 @@ def test_small_scene_full_parity(net, params):
 def test_launch_geometry_hint_does_not_change_a_bit(net, params):
     """sps_ctx_set_pipelined: one column tile per wave at the coarse levels (a context whose forwards run one after another,
     the default) or two (several contexts in flight: ScanEngine) -- the per-element summation order is the same, so scores
-    and every tapped feature map are bit-identical; the engine's pipelines agree with a direct call for the same reason."""
+    and every tapped feature map are bit-identical; the engine's pipelines agree with a direct call for the same reason.
+    The hint only matters while the arena is small (conv_geometry), and the default context's arena has grown to whatever the
+    tests before this one needed: a fresh context, reserved to 8 192 rows, and sps_get_conv_launch to see that the two modes
+    really launched different kernels."""
+    from sps_amd.models import models as M
     batch = synthetic.make_scene(scan_seed=3, n_azimuth=500)["batch"]        # LiDAR-like: levels 3 and 4 hold few tiles
-    out = {}
-    try:
-        for mode in (False, True):
-            ctx().set_pipelined(mode)
-            _, scores = run(net, batch)
-            out[mode] = (scores.clone(), {n: get_feature(n) for n in ("block3", "block4", "block5", "block8")})
-    finally:
-        ctx().set_pipelined(False)
+    wide = [f"block{b}.0.conv{i}" for b in (3, 4, 5) for i in (1, 2)]
+    out, ntw = {}, {}
+    st = torch.cuda.Stream()
+    with torch.cuda.stream(st):
+        c = M.get_context(0, st.cuda_stream)
+        try:
+            c.reserve(8192)
+            for mode in (False, True):
+                ctx(c).set_pipelined(mode)
+                _, scores = run(net, batch)
+                ntw[mode] = {n: c.conv_launch(n) for n in wide}
+                out[mode] = (scores.clone(), {n: get_feature(n, c) for n in ("block3", "block4", "block5", "block8")})
+        finally:
+            torch.cuda.synchronize()
+            M._CONTEXTS.pop((0, st.cuda_stream), None)
+            c.close()
+    for n in wide:
+        a, b = ntw[False][n], ntw[True][n]
+        assert a["family"] == b["family"] == "k_conv" and (a["ntw"], b["ntw"]) == (1, 2), (n, a, b)
+        assert a["order_ways"] == b["order_ways"] // 2 and a["cap"] == b["cap"] and (a["pipelined"], b["pipelined"]) == (False, True)
     assert torch.equal(out[False][0], out[True][0])
     for n, f in out[False][1].items():
         np.testing.assert_array_equal(f, out[True][1][n], err_msg=n)
